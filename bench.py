@@ -105,6 +105,44 @@ def residual_probe(sol, host_A, L_dev, nprobe=2, seed=5):
     return worst
 
 
+DUMP_SAMPLES = 2 * 1024 * 1024   # values + positions, 8 bytes each: 32 MB in all
+
+
+def dump_outputs(sol, step_out, out_dir, seed=2024):
+    """writes what the last timed factor() handed back -- the factored matrices, in the solver's
+    data layout -- to out_dir as factor_data.npy (values, in the data's own precision) and
+    factor_data_index.npy (their positions in the flat output of the step: matrix q of a batch
+    starts at q * dataSize(), float64).  Every entry when they fit in DUMP_SAMPLES, else a fixed
+    seeded sample; the strictly-upper entries of diagonal blocks are stored but unspecified
+    (lowerMask) and are left out."""
+    mats = list(step_out) if isinstance(step_out, (list, tuple)) else [step_out]
+    size = sol.dataSize()
+    total = size * len(mats)
+    if total <= DUMP_SAMPLES:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(seed).choice(total, DUMP_SAMPLES, replace=False))
+    # drop the unspecified entries: offsets past a diagonal block's start, inside it, above its diagonal
+    sk = sol.skel()
+    width = np.diff(sk["lumpStart"]).astype(np.int64)
+    d0 = sk["chainData"][sk["chainColPtr"][:-1]].astype(np.int64)
+    order = np.argsort(d0)
+    d0, width = d0[order], width[order]
+    local = idx % size
+    k = np.maximum(np.searchsorted(d0, local, side="right") - 1, 0)
+    off = local - d0[k]
+    inside = (off >= 0) & (off < width[k] * width[k])
+    w = np.maximum(width[k], 1)
+    idx = idx[~(inside & (off % w > off // w))]
+    vals = []
+    for q, m in enumerate(mats):
+        sel = idx[(idx >= q * size) & (idx < (q + 1) * size)] - q * size
+        vals.append(m.reshape(-1)[torch.from_numpy(sel).to(m.device)].cpu().numpy())
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "factor_data.npy"), np.concatenate(vals))
+    np.save(os.path.join(out_dir, "factor_data_index.npy"), idx.astype(np.float64))
+
+
 class Runner:
     """this rank's share of a workload: solver, pristine matrices in HBM, timed factor steps"""
 
@@ -141,26 +179,45 @@ class Runner:
         """W untimed + K timed factor() calls, barrier + synchronize on both sides, max over ranks"""
         dist, device = (self.ctx["dist"] if sync_ranks else None), self.ctx["device"]
         n_buf = steps + warmup
+        # one pristine copy per step while they fit in half the free device memory; beyond that a
+        # pool of copies is refilled from the pristine matrices whenever it is used up, and the
+        # refill (synchronised on both sides) is left out of the timed steps
+        per_buf = sum(a.numel() * a.element_size() for a in (self.A_devs if self.batched else self.A_devs[:1]))
+        pool = max(1, min(n_buf, int(0.5 * torch.cuda.mem_get_info(device)[0] // max(1, per_buf))))
         if self.batched:
-            bufs = [[a.clone() for a in self.A_devs] for _ in range(n_buf)]
+            bufs = [[a.clone() for a in self.A_devs] for _ in range(pool)]
         else:
-            bufs = [self.A_devs[0].clone() for _ in range(n_buf)]
+            bufs = [self.A_devs[0].clone() for _ in range(pool)]
+        paused = [0.0]
+
+        def buf(s):
+            if s and s % pool == 0:
+                torch.cuda.synchronize(device)
+                tp = time.perf_counter()
+                for b in bufs:
+                    for dst, src in zip(b if self.batched else [b], self.A_devs):
+                        dst.copy_(src)
+                torch.cuda.synchronize(device)
+                paused[0] += time.perf_counter() - tp
+            return bufs[s % pool]
+
         torch.cuda.synchronize(device)
         for i in range(warmup):
-            self.sol.factor(bufs[i])
+            self.sol.factor(buf(i))
         torch.cuda.synchronize(device)
         if dist:
             dist.barrier()
         torch.cuda.synchronize(device)
+        paused[0] = 0.0
         t0 = time.perf_counter()
         for i in range(steps):
-            self.sol.factor(bufs[warmup + i])
+            self.sol.factor(buf(warmup + i))
         torch.cuda.synchronize(device)
-        own = time.perf_counter() - t0   # this rank's K steps, before it waits for the others
+        own = time.perf_counter() - t0 - paused[0]   # this rank's K steps, before it waits for the others
         if dist:
             dist.barrier()
         torch.cuda.synchronize(device)
-        elapsed = time.perf_counter() - t0
+        elapsed = time.perf_counter() - t0 - paused[0]
         rank_ms = None
         if dist:
             tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -180,7 +237,8 @@ class Runner:
                     "serialize_s_rank0": round(rows[0][1], 4),
                     "broadcast_s_max": round(max(r[2] for r in rows), 4),
                     "rebuild_s_max": round(max(r[3] for r in rows), 4)}
-        self.last = bufs[-1][0] if self.batched else bufs[-1]
+        self.last_step = bufs[(n_buf - 1) % pool]   # what the last timed factor() handed back
+        self.last = self.last_step[0] if self.batched else self.last_step
         if sync_ranks:   # every rank took part: the whole batch, or one matrix per rank
             n_mat = self.total_batch if self.batched else self.ctx["world"]
         else:            # this rank alone
@@ -269,12 +327,13 @@ def _cpu_baseline_once(sol, host, flops):
                 pinned = "one socket, %d cores, one hardware thread each" % want
     except OSError:
         pinned = None
-    _, blas_desc = cref.blas_lib(want)
+    blas, blas_desc = cref.blas_lib(want)
     cap = want
     for tok in blas_desc.split():
         if tok.startswith("MAX_THREADS="):
             cap = int(tok.split("=")[1])
-    used = min(want, cap)
+    # (orc_blas_init never grows the BLAS's pool beyond the size it started with)
+    used = min(want, cap, blas.orc_blas_threads() or want)
     skh = cref.SkelHandle(sol.skel())
     ranges = sol.sparseEliminationRanges()
     times, elims = [], []
@@ -776,8 +835,13 @@ def main():
     ap.add_argument("--suite-iters", type=int, default=5,
                     help="instances per family of --suite ref (the reference's numIterations: 5)")
     ap.add_argument("--suite-out", default=None, help="write the suite's JSON document here too")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/*.npy "
+                         "(rank 0's matrices; a fixed sample of at most 32 MB: see dump_outputs)")
     ap.add_argument("--cpu-baseline-child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.cpu_baseline_child:
         return cpu_baseline_child(args)
@@ -824,6 +888,8 @@ def main():
     main_run = Runner(ctx, workload, total_batch, batched, args.bal_file)
     res = main_run.run(args.steps, args.warmup)
     sol = main_run.sol
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sol, main_run.last_step, args.dump_outputs)
 
     metric = {"bal871": "factor_gflops_fp64_bal871_schur"}.get(workload, "factor_gflops_fp64_" + workload)
     if batched:
@@ -895,7 +961,7 @@ def main():
         # the headline workload's device buffers go first, and torch's cached blocks with them: a
         # batch carved out of the cached 1.1 GB blocks ran 20 % slower than one in fresh allocations
         # (tools/exp_order.py)
-        main_run.A_devs = main_run.last = None
+        main_run.A_devs = main_run.last = main_run.last_step = None
         import gc
         gc.collect()
         torch.cuda.empty_cache()

@@ -30,6 +30,7 @@ typedef void (*dgemm_t)(const char*, const char*, const int*, const int*, const 
                         const double*, double*, const int*);
 typedef void (*setthreads_t)(int);
 typedef char* (*getconfig_t)(void);
+typedef int (*getthreads_t)(void);
 
 static dpotrf_t p_dpotrf;
 static dtrsm_t p_dtrsm;
@@ -37,6 +38,7 @@ static dsyrk_t p_dsyrk;
 static dgemm_t p_dgemm;
 static setthreads_t p_setthreads;
 static char g_blas_desc[512] = "unloaded";
+static int g_threads = 0;
 
 static void* sym2(void* h, const char* a, const char* b) {
   void* p = dlsym(h, a);
@@ -60,13 +62,22 @@ int orc_blas_init(const char* path, int num_threads) {
     snprintf(g_blas_desc, sizeof g_blas_desc, "BLAS symbols missing in %s", path);
     return 2;
   }
+  /* OpenBLAS 0.3.28 segfaults when openblas_set_num_threads grows its pool beyond the size it
+     started with (the CPUs it may run on, or OPENBLAS_NUM_THREADS / OMP_NUM_THREADS): never more */
+  getthreads_t getthreads =
+      (getthreads_t)sym2(h, "scipy_openblas_get_num_threads", "openblas_get_num_threads");
+  if (getthreads && num_threads > getthreads()) num_threads = getthreads();
   if (p_setthreads && num_threads > 0) p_setthreads(num_threads);
   if (num_threads > 0) omp_set_num_threads(num_threads);
+  g_threads = num_threads > 0 ? num_threads : 0;
   snprintf(g_blas_desc, sizeof g_blas_desc, "%s", cfg ? cfg() : path);
   return 0;
 }
 
 const char* orc_blas_desc(void) { return g_blas_desc; }
+
+/* BLAS / OpenMP team size set by orc_blas_init (0: left to the libraries) */
+int orc_blas_threads(void) { return g_threads; }
 
 static void bl_potrf(int64_t n, double* A) {
   int N = (int)n, info = 0;
