@@ -471,6 +471,41 @@ class Solver:
         _check(getattr(self._lib, "bsp_pseudo_factor_from_" + _suffix(data))(
             self._h, ctypes.c_void_p(_ptr_of(data)), ctypes.c_int64(span_index)))
 
+    def selectedInverse(self, data):
+        """extension: selected inversion, in place.  `data` holds a complete factor() of this
+        solver; it is overwritten by Z = A^-1 on the block pattern of L, in the factor's layout
+        (diagonal blocks full and symmetric, off-diagonal blocks in their stored orientation: the
+        accessors read Z as they read L).  bsp_selected_inverse_f64 / _f32"""
+        self._check_data(data)
+        _check(getattr(self._lib, "bsp_selected_inverse_" + _suffix(data))(
+            self._h, ctypes.c_void_p(_ptr_of(data))))
+
+    def marginals(self, data, params):
+        """diagonal covariance blocks of the given user-order parameters, read from the output of
+        selectedInverse(data): a device tensor [k, n, n] when every parameter has size n, else a
+        list of [n_i, n_i] tensors"""
+        params = [int(p) for p in params]
+        num = self.numSpans()
+        for p in params:
+            if p < 0 or p >= num:
+                raise IndexError("marginals: parameter %d out of range [0, %d)" % (p, num))
+        self._check_data(data)
+        import torch
+        ss = self.skel()["spanStart"]
+        p2s = self.paramToSpan()
+        sizes = [int(ss[p2s[p] + 1] - ss[p2s[p]]) for p in params]
+        offs = [self.diagBlockOffset(p) for p in params]
+        if len(params) == 0:
+            return torch.empty((0, 0, 0), dtype=data.dtype, device=data.device)
+        if len(set(sizes)) == 1:
+            n = sizes[0]
+            base = torch.tensor([o for o, _ in offs], dtype=torch.int64)
+            stride = torch.tensor([st for _, st in offs], dtype=torch.int64)
+            r = torch.arange(n, dtype=torch.int64)
+            idx = base[:, None, None] + r[None, :, None] * stride[:, None, None] + r[None, None, :]
+            return data[idx.to(data.device)]
+        return [data.as_strided((n, n), (st, 1), o).clone() for n, (o, st) in zip(sizes, offs)]
+
     # ---- measurement --------------------------------------------------------------------
     def factorFlops(self):
         return float(self._lib.bsp_factor_flops(self._h))

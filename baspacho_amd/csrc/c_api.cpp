@@ -415,6 +415,16 @@ int bsp_add_mv_from_f32(bsp_solver* s, const float* m, int64_t span, const float
   s->solver->addMvFrom(m, span, in, in_stride, out, out_stride, nrhs, alpha);
   BSP_CATCH
 }
+int bsp_selected_inverse_f64(bsp_solver* s, double* d) {
+  BSP_TRY
+  s->solver->selectedInverse(d);
+  BSP_CATCH
+}
+int bsp_selected_inverse_f32(bsp_solver* s, float* d) {
+  BSP_TRY
+  s->solver->selectedInverse(d);
+  BSP_CATCH
+}
 int bsp_pseudo_factor_from_f64(bsp_solver* s, double* d, int64_t span) {
   BSP_TRY
   s->solver->pseudoFactorFrom(d, span);

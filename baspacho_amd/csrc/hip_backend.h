@@ -91,6 +91,11 @@ int hipBackendReadSweepTrace(SymbolicCtx& sym, long long* out, int maxBlocks);
 // panel, trsm tasks, update tiles, lookahead tiles, rows below summed over the panels}
 std::vector<int64_t> hipBackendPlanLevels(SymbolicCtx& sym, int64_t startLump, int64_t upToLump);
 
+// Selected inversion: `data` holds a complete factor of this context's skeleton; Z = A^-1 on the
+// pattern of L overwrites it (hip_selinv_kernels.h), on the execution stream
+template <typename T>
+void hipBackendSelectedInverse(SymbolicCtx& sym, T* data);
+
 HipPlanStats hipBackendPlanStats(SymbolicCtx& sym, int64_t startLump, int64_t upToLump);
 
 }  // namespace BaSpaCho

@@ -19,6 +19,7 @@
 #include "hip_solve_wide.h"
 #include "hip_sweep_mfma.h"
 #include "hip_tail_kernel.h"
+#include "hip_selinv_kernels.h"
 #include "mat_ops.h"
 
 namespace BaSpaCho {
@@ -455,6 +456,28 @@ struct FlagOff {
   FlagOff& operator=(const FlagOff&) = delete;
 };
 
+// selected-inversion plan (hip_plan.h, SelInvPlanHost) on the device, with its scratch
+struct SelInvDev {
+  SelInvPlanHost host;
+  DevBuf smalls, nodes, tiles, zTasks, rowChain, rowLocal, pairOff, pairStr;
+  DevBuf linv, dd, U, P, Wp;  // scratch, sized for fp64 (fp32 uses the first half)
+  void upload() {
+    smalls.upload(host.smalls);
+    nodes.upload(host.nodes);
+    tiles.upload(host.tiles);
+    zTasks.upload(host.zTasks);
+    rowChain.upload(host.rowChain);
+    rowLocal.upload(host.rowLocal);
+    pairOff.upload(host.pairOff);
+    pairStr.upload(host.pairStr);
+    linv.resize(std::max<int64_t>(host.linvElems, 1) * sizeof(double));
+    dd.resize(std::max<int64_t>(host.linvElems, 1) * sizeof(double));
+    U.resize(std::max<int64_t>(host.uElems, 1) * sizeof(double));
+    P.resize(std::max<int64_t>(host.pElems, 1) * sizeof(double));
+    Wp.resize(std::max<int64_t>(host.wElems, 1) * sizeof(double));
+  }
+};
+
 struct HipSymbolicCtx : SymbolicCtx {
   // `o`: the caller's switches with the environment already applied (backend_options.h)
   HipSymbolicCtx(const CoalescedBlockMatrixSkel& skel_, const vector<int64_t>& permutation_,
@@ -522,6 +545,7 @@ struct HipSymbolicCtx : SymbolicCtx {
   // current; events and plans likewise)
   void releaseDeviceState() {
     plans.clear();
+    selinv.reset();
     for (hipEvent_t e : events) (void)hipEventDestroy(e);
     events.clear();
     nextEvent = 0;
@@ -660,6 +684,50 @@ struct HipSymbolicCtx : SymbolicCtx {
     e->lumpsBegin = lumpsBegin;
     e->lumpsEnd = lumpsEnd;
     return SymElimCtxPtr(e);
+  }
+
+  // Selected inversion of a complete factor, in place (hip_selinv_kernels.h).  The plan is built and
+  // uploaded on the first call; every launch goes to the execution stream, in level order, with no
+  // host synchronisation.
+  template <typename T>
+  void selectedInverse(T* data) {
+    checkDevice();
+    if (!selinv) {
+      std::unique_ptr<SelInvDev> p(new SelInvDev);
+      p->host = buildSelInvPlan(skel);
+      p->upload();
+      selinv = std::move(p);
+    }
+    const SelInvDev& d = *selinv;
+    const hipk::SkelDev sk = skelDev();
+    T* linv = reinterpret_cast<T*>(d.linv.ptr);
+    T* dd = reinterpret_cast<T*>(d.dd.ptr);
+    T* U = reinterpret_cast<T*>(d.U.ptr);
+    T* P = reinterpret_cast<T*>(d.P.ptr);
+    T* Wp = reinterpret_cast<T*>(d.Wp.ptr);
+    const SelInvNode* nodes = d.nodes.as<SelInvNode>();
+    const int2* tiles = d.tiles.as<int2>();
+    const int4* zTasks = d.zTasks.as<int4>();
+    for (const SelInvLevel& L : d.host.levels) {
+      if (L.smallEnd > L.smallBegin) {
+        hipk::selinvSmallLumps<T><<<(unsigned)(L.smallEnd - L.smallBegin), 64, 0, stream>>>(
+            d.smalls.as<SelInvSmall>() + L.smallBegin, sk, data);
+      }
+      const unsigned nNodes = (unsigned)(L.nodeEnd - L.nodeBegin);
+      if (nNodes == 0) continue;
+      const SelInvNode* nd = nodes + L.nodeBegin;
+      hipk::selinvDiagInverse<T><<<nNodes, 256, 0, stream>>>(nd, data, linv, dd);
+      const unsigned nTiles = (unsigned)(L.tileEnd - L.tileBegin);
+      if (nTiles > 0) {
+        hipk::selinvFormU<T><<<nTiles, 256, 0, stream>>>(nd, tiles + L.tileBegin, data, linv, U);
+        hipk::selinvZrrTimesU<T><<<(unsigned)(L.zEnd - L.zBegin), 256, 0, stream>>>(
+            nd, zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(),
+            d.pairOff.as<int64_t>(), d.pairStr.as<int32_t>(), data, U, P);
+        hipk::selinvReduceZ<T><<<nTiles, 256, 0, stream>>>(nd, tiles + L.tileBegin, data, U, P, Wp);
+      }
+      hipk::selinvDiagBlock<T><<<nNodes, 256, 0, stream>>>(nd, data, dd, Wp);
+    }
+    hipCHECK(hipGetLastError());
   }
 
   // plan of a fused factor over lumps [startLump, upToLump), built and uploaded on first use
@@ -883,6 +951,7 @@ struct HipSymbolicCtx : SymbolicCtx {
   DevBuf dSpanStart, dSpanToLump, dLumpStart, dSpanOffsetInLump, dChainColPtr, dChainRowSpan,
       dChainData, dChainRowsTillEnd, dBoardColPtr, dBoardChainColOrd, dPermutation;
   std::map<std::tuple<int, int64_t, int64_t>, std::unique_ptr<DevPlan>> plans;
+  std::unique_ptr<SelInvDev> selinv;  // selected-inversion plan, built on first use
 };
 
 template <typename T>
@@ -2459,5 +2528,14 @@ HipPlanStats hipBackendPlanStats(SymbolicCtx& sym, int64_t startLump, int64_t up
   for (const LevelRange& lr : p.levels) s.numTailPanels += lr.tail ? 1 : 0;
   return s;
 }
+
+template <typename T>
+void hipBackendSelectedInverse(SymbolicCtx& sym, T* data) {
+  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
+  BASPACHO_CHECK_NOTNULL(h);
+  h->selectedInverse(data);
+}
+template void hipBackendSelectedInverse<double>(SymbolicCtx&, double*);
+template void hipBackendSelectedInverse<float>(SymbolicCtx&, float*);
 
 }  // namespace BaSpaCho

@@ -1141,4 +1141,142 @@ SolveGatherPlan buildSolveGather(const CoalescedBlockMatrixSkel& sk, const HipPl
   return out;
 }
 
+SelInvPlanHost buildSelInvPlan(const CoalescedBlockMatrixSkel& sk) {
+  SelInvPlanHost p;
+  const int64_t nLumps = sk.numLumps();
+  constexpr int64_t W = kSelInvW;
+  struct Pending {
+    int64_t lump;
+    int32_t c0, w;  // w = 0: small lump
+  };
+  vector<vector<Pending>> byLevel;
+  vector<int64_t> doneLevel(nLumps, -1);
+  vector<int32_t> rowBaseOf(nLumps, -1);
+  vector<int64_t> pairBaseOf(nLumps, -1);
+  auto push = [&](int64_t level, Pending q) {
+    if ((int64_t)byLevel.size() <= level) byLevel.resize(level + 1);
+    byLevel[level].push_back(q);
+  };
+  for (int64_t l = nLumps - 1; l >= 0; l--) {
+    const LumpCols g = lumpCols(sk, l);
+    const int64_t firstBelow = g.chain0 + g.diagChains, k = g.nChains - g.diagChains;
+    int64_t base = 0;
+    for (int64_t c = firstBelow; c < g.chain0 + g.nChains; c++) {
+      const int64_t J = sk.spanToLump[sk.chainRowSpan[c]];
+      BASPACHO_CHECK_GT(J, l);
+      base = std::max(base, doneLevel[J] + 1);
+    }
+    if (g.width <= kSelInvSmallW && k <= kSelInvSmallChains &&
+        g.rowsBelow * g.width <= kSelInvSmallElems) {
+      push(base, Pending{l, 0, 0});
+      doneLevel[l] = base;
+      continue;
+    }
+    // chain rows and chain-pair table of the lump (shared by its nodes)
+    rowBaseOf[l] = (int32_t)p.rowChain.size();
+    for (int64_t q = 0; q < k; q++) {
+      const int64_t s = sk.chainRowSpan[firstBelow + q];
+      for (int64_t i = 0; i < sk.spanStart[s + 1] - sk.spanStart[s]; i++) {
+        p.rowChain.push_back((int32_t)q);
+        p.rowLocal.push_back((int32_t)i);
+      }
+    }
+    pairBaseOf[l] = (int64_t)p.pairOff.size();
+    for (int64_t ka = 0; ka < k; ka++) {
+      const int64_t sa = sk.chainRowSpan[firstBelow + ka];
+      for (int64_t kb = 0; kb <= ka; kb++) {
+        const int64_t sb = sk.chainRowSpan[firstBelow + kb];
+        const int64_t J = sk.spanToLump[sb];
+        const int64_t* b0 = sk.chainRowSpan.data() + sk.chainColPtr[J];
+        const int64_t* b1 = sk.chainRowSpan.data() + sk.chainColPtr[J + 1];
+        const int64_t* it = std::lower_bound(b0, b1, sa);
+        // the chain rows of a lump form a clique in the factor's pattern (complete fill)
+        BASPACHO_CHECK(it != b1 && *it == sa);
+        const int64_t ch = sk.chainColPtr[J] + (it - b0);
+        p.pairOff.push_back(sk.chainData[ch] + sk.spanStart[sb] - sk.lumpStart[J]);
+        p.pairStr.push_back((int32_t)(sk.lumpStart[J + 1] - sk.lumpStart[J]));
+      }
+    }
+    const int64_t nb = (g.width + W - 1) / W;
+    for (int64_t t = nb - 1; t >= 0; t--) {
+      push(base + (nb - 1 - t), Pending{l, (int32_t)(t * W), (int32_t)std::min(W, g.width - t * W)});
+    }
+    doneLevel[l] = base + nb - 1;
+  }
+  for (const auto& lev : byLevel) {
+    SelInvLevel L;
+    L.smallBegin = (int64_t)p.smalls.size();
+    L.nodeBegin = (int64_t)p.nodes.size();
+    L.tileBegin = (int64_t)p.tiles.size() / 2;
+    L.zBegin = (int64_t)p.zTasks.size() / 4;
+    int64_t tilesInLevel = 0;
+    for (const Pending& q : lev) {
+      if (q.w == 0) continue;
+      const LumpCols g = lumpCols(sk, q.lump);
+      tilesInLevel += (g.width - q.c0 - q.w + g.rowsBelow + 63) / 64;
+    }
+    // split the source rows of Z_RR U so that a level has some 512 workgroups where it can
+    const int64_t wantSplit = std::max<int64_t>(1, (512 + tilesInLevel - 1) / std::max<int64_t>(1, tilesInLevel));
+    int64_t uOff = 0, pOff = 0, tile = 0;
+    for (const Pending& q : lev) {
+      const LumpCols g = lumpCols(sk, q.lump);
+      if (q.w == 0) {
+        SelInvSmall s;
+        s.diagOff = g.diagOff;
+        s.n = (int32_t)g.width;
+        s.r = (int32_t)g.rowsBelow;
+        s.chainBegin = g.chain0 + g.diagChains;
+        s.k = (int32_t)(g.nChains - g.diagChains);
+        s.pad = 0;
+        p.smalls.push_back(s);
+        continue;
+      }
+      SelInvNode nd;
+      nd.lumpOff = g.diagOff;
+      nd.lda = (int32_t)g.width;
+      nd.c0 = q.c0;
+      nd.w = q.w;
+      nd.nRest = (int32_t)(g.width - q.c0 - q.w);
+      nd.r = (int32_t)(nd.nRest + g.rowsBelow);
+      nd.rowBase = rowBaseOf[q.lump];
+      nd.pairBase = pairBaseOf[q.lump];
+      const int64_t split = std::min<int64_t>(wantSplit, std::max<int64_t>(1, nd.r / 256));
+      nd.kChunk = (int32_t)(((nd.r + split - 1) / split + 15) / 16 * 16);
+      nd.nk = nd.r > 0 ? (int32_t)((nd.r + nd.kChunk - 1) / nd.kChunk) : 0;
+      nd.nTiles = (int32_t)((nd.r + 63) / 64);
+      nd.tileBase = (int32_t)tile;
+      nd.uOff = uOff;
+      nd.pOff = pOff;
+      const int32_t nodeIdx = (int32_t)(p.nodes.size() - L.nodeBegin);
+      for (int32_t t = 0; t < nd.nTiles; t++) {
+        p.tiles.push_back(nodeIdx);
+        p.tiles.push_back(t * 64);
+        for (int32_t kc = 0; kc < nd.nk; kc++) {
+          p.zTasks.insert(p.zTasks.end(), {nodeIdx, t * 64, kc, 0});
+        }
+      }
+      tile += nd.nTiles;
+      uOff += (int64_t)nd.r * W;
+      pOff += (int64_t)nd.nk * nd.r * W;
+      p.nodes.push_back(nd);
+    }
+    L.smallEnd = (int64_t)p.smalls.size();
+    L.nodeEnd = (int64_t)p.nodes.size();
+    L.tileEnd = (int64_t)p.tiles.size() / 2;
+    L.zEnd = (int64_t)p.zTasks.size() / 4;
+    p.linvElems = std::max(p.linvElems, (L.nodeEnd - L.nodeBegin) * W * W);
+    p.uElems = std::max(p.uElems, uOff);
+    p.pElems = std::max(p.pElems, pOff);
+    p.wElems = std::max(p.wElems, tile * W * W);
+    p.levels.push_back(L);
+  }
+  // every task index of a level must fit the 32-bit fields and grid dimensions the kernels use
+  BASPACHO_CHECK_LT((int64_t)p.rowChain.size(), (int64_t)INT32_MAX);
+  for (const SelInvLevel& L : p.levels) {
+    BASPACHO_CHECK_LT(L.zEnd - L.zBegin, (int64_t)INT32_MAX);
+    BASPACHO_CHECK_LT(L.smallEnd - L.smallBegin, (int64_t)INT32_MAX);
+  }
+  return p;
+}
+
 }  // namespace BaSpaCho

@@ -371,4 +371,58 @@ struct SolveGatherPlan {
 };
 SolveGatherPlan buildSolveGather(const CoalescedBlockMatrixSkel& skel, const HipPlanHost& plan);
 
+// ------------------------------------------------------------------------------------------
+// SELECTED INVERSION (hip_selinv_kernels.h): Z = A^-1 on the pattern of L, in place.  Lumps are taken
+// in reverse elimination order; a lump needs the Z of the lumps that own its chain rows, so its level
+// is one more than theirs.  Small lumps are one wave each (SelInvSmall); every other lump is cut into
+// column blocks of kSelInvW (SelInvNode), taken right to left, one level per block.
+constexpr int kSelInvW = 64;              // width of a node (column block of a lump)
+constexpr int kSelInvSmallW = 16;         // small-lump path: widest lump ...
+constexpr int kSelInvSmallChains = 16;    // ... most chains below the diagonal block ...
+constexpr int kSelInvSmallElems = 512;    // ... largest r * n
+
+struct SelInvSmall {
+  int64_t diagOff;     // data offset of the lump column (its n x n diagonal block)
+  int32_t n, r;        // width, rows below the diagonal block
+  int64_t chainBegin;  // first chain below the diagonal block
+  int32_t k, pad;      // chains below the diagonal block
+};
+
+struct SelInvNode {
+  int64_t lumpOff;   // data offset of the lump column
+  int64_t uOff;      // scratch offsets of this level: U (r x kSelInvW) ...
+  int64_t pOff;      // ... and the nk partial products (nk x r x kSelInvW)
+  int64_t pairBase;  // chain-pair table of the lump: entry ka * (ka + 1) / 2 + kb (ka >= kb)
+  int32_t lda, c0, w, r;
+  int32_t nRest;     // rows of R inside the lump's own diagonal block
+  int32_t rowBase;   // first entry of the lump's chain rows in selInvRowChain / selInvRowLocal
+  int32_t kChunk;    // source rows per partial product
+  int32_t nk;        // partial products
+  int32_t tileBase;  // first 64-row tile of the node among the level's tiles
+  int32_t nTiles;
+};
+
+struct SelInvLevel {
+  int64_t smallBegin, smallEnd;  // into smalls
+  int64_t nodeBegin, nodeEnd;    // into nodes
+  int64_t tileBegin, tileEnd;    // into tiles: {node (level-relative), first row}
+  int64_t zBegin, zEnd;          // into zTasks: {node (level-relative), first row, chunk, 0}
+};
+
+struct SelInvPlanHost {
+  std::vector<SelInvSmall> smalls;
+  std::vector<SelInvNode> nodes;
+  std::vector<int32_t> tiles;   // pairs
+  std::vector<int32_t> zTasks;  // quadruples
+  std::vector<int32_t> rowChain, rowLocal;  // per chain row of every lump that has nodes
+  std::vector<int64_t> pairOff;
+  std::vector<int32_t> pairStr;
+  std::vector<SelInvLevel> levels;
+  // scratch elements (largest over the levels: the levels run one after the other)
+  int64_t linvElems = 0, uElems = 0, pElems = 0, wElems = 0;
+};
+
+// levels in launch order (roots first)
+SelInvPlanHost buildSelInvPlan(const CoalescedBlockMatrixSkel& skel);
+
 }  // namespace BaSpaCho

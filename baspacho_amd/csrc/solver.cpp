@@ -14,6 +14,7 @@
 
 #include "computation_model.h"
 #include "elimination_tree.h"
+#include "hip_backend.h"
 
 namespace BaSpaCho {
 
@@ -473,6 +474,21 @@ template void Solver::addMvFrom<float>(const float*, int64_t, const float*, int6
                                        int64_t, int, float) const;
 template void Solver::pseudoFactorFrom<double>(double*, int64_t, bool) const;
 template void Solver::pseudoFactorFrom<float>(float*, int64_t, bool) const;
+
+template <typename T>
+void Solver::selectedInverse(T* data) const {
+  if (data == nullptr) throw std::runtime_error("selectedInverse: the data pointer is NULL");
+  if (canFactorUpTo < factorSkel.numSpans()) {
+    throw std::runtime_error(
+        "selectedInverse: this Solver can only factor up to span " + std::to_string(canFactorUpTo) +
+        " (fill added for the given elimination ranges only); the selected inverse needs a complete "
+        "factor");
+  }
+  hipBackendSelectedInverse(*symCtx, data);
+}
+
+template void Solver::selectedInverse<double>(double*) const;
+template void Solver::selectedInverse<float>(float*) const;
 
 #define BSP_INSTANTIATE(T)                                                                     \
   template void Solver::factor<T>(T*, bool) const;                                             \

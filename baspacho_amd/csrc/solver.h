@@ -72,6 +72,13 @@ class Solver {
   template <typename T>
   void pseudoFactorFrom(T* data, int64_t spanIndex, bool verbose = false) const;
 
+  // extension: selected inversion.  `data` holds a complete factor() of this Solver; it is overwritten
+  // in place by Z = A^-1 restricted to the block pattern of L, in the factor's layout (diagonal blocks
+  // full and symmetric, off-diagonal blocks in their stored orientation).  Runs on the stream of
+  // setStream(), without host synchronisation ("Selected inversion")
+  template <typename T>
+  void selectedInverse(T* data) const;
+
   int64_t order() const { return factorSkel.order(); }
   int64_t dataSize() const { return factorSkel.dataSize(); }
   int64_t canFactorUpToSpan() const { return canFactorUpTo; }

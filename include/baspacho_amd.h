@@ -221,6 +221,17 @@ int bsp_add_mv_from_f32(bsp_solver* s, const float* dev_mat, int64_t span_index,
    span_index on, the rows below it divided by the factor (any span width, MatOpsCuda.cu:188-233) */
 int bsp_pseudo_factor_from_f64(bsp_solver* s, double* dev_data, int64_t span_index);
 int bsp_pseudo_factor_from_f32(bsp_solver* s, float* dev_data, int64_t span_index);
+/* Extension (no counterpart in the reference): selected inversion, the marginal covariances of a
+   least-squares problem.  Precondition: dev_data holds a complete factor() of this solver (a solver
+   that can only factor up to a span, AddFillForGivenElims, is refused).  In place, Z = A^-1
+   restricted to the block pattern of L overwrites L in the factor's layout: every lump's diagonal
+   block is written full and symmetric (both triangles), every off-diagonal block keeps its stored
+   orientation, so bsp_diag_block_offset / bsp_block_offset (and its `flipped` flag) read Z as they
+   read L.  Entries of A^-1 outside the pattern are not computed.  Runs on the bsp_set_stream stream,
+   no host synchronisation (the first call builds the plan); the result is bitwise reproducible.
+   No GPU or a NULL dev_data: non-zero return, bsp_last_error() says why. */
+int bsp_selected_inverse_f64(bsp_solver* s, double* dev_data);
+int bsp_selected_inverse_f32(bsp_solver* s, float* dev_data);
 /* Solver::solve<std::vector<T*>> etc. (Solver.h:64-73 with the batch types of MatOps.h:38-42):
    `batch` factored matrices of the same structure and one block of right-hand sides each
    (host arrays of device pointers).  which: 0 = solve, 1 = solveL, 2 = solveLt */
