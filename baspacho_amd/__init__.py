@@ -348,6 +348,29 @@ class Solver:
         update, 0 = off"""
         _check(self._lib.bsp_test_set_fault(self._h, ctypes.c_int32(kind)))
 
+    _SELINV_SMALL_FIELDS = ("lump", "level", "n", "r", "k")
+    _SELINV_NODE_FIELDS = ("lump", "level", "c0", "w", "r", "nRest", "kChunk", "nk", "nTiles", "tileBase")
+
+    def _testSelInvPlan(self):
+        """TESTING: the selected-inversion plan of this solver (bsp_test_selinv_plan, built on the host
+        by the function selectedInverse() uses).  {"numLevels", "linvElems", "uElems", "pElems",
+        "wElems": int, "small": {field: int64 array}, "node": {field: int64 array}}, records in launch
+        order; small fields lump, level, n, r, k; node fields lump, level, c0, w, r, nRest, kChunk, nk,
+        nTiles, tileBase"""
+        need = ctypes.c_int64(0)
+        _check(self._lib.bsp_test_selinv_plan(self._h, None, ctypes.c_int64(0), ctypes.byref(need)))
+        buf = np.empty(need.value, dtype=np.int64)
+        _check(self._lib.bsp_test_selinv_plan(self._h, buf.ctypes.data_as(_I64P), need, ctypes.byref(need)))
+        nlev, ns, nn = (int(x) for x in buf[:3])
+        out = {"numLevels": nlev, "linvElems": int(buf[3]), "uElems": int(buf[4]), "pElems": int(buf[5]),
+               "wElems": int(buf[6])}
+        fs, fn = self._SELINV_SMALL_FIELDS, self._SELINV_NODE_FIELDS
+        sm = buf[7:7 + ns * len(fs)].reshape(ns, len(fs))
+        nd = buf[7 + ns * len(fs):].reshape(nn, len(fn))
+        out["small"] = {f: sm[:, i].copy() for i, f in enumerate(fs)}
+        out["node"] = {f: nd[:, i].copy() for i, f in enumerate(fn)}
+        return out
+
     def collectOpStats(self, on=True):
         """Solver::enableStats + per-op samples of the per-op boundary (bsp_collect_op_stats)"""
         _check(self._lib.bsp_collect_op_stats(self._h, ctypes.c_int32(1 if on else 0)))

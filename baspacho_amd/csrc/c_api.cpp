@@ -6,12 +6,14 @@
 #include <cstring>
 #include <numeric>
 #include <string>
+#include <unordered_map>
 #include <unordered_set>
 
 #include "bal_pipeline.h"
 #include "../../include/baspacho_amd_testing.h"
 #include "computation_model.h"
 #include "hip_backend.h"
+#include "hip_plan.h"
 #include "solver.h"
 
 using namespace BaSpaCho;
@@ -320,6 +322,35 @@ int bsp_test_read_sweep_trace(bsp_solver* s, long long* out, int32_t max_blocks,
 int bsp_test_set_fault(bsp_solver* s, int32_t kind) {
   BSP_TRY
   hipBackendSetFault(s->solver->internalSymbolicContext(), kind);
+  BSP_CATCH
+}
+
+int bsp_test_selinv_plan(const bsp_solver* s, int64_t* buf, int64_t capacity, int64_t* needed) {
+  BSP_TRY
+  const CoalescedBlockMatrixSkel& sk = s->solver->skel();
+  const SelInvPlanHost p = buildSelInvPlan(sk);
+  std::unordered_map<int64_t, int64_t> lumpOfOff;  // data offset of a lump column -> lump
+  for (int64_t l = 0; l < sk.numLumps(); l++) lumpOfOff[sk.chainData[sk.chainColPtr[l]]] = l;
+  std::vector<int64_t> out = {(int64_t)p.levels.size(), (int64_t)p.smalls.size(), (int64_t)p.nodes.size(),
+                              p.linvElems, p.uElems, p.pElems, p.wElems};
+  for (int64_t lv = 0; lv < (int64_t)p.levels.size(); lv++) {
+    const SelInvLevel& L = p.levels[lv];
+    for (int64_t i = L.smallBegin; i < L.smallEnd; i++) {
+      const SelInvSmall& q = p.smalls[i];
+      out.insert(out.end(), {lumpOfOff.at(q.diagOff), lv, (int64_t)q.n, (int64_t)q.r, (int64_t)q.k});
+    }
+  }
+  for (int64_t lv = 0; lv < (int64_t)p.levels.size(); lv++) {
+    const SelInvLevel& L = p.levels[lv];
+    for (int64_t i = L.nodeBegin; i < L.nodeEnd; i++) {
+      const SelInvNode& q = p.nodes[i];
+      out.insert(out.end(), {lumpOfOff.at(q.lumpOff), lv, (int64_t)q.c0, (int64_t)q.w, (int64_t)q.r,
+                             (int64_t)q.nRest, (int64_t)q.kChunk, (int64_t)q.nk, (int64_t)q.nTiles,
+                             (int64_t)q.tileBase});
+    }
+  }
+  *needed = (int64_t)out.size();
+  if (buf != nullptr) std::copy(out.begin(), out.begin() + std::min(capacity, *needed), buf);
   BSP_CATCH
 }
 

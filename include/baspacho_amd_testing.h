@@ -20,6 +20,15 @@ int bsp_test_set_fault(bsp_solver* s, int32_t kind);
  * never publishes its x, and the sweeps' watchdog is set to 50 ms: the launch must end by itself and
  * the next solve must report the failed call (tests/test_sweep_gpu.py). */
 
+/* The selected-inversion plan of the solver's skeleton (buildSelInvPlan, csrc/hip_plan.cpp: the plan
+ * selectedInverse() runs), built on the host with no device involved.  Layout (int64):
+ *   nLevels, nSmall, nNodes, linvElems, uElems, pElems, wElems,
+ *   nSmall records {lump, level, n, r, k},
+ *   nNodes records {lump, level, c0, w, r, nRest, kChunk, nk, nTiles, tileBase},
+ * both in launch order.  *needed = total length; at most `capacity` values are written (buf may be
+ * NULL to query the length). */
+int bsp_test_selinv_plan(const bsp_solver* s, int64_t* buf, int64_t capacity, int64_t* needed);
+
 /* Developer aid: with BSP_SWEEP_TRACE=1 in the environment when the solver is created, every spine
  * workgroup of a persistent solve sweep stamps {start, operands on chip, inputs arrived, x published}
  * (wall clock, 100 MHz); this reads the stamps of the LAST sweep, 4 values per block. */
