@@ -70,7 +70,8 @@ class _CRunCounters(ctypes.Structure):
                 ["sweep_launches", "sweep_timeouts", "split_lists_used", "sub_batches_enqueued",
                  "lookahead_forks", "sweeps_retired", "sweep_error_pending",
                  "gather_chunks_overlapped", "tail_launches", "sweep_mfma_launches",
-                 "solve_wide_launches", "inv_reused", "potrf_folded_levels"]]
+                 "solve_wide_launches", "inv_reused", "potrf_folded_levels", "selinv_launches",
+                 "selinv_chunks"]]
 
 
 @dataclass
@@ -348,6 +349,11 @@ class Solver:
         update, 0 = off"""
         _check(self._lib.bsp_test_set_fault(self._h, ctypes.c_int32(kind)))
 
+    def _testSetSelInvBatchChunk(self, max_matrices):
+        """TESTING: at most `max_matrices` matrices per chunk of a batched selectedInverse
+        (bsp_test_set_selinv_batch_chunk); 0 = the product's rule"""
+        _check(self._lib.bsp_test_set_selinv_batch_chunk(self._h, ctypes.c_int32(max_matrices)))
+
     _SELINV_SMALL_FIELDS = ("lump", "level", "n", "r", "k")
     _SELINV_NODE_FIELDS = ("lump", "level", "c0", "w", "r", "nRest", "kChunk", "nk", "nTiles", "tileBase")
 
@@ -498,7 +504,22 @@ class Solver:
         """extension: selected inversion, in place.  `data` holds a complete factor() of this
         solver; it is overwritten by Z = A^-1 on the block pattern of L, in the factor's layout
         (diagonal blocks full and symmetric, off-diagonal blocks in their stored orientation: the
-        accessors read Z as they read L).  bsp_selected_inverse_f64 / _f32"""
+        accessors read Z as they read L).  bsp_selected_inverse_f64 / _f32.
+        A list/tuple of tensors (one dtype, distinct buffers) = a batch of factors of this solver
+        (bsp_selected_inverse_batched_*): member q is bitwise selectedInverse(data[q])."""
+        if isinstance(data, (list, tuple)):
+            if len(data) == 0:
+                raise ValueError("selectedInverse: empty batch")
+            if len({t.dtype for t in data}) != 1:
+                raise TypeError("selectedInverse: the members of a batch must share one dtype, got %s"
+                                % sorted({str(t.dtype) for t in data}))
+            sfx = _suffix(data[0])
+            for t in data:
+                self._check_data(t)
+            ptrs = (ctypes.c_void_p * len(data))(*[_ptr_of(t) for t in data])
+            _check(getattr(self._lib, "bsp_selected_inverse_batched_" + sfx)(
+                self._h, ptrs, ctypes.c_int32(len(data))))
+            return
         self._check_data(data)
         _check(getattr(self._lib, "bsp_selected_inverse_" + _suffix(data))(
             self._h, ctypes.c_void_p(_ptr_of(data))))
@@ -506,7 +527,16 @@ class Solver:
     def marginals(self, data, params):
         """diagonal covariance blocks of the given user-order parameters, read from the output of
         selectedInverse(data): a device tensor [k, n, n] when every parameter has size n, else a
-        list of [n_i, n_i] tensors"""
+        list of [n_i, n_i] tensors.  `data` a list/tuple of B tensors (a batch): [B, k, n, n] when
+        every parameter has size n, else one such list per matrix"""
+        if isinstance(data, (list, tuple)):
+            if len(data) == 0:
+                raise ValueError("marginals: empty batch")
+            import torch
+            per = [self.marginals(t, params) for t in data]
+            if all(isinstance(m, torch.Tensor) for m in per):
+                return torch.stack(per)
+            return per
         params = [int(p) for p in params]
         num = self.numSpans()
         for p in params:

@@ -456,6 +456,29 @@ int bsp_selected_inverse_f32(bsp_solver* s, float* d) {
   s->solver->selectedInverse(d);
   BSP_CATCH
 }
+template <typename T>
+static void selectedInverseBatched(bsp_solver* s, T* const* ptrs, int32_t batch) {
+  if (batch <= 0) throw std::runtime_error("selectedInverse: the batch is empty (batch = " + std::to_string(batch) + ")");
+  if (ptrs == nullptr) throw std::runtime_error("selectedInverse: the array of data pointers is NULL");
+  std::vector<T*> v(ptrs, ptrs + batch);
+  s->solver->selectedInverse(&v);
+}
+int bsp_selected_inverse_batched_f64(bsp_solver* s, double* const* ptrs, int32_t batch) {
+  BSP_TRY
+  selectedInverseBatched(s, ptrs, batch);
+  BSP_CATCH
+}
+int bsp_selected_inverse_batched_f32(bsp_solver* s, float* const* ptrs, int32_t batch) {
+  BSP_TRY
+  selectedInverseBatched(s, ptrs, batch);
+  BSP_CATCH
+}
+int bsp_test_set_selinv_batch_chunk(bsp_solver* s, int32_t max_matrices) {
+  BSP_TRY
+  if (max_matrices < 0) throw std::runtime_error("bsp_test_set_selinv_batch_chunk: max_matrices < 0");
+  hipBackendSetSelInvBatchChunk(s->solver->internalSymbolicContext(), max_matrices);
+  BSP_CATCH
+}
 int bsp_pseudo_factor_from_f64(bsp_solver* s, double* d, int64_t span) {
   BSP_TRY
   s->solver->pseudoFactorFrom(d, span);
@@ -699,6 +722,8 @@ int bsp_run_counters_get(bsp_solver* s, bsp_run_counters* out) {
   out->solve_wide_launches = c.solveWideLaunches;
   out->inv_reused = c.invReused;
   out->potrf_folded_levels = c.potrfFoldedLevels;
+  out->selinv_launches = c.selinvLaunches;
+  out->selinv_chunks = c.selinvChunks;
   BSP_CATCH
 }
 

@@ -81,6 +81,8 @@ struct HipRunCounters {
   int64_t sweepMfmaLaunches = 0;   // ... of sweepLaunches: the matrix-core form for several right-hand sides
   int64_t sweepsRetired = 0;       // 1: a time-out retired the sweeps of this Solver
   int64_t sweepErrorPending = 0;   // 1: a time-out has been raised and not been reported yet
+  int64_t selinvLaunches = 0;      // kernels enqueued by selected inversion (single or batched)
+  int64_t selinvChunks = 0;        // passes over the selected-inversion levels (one per single call)
 };
 HipRunCounters hipBackendRunCounters(SymbolicCtx& sym);
 // developer aid (BSP_SWEEP_TRACE=1 when the Solver is created): clock stamps {start, operands on chip,
@@ -95,6 +97,11 @@ std::vector<int64_t> hipBackendPlanLevels(SymbolicCtx& sym, int64_t startLump, i
 // pattern of L overwrites it (hip_selinv_kernels.h), on the execution stream
 template <typename T>
 void hipBackendSelectedInverse(SymbolicCtx& sym, T* data);
+// ... of a batch of factors (distinct device pointers), in memory-bounded chunks of matrices
+template <typename T>
+void hipBackendSelectedInverse(SymbolicCtx& sym, const std::vector<T*>& data);
+// TESTING: at most `maxMatrices` matrices per chunk of a batched selected inversion (0: no cap)
+void hipBackendSetSelInvBatchChunk(SymbolicCtx& sym, int64_t maxMatrices);
 
 HipPlanStats hipBackendPlanStats(SymbolicCtx& sym, int64_t startLump, int64_t upToLump);
 

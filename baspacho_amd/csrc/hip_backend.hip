@@ -460,7 +460,33 @@ struct FlagOff {
 struct SelInvDev {
   SelInvPlanHost host;
   DevBuf smalls, nodes, tiles, zTasks, rowChain, rowLocal, pairOff, pairStr;
-  DevBuf linv, dd, U, P, Wp;  // scratch, sized for fp64 (fp32 uses the first half)
+  // scratch: `slices` per-matrix slices of the plan's element counts, matrix q of a batch chunk in
+  // slice q (hipk::SelInvStrides, counted in elements of T).  The buffers are sized in fp64: the fp32
+  // slices, half as many bytes each, are packed into the first half of every buffer
+  DevBuf linv, dd, U, P, Wp;
+  int64_t slices = 0;
+  hipk::SelInvStrides strides() const { return {host.linvElems, host.uElems, host.pElems, host.wElems}; }
+  // fp64 bytes of one slice of every scratch buffer
+  int64_t sliceBytes() const {
+    return (2 * host.linvElems + host.uElems + host.pElems + host.wElems) * (int64_t)sizeof(double);
+  }
+  // grow the scratch to n slices.  Kernels queued by an earlier call (on any stream) may still use the
+  // old buffers: wait for them before freeing (as PtrRing::push does).  No slice counts as usable until
+  // all five allocations have succeeded: a failed grow (an allocation that throws) leaves slices = 0,
+  // and the next call allocates again instead of launching on released buffers
+  void reserve(int64_t n) {
+    if (n <= slices) return;
+    if (slices > 0) hipCHECK(hipDeviceSynchronize());
+    slices = 0;
+    for (DevBuf* b : {&linv, &dd, &U, &P, &Wp}) b->release();
+    const auto bytes = [n](int64_t elems) { return (size_t)std::max<int64_t>(elems * n, 1) * sizeof(double); };
+    linv.resize(bytes(host.linvElems));
+    dd.resize(bytes(host.linvElems));
+    U.resize(bytes(host.uElems));
+    P.resize(bytes(host.pElems));
+    Wp.resize(bytes(host.wElems));
+    slices = n;
+  }
   void upload() {
     smalls.upload(host.smalls);
     nodes.upload(host.nodes);
@@ -470,11 +496,7 @@ struct SelInvDev {
     rowLocal.upload(host.rowLocal);
     pairOff.upload(host.pairOff);
     pairStr.upload(host.pairStr);
-    linv.resize(std::max<int64_t>(host.linvElems, 1) * sizeof(double));
-    dd.resize(std::max<int64_t>(host.linvElems, 1) * sizeof(double));
-    U.resize(std::max<int64_t>(host.uElems, 1) * sizeof(double));
-    P.resize(std::max<int64_t>(host.pElems, 1) * sizeof(double));
-    Wp.resize(std::max<int64_t>(host.wElems, 1) * sizeof(double));
+    reserve(1);
   }
 };
 
@@ -692,14 +714,55 @@ struct HipSymbolicCtx : SymbolicCtx {
   template <typename T>
   void selectedInverse(T* data) {
     checkDevice();
+    SelInvDev& d = selInvPlan();
+    d.reserve(1);
+    selInvLevels<T>(d, {data, nullptr}, 1);
+    hipCHECK(hipGetLastError());
+  }
+
+  // A batch of factors of this skeleton: the pointer array goes through the PtrRing, and the batch runs
+  // in chunks of `chunk` matrices, one after the other on the execution stream.  A chunk is one pass
+  // over the levels with gridDim.y = its matrices, each in its own scratch slice.  Chunk size:
+  // min(batch, 65535 (gridDim.y), what half the free device memory holds in slices -- slices the
+  // solver already holds count as free), at least 1, at most the testing cap.  The scratch grows to the
+  // chunk and stays with the solver.
+  template <typename T>
+  void selectedInverse(const vector<T*>& data) {
+    checkDevice();
+    SelInvDev& d = selInvPlan();
+    const int64_t batch = (int64_t)data.size();
+    int64_t chunk = std::min<int64_t>(batch, 65535);
+    if (selInvChunkCap > 0) chunk = std::min<int64_t>(chunk, selInvChunkCap);
+    const int64_t slice = d.sliceBytes();
+    if (chunk > d.slices && slice > 0) {
+      size_t freeBytes = 0, totalBytes = 0;
+      hipCHECK(hipMemGetInfo(&freeBytes, &totalBytes));
+      const int64_t fit = std::max<int64_t>(d.slices, (int64_t)(freeBytes / 2) / slice);
+      chunk = std::max<int64_t>(1, std::min(chunk, fit));
+    }
+    d.reserve(chunk);
+    T* const* many = (T* const*)ptrRing.push(data.data(), data.size() * sizeof(T*), stream);
+    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
+      selInvLevels<T>(d, {nullptr, many + q0}, (unsigned)std::min(chunk, batch - q0));
+    }
+    hipCHECK(hipGetLastError());
+  }
+
+  SelInvDev& selInvPlan() {
     if (!selinv) {
       std::unique_ptr<SelInvDev> p(new SelInvDev);
       p->host = buildSelInvPlan(skel);
       p->upload();
       selinv = std::move(p);
     }
-    const SelInvDev& d = *selinv;
+    return *selinv;
+  }
+
+  // one pass over the levels for `nMats` matrices (gridDim.y), in scratch slices 0 .. nMats-1
+  template <typename T>
+  void selInvLevels(const SelInvDev& d, hipk::DataRef<T> data, unsigned nMats) {
     const hipk::SkelDev sk = skelDev();
+    const hipk::SelInvStrides st = d.strides();
     T* linv = reinterpret_cast<T*>(d.linv.ptr);
     T* dd = reinterpret_cast<T*>(d.dd.ptr);
     T* U = reinterpret_cast<T*>(d.U.ptr);
@@ -708,26 +771,31 @@ struct HipSymbolicCtx : SymbolicCtx {
     const SelInvNode* nodes = d.nodes.as<SelInvNode>();
     const int2* tiles = d.tiles.as<int2>();
     const int4* zTasks = d.zTasks.as<int4>();
+    int64_t launches = 0;
     for (const SelInvLevel& L : d.host.levels) {
       if (L.smallEnd > L.smallBegin) {
-        hipk::selinvSmallLumps<T><<<(unsigned)(L.smallEnd - L.smallBegin), 64, 0, stream>>>(
+        hipk::selinvSmallLumps<T><<<dim3((unsigned)(L.smallEnd - L.smallBegin), nMats), 64, 0, stream>>>(
             d.smalls.as<SelInvSmall>() + L.smallBegin, sk, data);
+        launches++;
       }
       const unsigned nNodes = (unsigned)(L.nodeEnd - L.nodeBegin);
       if (nNodes == 0) continue;
       const SelInvNode* nd = nodes + L.nodeBegin;
-      hipk::selinvDiagInverse<T><<<nNodes, 256, 0, stream>>>(nd, data, linv, dd);
+      hipk::selinvDiagInverse<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, data, linv, dd, st);
       const unsigned nTiles = (unsigned)(L.tileEnd - L.tileBegin);
       if (nTiles > 0) {
-        hipk::selinvFormU<T><<<nTiles, 256, 0, stream>>>(nd, tiles + L.tileBegin, data, linv, U);
-        hipk::selinvZrrTimesU<T><<<(unsigned)(L.zEnd - L.zBegin), 256, 0, stream>>>(
+        hipk::selinvFormU<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, tiles + L.tileBegin, data, linv, U, st);
+        hipk::selinvZrrTimesU<T><<<dim3((unsigned)(L.zEnd - L.zBegin), nMats), 256, 0, stream>>>(
             nd, zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(),
-            d.pairOff.as<int64_t>(), d.pairStr.as<int32_t>(), data, U, P);
-        hipk::selinvReduceZ<T><<<nTiles, 256, 0, stream>>>(nd, tiles + L.tileBegin, data, U, P, Wp);
+            d.pairOff.as<int64_t>(), d.pairStr.as<int32_t>(), data, U, P, st);
+        hipk::selinvReduceZ<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, tiles + L.tileBegin, data, U, P, Wp, st);
+        launches += 3;
       }
-      hipk::selinvDiagBlock<T><<<nNodes, 256, 0, stream>>>(nd, data, dd, Wp);
+      hipk::selinvDiagBlock<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, data, dd, Wp, st);
+      launches += 2;
     }
-    hipCHECK(hipGetLastError());
+    counters.selinvLaunches += launches;
+    counters.selinvChunks++;
   }
 
   // plan of a fused factor over lumps [startLump, upToLump), built and uploaded on first use
@@ -860,6 +928,7 @@ struct HipSymbolicCtx : SymbolicCtx {
   struct RunCounters {
     int64_t sweepLaunches = 0, sweepTimeouts = 0, splitListsUsed = 0, subBatchesEnqueued = 0,
             lookaheadForks = 0, gatherChunksOverlapped = 0, tailLaunches = 0, sweepMfmaLaunches = 0, invReused = 0, solveWideLaunches = 0, potrfFoldedLevels = 0;
+    int64_t selinvLaunches = 0, selinvChunks = 0;
   } counters;
   // a timed-out persistent launch (solve sweep, factor tail) is reported ONCE, by the next factor()
   // or solve() on this Solver; the persistent kernels are then retired for good
@@ -952,6 +1021,7 @@ struct HipSymbolicCtx : SymbolicCtx {
       dChainData, dChainRowsTillEnd, dBoardColPtr, dBoardChainColOrd, dPermutation;
   std::map<std::tuple<int, int64_t, int64_t>, std::unique_ptr<DevPlan>> plans;
   std::unique_ptr<SelInvDev> selinv;  // selected-inversion plan, built on first use
+  int64_t selInvChunkCap = 0;          // TESTING: most matrices per selected-inversion chunk (0: no cap)
 };
 
 template <typename T>
@@ -2480,6 +2550,8 @@ HipRunCounters hipBackendRunCounters(SymbolicCtx& sym) {
   c.solveWideLaunches = h->counters.solveWideLaunches;
   c.invReused = h->counters.invReused;
   c.potrfFoldedLevels = h->counters.potrfFoldedLevels;
+  c.selinvLaunches = h->counters.selinvLaunches;
+  c.selinvChunks = h->counters.selinvChunks;
   c.sweepsRetired = h->sweepBroken ? 1 : 0;
   c.sweepErrorPending = (h->sweepHostErr && *reinterpret_cast<volatile unsigned*>(h->sweepHostErr)) ? 1 : 0;
   return c;
@@ -2537,5 +2609,21 @@ void hipBackendSelectedInverse(SymbolicCtx& sym, T* data) {
 }
 template void hipBackendSelectedInverse<double>(SymbolicCtx&, double*);
 template void hipBackendSelectedInverse<float>(SymbolicCtx&, float*);
+
+template <typename T>
+void hipBackendSelectedInverse(SymbolicCtx& sym, const vector<T*>& data) {
+  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
+  BASPACHO_CHECK_NOTNULL(h);
+  h->selectedInverse(data);
+}
+template void hipBackendSelectedInverse<double>(SymbolicCtx&, const vector<double*>&);
+template void hipBackendSelectedInverse<float>(SymbolicCtx&, const vector<float*>&);
+
+void hipBackendSetSelInvBatchChunk(SymbolicCtx& sym, int64_t maxMatrices) {
+  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
+  BASPACHO_CHECK_NOTNULL(h);
+  BASPACHO_CHECK_GE(maxMatrices, 0);
+  h->selInvChunkCap = maxMatrices;
+}
 
 }  // namespace BaSpaCho

@@ -12,16 +12,29 @@
 //   Z_II = Linv^T Linv - U^T Z_RI           (written full and symmetric)
 // Every element of Z has exactly one writer and every sum runs in a fixed order: the result is
 // bitwise reproducible.
+//
+// BATCH: every kernel runs the same launch for `gridDim.y` matrices of one structure.  Matrix
+// q = blockIdx.y finds its data through pickData (hip_kernels.h: the GP<T> pointer keeps the global
+// address space down to the access) and uses slice q of every scratch buffer (SelInvStrides).  The
+// arithmetic of a matrix does not depend on q: member q of a batch is bitwise a single call (a single
+// call is DataRef{data, nullptr} with gridDim.y = 1).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "hip_kernels.h"
 #include "hip_plan.h"
 
 namespace BaSpaCho {
 namespace hipk {
+
+// elements per matrix of each selected-inversion scratch buffer (the plan's linvElems (Linv and DD),
+// uElems, pElems, wElems): matrix blockIdx.y of a batch works in slice blockIdx.y
+struct SelInvStrides {
+  int64_t linv, u, p, w;
+};
 
 // Z(a, b) of a node's R x R block, a and b row indices of R (any order).  Own-lump columns (b < nRest)
 // are read from the lump column itself: the trailing diagonal block is stored full and symmetric, the
@@ -49,11 +62,14 @@ __device__ __forceinline__ int64_t selinvZAddr(const SelInvNode& nd, const int32
 // (zero outside w x w).  One workgroup of 256 per node.
 template <typename T>
 __global__ void __launch_bounds__(256) selinvDiagInverse(const SelInvNode* __restrict__ nodes,
-                                                         const T* __restrict__ data, T* __restrict__ linv,
-                                                         T* __restrict__ dd) {
+                                                         DataRef<T> dref, T* __restrict__ linv,
+                                                         T* __restrict__ dd, SelInvStrides st) {
   constexpr int W = kSelInvW;
   __shared__ T Ls[W][W + 1];
   __shared__ T Xs[W][W + 1];
+  const GP<T> data = pickData(dref);
+  linv += (int64_t)blockIdx.y * st.linv;
+  dd += (int64_t)blockIdx.y * st.linv;
   const SelInvNode nd = nodes[blockIdx.x];
   const int w = nd.w, tid = threadIdx.x;
   for (int e = tid; e < W * W; e += 256) {
@@ -86,11 +102,14 @@ __global__ void __launch_bounds__(256) selinvDiagInverse(const SelInvNode* __res
 template <typename T>
 __global__ void __launch_bounds__(256) selinvFormU(const SelInvNode* __restrict__ nodes,
                                                    const int2* __restrict__ tasks,
-                                                   const T* __restrict__ data, const T* __restrict__ linv,
-                                                   T* __restrict__ U) {
+                                                   DataRef<T> dref, const T* __restrict__ linv,
+                                                   T* __restrict__ U, SelInvStrides st) {
   constexpr int W = kSelInvW;
   __shared__ T Xs[W][W + 1];
   __shared__ T Rs[64][W + 1];
+  const GP<T> data = pickData(dref);
+  linv += (int64_t)blockIdx.y * st.linv;
+  U += (int64_t)blockIdx.y * st.u;
   const int2 tk = tasks[blockIdx.x];
   const SelInvNode nd = nodes[tk.x];
   const int a0 = tk.y, w = nd.w, tid = threadIdx.x;
@@ -120,10 +139,13 @@ __global__ void __launch_bounds__(256) selinvZrrTimesU(
     const SelInvNode* __restrict__ nodes, const int4* __restrict__ tasks,
     const int32_t* __restrict__ rowChain, const int32_t* __restrict__ rowLocal,
     const int64_t* __restrict__ pairOff, const int32_t* __restrict__ pairStr,
-    const T* __restrict__ data, const T* __restrict__ U, T* __restrict__ P) {
+    DataRef<T> dref, const T* __restrict__ U, T* __restrict__ P, SelInvStrides st) {
   constexpr int W = kSelInvW, KB = 16;
   __shared__ T Zs[KB][64 + 1];  // Zs[kb][row]
   __shared__ T Us[KB][W + 1];
+  const GP<T> data = pickData(dref);
+  U += (int64_t)blockIdx.y * st.u;
+  P += (int64_t)blockIdx.y * st.p;
   const int4 tk = tasks[blockIdx.x];
   const SelInvNode nd = nodes[tk.x];
   const int a0 = tk.y, tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
@@ -177,11 +199,16 @@ __global__ void __launch_bounds__(256) selinvZrrTimesU(
 template <typename T>
 __global__ void __launch_bounds__(256) selinvReduceZ(const SelInvNode* __restrict__ nodes,
                                                      const int2* __restrict__ tasks,
-                                                     T* __restrict__ data, const T* __restrict__ U,
-                                                     const T* __restrict__ P, T* __restrict__ Wp) {
+                                                     DataRef<T> dref, const T* __restrict__ U,
+                                                     const T* __restrict__ P, T* __restrict__ Wp,
+                                                     SelInvStrides st) {
   constexpr int W = kSelInvW;
   __shared__ T Zt[64][W + 1];
   __shared__ T Ut[64][W + 1];
+  const GP<T> data = pickData(dref);
+  U += (int64_t)blockIdx.y * st.u;
+  P += (int64_t)blockIdx.y * st.p;
+  Wp += (int64_t)blockIdx.y * st.w;
   const int2 tk = tasks[blockIdx.x];
   const SelInvNode nd = nodes[tk.x];
   const int a0 = tk.y, w = nd.w, tid = threadIdx.x;
@@ -216,9 +243,12 @@ __global__ void __launch_bounds__(256) selinvReduceZ(const SelInvNode* __restric
 // triangle is computed, the upper one mirrored: symmetric to the last bit)
 template <typename T>
 __global__ void __launch_bounds__(256) selinvDiagBlock(const SelInvNode* __restrict__ nodes,
-                                                       T* __restrict__ data, const T* __restrict__ dd,
-                                                       const T* __restrict__ Wp) {
+                                                       DataRef<T> dref, const T* __restrict__ dd,
+                                                       const T* __restrict__ Wp, SelInvStrides st) {
   constexpr int W = kSelInvW;
+  const GP<T> data = pickData(dref);
+  dd += (int64_t)blockIdx.y * st.linv;
+  Wp += (int64_t)blockIdx.y * st.w;
   const SelInvNode nd = nodes[blockIdx.x];
   const int w = nd.w;
   for (int e = threadIdx.x; e < W * W; e += 256) {
@@ -238,7 +268,7 @@ __global__ void __launch_bounds__(256) selinvDiagBlock(const SelInvNode* __restr
 // holds one 16-byte descriptor per lump.
 template <typename T>
 __global__ void __launch_bounds__(64) selinvSmallLumps(const SelInvSmall* __restrict__ lumps,
-                                                       SkelDev sk, T* __restrict__ data) {
+                                                       SkelDev sk, DataRef<T> dref) {
   constexpr int NW = kSelInvSmallW, NC = kSelInvSmallChains, NE = kSelInvSmallElems;
   static_assert(NC < 256, "chain ordinals are stored in bytes");
   __shared__ T Xs[NW][NW + 1];
@@ -249,6 +279,7 @@ __global__ void __launch_bounds__(64) selinvSmallLumps(const SelInvSmall* __rest
   __shared__ int32_t cRow0[NC + 1];
   __shared__ uint8_t rowK[NE];
   __shared__ int16_t rowL[NE];
+  const GP<T> data = pickData(dref);
   const SelInvSmall ls = lumps[blockIdx.x];
   const int n = ls.n, r = ls.r, k = ls.k, lane = threadIdx.x;
   const int64_t cBeg = ls.chainBegin;

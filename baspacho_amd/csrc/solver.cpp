@@ -475,20 +475,59 @@ template void Solver::addMvFrom<float>(const float*, int64_t, const float*, int6
 template void Solver::pseudoFactorFrom<double>(double*, int64_t, bool) const;
 template void Solver::pseudoFactorFrom<float>(float*, int64_t, bool) const;
 
+// the data of a selected inversion: one factor, or a batch of distinct factors (two members aliasing
+// one buffer would race).  Checked before any device work.
+template <typename T>
+static void checkSelInvData(T* data) {
+  if (data == nullptr) throw std::runtime_error("selectedInverse: the data pointer is NULL");
+}
+template <typename T>
+static void checkSelInvData(std::vector<T*>* data) {
+  if (data == nullptr) throw std::runtime_error("selectedInverse: the batch is NULL");
+  if (data->empty()) throw std::runtime_error("selectedInverse: the batch is empty");
+  std::vector<std::pair<T*, int64_t>> sorted;
+  sorted.reserve(data->size());
+  for (int64_t q = 0; q < (int64_t)data->size(); q++) {
+    if ((*data)[q] == nullptr) {
+      throw std::runtime_error("selectedInverse: the data pointer of batch member " + std::to_string(q) +
+                               " is NULL");
+    }
+    sorted.emplace_back((*data)[q], q);
+  }
+  std::sort(sorted.begin(), sorted.end());
+  for (size_t i = 1; i < sorted.size(); i++) {
+    if (sorted[i].first == sorted[i - 1].first) {
+      throw std::runtime_error("selectedInverse: batch members " + std::to_string(sorted[i - 1].second) +
+                               " and " + std::to_string(sorted[i].second) +
+                               " are the same pointer (two members must not share a buffer)");
+    }
+  }
+}
+template <typename T>
+static void runSelInv(SymbolicCtx& sym, T* data) {
+  hipBackendSelectedInverse(sym, data);
+}
+template <typename T>
+static void runSelInv(SymbolicCtx& sym, std::vector<T*>* data) {
+  hipBackendSelectedInverse(sym, *data);
+}
+
 template <typename T>
 void Solver::selectedInverse(T* data) const {
-  if (data == nullptr) throw std::runtime_error("selectedInverse: the data pointer is NULL");
+  checkSelInvData(data);
   if (canFactorUpTo < factorSkel.numSpans()) {
     throw std::runtime_error(
         "selectedInverse: this Solver can only factor up to span " + std::to_string(canFactorUpTo) +
         " (fill added for the given elimination ranges only); the selected inverse needs a complete "
         "factor");
   }
-  hipBackendSelectedInverse(*symCtx, data);
+  runSelInv(*symCtx, data);
 }
 
 template void Solver::selectedInverse<double>(double*) const;
 template void Solver::selectedInverse<float>(float*) const;
+template void Solver::selectedInverse<std::vector<double*>>(std::vector<double*>*) const;
+template void Solver::selectedInverse<std::vector<float*>>(std::vector<float*>*) const;
 
 #define BSP_INSTANTIATE(T)                                                                     \
   template void Solver::factor<T>(T*, bool) const;                                             \

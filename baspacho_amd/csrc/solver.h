@@ -75,7 +75,10 @@ class Solver {
   // extension: selected inversion.  `data` holds a complete factor() of this Solver; it is overwritten
   // in place by Z = A^-1 restricted to the block pattern of L, in the factor's layout (diagonal blocks
   // full and symmetric, off-diagonal blocks in their stored orientation).  Runs on the stream of
-  // setStream(), without host synchronisation ("Selected inversion")
+  // setStream(), without host synchronisation ("Selected inversion").
+  // T = std::vector<double*> / std::vector<float*>: a batch of factors of this Solver, as factor(&v);
+  // member q comes out bitwise equal to selectedInverse(v[q]).  An empty batch, a NULL member or two
+  // members with the same pointer are refused.  The batch runs in chunks bounded by device memory.
   template <typename T>
   void selectedInverse(T* data) const;
 

@@ -232,6 +232,16 @@ int bsp_pseudo_factor_from_f32(bsp_solver* s, float* dev_data, int64_t span_inde
    No GPU or a NULL dev_data: non-zero return, bsp_last_error() says why. */
 int bsp_selected_inverse_f64(bsp_solver* s, double* dev_data);
 int bsp_selected_inverse_f32(bsp_solver* s, float* dev_data);
+/* Solver::selectedInverse<std::vector<T*>>: the same for `batch` complete factors of this solver
+   (dev_ptrs is a HOST array of distinct device pointers).  Member q is bitwise equal to
+   bsp_selected_inverse_* of dev_ptrs[q].  The batch runs in chunks, one after the other on the
+   execution stream: each chunk takes one pass over the levels for all its matrices, with scratch
+   for each of them.  A chunk holds at most 65535 matrices and what half the free device memory
+   holds in scratch (at least one); the grown scratch stays with the solver until it is destroyed.
+   A batch <= 0, a NULL dev_ptrs, a NULL member or two equal members: non-zero return before any
+   device work, bsp_last_error() says why. */
+int bsp_selected_inverse_batched_f64(bsp_solver* s, double* const* dev_ptrs, int32_t batch);
+int bsp_selected_inverse_batched_f32(bsp_solver* s, float* const* dev_ptrs, int32_t batch);
 /* Solver::solve<std::vector<T*>> etc. (Solver.h:64-73 with the batch types of MatOps.h:38-42):
    `batch` factored matrices of the same structure and one block of right-hand sides each
    (host arrays of device pointers).  which: 0 = solve, 1 = solveL, 2 = solveLt */
@@ -336,6 +346,9 @@ typedef struct bsp_run_counters {
   int64_t solve_wide_launches;  /* backward elimination passes with the right-hand sides across the lanes */
   int64_t inv_reused;           /* backward passes that found the inverted diagonal blocks of their forward pass */
   int64_t potrf_folded_levels;  /* tree levels whose potrf launch was folded into their trsm launch */
+  int64_t selinv_launches;      /* kernels enqueued by selected inversion (single or batched) */
+  int64_t selinv_chunks;        /* passes over the selected-inversion levels: 1 per single call, 1 per
+                                   chunk of a batched call */
 } bsp_run_counters;
 int bsp_run_counters_get(bsp_solver* s, bsp_run_counters* out);
 

@@ -29,6 +29,10 @@ int bsp_test_set_fault(bsp_solver* s, int32_t kind);
  * NULL to query the length). */
 int bsp_test_selinv_plan(const bsp_solver* s, int64_t* buf, int64_t capacity, int64_t* needed);
 
+/* Caps the chunk of a batched selected inversion (bsp_selected_inverse_batched_*) at `max_matrices`
+ * matrices, so that tests can force several chunks on small batches; 0 = the product's rule. */
+int bsp_test_set_selinv_batch_chunk(bsp_solver* s, int32_t max_matrices);
+
 /* Developer aid: with BSP_SWEEP_TRACE=1 in the environment when the solver is created, every spine
  * workgroup of a persistent solve sweep stamps {start, operands on chip, inputs arrived, x published}
  * (wall clock, 100 MHz); this reads the stamps of the LAST sweep, 4 values per block. */

@@ -1,8 +1,10 @@
 """Time factor() + selectedInverse() on the device (events, warmed up, several repetitions) on BAL-871
 (synthetic, point range [0, 527480]), GRID 82x82 and one MERI problem; prints one JSON line per problem.
 Rates: selected inversion does 2 x bsp_factor_flops ("Selected inversion").
+--batch N: N copies of the problem's factor instead, one batched selectedInverse(list) against N
+single calls in a loop (each timed from a fresh batched factor, with the same events).
 
-    python tools/selinv_time.py [--reps 5] [--warmup 2] [--only bal871,grid82,meri]
+    python tools/selinv_time.py [--reps 5] [--warmup 2] [--only bal871,grid82,meri] [--batch N]
 """
 import argparse
 import json
@@ -39,6 +41,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--only", default="bal871,grid82,meri")
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
+    ap.add_argument("--batch", type=int, default=0)
     a = ap.parse_args()
     import torch
     dt = torch.float64 if a.dtype == "f64" else torch.float32
@@ -47,6 +50,9 @@ def main():
         h = T.random_data(sol.dataSize(), -1.0, 1.0, 37)
         sol.damp(h, 0.0, sol.order() * 1.2)
         src = torch.from_numpy(h).to("cuda", dt)
+        if a.batch > 0:
+            time_batch(sol, name, src, a)
+            continue
         d = torch.empty_like(src)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         fac, inv = [], []
@@ -71,6 +77,49 @@ def main():
             "selinv_ms_max": round(float(np.max(inv)), 3), "selinv_gflop": round(flops / 1e9, 2),
             "selinv_gflops_per_s": round(flops / (med * 1e6), 1),
             "selinv_over_factor": round(med / float(np.median(fac)), 2)}), flush=True)
+
+
+def time_batch(sol, name, src, a):
+    """one batched selectedInverse of `a.batch` factors against as many single calls"""
+    import torch
+    ds = [torch.empty_like(src) for _ in range(a.batch)]
+
+    def fresh():
+        for d in ds:
+            d.copy_(src)
+        sol.factor(ds)
+
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    batched, loop = [], []
+    c0 = sol.runCounters()
+    for it in range(a.warmup + a.reps):
+        fresh()
+        ev[0].record()
+        sol.selectedInverse(ds)
+        ev[1].record()
+        fresh()
+        ev[2].record()
+        for d in ds:
+            sol.selectedInverse(d)
+        ev[3].record()
+        torch.cuda.synchronize()
+        if it >= a.warmup:
+            batched.append(ev[0].elapsed_time(ev[1]))
+            loop.append(ev[2].elapsed_time(ev[3]))
+    c1 = sol.runCounters()
+    assert all(torch.isfinite(d).all().item() for d in ds)
+    runs = a.warmup + a.reps
+    mb, ml = float(np.median(batched)), float(np.median(loop))
+    flops = 2.0 * sol.factorFlops() * a.batch
+    print(json.dumps({
+        "problem": name, "dtype": a.dtype, "batch": a.batch, "order": sol.order(), "reps": a.reps,
+        "batched_ms_median": round(mb, 3), "batched_ms_min": round(float(np.min(batched)), 3),
+        "batched_ms_max": round(float(np.max(batched)), 3), "loop_ms_median": round(ml, 3),
+        "loop_ms_min": round(float(np.min(loop)), 3), "loop_ms_max": round(float(np.max(loop)), 3),
+        "batched_ms_per_matrix": round(mb / a.batch, 3), "loop_over_batched": round(ml / mb, 2),
+        "batched_gflops_per_s": round(flops / (mb * 1e6), 1),
+        "chunks_per_batched_call": (c1["selinv_chunks"] - c0["selinv_chunks"] - runs * a.batch) / runs}),
+        flush=True)
 
 
 if __name__ == "__main__":
