@@ -187,6 +187,7 @@ class Solver:
         self._lib = _lib.load()
         self._h = handle
         self._skel = None
+        self._stream = None  # what setStream() was last given (the autograd functions restore it)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -304,6 +305,7 @@ class Solver:
         """stream: torch.cuda.Stream, raw hipStream_t address, or None (default stream)"""
         addr = 0 if stream is None else getattr(stream, "cuda_stream", stream)
         self._lib.bsp_set_stream(self._h, ctypes.c_void_p(addr))
+        self._stream = stream
 
     def _check_data(self, t):
         if t.numel() != self.dataSize():
@@ -558,6 +560,78 @@ class Solver:
             idx = base[:, None, None] + r[None, :, None] * stride[:, None, None] + r[None, None, :]
             return data[idx.to(data.device)]
         return [data.as_strided((n, n), (st, 1), o).clone() for n, (o, st) in zip(sizes, offs)]
+
+    def logDet(self, data):
+        """extension: log det A = 2 sum_i log L_ii of a complete factor() in `data`, accumulated in
+        fp64 (bsp_log_det_f64 / _f32).  Returns a 0-dim device tensor of data's dtype, enqueued on the
+        solver's stream without synchronising; a non-positive or NaN pivot gives -inf or NaN.  A
+        list/tuple of tensors (one dtype) = a batch: a device tensor [B] (bsp_log_det_batched_*)."""
+        import torch
+        if isinstance(data, (list, tuple)):
+            if len(data) == 0:
+                raise ValueError("logDet: empty batch")
+            if len({t.dtype for t in data}) != 1:
+                raise TypeError("logDet: the members of a batch must share one dtype")
+            sfx = _suffix(data[0])
+            for t in data:
+                self._check_data(t)
+            ptrs = (ctypes.c_void_p * len(data))(*[_ptr_of(t) for t in data])
+            out = torch.empty(len(data), dtype=data[0].dtype, device=data[0].device)
+            _check(getattr(self._lib, "bsp_log_det_batched_" + sfx)(
+                self._h, ptrs, ctypes.c_void_p(_ptr_of(out)), ctypes.c_int32(len(data))))
+            return out
+        self._check_data(data)
+        out = torch.empty((), dtype=data.dtype, device=data.device)
+        _check(getattr(self._lib, "bsp_log_det_" + _suffix(data))(
+            self._h, ctypes.c_void_p(_ptr_of(data)), ctypes.c_void_p(_ptr_of(out))))
+        return out
+
+    def patternGrad(self, out, Z=None, zScale=None, U=None, V=None, nRHS=1, alpha=1.0, stride=None):
+        """extension: the write-only gradient projection on the pattern of L (bsp_pattern_grad_*).
+        For every stored element e = (i, j) of `out` (never read):
+          i > j: s 2 Z_e + alpha sum_k (U_ik V_jk + V_ik U_jk);  i = j: s Z_e + alpha sum_k U_ik V_ik;
+          strictly-upper elements of the diagonal blocks: 0.
+        s = zScale[0], a device tensor (no Z: no first term); U, V column-major order x nRHS with
+        leading dimension `stride` (default order()), e.g. tensors [nRHS, order] (none: no second
+        term).  `out` a list/tuple = a batch: Z, U, V lists of the same length (or None), s =
+        zScale[q] for member q."""
+        batched = isinstance(out, (list, tuple))
+        outs = list(out) if batched else [out]
+        if len(outs) == 0:
+            raise ValueError("patternGrad: empty batch")
+        if stride is None:
+            stride = self.order()
+
+        def members(x, name):
+            if x is None:
+                return None
+            xs = list(x) if batched else [x]
+            if len(xs) != len(outs):
+                raise ValueError("patternGrad: %s has %d members for a batch of %d" % (name, len(xs), len(outs)))
+            return xs
+        zs, us, vs = members(Z, "Z"), members(U, "U"), members(V, "V")
+        dt = outs[0].dtype
+        for t in outs + (zs or []) + (us or []) + (vs or []) + ([zScale] if zScale is not None else []):
+            if t.dtype != dt:
+                raise TypeError("patternGrad: every tensor must have the dtype of out (%s), got %s" % (dt, t.dtype))
+        for t in outs + (zs or []):
+            self._check_data(t)
+        sfx = _suffix(outs[0])
+        real = ctypes.c_double if sfx == "f64" else ctypes.c_float
+        zsp = ctypes.c_void_p(_ptr_of(zScale) if zScale is not None else None)
+        if batched:
+            def arr(xs):
+                return None if xs is None else (ctypes.c_void_p * len(xs))(*[_ptr_of(t) for t in xs])
+            _check(getattr(self._lib, "bsp_pattern_grad_batched_" + sfx)(
+                self._h, arr(zs), zsp, arr(us), arr(vs), ctypes.c_int64(stride), ctypes.c_int32(nRHS),
+                real(alpha), arr(outs), ctypes.c_int32(len(outs))))
+            return
+
+        def one(xs):
+            return ctypes.c_void_p(None if xs is None else _ptr_of(xs[0]))
+        _check(getattr(self._lib, "bsp_pattern_grad_" + sfx)(
+            self._h, one(zs), zsp, one(us), one(vs), ctypes.c_int64(stride), ctypes.c_int32(nRHS),
+            real(alpha), one(outs)))
 
     # ---- measurement --------------------------------------------------------------------
     def factorFlops(self):

@@ -473,6 +473,74 @@ int bsp_selected_inverse_batched_f32(bsp_solver* s, float* const* ptrs, int32_t 
   selectedInverseBatched(s, ptrs, batch);
   BSP_CATCH
 }
+int bsp_log_det_f64(bsp_solver* s, const double* f, double* out) {
+  BSP_TRY
+  s->solver->logDet(f, out);
+  BSP_CATCH
+}
+int bsp_log_det_f32(bsp_solver* s, const float* f, float* out) {
+  BSP_TRY
+  s->solver->logDet(f, out);
+  BSP_CATCH
+}
+template <typename T>
+static void logDetBatched(bsp_solver* s, const T* const* ptrs, T* out, int32_t batch) {
+  if (batch <= 0) throw std::runtime_error("logDet: the batch is empty (batch = " + std::to_string(batch) + ")");
+  if (ptrs == nullptr) throw std::runtime_error("logDet: the array of factor pointers is NULL");
+  std::vector<T*> v(batch);
+  for (int32_t q = 0; q < batch; q++) v[q] = const_cast<T*>(ptrs[q]);
+  s->solver->logDet(v, out);
+}
+int bsp_log_det_batched_f64(bsp_solver* s, const double* const* f, double* out, int32_t batch) {
+  BSP_TRY
+  logDetBatched(s, f, out, batch);
+  BSP_CATCH
+}
+int bsp_log_det_batched_f32(bsp_solver* s, const float* const* f, float* out, int32_t batch) {
+  BSP_TRY
+  logDetBatched(s, f, out, batch);
+  BSP_CATCH
+}
+int bsp_pattern_grad_f64(bsp_solver* s, const double* z, const double* zs, const double* u, const double* v,
+                         int64_t stride, int32_t nrhs, double alpha, double* out) {
+  BSP_TRY
+  s->solver->patternGrad(z, zs, u, v, stride, nrhs, alpha, out);
+  BSP_CATCH
+}
+int bsp_pattern_grad_f32(bsp_solver* s, const float* z, const float* zs, const float* u, const float* v,
+                         int64_t stride, int32_t nrhs, float alpha, float* out) {
+  BSP_TRY
+  s->solver->patternGrad(z, zs, u, v, stride, nrhs, alpha, out);
+  BSP_CATCH
+}
+template <typename T>
+static void patternGradBatched(bsp_solver* s, const T* const* z, const T* zs, const T* const* u,
+                               const T* const* v, int64_t stride, int32_t nrhs, T alpha, T* const* out,
+                               int32_t batch) {
+  if (batch <= 0) throw std::runtime_error("patternGrad: the batch is empty (batch = " + std::to_string(batch) + ")");
+  if (out == nullptr) throw std::runtime_error("patternGrad: the array of output pointers is NULL");
+  if ((u == nullptr) != (v == nullptr)) throw std::runtime_error("patternGrad: U and V must be given together");
+  const auto vec = [batch](const T* const* p) {
+    std::vector<T*> r;
+    if (p) for (int32_t q = 0; q < batch; q++) r.push_back(const_cast<T*>(p[q]));
+    return r;
+  };
+  s->solver->patternGrad(vec(z), zs, vec(u), vec(v), stride, nrhs, alpha, std::vector<T*>(out, out + batch));
+}
+int bsp_pattern_grad_batched_f64(bsp_solver* s, const double* const* z, const double* zs,
+                                 const double* const* u, const double* const* v, int64_t stride, int32_t nrhs,
+                                 double alpha, double* const* out, int32_t batch) {
+  BSP_TRY
+  patternGradBatched(s, z, zs, u, v, stride, nrhs, alpha, out, batch);
+  BSP_CATCH
+}
+int bsp_pattern_grad_batched_f32(bsp_solver* s, const float* const* z, const float* zs,
+                                 const float* const* u, const float* const* v, int64_t stride, int32_t nrhs,
+                                 float alpha, float* const* out, int32_t batch) {
+  BSP_TRY
+  patternGradBatched(s, z, zs, u, v, stride, nrhs, alpha, out, batch);
+  BSP_CATCH
+}
 int bsp_test_set_selinv_batch_chunk(bsp_solver* s, int32_t max_matrices) {
   BSP_TRY
   if (max_matrices < 0) throw std::runtime_error("bsp_test_set_selinv_batch_chunk: max_matrices < 0");

@@ -103,6 +103,29 @@ void hipBackendSelectedInverse(SymbolicCtx& sym, const std::vector<T*>& data);
 // TESTING: at most `maxMatrices` matrices per chunk of a batched selected inversion (0: no cap)
 void hipBackendSetSelInvBatchChunk(SymbolicCtx& sym, int64_t maxMatrices);
 
+// Gradients on the pattern of L (hip_grad_kernels.h), on the execution stream.
+// logDet: out[q] = 2 sum_i log L_ii of the complete factor factors[q], q < batch (out: device array).
+// single = true: one matrix, factors[0] used directly (no pointer array on the device).
+template <typename T>
+void hipBackendLogDet(SymbolicCtx& sym, const T* const* factors, int64_t batch, bool single, T* out);
+// patternGrad of `batch` matrices: z / u / v / out are host arrays of device pointers (z NULL: no Z term,
+// zScale then unused; u and v NULL: no rank-2k term).  zScale: device array of `batch` scales.
+template <typename T>
+struct HipGradArgs {
+  int64_t batch = 1;
+  bool single = true;
+  const T* const* z = nullptr;
+  const T* zScale = nullptr;
+  const T* const* u = nullptr;
+  const T* const* v = nullptr;
+  int64_t ld = 0;
+  int nRHS = 0;
+  T alpha = T(0);
+  T* const* out = nullptr;
+};
+template <typename T>
+void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a);
+
 HipPlanStats hipBackendPlanStats(SymbolicCtx& sym, int64_t startLump, int64_t upToLump);
 
 }  // namespace BaSpaCho

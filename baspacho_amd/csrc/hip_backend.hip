@@ -20,6 +20,7 @@
 #include "hip_sweep_mfma.h"
 #include "hip_tail_kernel.h"
 #include "hip_selinv_kernels.h"
+#include "hip_grad_kernels.h"
 #include "mat_ops.h"
 
 namespace BaSpaCho {
@@ -457,6 +458,66 @@ struct FlagOff {
 };
 
 // selected-inversion plan (hip_plan.h, SelInvPlanHost) on the device, with its scratch
+// work lists of the gradient kernels (hip_grad_kernels.h), built once per structure: the patternGrad
+// tiles of every lump column and, for logDet's first pass, the lump of the first diagonal element of
+// every workgroup.  `part` holds logDet's partial sums, nParts per matrix of a chunk.
+struct GradDev {
+  DevBuf tiles, firstLump, part;
+  int64_t nTiles = 0, nParts = 0, partSlices = 0;
+  void build(const CoalescedBlockMatrixSkel& sk) {
+    vector<hipk::GradTile> tl;
+    const int64_t nLumps = sk.numLumps();
+    for (int64_t l = 0; l < nLumps; l++) {
+      const int64_t w = sk.lumpStart[l + 1] - sk.lumpStart[l];
+      const int64_t cBeg = sk.chainColPtr[l], cEnd = sk.chainColPtr[l + 1];
+      const int64_t R = sk.chainRowsTillEnd[cEnd - 1], base = sk.chainData[cBeg];
+      for (int64_t c0 = 0; c0 < w; c0 += hipk::kGradCols) {
+        const int64_t nc = std::min<int64_t>(hipk::kGradCols, w - c0);
+        const int64_t trMax = std::min<int64_t>(hipk::kGradRows, std::max<int64_t>(1, hipk::kGradElems / nc));
+        int64_t chain = cBeg;
+        for (int64_t r0 = 0; r0 < R; r0 += trMax) {
+          const int64_t nr = std::min(trMax, R - r0);
+          while (sk.chainRowsTillEnd[chain] <= r0) chain++;
+          int64_t last = chain;
+          while (sk.chainRowsTillEnd[last] < r0 + nr) last++;
+          hipk::GradTile t{};
+          t.off = base + r0 * w + c0;
+          t.lump = (int32_t)l;
+          t.r0 = (int32_t)r0;
+          t.c0 = (int32_t)c0;
+          t.nr = (int32_t)nr;
+          t.nc = (int32_t)nc;
+          t.chain = (int32_t)chain;
+          t.chainEnd = (int32_t)(last + 1);
+          tl.push_back(t);
+        }
+      }
+    }
+    nTiles = (int64_t)tl.size();
+    tiles.upload(tl);
+    const int64_t n = sk.order();
+    nParts = (n + hipk::kLogDetChunk - 1) / hipk::kLogDetChunk;
+    vector<int32_t> fl;
+    int64_t l = 0;
+    for (int64_t b = 0; b < nParts; b++) {
+      while (sk.lumpStart[l + 1] <= b * hipk::kLogDetChunk) l++;
+      fl.push_back((int32_t)l);
+    }
+    fl.push_back((int32_t)std::max<int64_t>(nLumps - 1, 0));
+    firstLump.upload(fl);
+  }
+  // room for the partial sums of n matrices.  Growing waits for the kernels queued by earlier calls
+  // (they may still use the old buffer); a warm solver does not grow again
+  void reservePart(int64_t n) {
+    if (n <= partSlices) return;
+    if (partSlices > 0) hipCHECK(hipDeviceSynchronize());
+    partSlices = 0;
+    part.release();
+    part.resize((size_t)std::max<int64_t>(nParts * n, 1) * sizeof(double));
+    partSlices = n;
+  }
+};
+
 struct SelInvDev {
   SelInvPlanHost host;
   DevBuf smalls, nodes, tiles, zTasks, rowChain, rowLocal, pairOff, pairStr;
@@ -568,6 +629,7 @@ struct HipSymbolicCtx : SymbolicCtx {
   void releaseDeviceState() {
     plans.clear();
     selinv.reset();
+    grad.reset();
     for (hipEvent_t e : events) (void)hipEventDestroy(e);
     events.clear();
     nextEvent = 0;
@@ -744,6 +806,72 @@ struct HipSymbolicCtx : SymbolicCtx {
     T* const* many = (T* const*)ptrRing.push(data.data(), data.size() * sizeof(T*), stream);
     for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
       selInvLevels<T>(d, {nullptr, many + q0}, (unsigned)std::min(chunk, batch - q0));
+    }
+    hipCHECK(hipGetLastError());
+  }
+
+  // ---- gradients on the pattern of L (hip_grad_kernels.h) -------------------
+  GradDev& gradPlan() {
+    if (!grad) {
+      std::unique_ptr<GradDev> p(new GradDev);
+      p->build(skel);
+      grad = std::move(p);
+    }
+    return *grad;
+  }
+
+  // logDet of `batch` factors: two launches per chunk of at most 65535 matrices (gridDim.y), the
+  // partial sums of a chunk in GradDev::part
+  template <typename T>
+  void logDet(const T* const* factors, int64_t batch, bool single, T* out) {
+    checkDevice();
+    GradDev& g = gradPlan();
+    const hipk::SkelDev sk = skelDev();
+    const int64_t chunk = std::min<int64_t>(batch, 65535);
+    g.reservePart(chunk);
+    const T* const* many =
+        single ? nullptr : (const T* const*)ptrRing.push(factors, batch * sizeof(T*), stream);
+    double* part = reinterpret_cast<double*>(g.part.ptr);
+    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
+      const unsigned nm = (unsigned)std::min(chunk, batch - q0);
+      const hipk::DataRef<const T> ref{single ? factors[0] : nullptr, single ? nullptr : many + q0};
+      if (g.nParts > 0) {
+        hipk::logDetPartial<T><<<dim3((unsigned)g.nParts, nm), 256, 0, stream>>>(
+            sk, g.firstLump.as<int32_t>(), skel.order(), (int)g.nParts, ref, part);
+      }
+      hipk::logDetFinal<T><<<dim3(1, nm), 256, 0, stream>>>(part, (int)g.nParts, out + q0);
+    }
+    hipCHECK(hipGetLastError());
+  }
+
+  // patternGrad of a.batch matrices: one launch of every tile per chunk of at most 65535 matrices
+  template <typename T>
+  void patternGrad(const HipGradArgs<T>& a) {
+    checkDevice();
+    GradDev& g = gradPlan();
+    const hipk::SkelDev sk = skelDev();
+    if (g.nTiles == 0) return;
+    const int64_t batch = a.batch, chunk = std::min<int64_t>(batch, 65535);
+    const bool hasZ = a.z != nullptr, hasUV = a.u != nullptr;
+    const size_t bytes = batch * sizeof(T*);
+    const T* const* zMany = (hasZ && !a.single) ? (const T* const*)ptrRing.push(a.z, bytes, stream) : nullptr;
+    const T* const* uMany = (hasUV && !a.single) ? (const T* const*)ptrRing.push(a.u, bytes, stream) : nullptr;
+    const T* const* vMany = (hasUV && !a.single) ? (const T* const*)ptrRing.push(a.v, bytes, stream) : nullptr;
+    T* const* oMany = a.single ? nullptr : (T* const*)ptrRing.push(a.out, bytes, stream);
+    const int k = hasUV ? a.nRHS : 0;
+    const int kc = std::min(k, hipk::kGradK);
+    const size_t lds = k > 0 ? (size_t)(hipk::kGradRows + hipk::kGradCols) * (kc + 1) * 2 * sizeof(T) : 0;
+    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
+      const unsigned nm = (unsigned)std::min(chunk, batch - q0);
+      const auto ref = [&](const T* const* host, const T* const* dev) {
+        if (host == nullptr) return hipk::DataRef<const T>{nullptr, nullptr};
+        return a.single ? hipk::DataRef<const T>{host[0], nullptr} : hipk::DataRef<const T>{nullptr, dev + q0};
+      };
+      const hipk::DataRef<T> oref =
+          a.single ? hipk::DataRef<T>{a.out[0], nullptr} : hipk::DataRef<T>{nullptr, oMany + q0};
+      hipk::patternGradTiles<T><<<dim3((unsigned)g.nTiles, nm), 256, lds, stream>>>(
+          g.tiles.as<hipk::GradTile>(), sk, ref(a.z, zMany), hasZ ? a.zScale + q0 : nullptr,
+          ref(a.u, uMany), ref(a.v, vMany), a.ld, k, a.alpha, oref);
     }
     hipCHECK(hipGetLastError());
   }
@@ -1021,6 +1149,7 @@ struct HipSymbolicCtx : SymbolicCtx {
       dChainData, dChainRowsTillEnd, dBoardColPtr, dBoardChainColOrd, dPermutation;
   std::map<std::tuple<int, int64_t, int64_t>, std::unique_ptr<DevPlan>> plans;
   std::unique_ptr<SelInvDev> selinv;  // selected-inversion plan, built on first use
+  std::unique_ptr<GradDev> grad;      // work lists of logDet / patternGrad, built on first use
   int64_t selInvChunkCap = 0;          // TESTING: most matrices per selected-inversion chunk (0: no cap)
 };
 
@@ -2625,5 +2754,23 @@ void hipBackendSetSelInvBatchChunk(SymbolicCtx& sym, int64_t maxMatrices) {
   BASPACHO_CHECK_GE(maxMatrices, 0);
   h->selInvChunkCap = maxMatrices;
 }
+
+template <typename T>
+void hipBackendLogDet(SymbolicCtx& sym, const T* const* factors, int64_t batch, bool single, T* out) {
+  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
+  BASPACHO_CHECK_NOTNULL(h);
+  h->logDet(factors, batch, single, out);
+}
+template void hipBackendLogDet<double>(SymbolicCtx&, const double* const*, int64_t, bool, double*);
+template void hipBackendLogDet<float>(SymbolicCtx&, const float* const*, int64_t, bool, float*);
+
+template <typename T>
+void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a) {
+  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
+  BASPACHO_CHECK_NOTNULL(h);
+  h->patternGrad(a);
+}
+template void hipBackendPatternGrad<double>(SymbolicCtx&, const HipGradArgs<double>&);
+template void hipBackendPatternGrad<float>(SymbolicCtx&, const HipGradArgs<float>&);
 
 }  // namespace BaSpaCho

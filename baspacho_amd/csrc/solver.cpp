@@ -529,6 +529,130 @@ template void Solver::selectedInverse<float>(float*) const;
 template void Solver::selectedInverse<std::vector<double*>>(std::vector<double*>*) const;
 template void Solver::selectedInverse<std::vector<float*>>(std::vector<float*>*) const;
 
+// ---- gradients on the pattern of L -------------------------------------------------------------
+static void checkCompleteFactor(const char* what, int64_t canFactorUpTo, int64_t numSpans) {
+  if (canFactorUpTo < numSpans) {
+    throw std::runtime_error(std::string(what) + ": this Solver can only factor up to span " +
+                             std::to_string(canFactorUpTo) +
+                             " (fill added for the given elimination ranges only); it needs a complete factor");
+  }
+}
+
+template <typename T>
+void Solver::logDet(const T* factor, T* devOut) const {
+  if (factor == nullptr) throw std::runtime_error("logDet: the factor pointer is NULL");
+  if (devOut == nullptr) throw std::runtime_error("logDet: the output pointer is NULL");
+  checkCompleteFactor("logDet", canFactorUpTo, factorSkel.numSpans());
+  hipBackendLogDet<T>(*symCtx, &factor, 1, true, devOut);
+}
+
+template <typename T>
+void Solver::logDet(const std::vector<T*>& factors, T* devOut) const {
+  if (factors.empty()) throw std::runtime_error("logDet: the batch is empty");
+  for (size_t q = 0; q < factors.size(); q++) {
+    if (factors[q] == nullptr) {
+      throw std::runtime_error("logDet: the factor pointer of batch member " + std::to_string(q) + " is NULL");
+    }
+  }
+  if (devOut == nullptr) throw std::runtime_error("logDet: the output pointer is NULL");
+  checkCompleteFactor("logDet", canFactorUpTo, factorSkel.numSpans());
+  std::vector<const T*> c(factors.begin(), factors.end());
+  hipBackendLogDet<T>(*symCtx, c.data(), (int64_t)c.size(), false, devOut);
+}
+
+// the arguments of patternGrad, checked before any device work (single call: batch 1)
+template <typename T>
+static void checkPatternGrad(size_t batch, const std::vector<T*>& Z, const T* zScale,
+                             const std::vector<T*>& U, const std::vector<T*>& V, int64_t stride,
+                             int nRHS, const std::vector<T*>& out, int64_t order) {
+  const auto members = [batch](const char* name, const std::vector<T*>& v) {
+    if (v.size() != batch) {
+      throw std::runtime_error(std::string("patternGrad: ") + name + " has " + std::to_string(v.size()) +
+                               " pointers for a batch of " + std::to_string(batch));
+    }
+    for (size_t q = 0; q < v.size(); q++) {
+      if (v[q] == nullptr) {
+        throw std::runtime_error(std::string("patternGrad: the ") + name + " pointer of batch member " +
+                                 std::to_string(q) + " is NULL");
+      }
+    }
+  };
+  if (batch == 0) throw std::runtime_error("patternGrad: the batch is empty");
+  members("out", out);
+  if (Z.empty() && U.empty() && V.empty()) {
+    throw std::runtime_error("patternGrad: neither Z nor U / V given (nothing to compute)");
+  }
+  if (!Z.empty()) {
+    members("Z", Z);
+    if (zScale == nullptr) throw std::runtime_error("patternGrad: Z given without its device scale (NULL)");
+  }
+  if (U.empty() != V.empty()) throw std::runtime_error("patternGrad: U and V must be given together");
+  if (!U.empty()) {
+    members("U", U);
+    members("V", V);
+    if (nRHS < 1) throw std::runtime_error("patternGrad: nRHS = " + std::to_string(nRHS) + " < 1");
+    if (stride < order) {
+      throw std::runtime_error("patternGrad: stride " + std::to_string(stride) + " < order " +
+                               std::to_string(order));
+    }
+  }
+}
+
+template <typename T>
+static void runPatternGrad(SymbolicCtx& sym, bool single, const std::vector<T*>& Z, const T* zScale,
+                           const std::vector<T*>& U, const std::vector<T*>& V, int64_t stride, int nRHS,
+                           T alpha, const std::vector<T*>& out) {
+  std::vector<const T*> z(Z.begin(), Z.end()), u(U.begin(), U.end()), v(V.begin(), V.end());
+  HipGradArgs<T> a;
+  a.batch = (int64_t)out.size();
+  a.single = single;
+  a.z = z.empty() ? nullptr : z.data();
+  a.zScale = zScale;
+  a.u = u.empty() ? nullptr : u.data();
+  a.v = v.empty() ? nullptr : v.data();
+  a.ld = stride;
+  a.nRHS = u.empty() ? 0 : nRHS;
+  a.alpha = alpha;
+  a.out = out.data();
+  hipBackendPatternGrad<T>(sym, a);
+}
+
+template <typename T>
+void Solver::patternGrad(const T* Z, const T* zScale, const T* U, const T* V, int64_t stride, int nRHS,
+                         T alpha, T* out) const {
+  if (out == nullptr) throw std::runtime_error("patternGrad: the output pointer is NULL");
+  if ((U == nullptr) != (V == nullptr)) throw std::runtime_error("patternGrad: U and V must be given together");
+  const auto one = [](const T* p) { return p ? std::vector<T*>{const_cast<T*>(p)} : std::vector<T*>{}; };
+  const std::vector<T*> z = one(Z), u = one(U), v = one(V), o{out};
+  checkPatternGrad(1, z, zScale, u, v, stride, nRHS, o, order());
+  checkCompleteFactor("patternGrad", canFactorUpTo, factorSkel.numSpans());
+  runPatternGrad(*symCtx, true, z, zScale, u, v, stride, nRHS, alpha, o);
+}
+
+template <typename T>
+void Solver::patternGrad(const std::vector<T*>& Z, const T* zScale, const std::vector<T*>& U,
+                         const std::vector<T*>& V, int64_t stride, int nRHS, T alpha,
+                         const std::vector<T*>& out) const {
+  checkPatternGrad(out.size(), Z, zScale, U, V, stride, nRHS, out, order());
+  checkCompleteFactor("patternGrad", canFactorUpTo, factorSkel.numSpans());
+  runPatternGrad(*symCtx, false, Z, zScale, U, V, stride, nRHS, alpha, out);
+}
+
+template void Solver::logDet<double>(const double*, double*) const;
+template void Solver::logDet<float>(const float*, float*) const;
+template void Solver::logDet<double>(const std::vector<double*>&, double*) const;
+template void Solver::logDet<float>(const std::vector<float*>&, float*) const;
+template void Solver::patternGrad<double>(const double*, const double*, const double*, const double*, int64_t,
+                                          int, double, double*) const;
+template void Solver::patternGrad<float>(const float*, const float*, const float*, const float*, int64_t, int,
+                                         float, float*) const;
+template void Solver::patternGrad<double>(const std::vector<double*>&, const double*,
+                                          const std::vector<double*>&, const std::vector<double*>&, int64_t,
+                                          int, double, const std::vector<double*>&) const;
+template void Solver::patternGrad<float>(const std::vector<float*>&, const float*, const std::vector<float*>&,
+                                         const std::vector<float*>&, int64_t, int, float,
+                                         const std::vector<float*>&) const;
+
 #define BSP_INSTANTIATE(T)                                                                     \
   template void Solver::factor<T>(T*, bool) const;                                             \
   template void Solver::factorUpTo<T>(T*, int64_t, bool) const;                                \

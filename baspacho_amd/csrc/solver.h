@@ -82,6 +82,33 @@ class Solver {
   template <typename T>
   void selectedInverse(T* data) const;
 
+  // extension: gradients on the block pattern of L (hip_grad_kernels.h).  Data
+  // is this Solver's numeric layout, vectors are in its internal order (as for solve()); A(d) is the
+  // symmetric matrix with A_ij = A_ji = d_e for every stored element e = (i, j), i >= j (the
+  // strictly-upper elements of the diagonal blocks are not read).  Both run on the stream of
+  // setStream(), without host synchronisation, and refuse a Solver that cannot factor completely.
+  //
+  // logDet: devOut[0] = log det A = 2 sum_i log L_ii of a complete factor() (fp64 accumulation; a
+  // non-positive or NaN pivot gives -inf or NaN).  Batch form: devOut[q] for factors[q].
+  template <typename T>
+  void logDet(const T* factor, T* devOut) const;
+  template <typename T>
+  void logDet(const std::vector<T*>& factors, T* devOut) const;
+  // patternGrad: writes, for every stored element e = (i, j) (out is never read),
+  //   i > j: out_e = zScale[0] 2 Z_e + alpha sum_k (U_ik V_jk + V_ik U_jk)
+  //   i = j: out_e = zScale[0] Z_e   + alpha sum_k U_ik V_ik
+  //   strictly-upper elements of the diagonal blocks: out_e = 0
+  // Z (e.g. the output of selectedInverse) NULL: no Z term (zScale unused).  U and V (n x nRHS,
+  // column-major, leading dimension `stride`) both NULL: no rank-2k term; else nRHS >= 1.  zScale is a
+  // DEVICE value.  Batch form: element q of each vector (Z and U / V may be empty vectors), zScale[q].
+  template <typename T>
+  void patternGrad(const T* Z, const T* zScale, const T* U, const T* V, int64_t stride, int nRHS, T alpha,
+                   T* out) const;
+  template <typename T>
+  void patternGrad(const std::vector<T*>& Z, const T* zScale, const std::vector<T*>& U,
+                   const std::vector<T*>& V, int64_t stride, int nRHS, T alpha,
+                   const std::vector<T*>& out) const;
+
   int64_t order() const { return factorSkel.order(); }
   int64_t dataSize() const { return factorSkel.dataSize(); }
   int64_t canFactorUpToSpan() const { return canFactorUpTo; }

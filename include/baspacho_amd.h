@@ -242,6 +242,42 @@ int bsp_selected_inverse_f32(bsp_solver* s, float* dev_data);
    device work, bsp_last_error() says why. */
 int bsp_selected_inverse_batched_f64(bsp_solver* s, double* const* dev_ptrs, int32_t batch);
 int bsp_selected_inverse_batched_f32(bsp_solver* s, float* const* dev_ptrs, int32_t batch);
+/* Extension (no counterpart in the reference): gradients on the block pattern of L, for autograd
+   (DESIGN.md section 13).  Data is this solver's numeric layout and vectors are in its internal order,
+   as for bsp_solve_*.  A(d) is the symmetric matrix with A_ij = A_ji = d_e for every stored element
+   e = (i, j): all elements of the off-diagonal chain blocks and i >= j inside the diagonal blocks (the
+   strictly-upper elements of the diagonal blocks are not read).  All of them run on the bsp_set_stream
+   stream without host synchronisation (the first call builds the work lists); results are bitwise
+   reproducible and batch member q is bitwise the single call.  A solver that cannot factor completely
+   (AddFillForGivenElims), an empty batch, a NULL pointer or nrhs < 1: non-zero return before any
+   device work, bsp_last_error() says why.
+   bsp_log_det_*: dev_out[0] = log det A = 2 sum_i log L_ii of a complete factor() (accumulated in fp64
+   for both types; a non-positive or NaN pivot gives -inf or NaN, it does not fail).  The batched form
+   writes dev_out[q] for dev_factors[q] (a HOST array of device pointers), q < batch. */
+int bsp_log_det_f64(bsp_solver* s, const double* dev_factor, double* dev_out);
+int bsp_log_det_f32(bsp_solver* s, const float* dev_factor, float* dev_out);
+int bsp_log_det_batched_f64(bsp_solver* s, const double* const* dev_factors, double* dev_out, int32_t batch);
+int bsp_log_det_batched_f32(bsp_solver* s, const float* const* dev_factors, float* dev_out, int32_t batch);
+/* bsp_pattern_grad_*: a write-only pass (dev_out is never read) over every stored element e = (i, j):
+     i > j:  out_e = s 2 Z_e + alpha sum_k (U_ik V_jk + V_ik U_jk)
+     i = j:  out_e = s Z_e   + alpha sum_k U_ik V_ik
+     strictly-upper elements of the diagonal blocks:  out_e = 0
+   with s = dev_z_scale[0], a DEVICE value.  dev_z NULL: no Z term (dev_z_scale unused); dev_u and
+   dev_v NULL together: no rank-2k term (nrhs unused), else U, V are order x nrhs column-major with
+   leading dimension `stride` (>= order) and nrhs >= 1.  One of the two terms must be given.  Solve's
+   backward: U = A^-1 g_x, V = x, alpha = -1; logdet's backward: Z = bsp_selected_inverse_* of the
+   factor, s = the incoming gradient.  The batched form takes HOST arrays of `batch` device pointers
+   (dev_z / dev_u / dev_v may be NULL as above) and dev_z_scale[q] for member q. */
+int bsp_pattern_grad_f64(bsp_solver* s, const double* dev_z, const double* dev_z_scale, const double* dev_u,
+                         const double* dev_v, int64_t stride, int32_t nrhs, double alpha, double* dev_out);
+int bsp_pattern_grad_f32(bsp_solver* s, const float* dev_z, const float* dev_z_scale, const float* dev_u,
+                         const float* dev_v, int64_t stride, int32_t nrhs, float alpha, float* dev_out);
+int bsp_pattern_grad_batched_f64(bsp_solver* s, const double* const* dev_z, const double* dev_z_scale,
+                                 const double* const* dev_u, const double* const* dev_v, int64_t stride,
+                                 int32_t nrhs, double alpha, double* const* dev_out, int32_t batch);
+int bsp_pattern_grad_batched_f32(bsp_solver* s, const float* const* dev_z, const float* dev_z_scale,
+                                 const float* const* dev_u, const float* const* dev_v, int64_t stride,
+                                 int32_t nrhs, float alpha, float* const* dev_out, int32_t batch);
 /* Solver::solve<std::vector<T*>> etc. (Solver.h:64-73 with the batch types of MatOps.h:38-42):
    `batch` factored matrices of the same structure and one block of right-hand sides each
    (host arrays of device pointers).  which: 0 = solve, 1 = solveL, 2 = solveLt */
