@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["Settings", "Solver", "create_solver", "SparseStructure", "BackendHip", "BackendCuda",
+__all__ = ["Settings", "Solver", "Assembly", "create_solver", "SparseStructure", "BackendHip", "BackendCuda",
            "BackendRef", "BackendFast", "AddFillComplete", "AddFillForAutoElims",
            "AddFillForGivenElims", "AddFillNone"]
 
@@ -633,6 +633,19 @@ class Solver:
             self._h, one(zs), zsp, one(us), one(vs), ctypes.c_int64(stride), ctypes.c_int32(nRHS),
             real(alpha), one(outs)))
 
+    # ---- assembly of coordinate entries -----------------------------
+    def assembly(self, rows, cols, triangle="lower"):
+        """extension: the map from coordinate entries (rows[k], cols[k]) in the caller's scalar order to
+        this solver's layout (bsp_assembly_create), built once on the host.  triangle "lower": every
+        entry has row >= col; "full": entries with row < col are skipped.  See Assembly."""
+        return Assembly(self, rows, cols, triangle)
+
+    def scalarPermutation(self):
+        """extension: int64 array p of length order(), p[i_user] = i_internal (bsp_scalar_permutation)"""
+        out = np.empty(self.order(), dtype=np.int64)
+        _check(self._lib.bsp_scalar_permutation(self._h, out.ctypes.data_as(_I64P)))
+        return out
+
     # ---- measurement --------------------------------------------------------------------
     def factorFlops(self):
         return float(self._lib.bsp_factor_flops(self._h))
@@ -723,6 +736,103 @@ class Solver:
         idx = np.concatenate([d0[i] + np.arange(w[i]) * (w[i] + 1) for i in range(len(w))])
         data[idx] = data[idx] * (1 + alpha) + beta
         return data
+
+
+_TRIANGLES = {"lower": 0, "full": 1}
+
+
+def _host_indices(a, name):
+    """int64 numpy copy of an index array (numpy, sequence or torch tensor on any device)"""
+    if hasattr(a, "detach"):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.ndim != 1:
+        raise ValueError("assembly: %s must be one-dimensional, got shape %s" % (name, a.shape))
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise TypeError("assembly: %s must hold integers, got %s" % (name, a.dtype))
+    return _i64(a)
+
+
+class Assembly:
+    """extension: the host map from coordinate entries (rows[k], cols[k]) in the
+    caller's scalar order to a Solver's numeric layout, and the device kernels that use it.  Built by
+    Solver.assembly(); keeps its solver alive.  A_ij = A_ji = sum of the values of the entries at
+    (i, j), i >= j; duplicates are summed in ascending entry index (bitwise np.add.at).  The first
+    assemble / adjoint call uploads the map to the device; both run on the solver's stream without
+    synchronising."""
+
+    def __init__(self, solver, rows, cols, triangle="lower"):
+        if triangle not in _TRIANGLES:
+            raise ValueError("assembly: triangle must be 'lower' or 'full', got %r" % (triangle,))
+        self._lib = solver._lib
+        self._h = None
+        r, c = _host_indices(rows, "rows"), _host_indices(cols, "cols")
+        if len(r) != len(c):
+            raise ValueError("assembly: %d rows for %d cols" % (len(r), len(c)))
+        h = ctypes.c_void_p()
+        _check(self._lib.bsp_assembly_create(solver._h, ctypes.c_int64(len(r)), r.ctypes.data_as(_I64P),
+                                             c.ctypes.data_as(_I64P), ctypes.c_int32(_TRIANGLES[triangle]),
+                                             ctypes.byref(h)))
+        self._h = h
+        self.solver = solver
+        self.nnz = len(r)
+        self.triangle = triangle
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.bsp_assembly_destroy(h)
+
+    def entryOffsets(self):
+        """int64 array [nnz]: the layout offset of every entry, -1 for a skipped one"""
+        out = np.empty(self.nnz, dtype=np.int64)
+        _check(self._lib.bsp_assembly_entry_offsets(self._h, out.ctypes.data_as(_I64P)))
+        return out
+
+    def info(self):
+        """figures of the map (bsp_assembly_info)"""
+        out = (ctypes.c_int64 * 7)()
+        _check(self._lib.bsp_assembly_info(self._h, out))
+        keys = ["nnz", "kept", "elements", "max_run", "long_runs", "tiles", "device_bytes"]
+        return dict(zip(keys, [int(x) for x in out]))
+
+    def _run(self, name, x, n_in, n_out, out, adjoint):
+        import torch
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("%s: expected a torch.Tensor, got %s" % (name, type(x).__name__))
+        if x.dim() not in (1, 2) or x.shape[-1] != n_in:
+            raise ValueError("%s: expected [%d] or [B, %d], got shape %s" % (name, n_in, n_in, tuple(x.shape)))
+        if x.dim() == 2 and x.shape[0] == 0:
+            raise ValueError("%s: empty batch" % name)
+        sfx = _suffix(x)
+        shape = x.shape[:-1] + (n_out,)
+        if out is None:
+            out = torch.empty(shape, dtype=x.dtype, device=x.device)
+        elif out.shape != shape or out.dtype != x.dtype or out.device != x.device:
+            raise ValueError("%s: out must be %s %s on %s, got %s %s on %s" % (
+                name, tuple(shape), x.dtype, x.device, tuple(out.shape), out.dtype, out.device))
+        _ptr_of(x), _ptr_of(out)  # device memory, contiguous
+        fn = "bsp_assemble_adjoint_" if adjoint else "bsp_assemble_"
+        if x.dim() == 2:
+            B_ = x.shape[0]
+            ins = (ctypes.c_void_p * B_)(*[x[q].data_ptr() for q in range(B_)])
+            outs = (ctypes.c_void_p * B_)(*[out[q].data_ptr() for q in range(B_)])
+            _check(getattr(self._lib, fn + "batched_" + sfx)(self.solver._h, self._h, ins, outs,
+                                                            ctypes.c_int32(B_)))
+        else:
+            _check(getattr(self._lib, fn + sfx)(self.solver._h, self._h, ctypes.c_void_p(x.data_ptr()),
+                                               ctypes.c_void_p(out.data_ptr())))
+        return out
+
+    def assemble(self, values, out=None):
+        """values [nnz] or [B, nnz] (device, float64 / float32) -> the layout [dataSize] / [B, dataSize]:
+        every element written, 0 where no entry maps (bsp_assemble_*)"""
+        return self._run("assemble", values, self.nnz, self.solver.dataSize(), out, False)
+
+    def adjoint(self, gradData, out=None):
+        """gradData [dataSize] or [B, dataSize] -> [nnz] / [B, nnz]: gradData[entryOffsets()], 0 for
+        skipped entries (bsp_assemble_adjoint_*)"""
+        return self._run("adjoint", gradData, self.solver.dataSize(), self.nnz, out, True)
 
 
 def probe_mfma_f64_tflops():

@@ -9,6 +9,7 @@
 #include <unordered_map>
 #include <unordered_set>
 
+#include "assembly.h"
 #include "bal_pipeline.h"
 #include "../../include/baspacho_amd_testing.h"
 #include "computation_model.h"
@@ -539,6 +540,107 @@ int bsp_pattern_grad_batched_f32(bsp_solver* s, const float* const* z, const flo
                                  float alpha, float* const* out, int32_t batch) {
   BSP_TRY
   patternGradBatched(s, z, zs, u, v, stride, nrhs, alpha, out, batch);
+  BSP_CATCH
+}
+struct bsp_assembly {
+  std::unique_ptr<AssemblyMap> map;
+};
+
+int bsp_assembly_create(bsp_solver* s, int64_t nnz, const int64_t* rows, const int64_t* cols, int32_t triangle,
+                        bsp_assembly** out) {
+  BSP_TRY
+  if (s == nullptr || out == nullptr) throw std::runtime_error("bsp_assembly_create: NULL solver or output");
+  std::unique_ptr<bsp_assembly> a(new bsp_assembly);
+  a->map = createAssemblyMap(*s->solver, nnz, rows, cols, triangle);
+  *out = a.release();
+  BSP_CATCH
+}
+void bsp_assembly_destroy(bsp_assembly* a) { delete a; }
+int bsp_assembly_entry_offsets(const bsp_assembly* a, int64_t* out) {
+  BSP_TRY
+  if (a == nullptr) throw std::runtime_error("bsp_assembly_entry_offsets: the assembly is NULL");
+  if (a->map->nnz > 0 && out == nullptr) throw std::runtime_error("bsp_assembly_entry_offsets: out is NULL");
+  std::copy(a->map->entryOff.begin(), a->map->entryOff.end(), out);
+  BSP_CATCH
+}
+int bsp_assembly_info(const bsp_assembly* a, int64_t out[7]) {
+  BSP_TRY
+  if (a == nullptr || out == nullptr) throw std::runtime_error("bsp_assembly_info: NULL argument");
+  const AssemblyMap& m = *a->map;
+  const int64_t v[7] = {m.nnz, m.numKept(), (int64_t)m.dest.size(), m.maxRun, (int64_t)m.longDest.size(),
+                        m.numTiles, m.deviceBytes()};
+  std::copy(v, v + 7, out);
+  BSP_CATCH
+}
+static const AssemblyMap& assemblyOf(const bsp_assembly* a) {
+  if (a == nullptr) throw std::runtime_error("assemble: the assembly is NULL");
+  return *a->map;
+}
+template <typename T>
+static void assembleBatched(bsp_solver* s, const bsp_assembly* a, const T* const* in, T* const* out,
+                            int32_t batch, bool adjoint) {
+  const char* what = adjoint ? "assembleAdjoint" : "assemble";
+  if (batch <= 0) {
+    throw std::runtime_error(std::string(what) + ": the batch is empty (batch = " + std::to_string(batch) + ")");
+  }
+  if (in == nullptr || out == nullptr) throw std::runtime_error(std::string(what) + ": an array of pointers is NULL");
+  const std::vector<const T*> i(in, in + batch);
+  const std::vector<T*> o(out, out + batch);
+  if (adjoint) {
+    s->solver->assembleAdjoint(assemblyOf(a), i, o);
+  } else {
+    s->solver->assemble(assemblyOf(a), i, o);
+  }
+}
+int bsp_assemble_f64(bsp_solver* s, const bsp_assembly* a, const double* v, double* d) {
+  BSP_TRY
+  s->solver->assemble(assemblyOf(a), v, d);
+  BSP_CATCH
+}
+int bsp_assemble_f32(bsp_solver* s, const bsp_assembly* a, const float* v, float* d) {
+  BSP_TRY
+  s->solver->assemble(assemblyOf(a), v, d);
+  BSP_CATCH
+}
+int bsp_assemble_batched_f64(bsp_solver* s, const bsp_assembly* a, const double* const* v, double* const* d,
+                             int32_t batch) {
+  BSP_TRY
+  assembleBatched(s, a, v, d, batch, false);
+  BSP_CATCH
+}
+int bsp_assemble_batched_f32(bsp_solver* s, const bsp_assembly* a, const float* const* v, float* const* d,
+                             int32_t batch) {
+  BSP_TRY
+  assembleBatched(s, a, v, d, batch, false);
+  BSP_CATCH
+}
+int bsp_assemble_adjoint_f64(bsp_solver* s, const bsp_assembly* a, const double* g, double* gv) {
+  BSP_TRY
+  s->solver->assembleAdjoint(assemblyOf(a), g, gv);
+  BSP_CATCH
+}
+int bsp_assemble_adjoint_f32(bsp_solver* s, const bsp_assembly* a, const float* g, float* gv) {
+  BSP_TRY
+  s->solver->assembleAdjoint(assemblyOf(a), g, gv);
+  BSP_CATCH
+}
+int bsp_assemble_adjoint_batched_f64(bsp_solver* s, const bsp_assembly* a, const double* const* g,
+                                     double* const* gv, int32_t batch) {
+  BSP_TRY
+  assembleBatched(s, a, g, gv, batch, true);
+  BSP_CATCH
+}
+int bsp_assemble_adjoint_batched_f32(bsp_solver* s, const bsp_assembly* a, const float* const* g,
+                                     float* const* gv, int32_t batch) {
+  BSP_TRY
+  assembleBatched(s, a, g, gv, batch, true);
+  BSP_CATCH
+}
+int bsp_scalar_permutation(const bsp_solver* s, int64_t* out) {
+  BSP_TRY
+  if (out == nullptr) throw std::runtime_error("bsp_scalar_permutation: out is NULL");
+  const std::vector<int64_t> p = s->solver->scalarPermutation();
+  std::copy(p.begin(), p.end(), out);
   BSP_CATCH
 }
 int bsp_test_set_selinv_batch_chunk(bsp_solver* s, int32_t max_matrices) {

@@ -126,6 +126,18 @@ struct HipGradArgs {
 template <typename T>
 void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a);
 
+// Assembly of coordinate entries into the layout (hip_assembly_kernels.h), on
+// the execution stream.  `in` / `out` are host arrays of `batch` device pointers (single = true: one
+// matrix, in[0] / out[0] used directly).  The map is uploaded on the first call and kept in map.dev.
+// assemble: in = values (nnz each), out = data (dataSize each); adjoint: in = gradients of the data,
+// out = gradients of the values.
+struct AssemblyMap;
+struct HipAssemblyDev;
+template <typename T>
+void hipBackendAssemble(SymbolicCtx& sym, const AssemblyMap& map, const T* const* in, T* const* out,
+                        int64_t batch, bool single, bool adjoint);
+void hipBackendFreeAssembly(HipAssemblyDev* dev);
+
 HipPlanStats hipBackendPlanStats(SymbolicCtx& sym, int64_t startLump, int64_t upToLump);
 
 }  // namespace BaSpaCho

@@ -21,6 +21,7 @@
 #include "hip_tail_kernel.h"
 #include "hip_selinv_kernels.h"
 #include "hip_grad_kernels.h"
+#include "hip_assembly_kernels.h"
 #include "mat_ops.h"
 
 namespace BaSpaCho {
@@ -66,6 +67,24 @@ struct DevBuf {
   template <typename U>
   const U* as() const { return reinterpret_cast<const U*>(ptr); }
 };
+
+}  // namespace
+
+// an assembly map on the device (assembly.h), owned by its AssemblyMap
+struct HipAssemblyDev {
+  DevBuf entryOff, tileFirst, tileLongFirst, runStart, runEntry, destLocal, longDest;
+  void upload(const AssemblyMap& m) {
+    entryOff.upload(m.entryOff);
+    tileFirst.upload(m.tileFirst);
+    tileLongFirst.upload(m.tileLongFirst);
+    runStart.upload(m.runStart);
+    runEntry.upload(m.runEntry);
+    destLocal.upload(m.destLocal);
+    longDest.upload(m.longDest);
+  }
+};
+
+namespace {
 
 // block solves through inverted diagonal blocks (denseLevels): per level list of a plan, the panels
 // whose diagonal blocks are inverted (built and uploaded on the first solve)
@@ -811,6 +830,41 @@ struct HipSymbolicCtx : SymbolicCtx {
   }
 
   // ---- gradients on the pattern of L (hip_grad_kernels.h) -------------------
+  // ---- assembly of coordinate entries (hip_assembly_kernels.h) ---------------
+  // assemble (or its adjoint) of `batch` matrices: one launch per chunk of at most 65535 matrices
+  template <typename T>
+  void assemble(const AssemblyMap& m, const T* const* in, T* const* out, int64_t batch, bool single,
+                bool adjoint) {
+    checkDevice();
+    if (m.dev == nullptr) {
+      std::unique_ptr<HipAssemblyDev> d(new HipAssemblyDev);
+      d->upload(m);
+      m.dev = d.release();
+    }
+    const HipAssemblyDev& d = *m.dev;
+    if (adjoint && m.nnz == 0) return;
+    const int64_t chunk = std::min<int64_t>(batch, 65535);
+    const size_t bytes = batch * sizeof(T*);
+    const T* const* inMany = single ? nullptr : (const T* const*)ptrRing.push(in, bytes, stream);
+    T* const* outMany = single ? nullptr : (T* const*)ptrRing.push(out, bytes, stream);
+    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
+      const unsigned nm = (unsigned)std::min(chunk, batch - q0);
+      const hipk::DataRef<const T> iref =
+          single ? hipk::DataRef<const T>{in[0], nullptr} : hipk::DataRef<const T>{nullptr, inMany + q0};
+      const hipk::DataRef<T> oref = single ? hipk::DataRef<T>{out[0], nullptr} : hipk::DataRef<T>{nullptr, outMany + q0};
+      if (adjoint) {
+        const int64_t per = hipk::kAsmThreads * hipk::kAsmAdjPer;
+        hipk::assembleAdjointEntries<T><<<dim3((unsigned)((m.nnz + per - 1) / per), nm), hipk::kAsmThreads, 0,
+                                           stream>>>(m.nnz, d.entryOff.as<int64_t>(), iref, oref);
+      } else {
+        hipk::assembleTiles<T><<<dim3((unsigned)m.numTiles, nm), hipk::kAsmThreads, 0, stream>>>(
+            m.dataSize, d.tileFirst.as<int32_t>(), d.tileLongFirst.as<int32_t>(), d.runStart.as<int32_t>(),
+            d.runEntry.as<int32_t>(), d.destLocal.as<uint16_t>(), d.longDest.as<int32_t>(), iref, oref);
+      }
+    }
+    hipCHECK(hipGetLastError());
+  }
+
   GradDev& gradPlan() {
     if (!grad) {
       std::unique_ptr<GradDev> p(new GradDev);
@@ -2772,5 +2826,19 @@ void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a) {
 }
 template void hipBackendPatternGrad<double>(SymbolicCtx&, const HipGradArgs<double>&);
 template void hipBackendPatternGrad<float>(SymbolicCtx&, const HipGradArgs<float>&);
+
+template <typename T>
+void hipBackendAssemble(SymbolicCtx& sym, const AssemblyMap& map, const T* const* in, T* const* out,
+                        int64_t batch, bool single, bool adjoint) {
+  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
+  BASPACHO_CHECK_NOTNULL(h);
+  h->assemble(map, in, out, batch, single, adjoint);
+}
+template void hipBackendAssemble<double>(SymbolicCtx&, const AssemblyMap&, const double* const*, double* const*,
+                                         int64_t, bool, bool);
+template void hipBackendAssemble<float>(SymbolicCtx&, const AssemblyMap&, const float* const*, float* const*,
+                                        int64_t, bool, bool);
+
+void hipBackendFreeAssembly(HipAssemblyDev* dev) { delete dev; }
 
 }  // namespace BaSpaCho

@@ -12,6 +12,7 @@
 #include <chrono>
 #include <cstdlib>
 
+#include "assembly.h"
 #include "computation_model.h"
 #include "elimination_tree.h"
 #include "hip_backend.h"
@@ -652,6 +653,80 @@ template void Solver::patternGrad<double>(const std::vector<double*>&, const dou
 template void Solver::patternGrad<float>(const std::vector<float*>&, const float*, const std::vector<float*>&,
                                          const std::vector<float*>&, int64_t, int, float,
                                          const std::vector<float*>&) const;
+
+// ---- assembly of coordinate entries -----------------------------------------------------------
+std::vector<int64_t> Solver::scalarPermutation() const {
+  const std::vector<int64_t>& spanStart = factorSkel.spanStart;
+  std::vector<int64_t> out;
+  out.reserve(order());
+  for (int64_t sp : permutation) {
+    for (int64_t i = spanStart[sp]; i < spanStart[sp + 1]; i++) out.push_back(i);
+  }
+  return out;
+}
+
+// checks the arguments before any device work, then runs the batch.  `vals` is the nnz-sized side
+// (values forward, gradValues backward), `lay` the dataSize-sized one
+template <typename T>
+static void runAssembly(const char* what, const Solver* self, SymbolicCtx& sym, const AssemblyMap& map,
+                        const std::vector<const T*>& in, const std::vector<T*>& out, bool single, bool adjoint) {
+  const auto fail = [what](const std::string& m) { throw std::runtime_error(std::string(what) + ": " + m); };
+  if (map.solver != self) fail("the assembly was built on another solver");
+  if (in.empty()) fail("the batch is empty");
+  if (in.size() != out.size()) {
+    fail("the batch has " + std::to_string(in.size()) + " inputs and " + std::to_string(out.size()) + " outputs");
+  }
+  const char* inName = adjoint ? "gradient-of-data" : "values";
+  const char* outName = adjoint ? "gradient-of-values" : "data";
+  // with nnz = 0 the nnz-sized side is never touched and may be NULL
+  const bool inOptional = !adjoint && map.nnz == 0, outOptional = adjoint && map.nnz == 0;
+  std::unordered_set<const T*> seen;
+  for (size_t q = 0; q < in.size(); q++) {
+    if (in[q] == nullptr && !inOptional) {
+      fail(std::string("the ") + inName + " pointer of batch member " + std::to_string(q) + " is NULL");
+    }
+    if (out[q] == nullptr) {
+      if (outOptional) continue;
+      fail(std::string("the ") + outName + " pointer of batch member " + std::to_string(q) + " is NULL");
+    }
+    if (!seen.insert(out[q]).second) {
+      fail(std::string("the ") + outName + " pointer of batch member " + std::to_string(q) +
+           " repeats an earlier member's");
+    }
+  }
+  hipBackendAssemble<T>(sym, map, in.data(), out.data(), (int64_t)in.size(), single, adjoint);
+}
+
+template <typename T>
+void Solver::assemble(const AssemblyMap& map, const T* values, T* data) const {
+  runAssembly<T>("assemble", this, *symCtx, map, {values}, {data}, true, false);
+}
+template <typename T>
+void Solver::assemble(const AssemblyMap& map, const std::vector<const T*>& values,
+                      const std::vector<T*>& data) const {
+  runAssembly<T>("assemble", this, *symCtx, map, values, data, false, false);
+}
+template <typename T>
+void Solver::assembleAdjoint(const AssemblyMap& map, const T* gradData, T* gradValues) const {
+  runAssembly<T>("assembleAdjoint", this, *symCtx, map, {gradData}, {gradValues}, true, true);
+}
+template <typename T>
+void Solver::assembleAdjoint(const AssemblyMap& map, const std::vector<const T*>& gradData,
+                             const std::vector<T*>& gradValues) const {
+  runAssembly<T>("assembleAdjoint", this, *symCtx, map, gradData, gradValues, false, true);
+}
+template void Solver::assemble<double>(const AssemblyMap&, const double*, double*) const;
+template void Solver::assemble<float>(const AssemblyMap&, const float*, float*) const;
+template void Solver::assemble<double>(const AssemblyMap&, const std::vector<const double*>&,
+                                       const std::vector<double*>&) const;
+template void Solver::assemble<float>(const AssemblyMap&, const std::vector<const float*>&,
+                                      const std::vector<float*>&) const;
+template void Solver::assembleAdjoint<double>(const AssemblyMap&, const double*, double*) const;
+template void Solver::assembleAdjoint<float>(const AssemblyMap&, const float*, float*) const;
+template void Solver::assembleAdjoint<double>(const AssemblyMap&, const std::vector<const double*>&,
+                                              const std::vector<double*>&) const;
+template void Solver::assembleAdjoint<float>(const AssemblyMap&, const std::vector<const float*>&,
+                                             const std::vector<float*>&) const;
 
 #define BSP_INSTANTIATE(T)                                                                     \
   template void Solver::factor<T>(T*, bool) const;                                             \

@@ -16,6 +16,8 @@
 
 namespace BaSpaCho {
 
+struct AssemblyMap;
+
 class Solver {
  public:
   // from a RAW factor skeleton (normally use createSolver)
@@ -108,6 +110,27 @@ class Solver {
   void patternGrad(const std::vector<T*>& Z, const T* zScale, const std::vector<T*>& U,
                    const std::vector<T*>& V, int64_t stride, int nRHS, T alpha,
                    const std::vector<T*>& out) const;
+
+  // extension: assembly of coordinate entries (row, col, value) into this Solver's layout (DESIGN.md
+  // section 14; assembly.h).  `map` comes from createAssemblyMap(*this, ...).  assemble writes every
+  // element of `data` (never read): the sum, in ascending entry index from +0, of the values of the
+  // entries mapped to it, and 0 where none is.  assembleAdjoint: gradValues[k] = gradData[entryOff[k]],
+  // 0 for skipped entries.  Both run on the stream of setStream() without host synchronisation (the
+  // first call uploads the map).  Batch forms: member q of each vector, bitwise the single call.  A map
+  // of another Solver, an empty batch, a NULL pointer (the nnz-sized side may be NULL when nnz = 0) or
+  // a repeated output pointer are refused before any device work.
+  template <typename T>
+  void assemble(const AssemblyMap& map, const T* values, T* data) const;
+  template <typename T>
+  void assemble(const AssemblyMap& map, const std::vector<const T*>& values, const std::vector<T*>& data) const;
+  template <typename T>
+  void assembleAdjoint(const AssemblyMap& map, const T* gradData, T* gradValues) const;
+  template <typename T>
+  void assembleAdjoint(const AssemblyMap& map, const std::vector<const T*>& gradData,
+                       const std::vector<T*>& gradValues) const;
+  // scalarPermutation()[i] = internal index of the caller's scalar i (params in param order, each
+  // at the start of its span)
+  std::vector<int64_t> scalarPermutation() const;
 
   int64_t order() const { return factorSkel.order(); }
   int64_t dataSize() const { return factorSkel.dataSize(); }

@@ -278,6 +278,60 @@ int bsp_pattern_grad_batched_f64(bsp_solver* s, const double* const* dev_z, cons
 int bsp_pattern_grad_batched_f32(bsp_solver* s, const float* const* dev_z, const float* dev_z_scale,
                                  const float* const* dev_u, const float* const* dev_v, int64_t stride,
                                  int32_t nrhs, float alpha, float* const* dev_out, int32_t batch);
+/* Extension (no counterpart in the reference): assembly of a symmetric matrix given as coordinate
+   entries (rows[k], cols[k], values[k]) in the caller's scalar order into this solver's layout, and its
+   adjoint.
+   - Scalar index i belongs to param p at local position r, from the prefix sums of the param sizes in
+     param order.  Indices are int64 in [0, order); 0 <= nnz < 2^31 (nnz = 0: a zero matrix).
+   - triangle BSP_TRIANGLE_LOWER: every entry must have row >= col.  BSP_TRIANGLE_FULL: entries with
+     row < col are skipped (never read, gradient 0); the caller asserts the matrix is symmetric.  In
+     both modes A_ij = A_ji = sum of the values of the entries at (i, j), i >= j.
+   - Every kept entry must land on a stored element of the factor (an original block or fill-in): the
+     stored lower element, through the permuted block's `flipped` flag (bsp_block_offset) and
+     (r, c) -> (c, r) inside a diagonal block.  Anything else makes bsp_assembly_create fail;
+     bsp_last_error() names the first offending entry index and its (row, col).
+   bsp_assembly_create builds the map once on the host (no device work); the first assemble or adjoint
+   call uploads it, and it stays on the device until bsp_assembly_destroy.  An assembly belongs to the
+   solver it was built on and must be destroyed before that solver. */
+#define BSP_TRIANGLE_LOWER 0
+#define BSP_TRIANGLE_FULL 1
+typedef struct bsp_assembly bsp_assembly;
+int bsp_assembly_create(bsp_solver* s, int64_t nnz, const int64_t* rows, const int64_t* cols, int32_t triangle,
+                        bsp_assembly** out);
+void bsp_assembly_destroy(bsp_assembly* a);
+/* host copy of the map: out[k] = layout offset of entry k, -1 for a skipped entry (nnz values) */
+int bsp_assembly_entry_offsets(const bsp_assembly* a, int64_t* out);
+/* figures of the map: out[0] nnz, [1] kept entries, [2] distinct elements written by entries, [3] most
+   entries summed into one element, [4] elements summed by a whole wave (runs > 64), [5] tiles of the
+   assemble kernel, [6] device bytes of the map once uploaded */
+int bsp_assembly_info(const bsp_assembly* a, int64_t out[7]);
+/* bsp_assemble_*: writes EVERY element of dev_data (its previous contents never matter): the sum of the
+   values of the entries mapped to it, in ascending entry index in the value type starting from +0
+   (bitwise np.add.at(zeros(dataSize), offsets, values)), and 0 where no entry maps (fill-in, the
+   strictly-upper elements of the diagonal blocks).  bsp_assemble_adjoint_*: dev_grad_values[k] =
+   dev_grad_data[offset[k]], 0 for skipped entries; with section 13's convention for the gradient of the
+   data this is the exact gradient of the entry values, the same for every duplicate.  Both run on the
+   bsp_set_stream stream without host synchronisation, with no atomics; results are bitwise
+   reproducible and batch member q (HOST arrays of `batch` device pointers) is bitwise the single call.
+   An empty batch, a NULL array or member (the nnz-sized side may be NULL when nnz = 0), a repeated
+   output pointer or an assembly built on another solver: non-zero return before any device work. */
+int bsp_assemble_f64(bsp_solver* s, const bsp_assembly* a, const double* dev_values, double* dev_data);
+int bsp_assemble_f32(bsp_solver* s, const bsp_assembly* a, const float* dev_values, float* dev_data);
+int bsp_assemble_batched_f64(bsp_solver* s, const bsp_assembly* a, const double* const* dev_values,
+                             double* const* dev_data, int32_t batch);
+int bsp_assemble_batched_f32(bsp_solver* s, const bsp_assembly* a, const float* const* dev_values,
+                             float* const* dev_data, int32_t batch);
+int bsp_assemble_adjoint_f64(bsp_solver* s, const bsp_assembly* a, const double* dev_grad_data,
+                             double* dev_grad_values);
+int bsp_assemble_adjoint_f32(bsp_solver* s, const bsp_assembly* a, const float* dev_grad_data,
+                             float* dev_grad_values);
+int bsp_assemble_adjoint_batched_f64(bsp_solver* s, const bsp_assembly* a, const double* const* dev_grad_data,
+                                     double* const* dev_grad_values, int32_t batch);
+int bsp_assemble_adjoint_batched_f32(bsp_solver* s, const bsp_assembly* a, const float* const* dev_grad_data,
+                                     float* const* dev_grad_values, int32_t batch);
+/* out[i_user] = i_internal (order values): the caller's scalar i in the solver's internal vector order
+   (param p at spanStart[paramToSpan[p]], its scalars in order) */
+int bsp_scalar_permutation(const bsp_solver* s, int64_t* out);
 /* Solver::solve<std::vector<T*>> etc. (Solver.h:64-73 with the batch types of MatOps.h:38-42):
    `batch` factored matrices of the same structure and one block of right-hand sides each
    (host arrays of device pointers).  which: 0 = solve, 1 = solveL, 2 = solveLt */
