@@ -12,17 +12,26 @@ then damp(0, 1.2*order) (1.3 for batches), warm-up factors, timed factors on dev
   range {0, numPts}.  The BAL file is not available offline: the structure comes from the committed
   synthetic generator (baspacho_amd/testing.py: gen_bal_synthetic, 871 cameras / 527480 points /
   2.79 M observations) unless --bal-file PATH supplies a real one (loader: baspacho_amd/bal.py).
-  Extra workloads measured in the same run and reported inside the same JSON line: "batched" =
-  BASELINE configs[3] (64 x GRID 82x82 x 3, one batched factor() per step) and "c5" = BAL-1723
-  shaped fp32 factor + fp64 iterative refinement (configs[4]).
 --gpus N > 1 (torchrun, one process per GPU; or plain `python bench.py --gpus N`, which spawns its
   ranks): the SAME headline metric, one BAL-871 matrix per GPU -- a single factorisation is not
   sharded (no exchange step: replicas), "scaling": "weak", value = N matrices' flops / max-over-ranks
-  time.  The batched config of BASELINE's metric ("batch throughput at 1/2/4/8 GPUs") rides along in
-  "batched" at every N: rank 0 runs the symbolic analysis, broadcasts the flat plan over RCCL, the 64
-  matrices are sharded contiguously (no collective inside a factorisation), "scaling": "strong";
-  "batched_1gpu" = rank 0 alone factoring all 64 in the same job (the 1-GPU point of that curve).
+  time.
   `--workload grid82 --batch 64` makes the batched config the headline line instead.
+
+A plain run does only what the headline needs: set-up, warm-up, timed steps, --dump-outputs, the line.
+--full adds, to the same line, what else the bench measures and checks (each leg can be left out
+again with its --no-* option):
+  - the vector residual probe of the last timed factor against the CPU checker, plan statistics and
+    the symbolic analysis time;
+  - per-kernel-class times and the roofline of the dominant class (--no-profile);
+  - device solve() with 1 and 10 right-hand sides on the last factor;
+  - extra workloads (--no-extras; default workload only): "batched" = BASELINE configs[3] (64 x GRID
+    82x82 x 3, one batched factor() per step), at N > 1 sharded over the ranks: rank 0 runs the
+    symbolic analysis, broadcasts the flat plan over RCCL, the 64 matrices are sharded contiguously
+    (no collective inside a factorisation), "scaling": "strong", and "batched_1gpu" = rank 0 alone
+    factoring all 64 in the same job (the 1-GPU point of that curve); at N = 1 also "c5" = BAL-1723
+    shaped fp32 factor + fp64 iterative refinement (configs[4]) and the vendor comparators;
+  - the CPU baseline at N = 1 (--no-cpu-baseline).
 
 Prints ONE JSON line on rank 0.
 """
@@ -825,9 +834,13 @@ def main():
                     help="total number of identical-structure matrices (sharded over the GPUs); "
                          "0 = one matrix per GPU, each its own factor() (replicas)")
     ap.add_argument("--bal-file", default=None, help="BAL text file for the bal871 workload")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else the bench reports: "
+                         "residual probe, plan, kernel profile and roofline, solves, extra workloads, "
+                         "CPU baseline (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: leave out the kernel profile")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out the extra workloads")
     ap.add_argument("--suite", default=None, choices=["ref"],
                     help="ref: the reference's benchmark families (Bench.cpp:290-409): factor, solve-1, "
                          "solve-10 per problem, JSON lines to stdout, one summary line at the end")
@@ -878,8 +891,8 @@ def main():
         return suite_ref(args, device)
 
     # the headline line is the SAME metric at every N: BAL-871, one matrix per GPU (a single
-    # factorisation is not sharded: replicas, weak scaling); the batched config rides along in
-    # "batched" at every N (64 matrices sharded over the N GPUs: strong scaling)
+    # factorisation is not sharded: replicas, weak scaling); with --full the batched config rides
+    # along in "batched" at every N (64 matrices sharded over the N GPUs: strong scaling)
     workload = args.workload or "bal871"
     batch = 0 if args.batch is None else args.batch
     batched = batch > 0
@@ -913,12 +926,12 @@ def main():
     if "rank_ms_per_step" in res:   # N > 1: every rank's own time + what the plan broadcast cost
         out["rank_ms_per_step"] = res["rank_ms_per_step"]
         out["scaling_note"] = ("`metric` / `value` = one BAL-871 factorisation per GPU (replicas, weak scaling: no "
-                               "exchange step exists inside a factorisation, x N by construction); the metric's "
-                               "batched half -- 64 matrices sharded over the GPUs, STRONG scaling -- is at the top "
+                               "exchange step exists inside a factorisation, x N by construction); with --full the "
+                               "metric's batched half -- 64 matrices sharded over the GPUs, STRONG scaling -- is at the top "
                                "level as `batched_metric` / `batched_value` / `batched_strong_efficiency`, its "
                                "1-GPU point measured in this job is `batched_1gpu`")
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- parity at full size: vector residual probe of the last timed factor ---------------
         out["residual_probe"] = residual_probe(sol, main_run.hosts[0], main_run.last)
         out["residual_probe_kind"] = "vector probe ||L(L^T x) - A x|| / ||A x||, 2 random x (not the Frobenius norm)"
@@ -957,7 +970,7 @@ def main():
             out["solve1_ms"] = "error: %s" % e
 
     # ---- extra workloads (every rank takes part in the collective ones) ------------------------
-    if not args.no_extras and args.workload is None and args.batch is None and not args.bal_file:
+    if args.full and not args.no_extras and args.workload is None and args.batch is None and not args.bal_file:
         # the headline workload's device buffers go first, and torch's cached blocks with them: a
         # batch carved out of the cached 1.1 GB blocks ran 20 % slower than one in fresh allocations
         # (tools/exp_order.py)
@@ -1038,7 +1051,7 @@ def main():
             out["batched_strong_efficiency"] = round(sp / world, 3)
     if rank == 0:
         # ---- CPU baseline: the BackendFast restatement (oracle/blas_factor.c) on host cores ----
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(sol, main_run.hosts[0], main_run.flops,
                                                    out["value"] / total_batch,

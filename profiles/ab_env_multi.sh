@@ -5,7 +5,7 @@ for wl in "flat50k:--workload flat50k --steps 5" "grid82:--workload grid82 --ste
   name=${wl%%:*}; args=${wl#*:}
   for rep in $(seq $reps); do
     for envs in "" "$@"; do
-      env $envs python bench.py $args --no-extras --no-cpu-baseline --no-profile 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name', '[${envs:-default}]', d['ms_per_step'], d['residual_probe'])"
+      env $envs python bench.py --full $args --no-extras --no-cpu-baseline --no-profile 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name', '[${envs:-default}]', d['ms_per_step'], d['residual_probe'])"
     done
   done
 done

@@ -6,7 +6,7 @@ for wl in "grid82:--workload grid82 --steps 50" "grid82x8:--workload grid82 --ba
   for rep in $(seq $reps); do
     for lib in "" $*; do
       if [ -n "$lib" ]; then export BSP_LIB_PATH=$GRAFT_REPO_ROOT/baspacho_amd/lib$lib.so; else unset BSP_LIB_PATH; fi
-      python bench.py $args --no-extras --no-cpu-baseline --no-profile 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name', '${lib:-new}', d['ms_per_step'], d['residual_probe'])"
+      python bench.py --full $args --no-extras --no-cpu-baseline --no-profile 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name', '${lib:-new}', d['ms_per_step'], d['residual_probe'])"
     done
   done
 done

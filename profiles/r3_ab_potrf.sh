@@ -2,7 +2,7 @@ cd $GRAFT_REPO_ROOT
 for rep in 1 2; do
 for lib in "" _oldpotrf; do
   export BSP_LIB_PATH=$GRAFT_REPO_ROOT/baspacho_amd/libbaspacho_amd$lib.so
-  python bench.py --no-extras --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --no-extras --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('bal871 ${lib:-blocked} %.3f ms' % d['ms_per_step'], d['kernel_ms'])"
 done
 done
