@@ -7,6 +7,27 @@ import numpy as np
 import baspacho_amd as B
 from baspacho_amd import testing as T
 from helpers import dense_lower_chol, lower_of, spd_data, to_dev
+from known_factor import known_factor_data, vec_to_cols
+
+KNOWN_FACTOR_MAX_ORDER = 2500  # (dense float64 references of the known-factor pass)
+
+
+def known_factor_pass(sol, seed, dtype, nb=1, nrhs=1, desc=None):
+    """the factor of `nb` known-factor matrices (tests/known_factor.py) on the same solver, and a solve
+    with the first, checked at tolerances scaled to the working precision: on spd_data the updates are
+    too small against the factor for the fixed tolerances above to see a lost or rounded one"""
+    n = sol.order()
+    if n > KNOWN_FACTOR_MAX_ORDER:
+        return
+    kfs = [known_factor_data(sol, 7919 * seed + q, dtype) for q in range(nb)]
+    devs = [to_dev(k.data) for k in kfs]
+    sol.factor(devs if nb > 1 else devs[0])
+    for q in range(nb):
+        kfs[q].check_factor(devs[q].cpu().numpy(), ("known-factor factor", q, desc))
+    b = np.random.default_rng(seed).standard_normal((n, nrhs)).astype(dtype).astype(np.float64)
+    v = to_dev(b.T.ravel().astype(dtype))
+    sol.solve(devs[0], v, n, nrhs)
+    kfs[0].check_solve(b, vec_to_cols(v.cpu().numpy(), n, nrhs), "A", ("known-factor solve", desc))
 
 
 def run_case(seed, big=False):
@@ -108,14 +129,13 @@ def run_case(seed, big=False):
         got = lower_of(sol, d2.cpu().numpy())
         err = np.linalg.norm(got - L) / np.linalg.norm(L)
         assert err < tol, ("partial", span, err, desc)
+    known_factor_pass(sol, seed, dtype, nb, nrhs, desc)
     return desc
 
 
-def run_width_case(W, tail, dtype=np.float64):
-    """a dense lump of width W (spans of 8, a ragged last one), optionally followed by a second lump of
-    `tail` columns that most of its spans see; returns the relative error of the device factor
-    against numpy.  tools/sweep_widths.py walks every W; tests/test_stress_gpu.py a slice around the
-    panel (64) and outer-block (256) boundaries."""
+def width_solver(W, tail, hip_options=None):
+    """the structure of run_width_case: a dense lump of width W (spans of 8, a ragged last one),
+    optionally followed by a second lump of `tail` columns that most of its spans see"""
     sizes = [8] * (W // 8) + ([W % 8] if W % 8 else [])
     n0 = len(sizes)
     sizes = sizes + [7] * (tail // 7)
@@ -123,8 +143,16 @@ def run_width_case(W, tail, dtype=np.float64):
     cols = [list(range(c, n0)) + [q for q in range(n0, nparam) if (q + c) % 4 != 0] for c in range(n0)]
     cols += [list(range(c, nparam)) for c in range(n0, nparam)]
     ss = T.columns_to_structure(cols)
-    st = B.Settings(findSparseEliminationRanges=False)
-    sol = B.create_solver(st, np.asarray(sizes, dtype=np.int64), ss, [])
+    st = B.Settings(findSparseEliminationRanges=False, hipOptions=hip_options)
+    return B.create_solver(st, np.asarray(sizes, dtype=np.int64), ss, [])
+
+
+def run_width_case(W, tail, dtype=np.float64):
+    """a dense lump of width W (spans of 8, a ragged last one), optionally followed by a second lump of
+    `tail` columns that most of its spans see; returns the relative error of the device factor
+    against numpy.  tools/sweep_widths.py walks every W; tests/test_stress_gpu.py a slice around the
+    panel (64) and outer-block (256) boundaries."""
+    sol = width_solver(W, tail)
     d = spd_data(sol, 5 + W, dtype=dtype)
     dev = to_dev(d)
     sol.factor(dev)
@@ -138,6 +166,7 @@ def run_width_case(W, tail, dtype=np.float64):
     sol.solve(dev, v, n, 1)
     X = np.linalg.solve(A, rhs.astype(np.float64))
     serr = np.linalg.norm(v.cpu().numpy().astype(np.float64) - X) / np.linalg.norm(X)
+    known_factor_pass(sol, W, dtype, desc=("width", W, tail))
     return max(err, serr * (1e-2 if dtype == np.float64 else 1e-1))
 
 
@@ -184,4 +213,5 @@ def run_family_case(seed):
     X = np.linalg.solve(A, rhs.astype(np.float64))
     err = np.linalg.norm(v.cpu().numpy().astype(np.float64) - X) / np.linalg.norm(X)
     assert err < tol * 50, ("solve", err, desc)
+    known_factor_pass(sol, seed, dtype, desc=desc)
     return desc
