@@ -633,6 +633,71 @@ class Solver:
             self._h, one(zs), zsp, one(us), one(vs), ctypes.c_int64(stride), ctypes.c_int32(nRHS),
             real(alpha), one(outs)))
 
+    def patternOuter(self, out, U, V, nRHS=1, alpha=1.0, stride=None):
+        """extension: the non-symmetric rank-k projection on the pattern of L (bsp_pattern_outer_*).
+        For every stored element e = (i, j) of `out` (never read): i >= j: alpha sum_k U_ik V_jk;
+        strictly-upper elements of the diagonal blocks: 0.  U, V column-major order x nRHS with leading
+        dimension `stride` (default order()), e.g. tensors [nRHS, order].  `out` a list/tuple = a batch:
+        U, V lists of the same length."""
+        batched = isinstance(out, (list, tuple))
+        outs, us, vs = (list(out), list(U), list(V)) if batched else ([out], [U], [V])
+        if len(outs) == 0:
+            raise ValueError("patternOuter: empty batch")
+        if len(us) != len(outs) or len(vs) != len(outs):
+            raise ValueError("patternOuter: U / V have %d / %d members for a batch of %d"
+                             % (len(us), len(vs), len(outs)))
+        if stride is None:
+            stride = self.order()
+        dt = outs[0].dtype
+        for t in outs + us + vs:
+            if t.dtype != dt:
+                raise TypeError("patternOuter: every tensor must have the dtype of out (%s), got %s" % (dt, t.dtype))
+        for t in outs:
+            self._check_data(t)
+        sfx = _suffix(outs[0])
+        real = ctypes.c_double if sfx == "f64" else ctypes.c_float
+        if batched:
+            def arr(xs):
+                return (ctypes.c_void_p * len(xs))(*[_ptr_of(t) for t in xs])
+            _check(getattr(self._lib, "bsp_pattern_outer_batched_" + sfx)(
+                self._h, arr(us), arr(vs), ctypes.c_int64(stride), ctypes.c_int32(nRHS), real(alpha), arr(outs),
+                ctypes.c_int32(len(outs))))
+            return
+        _check(getattr(self._lib, "bsp_pattern_outer_" + sfx)(
+            self._h, ctypes.c_void_p(_ptr_of(us[0])), ctypes.c_void_p(_ptr_of(vs[0])), ctypes.c_int64(stride),
+            ctypes.c_int32(nRHS), real(alpha), ctypes.c_void_p(_ptr_of(outs[0]))))
+
+    def factorAdjoint(self, L, grad):
+        """extension: the reverse-mode sweep of factor(), in place in `grad` (bsp_factor_adjoint_*).
+        `L` holds a complete factor() of A(d) and is only read; `grad` holds df/dL on entry (stored
+        elements with i >= j; the strictly-upper elements of the diagonal blocks are ignored) and df/dd
+        on return: G_ij + G_ji below the diagonal, G_ii on it, 0 above it.
+        Lists/tuples of tensors (one dtype, distinct buffers) = a batch: member q is bitwise the single
+        call."""
+        if isinstance(L, (list, tuple)) != isinstance(grad, (list, tuple)):
+            raise TypeError("factorAdjoint: L and grad must both be tensors or both be lists")
+        if isinstance(L, (list, tuple)):
+            if len(grad) == 0:
+                raise ValueError("factorAdjoint: empty batch")
+            if len(L) != len(grad):
+                raise ValueError("factorAdjoint: %d factors for %d gradients" % (len(L), len(grad)))
+            ts = list(L) + list(grad)
+        else:
+            ts = [L, grad]
+        if len({t.dtype for t in ts}) != 1:
+            raise TypeError("factorAdjoint: every tensor must share one dtype, got %s" % sorted({str(t.dtype) for t in ts}))
+        for t in ts:
+            self._check_data(t)
+        sfx = _suffix(ts[0])
+        if isinstance(L, (list, tuple)):
+            def arr(xs):
+                return (ctypes.c_void_p * len(xs))(*[_ptr_of(t) for t in xs])
+            _check(getattr(self._lib, "bsp_factor_adjoint_batched_" + sfx)(
+                self._h, arr(L), arr(grad), ctypes.c_int32(len(grad))))
+            return
+        _check(getattr(self._lib, "bsp_factor_adjoint_" + sfx)(
+            self._h, ctypes.c_void_p(_ptr_of(L)), ctypes.c_void_p(_ptr_of(grad))))
+
     # ---- assembly of coordinate entries (DESIGN.md section 14) -----------------------------
     def assembly(self, rows, cols, triangle="lower"):
         """extension: the map from coordinate entries (rows[k], cols[k]) in the caller's scalar order to

@@ -18,11 +18,22 @@ log-determinant's gradient is A^-1 on the pattern, from a selected inversion of 
 factor, run only when the log-determinant has a gradient.  All work is enqueued on
 torch.cuda.current_stream(), nothing synchronises with the host, and the solver's own stream is
 restored afterwards.  Double backward is not supported.
+
+Through the factor itself:
+
+    L = BA.cholesky(solver, data)             # the factor, in the same layout
+    y = BA.solve_l(solver, L, b)              # y = L^-1 b
+    x = BA.solve_lt(solver, L, b)             # x = L^-T b, e.g. a sample x = mu + L^-T z
+
+cholesky returns L on the stored elements with i >= j and 0 on the strictly-upper elements of the
+diagonal blocks; its backward is Solver.factorAdjoint on a clone of the incoming gradient (the
+upper elements' gradient is ignored).  The half-solves' backward is one more half-solve and
+Solver.patternOuter: Lbar = -(L^-T g_y) y^T and Lbar = -x (L^-1 g_x)^T, on the elements with i >= j.
 """
 import torch
 from torch.autograd.function import once_differentiable
 
-__all__ = ["solve", "logdet", "solve_logdet"]
+__all__ = ["solve", "logdet", "solve_logdet", "cholesky", "solve_l", "solve_lt"]
 
 
 class _OnCurrentStream:
@@ -223,3 +234,114 @@ def solve_logdet(solver, data, b):
     _check_rhs(solver, data, b, "solve_logdet")
     _check_device(solver, "solve_logdet", data, b)
     return _SolveLogDet.apply(solver, data, b)
+
+
+# ---- through the factor: cholesky, solve_l, solve_lt ----------------------
+def _upper_mask(solver, device):
+    """bool device tensor [dataSize]: the strictly-upper elements of the diagonal blocks (cached)"""
+    cache = solver.__dict__.setdefault("_upper_mask_dev", {})
+    if device not in cache:
+        cache[device] = torch.from_numpy(~solver.lowerMask()).to(device)
+    return cache[device]
+
+
+class _Cholesky(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver, data):
+        with _OnCurrentStream(solver, data.device):
+            L = _factor(solver, data)
+            L.masked_fill_(_upper_mask(solver, data.device), 0)
+        ctx.solver = solver
+        ctx.save_for_backward(L)
+        ctx.set_materialize_grads(False)
+        return L
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_L):
+        if g_L is None or not ctx.needs_input_grad[1]:
+            return None, None
+        (L,) = ctx.saved_tensors
+        solver = ctx.solver
+        with _OnCurrentStream(solver, L.device):
+            grad = g_L.clone(memory_format=torch.contiguous_format)
+            if L.dim() == 2:
+                solver.factorAdjoint(_members(L), _members(grad))
+            else:
+                solver.factorAdjoint(L, grad)
+        return None, grad
+
+
+def _half_solve(solver, name, L, vt):
+    """vt <- L^-1 vt (name "solveL") or L^-T vt ("solveLt") in place ([.., k, n])"""
+    n, k = vt.shape[-1], vt.shape[-2]
+    if L.dim() == 2:
+        getattr(solver, name)(_members(L), _members(vt), stride=n, nRHS=k)
+    else:
+        getattr(solver, name)(L, vt, stride=n, nRHS=k)
+
+
+class _HalfSolve(torch.autograd.Function):
+    """y = L^-1 b (lower = True) or x = L^-T b (lower = False)"""
+
+    @staticmethod
+    def forward(ctx, solver, L, b, lower):
+        batched = L.dim() == 2
+        with _OnCurrentStream(solver, L.device):
+            L = L.detach().contiguous()
+            yt = _to_cols(b.detach(), batched)
+            _half_solve(solver, "solveL" if lower else "solveLt", L, yt)
+        ctx.solver, ctx.lower, ctx.b_shape = solver, lower, b.shape
+        ctx.save_for_backward(L, yt)
+        ctx.set_materialize_grads(False)
+        return _from_cols(yt, b.shape)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_y):
+        if g_y is None:
+            return None, None, None, None
+        solver = ctx.solver
+        L, yt = ctx.saved_tensors
+        batched = L.dim() == 2
+        need_L, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        grad_L = grad_b = None
+        if not (need_L or need_b):
+            return None, None, None, None
+        with _OnCurrentStream(solver, L.device):
+            bt = _to_cols(g_y, batched)  # b's gradient: L^-T g_y (lower) or L^-1 g_x (upper)
+            _half_solve(solver, "solveLt" if ctx.lower else "solveL", L, bt)
+            if need_b:
+                grad_b = _from_cols(bt, ctx.b_shape).clone()
+            if need_L:
+                grad_L = torch.empty_like(L)
+                # Lbar = -bbar y^T (y = L^-1 b) or -x bbar^T (x = L^-T b), on the elements i >= j
+                U, V = (bt, yt) if ctx.lower else (yt, bt)
+                sel = _members if batched else (lambda t: t)
+                solver.patternOuter(sel(grad_L), sel(U), sel(V), nRHS=bt.shape[-2], alpha=-1.0,
+                                    stride=bt.shape[-1])
+        return None, grad_L, grad_b, None
+
+
+def cholesky(solver, data):
+    """the factor L of A(data), in the solver's layout ([dataSize] or [B, dataSize]), differentiable in
+    data.  The strictly-upper elements of the diagonal blocks are 0 and their gradient is ignored."""
+    _check_data(solver, data, "cholesky")
+    _check_device(solver, "cholesky", data)
+    return _Cholesky.apply(solver, data)
+
+
+def solve_l(solver, L, b):
+    """y = L^-1 b for a factor L from cholesky(), differentiable in L and b (b as for solve)"""
+    _check_data(solver, L, "solve_l")
+    _check_rhs(solver, L, b, "solve_l")
+    _check_device(solver, "solve_l", L, b)
+    return _HalfSolve.apply(solver, L, b, True)
+
+
+def solve_lt(solver, L, b):
+    """x = L^-T b for a factor L from cholesky(), differentiable in L and b (b as for solve)"""
+    _check_data(solver, L, "solve_lt")
+    _check_rhs(solver, L, b, "solve_lt")
+    _check_device(solver, "solve_lt", L, b)
+    return _HalfSolve.apply(solver, L, b, False)

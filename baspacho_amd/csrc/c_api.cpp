@@ -542,6 +542,71 @@ int bsp_pattern_grad_batched_f32(bsp_solver* s, const float* const* z, const flo
   patternGradBatched(s, z, zs, u, v, stride, nrhs, alpha, out, batch);
   BSP_CATCH
 }
+template <typename T>
+static std::vector<T*> hostArray(const char* what, const char* name, const T* const* p, int32_t batch) {
+  if (batch <= 0) throw std::runtime_error(std::string(what) + ": the batch is empty (batch = " + std::to_string(batch) + ")");
+  if (p == nullptr) throw std::runtime_error(std::string(what) + ": the array of " + name + " pointers is NULL");
+  std::vector<T*> v(batch);
+  for (int32_t q = 0; q < batch; q++) v[q] = const_cast<T*>(p[q]);
+  return v;
+}
+int bsp_pattern_outer_f64(bsp_solver* s, const double* u, const double* v, int64_t stride, int32_t nrhs,
+                          double alpha, double* out) {
+  BSP_TRY
+  s->solver->patternOuter(u, v, stride, nrhs, alpha, out);
+  BSP_CATCH
+}
+int bsp_pattern_outer_f32(bsp_solver* s, const float* u, const float* v, int64_t stride, int32_t nrhs,
+                          float alpha, float* out) {
+  BSP_TRY
+  s->solver->patternOuter(u, v, stride, nrhs, alpha, out);
+  BSP_CATCH
+}
+template <typename T>
+static void patternOuterBatched(bsp_solver* s, const T* const* u, const T* const* v, int64_t stride, int32_t nrhs,
+                                T alpha, T* const* out, int32_t batch) {
+  const char* what = "patternOuter";
+  const std::vector<T*> o = hostArray(what, "output", out, batch);
+  s->solver->patternOuter(hostArray(what, "U", u, batch), hostArray(what, "V", v, batch), stride, nrhs, alpha, o);
+}
+int bsp_pattern_outer_batched_f64(bsp_solver* s, const double* const* u, const double* const* v, int64_t stride,
+                                  int32_t nrhs, double alpha, double* const* out, int32_t batch) {
+  BSP_TRY
+  patternOuterBatched(s, u, v, stride, nrhs, alpha, out, batch);
+  BSP_CATCH
+}
+int bsp_pattern_outer_batched_f32(bsp_solver* s, const float* const* u, const float* const* v, int64_t stride,
+                                  int32_t nrhs, float alpha, float* const* out, int32_t batch) {
+  BSP_TRY
+  patternOuterBatched(s, u, v, stride, nrhs, alpha, out, batch);
+  BSP_CATCH
+}
+int bsp_factor_adjoint_f64(bsp_solver* s, const double* l, double* grad) {
+  BSP_TRY
+  s->solver->factorAdjoint(l, grad);
+  BSP_CATCH
+}
+int bsp_factor_adjoint_f32(bsp_solver* s, const float* l, float* grad) {
+  BSP_TRY
+  s->solver->factorAdjoint(l, grad);
+  BSP_CATCH
+}
+template <typename T>
+static void factorAdjointBatched(bsp_solver* s, const T* const* l, T* const* grad, int32_t batch) {
+  const char* what = "factorAdjoint";
+  const std::vector<T*> g = hostArray(what, "gradient", grad, batch);
+  s->solver->factorAdjoint(hostArray(what, "factor", l, batch), g);
+}
+int bsp_factor_adjoint_batched_f64(bsp_solver* s, const double* const* l, double* const* grad, int32_t batch) {
+  BSP_TRY
+  factorAdjointBatched(s, l, grad, batch);
+  BSP_CATCH
+}
+int bsp_factor_adjoint_batched_f32(bsp_solver* s, const float* const* l, float* const* grad, int32_t batch) {
+  BSP_TRY
+  factorAdjointBatched(s, l, grad, batch);
+  BSP_CATCH
+}
 struct bsp_assembly {
   std::unique_ptr<AssemblyMap> map;
 };

@@ -122,9 +122,16 @@ struct HipGradArgs {
   int nRHS = 0;
   T alpha = T(0);
   T* const* out = nullptr;
+  bool outer = false;  // patternOuter: out_e = alpha sum_k U_ik V_jk for i >= j (z unused)
 };
 template <typename T>
 void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a);
+// Reverse-mode sweep of the factor (hip_chol_adjoint_kernels.h): grad[q] holds
+// Lbar of the complete factor L[q] and is overwritten by the data gradient; L is only read.  Host
+// arrays of `batch` device pointers (single = true: one matrix, L[0] / grad[0] used directly); the
+// batch runs in memory-bounded chunks, as selected inversion does.
+template <typename T>
+void hipBackendFactorAdjoint(SymbolicCtx& sym, const T* const* L, T* const* grad, int64_t batch, bool single);
 
 // Assembly of coordinate entries into the layout (hip_assembly_kernels.h), on
 // the execution stream.  `in` / `out` are host arrays of `batch` device pointers (single = true: one

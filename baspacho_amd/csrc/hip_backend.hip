@@ -20,6 +20,7 @@
 #include "hip_sweep_mfma.h"
 #include "hip_tail_kernel.h"
 #include "hip_selinv_kernels.h"
+#include "hip_chol_adjoint_kernels.h"
 #include "hip_grad_kernels.h"
 #include "hip_assembly_kernels.h"
 #include "mat_ops.h"
@@ -923,11 +924,92 @@ struct HipSymbolicCtx : SymbolicCtx {
       };
       const hipk::DataRef<T> oref =
           a.single ? hipk::DataRef<T>{a.out[0], nullptr} : hipk::DataRef<T>{nullptr, oMany + q0};
+      if (a.outer) {
+        hipk::patternGradTiles<T, true><<<dim3((unsigned)g.nTiles, nm), 256, lds, stream>>>(
+            g.tiles.as<hipk::GradTile>(), sk, hipk::DataRef<const T>{nullptr, nullptr}, nullptr,
+            ref(a.u, uMany), ref(a.v, vMany), a.ld, k, a.alpha, oref);
+        continue;
+      }
       hipk::patternGradTiles<T><<<dim3((unsigned)g.nTiles, nm), 256, lds, stream>>>(
           g.tiles.as<hipk::GradTile>(), sk, ref(a.z, zMany), hasZ ? a.zScale + q0 : nullptr,
           ref(a.u, uMany), ref(a.v, vMany), a.ld, k, a.alpha, oref);
     }
     hipCHECK(hipGetLastError());
+  }
+
+  // ---- reverse-mode sweep of the factor (hip_chol_adjoint_kernels.h) --------
+  // `batch` factors L[q] (read only) and gradients grad[q] (Lbar in, data gradient out), on the
+  // selected-inversion plan and scratch.  Chunks as in selectedInverse(vector): at most 65535 matrices
+  // (gridDim.y) and what half the free device memory holds in scratch slices, at least 1.
+  template <typename T>
+  void factorAdjoint(const T* const* L, T* const* G, int64_t batch, bool single) {
+    checkDevice();
+    SelInvDev& d = selInvPlan();
+    GradDev& g = gradPlan();
+    int64_t chunk = std::min<int64_t>(batch, 65535);
+    if (selInvChunkCap > 0) chunk = std::min<int64_t>(chunk, selInvChunkCap);
+    const int64_t slice = d.sliceBytes();
+    if (chunk > d.slices && slice > 0) {
+      size_t freeBytes = 0, totalBytes = 0;
+      hipCHECK(hipMemGetInfo(&freeBytes, &totalBytes));
+      const int64_t fit = std::max<int64_t>(d.slices, (int64_t)(freeBytes / 2) / slice);
+      chunk = std::max<int64_t>(1, std::min(chunk, fit));
+    }
+    d.reserve(chunk);
+    const size_t bytes = batch * sizeof(T*);
+    const T* const* lMany = single ? nullptr : (const T* const*)ptrRing.push(L, bytes, stream);
+    T* const* gMany = single ? nullptr : (T* const*)ptrRing.push(G, bytes, stream);
+    const hipk::SkelDev sk = skelDev();
+    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
+      const unsigned nm = (unsigned)std::min(chunk, batch - q0);
+      const hipk::DataRef<const T> lref = single ? hipk::DataRef<const T>{L[0], nullptr}
+                                                 : hipk::DataRef<const T>{nullptr, lMany + q0};
+      const hipk::DataRef<T> gref = single ? hipk::DataRef<T>{G[0], nullptr} : hipk::DataRef<T>{nullptr, gMany + q0};
+      cholAdjLevels<T>(d, lref, gref, nm);
+      if (g.nTiles > 0) {
+        hipk::cholAdjFinal<T><<<dim3((unsigned)g.nTiles, nm), 256, 0, stream>>>(g.tiles.as<hipk::GradTile>(), sk,
+                                                                               gref);
+      }
+    }
+    hipCHECK(hipGetLastError());
+  }
+
+  // one right-to-left pass over the selected-inversion levels for `nMats` matrices (gridDim.y), in
+  // scratch slices 0 .. nMats-1.  selinvDiagInverse and selinvZrrTimesU run as they are: the first
+  // reads L (it does not write its data), the second multiplies G_RR by the copy of L_RI in U.
+  template <typename T>
+  void cholAdjLevels(const SelInvDev& d, hipk::DataRef<const T> lref, hipk::DataRef<T> gref, unsigned nMats) {
+    const hipk::SkelDev sk = skelDev();
+    const hipk::SelInvStrides st = d.strides();
+    T* linv = reinterpret_cast<T*>(d.linv.ptr);
+    T* dd = reinterpret_cast<T*>(d.dd.ptr);
+    T* U = reinterpret_cast<T*>(d.U.ptr);
+    T* P = reinterpret_cast<T*>(d.P.ptr);
+    T* Wp = reinterpret_cast<T*>(d.Wp.ptr);
+    const hipk::DataRef<T> lmut{const_cast<T*>(lref.single), const_cast<T* const*>(lref.many)};
+    const SelInvNode* nodes = d.nodes.as<SelInvNode>();
+    const int2* tiles = d.tiles.as<int2>();
+    const int4* zTasks = d.zTasks.as<int4>();
+    for (const SelInvLevel& L : d.host.levels) {
+      if (L.smallEnd > L.smallBegin) {
+        hipk::cholAdjSmallLumps<T><<<dim3((unsigned)(L.smallEnd - L.smallBegin), nMats), 64, 0, stream>>>(
+            d.smalls.as<SelInvSmall>() + L.smallBegin, sk, lref, gref);
+      }
+      const unsigned nNodes = (unsigned)(L.nodeEnd - L.nodeBegin);
+      if (nNodes == 0) continue;
+      const SelInvNode* nd = nodes + L.nodeBegin;
+      hipk::selinvDiagInverse<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, lmut, linv, dd, st);
+      const unsigned nTiles = (unsigned)(L.tileEnd - L.tileBegin);
+      if (nTiles > 0) {
+        hipk::cholAdjGatherL<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, tiles + L.tileBegin, lref, U, st);
+        hipk::selinvZrrTimesU<T><<<dim3((unsigned)(L.zEnd - L.zBegin), nMats), 256, 0, stream>>>(
+            nd, zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(),
+            d.pairOff.as<int64_t>(), d.pairStr.as<int32_t>(), gref, U, P, st);
+        hipk::cholAdjReduce<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, tiles + L.tileBegin, gref, linv, U, P,
+                                                                        Wp, st);
+      }
+      hipk::cholAdjDiag<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, lref, gref, linv, Wp, st);
+    }
   }
 
   SelInvDev& selInvPlan() {
@@ -2817,6 +2899,15 @@ void hipBackendLogDet(SymbolicCtx& sym, const T* const* factors, int64_t batch, 
 }
 template void hipBackendLogDet<double>(SymbolicCtx&, const double* const*, int64_t, bool, double*);
 template void hipBackendLogDet<float>(SymbolicCtx&, const float* const*, int64_t, bool, float*);
+
+template <typename T>
+void hipBackendFactorAdjoint(SymbolicCtx& sym, const T* const* L, T* const* grad, int64_t batch, bool single) {
+  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
+  BASPACHO_CHECK_NOTNULL(h);
+  h->factorAdjoint(L, grad, batch, single);
+}
+template void hipBackendFactorAdjoint<double>(SymbolicCtx&, const double* const*, double* const*, int64_t, bool);
+template void hipBackendFactorAdjoint<float>(SymbolicCtx&, const float* const*, float* const*, int64_t, bool);
 
 template <typename T>
 void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a) {

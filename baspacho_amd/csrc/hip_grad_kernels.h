@@ -17,6 +17,9 @@
 //                  i < j:  out_e = 0          (strictly-upper elements of the diagonal blocks)
 //                U, V column-major n x k (U_ik at U[i + k * ld]); without Z the first term is 0, without
 //                U / V the second.  `out` is only written.
+//   patternOuter (patternGradTiles<T, true>): the non-symmetric rank-k projection, no Z term
+//                  i >= j: out_e = alpha sum_k U_ik V_jk
+//                  i < j:  out_e = 0
 //
 // BATCH: matrix q = blockIdx.y finds its arrays through pickData, as the selinv kernels do.  There are
 // no atomics and every sum runs in a fixed order that does not depend on q: results are bitwise
@@ -106,8 +109,9 @@ static_assert(sizeof(GradTile) == 40, "GradTile is uploaded as raw bytes");
 // (e -> (e / nc, e % nc)), so the stores stay coalesced for 3- and 9-wide lumps.  The U / V rows of the
 // tile's rows and of its columns go through LDS in chunks of kGradK right-hand sides; each thread keeps
 // the sums of its (at most 8) elements in registers.  Dynamic LDS: (kGradRows + kGradCols) x
-// (kc + 1) x 4 values of T, kc = min(k, kGradK) (0 without U / V).
-template <typename T>
+// (kc + 1) x 4 values of T, kc = min(k, kGradK) (0 without U / V).  Outer = true: patternOuter (only
+// the U rows and V columns of the tile are loaded; zref / zScale unused).
+template <typename T, bool Outer = false>
 __global__ void __launch_bounds__(256) patternGradTiles(const GradTile* __restrict__ tiles, SkelDev sk,
                                                         DataRef<const T> zref, const T* __restrict__ zScale,
                                                         DataRef<const T> uref, DataRef<const T> vref,
@@ -155,12 +159,12 @@ __global__ void __launch_bounds__(256) patternGradTiles(const GradTile* __restri
         const int r = x % t.nr, kk = x / t.nr;  // consecutive lanes: consecutive rows of one column
         const int64_t a = rowG[r] + (int64_t)(k0 + kk) * ld;
         Ur[r * S + kk] = U[a];
-        Vr[r * S + kk] = V[a];
+        if (!Outer) Vr[r * S + kk] = V[a];
       }
       for (int x = tid; x < t.nc * kc; x += 256) {
         const int c = x % t.nc, kk = x / t.nc;
         const int64_t a = j0 + c + (int64_t)(k0 + kk) * ld;
-        Uc[c * S + kk] = U[a];
+        if (!Outer) Uc[c * S + kk] = U[a];
         Vc[c * S + kk] = V[a];
       }
       __syncthreads();
@@ -175,7 +179,10 @@ __global__ void __launch_bounds__(256) patternGradTiles(const GradTile* __restri
           const T* uj = Uc + c * S;
           const T* vj = Vc + c * S;
           T s = acc[m];
-          if (i > j) {
+          if (Outer) {
+            if (i >= j)
+              for (int kk = 0; kk < kc; kk++) s = fma(ui[kk], vj[kk], s);
+          } else if (i > j) {
             for (int kk = 0; kk < kc; kk++) s = fma(ui[kk], vj[kk], fma(vi[kk], uj[kk], s));
           } else {
             for (int kk = 0; kk < kc; kk++) s = fma(ui[kk], vi[kk], s);

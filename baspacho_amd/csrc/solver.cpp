@@ -654,6 +654,133 @@ template void Solver::patternGrad<float>(const std::vector<float*>&, const float
                                          const std::vector<float*>&, int64_t, int, float,
                                          const std::vector<float*>&) const;
 
+// ---- reverse mode of the factor and of the triangular solves ------------------------------------
+// outputs (`outBytes` each) must not overlap one another nor any input (`inBytes` each); checked before
+// any device work
+template <typename T>
+static void checkNoOverlap(const char* what, const std::vector<T*>& outs, size_t outBytes,
+                           const std::vector<const T*>& ins, size_t inBytes) {
+  struct Range {
+    uintptr_t b, e;
+    size_t q;
+  };
+  std::vector<Range> o;
+  for (size_t q = 0; q < outs.size(); q++) {
+    const uintptr_t b = reinterpret_cast<uintptr_t>(outs[q]);
+    o.push_back({b, b + outBytes, q});
+  }
+  std::sort(o.begin(), o.end(), [](const Range& x, const Range& y) { return x.b < y.b; });
+  for (size_t i = 1; i < o.size(); i++) {
+    if (o[i].b < o[i - 1].e) {
+      throw std::runtime_error(std::string(what) + ": the output buffers of batch members " +
+                               std::to_string(o[i - 1].q) + " and " + std::to_string(o[i].q) + " overlap");
+    }
+  }
+  for (size_t q = 0; q < ins.size(); q++) {
+    const uintptr_t b = reinterpret_cast<uintptr_t>(ins[q]), e = b + inBytes;
+    // the first output that ends past b
+    auto it = std::upper_bound(o.begin(), o.end(), b, [](uintptr_t x, const Range& r) { return x < r.e; });
+    // outputs are sorted by start and disjoint, so their ends are sorted too
+    if (it != o.end() && it->b < e) {
+      throw std::runtime_error(std::string(what) + ": the output buffer of batch member " +
+                               std::to_string(it->q) + " overlaps input " + std::to_string(q));
+    }
+  }
+}
+
+template <typename T>
+static void checkMembers(const char* what, const char* name, const std::vector<T*>& v, size_t batch) {
+  if (v.size() != batch) {
+    throw std::runtime_error(std::string(what) + ": " + name + " has " + std::to_string(v.size()) +
+                             " pointers for a batch of " + std::to_string(batch));
+  }
+  for (size_t q = 0; q < v.size(); q++) {
+    if (v[q] == nullptr) {
+      throw std::runtime_error(std::string(what) + ": the " + name + " pointer of batch member " +
+                               std::to_string(q) + " is NULL");
+    }
+  }
+}
+
+template <typename T>
+static void runPatternOuter(const Solver& s, SymbolicCtx& sym, bool single, const std::vector<T*>& U,
+                            const std::vector<T*>& V, int64_t stride, int nRHS, T alpha,
+                            const std::vector<T*>& out) {
+  const char* what = "patternOuter";
+  if (out.empty()) throw std::runtime_error("patternOuter: the batch is empty");
+  checkMembers(what, "out", out, out.size());
+  checkMembers(what, "U", U, out.size());
+  checkMembers(what, "V", V, out.size());
+  if (nRHS < 1) throw std::runtime_error("patternOuter: nRHS = " + std::to_string(nRHS) + " < 1");
+  if (stride < s.order()) {
+    throw std::runtime_error("patternOuter: stride " + std::to_string(stride) + " < order " +
+                             std::to_string(s.order()));
+  }
+  std::vector<const T*> in(U.begin(), U.end());
+  in.insert(in.end(), V.begin(), V.end());
+  checkNoOverlap(what, out, s.dataSize() * sizeof(T), in, (stride * (nRHS - 1) + s.order()) * sizeof(T));
+  checkCompleteFactor(what, s.canFactorUpToSpan(), s.skel().numSpans());
+  std::vector<const T*> u(U.begin(), U.end()), v(V.begin(), V.end());
+  HipGradArgs<T> a;
+  a.batch = (int64_t)out.size();
+  a.single = single;
+  a.u = u.data();
+  a.v = v.data();
+  a.ld = stride;
+  a.nRHS = nRHS;
+  a.alpha = alpha;
+  a.out = out.data();
+  a.outer = true;
+  hipBackendPatternGrad<T>(sym, a);
+}
+
+template <typename T>
+void Solver::patternOuter(const T* U, const T* V, int64_t stride, int nRHS, T alpha, T* out) const {
+  runPatternOuter(*this, *symCtx, true, std::vector<T*>{const_cast<T*>(U)}, std::vector<T*>{const_cast<T*>(V)},
+                  stride, nRHS, alpha, std::vector<T*>{out});
+}
+
+template <typename T>
+void Solver::patternOuter(const std::vector<T*>& U, const std::vector<T*>& V, int64_t stride, int nRHS, T alpha,
+                          const std::vector<T*>& out) const {
+  runPatternOuter(*this, *symCtx, false, U, V, stride, nRHS, alpha, out);
+}
+
+template <typename T>
+static void runFactorAdjoint(const Solver& s, SymbolicCtx& sym, bool single, const std::vector<T*>& L,
+                             const std::vector<T*>& grad) {
+  const char* what = "factorAdjoint";
+  if (grad.empty()) throw std::runtime_error("factorAdjoint: the batch is empty");
+  checkMembers(what, "grad", grad, grad.size());
+  checkMembers(what, "L", L, grad.size());
+  const size_t bytes = s.dataSize() * sizeof(T);
+  checkNoOverlap(what, grad, bytes, std::vector<const T*>(L.begin(), L.end()), bytes);
+  checkCompleteFactor(what, s.canFactorUpToSpan(), s.skel().numSpans());
+  std::vector<const T*> l(L.begin(), L.end());
+  hipBackendFactorAdjoint<T>(sym, l.data(), grad.data(), (int64_t)grad.size(), single);
+}
+
+template <typename T>
+void Solver::factorAdjoint(const T* L, T* grad) const {
+  runFactorAdjoint(*this, *symCtx, true, std::vector<T*>{const_cast<T*>(L)}, std::vector<T*>{grad});
+}
+
+template <typename T>
+void Solver::factorAdjoint(const std::vector<T*>& L, const std::vector<T*>& grad) const {
+  runFactorAdjoint(*this, *symCtx, false, L, grad);
+}
+
+template void Solver::patternOuter<double>(const double*, const double*, int64_t, int, double, double*) const;
+template void Solver::patternOuter<float>(const float*, const float*, int64_t, int, float, float*) const;
+template void Solver::patternOuter<double>(const std::vector<double*>&, const std::vector<double*>&, int64_t, int,
+                                           double, const std::vector<double*>&) const;
+template void Solver::patternOuter<float>(const std::vector<float*>&, const std::vector<float*>&, int64_t, int,
+                                          float, const std::vector<float*>&) const;
+template void Solver::factorAdjoint<double>(const double*, double*) const;
+template void Solver::factorAdjoint<float>(const float*, float*) const;
+template void Solver::factorAdjoint<double>(const std::vector<double*>&, const std::vector<double*>&) const;
+template void Solver::factorAdjoint<float>(const std::vector<float*>&, const std::vector<float*>&) const;
+
 // ---- assembly of coordinate entries -----------------------------------------------------------
 std::vector<int64_t> Solver::scalarPermutation() const {
   const std::vector<int64_t>& spanStart = factorSkel.spanStart;

@@ -110,6 +110,28 @@ class Solver {
   void patternGrad(const std::vector<T*>& Z, const T* zScale, const std::vector<T*>& U,
                    const std::vector<T*>& V, int64_t stride, int nRHS, T alpha,
                    const std::vector<T*>& out) const;
+  // patternOuter: the non-symmetric rank-k projection, for every stored element e = (i, j) (out is never
+  // read): i >= j: out_e = alpha sum_k U_ik V_jk; strictly-upper elements of the diagonal blocks: 0.
+  // U, V as for patternGrad (both required, nRHS >= 1).  Batch form: member q of each vector.  NULL
+  // pointers, an empty batch and output buffers that overlap each other or an input are refused.
+  template <typename T>
+  void patternOuter(const T* U, const T* V, int64_t stride, int nRHS, T alpha, T* out) const;
+  template <typename T>
+  void patternOuter(const std::vector<T*>& U, const std::vector<T*>& V, int64_t stride, int nRHS, T alpha,
+                    const std::vector<T*>& out) const;
+
+  // extension: reverse-mode sweep of factor() (hip_chol_adjoint_kernels.h).  `L`
+  // holds a complete factor() of A(d); `grad` holds Lbar = df/dL on entry (every stored element with
+  // i >= j; the strictly-upper elements of the diagonal blocks are ignored) and df/dd on return, in
+  // patternGrad's convention.  L is only read.  Runs on the stream of setStream() without host
+  // synchronisation.  Batch form: member q of each vector, bitwise the single call; the batch runs in
+  // chunks bounded by device memory, as selectedInverse does.  NULL pointers, an empty batch, sizes
+  // that differ, gradient buffers that overlap each other or a factor, and a Solver that cannot
+  // factor completely are refused before any device work.
+  template <typename T>
+  void factorAdjoint(const T* L, T* grad) const;
+  template <typename T>
+  void factorAdjoint(const std::vector<T*>& L, const std::vector<T*>& grad) const;
 
   // extension: assembly of coordinate entries (row, col, value) into this Solver's layout (DESIGN.md
   // section 14; assembly.h).  `map` comes from createAssemblyMap(*this, ...).  assemble writes every

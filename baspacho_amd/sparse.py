@@ -6,11 +6,12 @@
     ld = S.logdet(pat, values)                     # log det A
     x, ld = S.solve_logdet(pat, values, b)         # both, one factor
     data = S.assemble(pat, values)                 # the solver's layout, for baspacho_amd.autograd
+    x = S.sample(pat, values, z, mu)               # x = mu + L^-T z: Cov(x) = A^-1
 
 The matrix is given by entries (rows[k], cols[k], values[k]) in the caller's scalar order: A_ij = A_ji =
 the sum of the values of the entries at (i, j), i >= j.  `values` is [nnz] or a
 batch [B, nnz] of matrices of one pattern; `b` and `x` are in the caller's order, [n] or [n, k], with a
-leading B when batched.  Gradients go to `values` and `b`.
+leading B when batched.  Gradients go to `values` and `b` (and to `z` and `mu` for sample).
 
 Each function composes the assembly kernel (whose backward is its adjoint), baspacho_amd.autograd's
 solve / logdet / solve_logdet and a permutation of the vectors.  Everything runs on
@@ -26,7 +27,7 @@ from . import Settings, SparseStructure, create_solver
 from . import autograd as _ag
 from .autograd import _OnCurrentStream
 
-__all__ = ["SymmetricPattern", "assemble", "solve", "logdet", "solve_logdet"]
+__all__ = ["SymmetricPattern", "assemble", "solve", "logdet", "solve_logdet", "sample"]
 
 
 def _host_i64(a):
@@ -194,3 +195,17 @@ def solve_logdet(pattern, values, b):
     dim = _check_b(pattern, values, b, "solve_logdet")
     x, ld = _ag.solve_logdet(pattern.solver, assemble(pattern, values), pattern.toInternal(b, dim))
     return pattern.fromInternal(x, dim), ld
+
+
+def sample(pattern, values, z, mu=None):
+    """x = mu + P^T L^-T (P z) in the caller's order, P the solver's permutation and L the factor of
+    A(values) in internal order, so that Cov(x) = A^-1 for z ~ N(0, I): a sample of the Gaussian with
+    precision A.  z (and mu) are shaped like solve's b; differentiable in values, z and mu"""
+    _check_values(pattern, values, "sample")
+    dim = _check_b(pattern, values, z, "sample")
+    if mu is not None:
+        if not isinstance(mu, torch.Tensor) or mu.shape != z.shape:
+            raise ValueError("sample: mu must be a tensor of z's shape %s" % (tuple(z.shape),))
+    L = _ag.cholesky(pattern.solver, assemble(pattern, values))
+    x = pattern.fromInternal(_ag.solve_lt(pattern.solver, L, pattern.toInternal(z, dim)), dim)
+    return x if mu is None else mu + x

@@ -278,6 +278,38 @@ int bsp_pattern_grad_batched_f64(bsp_solver* s, const double* const* dev_z, cons
 int bsp_pattern_grad_batched_f32(bsp_solver* s, const float* const* dev_z, const float* dev_z_scale,
                                  const float* const* dev_u, const float* const* dev_v, int64_t stride,
                                  int32_t nrhs, float alpha, float* const* dev_out, int32_t batch);
+/* bsp_pattern_outer_*: the non-symmetric rank-k projection (write-only, dev_out is never read):
+     i >= j: out_e = alpha sum_k U_ik V_jk
+     strictly-upper elements of the diagonal blocks:  out_e = 0
+   U, V order x nrhs column-major with leading dimension `stride` (>= order), nrhs >= 1, both required.
+   The backward of y = L^-1 b is Lbar = -(L^-T g_y) y^T (U = L^-T g_y, V = y, alpha = -1); that of
+   x = L^-T b is Lbar = -x (L^-1 g_x)^T (U = x, V = L^-1 g_x, alpha = -1).  An
+   output buffer that overlaps another member's output or any U / V: non-zero return before any
+   device work.  The batched form takes HOST arrays of `batch` device pointers. */
+int bsp_pattern_outer_f64(bsp_solver* s, const double* dev_u, const double* dev_v, int64_t stride, int32_t nrhs,
+                          double alpha, double* dev_out);
+int bsp_pattern_outer_f32(bsp_solver* s, const float* dev_u, const float* dev_v, int64_t stride, int32_t nrhs,
+                          float alpha, float* dev_out);
+int bsp_pattern_outer_batched_f64(bsp_solver* s, const double* const* dev_u, const double* const* dev_v,
+                                  int64_t stride, int32_t nrhs, double alpha, double* const* dev_out, int32_t batch);
+int bsp_pattern_outer_batched_f32(bsp_solver* s, const float* const* dev_u, const float* const* dev_v,
+                                  int64_t stride, int32_t nrhs, float alpha, float* const* dev_out, int32_t batch);
+/* bsp_factor_adjoint_*: the reverse-mode sweep of bsp_factor_* (DESIGN.md section 15).  dev_l holds a
+   complete factor() of A(d) and is only read.  dev_grad holds Lbar = df/dL on entry, for every stored
+   element with i >= j (the strictly-upper elements of the diagonal blocks are ignored), and df/dd on
+   return in bsp_pattern_grad_*'s convention: G_ij + G_ji for i > j, G_ii for i = j, 0 on the
+   strictly-upper elements, for the dense symmetric gradient G = df/dA.  The cost is about that of
+   bsp_selected_inverse_*, whose plan and scratch it shares.  The batched form takes HOST arrays of
+   `batch` device pointers, runs in chunks as bsp_selected_inverse_batched_* does, and member q is
+   bitwise the single call.  dev_grad == dev_l, gradient buffers that overlap each other or any factor,
+   a NULL pointer, batch <= 0 or a solver that cannot factor completely: non-zero return before any
+   device work. */
+int bsp_factor_adjoint_f64(bsp_solver* s, const double* dev_l, double* dev_grad);
+int bsp_factor_adjoint_f32(bsp_solver* s, const float* dev_l, float* dev_grad);
+int bsp_factor_adjoint_batched_f64(bsp_solver* s, const double* const* dev_l, double* const* dev_grad,
+                                   int32_t batch);
+int bsp_factor_adjoint_batched_f32(bsp_solver* s, const float* const* dev_l, float* const* dev_grad,
+                                   int32_t batch);
 /* Extension (no counterpart in the reference): assembly of a symmetric matrix given as coordinate
    entries (rows[k], cols[k], values[k]) in the caller's scalar order into this solver's layout, and its
    adjoint.
