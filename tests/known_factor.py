@@ -11,6 +11,11 @@ to the device, after rounding to the working precision; L0 is only the generator
 
 tests/test_known_factor_cpu.py simulates correct and deliberately wrong blocked factors and solves in
 numpy and asserts that the checks pass the former and fail the latter, each by at least 10x.
+
+Partial factors (factorUpTo(k) at the column bar = spanStart[k]) are checked on the leading columns
+(lead_off, lead_diag, lead_backward) and on the Schur complement S = A22 - L21 L21^T left in the
+trailing block (schur); trailing entries that no cross-cut product reaches must keep their input
+bitwise.  tests/test_partial_factor_cpu.py proves those checks in numpy the same way.
 """
 import atexit
 import json
@@ -23,12 +28,15 @@ UNIT_ROUNDOFF = {np.dtype(np.float64): 2.0 ** -53, np.dtype(np.float32): 2.0 ** 
 # C of every metric, tolerance = C * u(dtype).  The device's errors on correct paths stay within
 # about C / 10 (measured over test_known_factor_gpu.py and the stress slice: at most 5 u for the factor
 # metrics, 12 u forward and 3 u backward for the solves, both precisions), and the simulated mistakes
-# of test_known_factor_cpu.py exceed 10 C.
+# of test_known_factor_cpu.py exceed 10 C.  The partial-factor metrics (lead_*, schur) were fixed
+# before their first device run at the values of the factor metrics they restrict; their simulated
+# mistakes (test_partial_factor_cpu.py) exceed 10 C as well.
+_PARTIAL_C = {"lead_off": 128.0, "lead_diag": 128.0, "lead_backward": 64.0, "schur": 128.0}
 C = {
     np.dtype(np.float64): {"off": 128.0, "diag": 128.0, "backward": 64.0,
-                           "solve_forward": 512.0, "solve_backward": 64.0},
+                           "solve_forward": 512.0, "solve_backward": 64.0, **_PARTIAL_C},
     np.dtype(np.float32): {"off": 128.0, "diag": 128.0, "backward": 64.0,
-                           "solve_forward": 512.0, "solve_backward": 64.0},
+                           "solve_forward": 512.0, "solve_backward": 64.0, **_PARTIAL_C},
 }
 
 
@@ -60,6 +68,32 @@ def stored_pattern(sol):
     return np.tril(sol.densify(ones)) != 0
 
 
+def data_index(sol):
+    """dense int64 matrix: the position in the numeric data of each stored lower entry, -1 elsewhere"""
+    pos = np.arange(1, sol.dataSize() + 1, dtype=np.float64)
+    return np.tril(sol.densify(pos)).astype(np.int64) - 1
+
+
+def leading_words(sol, span):
+    """the numeric data of the lump columns before `span` (a lump boundary) is one leading stretch
+    data[:end]; returns end (asserted against the layout)"""
+    sk = sol.skel()
+    lump = int(sk["spanToLump"][span])
+    end = int(sk["chainData"][sk["chainColPtr"][lump]]) if lump < sol.numLumps() else sol.dataSize()
+    bar = int(sk["spanStart"][span])
+    idx = data_index(sol)
+    assert np.all(idx[:, :bar][idx[:, :bar] >= 0] < end) and np.all(idx[:, bar:][idx[:, bar:] >= 0] >= end)
+    return end
+
+
+def bitwise_equal(a, b):
+    """equal words (NaN payloads included)"""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    assert a.dtype == b.dtype
+    u = np.uint64 if a.dtype.itemsize == 8 else np.uint32
+    return np.array_equal(a.view(u), b.view(u))
+
+
 class KnownFactor:
     """one matrix: `data` (host, in `dtype`, the solver's layout), its float64 dense form `A` and the
     float64 reference factor `L` of exactly that data"""
@@ -88,15 +122,88 @@ class KnownFactor:
     def check_solve(self, b, x, op="A", what=""):
         check(self.solve_errors(b, x, op), self.dtype, what)
 
+    # ---- partial factors: factorUpTo(k), bar = spanStart[k]
+    def partial_errors_dense(self, G, bar):
+        """lead_off / lead_diag: relative errors of the stored entries of columns < bar (strictly lower,
+        diagonal); lead_backward: ||A[:, :bar] - G[:, :bar] G[:bar, :bar]^T|| / ||A[:, :bar]||; schur:
+        ||S_dev - S_ref|| / (||A22|| + ||L21 L21^T||) on the lower stored pattern of the trailing block,
+        S_ref = A22 - L21 L21^T (G: dense, lower, float64)"""
+        P, L, A = self.pattern, self.L, self.A
+        G = np.where(P, G, 0.0)
+        strict = np.tril(P, -1)
+        strict[:, bar:] = False
+        ref_off = np.linalg.norm(L[strict])
+        off = np.linalg.norm(G[strict] - L[strict]) / ref_off if ref_off > 0 else 0.0
+        d = np.arange(bar)
+        diag = np.linalg.norm(G[d, d] - L[d, d]) / np.linalg.norm(L[d, d]) if bar else 0.0
+        back = 0.0
+        if bar:
+            Gl = G[:, :bar]
+            back = np.linalg.norm(A[:, :bar] - Gl @ Gl[:bar].T) / np.linalg.norm(A[:, :bar])
+        schur = 0.0
+        if bar < len(A):
+            T = P[bar:, bar:]
+            L21 = L[bar:, :bar]
+            LL = L21 @ L21.T
+            S_ref = A[bar:, bar:] - LL
+            den = np.linalg.norm(A[bar:, bar:][T]) + np.linalg.norm(LL[T])
+            schur = np.linalg.norm(G[bar:, bar:][T] - S_ref[T]) / den
+        return {"lead_off": float(off), "lead_diag": float(diag), "lead_backward": float(back),
+                "schur": float(schur)}
 
-def known_factor_data(sol, seed, dtype, rho=1.0):
+    def untouched(self, bar):
+        """boolean mask of the trailing stored lower entries that no cross-cut product reaches
+        (structurally |L21| |L21|^T == 0)"""
+        P = self.pattern
+        out = np.zeros_like(P)
+        if 0 < bar < len(P):
+            B21 = P[bar:, :bar].astype(np.float32)
+            reach = (B21 @ B21.T) > 0
+            out[bar:, bar:] = P[bar:, bar:] & ~reach
+        elif bar == 0:
+            out = P.copy()
+        return out
+
+    def check_partial(self, got, bar, what=""):
+        """factorUpTo's result `got` (the solver's layout, in dtype): leading columns, Schur
+        complement, and the untouched entries bitwise"""
+        got = np.asarray(got)
+        G = np.tril(self.sol.densify(got.astype(np.float64)))
+        check(self.partial_errors_dense(G, bar), self.dtype, what)
+        idx = data_index(self.sol)[self.untouched(bar)]
+        assert bitwise_equal(got[idx], self.data[idx]), ("untouched entries changed", what,
+                                                         int(np.count_nonzero(got[idx] != self.data[idx])))
+
+    def trailing(self, bar):
+        """the reference of factorFrom on data whose leading columns are not used: the float64
+        Cholesky factor of A22 alone, as (L22, A22, pattern22)"""
+        A22 = self.A[bar:, bar:]
+        return np.linalg.cholesky(A22), A22, self.pattern[bar:, bar:]
+
+    def check_trailing_factor(self, got, bar, what=""):
+        """factorFrom(k) of data whose trailing block is A22: that block against the Cholesky of A22"""
+        L22, A22, P22 = self.trailing(bar)
+        G = np.tril(self.sol.densify(np.asarray(got, dtype=np.float64)))[bar:, bar:]
+        G[~P22] = 0.0
+        check(factor_errors_dense(G, L22, A22, P22), self.dtype, what)
+
+
+def known_factor_data(sol, seed, dtype, rho=1.0, full_from=None):
     """a matrix A = L0 L0^T with L0 random on the stored pattern: diagonal uniform in [1, 2],
-    off-diagonals uniform(-1, 1) * rho / sqrt(stored off-diagonal entries in the row)"""
+    off-diagonals uniform(-1, 1) * rho / sqrt(stored off-diagonal entries in the row).
+    full_from=bar (a lump boundary): L0 random on the stored pattern of the columns < bar only, and on the
+    columns >= bar nonzero only in the square diagonal blocks of the lumps (for solvers whose fill is
+    incomplete past canFactorUpToSpan(): L0 L0^T must still lie on the stored pattern)"""
     dtype = np.dtype(dtype)
     n = sol.order()
     P = stored_pattern(sol)
     rng = np.random.default_rng(seed)
     strict = np.tril(P, -1)
+    if full_from is not None:
+        ls = sol.skel()["lumpStart"]
+        lump_of = np.searchsorted(ls, np.arange(n), side="right") - 1
+        same = lump_of[:, None] == lump_of[None, :]
+        strict[:, full_from:] &= same[:, full_from:]
     per_row = np.maximum(strict.sum(axis=1), 1).astype(np.float64)
     L0 = np.where(strict, rng.uniform(-1.0, 1.0, size=(n, n)) * (rho / np.sqrt(per_row))[:, None], 0.0)
     L0[np.diag_indices(n)] = rng.uniform(1.0, 2.0, size=n)

@@ -12,6 +12,11 @@ import baspacho_amd as B
 from baspacho_amd import testing as T
 from helpers import solver_random, to_dev
 from known_factor import check, known_factor_data, stored_pattern, tolerance, vec_to_cols
+from kf_structures import bipartite as _bipartite
+from kf_structures import blocks_over_separator as _blocks_over_separator
+from kf_structures import counter_delta as _counter_delta
+from kf_structures import dense_solver as _dense_solver
+from kf_structures import random_with_range as _random_with_range
 from stress_cases import width_solver
 
 pytestmark = pytest.mark.gpu
@@ -38,54 +43,6 @@ def _solve(kf, dev, nrhs, op="A", seed=1, what=""):
     v = to_dev(b.T.ravel().astype(dtype))
     getattr(sol, {"A": "solve", "L": "solveL", "Lt": "solveLt"}[op])(dev, v, n, nrhs)
     kf.check_solve(b, vec_to_cols(v.cpu().numpy(), n, nrhs), op, (what, op, nrhs))
-
-
-def _dense_solver(W, span=8, hip_options=None):
-    sizes = [span] * (W // span) + ([W % span] if W % span else [])
-    cols = [list(range(c, len(sizes))) for c in range(len(sizes))]
-    st = B.Settings(findSparseEliminationRanges=False, hipOptions=hip_options)
-    return B.create_solver(st, np.asarray(sizes, dtype=np.int64), T.columns_to_structure(cols), [])
-
-
-def _blocks_over_separator(widths, sep, hip_options=None):
-    """independent dense blocks over a common separator (levels of several panels)"""
-    n = sum(widths) + sep
-    cols, base = [], 0
-    for w in widths:
-        for i in range(w):
-            cols.append(set(range(base + i, base + w)) | set(range(n - sep, n)))
-        base += w
-    for i in range(sep):
-        cols.append(set(range(n - sep + i, n)))
-    return B.create_solver(B.Settings(hipOptions=hip_options), np.ones(n, dtype=np.int64),
-                           T.columns_to_structure(cols))
-
-
-def _bipartite(num_pts, num_cams, pt_size, cam_size, seed, track=4, hip_options=None):
-    """points (eliminated, pt_size wide) seen by `track` cameras (cam_size rows per block) each, and the
-    point range [0, num_pts) as the given elimination range"""
-    rng = np.random.default_rng(seed)
-    pt = np.repeat(np.arange(num_pts, dtype=np.int64), track)
-    cam = rng.integers(0, num_cams, size=num_pts * track)
-    key = np.unique(pt * num_cams + cam)
-    pt, cam = key // num_cams, key % num_cams
-    sizes = np.concatenate([np.full(num_pts, pt_size, dtype=np.int64), np.full(num_cams, cam_size, dtype=np.int64)])
-    ss = T.structure_from_pairs(num_pts + num_cams, num_pts + cam, pt)
-    return B.create_solver(B.Settings(hipOptions=hip_options), sizes, ss, [0, num_pts])
-
-
-def _random_with_range(seed, hip_options=None):
-    """a random structure whose first 150 parameters are an independent elimination range, with several
-    dense lumps behind it (lump boundaries for the partial solves)"""
-    cols = T.make_independent_elim_set(T.random_cols(300, 0.03, seed), 0, 150)
-    sizes = np.random.default_rng(seed).integers(1, 5, size=300).astype(np.int64)
-    return B.create_solver(B.Settings(hipOptions=hip_options), sizes, T.columns_to_structure(cols), [0, 150])
-
-
-def _counter_delta(sol, name, fn):
-    before = sol.runCounters()[name]
-    fn()
-    return sol.runCounters()[name] - before
 
 
 # ---- lump widths ------------------------------------------------------------------------------
