@@ -359,16 +359,23 @@ class Solver:
     _SELINV_SMALL_FIELDS = ("lump", "level", "n", "r", "k")
     _SELINV_NODE_FIELDS = ("lump", "level", "c0", "w", "r", "nRest", "kChunk", "nk", "nTiles", "tileBase")
 
-    def _testSelInvPlan(self):
+    def _testSelInvPlan(self, upToSpan=None):
         """TESTING: the selected-inversion plan of this solver (bsp_test_selinv_plan, built on the host
         by the function selectedInverse() uses).  {"numLevels", "linvElems", "uElems", "pElems",
         "wElems": int, "small": {field: int64 array}, "node": {field: int64 array}}, records in launch
         order; small fields lump, level, n, r, k; node fields lump, level, c0, w, r, nRest, kChunk, nk,
-        nTiles, tileBase"""
+        nTiles, tileBase.  upToSpan: the plan of the lumps before that span alone, which
+        factorAdjointUpTo runs (bsp_test_selinv_plan_up_to)"""
+        if upToSpan is None:
+            def call(buf, cap, need):
+                return self._lib.bsp_test_selinv_plan(self._h, buf, cap, need)
+        else:
+            def call(buf, cap, need):
+                return self._lib.bsp_test_selinv_plan_up_to(self._h, ctypes.c_int64(upToSpan), buf, cap, need)
         need = ctypes.c_int64(0)
-        _check(self._lib.bsp_test_selinv_plan(self._h, None, ctypes.c_int64(0), ctypes.byref(need)))
+        _check(call(None, ctypes.c_int64(0), ctypes.byref(need)))
         buf = np.empty(need.value, dtype=np.int64)
-        _check(self._lib.bsp_test_selinv_plan(self._h, buf.ctypes.data_as(_I64P), need, ctypes.byref(need)))
+        _check(call(buf.ctypes.data_as(_I64P), need, ctypes.byref(need)))
         nlev, ns, nn = (int(x) for x in buf[:3])
         out = {"numLevels": nlev, "linvElems": int(buf[3]), "uElems": int(buf[4]), "pElems": int(buf[5]),
                "wElems": int(buf[6])}
@@ -697,6 +704,103 @@ class Solver:
             return
         _check(getattr(self._lib, "bsp_factor_adjoint_" + sfx)(
             self._h, ctypes.c_void_p(_ptr_of(L)), ctypes.c_void_p(_ptr_of(grad))))
+
+    # ---- the partial factor and its Schur complement -----------------
+    def _same_kind(self, what, names, *xs):
+        """(batched, [members of every x]) for arguments that are all tensors or all lists of one length"""
+        kinds = {isinstance(x, (list, tuple)) for x in xs}
+        if len(kinds) != 1:
+            raise TypeError("%s: %s must all be tensors or all be lists" % (what, names))
+        batched = kinds.pop()
+        ms = [list(x) if batched else [x] for x in xs]
+        if len(ms[0]) == 0:
+            raise ValueError("%s: empty batch" % what)
+        if len({len(m) for m in ms}) != 1:
+            raise ValueError("%s: %s have %s members" % (what, names, " / ".join(str(len(m)) for m in ms)))
+        ts = [t for m in ms for t in m]
+        if len({t.dtype for t in ts}) != 1:
+            raise TypeError("%s: every tensor must share one dtype, got %s" % (what, sorted({str(t.dtype) for t in ts})))
+        if len({t.device for t in ts}) != 1:
+            raise ValueError("%s: tensors on different devices: %s" % (what, sorted({str(t.device) for t in ts})))
+        return batched, ms
+
+    def _schurOrder(self, span):
+        """scalars from span `span` on: the order m of the Schur complement of factorUpTo(span)"""
+        if not 0 <= span <= self.numSpans():
+            raise ValueError("span %d is not in [0, %d]" % (span, self.numSpans()))
+        return self.order() - int(self.skel()["spanStart"][span])
+
+    def factorAdjointUpTo(self, P, grad, span):
+        """extension: the reverse-mode sweep of factorUpTo(span), in place in `grad`
+        (bsp_factor_adjoint_up_to_*).  `P` holds factorUpTo(span) of A(d) -- L11, L21 before the cut, the
+        Schur complement S behind it -- and is only read; `grad` holds df/dP on entry (stored elements
+        with i >= j; strictly-upper elements ignored) and df/dd on return.
+        span = numSpans() is factorAdjoint.  Lists/tuples = a batch, member q bitwise the single call."""
+        batched, (ps, gs) = self._same_kind("factorAdjointUpTo", "P and grad", P, grad)
+        for t in ps + gs:
+            self._check_data(t)
+        sfx = _suffix(gs[0])
+        if batched:
+            def arr(xs):
+                return (ctypes.c_void_p * len(xs))(*[_ptr_of(t) for t in xs])
+            _check(getattr(self._lib, "bsp_factor_adjoint_up_to_batched_" + sfx)(
+                self._h, arr(ps), arr(gs), ctypes.c_int32(len(gs)), ctypes.c_int64(span)))
+            return
+        _check(getattr(self._lib, "bsp_factor_adjoint_up_to_" + sfx)(
+            self._h, ctypes.c_void_p(_ptr_of(ps[0])), ctypes.c_void_p(_ptr_of(gs[0])), ctypes.c_int64(span)))
+
+    def _schur_dense(self, what, name, src, span, out, dest, to_dense):
+        import torch
+        m = self._schurOrder(span)
+        batched = isinstance(src, (list, tuple))
+        srcs = list(src) if batched else [src]
+        if len(srcs) == 0:
+            raise ValueError("%s: empty batch" % what)
+        dense_shape, n_dense, n_data = (m, m), m * m, self.dataSize()
+        if out is None:
+            outs = [torch.empty(dense_shape if to_dense else (n_data,), dtype=t.dtype, device=t.device) for t in srcs]
+            out = outs if batched else outs[0]
+        batched, (srcs, outs) = self._same_kind(what, "%s and out" % name, src, out)
+        for t in srcs:
+            if t.numel() != (n_data if to_dense else n_dense):
+                raise ValueError("%s: %s has %d elements, expected %d" % (
+                    what, name, t.numel(), n_data if to_dense else n_dense))
+        for t in outs:
+            if t.numel() != (n_dense if to_dense else n_data):
+                raise ValueError("%s: out has %d elements, expected %d" % (
+                    what, t.numel(), n_dense if to_dense else n_data))
+        dp = None
+        if dest is not None:
+            if dest.dtype != torch.int32 or dest.numel() != m or dest.device != srcs[0].device:
+                raise ValueError("%s: dest must be an int32 tensor of %d elements on %s" % (what, m, srcs[0].device))
+            dp = _ptr_of(dest)
+        sfx = _suffix(srcs[0])
+        fn = "bsp_schur_to_dense_" if to_dense else "bsp_schur_from_dense_"
+        if batched:
+            def arr(xs):
+                return (ctypes.c_void_p * len(xs))(*[_ptr_of(t) for t in xs])
+            _check(getattr(self._lib, fn + "batched_" + sfx)(
+                self._h, arr(srcs), ctypes.c_int64(span), arr(outs), ctypes.c_void_p(dp), ctypes.c_int32(len(outs))))
+        else:
+            _check(getattr(self._lib, fn + sfx)(
+                self._h, ctypes.c_void_p(_ptr_of(srcs[0])), ctypes.c_int64(span), ctypes.c_void_p(_ptr_of(outs[0])),
+                ctypes.c_void_p(dp)))
+        return out
+
+    def schurComplement(self, P, span, out=None, dest=None):
+        """extension: the trailing block of the layout buffer `P` (e.g. after factorUpTo(span): the Schur
+        complement) as a dense symmetric [m, m] tensor, m = order() - spanStart[span] (bsp_schur_to_dense_*): row /
+        column dest[k] for the k-th scalar behind the cut (`dest`: int32 device permutation; None =
+        internal order), zeros where the pattern has no block.  Every element of `out` is written (it
+        is allocated when None).  Lists = a batch.  Returns out."""
+        return self._schur_dense("schurComplement", "P", P, span, out, dest, True)
+
+    def schurComplementAdjoint(self, gradDense, span, out=None, dest=None):
+        """extension: the adjoint of schurComplement (bsp_schur_from_dense_*): a gradient in the data
+        layout from a dense [m, m] gradient (it need not be symmetric): g_ij + g_ji below the diagonal of
+        the trailing block, g_ii on it, 0 above it and on every column before the cut.  Every element of
+        `out` ([dataSize], allocated when None) is written.  Lists = a batch.  Returns out."""
+        return self._schur_dense("schurComplementAdjoint", "gradDense", gradDense, span, out, dest, False)
 
     # ---- assembly of coordinate entries (DESIGN.md section 14) -----------------------------
     def assembly(self, rows, cols, triangle="lower"):

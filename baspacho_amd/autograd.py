@@ -29,11 +29,21 @@ cholesky returns L on the stored elements with i >= j and 0 on the strictly-uppe
 diagonal blocks; its backward is Solver.factorAdjoint on a clone of the incoming gradient (the
 upper elements' gradient is ignored).  The half-solves' backward is one more half-solve and
 Solver.patternOuter: Lbar = -(L^-T g_y) y^T and Lbar = -x (L^-1 g_x)^T, on the elements with i >= j.
+
+Through the partial factor, `span` a span that Solver.factorUpTo accepts:
+
+    P = BA.factor_up_to(solver, data, span)        # [L11 0; L21 S] in the layout
+    S = BA.schur_complement(solver, data, span)    # dense S = A22 - A21 A11^-1 A12, [m, m], internal order
+    y = BA.solve_l_up_to(solver, P, span, b)       # [L11 0; L21 I]^-1 b; y[bar:] = b2 - A21 A11^-1 b1
+
+Backward is Solver.factorAdjointUpTo (for schur_complement after Solver.schurComplementAdjoint, in one
+Function); solve_l_up_to's is Solver.solveLtUpTo and Solver.patternOuter with y zeroed behind the cut.
 """
 import torch
 from torch.autograd.function import once_differentiable
 
-__all__ = ["solve", "logdet", "solve_logdet", "cholesky", "solve_l", "solve_lt"]
+__all__ = ["solve", "logdet", "solve_logdet", "cholesky", "solve_l", "solve_lt", "factor_up_to",
+           "schur_complement", "solve_l_up_to"]
 
 
 class _OnCurrentStream:
@@ -345,3 +355,193 @@ def solve_lt(solver, L, b):
     _check_rhs(solver, L, b, "solve_lt")
     _check_device(solver, "solve_lt", L, b)
     return _HalfSolve.apply(solver, L, b, False)
+
+
+# ---- through the partial factor: factor_up_to, schur_complement, solve_l_up_to ----
+def _check_span(solver, span, what):
+    """the first scalar behind the cut; refuses what Solver.factorUpTo refuses (host-side, from the skeleton)"""
+    if not isinstance(span, int) or not 0 <= span <= solver.numSpans():
+        raise ValueError("%s: span must be an int in [0, %d], got %r" % (what, solver.numSpans(), span))
+    sk = solver.skel()
+    if int(sk["spanOffsetInLump"][span]) != 0:
+        raise ValueError("%s: span %d lies inside a lump" % (what, span))
+    lump = int(sk["spanToLump"][span])
+    rs = [int(r) for r in solver.sparseEliminationRanges()]
+    for a, b in zip(rs[:-1], rs[1:]):
+        if a < lump < b:
+            raise ValueError("%s: span %d cuts the sparse-elimination range [%d, %d)" % (what, span, a, b))
+    return int(sk["spanStart"][span])
+
+
+def _check_dest(solver, data, bar, dest, what):
+    if dest is None:
+        return
+    m = solver.order() - bar
+    if not isinstance(dest, torch.Tensor) or dest.dtype != torch.int32 or dest.shape != (m,) \
+            or dest.device != data.device or not dest.is_contiguous():
+        raise ValueError("%s: dest must be a contiguous int32 tensor [%d] on %s" % (what, m, data.device))
+
+
+def _factor_up_to(solver, data, span):
+    P = data.detach().clone(memory_format=torch.contiguous_format)
+    solver.factorUpTo(_members(P) if P.dim() == 2 else P, span)
+    P.masked_fill_(_upper_mask(solver, data.device), 0)
+    return P
+
+
+class _FactorUpTo(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver, data, span):
+        with _OnCurrentStream(solver, data.device):
+            P = _factor_up_to(solver, data, span)
+        ctx.solver, ctx.span = solver, span
+        ctx.save_for_backward(P)
+        ctx.set_materialize_grads(False)
+        return P
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_P):
+        if g_P is None or not ctx.needs_input_grad[1]:
+            return None, None, None
+        (P,) = ctx.saved_tensors
+        solver = ctx.solver
+        with _OnCurrentStream(solver, P.device):
+            grad = g_P.clone(memory_format=torch.contiguous_format)
+            sel = _members if P.dim() == 2 else (lambda t: t)
+            solver.factorAdjointUpTo(sel(P), sel(grad), ctx.span)
+        return None, grad, None
+
+
+class _SchurComplement(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver, data, span, dest):
+        batched = data.dim() == 2
+        sel = _members if batched else (lambda t: t)
+        with _OnCurrentStream(solver, data.device):
+            P = _factor_up_to(solver, data, span)
+            m = solver._schurOrder(span)
+            S = torch.empty(data.shape[:-1] + (m, m), dtype=data.dtype, device=data.device)
+            solver.schurComplement(sel(P), span, out=sel(S), dest=dest)
+        ctx.solver, ctx.span, ctx.dest = solver, span, dest
+        ctx.save_for_backward(P)
+        ctx.set_materialize_grads(False)
+        return S
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_S):
+        if g_S is None or not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        (P,) = ctx.saved_tensors
+        solver = ctx.solver
+        sel = _members if P.dim() == 2 else (lambda t: t)
+        with _OnCurrentStream(solver, P.device):
+            grad = torch.empty_like(P)  # written whole by the adjoint of the extraction
+            solver.schurComplementAdjoint(sel(g_S.contiguous()), ctx.span, out=sel(grad), dest=ctx.dest)
+            solver.factorAdjointUpTo(sel(P), sel(grad), ctx.span)
+        return None, grad, None, None
+
+
+class _SchurOfFactor(torch.autograd.Function):
+    """the dense trailing block of a partial factor P (for callers that also need P itself)"""
+
+    @staticmethod
+    def forward(ctx, solver, P, span, dest):
+        sel = _members if P.dim() == 2 else (lambda t: t)
+        m = solver._schurOrder(span)
+        with _OnCurrentStream(solver, P.device):
+            S = torch.empty(P.shape[:-1] + (m, m), dtype=P.dtype, device=P.device)
+            solver.schurComplement(sel(P.detach().contiguous()), span, out=sel(S), dest=dest)
+        ctx.solver, ctx.span, ctx.dest, ctx.shape = solver, span, dest, P.shape
+        ctx.set_materialize_grads(False)
+        return S
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_S):
+        if g_S is None or not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        solver = ctx.solver
+        sel = _members if len(ctx.shape) == 2 else (lambda t: t)
+        with _OnCurrentStream(solver, g_S.device):
+            grad = torch.empty(ctx.shape, dtype=g_S.dtype, device=g_S.device)
+            solver.schurComplementAdjoint(sel(g_S.contiguous()), ctx.span, out=sel(grad), dest=ctx.dest)
+        return None, grad, None, None
+
+
+class _SolveLUpTo(torch.autograd.Function):
+    """y = M^-1 b, M = [L11 0; L21 I] of the partial factor P"""
+
+    @staticmethod
+    def forward(ctx, solver, P, span, bar, b):
+        batched = P.dim() == 2
+        sel = _members if batched else (lambda t: t)
+        with _OnCurrentStream(solver, P.device):
+            P = P.detach().contiguous()
+            yt = _to_cols(b.detach(), batched)
+            solver.solveLUpTo(sel(P), span, sel(yt), stride=yt.shape[-1], nRHS=yt.shape[-2])
+        ctx.solver, ctx.span, ctx.bar, ctx.b_shape = solver, span, bar, b.shape
+        ctx.save_for_backward(P, yt)
+        ctx.set_materialize_grads(False)
+        return _from_cols(yt, b.shape)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_y):
+        need_P, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[4]
+        if g_y is None or not (need_P or need_b):
+            return None, None, None, None, None
+        solver = ctx.solver
+        P, yt = ctx.saved_tensors
+        batched = P.dim() == 2
+        sel = _members if batched else (lambda t: t)
+        grad_P = grad_b = None
+        with _OnCurrentStream(solver, P.device):
+            bt = _to_cols(g_y, batched)  # b's gradient: M^-T g_y
+            solver.solveLtUpTo(sel(P), ctx.span, sel(bt), stride=bt.shape[-1], nRHS=bt.shape[-2])
+            if need_b:
+                grad_b = _from_cols(bt, ctx.b_shape).clone()
+            if need_P:
+                # Pbar = -bbar y0^T on i >= j, y0 = y zeroed behind the cut: M does not depend on the
+                # columns behind it, which get exactly 0
+                y0 = yt.clone()
+                y0[..., ctx.bar:] = 0
+                grad_P = torch.empty_like(P)
+                solver.patternOuter(sel(grad_P), sel(bt), sel(y0), nRHS=bt.shape[-2], alpha=-1.0,
+                                    stride=bt.shape[-1])
+        return None, grad_P, None, None, grad_b
+
+
+def factor_up_to(solver, data, span):
+    """the partial factor P = [L11 0; L21 S] of A(data) up to `span` (Solver.factorUpTo), in the solver's
+    layout ([dataSize] or [B, dataSize]), differentiable in data.  The strictly-upper elements of the
+    diagonal blocks are 0 and their gradient is ignored."""
+    _check_data(solver, data, "factor_up_to")
+    _check_device(solver, "factor_up_to", data)
+    _check_span(solver, span, "factor_up_to")
+    return _FactorUpTo.apply(solver, data, span)
+
+
+def schur_complement(solver, data, span, dest=None):
+    """the Schur complement S = A22 - A21 A11^-1 A12 of A(data) on the spans from `span` on, dense and
+    symmetric, [m, m] or [B, m, m], differentiable in data.  Rows and columns in the solver's internal
+    order, or at dest[k] for the k-th scalar behind the cut (int32 device permutation)."""
+    _check_data(solver, data, "schur_complement")
+    _check_device(solver, "schur_complement", data)
+    bar = _check_span(solver, span, "schur_complement")
+    if bar == solver.order():
+        raise ValueError("schur_complement: no span behind span %d" % span)
+    _check_dest(solver, data, bar, dest, "schur_complement")
+    return _SchurComplement.apply(solver, data, span, dest)
+
+
+def solve_l_up_to(solver, P, span, b):
+    """y = [L11 0; L21 I]^-1 b for a partial factor P from factor_up_to() (Solver.solveLUpTo),
+    differentiable in P and b (b as for solve).  y[bar:] is the reduced right-hand side
+    b2 - A21 A11^-1 b1."""
+    _check_data(solver, P, "solve_l_up_to")
+    _check_rhs(solver, P, b, "solve_l_up_to")
+    _check_device(solver, "solve_l_up_to", P, b)
+    bar = _check_span(solver, span, "solve_l_up_to")
+    return _SolveLUpTo.apply(solver, P, span, bar, b)

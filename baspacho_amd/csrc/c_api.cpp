@@ -326,10 +326,21 @@ int bsp_test_set_fault(bsp_solver* s, int32_t kind) {
   BSP_CATCH
 }
 
+static int selinvPlanRecords(const bsp_solver* s, bool upTo, int64_t span, int64_t* buf, int64_t capacity,
+                             int64_t* needed);
 int bsp_test_selinv_plan(const bsp_solver* s, int64_t* buf, int64_t capacity, int64_t* needed) {
+  return selinvPlanRecords(s, false, 0, buf, capacity, needed);
+}
+int bsp_test_selinv_plan_up_to(const bsp_solver* s, int64_t span, int64_t* buf, int64_t capacity, int64_t* needed) {
+  return selinvPlanRecords(s, true, span, buf, capacity, needed);
+}
+// the complete plan, or (upTo) the plan of the lumps before the cut at `span`
+static int selinvPlanRecords(const bsp_solver* s, bool upTo, int64_t span, int64_t* buf, int64_t capacity,
+                             int64_t* needed) {
   BSP_TRY
   const CoalescedBlockMatrixSkel& sk = s->solver->skel();
-  const SelInvPlanHost p = buildSelInvPlan(sk);
+  const SelInvPlanHost p =
+      upTo ? buildSelInvPlan(sk, s->solver->partialCutLump("bsp_test_selinv_plan_up_to", span)) : buildSelInvPlan(sk);
   std::unordered_map<int64_t, int64_t> lumpOfOff;  // data offset of a lump column -> lump
   for (int64_t l = 0; l < sk.numLumps(); l++) lumpOfOff[sk.chainData[sk.chainColPtr[l]]] = l;
   std::vector<int64_t> out = {(int64_t)p.levels.size(), (int64_t)p.smalls.size(), (int64_t)p.nodes.size(),
@@ -607,6 +618,61 @@ int bsp_factor_adjoint_batched_f32(bsp_solver* s, const float* const* l, float* 
   factorAdjointBatched(s, l, grad, batch);
   BSP_CATCH
 }
+template <typename T>
+static void factorAdjointUpToBatched(bsp_solver* s, const T* const* p, T* const* grad, int32_t batch, int64_t span) {
+  const char* what = "factorAdjointUpTo";
+  const std::vector<T*> g = hostArray(what, "gradient", grad, batch);
+  s->solver->factorAdjointUpTo(hostArray(what, "factor", p, batch), g, span);
+}
+template <typename T>
+static void schurDenseBatched(bsp_solver* s, const T* const* in, int64_t span, T* const* out, const int32_t* dest,
+                              int32_t batch, bool toDense) {
+  const char* what = toDense ? "schurComplement" : "schurComplementAdjoint";
+  const std::vector<T*> o = hostArray(what, "output", out, batch);
+  const std::vector<T*> i = hostArray(what, "input", in, batch);
+  if (toDense) {
+    s->solver->schurComplement(i, span, o, dest);
+  } else {
+    s->solver->schurComplementAdjoint(i, span, o, dest);
+  }
+}
+#define BSP_PARTIAL_ADJOINT_API(SFX, T)                                                                          \
+  int bsp_factor_adjoint_up_to_##SFX(bsp_solver* s, const T* p, T* grad, int64_t span) {                         \
+    BSP_TRY                                                                                                      \
+    s->solver->factorAdjointUpTo(p, grad, span);                                                                 \
+    BSP_CATCH                                                                                                    \
+  }                                                                                                              \
+  int bsp_factor_adjoint_up_to_batched_##SFX(bsp_solver* s, const T* const* p, T* const* grad, int32_t batch,    \
+                                             int64_t span) {                                                     \
+    BSP_TRY                                                                                                      \
+    factorAdjointUpToBatched(s, p, grad, batch, span);                                                           \
+    BSP_CATCH                                                                                                    \
+  }                                                                                                              \
+  int bsp_schur_to_dense_##SFX(bsp_solver* s, const T* p, int64_t span, T* out, const int32_t* dest) {           \
+    BSP_TRY                                                                                                      \
+    s->solver->schurComplement(p, span, out, dest);                                                              \
+    BSP_CATCH                                                                                                    \
+  }                                                                                                              \
+  int bsp_schur_to_dense_batched_##SFX(bsp_solver* s, const T* const* p, int64_t span, T* const* out,            \
+                                       const int32_t* dest, int32_t batch) {                                     \
+    BSP_TRY                                                                                                      \
+    schurDenseBatched(s, p, span, out, dest, batch, true);                                                       \
+    BSP_CATCH                                                                                                    \
+  }                                                                                                              \
+  int bsp_schur_from_dense_##SFX(bsp_solver* s, const T* gd, int64_t span, T* grad, const int32_t* dest) {       \
+    BSP_TRY                                                                                                      \
+    s->solver->schurComplementAdjoint(gd, span, grad, dest);                                                     \
+    BSP_CATCH                                                                                                    \
+  }                                                                                                              \
+  int bsp_schur_from_dense_batched_##SFX(bsp_solver* s, const T* const* gd, int64_t span, T* const* grad,        \
+                                         const int32_t* dest, int32_t batch) {                                   \
+    BSP_TRY                                                                                                      \
+    schurDenseBatched(s, gd, span, grad, dest, batch, false);                                                    \
+    BSP_CATCH                                                                                                    \
+  }
+BSP_PARTIAL_ADJOINT_API(f64, double)
+BSP_PARTIAL_ADJOINT_API(f32, float)
+#undef BSP_PARTIAL_ADJOINT_API
 struct bsp_assembly {
   std::unique_ptr<AssemblyMap> map;
 };

@@ -132,6 +132,19 @@ void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a);
 // batch runs in memory-bounded chunks, as selected inversion does.
 template <typename T>
 void hipBackendFactorAdjoint(SymbolicCtx& sym, const T* const* L, T* const* grad, int64_t batch, bool single);
+// ... of a partial factor: P[q] holds the factor of the lumps < upToLump with the
+// Schur complement behind them; grad[q] holds Lbar before the cut and Sbar behind it.  The plan of the
+// cut is built on first use and cached; upToLump = numLumps is hipBackendFactorAdjoint.
+template <typename T>
+void hipBackendFactorAdjointUpTo(SymbolicCtx& sym, const T* const* P, T* const* grad, int64_t batch, bool single,
+                                 int64_t upToLump);
+// The trailing block of layout buffers (from lump `fromLump` on) to dense symmetric m x m matrices, m =
+// order - lumpStart[fromLump] (toDense: in = layout buffers, out = dense, every element written), or the
+// adjoint in the data-gradient convention (in = dense gradients, out = layout buffers, written whole).
+// dest: device permutation of 0 .. m-1 (dense row / column of trailing scalar k), NULL = identity.
+template <typename T>
+void hipBackendSchurDense(SymbolicCtx& sym, const T* const* in, T* const* out, int64_t batch, bool single,
+                          int64_t fromLump, const int32_t* dest, bool toDense);
 
 // Assembly of coordinate entries into the layout (hip_assembly_kernels.h), on
 // the execution stream.  `in` / `out` are host arrays of `batch` device pointers (single = true: one

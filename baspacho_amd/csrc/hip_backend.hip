@@ -484,10 +484,13 @@ struct FlagOff {
 struct GradDev {
   DevBuf tiles, firstLump, part;
   int64_t nTiles = 0, nParts = 0, partSlices = 0;
+  vector<int64_t> lumpFirstTile;  // host: first tile of every lump (tiles never cross lumps), then nTiles
   void build(const CoalescedBlockMatrixSkel& sk) {
     vector<hipk::GradTile> tl;
     const int64_t nLumps = sk.numLumps();
+    lumpFirstTile.clear();
     for (int64_t l = 0; l < nLumps; l++) {
+      lumpFirstTile.push_back((int64_t)tl.size());
       const int64_t w = sk.lumpStart[l + 1] - sk.lumpStart[l];
       const int64_t cBeg = sk.chainColPtr[l], cEnd = sk.chainColPtr[l + 1];
       const int64_t R = sk.chainRowsTillEnd[cEnd - 1], base = sk.chainData[cBeg];
@@ -514,6 +517,7 @@ struct GradDev {
       }
     }
     nTiles = (int64_t)tl.size();
+    lumpFirstTile.push_back(nTiles);
     tiles.upload(tl);
     const int64_t n = sk.order();
     nParts = (n + hipk::kLogDetChunk - 1) / hipk::kLogDetChunk;
@@ -538,37 +542,69 @@ struct GradDev {
   }
 };
 
+// Scratch of the selected-inversion plans of one structure (the complete plan and the plans up to a
+// lump of section 16 share it; it grows to the largest).  Per-matrix slices of a plan's element counts,
+// matrix q of a batch chunk in slice q (hipk::SelInvStrides, counted in elements of T).  The buffers are
+// sized in fp64: the fp32 slices, half as many bytes each, are packed into the first half of every buffer
+struct SelInvScratch {
+  DevBuf linv, dd, U, P, Wp;
+  int64_t linvCap = 0, uCap = 0, pCap = 0, wCap = 0;  // fp64 elements allocated
+  bool allocated = false;
+  void release() {
+    allocated = false;
+    for (DevBuf* b : {&linv, &dd, &U, &P, &Wp}) b->release();
+    linvCap = uCap = pCap = wCap = 0;
+  }
+  // slices of plan `h` that fit
+  int64_t slicesFor(const SelInvPlanHost& h) const {
+    if (!allocated) return 0;
+    int64_t n = INT64_MAX;
+    const auto fit = [&n](int64_t cap, int64_t elems) {
+      if (elems > 0) n = std::min(n, cap / elems);
+    };
+    fit(linvCap, h.linvElems);
+    fit(uCap, h.uElems);
+    fit(pCap, h.pElems);
+    fit(wCap, h.wElems);
+    return n;
+  }
+  // grow the scratch to n slices of plan `h`.  Kernels queued by an earlier call (on any stream) may
+  // still use the old buffers: wait for them before freeing (as PtrRing::push does).  No slice counts as
+  // usable until all five allocations have succeeded: a failed grow (an allocation that throws) leaves
+  // nothing allocated, and the next call allocates again instead of launching on released buffers
+  void reserve(const SelInvPlanHost& h, int64_t n) {
+    if (n <= slicesFor(h)) return;
+    if (allocated) hipCHECK(hipDeviceSynchronize());
+    allocated = false;
+    for (DevBuf* b : {&linv, &dd, &U, &P, &Wp}) b->release();
+    const int64_t lc = std::max(linvCap, h.linvElems * n), uc = std::max(uCap, h.uElems * n);
+    const int64_t pc = std::max(pCap, h.pElems * n), wc = std::max(wCap, h.wElems * n);
+    linvCap = uCap = pCap = wCap = 0;
+    const auto bytes = [](int64_t elems) { return (size_t)std::max<int64_t>(elems, 1) * sizeof(double); };
+    linv.resize(bytes(lc));
+    dd.resize(bytes(lc));
+    U.resize(bytes(uc));
+    P.resize(bytes(pc));
+    Wp.resize(bytes(wc));
+    linvCap = lc, uCap = uc, pCap = pc, wCap = wc;
+    allocated = true;
+  }
+};
+
+// selected-inversion plan (hip_plan.h, SelInvPlanHost) on the device, with the shared scratch
 struct SelInvDev {
   SelInvPlanHost host;
   DevBuf smalls, nodes, tiles, zTasks, rowChain, rowLocal, pairOff, pairStr;
-  // scratch: `slices` per-matrix slices of the plan's element counts, matrix q of a batch chunk in
-  // slice q (hipk::SelInvStrides, counted in elements of T).  The buffers are sized in fp64: the fp32
-  // slices, half as many bytes each, are packed into the first half of every buffer
-  DevBuf linv, dd, U, P, Wp;
-  int64_t slices = 0;
+  SelInvScratch* scratch = nullptr;
   hipk::SelInvStrides strides() const { return {host.linvElems, host.uElems, host.pElems, host.wElems}; }
   // fp64 bytes of one slice of every scratch buffer
   int64_t sliceBytes() const {
     return (2 * host.linvElems + host.uElems + host.pElems + host.wElems) * (int64_t)sizeof(double);
   }
-  // grow the scratch to n slices.  Kernels queued by an earlier call (on any stream) may still use the
-  // old buffers: wait for them before freeing (as PtrRing::push does).  No slice counts as usable until
-  // all five allocations have succeeded: a failed grow (an allocation that throws) leaves slices = 0,
-  // and the next call allocates again instead of launching on released buffers
-  void reserve(int64_t n) {
-    if (n <= slices) return;
-    if (slices > 0) hipCHECK(hipDeviceSynchronize());
-    slices = 0;
-    for (DevBuf* b : {&linv, &dd, &U, &P, &Wp}) b->release();
-    const auto bytes = [n](int64_t elems) { return (size_t)std::max<int64_t>(elems * n, 1) * sizeof(double); };
-    linv.resize(bytes(host.linvElems));
-    dd.resize(bytes(host.linvElems));
-    U.resize(bytes(host.uElems));
-    P.resize(bytes(host.pElems));
-    Wp.resize(bytes(host.wElems));
-    slices = n;
-  }
-  void upload() {
+  int64_t slices() const { return scratch->slicesFor(host); }
+  void reserve(int64_t n) { scratch->reserve(host, n); }
+  void upload(SelInvScratch* sc) {
+    scratch = sc;
     smalls.upload(host.smalls);
     nodes.upload(host.nodes);
     tiles.upload(host.tiles);
@@ -649,6 +685,8 @@ struct HipSymbolicCtx : SymbolicCtx {
   void releaseDeviceState() {
     plans.clear();
     selinv.reset();
+    selinvUpTo.clear();
+    selinvScratch.release();
     grad.reset();
     for (hipEvent_t e : events) (void)hipEventDestroy(e);
     events.clear();
@@ -813,16 +851,7 @@ struct HipSymbolicCtx : SymbolicCtx {
     checkDevice();
     SelInvDev& d = selInvPlan();
     const int64_t batch = (int64_t)data.size();
-    int64_t chunk = std::min<int64_t>(batch, 65535);
-    if (selInvChunkCap > 0) chunk = std::min<int64_t>(chunk, selInvChunkCap);
-    const int64_t slice = d.sliceBytes();
-    if (chunk > d.slices && slice > 0) {
-      size_t freeBytes = 0, totalBytes = 0;
-      hipCHECK(hipMemGetInfo(&freeBytes, &totalBytes));
-      const int64_t fit = std::max<int64_t>(d.slices, (int64_t)(freeBytes / 2) / slice);
-      chunk = std::max<int64_t>(1, std::min(chunk, fit));
-    }
-    d.reserve(chunk);
+    const int64_t chunk = selInvChunk(d, batch);
     T* const* many = (T* const*)ptrRing.push(data.data(), data.size() * sizeof(T*), stream);
     for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
       selInvLevels<T>(d, {nullptr, many + q0}, (unsigned)std::min(chunk, batch - q0));
@@ -946,16 +975,7 @@ struct HipSymbolicCtx : SymbolicCtx {
     checkDevice();
     SelInvDev& d = selInvPlan();
     GradDev& g = gradPlan();
-    int64_t chunk = std::min<int64_t>(batch, 65535);
-    if (selInvChunkCap > 0) chunk = std::min<int64_t>(chunk, selInvChunkCap);
-    const int64_t slice = d.sliceBytes();
-    if (chunk > d.slices && slice > 0) {
-      size_t freeBytes = 0, totalBytes = 0;
-      hipCHECK(hipMemGetInfo(&freeBytes, &totalBytes));
-      const int64_t fit = std::max<int64_t>(d.slices, (int64_t)(freeBytes / 2) / slice);
-      chunk = std::max<int64_t>(1, std::min(chunk, fit));
-    }
-    d.reserve(chunk);
+    const int64_t chunk = selInvChunk(d, batch);
     const size_t bytes = batch * sizeof(T*);
     const T* const* lMany = single ? nullptr : (const T* const*)ptrRing.push(L, bytes, stream);
     T* const* gMany = single ? nullptr : (T* const*)ptrRing.push(G, bytes, stream);
@@ -974,6 +994,76 @@ struct HipSymbolicCtx : SymbolicCtx {
     hipCHECK(hipGetLastError());
   }
 
+  // ---- reverse-mode sweep of a partial factor ------------------------------
+  // P[q] = factorUpTo of the lumps < upToLump (read only); grad[q]: Lbar before the cut and Sbar behind
+  // it on entry, the data gradient on return.  Seed the trailing lumps, run the plan of the cut, and
+  // the final pass over every tile.  upToLump = numLumps is factorAdjoint, launch for launch.
+  template <typename T>
+  void factorAdjointUpTo(const T* const* L, T* const* G, int64_t batch, bool single, int64_t upToLump) {
+    if (upToLump == skel.numLumps()) return factorAdjoint<T>(L, G, batch, single);
+    checkDevice();
+    SelInvDev& d = selInvPlanUpTo(upToLump);
+    GradDev& g = gradPlan();
+    const int64_t chunk = selInvChunk(d, batch);
+    const size_t bytes = batch * sizeof(T*);
+    const T* const* lMany = single ? nullptr : (const T* const*)ptrRing.push(L, bytes, stream);
+    T* const* gMany = single ? nullptr : (T* const*)ptrRing.push(G, bytes, stream);
+    const hipk::SkelDev sk = skelDev();
+    const int64_t seed0 = g.lumpFirstTile[upToLump], nSeed = g.nTiles - seed0;
+    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
+      const unsigned nm = (unsigned)std::min(chunk, batch - q0);
+      const hipk::DataRef<const T> lref = single ? hipk::DataRef<const T>{L[0], nullptr}
+                                                 : hipk::DataRef<const T>{nullptr, lMany + q0};
+      const hipk::DataRef<T> gref = single ? hipk::DataRef<T>{G[0], nullptr} : hipk::DataRef<T>{nullptr, gMany + q0};
+      if (nSeed > 0) {
+        hipk::cholAdjSeedTrailing<T><<<dim3((unsigned)nSeed, nm), 256, 0, stream>>>(
+            g.tiles.as<hipk::GradTile>() + seed0, sk, gref);
+      }
+      cholAdjLevels<T>(d, lref, gref, nm);
+      if (g.nTiles > 0) {
+        hipk::cholAdjFinal<T><<<dim3((unsigned)g.nTiles, nm), 256, 0, stream>>>(g.tiles.as<hipk::GradTile>(), sk,
+                                                                               gref);
+      }
+    }
+    hipCHECK(hipGetLastError());
+  }
+
+  // The trailing block (from the first scalar of lump `fromLump` on) of `batch` layout buffers to dense
+  // symmetric m x m matrices (toDense), or the adjoint of that in the data-gradient convention
+  // (!toDense: in = dense gradients, out = layout buffers, written whole).  dest: device permutation of
+  // 0 .. m-1 or NULL.  One launch per chunk of at most 65535 matrices.
+  template <typename T>
+  void schurDense(const T* const* in, T* const* out, int64_t batch, bool single, int64_t fromLump,
+                  const int32_t* dest, bool toDense) {
+    checkDevice();
+    const hipk::SkelDev sk = skelDev();
+    const int64_t bar = skel.lumpStart[fromLump], m = skel.order() - bar;
+    BASPACHO_CHECK_LT(m, (int64_t)INT32_MAX);
+    const int64_t nT = (m + hipk::kSchurTile - 1) / hipk::kSchurTile, nPairs = nT * (nT + 1) / 2;
+    BASPACHO_CHECK_LT(nPairs, (int64_t)INT32_MAX);
+    GradDev* g = toDense ? nullptr : &gradPlan();
+    const int64_t nWork = toDense ? nPairs : g->nTiles;
+    if (nWork == 0) return;
+    const int64_t chunk = std::min<int64_t>(batch, 65535);
+    const size_t bytes = batch * sizeof(T*);
+    const T* const* inMany = single ? nullptr : (const T* const*)ptrRing.push(in, bytes, stream);
+    T* const* outMany = single ? nullptr : (T* const*)ptrRing.push(out, bytes, stream);
+    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
+      const unsigned nm = (unsigned)std::min(chunk, batch - q0);
+      const hipk::DataRef<const T> iref =
+          single ? hipk::DataRef<const T>{in[0], nullptr} : hipk::DataRef<const T>{nullptr, inMany + q0};
+      const hipk::DataRef<T> oref = single ? hipk::DataRef<T>{out[0], nullptr} : hipk::DataRef<T>{nullptr, outMany + q0};
+      if (toDense) {
+        hipk::schurToDense<T><<<dim3((unsigned)nPairs, nm), 256, 0, stream>>>(
+            sk, skel.lumpToSpan[fromLump], skel.numSpans(), bar, m, dest, iref, oref);
+      } else {
+        hipk::schurFromDense<T><<<dim3((unsigned)g->nTiles, nm), 256, 0, stream>>>(
+            g->tiles.as<hipk::GradTile>(), sk, (int)g->lumpFirstTile[fromLump], bar, m, dest, iref, oref);
+      }
+    }
+    hipCHECK(hipGetLastError());
+  }
+
   // one right-to-left pass over the selected-inversion levels for `nMats` matrices (gridDim.y), in
   // scratch slices 0 .. nMats-1.  selinvDiagInverse and selinvZrrTimesU run as they are: the first
   // reads L (it does not write its data), the second multiplies G_RR by the copy of L_RI in U.
@@ -981,11 +1071,11 @@ struct HipSymbolicCtx : SymbolicCtx {
   void cholAdjLevels(const SelInvDev& d, hipk::DataRef<const T> lref, hipk::DataRef<T> gref, unsigned nMats) {
     const hipk::SkelDev sk = skelDev();
     const hipk::SelInvStrides st = d.strides();
-    T* linv = reinterpret_cast<T*>(d.linv.ptr);
-    T* dd = reinterpret_cast<T*>(d.dd.ptr);
-    T* U = reinterpret_cast<T*>(d.U.ptr);
-    T* P = reinterpret_cast<T*>(d.P.ptr);
-    T* Wp = reinterpret_cast<T*>(d.Wp.ptr);
+    T* linv = reinterpret_cast<T*>(d.scratch->linv.ptr);
+    T* dd = reinterpret_cast<T*>(d.scratch->dd.ptr);
+    T* U = reinterpret_cast<T*>(d.scratch->U.ptr);
+    T* P = reinterpret_cast<T*>(d.scratch->P.ptr);
+    T* Wp = reinterpret_cast<T*>(d.scratch->Wp.ptr);
     const hipk::DataRef<T> lmut{const_cast<T*>(lref.single), const_cast<T* const*>(lref.many)};
     const SelInvNode* nodes = d.nodes.as<SelInvNode>();
     const int2* tiles = d.tiles.as<int2>();
@@ -1012,14 +1102,45 @@ struct HipSymbolicCtx : SymbolicCtx {
     }
   }
 
+  // matrices per chunk of a batched pass over plan `d`, with the scratch grown to it: min(batch, 65535
+  // (gridDim.y), what half the free device memory holds in slices -- slices already held count as
+  // free), at least 1, at most the testing cap
+  int64_t selInvChunk(SelInvDev& d, int64_t batch) {
+    int64_t chunk = std::min<int64_t>(batch, 65535);
+    if (selInvChunkCap > 0) chunk = std::min<int64_t>(chunk, selInvChunkCap);
+    const int64_t slice = d.sliceBytes();
+    if (chunk > d.slices() && slice > 0) {
+      size_t freeBytes = 0, totalBytes = 0;
+      hipCHECK(hipMemGetInfo(&freeBytes, &totalBytes));
+      const int64_t fit = std::max<int64_t>(d.slices(), (int64_t)(freeBytes / 2) / slice);
+      chunk = std::max<int64_t>(1, std::min(chunk, fit));
+    }
+    d.reserve(chunk);
+    return chunk;
+  }
+
   SelInvDev& selInvPlan() {
     if (!selinv) {
       std::unique_ptr<SelInvDev> p(new SelInvDev);
       p->host = buildSelInvPlan(skel);
-      p->upload();
+      p->upload(&selinvScratch);
       selinv = std::move(p);
     }
     return *selinv;
+  }
+
+  // the plan of the lumps < upToLump (section 16), cached per cut beside the complete one, as planFor
+  // caches factor plans; all of them work in the one scratch
+  SelInvDev& selInvPlanUpTo(int64_t upToLump) {
+    if (upToLump == skel.numLumps()) return selInvPlan();
+    std::unique_ptr<SelInvDev>& slot = selinvUpTo[upToLump];
+    if (!slot) {
+      std::unique_ptr<SelInvDev> p(new SelInvDev);
+      p->host = buildSelInvPlan(skel, upToLump);
+      p->upload(&selinvScratch);
+      slot = std::move(p);
+    }
+    return *slot;
   }
 
   // one pass over the levels for `nMats` matrices (gridDim.y), in scratch slices 0 .. nMats-1
@@ -1027,11 +1148,11 @@ struct HipSymbolicCtx : SymbolicCtx {
   void selInvLevels(const SelInvDev& d, hipk::DataRef<T> data, unsigned nMats) {
     const hipk::SkelDev sk = skelDev();
     const hipk::SelInvStrides st = d.strides();
-    T* linv = reinterpret_cast<T*>(d.linv.ptr);
-    T* dd = reinterpret_cast<T*>(d.dd.ptr);
-    T* U = reinterpret_cast<T*>(d.U.ptr);
-    T* P = reinterpret_cast<T*>(d.P.ptr);
-    T* Wp = reinterpret_cast<T*>(d.Wp.ptr);
+    T* linv = reinterpret_cast<T*>(d.scratch->linv.ptr);
+    T* dd = reinterpret_cast<T*>(d.scratch->dd.ptr);
+    T* U = reinterpret_cast<T*>(d.scratch->U.ptr);
+    T* P = reinterpret_cast<T*>(d.scratch->P.ptr);
+    T* Wp = reinterpret_cast<T*>(d.scratch->Wp.ptr);
     const SelInvNode* nodes = d.nodes.as<SelInvNode>();
     const int2* tiles = d.tiles.as<int2>();
     const int4* zTasks = d.zTasks.as<int4>();
@@ -1285,6 +1406,8 @@ struct HipSymbolicCtx : SymbolicCtx {
       dChainData, dChainRowsTillEnd, dBoardColPtr, dBoardChainColOrd, dPermutation;
   std::map<std::tuple<int, int64_t, int64_t>, std::unique_ptr<DevPlan>> plans;
   std::unique_ptr<SelInvDev> selinv;  // selected-inversion plan, built on first use
+  std::map<int64_t, std::unique_ptr<SelInvDev>> selinvUpTo;  // ... up to a lump, per cut
+  SelInvScratch selinvScratch;
   std::unique_ptr<GradDev> grad;      // work lists of logDet / patternGrad, built on first use
   int64_t selInvChunkCap = 0;          // TESTING: most matrices per selected-inversion chunk (0: no cap)
 };
@@ -2908,6 +3031,30 @@ void hipBackendFactorAdjoint(SymbolicCtx& sym, const T* const* L, T* const* grad
 }
 template void hipBackendFactorAdjoint<double>(SymbolicCtx&, const double* const*, double* const*, int64_t, bool);
 template void hipBackendFactorAdjoint<float>(SymbolicCtx&, const float* const*, float* const*, int64_t, bool);
+
+template <typename T>
+void hipBackendFactorAdjointUpTo(SymbolicCtx& sym, const T* const* P, T* const* grad, int64_t batch, bool single,
+                                 int64_t upToLump) {
+  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
+  BASPACHO_CHECK_NOTNULL(h);
+  h->factorAdjointUpTo(P, grad, batch, single, upToLump);
+}
+template void hipBackendFactorAdjointUpTo<double>(SymbolicCtx&, const double* const*, double* const*, int64_t, bool,
+                                                  int64_t);
+template void hipBackendFactorAdjointUpTo<float>(SymbolicCtx&, const float* const*, float* const*, int64_t, bool,
+                                                 int64_t);
+
+template <typename T>
+void hipBackendSchurDense(SymbolicCtx& sym, const T* const* in, T* const* out, int64_t batch, bool single,
+                          int64_t fromLump, const int32_t* dest, bool toDense) {
+  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
+  BASPACHO_CHECK_NOTNULL(h);
+  h->schurDense(in, out, batch, single, fromLump, dest, toDense);
+}
+template void hipBackendSchurDense<double>(SymbolicCtx&, const double* const*, double* const*, int64_t, bool, int64_t,
+                                           const int32_t*, bool);
+template void hipBackendSchurDense<float>(SymbolicCtx&, const float* const*, float* const*, int64_t, bool, int64_t,
+                                          const int32_t*, bool);
 
 template <typename T>
 void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a) {

@@ -389,5 +389,266 @@ __global__ void __launch_bounds__(256) cholAdjFinal(const GradTile* __restrict__
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// PARTIAL FACTOR.  For P = [L11 0; L21 S] of factorUpTo the trailing block starts
+// final: dS/dA22 = I, so the incoming Sbar on the lumps >= the cut, put into G storage, is G_22, and
+// only the plan of the lumps before the cut runs (buildSelInvPlan(skel, upToLump)).
+//
+// Seed, over the patternGrad tiles of the trailing lumps (a suffix of the tile list), in place: elements
+// below the diagonal are halved (G_e = Sbar_e / 2), the diagonal is kept, and every halved element of a
+// diagonal block is also written to its mirror slot above the diagonal.  A strictly-upper slot is
+// written by the tile that owns its lower partner and by nobody else, and it is never read here, so
+// tiles do not race.  The mirror goes through LDS (odd row stride: the transposed read is free of
+// bank conflicts) so that loads and both stores run along the lanes.
+template <typename T>
+__global__ void __launch_bounds__(256) cholAdjSeedTrailing(const GradTile* __restrict__ tiles, SkelDev sk,
+                                                           DataRef<T> gref) {
+  constexpr int PER = kGradElems / 256;
+  __shared__ T Ts[kGradElems + kGradRows];
+  const GP<T> G = pickData(gref);
+  const GradTile t = tiles[blockIdx.x];
+  const int64_t w = sk.lumpStart[t.lump + 1] - sk.lumpStart[t.lump];
+  const int nEl = t.nr * t.nc, S = t.nc | 1;
+  // some element of the tile lies in the diagonal block, strictly below the diagonal
+  const bool mirror = t.r0 < w && t.r0 + t.nr - 1 > t.c0;
+#pragma unroll
+  for (int m = 0; m < PER; m++) {
+    const int e = m * 256 + threadIdx.x;
+    if (e < nEl) {
+      const int r = e / t.nc, c = e - r * t.nc;
+      const int64_t lr = t.r0 + r, lc = t.c0 + c;
+      if (lr >= w || lr > lc) {
+        const int64_t a = t.off + r * w + c;
+        const T g = T(0.5) * G[a];
+        G[a] = g;
+        if (mirror) Ts[r * S + c] = g;
+      }
+    }
+  }
+  if (!mirror) return;
+  __syncthreads();
+  const int64_t lumpOff = t.off - t.r0 * w - t.c0;
+#pragma unroll
+  for (int m = 0; m < PER; m++) {
+    const int e = m * 256 + threadIdx.x;
+    if (e < nEl) {
+      const int c = e / t.nr, r = e - c * t.nr;  // consecutive lanes: consecutive columns of the mirror
+      const int64_t lr = t.r0 + r, lc = t.c0 + c;
+      if (lr < w && lr > lc) G[lumpOff + lc * w + lr] = Ts[r * S + c];
+    }
+  }
+}
+
+// ---- the trailing block as a dense matrix ---------------------------------------------------------
+// m = order - bar scalars from internal scalar `bar` on (the start of a lump); dense row / column of
+// internal scalar i: dest[i - bar] (a permutation of 0 .. m-1), or i - bar without dest.
+constexpr int kSchurTile = 64;
+
+// span of internal scalar i, by bisection on spanStart over [s0, numSpans)
+__device__ __forceinline__ int64_t schurSpanOf(const SkelDev& sk, int64_t s0, int64_t numSpans, int64_t i) {
+  int64_t lo = s0, hi = numSpans - 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if (sk.spanStart[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// out (m x m, row-major, symmetric) = the trailing block of the layout buffer P, zero where the pattern
+// has no block.  One workgroup per pair of 64 x 64 output tiles (I, J), I >= J (blockIdx.x = I (I + 1) / 2
+// + J): it finds, for each of its rows and each lump under its columns, the chain that holds the row
+// (none: zeros), gathers the lower tile along the columns, and writes tile (I, J) as it is and tile
+// (J, I) transposed through LDS.  Every output element is written exactly once; `out` is never read.
+template <typename T>
+__global__ void __launch_bounds__(256) schurToDense(SkelDev sk, int64_t span0, int64_t numSpans, int64_t bar,
+                                                    int64_t m, const int32_t* __restrict__ dest,
+                                                    DataRef<const T> pref, DataRef<T> oref) {
+  constexpr int TS = kSchurTile, PER = TS * TS / 256;
+  constexpr size_t kTable = sizeof(int64_t) * TS * TS, kImage = sizeof(T) * TS * (TS + 1);
+  // the chain table (while gathering), then the tile image
+  __shared__ __align__(16) unsigned char raw[kTable > kImage ? kTable : kImage];
+  __shared__ int32_t rowSpan[TS], rowLoc[TS], colLump[TS], ordLump[TS], dR[TS], dC[TS];
+  __shared__ uint8_t colOrd[TS];
+  __shared__ int nOrdS;
+  int64_t* base = reinterpret_cast<int64_t*>(raw);
+  T(*Ts)[TS + 1] = reinterpret_cast<T(*)[TS + 1]>(raw);
+  const GP<const T> P = pickData(pref);
+  const GP<T> out = pickData(oref);
+  const GP<const int32_t> dst = (GP<const int32_t>)dest;
+  const int tid = threadIdx.x;
+  const int64_t p = blockIdx.x;
+  int I = (int)((sqrtf(8.f * (float)p + 1.f) - 1.f) * 0.5f);
+  while ((int64_t)(I + 1) * (I + 2) / 2 <= p) I++;
+  while ((int64_t)I * (I + 1) / 2 > p) I--;
+  const int J = (int)(p - (int64_t)I * (I + 1) / 2);
+  const int64_t i0 = (int64_t)I * TS, j0 = (int64_t)J * TS;  // counted from bar
+  const int nr = (int)min((int64_t)TS, m - i0), nc = (int)min((int64_t)TS, m - j0);
+  if (tid < TS) {
+    const int r = tid;
+    int32_t sp = 0, loc = 0, d = 0;
+    if (r < nr) {
+      const int64_t i = bar + i0 + r;
+      const int64_t s = schurSpanOf(sk, span0, numSpans, i);
+      sp = (int32_t)s;
+      loc = (int32_t)(i - sk.spanStart[s]);
+      d = dest ? dst[i0 + r] : (int32_t)(i0 + r);
+    }
+    rowSpan[r] = sp;
+    rowLoc[r] = loc;
+    dR[r] = d;
+  } else if (tid < 2 * TS) {
+    const int c = tid - TS;
+    int32_t l = -1, d = 0;
+    if (c < nc) {
+      const int64_t j = bar + j0 + c;
+      l = (int32_t)sk.spanToLump[schurSpanOf(sk, span0, numSpans, j)];
+      d = dest ? dst[j0 + c] : (int32_t)(j0 + c);
+    }
+    colLump[c] = l;
+    dC[c] = d;
+  }
+  __syncthreads();
+  if (tid < TS) {  // wave 0: ordinal of every column's lump among the lumps under the tile's columns
+    const int c = tid;
+    const bool first = c < nc && (c == 0 || colLump[c] != colLump[c - 1]);
+    const unsigned long long firsts = __ballot(first);
+    const int o = __popcll(firsts & (~0ull >> (63 - c))) - 1;
+    if (first) ordLump[o] = colLump[c];
+    if (c < nc) colOrd[c] = (uint8_t)o;
+    if (c == 0) nOrdS = __popcll(firsts);
+  }
+  __syncthreads();
+  const int nOrd = nOrdS;
+  // base[r][o]: data offset of (row r, scalar 0) in lump o's column, so that element (r, j) is at
+  // base + j (j an internal scalar); -1 where lump o has no block on the span of row r
+  for (int x = tid; x < nr * nOrd; x += 256) {
+    const int r = x / nOrd, o = x - r * nOrd;
+    const int64_t L = ordLump[o], sa = rowSpan[r];
+    int64_t lo = sk.chainColPtr[L], hi = sk.chainColPtr[L + 1] - 1;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (sk.chainRowSpan[mid] < sa) lo = mid + 1; else hi = mid;
+    }
+    int64_t b = -1;
+    if (sk.chainRowSpan[lo] == sa) {
+      const int64_t l0 = sk.lumpStart[L];
+      b = sk.chainData[lo] + (int64_t)rowLoc[r] * (sk.lumpStart[L + 1] - l0) - l0;
+    }
+    base[r * TS + o] = b;
+  }
+  __syncthreads();
+  T v[PER];
+#pragma unroll
+  for (int q = 0; q < PER; q++) {
+    const int e = q * 256 + tid, r = e / TS, c = e % TS;
+    T x = T(0);
+    if (r < nr && c < nc && i0 + r >= j0 + c) {
+      const int64_t b = base[r * TS + colOrd[c]];
+      if (b >= 0) x = P[b + bar + j0 + c];
+    }
+    v[q] = x;
+  }
+  __syncthreads();  // the table is dead: its bytes take the image
+#pragma unroll
+  for (int q = 0; q < PER; q++) {
+    const int e = q * 256 + tid;
+    Ts[e / TS][e % TS] = v[q];
+  }
+  __syncthreads();
+  if (I == J) {
+#pragma unroll
+    for (int q = 0; q < PER; q++) {
+      const int e = q * 256 + tid, r = e / TS, c = e % TS;
+      if (r < nr && c < nc) out[(int64_t)dR[r] * m + dC[c]] = r >= c ? Ts[r][c] : Ts[c][r];
+    }
+    return;
+  }
+#pragma unroll
+  for (int q = 0; q < PER; q++) {
+    const int e = q * 256 + tid, r = e / TS, c = e % TS;
+    if (r < nr && c < nc) out[(int64_t)dR[r] * m + dC[c]] = v[q];
+  }
+#pragma unroll
+  for (int q = 0; q < PER; q++) {
+    const int e = q * 256 + tid, c = e / TS, r = e % TS;  // consecutive lanes: consecutive columns of (J, I)
+    if (r < nr && c < nc) out[(int64_t)dC[c] * m + dR[r]] = Ts[r][c];
+  }
+}
+
+// The adjoint of schurToDense in the data-gradient convention, over ALL patternGrad tiles (the whole
+// buffer is written, never read): for a stored element e = (i, j) of a lump behind the cut
+// Gd[i, j] + Gd[j, i] below the diagonal, Gd[i, i] on it, 0 above it; 0 for every element of a lump
+// before the cut (tiles < firstTrailing).  Gd is any dense m x m matrix (it need not be symmetric).
+// The Gd[j, i] of a tile are read along its rows into LDS, so both reads run along the lanes.
+template <typename T>
+__global__ void __launch_bounds__(256) schurFromDense(const GradTile* __restrict__ tiles, SkelDev sk,
+                                                      int firstTrailing, int64_t bar, int64_t m,
+                                                      const int32_t* __restrict__ dest, DataRef<const T> gdref,
+                                                      DataRef<T> oref) {
+  constexpr int PER = kGradElems / 256;
+  __shared__ T Ts[kGradElems + kGradRows];
+  __shared__ int32_t rowI[kGradRows], dI[kGradRows], dJ[kGradCols];
+  const GP<const T> Gd = pickData(gdref);
+  const GP<T> out = pickData(oref);
+  const GP<const int32_t> dst = (GP<const int32_t>)dest;
+  const GradTile t = tiles[blockIdx.x];
+  const int tid = threadIdx.x;
+  const int64_t l0 = sk.lumpStart[t.lump];
+  const int64_t w = sk.lumpStart[t.lump + 1] - l0;
+  const int nEl = t.nr * t.nc, S = t.nc | 1;
+  if ((int)blockIdx.x < firstTrailing) {
+#pragma unroll
+    for (int q = 0; q < PER; q++) {
+      const int e = q * 256 + tid;
+      if (e < nEl) {
+        const int r = e / t.nc, c = e - r * t.nc;
+        out[t.off + r * w + c] = T(0);
+      }
+    }
+    return;
+  }
+  const int64_t jb = l0 + t.c0 - bar;  // tile column 0, counted from bar
+  if (tid < t.nr) {  // as patternGradTiles: the scalar of every tile row
+    const int64_t r = t.r0 + tid;
+    int32_t lo = t.chain, hi = t.chainEnd - 1;
+    while (lo < hi) {
+      const int32_t mid = (lo + hi) >> 1;
+      if (sk.chainRowsTillEnd[mid] > r) hi = mid; else lo = mid + 1;
+    }
+    const int64_t sp = sk.chainRowSpan[lo];
+    const int64_t s0 = sk.spanStart[sp], rows = sk.spanStart[sp + 1] - s0;
+    const int64_t i = s0 + r - (sk.chainRowsTillEnd[lo] - rows) - bar;
+    rowI[tid] = (int32_t)i;
+    dI[tid] = dest ? dst[i] : (int32_t)i;
+  } else if (tid >= kGradRows && tid < kGradRows + t.nc) {
+    const int c = tid - kGradRows;
+    dJ[c] = dest ? dst[jb + c] : (int32_t)(jb + c);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < PER; q++) {
+    const int e = q * 256 + tid;
+    if (e < nEl) {
+      const int c = e / t.nr, r = e - c * t.nr;
+      if (rowI[r] > jb + c) Ts[r * S + c] = Gd[(int64_t)dJ[c] * m + dI[r]];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < PER; q++) {
+    const int e = q * 256 + tid;
+    if (e < nEl) {
+      const int r = e / t.nc, c = e - r * t.nc;
+      const int64_t i = rowI[r], j = jb + c;
+      T x = T(0);
+      if (i >= j) {
+        x = Gd[(int64_t)dI[r] * m + dJ[c]];
+        if (i > j) x += Ts[r * S + c];
+      }
+      out[t.off + r * w + c] = x;
+    }
+  }
+}
+
 }  // namespace hipk
 }  // namespace BaSpaCho

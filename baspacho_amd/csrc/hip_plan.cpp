@@ -1141,9 +1141,13 @@ SolveGatherPlan buildSolveGather(const CoalescedBlockMatrixSkel& sk, const HipPl
   return out;
 }
 
-SelInvPlanHost buildSelInvPlan(const CoalescedBlockMatrixSkel& sk) {
+SelInvPlanHost buildSelInvPlan(const CoalescedBlockMatrixSkel& sk) { return buildSelInvPlan(sk, sk.numLumps()); }
+
+SelInvPlanHost buildSelInvPlan(const CoalescedBlockMatrixSkel& sk, int64_t upToLump) {
   SelInvPlanHost p;
   const int64_t nLumps = sk.numLumps();
+  BASPACHO_CHECK_GE(upToLump, 0);
+  BASPACHO_CHECK_LE(upToLump, nLumps);
   constexpr int64_t W = kSelInvW;
   struct Pending {
     int64_t lump;
@@ -1157,13 +1161,14 @@ SelInvPlanHost buildSelInvPlan(const CoalescedBlockMatrixSkel& sk) {
     if ((int64_t)byLevel.size() <= level) byLevel.resize(level + 1);
     byLevel[level].push_back(q);
   };
-  for (int64_t l = nLumps - 1; l >= 0; l--) {
+  for (int64_t l = upToLump - 1; l >= 0; l--) {
     const LumpCols g = lumpCols(sk, l);
     const int64_t firstBelow = g.chain0 + g.diagChains, k = g.nChains - g.diagChains;
     int64_t base = 0;
     for (int64_t c = firstBelow; c < g.chain0 + g.nChains; c++) {
       const int64_t J = sk.spanToLump[sk.chainRowSpan[c]];
       BASPACHO_CHECK_GT(J, l);
+      // rows owned by a lump >= upToLump are final before the sweep starts (doneLevel stays -1)
       base = std::max(base, doneLevel[J] + 1);
     }
     if (g.width <= kSelInvSmallW && k <= kSelInvSmallChains &&

@@ -424,5 +424,10 @@ struct SelInvPlanHost {
 
 // levels in launch order (roots first)
 SelInvPlanHost buildSelInvPlan(const CoalescedBlockMatrixSkel& skel);
+// ... of the lumps < upToLump alone (the reverse sweep of a partial factor): a
+// row span owned by a lump >= upToLump is final and gives no dependency, so the levels are counted
+// among the leading lumps only; the pair and row tables still resolve rows in trailing lumps.
+// upToLump = numLumps is the plan above, record for record.
+SelInvPlanHost buildSelInvPlan(const CoalescedBlockMatrixSkel& skel, int64_t upToLump);
 
 }  // namespace BaSpaCho

@@ -770,6 +770,107 @@ void Solver::factorAdjoint(const std::vector<T*>& L, const std::vector<T*>& grad
   runFactorAdjoint(*this, *symCtx, false, L, grad);
 }
 
+// ---- reverse-mode sweep of the partial factor and its dense Schur complement ----
+// the lump of a span that factorUpTo accepts as its end; anything else throws before any device work
+int64_t Solver::partialCutLump(const char* what, int64_t spanIndex) const {
+  const int64_t nSpans = factorSkel.numSpans();
+  checkCompleteFactor(what, canFactorUpTo, nSpans);
+  if (spanIndex < 0 || spanIndex > nSpans) {
+    throw std::runtime_error(std::string(what) + ": span " + std::to_string(spanIndex) + " is not in [0, " +
+                             std::to_string(nSpans) + "]");
+  }
+  if (factorSkel.spanOffsetInLump[spanIndex] != 0) {
+    throw std::runtime_error(std::string(what) + ": span " + std::to_string(spanIndex) +
+                             " lies inside a lump (a partial factor ends at a lump boundary)");
+  }
+  const int64_t lump = factorSkel.spanToLump[spanIndex];
+  for (size_t r = 0; r + 1 < sparseElimRanges.size(); r++) {
+    if (sparseElimRanges[r] < lump && lump < sparseElimRanges[r + 1]) {
+      throw std::runtime_error(std::string(what) + ": span " + std::to_string(spanIndex) + " (lump " +
+                               std::to_string(lump) + ") cuts the sparse-elimination range [" +
+                               std::to_string(sparseElimRanges[r]) + ", " +
+                               std::to_string(sparseElimRanges[r + 1]) + ")");
+    }
+  }
+  return lump;
+}
+
+template <typename T>
+static void runFactorAdjointUpTo(const Solver& s, SymbolicCtx& sym, bool single, const std::vector<T*>& P,
+                                 const std::vector<T*>& grad, int64_t spanIndex) {
+  const char* what = "factorAdjointUpTo";
+  if (grad.empty()) throw std::runtime_error("factorAdjointUpTo: the batch is empty");
+  checkMembers(what, "grad", grad, grad.size());
+  checkMembers(what, "P", P, grad.size());
+  const size_t bytes = s.dataSize() * sizeof(T);
+  checkNoOverlap(what, grad, bytes, std::vector<const T*>(P.begin(), P.end()), bytes);
+  const int64_t lump = s.partialCutLump(what, spanIndex);
+  std::vector<const T*> p(P.begin(), P.end());
+  hipBackendFactorAdjointUpTo<T>(sym, p.data(), grad.data(), (int64_t)grad.size(), single, lump);
+}
+
+template <typename T>
+void Solver::factorAdjointUpTo(const T* P, T* grad, int64_t spanIndex) const {
+  runFactorAdjointUpTo(*this, *symCtx, true, std::vector<T*>{const_cast<T*>(P)}, std::vector<T*>{grad}, spanIndex);
+}
+
+template <typename T>
+void Solver::factorAdjointUpTo(const std::vector<T*>& P, const std::vector<T*>& grad, int64_t spanIndex) const {
+  runFactorAdjointUpTo(*this, *symCtx, false, P, grad, spanIndex);
+}
+
+// toDense: in = layout buffers, out = dense m x m; else in = dense gradients, out = layout buffers
+template <typename T>
+static void runSchurDense(const Solver& s, SymbolicCtx& sym, const char* what, bool single,
+                          const std::vector<T*>& in, const std::vector<T*>& out, int64_t spanIndex,
+                          const int32_t* dest, bool toDense) {
+  if (out.empty()) throw std::runtime_error(std::string(what) + ": the batch is empty");
+  checkMembers(what, "out", out, out.size());
+  checkMembers(what, "in", in, out.size());
+  const int64_t lump = s.partialCutLump(what, spanIndex);
+  const int64_t m = s.order() - s.skel().spanStart[spanIndex];
+  if (m == 0) throw std::runtime_error(std::string(what) + ": no span behind span " + std::to_string(spanIndex));
+  const size_t dataBytes = s.dataSize() * sizeof(T), denseBytes = (size_t)m * m * sizeof(T);
+  checkNoOverlap(what, out, toDense ? denseBytes : dataBytes, std::vector<const T*>(in.begin(), in.end()),
+                 toDense ? dataBytes : denseBytes);
+  std::vector<const T*> i(in.begin(), in.end());
+  hipBackendSchurDense<T>(sym, i.data(), out.data(), (int64_t)out.size(), single, lump, dest, toDense);
+}
+
+template <typename T>
+void Solver::schurComplement(const T* P, int64_t spanIndex, T* out, const int32_t* dest) const {
+  runSchurDense(*this, *symCtx, "schurComplement", true, std::vector<T*>{const_cast<T*>(P)}, std::vector<T*>{out},
+                spanIndex, dest, true);
+}
+template <typename T>
+void Solver::schurComplement(const std::vector<T*>& P, int64_t spanIndex, const std::vector<T*>& out,
+                             const int32_t* dest) const {
+  runSchurDense(*this, *symCtx, "schurComplement", false, P, out, spanIndex, dest, true);
+}
+template <typename T>
+void Solver::schurComplementAdjoint(const T* gradDense, int64_t spanIndex, T* gradData, const int32_t* dest) const {
+  runSchurDense(*this, *symCtx, "schurComplementAdjoint", true, std::vector<T*>{const_cast<T*>(gradDense)},
+                std::vector<T*>{gradData}, spanIndex, dest, false);
+}
+template <typename T>
+void Solver::schurComplementAdjoint(const std::vector<T*>& gradDense, int64_t spanIndex,
+                                    const std::vector<T*>& gradData, const int32_t* dest) const {
+  runSchurDense(*this, *symCtx, "schurComplementAdjoint", false, gradDense, gradData, spanIndex, dest, false);
+}
+
+#define BSP_INSTANTIATE_PARTIAL_ADJOINT(T)                                                                    \
+  template void Solver::factorAdjointUpTo<T>(const T*, T*, int64_t) const;                                    \
+  template void Solver::factorAdjointUpTo<T>(const std::vector<T*>&, const std::vector<T*>&, int64_t) const;  \
+  template void Solver::schurComplement<T>(const T*, int64_t, T*, const int32_t*) const;                      \
+  template void Solver::schurComplement<T>(const std::vector<T*>&, int64_t, const std::vector<T*>&,           \
+                                           const int32_t*) const;                                             \
+  template void Solver::schurComplementAdjoint<T>(const T*, int64_t, T*, const int32_t*) const;               \
+  template void Solver::schurComplementAdjoint<T>(const std::vector<T*>&, int64_t, const std::vector<T*>&,    \
+                                                  const int32_t*) const;
+BSP_INSTANTIATE_PARTIAL_ADJOINT(double)
+BSP_INSTANTIATE_PARTIAL_ADJOINT(float)
+#undef BSP_INSTANTIATE_PARTIAL_ADJOINT
+
 template void Solver::patternOuter<double>(const double*, const double*, int64_t, int, double, double*) const;
 template void Solver::patternOuter<float>(const float*, const float*, int64_t, int, float, float*) const;
 template void Solver::patternOuter<double>(const std::vector<double*>&, const std::vector<double*>&, int64_t, int,

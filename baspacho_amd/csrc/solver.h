@@ -133,6 +133,40 @@ class Solver {
   template <typename T>
   void factorAdjoint(const std::vector<T*>& L, const std::vector<T*>& grad) const;
 
+  // extension: reverse-mode sweep of factorUpTo().  `P` holds factorUpTo(spanIndex)
+  // of A(d): [L11 0; L21 S], S = A22 - A21 A11^-1 A12 on the spans from spanIndex on; it is only read.
+  // `grad` holds df/dP_e on entry for every stored element i >= j (Lbar on the columns before the cut,
+  // Sbar behind it; strictly-upper elements ignored) and df/dd on return.  spanIndex = numSpans() is
+  // factorAdjoint; spanIndex = 0 returns the input (strictly-upper elements zeroed).  Stream, batch
+  // form and chunks as factorAdjoint.  Refused before any device work: a span that factorUpTo refuses
+  // (inside a lump, cutting a sparse-elimination range), NULL or overlapping buffers, an empty batch,
+  // a Solver that cannot factor completely.
+  template <typename T>
+  void factorAdjointUpTo(const T* P, T* grad, int64_t spanIndex) const;
+  template <typename T>
+  void factorAdjointUpTo(const std::vector<T*>& P, const std::vector<T*>& grad, int64_t spanIndex) const;
+  // schurComplement: the trailing block of a layout buffer (rows and columns from span spanIndex on, m =
+  // order() - spanStart[spanIndex] scalars) as a dense symmetric m x m matrix, row-major: out[dest[i] m +
+  // dest[j]] for trailing scalars i, j counted from the cut, zero where the pattern has no block.  Every
+  // element of `out` is written, none is read.  dest: DEVICE permutation of 0 .. m-1, NULL = identity.
+  // schurComplementAdjoint: its adjoint in patternGrad's convention; every element of gradData is
+  // written: gradDense[i, j] + gradDense[j, i] below the diagonal, gradDense[i, i] on it, 0 above it and
+  // on every column before the cut.  gradDense need not be symmetric.  Span checks as factorAdjointUpTo.
+  template <typename T>
+  void schurComplement(const T* P, int64_t spanIndex, T* out, const int32_t* dest = nullptr) const;
+  template <typename T>
+  void schurComplement(const std::vector<T*>& P, int64_t spanIndex, const std::vector<T*>& out,
+                       const int32_t* dest = nullptr) const;
+  template <typename T>
+  void schurComplementAdjoint(const T* gradDense, int64_t spanIndex, T* gradData,
+                              const int32_t* dest = nullptr) const;
+  template <typename T>
+  void schurComplementAdjoint(const std::vector<T*>& gradDense, int64_t spanIndex,
+                              const std::vector<T*>& gradData, const int32_t* dest = nullptr) const;
+  // the lump at which a partial factor up to spanIndex ends; throws (prefix `what`) for a span that
+  // factorUpTo refuses and for a Solver that cannot factor completely
+  int64_t partialCutLump(const char* what, int64_t spanIndex) const;
+
   // extension: assembly of coordinate entries (row, col, value) into this Solver's layout (DESIGN.md
   // section 14; assembly.h).  `map` comes from createAssemblyMap(*this, ...).  assemble writes every
   // element of `data` (never read): the sum, in ascending entry index from +0, of the values of the

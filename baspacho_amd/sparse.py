@@ -7,6 +7,8 @@
     x, ld = S.solve_logdet(pat, values, b)         # both, one factor
     data = S.assemble(pat, values)                 # the solver's layout, for baspacho_amd.autograd
     x = S.sample(pat, values, z, mu)               # x = mu + L^-T z: Cov(x) = A^-1
+    pat = S.SymmetricPattern(rows, cols, n, keep=kept)     # kept scalars ordered last
+    Sk, rk = S.marginalize(pat, values, b)         # marginal precision / information of the kept scalars
 
 The matrix is given by entries (rows[k], cols[k], values[k]) in the caller's scalar order: A_ij = A_ji =
 the sum of the values of the entries at (i, j), i >= j.  `values` is [nnz] or a
@@ -18,6 +20,10 @@ solve / logdet / solve_logdet and a permutation of the vectors.  Everything runs
 torch.cuda.current_stream() without host synchronisation, and the solver's own stream is restored
 afterwards; the first call on a device uploads the assembly map and the permutation.  Double backward
 is not supported.
+
+marginalize eliminates every scalar outside `keep`: S = A22 - A21 A11^-1 A12 and
+r = b2 - A21 A11^-1 b1 with block 2 the kept scalars, rows and columns in the order of `keep`.  inv(S) is
+the `keep` block of inv(A): S and r are the precision and the information vector of the marginal.
 """
 import numpy as np
 import torch
@@ -27,7 +33,7 @@ from . import Settings, SparseStructure, create_solver
 from . import autograd as _ag
 from .autograd import _OnCurrentStream
 
-__all__ = ["SymmetricPattern", "assemble", "solve", "logdet", "solve_logdet", "sample"]
+__all__ = ["SymmetricPattern", "assemble", "solve", "logdet", "solve_logdet", "sample", "marginalize"]
 
 
 def _host_i64(a):
@@ -51,9 +57,11 @@ class SymmetricPattern:
     `param_sizes` (default: all 1) in order; the param-level lower block structure is derived from the
     entries and handed to create_solver (fill and ordering as `settings` say).  triangle: "lower"
     (every entry has row >= col) or "full" (entries with row < col are skipped; the caller asserts the
-    matrix is symmetric).  Invalid entries are refused by the assembly, which names the first one."""
+    matrix is symmetric).  Invalid entries are refused by the assembly, which names the first one.
+    keep: caller-order scalar indices (distinct, covering whole params) that marginalize() keeps; their
+    params are ordered behind all others, from span `keep_span` on."""
 
-    def __init__(self, rows, cols, n, param_sizes=None, settings=None, triangle="lower"):
+    def __init__(self, rows, cols, n, param_sizes=None, settings=None, triangle="lower", keep=None):
         rows, cols = _host_i64(rows), _host_i64(cols)
         if len(rows) != len(cols):
             raise ValueError("SymmetricPattern: %d rows for %d cols" % (len(rows), len(cols)))
@@ -69,13 +77,37 @@ class SymmetricPattern:
         self.n = n
         self.param_sizes = ps
         self.structure = ss
-        self.solver = create_solver(settings or Settings(), ps, ss)
+        keep_params = ()
+        if keep is not None:
+            keep = _host_i64(keep)
+            if len(keep) == 0 or np.any(keep < 0) or np.any(keep >= n) or len(np.unique(keep)) != len(keep):
+                raise ValueError("SymmetricPattern: keep must hold distinct scalar indices in [0, %d), at least one" % n)
+            keep_params = np.unique(param_of(keep))
+            if int(ps[keep_params].sum()) != len(keep):
+                raise ValueError("SymmetricPattern: keep must cover whole params (it touches %d params of %d "
+                                 "scalars with %d indices)" % (len(keep_params), int(ps[keep_params].sum()), len(keep)))
+        self.solver = create_solver(settings or Settings(), ps, ss, elim_last_ids=[int(p) for p in keep_params])
         self.assembly = self.solver.assembly(rows, cols, triangle)
         self.nnz = len(rows)
         perm = self.solver.scalarPermutation()
         self._to_user = perm                 # internal -> user: x_user = x_int[perm]
         self._to_internal = np.argsort(perm)  # user -> internal: v_int = v_user[inv]
         self._dev = {}
+        self.keep = keep
+        self.keep_span = None
+        if keep is not None:
+            sol, sk = self.solver, self.solver.skel()
+            spans = np.sort(sol.paramToSpan()[keep_params])
+            self.keep_span = int(spans[0])
+            if not np.array_equal(spans, np.arange(self.keep_span, sol.numSpans())) \
+                    or int(sk["spanOffsetInLump"][self.keep_span]) != 0:
+                raise RuntimeError("SymmetricPattern: the solver did not place the kept params behind a lump "
+                                   "boundary (spans %s of %d)" % (spans.tolist(), sol.numSpans()))
+            bar = int(sk["spanStart"][self.keep_span])
+            self._keep_internal = perm[keep]  # internal scalar of keep[t]
+            dest = np.empty(n - bar, dtype=np.int32)
+            dest[self._keep_internal - bar] = np.arange(len(keep), dtype=np.int32)
+            self._keep_dest = dest            # position in keep of the k-th scalar behind the cut
 
     @staticmethod
     def from_torch(A, param_sizes=None, settings=None, triangle="lower"):
@@ -99,7 +131,9 @@ class SymmetricPattern:
     def _index(self, which, device):
         key = (which, device)
         if key not in self._dev:
-            src = self._to_internal if which == "to_internal" else self._to_user
+            src = {"to_internal": self._to_internal, "to_user": self._to_user,
+                   "keep_internal": getattr(self, "_keep_internal", None),
+                   "keep_dest": getattr(self, "_keep_dest", None)}[which]
             self._dev[key] = torch.from_numpy(src).to(device)
         return self._dev[key]
 
@@ -209,3 +243,25 @@ def sample(pattern, values, z, mu=None):
     L = _ag.cholesky(pattern.solver, assemble(pattern, values))
     x = pattern.fromInternal(_ag.solve_lt(pattern.solver, L, pattern.toInternal(z, dim)), dim)
     return x if mu is None else mu + x
+
+
+def marginalize(pattern, values, b=None):
+    """S = A22 - A21 A11^-1 A12, [m, m] (or [B, m, m]), block 2 = pattern.keep, rows and columns in the order
+    of keep: the marginal precision of the kept scalars.  With b ([n] or [n, k], leading B when batched)
+    also r = b2 - A21 A11^-1 b1, [m] or [m, k]: their information vector.  Differentiable in values and b.
+    Needs a pattern built with keep=..."""
+    _check_values(pattern, values, "marginalize")
+    if pattern.keep is None:
+        raise ValueError("marginalize: the pattern was built without keep=...")
+    sol, span = pattern.solver, pattern.keep_span
+    dest = pattern._index("keep_dest", values.device)
+    data = assemble(pattern, values)
+    if b is None:
+        return _ag.schur_complement(sol, data, span, dest=dest)
+    dim = _check_b(pattern, values, b, "marginalize")
+    if b.dtype != values.dtype:
+        raise TypeError("marginalize: b has dtype %s, values have %s" % (b.dtype, values.dtype))
+    P = _ag.factor_up_to(sol, data, span)
+    S = _ag._SchurOfFactor.apply(sol, P, span, dest)
+    y = _ag.solve_l_up_to(sol, P, span, pattern.toInternal(b, dim))
+    return S, y.index_select(dim, pattern._index("keep_internal", values.device))

@@ -310,6 +310,47 @@ int bsp_factor_adjoint_batched_f64(bsp_solver* s, const double* const* dev_l, do
                                    int32_t batch);
 int bsp_factor_adjoint_batched_f32(bsp_solver* s, const float* const* dev_l, float* const* dev_grad,
                                    int32_t batch);
+/* bsp_factor_adjoint_up_to_*: the reverse-mode sweep of bsp_factor_up_to_* (DESIGN.md section 16).  dev_p
+   holds factorUpTo(span) of A(d) -- the factor L11, L21 on the columns before the cut and the Schur
+   complement S = A22 - A21 A11^-1 A12 behind it -- and is only read.  dev_grad holds df/dP_e on entry
+   for every stored element with i >= j (Lbar before the cut, Sbar behind it; the strictly-upper
+   elements of the diagonal blocks are ignored) and df/dd on return, in bsp_pattern_grad_*'s
+   convention.  Only the lumps before the cut are swept (a plan of their own, cached per cut; the
+   scratch is shared with bsp_selected_inverse_*).  span == bsp_num_spans is bsp_factor_adjoint_*, bit
+   for bit; span == 0 returns the input with the strictly-upper elements zeroed.  Batched form as
+   bsp_factor_adjoint_batched_*.  Non-zero return before any device work, buffers untouched: a span that
+   bsp_factor_up_to_* refuses (inside a lump, cutting a sparse-elimination range, out of range),
+   dev_grad == dev_p or overlapping buffers, a NULL pointer, batch <= 0, a solver that cannot factor
+   completely. */
+int bsp_factor_adjoint_up_to_f64(bsp_solver* s, const double* dev_p, double* dev_grad, int64_t span);
+int bsp_factor_adjoint_up_to_f32(bsp_solver* s, const float* dev_p, float* dev_grad, int64_t span);
+int bsp_factor_adjoint_up_to_batched_f64(bsp_solver* s, const double* const* dev_p, double* const* dev_grad,
+                                         int32_t batch, int64_t span);
+int bsp_factor_adjoint_up_to_batched_f32(bsp_solver* s, const float* const* dev_p, float* const* dev_grad,
+                                         int32_t batch, int64_t span);
+/* bsp_schur_to_dense_*: the trailing block of a layout buffer (rows and columns from `span` on; m = order
+   - first scalar of span) as a dense symmetric m x m matrix, row-major: dev_out[dest[i] * m + dest[j]] for
+   trailing scalars i, j counted from the cut; zero where the pattern has no block.  All m * m elements
+   are written, none is read.  dev_dest: DEVICE int32[m], a permutation of 0 .. m-1, or NULL (identity).
+   bsp_schur_from_dense_*: its adjoint in bsp_pattern_grad_*'s convention.  EVERY element of dev_grad
+   (data size) is written: g[i, j] + g[j, i] below the diagonal of the trailing block, g[i, i] on it, 0 on
+   the strictly-upper elements and on every column before the cut; dev_grad_dense need not be symmetric.
+   Span checks and batched forms (HOST arrays of `batch` device pointers, one dev_dest for all) as
+   bsp_factor_adjoint_up_to_*; span == bsp_num_spans (m = 0) is refused. */
+int bsp_schur_to_dense_f64(bsp_solver* s, const double* dev_p, int64_t span, double* dev_out, const int32_t* dev_dest);
+int bsp_schur_to_dense_f32(bsp_solver* s, const float* dev_p, int64_t span, float* dev_out, const int32_t* dev_dest);
+int bsp_schur_to_dense_batched_f64(bsp_solver* s, const double* const* dev_p, int64_t span, double* const* dev_out,
+                                   const int32_t* dev_dest, int32_t batch);
+int bsp_schur_to_dense_batched_f32(bsp_solver* s, const float* const* dev_p, int64_t span, float* const* dev_out,
+                                   const int32_t* dev_dest, int32_t batch);
+int bsp_schur_from_dense_f64(bsp_solver* s, const double* dev_grad_dense, int64_t span, double* dev_grad,
+                             const int32_t* dev_dest);
+int bsp_schur_from_dense_f32(bsp_solver* s, const float* dev_grad_dense, int64_t span, float* dev_grad,
+                             const int32_t* dev_dest);
+int bsp_schur_from_dense_batched_f64(bsp_solver* s, const double* const* dev_grad_dense, int64_t span,
+                                     double* const* dev_grad, const int32_t* dev_dest, int32_t batch);
+int bsp_schur_from_dense_batched_f32(bsp_solver* s, const float* const* dev_grad_dense, int64_t span,
+                                     float* const* dev_grad, const int32_t* dev_dest, int32_t batch);
 /* Extension (no counterpart in the reference): assembly of a symmetric matrix given as coordinate
    entries (rows[k], cols[k], values[k]) in the caller's scalar order into this solver's layout, and its
    adjoint.

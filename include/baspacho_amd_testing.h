@@ -28,6 +28,10 @@ int bsp_test_set_fault(bsp_solver* s, int32_t kind);
  * both in launch order.  *needed = total length; at most `capacity` values are written (buf may be
  * NULL to query the length). */
 int bsp_test_selinv_plan(const bsp_solver* s, int64_t* buf, int64_t capacity, int64_t* needed);
+/* ... of the lumps before the cut at `span` alone (buildSelInvPlan(skel, upToLump): the plan
+ * bsp_factor_adjoint_up_to_* runs), same record layout.  span == bsp_num_spans gives the plan above; a
+ * span that bsp_factor_up_to_* refuses gives a non-zero return. */
+int bsp_test_selinv_plan_up_to(const bsp_solver* s, int64_t span, int64_t* buf, int64_t capacity, int64_t* needed);
 
 /* Caps the chunk of a batched selected inversion (bsp_selected_inverse_batched_*) at `max_matrices`
  * matrices, so that tests can force several chunks on small batches; 0 = the product's rule. */
