@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["Settings", "Solver", "Assembly", "create_solver", "SparseStructure", "BackendHip", "BackendCuda",
+__all__ = ["Settings", "Solver", "Assembly", "NormalEquations", "create_solver", "SparseStructure", "BackendHip", "BackendCuda",
            "BackendRef", "BackendFast", "AddFillComplete", "AddFillForAutoElims",
            "AddFillForGivenElims", "AddFillNone"]
 
@@ -809,6 +809,23 @@ class Solver:
         entry has row >= col; "full": entries with row < col are skipped.  See Assembly."""
         return Assembly(self, rows, cols, triangle)
 
+    # ---- normal equations of a sparse Jacobian (DESIGN.md section 17) -----------------------
+    def normalEquations(self, rows, cols, m):
+        """extension: the maps from the entries (rows[k], cols[k]) of an m x order() Jacobian in the
+        caller's scalar order to this solver's layout (bsp_normal_eq_create), built once on the host.
+        No (row, col) may repeat.  See NormalEquations."""
+        return NormalEquations(self, rows, cols, m)
+
+    def diagOffsets(self):
+        """extension: int64 array [order()], the layout offsets of the diagonal elements in internal
+        order (what damp() touches)"""
+        sk = self.skel()
+        ls = sk["lumpStart"]
+        w = (ls[1:] - ls[:-1]).astype(np.int64)
+        d0 = sk["chainData"][sk["chainColPtr"][:-1]].astype(np.int64)
+        local = np.arange(self.order(), dtype=np.int64) - np.repeat(ls[:-1], w)
+        return np.repeat(d0, w) + local * (np.repeat(w, w) + 1)
+
     def scalarPermutation(self):
         """extension: int64 array p of length order(), p[i_user] = i_internal (bsp_scalar_permutation)"""
         out = np.empty(self.order(), dtype=np.int64)
@@ -1002,6 +1019,129 @@ class Assembly:
         """gradData [dataSize] or [B, dataSize] -> [nnz] / [B, nnz]: gradData[entryOffsets()], 0 for
         skipped entries (bsp_assemble_adjoint_*)"""
         return self._run("adjoint", gradData, self.solver.dataSize(), self.nnz, out, True)
+
+
+_I32P = ctypes.POINTER(ctypes.c_int32)
+
+
+class NormalEquations:
+    """extension: the host maps from the entries (rows[k], cols[k]) of an m x n
+    Jacobian J (n = the solver's order(), caller's scalar order, no position repeated) to the solver's
+    layout, and the device kernels that use them.  Built by Solver.normalEquations(); keeps its solver
+    alive.  hessian: H = J^T J in the layout; hessianAdjoint: the gradient of the values from the gradient
+    of the data; jtVec: J^T r; jVec: J v.  Sums run in a fixed order with every product rounded first
+    (bitwise the numpy restatement); each part of the map is uploaded by the first call that needs it;
+    everything runs on the solver's stream without synchronising."""
+
+    def __init__(self, solver, rows, cols, m):
+        self._lib = solver._lib
+        self._h = None
+        r, c = _host_indices(rows, "rows"), _host_indices(cols, "cols")
+        if len(r) != len(c):
+            raise ValueError("normalEquations: %d rows for %d cols" % (len(r), len(c)))
+        h = ctypes.c_void_p()
+        _check(self._lib.bsp_normal_eq_create(solver._h, ctypes.c_int64(int(m)), ctypes.c_int64(len(r)),
+                                              r.ctypes.data_as(_I64P), c.ctypes.data_as(_I64P), ctypes.byref(h)))
+        self._h = h
+        self.solver = solver
+        self.nnz = len(r)
+        self.m = int(m)
+        self.n = solver.order()
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.bsp_normal_eq_destroy(h)
+
+    def info(self):
+        """figures of the maps (bsp_normal_eq_info)"""
+        out = (ctypes.c_int64 * 10)()
+        _check(self._lib.bsp_normal_eq_info(self._h, out))
+        keys = ["nnz", "pairs", "destinations", "max_run", "long_runs", "tiles", "forward_bytes", "adjoint_bytes",
+                "vector_bytes", "adjoint_terms"]
+        return dict(zip(keys, [int(x) for x in out]))
+
+    def pairTable(self):
+        """(ka, kb, offset) of every pair in run order: int32, int32, int64 arrays of info()["pairs"]"""
+        P = self.info()["pairs"]
+        ka, kb, off = np.empty(P, dtype=np.int32), np.empty(P, dtype=np.int32), np.empty(P, dtype=np.int64)
+        _check(self._lib.bsp_normal_eq_pair_table(self._h, ka.ctypes.data_as(_I32P), kb.ctypes.data_as(_I32P),
+                                                  off.ctypes.data_as(_I64P)))
+        return ka, kb, off
+
+    def _run(self, name, fn, values, x, x_rows, out_rows, out):
+        """values [nnz] / [B, nnz]; x None, or [.., x_rows] / [.., x_rows, q]; out [.., out_rows(, q)]"""
+        import torch
+        for what, t in (("values", values), (name + " input", x)):
+            if t is not None and not isinstance(t, torch.Tensor):
+                raise TypeError("%s: %s must be a torch.Tensor, got %s" % (name, what, type(t).__name__))
+        if values.dim() not in (1, 2) or values.shape[-1] != self.nnz:
+            raise ValueError("%s: values must be [%d] or [B, %d], got shape %s"
+                             % (name, self.nnz, self.nnz, tuple(values.shape)))
+        batched = values.dim() == 2
+        if batched and values.shape[0] == 0:
+            raise ValueError("%s: empty batch" % name)
+        sfx = _suffix(values)
+        lead = tuple(values.shape[:-1])
+        q = None
+        if x is None:
+            shape = lead + (out_rows,)
+        else:
+            if x.dtype != values.dtype or x.device != values.device:
+                raise TypeError("%s: the input is %s on %s, values are %s on %s"
+                                % (name, x.dtype, x.device, values.dtype, values.device))
+            vec = fn.startswith("bsp_normal_eq_j")
+            ok = x.dim() in ((len(lead) + 1, len(lead) + 2) if vec else (len(lead) + 1,))
+            if not ok or tuple(x.shape[:len(lead)]) != lead or x.shape[len(lead)] != x_rows:
+                raise ValueError("%s: the input must be %s%s with leading size %d, got shape %s" % (
+                    name, "[B, ...] " if batched else "", "[rows] or [rows, q]" if vec else "[dataSize]", x_rows,
+                    tuple(x.shape)))
+            if vec:
+                q = x.shape[-1] if x.dim() == len(lead) + 2 else 1
+                if q < 1:
+                    raise ValueError("%s: the input has no vectors" % name)
+                shape = lead + (out_rows,) + ((q,) if x.dim() == len(lead) + 2 else ())
+            else:
+                shape = lead + (out_rows,)
+        if out is None:
+            out = torch.empty(shape, dtype=values.dtype, device=values.device)
+        elif tuple(out.shape) != shape or out.dtype != values.dtype or out.device != values.device:
+            raise ValueError("%s: out must be %s %s on %s, got %s %s on %s" % (
+                name, shape, values.dtype, values.device, tuple(out.shape), out.dtype, out.device))
+        for t in (values, x, out):
+            if t is not None:
+                _ptr_of(t)  # device memory, contiguous
+        P = ctypes.c_void_p
+        qa = () if q is None else (ctypes.c_int64(q),)
+        if batched:
+            B_ = values.shape[0]
+            arr = lambda t: (P * B_)(*[t[b].data_ptr() for b in range(B_)])
+            args = (arr(values),) + (() if x is None else (arr(x),)) + qa + (arr(out), ctypes.c_int32(B_))
+            _check(getattr(self._lib, fn + "batched_" + sfx)(self.solver._h, self._h, *args))
+        else:
+            args = (P(values.data_ptr()),) + (() if x is None else (P(x.data_ptr()),)) + qa + (P(out.data_ptr()),)
+            _check(getattr(self._lib, fn + sfx)(self.solver._h, self._h, *args))
+        return out
+
+    def hessian(self, values, out=None):
+        """values [nnz] or [B, nnz] (device, float64 / float32) -> H = J^T J in the layout, [dataSize] /
+        [B, dataSize]: every element written, 0 where no pair lands (bsp_normal_eq_hessian_*)"""
+        return self._run("hessian", "bsp_normal_eq_hessian_", values, None, 0, self.solver.dataSize(), out)
+
+    def hessianAdjoint(self, values, gradData, out=None):
+        """gradData [dataSize] or [B, dataSize] -> the gradient of values, [nnz] / [B, nnz]
+        (bsp_normal_eq_hessian_adjoint_*)"""
+        return self._run("hessianAdjoint", "bsp_normal_eq_hessian_adjoint_", values, gradData,
+                         self.solver.dataSize(), self.nnz, out)
+
+    def jtVec(self, values, r, out=None):
+        """r [m] or [m, q] (leading B when values are batched) -> J^T r, [n] / [n, q], caller's order
+        (bsp_normal_eq_jt_vec_*)"""
+        return self._run("jtVec", "bsp_normal_eq_jt_vec_", values, r, self.m, self.n, out)
+
+    def jVec(self, values, v, out=None):
+        """v [n] or [n, q] (leading B when values are batched) -> J v, [m] / [m, q] (bsp_normal_eq_j_vec_*)"""
+        return self._run("jVec", "bsp_normal_eq_j_vec_", values, v, self.n, self.m, out)
 
 
 def probe_mfma_f64_tflops():

@@ -5,6 +5,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "entry_map.h"
 #include "hip_backend.h"
 #include "solver.h"
 
@@ -23,16 +24,6 @@ int64_t AssemblyMap::deviceBytes() const {
 
 static std::string entryName(int64_t k, int64_t i, int64_t j) {
   return "entry " + std::to_string(k) + " at (" + std::to_string(i) + ", " + std::to_string(j) + ")";
-}
-
-// stable counting sort of idx by key(idx) in [0, numKeys)
-template <typename Key>
-static void countingSort(const std::vector<int32_t>& in, std::vector<int32_t>& out, int64_t numKeys, Key key) {
-  std::vector<int64_t> start(numKeys + 1, 0);
-  for (int32_t k : in) start[key(k) + 1]++;
-  for (int64_t b = 0; b < numKeys; b++) start[b + 1] += start[b];
-  out.resize(in.size());
-  for (int32_t k : in) out[start[key(k)]++] = k;
 }
 
 std::unique_ptr<AssemblyMap> createAssemblyMap(const Solver& solver, int64_t nnz, const int64_t* rows,
@@ -54,17 +45,8 @@ std::unique_ptr<AssemblyMap> createAssemblyMap(const Solver& solver, int64_t nnz
   m->dataSize = solver.dataSize();
   m->numTiles = (m->dataSize + kAssemblyTile - 1) / kAssemblyTile;
 
-  // caller's scalar -> (param, local position), params in param order
-  const PermutedCoalescedAccessor acc = solver.accessor();
-  const std::vector<int64_t>& perm = solver.paramToSpan();
-  const std::vector<int64_t>& spanStart = solver.skel().spanStart;
-  const int64_t numParams = (int64_t)perm.size(), n = solver.order();
-  std::vector<int64_t> userStart(numParams + 1, 0), paramOf(n);
-  for (int64_t p = 0; p < numParams; p++) {
-    const int64_t size = spanStart[perm[p] + 1] - spanStart[perm[p]];
-    userStart[p + 1] = userStart[p] + size;
-    std::fill(paramOf.begin() + userStart[p], paramOf.begin() + userStart[p + 1], p);
-  }
+  const ScalarLocator loc(solver);
+  const int64_t n = solver.order();
 
   m->entryOff.resize(nnz);
   std::vector<int32_t> kept;
@@ -83,56 +65,20 @@ std::unique_ptr<AssemblyMap> createAssemblyMap(const Solver& solver, int64_t nnz
       m->entryOff[k] = -1;
       continue;
     }
-    const int64_t p = paramOf[i], q = paramOf[j];
-    int64_t r = i - userStart[p], c = j - userStart[q];
-    const int64_t sp = perm[p], sq = perm[q];
-    if (!acc.plainAcc.hasBlock(std::max(sp, sq), std::min(sp, sq))) {
-      throw std::runtime_error("assembly: " + entryName(k, i, j) + " (params " + std::to_string(p) + ", " +
-                               std::to_string(q) + ") is not in the solver's stored pattern");
+    m->entryOff[k] = loc.offset(i, j);
+    if (m->entryOff[k] < 0) {
+      throw std::runtime_error("assembly: " + entryName(k, i, j) + " (params " + std::to_string(loc.paramOf[i]) +
+                               ", " + std::to_string(loc.paramOf[j]) + ") is not in the solver's stored pattern");
     }
-    const auto osf = acc.blockOffset(p, q);
-    if (sp == sq && r < c) std::swap(r, c);
-    const int64_t off = std::get<0>(osf), stride = std::get<1>(osf);
-    m->entryOff[k] = std::get<2>(osf) ? off + c * stride + r : off + r * stride + c;
     kept.push_back((int32_t)k);
   }
 
-  // entries by (offset, entry index): LSD counting sort, first on the position inside the tile, then
-  // on the tile, both stable on ascending k
+  // entries by (offset, entry index), then runs, tile index, long runs
   const int64_t* off = m->entryOff.data();
-  std::vector<int32_t> byLocal;
-  countingSort(kept, byLocal, kAssemblyTile, [off](int32_t k) { return off[k] & (kAssemblyTile - 1); });
-  std::vector<int32_t>().swap(kept);
-  countingSort(byLocal, m->runEntry, m->numTiles, [off](int32_t k) { return off[k] / kAssemblyTile; });
-  std::vector<int32_t>().swap(byLocal);
-
-  // runs, tile index, long runs
-  const int64_t numKept = (int64_t)m->runEntry.size();
-  m->tileFirst.assign(m->numTiles + 1, 0);
-  m->tileLongFirst.assign(m->numTiles + 1, 0);
-  for (int64_t x = 0; x < numKept; x++) {
-    const int64_t o = off[m->runEntry[x]];
-    if (x == 0 || o != m->dest.back()) {
-      m->dest.push_back(o);
-      m->runStart.push_back((int32_t)x);
-      m->destLocal.push_back((uint16_t)(o & (kAssemblyTile - 1)));
-      m->tileFirst[o / kAssemblyTile + 1]++;
-    }
-  }
-  m->runStart.push_back((int32_t)numKept);
-  const int64_t numDest = (int64_t)m->dest.size();
-  for (int64_t u = 0; u < numDest; u++) {
-    const int64_t len = m->runStart[u + 1] - m->runStart[u];
-    m->maxRun = std::max(m->maxRun, len);
-    if (len > kAssemblyLongRun) {
-      m->longDest.push_back((int32_t)u);
-      m->tileLongFirst[m->dest[u] / kAssemblyTile + 1]++;
-    }
-  }
-  for (int64_t t = 0; t < m->numTiles; t++) {
-    m->tileFirst[t + 1] += m->tileFirst[t];
-    m->tileLongFirst[t + 1] += m->tileLongFirst[t];
-  }
+  sortByOffset(kept, m->runEntry, m->numTiles, [off](int32_t k) { return off[k]; });
+  const int32_t* runEntry = m->runEntry.data();
+  buildTileRuns((int64_t)m->runEntry.size(), m->numTiles, [off, runEntry](int64_t x) { return off[runEntry[x]]; },
+                TileRuns{m->dest, m->runStart, m->tileFirst, m->destLocal, m->longDest, m->tileLongFirst, m->maxRun});
   return m;
 }
 

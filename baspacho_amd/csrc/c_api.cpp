@@ -10,6 +10,7 @@
 #include <unordered_set>
 
 #include "assembly.h"
+#include "normal_eq.h"
 #include "bal_pipeline.h"
 #include "../../include/baspacho_amd_testing.h"
 #include "computation_model.h"
@@ -767,6 +768,111 @@ int bsp_assemble_adjoint_batched_f32(bsp_solver* s, const bsp_assembly* a, const
   assembleBatched(s, a, g, gv, batch, true);
   BSP_CATCH
 }
+struct bsp_normal_eq {
+  std::unique_ptr<NormalEqMap> map;
+};
+
+int bsp_normal_eq_create(bsp_solver* s, int64_t m, int64_t nnz, const int64_t* rows, const int64_t* cols,
+                         bsp_normal_eq** out) {
+  BSP_TRY
+  if (s == nullptr || out == nullptr) throw std::runtime_error("bsp_normal_eq_create: NULL solver or output");
+  std::unique_ptr<bsp_normal_eq> e(new bsp_normal_eq);
+  e->map = createNormalEqMap(*s->solver, m, nnz, rows, cols);
+  *out = e.release();
+  BSP_CATCH
+}
+void bsp_normal_eq_destroy(bsp_normal_eq* e) { delete e; }
+int bsp_normal_eq_info(const bsp_normal_eq* e, int64_t out[10]) {
+  BSP_TRY
+  if (e == nullptr || out == nullptr) throw std::runtime_error("bsp_normal_eq_info: NULL argument");
+  const NormalEqMap& m = *e->map;
+  const int64_t v[10] = {m.nnz, m.numPairs, (int64_t)m.dest.size(), m.maxRun, (int64_t)m.longDest.size(),
+                         m.numTiles, m.forwardDeviceBytes(), m.adjointDeviceBytes(), m.vectorDeviceBytes(),
+                         m.numAdjointTerms()};
+  std::copy(v, v + 10, out);
+  BSP_CATCH
+}
+int bsp_normal_eq_pair_table(const bsp_normal_eq* e, int32_t* ka, int32_t* kb, int64_t* offset) {
+  BSP_TRY
+  if (e == nullptr) throw std::runtime_error("bsp_normal_eq_pair_table: the map is NULL");
+  const NormalEqMap& m = *e->map;
+  if (m.numPairs > 0 && (ka == nullptr || kb == nullptr || offset == nullptr)) {
+    throw std::runtime_error("bsp_normal_eq_pair_table: an output array is NULL");
+  }
+  std::copy(m.pairA.begin(), m.pairA.end(), ka);
+  std::copy(m.pairB.begin(), m.pairB.end(), kb);
+  for (size_t u = 0; u < m.dest.size(); u++) {
+    std::fill(offset + m.runStart[u], offset + m.runStart[u + 1], m.dest[u]);
+  }
+  BSP_CATCH
+}
+template <typename T>
+static void normalEqRun(bsp_solver* s, const bsp_normal_eq* e, int32_t op, const T* const* values, const T* const* x,
+                        T* const* out, int64_t q, int32_t batch, bool single) {
+  static const char* names[4] = {"normalEqHessian", "normalEqHessianAdjoint", "normalEqJtVec", "normalEqJVec"};
+  const std::string what = names[op];
+  if (s == nullptr) throw std::runtime_error(what + ": the solver is NULL");
+  if (e == nullptr) throw std::runtime_error(what + ": the map is NULL");
+  if (batch <= 0) throw std::runtime_error(what + ": the batch is empty (batch = " + std::to_string(batch) + ")");
+  const bool hasX = op != NormalEqHessian;
+  if (values == nullptr || out == nullptr || (hasX && x == nullptr)) {
+    throw std::runtime_error(what + ": an array of pointers is NULL");
+  }
+  const std::vector<const T*> v(values, values + batch);
+  const std::vector<const T*> xs(hasX ? x : values, hasX ? x + batch : values);
+  const std::vector<T*> o(out, out + batch);
+  s->solver->normalEq<T>(*e->map, op, v, xs, o, q, single);
+}
+#define BSP_NORMAL_EQ_API(SFX, T)                                                                                \
+  int bsp_normal_eq_hessian_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* v, T* d) {                      \
+    BSP_TRY                                                                                                      \
+    normalEqRun<T>(s, e, NormalEqHessian, &v, nullptr, &d, 0, 1, true);                                          \
+    BSP_CATCH                                                                                                    \
+  }                                                                                                              \
+  int bsp_normal_eq_hessian_batched_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* const* v, T* const* d, \
+                                          int32_t batch) {                                                       \
+    BSP_TRY                                                                                                      \
+    normalEqRun<T>(s, e, NormalEqHessian, v, nullptr, d, 0, batch, false);                                       \
+    BSP_CATCH                                                                                                    \
+  }                                                                                                              \
+  int bsp_normal_eq_hessian_adjoint_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* v, const T* g, T* gv) { \
+    BSP_TRY                                                                                                      \
+    normalEqRun<T>(s, e, NormalEqAdjoint, &v, &g, &gv, 0, 1, true);                                              \
+    BSP_CATCH                                                                                                    \
+  }                                                                                                              \
+  int bsp_normal_eq_hessian_adjoint_batched_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* const* v,      \
+                                                  const T* const* g, T* const* gv, int32_t batch) {              \
+    BSP_TRY                                                                                                      \
+    normalEqRun<T>(s, e, NormalEqAdjoint, v, g, gv, 0, batch, false);                                            \
+    BSP_CATCH                                                                                                    \
+  }                                                                                                              \
+  int bsp_normal_eq_jt_vec_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* v, const T* r, int64_t q,       \
+                                 T* out) {                                                                       \
+    BSP_TRY                                                                                                      \
+    normalEqRun<T>(s, e, NormalEqJtVec, &v, &r, &out, q, 1, true);                                               \
+    BSP_CATCH                                                                                                    \
+  }                                                                                                              \
+  int bsp_normal_eq_jt_vec_batched_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* const* v,               \
+                                         const T* const* r, int64_t q, T* const* out, int32_t batch) {           \
+    BSP_TRY                                                                                                      \
+    normalEqRun<T>(s, e, NormalEqJtVec, v, r, out, q, batch, false);                                             \
+    BSP_CATCH                                                                                                    \
+  }                                                                                                              \
+  int bsp_normal_eq_j_vec_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* v, const T* x, int64_t q,        \
+                                T* out) {                                                                        \
+    BSP_TRY                                                                                                      \
+    normalEqRun<T>(s, e, NormalEqJVec, &v, &x, &out, q, 1, true);                                                \
+    BSP_CATCH                                                                                                    \
+  }                                                                                                              \
+  int bsp_normal_eq_j_vec_batched_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* const* v,                \
+                                        const T* const* x, int64_t q, T* const* out, int32_t batch) {            \
+    BSP_TRY                                                                                                      \
+    normalEqRun<T>(s, e, NormalEqJVec, v, x, out, q, batch, false);                                              \
+    BSP_CATCH                                                                                                    \
+  }
+BSP_NORMAL_EQ_API(f64, double)
+BSP_NORMAL_EQ_API(f32, float)
+#undef BSP_NORMAL_EQ_API
 int bsp_scalar_permutation(const bsp_solver* s, int64_t* out) {
   BSP_TRY
   if (out == nullptr) throw std::runtime_error("bsp_scalar_permutation: out is NULL");

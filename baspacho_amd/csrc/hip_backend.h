@@ -158,6 +158,20 @@ void hipBackendAssemble(SymbolicCtx& sym, const AssemblyMap& map, const T* const
                         int64_t batch, bool single, bool adjoint);
 void hipBackendFreeAssembly(HipAssemblyDev* dev);
 
+// Normal equations of a sparse Jacobian (hip_normal_eq_kernels.h), on the
+// execution stream.  Host arrays of `batch` device pointers as for hipBackendAssemble.  Each part of the
+// map is uploaded on the first call that needs it and kept in map.dev.
+//   NormalEqHessian:  out = data (dataSize each) from values;  x unused
+//   NormalEqAdjoint:  out = gradients of the values from values and x = gradients of the data
+//   NormalEqJtVec:    out = J^T x ([n, q] each) from values and x ([m, q]);  NormalEqJVec: out = J x
+struct NormalEqMap;
+struct HipNormalEqDev;
+enum NormalEqOp : int32_t { NormalEqHessian = 0, NormalEqAdjoint = 1, NormalEqJtVec = 2, NormalEqJVec = 3 };
+template <typename T>
+void hipBackendNormalEq(SymbolicCtx& sym, const NormalEqMap& map, int32_t op, const T* const* values,
+                        const T* const* x, T* const* out, int64_t q, int64_t batch, bool single);
+void hipBackendFreeNormalEq(HipNormalEqDev* dev);
+
 HipPlanStats hipBackendPlanStats(SymbolicCtx& sym, int64_t startLump, int64_t upToLump);
 
 }  // namespace BaSpaCho

@@ -23,6 +23,7 @@
 #include "hip_chol_adjoint_kernels.h"
 #include "hip_grad_kernels.h"
 #include "hip_assembly_kernels.h"
+#include "hip_normal_eq_kernels.h"
 #include "mat_ops.h"
 
 namespace BaSpaCho {
@@ -82,6 +83,40 @@ struct HipAssemblyDev {
     runEntry.upload(m.runEntry);
     destLocal.upload(m.destLocal);
     longDest.upload(m.longDest);
+  }
+};
+
+// the three parts of a normal-equations map on the device (normal_eq.h), owned by its NormalEqMap
+struct HipNormalEqDev {
+  bool hasForward = false, hasAdjoint = false, hasVectors = false;
+  DevBuf tileFirst, tileLongFirst, runStart, pairA, pairB, destLocal, longDest;
+  DevBuf adjStart, adjPartner, adjDest, adjLong;
+  DevBuf colStart, colEntry, colIdx, rowStart, rowEntry, rowIdx;
+  void uploadForward(const NormalEqMap& m) {
+    tileFirst.upload(m.tileFirst);
+    tileLongFirst.upload(m.tileLongFirst);
+    runStart.upload(m.runStart);
+    pairA.upload(m.pairA);
+    pairB.upload(m.pairB);
+    destLocal.upload(m.destLocal);
+    longDest.upload(m.longDest);
+    hasForward = true;
+  }
+  void uploadAdjoint(const NormalEqMap& m) {
+    adjStart.upload(m.adjStart);
+    adjPartner.upload(m.adjPartner);
+    adjDest.upload(m.adjDest);
+    adjLong.upload(m.adjLong);
+    hasAdjoint = true;
+  }
+  void uploadVectors(const NormalEqMap& m) {
+    colStart.upload(m.colStart);
+    colEntry.upload(m.colEntry);
+    colIdx.upload(m.colIdx);
+    rowStart.upload(m.rowStart);
+    rowEntry.upload(m.rowEntry);
+    rowIdx.upload(m.rowIdx);
+    hasVectors = true;
   }
 };
 
@@ -890,6 +925,58 @@ struct HipSymbolicCtx : SymbolicCtx {
         hipk::assembleTiles<T><<<dim3((unsigned)m.numTiles, nm), hipk::kAsmThreads, 0, stream>>>(
             m.dataSize, d.tileFirst.as<int32_t>(), d.tileLongFirst.as<int32_t>(), d.runStart.as<int32_t>(),
             d.runEntry.as<int32_t>(), d.destLocal.as<uint16_t>(), d.longDest.as<int32_t>(), iref, oref);
+      }
+    }
+    hipCHECK(hipGetLastError());
+  }
+
+  // ---- normal equations of a sparse Jacobian (hip_normal_eq_kernels.h) --------
+  // one of the four operations on `batch` members: one launch per chunk of at most 65535 members
+  template <typename T>
+  void normalEq(const NormalEqMap& m, int32_t op, const T* const* values, const T* const* x, T* const* out,
+                int64_t q, int64_t batch, bool single) {
+    checkDevice();
+    if (m.dev == nullptr) m.dev = new HipNormalEqDev;
+    HipNormalEqDev& d = *m.dev;
+    if (op == NormalEqHessian && !d.hasForward) d.uploadForward(m);
+    if (op == NormalEqAdjoint && !d.hasAdjoint) d.uploadAdjoint(m);
+    if ((op == NormalEqJtVec || op == NormalEqJVec) && !d.hasVectors) d.uploadVectors(m);
+    const bool jt = op == NormalEqJtVec;
+    const int64_t numRuns = jt ? m.n : m.m;
+    if (op == NormalEqAdjoint && m.nnz == 0) return;
+    if (op == NormalEqHessian && m.numTiles == 0) return;
+    if ((op == NormalEqJtVec || op == NormalEqJVec) && numRuns * q == 0) return;
+    const int64_t chunk = std::min<int64_t>(batch, 65535);
+    const size_t bytes = batch * sizeof(T*);
+    const T* const* vMany = single ? nullptr : (const T* const*)ptrRing.push(values, bytes, stream);
+    const T* const* xMany = single || x == nullptr ? nullptr : (const T* const*)ptrRing.push(x, bytes, stream);
+    T* const* oMany = single ? nullptr : (T* const*)ptrRing.push(out, bytes, stream);
+    const int64_t shortWgs = (m.nnz + hipk::kAsmThreads - 1) / hipk::kAsmThreads;
+    const int64_t numLong = (int64_t)m.adjLong.size();
+    const int64_t longWgs = (numLong + hipk::kNeqWavesPerWg - 1) / hipk::kNeqWavesPerWg;
+    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
+      const unsigned nm = (unsigned)std::min(chunk, batch - q0);
+      const hipk::DataRef<const T> vref =
+          single ? hipk::DataRef<const T>{values[0], nullptr} : hipk::DataRef<const T>{nullptr, vMany + q0};
+      const hipk::DataRef<const T> xref = x == nullptr ? hipk::DataRef<const T>{nullptr, nullptr}
+                                          : single     ? hipk::DataRef<const T>{x[0], nullptr}
+                                                       : hipk::DataRef<const T>{nullptr, xMany + q0};
+      const hipk::DataRef<T> oref = single ? hipk::DataRef<T>{out[0], nullptr} : hipk::DataRef<T>{nullptr, oMany + q0};
+      if (op == NormalEqHessian) {
+        hipk::normalEqTiles<T><<<dim3((unsigned)m.numTiles, nm), hipk::kAsmThreads, 0, stream>>>(
+            m.dataSize, d.tileFirst.as<int32_t>(), d.tileLongFirst.as<int32_t>(), d.runStart.as<int32_t>(),
+            d.pairA.as<int32_t>(), d.pairB.as<int32_t>(), d.destLocal.as<uint16_t>(), d.longDest.as<int32_t>(), vref,
+            oref);
+      } else if (op == NormalEqAdjoint) {
+        hipk::normalEqAdjointEntries<T><<<dim3((unsigned)(shortWgs + longWgs), nm), hipk::kAsmThreads, 0, stream>>>(
+            m.nnz, (int32_t)shortWgs, (int32_t)numLong, d.adjStart.as<int64_t>(), d.adjPartner.as<int32_t>(),
+            d.adjDest.as<int64_t>(), d.adjLong.as<int32_t>(), vref, xref, oref);
+      } else {
+        const int64_t wgs = (numRuns * q + hipk::kAsmThreads - 1) / hipk::kAsmThreads;
+        hipk::runDotVec<T><<<dim3((unsigned)wgs, nm), hipk::kAsmThreads, 0, stream>>>(
+            numRuns, (int32_t)q, (jt ? d.colStart : d.rowStart).template as<int32_t>(),
+            (jt ? d.colEntry : d.rowEntry).template as<int32_t>(), (jt ? d.colIdx : d.rowIdx).template as<int32_t>(),
+            vref, xref, oref);
       }
     }
     hipCHECK(hipGetLastError());
@@ -3078,5 +3165,19 @@ template void hipBackendAssemble<float>(SymbolicCtx&, const AssemblyMap&, const 
                                         int64_t, bool, bool);
 
 void hipBackendFreeAssembly(HipAssemblyDev* dev) { delete dev; }
+
+template <typename T>
+void hipBackendNormalEq(SymbolicCtx& sym, const NormalEqMap& map, int32_t op, const T* const* values,
+                        const T* const* x, T* const* out, int64_t q, int64_t batch, bool single) {
+  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
+  BASPACHO_CHECK_NOTNULL(h);
+  h->normalEq(map, op, values, x, out, q, batch, single);
+}
+template void hipBackendNormalEq<double>(SymbolicCtx&, const NormalEqMap&, int32_t, const double* const*,
+                                         const double* const*, double* const*, int64_t, int64_t, bool);
+template void hipBackendNormalEq<float>(SymbolicCtx&, const NormalEqMap&, int32_t, const float* const*,
+                                        const float* const*, float* const*, int64_t, int64_t, bool);
+
+void hipBackendFreeNormalEq(HipNormalEqDev* dev) { delete dev; }
 
 }  // namespace BaSpaCho

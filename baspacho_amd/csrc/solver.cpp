@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "assembly.h"
+#include "normal_eq.h"
 #include "computation_model.h"
 #include "elimination_tree.h"
 #include "hip_backend.h"
@@ -955,6 +956,63 @@ template void Solver::assembleAdjoint<double>(const AssemblyMap&, const std::vec
                                               const std::vector<double*>&) const;
 template void Solver::assembleAdjoint<float>(const AssemblyMap&, const std::vector<const float*>&,
                                              const std::vector<float*>&) const;
+
+// ---- normal equations of a sparse Jacobian -------------------------------------------------------
+template <typename T>
+void Solver::normalEq(const NormalEqMap& map, int32_t op, const std::vector<const T*>& values,
+                      const std::vector<const T*>& x, const std::vector<T*>& out, int64_t q, bool single) const {
+  static const char* names[4] = {"normalEqHessian", "normalEqHessianAdjoint", "normalEqJtVec", "normalEqJVec"};
+  if (op < 0 || op > 3) throw std::runtime_error("normalEq: unknown operation " + std::to_string(op));
+  const char* what = names[op];
+  const auto fail = [what](const std::string& m) { throw std::runtime_error(std::string(what) + ": " + m); };
+  if (map.solver != this) fail("the map was built on another solver");
+  if (values.empty()) fail("the batch is empty");
+  const bool hasX = op != NormalEqHessian;
+  if (values.size() != out.size() || (hasX && x.size() != values.size())) {
+    fail("the batch has " + std::to_string(values.size()) + " values, " + std::to_string(x.size()) + " inputs and " +
+         std::to_string(out.size()) + " outputs");
+  }
+  if (hasX && op != NormalEqAdjoint && q < 1) fail("q = " + std::to_string(q) + " vectors; at least one is needed");
+  // element counts of the three sides; a side of size 0 is never touched and may be NULL
+  const int64_t nX = op == NormalEqAdjoint ? map.dataSize : op == NormalEqJtVec ? map.m * q : map.n * q;
+  const int64_t nOut = op == NormalEqHessian   ? map.dataSize
+                       : op == NormalEqAdjoint ? map.nnz
+                       : op == NormalEqJtVec   ? map.n * q
+                                               : map.m * q;
+  const char* xName = op == NormalEqAdjoint ? "gradient-of-data" : "vector";
+  const char* outName = op == NormalEqHessian ? "data" : op == NormalEqAdjoint ? "gradient-of-values" : "output";
+  const auto overlap = [](const T* a, int64_t na, const T* b, int64_t nb) {
+    return a != nullptr && b != nullptr && na > 0 && nb > 0 && a < b + nb && b < a + na;
+  };
+  std::unordered_set<const T*> seen;
+  for (size_t b = 0; b < values.size(); b++) {
+    const std::string member = " pointer of batch member " + std::to_string(b);
+    if (values[b] == nullptr && map.nnz > 0) fail("the values" + member + " is NULL");
+    if (hasX && x[b] == nullptr && nX > 0) fail(std::string("the ") + xName + member + " is NULL");
+    if (out[b] == nullptr) {
+      if (nOut == 0) continue;
+      fail(std::string("the ") + outName + member + " is NULL");
+    }
+    if (!seen.insert(out[b]).second) fail(std::string("the ") + outName + member + " repeats an earlier member's");
+    if (overlap(out[b], nOut, values[b], map.nnz)) fail(std::string("the ") + outName + member + " aliases its values");
+    if (hasX && overlap(out[b], nOut, x[b], nX)) {
+      fail(std::string("the ") + outName + member + " aliases its " + xName);
+    }
+  }
+  for (size_t b = 0; b < values.size(); b++) {  // an output of one member that is an input of another
+    if (seen.count(values[b]) || (hasX && seen.count(x[b]))) {
+      fail("an input pointer of batch member " + std::to_string(b) + " is also an output of the batch");
+    }
+  }
+  hipBackendNormalEq<T>(*symCtx, map, op, values.data(), hasX ? x.data() : nullptr, out.data(), q,
+                        (int64_t)values.size(), single);
+}
+template void Solver::normalEq<double>(const NormalEqMap&, int32_t, const std::vector<const double*>&,
+                                       const std::vector<const double*>&, const std::vector<double*>&, int64_t,
+                                       bool) const;
+template void Solver::normalEq<float>(const NormalEqMap&, int32_t, const std::vector<const float*>&,
+                                      const std::vector<const float*>&, const std::vector<float*>&, int64_t,
+                                      bool) const;
 
 #define BSP_INSTANTIATE(T)                                                                     \
   template void Solver::factor<T>(T*, bool) const;                                             \

@@ -17,6 +17,7 @@
 namespace BaSpaCho {
 
 struct AssemblyMap;
+struct NormalEqMap;
 
 class Solver {
  public:
@@ -184,6 +185,20 @@ class Solver {
   template <typename T>
   void assembleAdjoint(const AssemblyMap& map, const std::vector<const T*>& gradData,
                        const std::vector<T*>& gradValues) const;
+  // extension: normal equations of a sparse Jacobian J (normal_eq.h).  `map` comes
+  // from createNormalEqMap(*this, ...); op is a NormalEqOp (hip_backend.h); member b of the batch uses
+  // values[b] (nnz), x[b] and out[b]:
+  //   NormalEqHessian: out = H = J^T J in this Solver's layout (dataSize, every element written), x empty
+  //   NormalEqAdjoint: out = gradient of the values (nnz) from x = gradient of the data (dataSize)
+  //   NormalEqJtVec:   out = J^T x ([n, q] row-major) from x ([m, q]);  NormalEqJVec: out = J x ([m, q])
+  // single = true: one member handed to the kernels directly (the batch forms go through a pointer
+  // array); member b is bitwise the single call either way.  Runs on the stream of setStream() without
+  // host synchronisation (the first call of a kind uploads its part of the map).  A map of another
+  // Solver, an empty batch, a NULL pointer (a side of size 0 may be NULL), a repeated output pointer or
+  // an output that overlaps an input of its member are refused before any device work.
+  template <typename T>
+  void normalEq(const NormalEqMap& map, int32_t op, const std::vector<const T*>& values,
+                const std::vector<const T*>& x, const std::vector<T*>& out, int64_t q, bool single) const;
   // scalarPermutation()[i] = internal index of the caller's scalar i (params in param order, each
   // at the start of its span)
   std::vector<int64_t> scalarPermutation() const;

@@ -10,6 +10,10 @@
     pat = S.SymmetricPattern(rows, cols, n, keep=kept)     # kept scalars ordered last
     Sk, rk = S.marginalize(pat, values, b)         # marginal precision / information of the kept scalars
 
+    jpat = S.JacobianPattern(jrows, jcols, m, n)   # once per Jacobian pattern: solver + normal-equations maps
+    x = S.lstsq(jpat, jvalues, r, damping=(a, b))  # x = (J^T J + D)^-1 J^T r, D = a diag(J^T J) + b I
+    data, g = S.normal_equations(jpat, jvalues, r) # H = J^T J in the layout and g = J^T r
+
 The matrix is given by entries (rows[k], cols[k], values[k]) in the caller's scalar order: A_ij = A_ji =
 the sum of the values of the entries at (i, j), i >= j.  `values` is [nnz] or a
 batch [B, nnz] of matrices of one pattern; `b` and `x` are in the caller's order, [n] or [n, k], with a
@@ -20,6 +24,11 @@ solve / logdet / solve_logdet and a permutation of the vectors.  Everything runs
 torch.cuda.current_stream() without host synchronisation, and the solver's own stream is restored
 afterwards; the first call on a device uploads the assembly map and the permutation.  Double backward
 is not supported.
+
+A JacobianPattern takes the entries (rows[k], cols[k], values[k]) of an m x n Jacobian, no position
+repeated; H = J^T J is formed on the device straight in the solver's layout, in a
+fixed summation order.  hessian / jt_vec / j_vec / normal_equations / lstsq are differentiable in the
+Jacobian values and the vectors, and in the two damping factors when they are tensors.
 
 marginalize eliminates every scalar outside `keep`: S = A22 - A21 A11^-1 A12 and
 r = b2 - A21 A11^-1 b1 with block 2 the kept scalars, rows and columns in the order of `keep`.  inv(S) is
@@ -33,7 +42,8 @@ from . import Settings, SparseStructure, create_solver
 from . import autograd as _ag
 from .autograd import _OnCurrentStream
 
-__all__ = ["SymmetricPattern", "assemble", "solve", "logdet", "solve_logdet", "sample", "marginalize"]
+__all__ = ["SymmetricPattern", "JacobianPattern", "assemble", "solve", "logdet", "solve_logdet", "sample", "marginalize",
+           "hessian", "jt_vec", "j_vec", "normal_equations", "lstsq"]
 
 
 def _host_i64(a):
@@ -51,44 +61,40 @@ def _block_structure(num_params, p, q):
     return SparseStructure(np.cumsum(ptrs), c)
 
 
-class SymmetricPattern:
-    """A solver and its assembly map for the symmetric pattern of the entries (rows[k], cols[k]),
-    0 <= rows, cols < n, in the caller's scalar order.  Scalars are grouped into params of
-    `param_sizes` (default: all 1) in order; the param-level lower block structure is derived from the
-    entries and handed to create_solver (fill and ordering as `settings` say).  triangle: "lower"
-    (every entry has row >= col) or "full" (entries with row < col are skipped; the caller asserts the
-    matrix is symmetric).  Invalid entries are refused by the assembly, which names the first one.
-    keep: caller-order scalar indices (distinct, covering whole params) that marginalize() keeps; their
-    params are ordered behind all others, from span `keep_span` on."""
+class _Pattern:
+    """what SymmetricPattern and JacobianPattern share: the params, the solver with the kept params
+    ordered last, and the permutations between the caller's order and the solver's"""
 
-    def __init__(self, rows, cols, n, param_sizes=None, settings=None, triangle="lower", keep=None):
-        rows, cols = _host_i64(rows), _host_i64(cols)
-        if len(rows) != len(cols):
-            raise ValueError("SymmetricPattern: %d rows for %d cols" % (len(rows), len(cols)))
+    def _init_params(self, n, param_sizes):
+        name = type(self).__name__
         n = int(n)
         ps = np.ones(n, dtype=np.int64) if param_sizes is None else _host_i64(param_sizes)
         if np.any(ps < 1) or int(ps.sum()) != n:
-            raise ValueError("SymmetricPattern: param sizes must be >= 1 and sum to n = %d" % n)
+            raise ValueError("%s: param sizes must be >= 1 and sum to n = %d" % (name, n))
         starts = np.concatenate([[0], np.cumsum(ps)])
-        # the structure takes the well-formed lower entries; the assembly refuses the others by name
-        ok = (rows >= 0) & (rows < n) & (cols >= 0) & (cols < n) & (rows >= cols)
-        param_of = lambda i: np.searchsorted(starts, i, side="right") - 1
-        ss = _block_structure(len(ps), param_of(rows[ok]), param_of(cols[ok]))
         self.n = n
         self.param_sizes = ps
+        return lambda i: np.searchsorted(starts, i, side="right") - 1
+
+    def _init_solver(self, ss, settings, keep, param_of):
+        name, n, ps = type(self).__name__, self.n, self.param_sizes
         self.structure = ss
         keep_params = ()
         if keep is not None:
             keep = _host_i64(keep)
             if len(keep) == 0 or np.any(keep < 0) or np.any(keep >= n) or len(np.unique(keep)) != len(keep):
-                raise ValueError("SymmetricPattern: keep must hold distinct scalar indices in [0, %d), at least one" % n)
+                raise ValueError("%s: keep must hold distinct scalar indices in [0, %d), at least one" % (name, n))
             keep_params = np.unique(param_of(keep))
             if int(ps[keep_params].sum()) != len(keep):
-                raise ValueError("SymmetricPattern: keep must cover whole params (it touches %d params of %d "
-                                 "scalars with %d indices)" % (len(keep_params), int(ps[keep_params].sum()), len(keep)))
+                raise ValueError("%s: keep must cover whole params (it touches %d params of %d "
+                                 "scalars with %d indices)" % (name, len(keep_params), int(ps[keep_params].sum()),
+                                                               len(keep)))
         self.solver = create_solver(settings or Settings(), ps, ss, elim_last_ids=[int(p) for p in keep_params])
-        self.assembly = self.solver.assembly(rows, cols, triangle)
-        self.nnz = len(rows)
+        self._keep_params = keep_params
+        self._keep_arg = keep
+
+    def _init_order(self):
+        name, n, keep, keep_params = type(self).__name__, self.n, self._keep_arg, self._keep_params
         perm = self.solver.scalarPermutation()
         self._to_user = perm                 # internal -> user: x_user = x_int[perm]
         self._to_internal = np.argsort(perm)  # user -> internal: v_int = v_user[inv]
@@ -101,37 +107,20 @@ class SymmetricPattern:
             self.keep_span = int(spans[0])
             if not np.array_equal(spans, np.arange(self.keep_span, sol.numSpans())) \
                     or int(sk["spanOffsetInLump"][self.keep_span]) != 0:
-                raise RuntimeError("SymmetricPattern: the solver did not place the kept params behind a lump "
-                                   "boundary (spans %s of %d)" % (spans.tolist(), sol.numSpans()))
+                raise RuntimeError("%s: the solver did not place the kept params behind a lump "
+                                   "boundary (spans %s of %d)" % (name, spans.tolist(), sol.numSpans()))
             bar = int(sk["spanStart"][self.keep_span])
             self._keep_internal = perm[keep]  # internal scalar of keep[t]
             dest = np.empty(n - bar, dtype=np.int32)
             dest[self._keep_internal - bar] = np.arange(len(keep), dtype=np.int32)
             self._keep_dest = dest            # position in keep of the k-th scalar behind the cut
 
-    @staticmethod
-    def from_torch(A, param_sizes=None, settings=None, triangle="lower"):
-        """(pattern, values) of a square torch sparse COO or CSR tensor, duplicates of an uncoalesced
-        COO tensor kept as separate entries.  Gradients are promised only for the `values` tensor
-        passed explicitly to the functions of this module."""
-        if A.dim() != 2 or A.shape[0] != A.shape[1]:
-            raise ValueError("from_torch: expected a square matrix, got shape %s" % (tuple(A.shape),))
-        if A.layout == torch.sparse_coo:
-            idx, values = A._indices(), A._values()
-            rows, cols = idx[0], idx[1]
-        elif A.layout == torch.sparse_csr:
-            crow = A.crow_indices()
-            rows = torch.repeat_interleave(torch.arange(A.shape[0], device=crow.device), crow[1:] - crow[:-1])
-            cols, values = A.col_indices(), A.values()
-        else:
-            raise TypeError("from_torch: expected a sparse COO or CSR tensor, got layout %s" % A.layout)
-        pat = SymmetricPattern(rows, cols, A.shape[0], param_sizes, settings, triangle)
-        return pat, values.detach()
-
     def _index(self, which, device):
         key = (which, device)
         if key not in self._dev:
             src = {"to_internal": self._to_internal, "to_user": self._to_user,
+                   "diag": getattr(self, "_diag", None), "jrows": getattr(self, "_jrows", None),
+                   "jcols": getattr(self, "_jcols", None),
                    "keep_internal": getattr(self, "_keep_internal", None),
                    "keep_dest": getattr(self, "_keep_dest", None)}[which]
             self._dev[key] = torch.from_numpy(src).to(device)
@@ -153,6 +142,93 @@ class SymmetricPattern:
         return self._permute(v, "to_user", dim, "fromInternal")
 
 
+
+class SymmetricPattern(_Pattern):
+    """A solver and its assembly map for the symmetric pattern of the entries (rows[k], cols[k]),
+    0 <= rows, cols < n, in the caller's scalar order.  Scalars are grouped into params of
+    `param_sizes` (default: all 1) in order; the param-level lower block structure is derived from the
+    entries and handed to create_solver (fill and ordering as `settings` say).  triangle: "lower"
+    (every entry has row >= col) or "full" (entries with row < col are skipped; the caller asserts the
+    matrix is symmetric).  Invalid entries are refused by the assembly, which names the first one.
+    keep: caller-order scalar indices (distinct, covering whole params) that marginalize() keeps; their
+    params are ordered behind all others, from span `keep_span` on."""
+
+    def __init__(self, rows, cols, n, param_sizes=None, settings=None, triangle="lower", keep=None):
+        rows, cols = _host_i64(rows), _host_i64(cols)
+        if len(rows) != len(cols):
+            raise ValueError("SymmetricPattern: %d rows for %d cols" % (len(rows), len(cols)))
+        param_of = self._init_params(n, param_sizes)
+        n = self.n
+        # the structure takes the well-formed lower entries; the assembly refuses the others by name
+        ok = (rows >= 0) & (rows < n) & (cols >= 0) & (cols < n) & (rows >= cols)
+        ss = _block_structure(len(self.param_sizes), param_of(rows[ok]), param_of(cols[ok]))
+        self._init_solver(ss, settings, keep, param_of)
+        self.assembly = self.solver.assembly(rows, cols, triangle)
+        self.nnz = len(rows)
+        self._init_order()
+
+    @staticmethod
+    def from_torch(A, param_sizes=None, settings=None, triangle="lower"):
+        """(pattern, values) of a square torch sparse COO or CSR tensor, duplicates of an uncoalesced
+        COO tensor kept as separate entries.  Gradients are promised only for the `values` tensor
+        passed explicitly to the functions of this module."""
+        if A.dim() != 2 or A.shape[0] != A.shape[1]:
+            raise ValueError("from_torch: expected a square matrix, got shape %s" % (tuple(A.shape),))
+        if A.layout == torch.sparse_coo:
+            idx, values = A._indices(), A._values()
+            rows, cols = idx[0], idx[1]
+        elif A.layout == torch.sparse_csr:
+            crow = A.crow_indices()
+            rows = torch.repeat_interleave(torch.arange(A.shape[0], device=crow.device), crow[1:] - crow[:-1])
+            cols, values = A.col_indices(), A.values()
+        else:
+            raise TypeError("from_torch: expected a sparse COO or CSR tensor, got layout %s" % A.layout)
+        pat = SymmetricPattern(rows, cols, A.shape[0], param_sizes, settings, triangle)
+        return pat, values.detach()
+
+
+def _row_pairs(starts):
+    """(a, b) positions with a >= b inside each group [starts[g], starts[g + 1]): every unordered pair
+    of a group, self-pairs included, in ascending a"""
+    d = np.diff(starts)
+    total = int(starts[-1])
+    pos = np.arange(total, dtype=np.int64) - np.repeat(starts[:-1], d)
+    a = np.repeat(np.arange(total, dtype=np.int64), pos + 1)
+    first = np.concatenate([[0], np.cumsum(pos + 1)])[:-1]
+    b = np.arange(len(a), dtype=np.int64) - np.repeat(first, pos + 1) + np.repeat(np.arange(total) - pos, pos + 1)
+    return a, b
+
+
+class JacobianPattern(_Pattern):
+    """A solver and the normal-equations maps for the m x n Jacobian with entries
+    (rows[k], cols[k]), 0 <= rows < m, 0 <= cols < n, in the caller's scalar order, no position repeated.
+    Scalars are grouped into params of `param_sizes` (default: all 1); two params are coupled in J^T J
+    when one Jacobian row touches both, so the param-level lower block structure is the union of the
+    rows' cliques, handed to create_solver (fill and ordering as `settings` say).  Invalid entries are
+    refused by the map, which names the first one.  keep: as for SymmetricPattern."""
+
+    def __init__(self, rows, cols, m, n, param_sizes=None, settings=None, keep=None):
+        rows, cols = _host_i64(rows), _host_i64(cols)
+        if len(rows) != len(cols):
+            raise ValueError("JacobianPattern: %d rows for %d cols" % (len(rows), len(cols)))
+        param_of = self._init_params(n, param_sizes)
+        n, m = self.n, int(m)
+        self.m = m
+        # the structure takes the well-formed entries; the map refuses the others by name
+        ok = (rows >= 0) & (rows < m) & (cols >= 0) & (cols < n)
+        num_params = len(self.param_sizes)
+        touch = np.unique(rows[ok] * num_params + param_of(cols[ok]))  # (row, param), sorted by row
+        trow, tpar = touch // num_params, touch % num_params
+        starts = np.concatenate([[0], np.cumsum(np.bincount(trow, minlength=max(m, 1)))]).astype(np.int64)
+        a, b = _row_pairs(starts)
+        ss = _block_structure(num_params, tpar[a], tpar[b])  # tpar ascends inside a row: tpar[a] >= tpar[b]
+        self._init_solver(ss, settings, keep, param_of)
+        self.normal_eq = self.solver.normalEquations(rows, cols, m)
+        self.nnz = len(rows)
+        self._init_order()
+        self._diag = self.solver.diagOffsets()
+        self._jrows, self._jcols = rows, cols
+
 class _Assemble(torch.autograd.Function):
     @staticmethod
     def forward(ctx, asm, values):
@@ -173,9 +249,9 @@ class _Assemble(torch.autograd.Function):
         return None, gv
 
 
-def _check_values(pattern, values, what):
-    if not isinstance(pattern, SymmetricPattern):
-        raise TypeError("%s: pattern must be a SymmetricPattern, got %s" % (what, type(pattern).__name__))
+def _check_values(pattern, values, what, kind=SymmetricPattern):
+    if not isinstance(pattern, kind):
+        raise TypeError("%s: pattern must be a %s, got %s" % (what, kind.__name__, type(pattern).__name__))
     if not isinstance(values, torch.Tensor):
         raise TypeError("%s: values must be a torch.Tensor, got %s" % (what, type(values).__name__))
     if values.dtype not in (torch.float64, torch.float32):
@@ -249,15 +325,19 @@ def marginalize(pattern, values, b=None):
     """S = A22 - A21 A11^-1 A12, [m, m] (or [B, m, m]), block 2 = pattern.keep, rows and columns in the order
     of keep: the marginal precision of the kept scalars.  With b ([n] or [n, k], leading B when batched)
     also r = b2 - A21 A11^-1 b1, [m] or [m, k]: their information vector.  Differentiable in values and b.
-    Needs a pattern built with keep=..."""
-    _check_values(pattern, values, "marginalize")
+    Needs a pattern built with keep=...  With a JacobianPattern, `values` are the Jacobian's and `b` is the
+    residual r ([m] or [m, k]): A = J^T J and the right-hand side is J^T r."""
+    jac = isinstance(pattern, JacobianPattern)
+    _check_values(pattern, values, "marginalize", _Pattern)
     if pattern.keep is None:
         raise ValueError("marginalize: the pattern was built without keep=...")
     sol, span = pattern.solver, pattern.keep_span
     dest = pattern._index("keep_dest", values.device)
-    data = assemble(pattern, values)
+    data = hessian(pattern, values) if jac else assemble(pattern, values)
     if b is None:
         return _ag.schur_complement(sol, data, span, dest=dest)
+    if jac:
+        b = jt_vec(pattern, values, b)
     dim = _check_b(pattern, values, b, "marginalize")
     if b.dtype != values.dtype:
         raise TypeError("marginalize: b has dtype %s, values have %s" % (b.dtype, values.dtype))
@@ -265,3 +345,139 @@ def marginalize(pattern, values, b=None):
     S = _ag._SchurOfFactor.apply(sol, P, span, dest)
     y = _ag.solve_l_up_to(sol, P, span, pattern.toInternal(b, dim))
     return S, y.index_select(dim, pattern._index("keep_internal", values.device))
+
+
+# ---- normal equations of a sparse Jacobian ----------------------------------
+class _Hessian(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ne, values):
+        v = values.detach().contiguous()
+        with _OnCurrentStream(ne.solver, v.device):
+            data = ne.hessian(v)
+        ctx.ne = ne
+        ctx.save_for_backward(v)
+        ctx.set_materialize_grads(False)
+        return data
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if g is None or not ctx.needs_input_grad[1]:
+            return None, None
+        ne, (v,) = ctx.ne, ctx.saved_tensors
+        with _OnCurrentStream(ne.solver, g.device):
+            gv = ne.hessianAdjoint(v, g.contiguous())
+        return None, gv
+
+
+class _JVec(torch.autograd.Function):
+    """transposed: J^T x (x [.., m(, q)]), else J x (x [.., n(, q)]).  The gradient of x is the other
+    kernel on the incoming gradient; that of values[k] is the dot product over the q vectors of the two
+    rows that entry k joins, an elementwise gather."""
+
+    @staticmethod
+    def forward(ctx, jpat, values, x, transposed):
+        ne = jpat.normal_eq
+        v, xc = values.detach().contiguous(), x.detach().contiguous()
+        with _OnCurrentStream(ne.solver, v.device):
+            out = ne.jtVec(v, xc) if transposed else ne.jVec(v, xc)
+        ctx.jpat, ctx.transposed = jpat, transposed
+        ctx.save_for_backward(v, xc)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None
+        jpat, (v, x) = ctx.jpat, ctx.saved_tensors
+        ne, g = jpat.normal_eq, g.contiguous()
+        gv = gx = None
+        if ctx.needs_input_grad[2]:
+            with _OnCurrentStream(ne.solver, g.device):
+                gx = ne.jVec(v, g) if ctx.transposed else ne.jtVec(v, g)
+        if ctx.needs_input_grad[1]:
+            dim = v.dim() - 1
+            rows, cols = jpat._index("jrows", g.device), jpat._index("jcols", g.device)
+            of_rows, of_cols = (x, g) if ctx.transposed else (g, x)  # the [m]-sized and the [n]-sized side
+            gv = of_rows.index_select(dim, rows) * of_cols.index_select(dim, cols)
+            if gv.dim() > v.dim():
+                gv = gv.sum(-1)
+        return None, gv, gx, None
+
+
+def _check_vec(jpat, values, x, size, what, name):
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("%s: %s must be a torch.Tensor, got %s" % (what, name, type(x).__name__))
+    if x.dtype != values.dtype:
+        raise TypeError("%s: %s has dtype %s, jvalues have %s" % (what, name, x.dtype, values.dtype))
+    if x.device != values.device:
+        raise ValueError("%s: %s is on %s, jvalues on %s" % (what, name, x.device, values.device))
+    lo = values.dim()
+    if x.dim() not in (lo, lo + 1) or x.shape[:lo - 1] != values.shape[:lo - 1] or x.shape[lo - 1] != size \
+            or (x.dim() == lo + 1 and x.shape[-1] < 1):
+        raise ValueError("%s: %s must be %s with %d rows, got shape %s" % (
+            what, name, "[B, rows] or [B, rows, q]" if lo == 2 else "[rows] or [rows, q]", size, tuple(x.shape)))
+
+
+def _damp(jpat, data, damping, what):
+    """diag <- diag (1 + alpha) + beta, out of place over the unique diagonal offsets"""
+    if damping is None:
+        return data
+    try:
+        alpha, beta = damping
+    except (TypeError, ValueError):
+        raise TypeError("%s: damping must be a pair (alpha, beta), got %r" % (what, damping)) from None
+    for name, t in (("alpha", alpha), ("beta", beta)):
+        if isinstance(t, torch.Tensor):
+            if t.dim() != 0:
+                raise ValueError("%s: damping %s must be a float or a 0-dim tensor, got shape %s"
+                                 % (what, name, tuple(t.shape)))
+            if t.device != data.device:
+                raise ValueError("%s: damping %s is on %s, jvalues on %s" % (what, name, t.device, data.device))
+        elif not isinstance(t, (int, float)):
+            raise TypeError("%s: damping %s must be a float or a 0-dim tensor, got %s" % (what, name, type(t).__name__))
+    idx = jpat._index("diag", data.device)
+    diag = data.index_select(-1, idx)
+    return data.index_copy(-1, idx, (diag * (1 + alpha) + beta).to(data.dtype))
+
+
+def hessian(jpat, jvalues, damping=None):
+    """H = J^T J (+ D) in the solver's layout, [dataSize] or [B, dataSize], for baspacho_amd.autograd;
+    damping = (alpha, beta): diag <- diag (1 + alpha) + beta, floats or 0-dim tensors.  Differentiable in
+    jvalues, alpha and beta"""
+    _check_values(jpat, jvalues, "hessian", JacobianPattern)
+    return _damp(jpat, _Hessian.apply(jpat.normal_eq, jvalues), damping, "hessian")
+
+
+def jt_vec(jpat, jvalues, r):
+    """g = J^T r in the caller's order: r [m] or [m, q] -> [n] or [n, q] (leading B when batched)"""
+    _check_values(jpat, jvalues, "jt_vec", JacobianPattern)
+    _check_vec(jpat, jvalues, r, jpat.m, "jt_vec", "r")
+    return _JVec.apply(jpat, jvalues, r, True)
+
+
+def j_vec(jpat, jvalues, v):
+    """y = J v: v [n] or [n, q] in the caller's order -> [m] or [m, q] (leading B when batched)"""
+    _check_values(jpat, jvalues, "j_vec", JacobianPattern)
+    _check_vec(jpat, jvalues, v, jpat.n, "j_vec", "v")
+    return _JVec.apply(jpat, jvalues, v, False)
+
+
+def normal_equations(jpat, jvalues, r, damping=None):
+    """(data, g): H = J^T J (+ D) in the solver's layout and g = J^T r in the caller's order"""
+    _check_values(jpat, jvalues, "normal_equations", JacobianPattern)
+    _check_vec(jpat, jvalues, r, jpat.m, "normal_equations", "r")
+    return _damp(jpat, _Hessian.apply(jpat.normal_eq, jvalues), damping, "normal_equations"), \
+        _JVec.apply(jpat, jvalues, r, True)
+
+
+def lstsq(jpat, jvalues, r, damping=None):
+    """x = (J^T J + D)^-1 J^T r in the caller's order, [n] or [n, q]: the Gauss-Newton / Levenberg-Marquardt
+    step of the residual r.  Differentiable in jvalues, r and the damping factors"""
+    _check_values(jpat, jvalues, "lstsq", JacobianPattern)
+    _check_vec(jpat, jvalues, r, jpat.m, "lstsq", "r")
+    data, g = normal_equations(jpat, jvalues, r, damping)
+    dim = jvalues.dim() - 1
+    return jpat.fromInternal(_ag.solve(jpat.solver, data, jpat.toInternal(g, dim)), dim)

@@ -402,6 +402,76 @@ int bsp_assemble_adjoint_batched_f64(bsp_solver* s, const bsp_assembly* a, const
                                      double* const* dev_grad_values, int32_t batch);
 int bsp_assemble_adjoint_batched_f32(bsp_solver* s, const bsp_assembly* a, const float* const* dev_grad_data,
                                      float* const* dev_grad_values, int32_t batch);
+/* Extension (no counterpart in the reference): the normal equations of a sparse Jacobian J, m x order(),
+   given as entries (rows[k], cols[k], values[k]) in the caller's scalar order.
+   - No (row, col) may repeat; empty rows and columns are fine; nnz, m and the pair count P = sum over
+     rows of d (d + 1) / 2 (d: entries of the row) must be in [0, 2^31).
+   - Every unordered pair of entries of one row, self-pairs included, is a pair (ka, kb) with cols[ka] >=
+     cols[kb]; it adds values[ka] * values[kb] to the stored lower element of (cols[ka], cols[kb]), found
+     as the assembly finds it.  That element must be stored by the solver.
+   bsp_normal_eq_create builds the map once on the host (no device work) and fails, with bsp_last_error()
+   naming the first offending entry and its (row, col), on an index out of range, a repeated position
+   or a pair outside the stored pattern, and stating P when P >= 2^31.  The map has three parts, each
+   uploaded by the first call that needs it (forward: hessian; adjoint: hessian_adjoint; vector lists:
+   jt_vec / j_vec) and kept until bsp_normal_eq_destroy.  A map belongs to the solver it was built on and
+   must be destroyed before that solver. */
+typedef struct bsp_normal_eq bsp_normal_eq;
+int bsp_normal_eq_create(bsp_solver* s, int64_t m, int64_t nnz, const int64_t* rows, const int64_t* cols,
+                         bsp_normal_eq** out);
+void bsp_normal_eq_destroy(bsp_normal_eq* e);
+/* figures of the map: out[0] nnz, [1] pairs P, [2] distinct elements written by pairs, [3] most pairs summed
+   into one element, [4] elements summed by a whole wave (runs > 64), [5] tiles of the hessian kernel,
+   [6] / [7] / [8] device bytes of the forward / adjoint / vector parts once uploaded, [9] adjoint terms (2 P) */
+int bsp_normal_eq_info(const bsp_normal_eq* e, int64_t out[10]);
+/* host copy of the forward map in run order (P values each): pair x is (ka[x], kb[x]) and lands on
+   layout offset offset[x]; ascending offset, ascending ka inside one offset */
+int bsp_normal_eq_pair_table(const bsp_normal_eq* e, int32_t* ka, int32_t* kb, int64_t* offset);
+/* bsp_normal_eq_hessian_*: writes EVERY element of dev_data (its previous contents never matter): the sum of
+   the products of its pairs in ascending ka, each product rounded in the value type, added one by one from
+   +0 (bitwise np.add.at(zeros(dataSize), offset, values[ka] * values[kb])), 0 where no pair lands.
+   bsp_normal_eq_hessian_adjoint_*: dev_grad_values[k] = sum of dev_grad_data[offset of the pair] *
+   dev_values[partner] over the pairs that hold k, in ascending partner index, the self-pair twice; with
+   section 13's convention for the gradient of the data this is the exact gradient of the entry values.
+   bsp_normal_eq_jt_vec_*: dev_out[c, j] = sum over the entries of column c, ascending k, of values[k] *
+   dev_r[rows[k], j]  (dev_r [m, q], dev_out [order, q], row-major, q >= 1 vectors).
+   bsp_normal_eq_j_vec_*: dev_out[i, j] = sum over the entries of row i, ascending k, of values[k] *
+   dev_v[cols[k], j]  (dev_v [order, q], dev_out [m, q]).
+   All run on the stream of bsp_set_stream without atomics or host synchronisation; results are bitwise
+   reproducible and batch member b (HOST arrays of `batch` device pointers) is bitwise the single call.
+   An empty batch, a NULL array or member (a side of size 0 may be NULL), a repeated output pointer, an
+   output that aliases an input, or a map built on another solver: non-zero return before any device work. */
+int bsp_normal_eq_hessian_f64(bsp_solver* s, const bsp_normal_eq* e, const double* dev_values, double* dev_data);
+int bsp_normal_eq_hessian_batched_f64(bsp_solver* s, const bsp_normal_eq* e, const double* const* dev_values,
+                                      double* const* dev_data, int32_t batch);
+int bsp_normal_eq_hessian_adjoint_f64(bsp_solver* s, const bsp_normal_eq* e, const double* dev_values,
+                                      const double* dev_grad_data, double* dev_grad_values);
+int bsp_normal_eq_hessian_adjoint_batched_f64(bsp_solver* s, const bsp_normal_eq* e, const double* const* dev_values,
+                                              const double* const* dev_grad_data, double* const* dev_grad_values,
+                                              int32_t batch);
+int bsp_normal_eq_jt_vec_f64(bsp_solver* s, const bsp_normal_eq* e, const double* dev_values, const double* dev_r,
+                             int64_t q, double* dev_out);
+int bsp_normal_eq_jt_vec_batched_f64(bsp_solver* s, const bsp_normal_eq* e, const double* const* dev_values,
+                                     const double* const* dev_r, int64_t q, double* const* dev_out, int32_t batch);
+int bsp_normal_eq_j_vec_f64(bsp_solver* s, const bsp_normal_eq* e, const double* dev_values, const double* dev_v,
+                            int64_t q, double* dev_out);
+int bsp_normal_eq_j_vec_batched_f64(bsp_solver* s, const bsp_normal_eq* e, const double* const* dev_values,
+                                    const double* const* dev_v, int64_t q, double* const* dev_out, int32_t batch);
+int bsp_normal_eq_hessian_f32(bsp_solver* s, const bsp_normal_eq* e, const float* dev_values, float* dev_data);
+int bsp_normal_eq_hessian_batched_f32(bsp_solver* s, const bsp_normal_eq* e, const float* const* dev_values,
+                                      float* const* dev_data, int32_t batch);
+int bsp_normal_eq_hessian_adjoint_f32(bsp_solver* s, const bsp_normal_eq* e, const float* dev_values,
+                                      const float* dev_grad_data, float* dev_grad_values);
+int bsp_normal_eq_hessian_adjoint_batched_f32(bsp_solver* s, const bsp_normal_eq* e, const float* const* dev_values,
+                                              const float* const* dev_grad_data, float* const* dev_grad_values,
+                                              int32_t batch);
+int bsp_normal_eq_jt_vec_f32(bsp_solver* s, const bsp_normal_eq* e, const float* dev_values, const float* dev_r,
+                             int64_t q, float* dev_out);
+int bsp_normal_eq_jt_vec_batched_f32(bsp_solver* s, const bsp_normal_eq* e, const float* const* dev_values,
+                                     const float* const* dev_r, int64_t q, float* const* dev_out, int32_t batch);
+int bsp_normal_eq_j_vec_f32(bsp_solver* s, const bsp_normal_eq* e, const float* dev_values, const float* dev_v,
+                            int64_t q, float* dev_out);
+int bsp_normal_eq_j_vec_batched_f32(bsp_solver* s, const bsp_normal_eq* e, const float* const* dev_values,
+                                    const float* const* dev_v, int64_t q, float* const* dev_out, int32_t batch);
 /* out[i_user] = i_internal (order values): the caller's scalar i in the solver's internal vector order
    (param p at spanStart[paramToSpan[p]], its scalars in order) */
 int bsp_scalar_permutation(const bsp_solver* s, int64_t* out);
