@@ -179,6 +179,32 @@ def _suffix(t):
     raise TypeError("only float64 / float32 data is supported, got %s" % t.dtype)
 
 
+def _ptr_array(tensors):
+    """host array of the device pointers of `tensors`, one per batch member (None: a NULL array)"""
+    if tensors is None:
+        return None
+    return (ctypes.c_void_p * len(tensors))(*[_ptr_of(t) for t in tensors])
+
+
+def _ptr_arg(members, batched):
+    """a pointer argument of an entry that has a batched form: the pointer array of the members for a
+    batch, the pointer of the one member else (None: NULL either way)"""
+    if members is None:
+        return None
+    return _ptr_array(members) if batched else ctypes.c_void_p(_ptr_of(members[0]))
+
+
+def _count(members, batched):
+    """the batch-size argument of a batched entry (none for a single call)"""
+    return (ctypes.c_int32(len(members)),) if batched else ()
+
+
+def _call(lib, name, batched, sfx, *args):
+    """call `name` + ["batched_"] + sfx, the single or the batched entry of one operation; raises the
+    library's error"""
+    _check(getattr(lib, name + ("batched_" if batched else "") + sfx)(*args))
+
+
 class Solver:
     """Mirror of BaSpaCho::Solver (Solver.h:34-180).  Do not construct directly: use
     `create_solver`, `Solver.from_skeleton` or `Solver.from_plan`."""
@@ -317,7 +343,7 @@ class Solver:
             sfx = _suffix(data[0])
             for t in data:
                 self._check_data(t)
-            ptrs = (ctypes.c_void_p * len(data))(*[_ptr_of(t) for t in data])
+            ptrs = _ptr_array(data)
             _check(getattr(self._lib, "bsp_factor_batched_" + sfx)(self._h, ptrs,
                                                                    ctypes.c_int32(len(data))))
         else:
@@ -409,7 +435,7 @@ class Solver:
     def _factor_partial_batched(self, which, data, span_index):
         for t in data:
             self._check_data(t)
-        ptrs = (ctypes.c_void_p * len(data))(*[_ptr_of(t) for t in data])
+        ptrs = _ptr_array(data)
         _check(getattr(self._lib, "bsp_factor_partial_batched_" + _suffix(data[0]))(
             self._h, ptrs, ctypes.c_int32(len(data)), ctypes.c_int64(span_index), ctypes.c_int32(which)))
 
@@ -442,8 +468,8 @@ class Solver:
             for t in mat:
                 self._check_data(t)
             which = {"bsp_solve_": 0, "bsp_solve_l_": 1, "bsp_solve_lt_": 2}[name]
-            mats = (ctypes.c_void_p * len(mat))(*[_ptr_of(t) for t in mat])
-            vecs = (ctypes.c_void_p * len(vec))(*[_ptr_of(t) for t in vec])
+            mats = _ptr_array(mat)
+            vecs = _ptr_array(vec)
             _check(getattr(self._lib, "bsp_solve_batched_" + _suffix(mat[0]))(
                 self._h, mats, vecs, ctypes.c_int32(len(mat)), ctypes.c_int64(stride),
                 ctypes.c_int32(nrhs), ctypes.c_int32(which)))
@@ -469,8 +495,8 @@ class Solver:
             assert isinstance(vec, (list, tuple)) and len(vec) == len(mat)
             for t in mat:
                 self._check_data(t)
-            mats = (ctypes.c_void_p * len(mat))(*[_ptr_of(t) for t in mat])
-            vecs = (ctypes.c_void_p * len(vec))(*[_ptr_of(t) for t in vec])
+            mats = _ptr_array(mat)
+            vecs = _ptr_array(vec)
             _check(getattr(self._lib, "bsp_solve_partial_batched_" + _suffix(mat[0]))(
                 self._h, mats, vecs, ctypes.c_int32(len(mat)), ctypes.c_int64(stride),
                 ctypes.c_int32(nrhs), ctypes.c_int32(which), ctypes.c_int64(span_index)))
@@ -516,22 +542,11 @@ class Solver:
         accessors read Z as they read L).  bsp_selected_inverse_f64 / _f32.
         A list/tuple of tensors (one dtype, distinct buffers) = a batch of factors of this solver
         (bsp_selected_inverse_batched_*): member q is bitwise selectedInverse(data[q])."""
-        if isinstance(data, (list, tuple)):
-            if len(data) == 0:
-                raise ValueError("selectedInverse: empty batch")
-            if len({t.dtype for t in data}) != 1:
-                raise TypeError("selectedInverse: the members of a batch must share one dtype, got %s"
-                                % sorted({str(t.dtype) for t in data}))
-            sfx = _suffix(data[0])
-            for t in data:
-                self._check_data(t)
-            ptrs = (ctypes.c_void_p * len(data))(*[_ptr_of(t) for t in data])
-            _check(getattr(self._lib, "bsp_selected_inverse_batched_" + sfx)(
-                self._h, ptrs, ctypes.c_int32(len(data))))
-            return
-        self._check_data(data)
-        _check(getattr(self._lib, "bsp_selected_inverse_" + _suffix(data))(
-            self._h, ctypes.c_void_p(_ptr_of(data))))
+        batched, (ds,) = self._same_kind("selectedInverse", "data", data)
+        for t in ds:
+            self._check_data(t)
+        _call(self._lib, "bsp_selected_inverse_", batched, _suffix(ds[0]), self._h, _ptr_arg(ds, batched),
+              *_count(ds, batched))
 
     def marginals(self, data, params):
         """diagonal covariance blocks of the given user-order parameters, read from the output of
@@ -574,23 +589,12 @@ class Solver:
         solver's stream without synchronising; a non-positive or NaN pivot gives -inf or NaN.  A
         list/tuple of tensors (one dtype) = a batch: a device tensor [B] (bsp_log_det_batched_*)."""
         import torch
-        if isinstance(data, (list, tuple)):
-            if len(data) == 0:
-                raise ValueError("logDet: empty batch")
-            if len({t.dtype for t in data}) != 1:
-                raise TypeError("logDet: the members of a batch must share one dtype")
-            sfx = _suffix(data[0])
-            for t in data:
-                self._check_data(t)
-            ptrs = (ctypes.c_void_p * len(data))(*[_ptr_of(t) for t in data])
-            out = torch.empty(len(data), dtype=data[0].dtype, device=data[0].device)
-            _check(getattr(self._lib, "bsp_log_det_batched_" + sfx)(
-                self._h, ptrs, ctypes.c_void_p(_ptr_of(out)), ctypes.c_int32(len(data))))
-            return out
-        self._check_data(data)
-        out = torch.empty((), dtype=data.dtype, device=data.device)
-        _check(getattr(self._lib, "bsp_log_det_" + _suffix(data))(
-            self._h, ctypes.c_void_p(_ptr_of(data)), ctypes.c_void_p(_ptr_of(out))))
+        batched, (ds,) = self._same_kind("logDet", "data", data)
+        for t in ds:
+            self._check_data(t)
+        out = torch.empty((len(ds),) if batched else (), dtype=ds[0].dtype, device=ds[0].device)
+        _call(self._lib, "bsp_log_det_", batched, _suffix(ds[0]), self._h, _ptr_arg(ds, batched),
+              ctypes.c_void_p(_ptr_of(out)), *_count(ds, batched))
         return out
 
     def patternGrad(self, out, Z=None, zScale=None, U=None, V=None, nRHS=1, alpha=1.0, stride=None):
@@ -602,43 +606,20 @@ class Solver:
         leading dimension `stride` (default order()), e.g. tensors [nRHS, order] (none: no second
         term).  `out` a list/tuple = a batch: Z, U, V lists of the same length (or None), s =
         zScale[q] for member q."""
-        batched = isinstance(out, (list, tuple))
-        outs = list(out) if batched else [out]
-        if len(outs) == 0:
-            raise ValueError("patternGrad: empty batch")
-        if stride is None:
-            stride = self.order()
-
-        def members(x, name):
-            if x is None:
-                return None
-            xs = list(x) if batched else [x]
-            if len(xs) != len(outs):
-                raise ValueError("patternGrad: %s has %d members for a batch of %d" % (name, len(xs), len(outs)))
-            return xs
-        zs, us, vs = members(Z, "Z"), members(U, "U"), members(V, "V")
-        dt = outs[0].dtype
-        for t in outs + (zs or []) + (us or []) + (vs or []) + ([zScale] if zScale is not None else []):
-            if t.dtype != dt:
-                raise TypeError("patternGrad: every tensor must have the dtype of out (%s), got %s" % (dt, t.dtype))
+        given = {n: x for n, x in (("out", out), ("Z", Z), ("U", U), ("V", V)) if x is not None}
+        batched, ms = self._same_kind("patternGrad", " / ".join(given), *given.values())
+        ms = dict(zip(given, ms))
+        outs, zs, us, vs = ms["out"], ms.get("Z"), ms.get("U"), ms.get("V")
+        if zScale is not None and zScale.dtype != outs[0].dtype:
+            raise TypeError("patternGrad: zScale must have the dtype of out (%s), got %s" % (outs[0].dtype, zScale.dtype))
         for t in outs + (zs or []):
             self._check_data(t)
         sfx = _suffix(outs[0])
         real = ctypes.c_double if sfx == "f64" else ctypes.c_float
-        zsp = ctypes.c_void_p(_ptr_of(zScale) if zScale is not None else None)
-        if batched:
-            def arr(xs):
-                return None if xs is None else (ctypes.c_void_p * len(xs))(*[_ptr_of(t) for t in xs])
-            _check(getattr(self._lib, "bsp_pattern_grad_batched_" + sfx)(
-                self._h, arr(zs), zsp, arr(us), arr(vs), ctypes.c_int64(stride), ctypes.c_int32(nRHS),
-                real(alpha), arr(outs), ctypes.c_int32(len(outs))))
-            return
-
-        def one(xs):
-            return ctypes.c_void_p(None if xs is None else _ptr_of(xs[0]))
-        _check(getattr(self._lib, "bsp_pattern_grad_" + sfx)(
-            self._h, one(zs), zsp, one(us), one(vs), ctypes.c_int64(stride), ctypes.c_int32(nRHS),
-            real(alpha), one(outs)))
+        _call(self._lib, "bsp_pattern_grad_", batched, sfx, self._h, _ptr_arg(zs, batched),
+              ctypes.c_void_p(_ptr_of(zScale) if zScale is not None else None), _ptr_arg(us, batched),
+              _ptr_arg(vs, batched), ctypes.c_int64(self.order() if stride is None else stride), ctypes.c_int32(nRHS),
+              real(alpha), _ptr_arg(outs, batched), *_count(outs, batched))
 
     def patternOuter(self, out, U, V, nRHS=1, alpha=1.0, stride=None):
         """extension: the non-symmetric rank-k projection on the pattern of L (bsp_pattern_outer_*).
@@ -646,33 +627,14 @@ class Solver:
         strictly-upper elements of the diagonal blocks: 0.  U, V column-major order x nRHS with leading
         dimension `stride` (default order()), e.g. tensors [nRHS, order].  `out` a list/tuple = a batch:
         U, V lists of the same length."""
-        batched = isinstance(out, (list, tuple))
-        outs, us, vs = (list(out), list(U), list(V)) if batched else ([out], [U], [V])
-        if len(outs) == 0:
-            raise ValueError("patternOuter: empty batch")
-        if len(us) != len(outs) or len(vs) != len(outs):
-            raise ValueError("patternOuter: U / V have %d / %d members for a batch of %d"
-                             % (len(us), len(vs), len(outs)))
-        if stride is None:
-            stride = self.order()
-        dt = outs[0].dtype
-        for t in outs + us + vs:
-            if t.dtype != dt:
-                raise TypeError("patternOuter: every tensor must have the dtype of out (%s), got %s" % (dt, t.dtype))
+        batched, (outs, us, vs) = self._same_kind("patternOuter", "out / U / V", out, U, V)
         for t in outs:
             self._check_data(t)
         sfx = _suffix(outs[0])
         real = ctypes.c_double if sfx == "f64" else ctypes.c_float
-        if batched:
-            def arr(xs):
-                return (ctypes.c_void_p * len(xs))(*[_ptr_of(t) for t in xs])
-            _check(getattr(self._lib, "bsp_pattern_outer_batched_" + sfx)(
-                self._h, arr(us), arr(vs), ctypes.c_int64(stride), ctypes.c_int32(nRHS), real(alpha), arr(outs),
-                ctypes.c_int32(len(outs))))
-            return
-        _check(getattr(self._lib, "bsp_pattern_outer_" + sfx)(
-            self._h, ctypes.c_void_p(_ptr_of(us[0])), ctypes.c_void_p(_ptr_of(vs[0])), ctypes.c_int64(stride),
-            ctypes.c_int32(nRHS), real(alpha), ctypes.c_void_p(_ptr_of(outs[0]))))
+        _call(self._lib, "bsp_pattern_outer_", batched, sfx, self._h, _ptr_arg(us, batched), _ptr_arg(vs, batched),
+              ctypes.c_int64(self.order() if stride is None else stride), ctypes.c_int32(nRHS), real(alpha),
+              _ptr_arg(outs, batched), *_count(outs, batched))
 
     def factorAdjoint(self, L, grad):
         """extension: the reverse-mode sweep of factor(), in place in `grad` (bsp_factor_adjoint_*).
@@ -681,31 +643,13 @@ class Solver:
         on return: G_ij + G_ji below the diagonal, G_ii on it, 0 above it.
         Lists/tuples of tensors (one dtype, distinct buffers) = a batch: member q is bitwise the single
         call."""
-        if isinstance(L, (list, tuple)) != isinstance(grad, (list, tuple)):
-            raise TypeError("factorAdjoint: L and grad must both be tensors or both be lists")
-        if isinstance(L, (list, tuple)):
-            if len(grad) == 0:
-                raise ValueError("factorAdjoint: empty batch")
-            if len(L) != len(grad):
-                raise ValueError("factorAdjoint: %d factors for %d gradients" % (len(L), len(grad)))
-            ts = list(L) + list(grad)
-        else:
-            ts = [L, grad]
-        if len({t.dtype for t in ts}) != 1:
-            raise TypeError("factorAdjoint: every tensor must share one dtype, got %s" % sorted({str(t.dtype) for t in ts}))
-        for t in ts:
+        batched, (ls, gs) = self._same_kind("factorAdjoint", "L and grad", L, grad)
+        for t in ls + gs:
             self._check_data(t)
-        sfx = _suffix(ts[0])
-        if isinstance(L, (list, tuple)):
-            def arr(xs):
-                return (ctypes.c_void_p * len(xs))(*[_ptr_of(t) for t in xs])
-            _check(getattr(self._lib, "bsp_factor_adjoint_batched_" + sfx)(
-                self._h, arr(L), arr(grad), ctypes.c_int32(len(grad))))
-            return
-        _check(getattr(self._lib, "bsp_factor_adjoint_" + sfx)(
-            self._h, ctypes.c_void_p(_ptr_of(L)), ctypes.c_void_p(_ptr_of(grad))))
+        _call(self._lib, "bsp_factor_adjoint_", batched, _suffix(gs[0]), self._h, _ptr_arg(ls, batched),
+              _ptr_arg(gs, batched), *_count(gs, batched))
 
-    # ---- the partial factor and its Schur complement (DESIGN.md section 16) -----------------
+    # ---- arguments that are one tensor each, or lists of tensors = a batch ---------------------
     def _same_kind(self, what, names, *xs):
         """(batched, [members of every x]) for arguments that are all tensors or all lists of one length"""
         kinds = {isinstance(x, (list, tuple)) for x in xs}
@@ -724,6 +668,7 @@ class Solver:
             raise ValueError("%s: tensors on different devices: %s" % (what, sorted({str(t.device) for t in ts})))
         return batched, ms
 
+    # ---- the partial factor and its Schur complement -----------------
     def _schurOrder(self, span):
         """scalars from span `span` on: the order m of the Schur complement of factorUpTo(span)"""
         if not 0 <= span <= self.numSpans():
@@ -739,15 +684,8 @@ class Solver:
         batched, (ps, gs) = self._same_kind("factorAdjointUpTo", "P and grad", P, grad)
         for t in ps + gs:
             self._check_data(t)
-        sfx = _suffix(gs[0])
-        if batched:
-            def arr(xs):
-                return (ctypes.c_void_p * len(xs))(*[_ptr_of(t) for t in xs])
-            _check(getattr(self._lib, "bsp_factor_adjoint_up_to_batched_" + sfx)(
-                self._h, arr(ps), arr(gs), ctypes.c_int32(len(gs)), ctypes.c_int64(span)))
-            return
-        _check(getattr(self._lib, "bsp_factor_adjoint_up_to_" + sfx)(
-            self._h, ctypes.c_void_p(_ptr_of(ps[0])), ctypes.c_void_p(_ptr_of(gs[0])), ctypes.c_int64(span)))
+        _call(self._lib, "bsp_factor_adjoint_up_to_", batched, _suffix(gs[0]), self._h, _ptr_arg(ps, batched),
+              _ptr_arg(gs, batched), *_count(gs, batched), ctypes.c_int64(span))
 
     def _schur_dense(self, what, name, src, span, out, dest, to_dense):
         import torch
@@ -774,17 +712,9 @@ class Solver:
             if dest.dtype != torch.int32 or dest.numel() != m or dest.device != srcs[0].device:
                 raise ValueError("%s: dest must be an int32 tensor of %d elements on %s" % (what, m, srcs[0].device))
             dp = _ptr_of(dest)
-        sfx = _suffix(srcs[0])
-        fn = "bsp_schur_to_dense_" if to_dense else "bsp_schur_from_dense_"
-        if batched:
-            def arr(xs):
-                return (ctypes.c_void_p * len(xs))(*[_ptr_of(t) for t in xs])
-            _check(getattr(self._lib, fn + "batched_" + sfx)(
-                self._h, arr(srcs), ctypes.c_int64(span), arr(outs), ctypes.c_void_p(dp), ctypes.c_int32(len(outs))))
-        else:
-            _check(getattr(self._lib, fn + sfx)(
-                self._h, ctypes.c_void_p(_ptr_of(srcs[0])), ctypes.c_int64(span), ctypes.c_void_p(_ptr_of(outs[0])),
-                ctypes.c_void_p(dp)))
+        _call(self._lib, "bsp_schur_to_dense_" if to_dense else "bsp_schur_from_dense_", batched, _suffix(srcs[0]),
+              self._h, _ptr_arg(srcs, batched), ctypes.c_int64(span), _ptr_arg(outs, batched), ctypes.c_void_p(dp),
+              *_count(outs, batched))
         return out
 
     def schurComplement(self, P, span, out=None, dest=None):
@@ -998,16 +928,10 @@ class Assembly:
             raise ValueError("%s: out must be %s %s on %s, got %s %s on %s" % (
                 name, tuple(shape), x.dtype, x.device, tuple(out.shape), out.dtype, out.device))
         _ptr_of(x), _ptr_of(out)  # device memory, contiguous
-        fn = "bsp_assemble_adjoint_" if adjoint else "bsp_assemble_"
-        if x.dim() == 2:
-            B_ = x.shape[0]
-            ins = (ctypes.c_void_p * B_)(*[x[q].data_ptr() for q in range(B_)])
-            outs = (ctypes.c_void_p * B_)(*[out[q].data_ptr() for q in range(B_)])
-            _check(getattr(self._lib, fn + "batched_" + sfx)(self.solver._h, self._h, ins, outs,
-                                                            ctypes.c_int32(B_)))
-        else:
-            _check(getattr(self._lib, fn + sfx)(self.solver._h, self._h, ctypes.c_void_p(x.data_ptr()),
-                                               ctypes.c_void_p(out.data_ptr())))
+        batched = x.dim() == 2
+        xs, outs = (x.unbind(0), out.unbind(0)) if batched else ([x], [out])
+        _call(self._lib, "bsp_assemble_adjoint_" if adjoint else "bsp_assemble_", batched, sfx, self.solver._h, self._h,
+              _ptr_arg(xs, batched), _ptr_arg(outs, batched), *_count(xs, batched))
         return out
 
     def assemble(self, values, out=None):
@@ -1108,19 +1032,13 @@ class NormalEquations:
         elif tuple(out.shape) != shape or out.dtype != values.dtype or out.device != values.device:
             raise ValueError("%s: out must be %s %s on %s, got %s %s on %s" % (
                 name, shape, values.dtype, values.device, tuple(out.shape), out.dtype, out.device))
-        for t in (values, x, out):
-            if t is not None:
-                _ptr_of(t)  # device memory, contiguous
-        P = ctypes.c_void_p
-        qa = () if q is None else (ctypes.c_int64(q),)
-        if batched:
-            B_ = values.shape[0]
-            arr = lambda t: (P * B_)(*[t[b].data_ptr() for b in range(B_)])
-            args = (arr(values),) + (() if x is None else (arr(x),)) + qa + (arr(out), ctypes.c_int32(B_))
-            _check(getattr(self._lib, fn + "batched_" + sfx)(self.solver._h, self._h, *args))
-        else:
-            args = (P(values.data_ptr()),) + (() if x is None else (P(x.data_ptr()),)) + qa + (P(out.data_ptr()),)
-            _check(getattr(self._lib, fn + sfx)(self.solver._h, self._h, *args))
+        ts = [t for t in (values, x, out) if t is not None]
+        for t in ts:
+            _ptr_of(t)  # device memory, contiguous
+        ptrs = [_ptr_arg(t.unbind(0) if batched else [t], batched) for t in ts]
+        qa = [] if q is None else [ctypes.c_int64(q)]
+        _call(self._lib, fn, batched, sfx, self.solver._h, self._h, *ptrs[:-1], *qa, ptrs[-1],
+              *_count(values, batched))
         return out
 
     def hessian(self, values, out=None):

@@ -45,6 +45,13 @@ const char* bsp_version(void) { return "baspacho_amd 0.1 (gfx950)"; }
     return 1;                          \
   }                                    \
   return 0;
+// the whole body of an entry that is one statement (the per-dtype macros below)
+#define BSP_BODY(...) \
+  {                   \
+    BSP_TRY           \
+    __VA_ARGS__;      \
+    BSP_CATCH         \
+  }
 
 void bsp_hip_options_default(bsp_hip_options* o) {
   o->lookahead = o->due_stream = o->split_k = o->gather_max_pairs = o->gather_overlap = o->sub_batch_min =
@@ -459,218 +466,114 @@ int bsp_add_mv_from_f32(bsp_solver* s, const float* m, int64_t span, const float
   s->solver->addMvFrom(m, span, in, in_stride, out, out_stride, nrhs, alpha);
   BSP_CATCH
 }
-int bsp_selected_inverse_f64(bsp_solver* s, double* d) {
-  BSP_TRY
-  s->solver->selectedInverse(d);
-  BSP_CATCH
-}
-int bsp_selected_inverse_f32(bsp_solver* s, float* d) {
-  BSP_TRY
-  s->solver->selectedInverse(d);
-  BSP_CATCH
+// ---- extension operations: single and batched entry of every operation, once per dtype -------------
+// the `batch` device pointers of a batched entry as a vector of P (T* or const T*), checked first.
+// `name` says which array it is; NULL: the operation's message does not tell its arrays apart
+template <typename P, typename T>
+static std::vector<P> hostArray(const std::string& what, const char* name, const T* const* p, int32_t batch) {
+  if (batch <= 0) throw std::runtime_error(what + ": the batch is empty (batch = " + std::to_string(batch) + ")");
+  if (p == nullptr) {
+    throw std::runtime_error(what + (name ? std::string(": the array of ") + name + " pointers" : ": an array of pointers") +
+                             " is NULL");
+  }
+  std::vector<P> v(batch);
+  for (int32_t q = 0; q < batch; q++) v[q] = const_cast<P>(p[q]);
+  return v;
 }
 template <typename T>
 static void selectedInverseBatched(bsp_solver* s, T* const* ptrs, int32_t batch) {
-  if (batch <= 0) throw std::runtime_error("selectedInverse: the batch is empty (batch = " + std::to_string(batch) + ")");
-  if (ptrs == nullptr) throw std::runtime_error("selectedInverse: the array of data pointers is NULL");
-  std::vector<T*> v(ptrs, ptrs + batch);
+  std::vector<T*> v = hostArray<T*>("selectedInverse", "data", ptrs, batch);
   s->solver->selectedInverse(&v);
-}
-int bsp_selected_inverse_batched_f64(bsp_solver* s, double* const* ptrs, int32_t batch) {
-  BSP_TRY
-  selectedInverseBatched(s, ptrs, batch);
-  BSP_CATCH
-}
-int bsp_selected_inverse_batched_f32(bsp_solver* s, float* const* ptrs, int32_t batch) {
-  BSP_TRY
-  selectedInverseBatched(s, ptrs, batch);
-  BSP_CATCH
-}
-int bsp_log_det_f64(bsp_solver* s, const double* f, double* out) {
-  BSP_TRY
-  s->solver->logDet(f, out);
-  BSP_CATCH
-}
-int bsp_log_det_f32(bsp_solver* s, const float* f, float* out) {
-  BSP_TRY
-  s->solver->logDet(f, out);
-  BSP_CATCH
 }
 template <typename T>
 static void logDetBatched(bsp_solver* s, const T* const* ptrs, T* out, int32_t batch) {
-  if (batch <= 0) throw std::runtime_error("logDet: the batch is empty (batch = " + std::to_string(batch) + ")");
-  if (ptrs == nullptr) throw std::runtime_error("logDet: the array of factor pointers is NULL");
-  std::vector<T*> v(batch);
-  for (int32_t q = 0; q < batch; q++) v[q] = const_cast<T*>(ptrs[q]);
-  s->solver->logDet(v, out);
-}
-int bsp_log_det_batched_f64(bsp_solver* s, const double* const* f, double* out, int32_t batch) {
-  BSP_TRY
-  logDetBatched(s, f, out, batch);
-  BSP_CATCH
-}
-int bsp_log_det_batched_f32(bsp_solver* s, const float* const* f, float* out, int32_t batch) {
-  BSP_TRY
-  logDetBatched(s, f, out, batch);
-  BSP_CATCH
-}
-int bsp_pattern_grad_f64(bsp_solver* s, const double* z, const double* zs, const double* u, const double* v,
-                         int64_t stride, int32_t nrhs, double alpha, double* out) {
-  BSP_TRY
-  s->solver->patternGrad(z, zs, u, v, stride, nrhs, alpha, out);
-  BSP_CATCH
-}
-int bsp_pattern_grad_f32(bsp_solver* s, const float* z, const float* zs, const float* u, const float* v,
-                         int64_t stride, int32_t nrhs, float alpha, float* out) {
-  BSP_TRY
-  s->solver->patternGrad(z, zs, u, v, stride, nrhs, alpha, out);
-  BSP_CATCH
+  s->solver->logDet(hostArray<T*>("logDet", "factor", ptrs, batch), out);
 }
 template <typename T>
 static void patternGradBatched(bsp_solver* s, const T* const* z, const T* zs, const T* const* u,
                                const T* const* v, int64_t stride, int32_t nrhs, T alpha, T* const* out,
                                int32_t batch) {
-  if (batch <= 0) throw std::runtime_error("patternGrad: the batch is empty (batch = " + std::to_string(batch) + ")");
-  if (out == nullptr) throw std::runtime_error("patternGrad: the array of output pointers is NULL");
+  const char* what = "patternGrad";
+  const std::vector<T*> o = hostArray<T*>(what, "output", out, batch);
   if ((u == nullptr) != (v == nullptr)) throw std::runtime_error("patternGrad: U and V must be given together");
-  const auto vec = [batch](const T* const* p) {
-    std::vector<T*> r;
-    if (p) for (int32_t q = 0; q < batch; q++) r.push_back(const_cast<T*>(p[q]));
-    return r;
+  const auto opt = [&](const char* name, const T* const* p) {  // an array that was not given: no members
+    return p ? hostArray<T*>(what, name, p, batch) : std::vector<T*>{};
   };
-  s->solver->patternGrad(vec(z), zs, vec(u), vec(v), stride, nrhs, alpha, std::vector<T*>(out, out + batch));
-}
-int bsp_pattern_grad_batched_f64(bsp_solver* s, const double* const* z, const double* zs,
-                                 const double* const* u, const double* const* v, int64_t stride, int32_t nrhs,
-                                 double alpha, double* const* out, int32_t batch) {
-  BSP_TRY
-  patternGradBatched(s, z, zs, u, v, stride, nrhs, alpha, out, batch);
-  BSP_CATCH
-}
-int bsp_pattern_grad_batched_f32(bsp_solver* s, const float* const* z, const float* zs,
-                                 const float* const* u, const float* const* v, int64_t stride, int32_t nrhs,
-                                 float alpha, float* const* out, int32_t batch) {
-  BSP_TRY
-  patternGradBatched(s, z, zs, u, v, stride, nrhs, alpha, out, batch);
-  BSP_CATCH
-}
-template <typename T>
-static std::vector<T*> hostArray(const char* what, const char* name, const T* const* p, int32_t batch) {
-  if (batch <= 0) throw std::runtime_error(std::string(what) + ": the batch is empty (batch = " + std::to_string(batch) + ")");
-  if (p == nullptr) throw std::runtime_error(std::string(what) + ": the array of " + name + " pointers is NULL");
-  std::vector<T*> v(batch);
-  for (int32_t q = 0; q < batch; q++) v[q] = const_cast<T*>(p[q]);
-  return v;
-}
-int bsp_pattern_outer_f64(bsp_solver* s, const double* u, const double* v, int64_t stride, int32_t nrhs,
-                          double alpha, double* out) {
-  BSP_TRY
-  s->solver->patternOuter(u, v, stride, nrhs, alpha, out);
-  BSP_CATCH
-}
-int bsp_pattern_outer_f32(bsp_solver* s, const float* u, const float* v, int64_t stride, int32_t nrhs,
-                          float alpha, float* out) {
-  BSP_TRY
-  s->solver->patternOuter(u, v, stride, nrhs, alpha, out);
-  BSP_CATCH
+  s->solver->patternGrad(opt("Z", z), zs, opt("U", u), opt("V", v), stride, nrhs, alpha, o);
 }
 template <typename T>
 static void patternOuterBatched(bsp_solver* s, const T* const* u, const T* const* v, int64_t stride, int32_t nrhs,
                                 T alpha, T* const* out, int32_t batch) {
   const char* what = "patternOuter";
-  const std::vector<T*> o = hostArray(what, "output", out, batch);
-  s->solver->patternOuter(hostArray(what, "U", u, batch), hostArray(what, "V", v, batch), stride, nrhs, alpha, o);
-}
-int bsp_pattern_outer_batched_f64(bsp_solver* s, const double* const* u, const double* const* v, int64_t stride,
-                                  int32_t nrhs, double alpha, double* const* out, int32_t batch) {
-  BSP_TRY
-  patternOuterBatched(s, u, v, stride, nrhs, alpha, out, batch);
-  BSP_CATCH
-}
-int bsp_pattern_outer_batched_f32(bsp_solver* s, const float* const* u, const float* const* v, int64_t stride,
-                                  int32_t nrhs, float alpha, float* const* out, int32_t batch) {
-  BSP_TRY
-  patternOuterBatched(s, u, v, stride, nrhs, alpha, out, batch);
-  BSP_CATCH
-}
-int bsp_factor_adjoint_f64(bsp_solver* s, const double* l, double* grad) {
-  BSP_TRY
-  s->solver->factorAdjoint(l, grad);
-  BSP_CATCH
-}
-int bsp_factor_adjoint_f32(bsp_solver* s, const float* l, float* grad) {
-  BSP_TRY
-  s->solver->factorAdjoint(l, grad);
-  BSP_CATCH
+  const std::vector<T*> o = hostArray<T*>(what, "output", out, batch);
+  s->solver->patternOuter(hostArray<T*>(what, "U", u, batch), hostArray<T*>(what, "V", v, batch), stride, nrhs, alpha,
+                          o);
 }
 template <typename T>
 static void factorAdjointBatched(bsp_solver* s, const T* const* l, T* const* grad, int32_t batch) {
   const char* what = "factorAdjoint";
-  const std::vector<T*> g = hostArray(what, "gradient", grad, batch);
-  s->solver->factorAdjoint(hostArray(what, "factor", l, batch), g);
-}
-int bsp_factor_adjoint_batched_f64(bsp_solver* s, const double* const* l, double* const* grad, int32_t batch) {
-  BSP_TRY
-  factorAdjointBatched(s, l, grad, batch);
-  BSP_CATCH
-}
-int bsp_factor_adjoint_batched_f32(bsp_solver* s, const float* const* l, float* const* grad, int32_t batch) {
-  BSP_TRY
-  factorAdjointBatched(s, l, grad, batch);
-  BSP_CATCH
+  const std::vector<T*> g = hostArray<T*>(what, "gradient", grad, batch);
+  s->solver->factorAdjoint(hostArray<T*>(what, "factor", l, batch), g);
 }
 template <typename T>
 static void factorAdjointUpToBatched(bsp_solver* s, const T* const* p, T* const* grad, int32_t batch, int64_t span) {
   const char* what = "factorAdjointUpTo";
-  const std::vector<T*> g = hostArray(what, "gradient", grad, batch);
-  s->solver->factorAdjointUpTo(hostArray(what, "factor", p, batch), g, span);
+  const std::vector<T*> g = hostArray<T*>(what, "gradient", grad, batch);
+  s->solver->factorAdjointUpTo(hostArray<T*>(what, "factor", p, batch), g, span);
 }
 template <typename T>
 static void schurDenseBatched(bsp_solver* s, const T* const* in, int64_t span, T* const* out, const int32_t* dest,
                               int32_t batch, bool toDense) {
   const char* what = toDense ? "schurComplement" : "schurComplementAdjoint";
-  const std::vector<T*> o = hostArray(what, "output", out, batch);
-  const std::vector<T*> i = hostArray(what, "input", in, batch);
+  const std::vector<T*> o = hostArray<T*>(what, "output", out, batch);
+  const std::vector<T*> i = hostArray<T*>(what, "input", in, batch);
   if (toDense) {
     s->solver->schurComplement(i, span, o, dest);
   } else {
     s->solver->schurComplementAdjoint(i, span, o, dest);
   }
 }
+#define BSP_PATTERN_API(SFX, T)                                                                                  \
+  int bsp_selected_inverse_##SFX(bsp_solver* s, T* d) BSP_BODY(s->solver->selectedInverse(d))                    \
+  int bsp_selected_inverse_batched_##SFX(bsp_solver* s, T* const* ptrs, int32_t batch)                           \
+      BSP_BODY(selectedInverseBatched(s, ptrs, batch))                                                           \
+  int bsp_log_det_##SFX(bsp_solver* s, const T* f, T* out) BSP_BODY(s->solver->logDet(f, out))                   \
+  int bsp_log_det_batched_##SFX(bsp_solver* s, const T* const* f, T* out, int32_t batch)                         \
+      BSP_BODY(logDetBatched(s, f, out, batch))                                                                  \
+  int bsp_pattern_grad_##SFX(bsp_solver* s, const T* z, const T* zs, const T* u, const T* v, int64_t stride,     \
+                             int32_t nrhs, T alpha, T* out)                                                      \
+      BSP_BODY(s->solver->patternGrad(z, zs, u, v, stride, nrhs, alpha, out))                                    \
+  int bsp_pattern_grad_batched_##SFX(bsp_solver* s, const T* const* z, const T* zs, const T* const* u,           \
+                                     const T* const* v, int64_t stride, int32_t nrhs, T alpha, T* const* out,    \
+                                     int32_t batch)                                                              \
+      BSP_BODY(patternGradBatched(s, z, zs, u, v, stride, nrhs, alpha, out, batch))                              \
+  int bsp_pattern_outer_##SFX(bsp_solver* s, const T* u, const T* v, int64_t stride, int32_t nrhs, T alpha,      \
+                              T* out) BSP_BODY(s->solver->patternOuter(u, v, stride, nrhs, alpha, out))          \
+  int bsp_pattern_outer_batched_##SFX(bsp_solver* s, const T* const* u, const T* const* v, int64_t stride,       \
+                                      int32_t nrhs, T alpha, T* const* out, int32_t batch)                       \
+      BSP_BODY(patternOuterBatched(s, u, v, stride, nrhs, alpha, out, batch))                                    \
+  int bsp_factor_adjoint_##SFX(bsp_solver* s, const T* l, T* grad) BSP_BODY(s->solver->factorAdjoint(l, grad))   \
+  int bsp_factor_adjoint_batched_##SFX(bsp_solver* s, const T* const* l, T* const* grad, int32_t batch)          \
+      BSP_BODY(factorAdjointBatched(s, l, grad, batch))
+BSP_PATTERN_API(f64, double)
+BSP_PATTERN_API(f32, float)
+#undef BSP_PATTERN_API
 #define BSP_PARTIAL_ADJOINT_API(SFX, T)                                                                          \
-  int bsp_factor_adjoint_up_to_##SFX(bsp_solver* s, const T* p, T* grad, int64_t span) {                         \
-    BSP_TRY                                                                                                      \
-    s->solver->factorAdjointUpTo(p, grad, span);                                                                 \
-    BSP_CATCH                                                                                                    \
-  }                                                                                                              \
+  int bsp_factor_adjoint_up_to_##SFX(bsp_solver* s, const T* p, T* grad, int64_t span)                           \
+      BSP_BODY(s->solver->factorAdjointUpTo(p, grad, span))                                                      \
   int bsp_factor_adjoint_up_to_batched_##SFX(bsp_solver* s, const T* const* p, T* const* grad, int32_t batch,    \
-                                             int64_t span) {                                                     \
-    BSP_TRY                                                                                                      \
-    factorAdjointUpToBatched(s, p, grad, batch, span);                                                           \
-    BSP_CATCH                                                                                                    \
-  }                                                                                                              \
-  int bsp_schur_to_dense_##SFX(bsp_solver* s, const T* p, int64_t span, T* out, const int32_t* dest) {           \
-    BSP_TRY                                                                                                      \
-    s->solver->schurComplement(p, span, out, dest);                                                              \
-    BSP_CATCH                                                                                                    \
-  }                                                                                                              \
+                                             int64_t span)                                                       \
+      BSP_BODY(factorAdjointUpToBatched(s, p, grad, batch, span))                                                \
+  int bsp_schur_to_dense_##SFX(bsp_solver* s, const T* p, int64_t span, T* out, const int32_t* dest)             \
+      BSP_BODY(s->solver->schurComplement(p, span, out, dest))                                                   \
   int bsp_schur_to_dense_batched_##SFX(bsp_solver* s, const T* const* p, int64_t span, T* const* out,            \
-                                       const int32_t* dest, int32_t batch) {                                     \
-    BSP_TRY                                                                                                      \
-    schurDenseBatched(s, p, span, out, dest, batch, true);                                                       \
-    BSP_CATCH                                                                                                    \
-  }                                                                                                              \
-  int bsp_schur_from_dense_##SFX(bsp_solver* s, const T* gd, int64_t span, T* grad, const int32_t* dest) {       \
-    BSP_TRY                                                                                                      \
-    s->solver->schurComplementAdjoint(gd, span, grad, dest);                                                     \
-    BSP_CATCH                                                                                                    \
-  }                                                                                                              \
+                                       const int32_t* dest, int32_t batch)                                       \
+      BSP_BODY(schurDenseBatched(s, p, span, out, dest, batch, true))                                            \
+  int bsp_schur_from_dense_##SFX(bsp_solver* s, const T* gd, int64_t span, T* grad, const int32_t* dest)         \
+      BSP_BODY(s->solver->schurComplementAdjoint(gd, span, grad, dest))                                          \
   int bsp_schur_from_dense_batched_##SFX(bsp_solver* s, const T* const* gd, int64_t span, T* const* grad,        \
-                                         const int32_t* dest, int32_t batch) {                                   \
-    BSP_TRY                                                                                                      \
-    schurDenseBatched(s, gd, span, grad, dest, batch, false);                                                    \
-    BSP_CATCH                                                                                                    \
-  }
+                                         const int32_t* dest, int32_t batch)                                     \
+      BSP_BODY(schurDenseBatched(s, gd, span, grad, dest, batch, false))
 BSP_PARTIAL_ADJOINT_API(f64, double)
 BSP_PARTIAL_ADJOINT_API(f32, float)
 #undef BSP_PARTIAL_ADJOINT_API
@@ -712,62 +615,26 @@ template <typename T>
 static void assembleBatched(bsp_solver* s, const bsp_assembly* a, const T* const* in, T* const* out,
                             int32_t batch, bool adjoint) {
   const char* what = adjoint ? "assembleAdjoint" : "assemble";
-  if (batch <= 0) {
-    throw std::runtime_error(std::string(what) + ": the batch is empty (batch = " + std::to_string(batch) + ")");
-  }
-  if (in == nullptr || out == nullptr) throw std::runtime_error(std::string(what) + ": an array of pointers is NULL");
-  const std::vector<const T*> i(in, in + batch);
-  const std::vector<T*> o(out, out + batch);
+  const std::vector<const T*> i = hostArray<const T*>(what, nullptr, in, batch);
+  const std::vector<T*> o = hostArray<T*>(what, nullptr, out, batch);
   if (adjoint) {
     s->solver->assembleAdjoint(assemblyOf(a), i, o);
   } else {
     s->solver->assemble(assemblyOf(a), i, o);
   }
 }
-int bsp_assemble_f64(bsp_solver* s, const bsp_assembly* a, const double* v, double* d) {
-  BSP_TRY
-  s->solver->assemble(assemblyOf(a), v, d);
-  BSP_CATCH
-}
-int bsp_assemble_f32(bsp_solver* s, const bsp_assembly* a, const float* v, float* d) {
-  BSP_TRY
-  s->solver->assemble(assemblyOf(a), v, d);
-  BSP_CATCH
-}
-int bsp_assemble_batched_f64(bsp_solver* s, const bsp_assembly* a, const double* const* v, double* const* d,
-                             int32_t batch) {
-  BSP_TRY
-  assembleBatched(s, a, v, d, batch, false);
-  BSP_CATCH
-}
-int bsp_assemble_batched_f32(bsp_solver* s, const bsp_assembly* a, const float* const* v, float* const* d,
-                             int32_t batch) {
-  BSP_TRY
-  assembleBatched(s, a, v, d, batch, false);
-  BSP_CATCH
-}
-int bsp_assemble_adjoint_f64(bsp_solver* s, const bsp_assembly* a, const double* g, double* gv) {
-  BSP_TRY
-  s->solver->assembleAdjoint(assemblyOf(a), g, gv);
-  BSP_CATCH
-}
-int bsp_assemble_adjoint_f32(bsp_solver* s, const bsp_assembly* a, const float* g, float* gv) {
-  BSP_TRY
-  s->solver->assembleAdjoint(assemblyOf(a), g, gv);
-  BSP_CATCH
-}
-int bsp_assemble_adjoint_batched_f64(bsp_solver* s, const bsp_assembly* a, const double* const* g,
-                                     double* const* gv, int32_t batch) {
-  BSP_TRY
-  assembleBatched(s, a, g, gv, batch, true);
-  BSP_CATCH
-}
-int bsp_assemble_adjoint_batched_f32(bsp_solver* s, const bsp_assembly* a, const float* const* g,
-                                     float* const* gv, int32_t batch) {
-  BSP_TRY
-  assembleBatched(s, a, g, gv, batch, true);
-  BSP_CATCH
-}
+#define BSP_ASSEMBLY_API(SFX, T)                                                                                 \
+  int bsp_assemble_##SFX(bsp_solver* s, const bsp_assembly* a, const T* v, T* d)                                 \
+      BSP_BODY(s->solver->assemble(assemblyOf(a), v, d))                                                         \
+  int bsp_assemble_batched_##SFX(bsp_solver* s, const bsp_assembly* a, const T* const* v, T* const* d,           \
+                                 int32_t batch) BSP_BODY(assembleBatched(s, a, v, d, batch, false))              \
+  int bsp_assemble_adjoint_##SFX(bsp_solver* s, const bsp_assembly* a, const T* g, T* gv)                        \
+      BSP_BODY(s->solver->assembleAdjoint(assemblyOf(a), g, gv))                                                 \
+  int bsp_assemble_adjoint_batched_##SFX(bsp_solver* s, const bsp_assembly* a, const T* const* g, T* const* gv,  \
+                                         int32_t batch) BSP_BODY(assembleBatched(s, a, g, gv, batch, true))
+BSP_ASSEMBLY_API(f64, double)
+BSP_ASSEMBLY_API(f32, float)
+#undef BSP_ASSEMBLY_API
 struct bsp_normal_eq {
   std::unique_ptr<NormalEqMap> map;
 };
@@ -813,63 +680,33 @@ static void normalEqRun(bsp_solver* s, const bsp_normal_eq* e, int32_t op, const
   const std::string what = names[op];
   if (s == nullptr) throw std::runtime_error(what + ": the solver is NULL");
   if (e == nullptr) throw std::runtime_error(what + ": the map is NULL");
-  if (batch <= 0) throw std::runtime_error(what + ": the batch is empty (batch = " + std::to_string(batch) + ")");
   const bool hasX = op != NormalEqHessian;
-  if (values == nullptr || out == nullptr || (hasX && x == nullptr)) {
-    throw std::runtime_error(what + ": an array of pointers is NULL");
-  }
-  const std::vector<const T*> v(values, values + batch);
-  const std::vector<const T*> xs(hasX ? x : values, hasX ? x + batch : values);
-  const std::vector<T*> o(out, out + batch);
+  const std::vector<const T*> v = hostArray<const T*>(what, nullptr, values, batch);
+  const std::vector<T*> o = hostArray<T*>(what, nullptr, out, batch);
+  const std::vector<const T*> xs = hasX ? hostArray<const T*>(what, nullptr, x, batch) : std::vector<const T*>{};
   s->solver->normalEq<T>(*e->map, op, v, xs, o, q, single);
 }
 #define BSP_NORMAL_EQ_API(SFX, T)                                                                                \
-  int bsp_normal_eq_hessian_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* v, T* d) {                      \
-    BSP_TRY                                                                                                      \
-    normalEqRun<T>(s, e, NormalEqHessian, &v, nullptr, &d, 0, 1, true);                                          \
-    BSP_CATCH                                                                                                    \
-  }                                                                                                              \
+  int bsp_normal_eq_hessian_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* v, T* d)                       \
+      BSP_BODY(normalEqRun<T>(s, e, NormalEqHessian, &v, nullptr, &d, 0, 1, true))                               \
   int bsp_normal_eq_hessian_batched_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* const* v, T* const* d, \
-                                          int32_t batch) {                                                       \
-    BSP_TRY                                                                                                      \
-    normalEqRun<T>(s, e, NormalEqHessian, v, nullptr, d, 0, batch, false);                                       \
-    BSP_CATCH                                                                                                    \
-  }                                                                                                              \
-  int bsp_normal_eq_hessian_adjoint_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* v, const T* g, T* gv) { \
-    BSP_TRY                                                                                                      \
-    normalEqRun<T>(s, e, NormalEqAdjoint, &v, &g, &gv, 0, 1, true);                                              \
-    BSP_CATCH                                                                                                    \
-  }                                                                                                              \
+                                          int32_t batch)                                                         \
+      BSP_BODY(normalEqRun<T>(s, e, NormalEqHessian, v, nullptr, d, 0, batch, false))                            \
+  int bsp_normal_eq_hessian_adjoint_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* v, const T* g, T* gv)  \
+      BSP_BODY(normalEqRun<T>(s, e, NormalEqAdjoint, &v, &g, &gv, 0, 1, true))                                   \
   int bsp_normal_eq_hessian_adjoint_batched_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* const* v,      \
-                                                  const T* const* g, T* const* gv, int32_t batch) {              \
-    BSP_TRY                                                                                                      \
-    normalEqRun<T>(s, e, NormalEqAdjoint, v, g, gv, 0, batch, false);                                            \
-    BSP_CATCH                                                                                                    \
-  }                                                                                                              \
+                                                  const T* const* g, T* const* gv, int32_t batch)                \
+      BSP_BODY(normalEqRun<T>(s, e, NormalEqAdjoint, v, g, gv, 0, batch, false))                                 \
   int bsp_normal_eq_jt_vec_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* v, const T* r, int64_t q,       \
-                                 T* out) {                                                                       \
-    BSP_TRY                                                                                                      \
-    normalEqRun<T>(s, e, NormalEqJtVec, &v, &r, &out, q, 1, true);                                               \
-    BSP_CATCH                                                                                                    \
-  }                                                                                                              \
+                                 T* out) BSP_BODY(normalEqRun<T>(s, e, NormalEqJtVec, &v, &r, &out, q, 1, true)) \
   int bsp_normal_eq_jt_vec_batched_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* const* v,               \
-                                         const T* const* r, int64_t q, T* const* out, int32_t batch) {           \
-    BSP_TRY                                                                                                      \
-    normalEqRun<T>(s, e, NormalEqJtVec, v, r, out, q, batch, false);                                             \
-    BSP_CATCH                                                                                                    \
-  }                                                                                                              \
+                                         const T* const* r, int64_t q, T* const* out, int32_t batch)             \
+      BSP_BODY(normalEqRun<T>(s, e, NormalEqJtVec, v, r, out, q, batch, false))                                  \
   int bsp_normal_eq_j_vec_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* v, const T* x, int64_t q,        \
-                                T* out) {                                                                        \
-    BSP_TRY                                                                                                      \
-    normalEqRun<T>(s, e, NormalEqJVec, &v, &x, &out, q, 1, true);                                                \
-    BSP_CATCH                                                                                                    \
-  }                                                                                                              \
+                                T* out) BSP_BODY(normalEqRun<T>(s, e, NormalEqJVec, &v, &x, &out, q, 1, true))   \
   int bsp_normal_eq_j_vec_batched_##SFX(bsp_solver* s, const bsp_normal_eq* e, const T* const* v,                \
-                                        const T* const* x, int64_t q, T* const* out, int32_t batch) {            \
-    BSP_TRY                                                                                                      \
-    normalEqRun<T>(s, e, NormalEqJVec, v, x, out, q, batch, false);                                              \
-    BSP_CATCH                                                                                                    \
-  }
+                                        const T* const* x, int64_t q, T* const* out, int32_t batch)              \
+      BSP_BODY(normalEqRun<T>(s, e, NormalEqJVec, v, x, out, q, batch, false))
 BSP_NORMAL_EQ_API(f64, double)
 BSP_NORMAL_EQ_API(f32, float)
 #undef BSP_NORMAL_EQ_API

@@ -93,27 +93,28 @@ int hipBackendReadSweepTrace(SymbolicCtx& sym, long long* out, int maxBlocks);
 // panel, trsm tasks, update tiles, lookahead tiles, rows below summed over the panels}
 std::vector<int64_t> hipBackendPlanLevels(SymbolicCtx& sym, int64_t startLump, int64_t upToLump);
 
-// Selected inversion: `data` holds a complete factor of this context's skeleton; Z = A^-1 on the
-// pattern of L overwrites it (hip_selinv_kernels.h), on the execution stream
+// ---- extension operations, on the execution stream --------------------------------------------------
+// One shape for all of them: every pointer argument is a HOST array of `batch` device pointers, one per
+// member.  single = true: one member (batch = 1), element 0 of each array handed to the kernels
+// directly; else the arrays travel to the device through the context's pointer ring and the batch runs
+// in chunks of at most 65535 members (gridDim.y), one after the other.  Arguments are checked by the
+// caller (solver.cpp), before any device work.
+//
+// Selected inversion (hip_selinv_kernels.h): data[q] holds a complete factor of this context's skeleton
+// and is overwritten by Z = A^-1 on the pattern of L.  Chunks are bounded by device memory as well.
 template <typename T>
-void hipBackendSelectedInverse(SymbolicCtx& sym, T* data);
-// ... of a batch of factors (distinct device pointers), in memory-bounded chunks of matrices
-template <typename T>
-void hipBackendSelectedInverse(SymbolicCtx& sym, const std::vector<T*>& data);
-// TESTING: at most `maxMatrices` matrices per chunk of a batched selected inversion (0: no cap)
+void hipBackendSelectedInverse(SymbolicCtx& sym, T* const* data, int64_t batch, bool single);
+// TESTING: at most `maxMatrices` matrices per chunk of a pass over the selected-inversion levels (0: no cap)
 void hipBackendSetSelInvBatchChunk(SymbolicCtx& sym, int64_t maxMatrices);
 
-// Gradients on the pattern of L (hip_grad_kernels.h), on the execution stream.
-// logDet: out[q] = 2 sum_i log L_ii of the complete factor factors[q], q < batch (out: device array).
-// single = true: one matrix, factors[0] used directly (no pointer array on the device).
+// Gradients on the pattern of L (hip_grad_kernels.h).
+// logDet: out[q] = 2 sum_i log L_ii of the complete factor factors[q] (out: device array of `batch`).
 template <typename T>
 void hipBackendLogDet(SymbolicCtx& sym, const T* const* factors, int64_t batch, bool single, T* out);
-// patternGrad of `batch` matrices: z / u / v / out are host arrays of device pointers (z NULL: no Z term,
-// zScale then unused; u and v NULL: no rank-2k term).  zScale: device array of `batch` scales.
+// patternGrad: z NULL: no Z term, zScale then unused; u and v NULL: no rank-2k term.  zScale: device
+// array of `batch` scales.
 template <typename T>
 struct HipGradArgs {
-  int64_t batch = 1;
-  bool single = true;
   const T* const* z = nullptr;
   const T* zScale = nullptr;
   const T* const* u = nullptr;
@@ -125,16 +126,12 @@ struct HipGradArgs {
   bool outer = false;  // patternOuter: out_e = alpha sum_k U_ik V_jk for i >= j (z unused)
 };
 template <typename T>
-void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a);
-// Reverse-mode sweep of the factor (hip_chol_adjoint_kernels.h): grad[q] holds
-// Lbar of the complete factor L[q] and is overwritten by the data gradient; L is only read.  Host
-// arrays of `batch` device pointers (single = true: one matrix, L[0] / grad[0] used directly); the
-// batch runs in memory-bounded chunks, as selected inversion does.
-template <typename T>
-void hipBackendFactorAdjoint(SymbolicCtx& sym, const T* const* L, T* const* grad, int64_t batch, bool single);
-// ... of a partial factor: P[q] holds the factor of the lumps < upToLump with the
-// Schur complement behind them; grad[q] holds Lbar before the cut and Sbar behind it.  The plan of the
-// cut is built on first use and cached; upToLump = numLumps is hipBackendFactorAdjoint.
+void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a, int64_t batch, bool single);
+// Reverse-mode sweep of the factor (hip_chol_adjoint_kernels.h; DESIGN.md sections 15 and 16): P[q] holds
+// the factor of the lumps < upToLump with the Schur complement behind them and is only read; grad[q]
+// holds Lbar before the cut and Sbar behind it and is overwritten by the data gradient.  upToLump =
+// numLumps: the sweep of a complete factor.  The plan of a cut is built on first use and cached; chunks
+// are bounded by device memory, as in selected inversion.
 template <typename T>
 void hipBackendFactorAdjointUpTo(SymbolicCtx& sym, const T* const* P, T* const* grad, int64_t batch, bool single,
                                  int64_t upToLump);
@@ -146,9 +143,8 @@ template <typename T>
 void hipBackendSchurDense(SymbolicCtx& sym, const T* const* in, T* const* out, int64_t batch, bool single,
                           int64_t fromLump, const int32_t* dest, bool toDense);
 
-// Assembly of coordinate entries into the layout (hip_assembly_kernels.h), on
-// the execution stream.  `in` / `out` are host arrays of `batch` device pointers (single = true: one
-// matrix, in[0] / out[0] used directly).  The map is uploaded on the first call and kept in map.dev.
+// Assembly of coordinate entries into the layout (hip_assembly_kernels.h).  The
+// map is uploaded on the first call and kept in map.dev.
 // assemble: in = values (nnz each), out = data (dataSize each); adjoint: in = gradients of the data,
 // out = gradients of the values.
 struct AssemblyMap;
@@ -158,9 +154,8 @@ void hipBackendAssemble(SymbolicCtx& sym, const AssemblyMap& map, const T* const
                         int64_t batch, bool single, bool adjoint);
 void hipBackendFreeAssembly(HipAssemblyDev* dev);
 
-// Normal equations of a sparse Jacobian (hip_normal_eq_kernels.h), on the
-// execution stream.  Host arrays of `batch` device pointers as for hipBackendAssemble.  Each part of the
-// map is uploaded on the first call that needs it and kept in map.dev.
+// Normal equations of a sparse Jacobian (hip_normal_eq_kernels.h).  Each part of
+// the map is uploaded on the first call that needs it and kept in map.dev.
 //   NormalEqHessian:  out = data (dataSize each) from values;  x unused
 //   NormalEqAdjoint:  out = gradients of the values from values and x = gradients of the data
 //   NormalEqJtVec:    out = J^T x ([n, q] each) from values and x ([m, q]);  NormalEqJVec: out = J x

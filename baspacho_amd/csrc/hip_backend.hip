@@ -388,6 +388,23 @@ struct PtrRing {
   }
 };
 
+// One pointer argument of an extension operation (hip_backend.h): `host` holds one device pointer per
+// batch member.  A batch stages the array through the ring, once; a single call hands host[0] to the
+// kernels directly.  at(q0): the members from q0 on.  A NULL array (an optional argument that was not
+// given) stays the null DataRef.
+template <typename T>
+struct BatchPtrs {
+  T* const* host = nullptr;
+  T* const* dev = nullptr;
+  BatchPtrs(PtrRing& ring, hipStream_t stream, T* const* host_, int64_t batch, bool single) : host(host_) {
+    if (host && !single) dev = (T* const*)ring.push(host, batch * sizeof(T*), stream);
+  }
+  hipk::DataRef<T> at(int64_t q0) const {
+    if (!host) return {nullptr, nullptr};
+    return dev ? hipk::DataRef<T>{nullptr, dev + q0} : hipk::DataRef<T>{host[0], nullptr};
+  }
+};
+
 struct HipSymElimCtx : SymElimCtx {
   int64_t lumpsBegin = 0, lumpsEnd = 0;
 };
@@ -638,6 +655,21 @@ struct SelInvDev {
   }
   int64_t slices() const { return scratch->slicesFor(host); }
   void reserve(int64_t n) { scratch->reserve(host, n); }
+  // what a pass over the levels hands to its kernels: the scratch as T, the plan tables, the strides
+  template <typename T>
+  struct View {
+    T *linv, *dd, *U, *P, *Wp;
+    const SelInvNode* nodes;
+    const int2* tiles;
+    const int4* zTasks;
+    hipk::SelInvStrides st;
+  };
+  template <typename T>
+  View<T> view() const {
+    const auto as = [](const DevBuf& b) { return reinterpret_cast<T*>(b.ptr); };
+    return {as(scratch->linv), as(scratch->dd), as(scratch->U), as(scratch->P), as(scratch->Wp),
+            nodes.as<SelInvNode>(), tiles.as<int2>(), zTasks.as<int4>(), strides()};
+  }
   void upload(SelInvScratch* sc) {
     scratch = sc;
     smalls.upload(host.smalls);
@@ -863,40 +895,38 @@ struct HipSymbolicCtx : SymbolicCtx {
     return SymElimCtxPtr(e);
   }
 
-  // Selected inversion of a complete factor, in place (hip_selinv_kernels.h).  The plan is built and
-  // uploaded on the first call; every launch goes to the execution stream, in level order, with no
-  // host synchronisation.
+  // ---- the call path of the extension operations (hip_backend.h) -----------------------------------
+  // Every argument is a host array of one device pointer per batch member (BatchPtrs), staged in the
+  // order the operation names them; the batch then runs in chunks of at most `chunk` members, one
+  // after the other on the execution stream, a chunk being launches with gridDim.y = its members.
   template <typename T>
-  void selectedInverse(T* data) {
-    checkDevice();
-    SelInvDev& d = selInvPlan();
-    d.reserve(1);
-    selInvLevels<T>(d, {data, nullptr}, 1);
+  BatchPtrs<T> stage(T* const* host, int64_t batch, bool single) {
+    return BatchPtrs<T>(ptrRing, stream, host, batch, single);
+  }
+  // run(q0, nm) enqueues the members q0 .. q0 + nm - 1
+  template <typename F>
+  void forChunks(int64_t batch, int64_t chunk, F&& run) {
+    for (int64_t q0 = 0; q0 < batch; q0 += chunk) run(q0, (unsigned)std::min(chunk, batch - q0));
     hipCHECK(hipGetLastError());
   }
+  // most members of one launch (gridDim.y)
+  static constexpr int64_t kMaxGridY = 65535;
 
-  // A batch of factors of this skeleton: the pointer array goes through the PtrRing, and the batch runs
-  // in chunks of `chunk` matrices, one after the other on the execution stream.  A chunk is one pass
-  // over the levels with gridDim.y = its matrices, each in its own scratch slice.  Chunk size:
-  // min(batch, 65535 (gridDim.y), what half the free device memory holds in slices -- slices the
-  // solver already holds count as free), at least 1, at most the testing cap.  The scratch grows to the
-  // chunk and stays with the solver.
+  // Selected inversion of `batch` complete factors, in place (hip_selinv_kernels.h).  The plan is built
+  // and uploaded on the first call; every launch goes to the execution stream, in level order, with no
+  // host synchronisation.  A chunk is one pass over the levels, each matrix in its own scratch slice;
+  // the scratch grows to the chunk (selInvChunk) and stays with the solver.
   template <typename T>
-  void selectedInverse(const vector<T*>& data) {
+  void selectedInverse(T* const* data, int64_t batch, bool single) {
     checkDevice();
     SelInvDev& d = selInvPlan();
-    const int64_t batch = (int64_t)data.size();
     const int64_t chunk = selInvChunk(d, batch);
-    T* const* many = (T* const*)ptrRing.push(data.data(), data.size() * sizeof(T*), stream);
-    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
-      selInvLevels<T>(d, {nullptr, many + q0}, (unsigned)std::min(chunk, batch - q0));
-    }
-    hipCHECK(hipGetLastError());
+    const BatchPtrs<T> z = stage(data, batch, single);
+    forChunks(batch, chunk, [&](int64_t q0, unsigned nm) { selInvLevels<T>(d, z.at(q0), nm); });
   }
 
-  // ---- gradients on the pattern of L (hip_grad_kernels.h, DESIGN.md section 13) -------------------
   // ---- assembly of coordinate entries (hip_assembly_kernels.h) ---------------
-  // assemble (or its adjoint) of `batch` matrices: one launch per chunk of at most 65535 matrices
+  // assemble (or its adjoint) of `batch` matrices: one launch per chunk
   template <typename T>
   void assemble(const AssemblyMap& m, const T* const* in, T* const* out, int64_t batch, bool single,
                 bool adjoint) {
@@ -908,30 +938,23 @@ struct HipSymbolicCtx : SymbolicCtx {
     }
     const HipAssemblyDev& d = *m.dev;
     if (adjoint && m.nnz == 0) return;
-    const int64_t chunk = std::min<int64_t>(batch, 65535);
-    const size_t bytes = batch * sizeof(T*);
-    const T* const* inMany = single ? nullptr : (const T* const*)ptrRing.push(in, bytes, stream);
-    T* const* outMany = single ? nullptr : (T* const*)ptrRing.push(out, bytes, stream);
-    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
-      const unsigned nm = (unsigned)std::min(chunk, batch - q0);
-      const hipk::DataRef<const T> iref =
-          single ? hipk::DataRef<const T>{in[0], nullptr} : hipk::DataRef<const T>{nullptr, inMany + q0};
-      const hipk::DataRef<T> oref = single ? hipk::DataRef<T>{out[0], nullptr} : hipk::DataRef<T>{nullptr, outMany + q0};
+    const BatchPtrs<const T> i = stage(in, batch, single);
+    const BatchPtrs<T> o = stage(out, batch, single);
+    forChunks(batch, kMaxGridY, [&](int64_t q0, unsigned nm) {
       if (adjoint) {
         const int64_t per = hipk::kAsmThreads * hipk::kAsmAdjPer;
         hipk::assembleAdjointEntries<T><<<dim3((unsigned)((m.nnz + per - 1) / per), nm), hipk::kAsmThreads, 0,
-                                           stream>>>(m.nnz, d.entryOff.as<int64_t>(), iref, oref);
+                                           stream>>>(m.nnz, d.entryOff.as<int64_t>(), i.at(q0), o.at(q0));
       } else {
         hipk::assembleTiles<T><<<dim3((unsigned)m.numTiles, nm), hipk::kAsmThreads, 0, stream>>>(
             m.dataSize, d.tileFirst.as<int32_t>(), d.tileLongFirst.as<int32_t>(), d.runStart.as<int32_t>(),
-            d.runEntry.as<int32_t>(), d.destLocal.as<uint16_t>(), d.longDest.as<int32_t>(), iref, oref);
+            d.runEntry.as<int32_t>(), d.destLocal.as<uint16_t>(), d.longDest.as<int32_t>(), i.at(q0), o.at(q0));
       }
-    }
-    hipCHECK(hipGetLastError());
+    });
   }
 
   // ---- normal equations of a sparse Jacobian (hip_normal_eq_kernels.h) --------
-  // one of the four operations on `batch` members: one launch per chunk of at most 65535 members
+  // one of the four operations on `batch` members: one launch per chunk
   template <typename T>
   void normalEq(const NormalEqMap& m, int32_t op, const T* const* values, const T* const* x, T* const* out,
                 int64_t q, int64_t batch, bool single) {
@@ -946,42 +969,32 @@ struct HipSymbolicCtx : SymbolicCtx {
     if (op == NormalEqAdjoint && m.nnz == 0) return;
     if (op == NormalEqHessian && m.numTiles == 0) return;
     if ((op == NormalEqJtVec || op == NormalEqJVec) && numRuns * q == 0) return;
-    const int64_t chunk = std::min<int64_t>(batch, 65535);
-    const size_t bytes = batch * sizeof(T*);
-    const T* const* vMany = single ? nullptr : (const T* const*)ptrRing.push(values, bytes, stream);
-    const T* const* xMany = single || x == nullptr ? nullptr : (const T* const*)ptrRing.push(x, bytes, stream);
-    T* const* oMany = single ? nullptr : (T* const*)ptrRing.push(out, bytes, stream);
+    const BatchPtrs<const T> v = stage(values, batch, single), xs = stage(x, batch, single);
+    const BatchPtrs<T> o = stage(out, batch, single);
     const int64_t shortWgs = (m.nnz + hipk::kAsmThreads - 1) / hipk::kAsmThreads;
     const int64_t numLong = (int64_t)m.adjLong.size();
     const int64_t longWgs = (numLong + hipk::kNeqWavesPerWg - 1) / hipk::kNeqWavesPerWg;
-    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
-      const unsigned nm = (unsigned)std::min(chunk, batch - q0);
-      const hipk::DataRef<const T> vref =
-          single ? hipk::DataRef<const T>{values[0], nullptr} : hipk::DataRef<const T>{nullptr, vMany + q0};
-      const hipk::DataRef<const T> xref = x == nullptr ? hipk::DataRef<const T>{nullptr, nullptr}
-                                          : single     ? hipk::DataRef<const T>{x[0], nullptr}
-                                                       : hipk::DataRef<const T>{nullptr, xMany + q0};
-      const hipk::DataRef<T> oref = single ? hipk::DataRef<T>{out[0], nullptr} : hipk::DataRef<T>{nullptr, oMany + q0};
+    forChunks(batch, kMaxGridY, [&](int64_t q0, unsigned nm) {
       if (op == NormalEqHessian) {
         hipk::normalEqTiles<T><<<dim3((unsigned)m.numTiles, nm), hipk::kAsmThreads, 0, stream>>>(
             m.dataSize, d.tileFirst.as<int32_t>(), d.tileLongFirst.as<int32_t>(), d.runStart.as<int32_t>(),
-            d.pairA.as<int32_t>(), d.pairB.as<int32_t>(), d.destLocal.as<uint16_t>(), d.longDest.as<int32_t>(), vref,
-            oref);
+            d.pairA.as<int32_t>(), d.pairB.as<int32_t>(), d.destLocal.as<uint16_t>(), d.longDest.as<int32_t>(),
+            v.at(q0), o.at(q0));
       } else if (op == NormalEqAdjoint) {
         hipk::normalEqAdjointEntries<T><<<dim3((unsigned)(shortWgs + longWgs), nm), hipk::kAsmThreads, 0, stream>>>(
             m.nnz, (int32_t)shortWgs, (int32_t)numLong, d.adjStart.as<int64_t>(), d.adjPartner.as<int32_t>(),
-            d.adjDest.as<int64_t>(), d.adjLong.as<int32_t>(), vref, xref, oref);
+            d.adjDest.as<int64_t>(), d.adjLong.as<int32_t>(), v.at(q0), xs.at(q0), o.at(q0));
       } else {
         const int64_t wgs = (numRuns * q + hipk::kAsmThreads - 1) / hipk::kAsmThreads;
         hipk::runDotVec<T><<<dim3((unsigned)wgs, nm), hipk::kAsmThreads, 0, stream>>>(
             numRuns, (int32_t)q, (jt ? d.colStart : d.rowStart).template as<int32_t>(),
             (jt ? d.colEntry : d.rowEntry).template as<int32_t>(), (jt ? d.colIdx : d.rowIdx).template as<int32_t>(),
-            vref, xref, oref);
+            v.at(q0), xs.at(q0), o.at(q0));
       }
-    }
-    hipCHECK(hipGetLastError());
+    });
   }
 
+  // ---- gradients on the pattern of L (hip_grad_kernels.h, DESIGN.md section 13) -------------------
   GradDev& gradPlan() {
     if (!grad) {
       std::unique_ptr<GradDev> p(new GradDev);
@@ -991,134 +1004,85 @@ struct HipSymbolicCtx : SymbolicCtx {
     return *grad;
   }
 
-  // logDet of `batch` factors: two launches per chunk of at most 65535 matrices (gridDim.y), the
-  // partial sums of a chunk in GradDev::part
+  // logDet of `batch` factors: two launches per chunk, the partial sums of a chunk in GradDev::part
   template <typename T>
   void logDet(const T* const* factors, int64_t batch, bool single, T* out) {
     checkDevice();
     GradDev& g = gradPlan();
     const hipk::SkelDev sk = skelDev();
-    const int64_t chunk = std::min<int64_t>(batch, 65535);
+    const int64_t chunk = std::min(batch, kMaxGridY);
     g.reservePart(chunk);
-    const T* const* many =
-        single ? nullptr : (const T* const*)ptrRing.push(factors, batch * sizeof(T*), stream);
+    const BatchPtrs<const T> f = stage(factors, batch, single);
     double* part = reinterpret_cast<double*>(g.part.ptr);
-    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
-      const unsigned nm = (unsigned)std::min(chunk, batch - q0);
-      const hipk::DataRef<const T> ref{single ? factors[0] : nullptr, single ? nullptr : many + q0};
+    forChunks(batch, chunk, [&](int64_t q0, unsigned nm) {
       if (g.nParts > 0) {
         hipk::logDetPartial<T><<<dim3((unsigned)g.nParts, nm), 256, 0, stream>>>(
-            sk, g.firstLump.as<int32_t>(), skel.order(), (int)g.nParts, ref, part);
+            sk, g.firstLump.as<int32_t>(), skel.order(), (int)g.nParts, f.at(q0), part);
       }
       hipk::logDetFinal<T><<<dim3(1, nm), 256, 0, stream>>>(part, (int)g.nParts, out + q0);
-    }
-    hipCHECK(hipGetLastError());
+    });
   }
 
-  // patternGrad of a.batch matrices: one launch of every tile per chunk of at most 65535 matrices
+  // patternGrad of a.batch matrices: one launch of every tile per chunk
   template <typename T>
-  void patternGrad(const HipGradArgs<T>& a) {
+  void patternGrad(const HipGradArgs<T>& a, int64_t batch, bool single) {
     checkDevice();
     GradDev& g = gradPlan();
     const hipk::SkelDev sk = skelDev();
     if (g.nTiles == 0) return;
-    const int64_t batch = a.batch, chunk = std::min<int64_t>(batch, 65535);
     const bool hasZ = a.z != nullptr, hasUV = a.u != nullptr;
-    const size_t bytes = batch * sizeof(T*);
-    const T* const* zMany = (hasZ && !a.single) ? (const T* const*)ptrRing.push(a.z, bytes, stream) : nullptr;
-    const T* const* uMany = (hasUV && !a.single) ? (const T* const*)ptrRing.push(a.u, bytes, stream) : nullptr;
-    const T* const* vMany = (hasUV && !a.single) ? (const T* const*)ptrRing.push(a.v, bytes, stream) : nullptr;
-    T* const* oMany = a.single ? nullptr : (T* const*)ptrRing.push(a.out, bytes, stream);
+    const BatchPtrs<const T> z = stage(a.z, batch, single);
+    const BatchPtrs<const T> u = stage(a.u, batch, single), v = stage(hasUV ? a.v : nullptr, batch, single);
+    const BatchPtrs<T> o = stage(a.out, batch, single);
     const int k = hasUV ? a.nRHS : 0;
     const int kc = std::min(k, hipk::kGradK);
     const size_t lds = k > 0 ? (size_t)(hipk::kGradRows + hipk::kGradCols) * (kc + 1) * 2 * sizeof(T) : 0;
-    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
-      const unsigned nm = (unsigned)std::min(chunk, batch - q0);
-      const auto ref = [&](const T* const* host, const T* const* dev) {
-        if (host == nullptr) return hipk::DataRef<const T>{nullptr, nullptr};
-        return a.single ? hipk::DataRef<const T>{host[0], nullptr} : hipk::DataRef<const T>{nullptr, dev + q0};
-      };
-      const hipk::DataRef<T> oref =
-          a.single ? hipk::DataRef<T>{a.out[0], nullptr} : hipk::DataRef<T>{nullptr, oMany + q0};
+    forChunks(batch, kMaxGridY, [&](int64_t q0, unsigned nm) {
       if (a.outer) {
         hipk::patternGradTiles<T, true><<<dim3((unsigned)g.nTiles, nm), 256, lds, stream>>>(
-            g.tiles.as<hipk::GradTile>(), sk, hipk::DataRef<const T>{nullptr, nullptr}, nullptr,
-            ref(a.u, uMany), ref(a.v, vMany), a.ld, k, a.alpha, oref);
-        continue;
+            g.tiles.as<hipk::GradTile>(), sk, hipk::DataRef<const T>{nullptr, nullptr}, nullptr, u.at(q0), v.at(q0),
+            a.ld, k, a.alpha, o.at(q0));
+      } else {
+        hipk::patternGradTiles<T><<<dim3((unsigned)g.nTiles, nm), 256, lds, stream>>>(
+            g.tiles.as<hipk::GradTile>(), sk, z.at(q0), hasZ ? a.zScale + q0 : nullptr, u.at(q0), v.at(q0), a.ld, k,
+            a.alpha, o.at(q0));
       }
-      hipk::patternGradTiles<T><<<dim3((unsigned)g.nTiles, nm), 256, lds, stream>>>(
-          g.tiles.as<hipk::GradTile>(), sk, ref(a.z, zMany), hasZ ? a.zScale + q0 : nullptr,
-          ref(a.u, uMany), ref(a.v, vMany), a.ld, k, a.alpha, oref);
-    }
-    hipCHECK(hipGetLastError());
+    });
   }
 
-  // ---- reverse-mode sweep of the factor (hip_chol_adjoint_kernels.h) --------
-  // `batch` factors L[q] (read only) and gradients grad[q] (Lbar in, data gradient out), on the
-  // selected-inversion plan and scratch.  Chunks as in selectedInverse(vector): at most 65535 matrices
-  // (gridDim.y) and what half the free device memory holds in scratch slices, at least 1.
-  template <typename T>
-  void factorAdjoint(const T* const* L, T* const* G, int64_t batch, bool single) {
-    checkDevice();
-    SelInvDev& d = selInvPlan();
-    GradDev& g = gradPlan();
-    const int64_t chunk = selInvChunk(d, batch);
-    const size_t bytes = batch * sizeof(T*);
-    const T* const* lMany = single ? nullptr : (const T* const*)ptrRing.push(L, bytes, stream);
-    T* const* gMany = single ? nullptr : (T* const*)ptrRing.push(G, bytes, stream);
-    const hipk::SkelDev sk = skelDev();
-    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
-      const unsigned nm = (unsigned)std::min(chunk, batch - q0);
-      const hipk::DataRef<const T> lref = single ? hipk::DataRef<const T>{L[0], nullptr}
-                                                 : hipk::DataRef<const T>{nullptr, lMany + q0};
-      const hipk::DataRef<T> gref = single ? hipk::DataRef<T>{G[0], nullptr} : hipk::DataRef<T>{nullptr, gMany + q0};
-      cholAdjLevels<T>(d, lref, gref, nm);
-      if (g.nTiles > 0) {
-        hipk::cholAdjFinal<T><<<dim3((unsigned)g.nTiles, nm), 256, 0, stream>>>(g.tiles.as<hipk::GradTile>(), sk,
-                                                                               gref);
-      }
-    }
-    hipCHECK(hipGetLastError());
-  }
-
-  // ---- reverse-mode sweep of a partial factor ------------------------------
+  // ---- reverse-mode sweep of the factor (DESIGN.md sections 15 and 16) -----------------------------
   // P[q] = factorUpTo of the lumps < upToLump (read only); grad[q]: Lbar before the cut and Sbar behind
-  // it on entry, the data gradient on return.  Seed the trailing lumps, run the plan of the cut, and
-  // the final pass over every tile.  upToLump = numLumps is factorAdjoint, launch for launch.
+  // it on entry, the data gradient on return.  Per chunk: seed the trailing lumps, run the plan of the
+  // cut on the selected-inversion scratch (chunks as selectedInverse), then the final pass over every
+  // tile.  upToLump = numLumps is the sweep of the complete factor: the complete plan, nothing to seed.
   template <typename T>
   void factorAdjointUpTo(const T* const* L, T* const* G, int64_t batch, bool single, int64_t upToLump) {
-    if (upToLump == skel.numLumps()) return factorAdjoint<T>(L, G, batch, single);
     checkDevice();
     SelInvDev& d = selInvPlanUpTo(upToLump);
     GradDev& g = gradPlan();
     const int64_t chunk = selInvChunk(d, batch);
-    const size_t bytes = batch * sizeof(T*);
-    const T* const* lMany = single ? nullptr : (const T* const*)ptrRing.push(L, bytes, stream);
-    T* const* gMany = single ? nullptr : (T* const*)ptrRing.push(G, bytes, stream);
+    const BatchPtrs<const T> l = stage(L, batch, single);
+    const BatchPtrs<T> gr = stage(G, batch, single);
     const hipk::SkelDev sk = skelDev();
     const int64_t seed0 = g.lumpFirstTile[upToLump], nSeed = g.nTiles - seed0;
-    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
-      const unsigned nm = (unsigned)std::min(chunk, batch - q0);
-      const hipk::DataRef<const T> lref = single ? hipk::DataRef<const T>{L[0], nullptr}
-                                                 : hipk::DataRef<const T>{nullptr, lMany + q0};
-      const hipk::DataRef<T> gref = single ? hipk::DataRef<T>{G[0], nullptr} : hipk::DataRef<T>{nullptr, gMany + q0};
+    forChunks(batch, chunk, [&](int64_t q0, unsigned nm) {
+      const hipk::DataRef<T> gref = gr.at(q0);
       if (nSeed > 0) {
         hipk::cholAdjSeedTrailing<T><<<dim3((unsigned)nSeed, nm), 256, 0, stream>>>(
             g.tiles.as<hipk::GradTile>() + seed0, sk, gref);
       }
-      cholAdjLevels<T>(d, lref, gref, nm);
+      cholAdjLevels<T>(d, l.at(q0), gref, nm);
       if (g.nTiles > 0) {
         hipk::cholAdjFinal<T><<<dim3((unsigned)g.nTiles, nm), 256, 0, stream>>>(g.tiles.as<hipk::GradTile>(), sk,
                                                                                gref);
       }
-    }
-    hipCHECK(hipGetLastError());
+    });
   }
 
   // The trailing block (from the first scalar of lump `fromLump` on) of `batch` layout buffers to dense
   // symmetric m x m matrices (toDense), or the adjoint of that in the data-gradient convention
   // (!toDense: in = dense gradients, out = layout buffers, written whole).  dest: device permutation of
-  // 0 .. m-1 or NULL.  One launch per chunk of at most 65535 matrices.
+  // 0 .. m-1 or NULL.  One launch per chunk.
   template <typename T>
   void schurDense(const T* const* in, T* const* out, int64_t batch, bool single, int64_t fromLump,
                   const int32_t* dest, bool toDense) {
@@ -1131,24 +1095,17 @@ struct HipSymbolicCtx : SymbolicCtx {
     GradDev* g = toDense ? nullptr : &gradPlan();
     const int64_t nWork = toDense ? nPairs : g->nTiles;
     if (nWork == 0) return;
-    const int64_t chunk = std::min<int64_t>(batch, 65535);
-    const size_t bytes = batch * sizeof(T*);
-    const T* const* inMany = single ? nullptr : (const T* const*)ptrRing.push(in, bytes, stream);
-    T* const* outMany = single ? nullptr : (T* const*)ptrRing.push(out, bytes, stream);
-    for (int64_t q0 = 0; q0 < batch; q0 += chunk) {
-      const unsigned nm = (unsigned)std::min(chunk, batch - q0);
-      const hipk::DataRef<const T> iref =
-          single ? hipk::DataRef<const T>{in[0], nullptr} : hipk::DataRef<const T>{nullptr, inMany + q0};
-      const hipk::DataRef<T> oref = single ? hipk::DataRef<T>{out[0], nullptr} : hipk::DataRef<T>{nullptr, outMany + q0};
+    const BatchPtrs<const T> i = stage(in, batch, single);
+    const BatchPtrs<T> o = stage(out, batch, single);
+    forChunks(batch, kMaxGridY, [&](int64_t q0, unsigned nm) {
       if (toDense) {
         hipk::schurToDense<T><<<dim3((unsigned)nPairs, nm), 256, 0, stream>>>(
-            sk, skel.lumpToSpan[fromLump], skel.numSpans(), bar, m, dest, iref, oref);
+            sk, skel.lumpToSpan[fromLump], skel.numSpans(), bar, m, dest, i.at(q0), o.at(q0));
       } else {
         hipk::schurFromDense<T><<<dim3((unsigned)g->nTiles, nm), 256, 0, stream>>>(
-            g->tiles.as<hipk::GradTile>(), sk, (int)g->lumpFirstTile[fromLump], bar, m, dest, iref, oref);
+            g->tiles.as<hipk::GradTile>(), sk, (int)g->lumpFirstTile[fromLump], bar, m, dest, i.at(q0), o.at(q0));
       }
-    }
-    hipCHECK(hipGetLastError());
+    });
   }
 
   // one right-to-left pass over the selected-inversion levels for `nMats` matrices (gridDim.y), in
@@ -1157,16 +1114,8 @@ struct HipSymbolicCtx : SymbolicCtx {
   template <typename T>
   void cholAdjLevels(const SelInvDev& d, hipk::DataRef<const T> lref, hipk::DataRef<T> gref, unsigned nMats) {
     const hipk::SkelDev sk = skelDev();
-    const hipk::SelInvStrides st = d.strides();
-    T* linv = reinterpret_cast<T*>(d.scratch->linv.ptr);
-    T* dd = reinterpret_cast<T*>(d.scratch->dd.ptr);
-    T* U = reinterpret_cast<T*>(d.scratch->U.ptr);
-    T* P = reinterpret_cast<T*>(d.scratch->P.ptr);
-    T* Wp = reinterpret_cast<T*>(d.scratch->Wp.ptr);
+    const SelInvDev::View<T> w = d.view<T>();
     const hipk::DataRef<T> lmut{const_cast<T*>(lref.single), const_cast<T* const*>(lref.many)};
-    const SelInvNode* nodes = d.nodes.as<SelInvNode>();
-    const int2* tiles = d.tiles.as<int2>();
-    const int4* zTasks = d.zTasks.as<int4>();
     for (const SelInvLevel& L : d.host.levels) {
       if (L.smallEnd > L.smallBegin) {
         hipk::cholAdjSmallLumps<T><<<dim3((unsigned)(L.smallEnd - L.smallBegin), nMats), 64, 0, stream>>>(
@@ -1174,18 +1123,18 @@ struct HipSymbolicCtx : SymbolicCtx {
       }
       const unsigned nNodes = (unsigned)(L.nodeEnd - L.nodeBegin);
       if (nNodes == 0) continue;
-      const SelInvNode* nd = nodes + L.nodeBegin;
-      hipk::selinvDiagInverse<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, lmut, linv, dd, st);
+      const SelInvNode* nd = w.nodes + L.nodeBegin;
+      hipk::selinvDiagInverse<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, lmut, w.linv, w.dd, w.st);
       const unsigned nTiles = (unsigned)(L.tileEnd - L.tileBegin);
       if (nTiles > 0) {
-        hipk::cholAdjGatherL<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, tiles + L.tileBegin, lref, U, st);
+        hipk::cholAdjGatherL<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, w.tiles + L.tileBegin, lref, w.U, w.st);
         hipk::selinvZrrTimesU<T><<<dim3((unsigned)(L.zEnd - L.zBegin), nMats), 256, 0, stream>>>(
-            nd, zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(),
-            d.pairOff.as<int64_t>(), d.pairStr.as<int32_t>(), gref, U, P, st);
-        hipk::cholAdjReduce<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, tiles + L.tileBegin, gref, linv, U, P,
-                                                                        Wp, st);
+            nd, w.zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(),
+            d.pairOff.as<int64_t>(), d.pairStr.as<int32_t>(), gref, w.U, w.P, w.st);
+        hipk::cholAdjReduce<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, w.tiles + L.tileBegin, gref, w.linv, w.U,
+                                                                        w.P, w.Wp, w.st);
       }
-      hipk::cholAdjDiag<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, lref, gref, linv, Wp, st);
+      hipk::cholAdjDiag<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, lref, gref, w.linv, w.Wp, w.st);
     }
   }
 
@@ -1193,7 +1142,7 @@ struct HipSymbolicCtx : SymbolicCtx {
   // (gridDim.y), what half the free device memory holds in slices -- slices already held count as
   // free), at least 1, at most the testing cap
   int64_t selInvChunk(SelInvDev& d, int64_t batch) {
-    int64_t chunk = std::min<int64_t>(batch, 65535);
+    int64_t chunk = std::min(batch, kMaxGridY);
     if (selInvChunkCap > 0) chunk = std::min<int64_t>(chunk, selInvChunkCap);
     const int64_t slice = d.sliceBytes();
     if (chunk > d.slices() && slice > 0) {
@@ -1234,15 +1183,7 @@ struct HipSymbolicCtx : SymbolicCtx {
   template <typename T>
   void selInvLevels(const SelInvDev& d, hipk::DataRef<T> data, unsigned nMats) {
     const hipk::SkelDev sk = skelDev();
-    const hipk::SelInvStrides st = d.strides();
-    T* linv = reinterpret_cast<T*>(d.scratch->linv.ptr);
-    T* dd = reinterpret_cast<T*>(d.scratch->dd.ptr);
-    T* U = reinterpret_cast<T*>(d.scratch->U.ptr);
-    T* P = reinterpret_cast<T*>(d.scratch->P.ptr);
-    T* Wp = reinterpret_cast<T*>(d.scratch->Wp.ptr);
-    const SelInvNode* nodes = d.nodes.as<SelInvNode>();
-    const int2* tiles = d.tiles.as<int2>();
-    const int4* zTasks = d.zTasks.as<int4>();
+    const SelInvDev::View<T> w = d.view<T>();
     int64_t launches = 0;
     for (const SelInvLevel& L : d.host.levels) {
       if (L.smallEnd > L.smallBegin) {
@@ -1252,18 +1193,20 @@ struct HipSymbolicCtx : SymbolicCtx {
       }
       const unsigned nNodes = (unsigned)(L.nodeEnd - L.nodeBegin);
       if (nNodes == 0) continue;
-      const SelInvNode* nd = nodes + L.nodeBegin;
-      hipk::selinvDiagInverse<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, data, linv, dd, st);
+      const SelInvNode* nd = w.nodes + L.nodeBegin;
+      hipk::selinvDiagInverse<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, data, w.linv, w.dd, w.st);
       const unsigned nTiles = (unsigned)(L.tileEnd - L.tileBegin);
       if (nTiles > 0) {
-        hipk::selinvFormU<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, tiles + L.tileBegin, data, linv, U, st);
+        hipk::selinvFormU<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, w.tiles + L.tileBegin, data, w.linv, w.U,
+                                                                      w.st);
         hipk::selinvZrrTimesU<T><<<dim3((unsigned)(L.zEnd - L.zBegin), nMats), 256, 0, stream>>>(
-            nd, zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(),
-            d.pairOff.as<int64_t>(), d.pairStr.as<int32_t>(), data, U, P, st);
-        hipk::selinvReduceZ<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, tiles + L.tileBegin, data, U, P, Wp, st);
+            nd, w.zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(),
+            d.pairOff.as<int64_t>(), d.pairStr.as<int32_t>(), data, w.U, w.P, w.st);
+        hipk::selinvReduceZ<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, w.tiles + L.tileBegin, data, w.U, w.P,
+                                                                        w.Wp, w.st);
         launches += 3;
       }
-      hipk::selinvDiagBlock<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, data, dd, Wp, st);
+      hipk::selinvDiagBlock<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, data, w.dd, w.Wp, w.st);
       launches += 2;
     }
     counters.selinvLaunches += launches;
@@ -1432,17 +1375,24 @@ struct HipSymbolicCtx : SymbolicCtx {
     }
     return reinterpret_cast<long long*>(sweepTrace.ptr);
   }
-  // pinned host word a watchdog raises (persistent sweeps and tails), and its device alias
-  unsigned* asyncErrWord() {
-    if (!sweepHostErr) {
-      void* hp = nullptr;
-      hipCHECK(hipHostMalloc(&hp, 64, hipHostMallocMapped));
-      sweepHostErr = reinterpret_cast<unsigned*>(hp);
-      *sweepHostErr = 0u;
-      void* dp = nullptr;
-      hipCHECK(hipHostGetDevicePointer(&dp, hp, 0));
-      sweepHostErrDev = reinterpret_cast<unsigned*>(dp);
+  // pinned host word a watchdog raises (persistent sweeps and tails), and its device alias: allocated
+  // on first use.  An error of the runtime is returned, and nothing is kept then
+  hipError_t allocAsyncErrWord() {
+    if (sweepHostErr) return hipSuccess;
+    void *hp = nullptr, *dp = nullptr;
+    hipError_t e = hipHostMalloc(&hp, 64, hipHostMallocMapped);
+    if (e == hipSuccess) e = hipHostGetDevicePointer(&dp, hp, 0);
+    if (e != hipSuccess) {
+      if (hp) (void)hipHostFree(hp);
+      return e;
     }
+    sweepHostErr = reinterpret_cast<unsigned*>(hp);
+    *sweepHostErr = 0u;
+    sweepHostErrDev = reinterpret_cast<unsigned*>(dp);
+    return hipSuccess;
+  }
+  unsigned* asyncErrWord() {
+    hipCHECK(allocAsyncErrWord());
     return sweepHostErrDev;
   }
   template <typename BT>
@@ -1464,17 +1414,7 @@ struct HipSymbolicCtx : SymbolicCtx {
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
         ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&hipk::solveSweepM<BT, true>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
-        if (ok && !sweepHostErr) {
-          void* hp = nullptr;
-          ok = hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess;
-          if (ok) {
-            sweepHostErr = reinterpret_cast<unsigned*>(hp);
-            *sweepHostErr = 0u;
-            void* dp = nullptr;
-            ok = hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess;
-            sweepHostErrDev = reinterpret_cast<unsigned*>(dp);
-          }
-        }
+        ok = ok && allocAsyncErrWord() == hipSuccess;
         if (ok) st = 1;
       }
       if (st < 0) (void)hipGetLastError();
@@ -3076,108 +3016,67 @@ HipPlanStats hipBackendPlanStats(SymbolicCtx& sym, int64_t startLump, int64_t up
   return s;
 }
 
-template <typename T>
-void hipBackendSelectedInverse(SymbolicCtx& sym, T* data) {
+// ---- the extension operations (hip_backend.h): every entry forwards to its HipSymbolicCtx method ----
+static HipSymbolicCtx& hipCtx(SymbolicCtx& sym) {
   HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
   BASPACHO_CHECK_NOTNULL(h);
-  h->selectedInverse(data);
+  return *h;
 }
-template void hipBackendSelectedInverse<double>(SymbolicCtx&, double*);
-template void hipBackendSelectedInverse<float>(SymbolicCtx&, float*);
-
-template <typename T>
-void hipBackendSelectedInverse(SymbolicCtx& sym, const vector<T*>& data) {
-  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
-  BASPACHO_CHECK_NOTNULL(h);
-  h->selectedInverse(data);
-}
-template void hipBackendSelectedInverse<double>(SymbolicCtx&, const vector<double*>&);
-template void hipBackendSelectedInverse<float>(SymbolicCtx&, const vector<float*>&);
 
 void hipBackendSetSelInvBatchChunk(SymbolicCtx& sym, int64_t maxMatrices) {
-  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
-  BASPACHO_CHECK_NOTNULL(h);
   BASPACHO_CHECK_GE(maxMatrices, 0);
-  h->selInvChunkCap = maxMatrices;
+  hipCtx(sym).selInvChunkCap = maxMatrices;
 }
 
+template <typename T>
+void hipBackendSelectedInverse(SymbolicCtx& sym, T* const* data, int64_t batch, bool single) {
+  hipCtx(sym).selectedInverse(data, batch, single);
+}
 template <typename T>
 void hipBackendLogDet(SymbolicCtx& sym, const T* const* factors, int64_t batch, bool single, T* out) {
-  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
-  BASPACHO_CHECK_NOTNULL(h);
-  h->logDet(factors, batch, single, out);
+  hipCtx(sym).logDet(factors, batch, single, out);
 }
-template void hipBackendLogDet<double>(SymbolicCtx&, const double* const*, int64_t, bool, double*);
-template void hipBackendLogDet<float>(SymbolicCtx&, const float* const*, int64_t, bool, float*);
-
 template <typename T>
-void hipBackendFactorAdjoint(SymbolicCtx& sym, const T* const* L, T* const* grad, int64_t batch, bool single) {
-  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
-  BASPACHO_CHECK_NOTNULL(h);
-  h->factorAdjoint(L, grad, batch, single);
+void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a, int64_t batch, bool single) {
+  hipCtx(sym).patternGrad(a, batch, single);
 }
-template void hipBackendFactorAdjoint<double>(SymbolicCtx&, const double* const*, double* const*, int64_t, bool);
-template void hipBackendFactorAdjoint<float>(SymbolicCtx&, const float* const*, float* const*, int64_t, bool);
-
 template <typename T>
 void hipBackendFactorAdjointUpTo(SymbolicCtx& sym, const T* const* P, T* const* grad, int64_t batch, bool single,
                                  int64_t upToLump) {
-  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
-  BASPACHO_CHECK_NOTNULL(h);
-  h->factorAdjointUpTo(P, grad, batch, single, upToLump);
+  hipCtx(sym).factorAdjointUpTo(P, grad, batch, single, upToLump);
 }
-template void hipBackendFactorAdjointUpTo<double>(SymbolicCtx&, const double* const*, double* const*, int64_t, bool,
-                                                  int64_t);
-template void hipBackendFactorAdjointUpTo<float>(SymbolicCtx&, const float* const*, float* const*, int64_t, bool,
-                                                 int64_t);
-
 template <typename T>
 void hipBackendSchurDense(SymbolicCtx& sym, const T* const* in, T* const* out, int64_t batch, bool single,
                           int64_t fromLump, const int32_t* dest, bool toDense) {
-  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
-  BASPACHO_CHECK_NOTNULL(h);
-  h->schurDense(in, out, batch, single, fromLump, dest, toDense);
+  hipCtx(sym).schurDense(in, out, batch, single, fromLump, dest, toDense);
 }
-template void hipBackendSchurDense<double>(SymbolicCtx&, const double* const*, double* const*, int64_t, bool, int64_t,
-                                           const int32_t*, bool);
-template void hipBackendSchurDense<float>(SymbolicCtx&, const float* const*, float* const*, int64_t, bool, int64_t,
-                                          const int32_t*, bool);
-
-template <typename T>
-void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a) {
-  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
-  BASPACHO_CHECK_NOTNULL(h);
-  h->patternGrad(a);
-}
-template void hipBackendPatternGrad<double>(SymbolicCtx&, const HipGradArgs<double>&);
-template void hipBackendPatternGrad<float>(SymbolicCtx&, const HipGradArgs<float>&);
-
 template <typename T>
 void hipBackendAssemble(SymbolicCtx& sym, const AssemblyMap& map, const T* const* in, T* const* out,
                         int64_t batch, bool single, bool adjoint) {
-  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
-  BASPACHO_CHECK_NOTNULL(h);
-  h->assemble(map, in, out, batch, single, adjoint);
+  hipCtx(sym).assemble(map, in, out, batch, single, adjoint);
 }
-template void hipBackendAssemble<double>(SymbolicCtx&, const AssemblyMap&, const double* const*, double* const*,
-                                         int64_t, bool, bool);
-template void hipBackendAssemble<float>(SymbolicCtx&, const AssemblyMap&, const float* const*, float* const*,
-                                        int64_t, bool, bool);
-
-void hipBackendFreeAssembly(HipAssemblyDev* dev) { delete dev; }
-
 template <typename T>
 void hipBackendNormalEq(SymbolicCtx& sym, const NormalEqMap& map, int32_t op, const T* const* values,
                         const T* const* x, T* const* out, int64_t q, int64_t batch, bool single) {
-  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
-  BASPACHO_CHECK_NOTNULL(h);
-  h->normalEq(map, op, values, x, out, q, batch, single);
+  hipCtx(sym).normalEq(map, op, values, x, out, q, batch, single);
 }
-template void hipBackendNormalEq<double>(SymbolicCtx&, const NormalEqMap&, int32_t, const double* const*,
-                                         const double* const*, double* const*, int64_t, int64_t, bool);
-template void hipBackendNormalEq<float>(SymbolicCtx&, const NormalEqMap&, int32_t, const float* const*,
-                                        const float* const*, float* const*, int64_t, int64_t, bool);
 
+#define BSP_INSTANTIATE_EXTENSIONS(T)                                                                            \
+  template void hipBackendSelectedInverse<T>(SymbolicCtx&, T* const*, int64_t, bool);                           \
+  template void hipBackendLogDet<T>(SymbolicCtx&, const T* const*, int64_t, bool, T*);                          \
+  template void hipBackendPatternGrad<T>(SymbolicCtx&, const HipGradArgs<T>&, int64_t, bool);                   \
+  template void hipBackendFactorAdjointUpTo<T>(SymbolicCtx&, const T* const*, T* const*, int64_t, bool, int64_t); \
+  template void hipBackendSchurDense<T>(SymbolicCtx&, const T* const*, T* const*, int64_t, bool, int64_t,       \
+                                        const int32_t*, bool);                                                  \
+  template void hipBackendAssemble<T>(SymbolicCtx&, const AssemblyMap&, const T* const*, T* const*, int64_t,    \
+                                      bool, bool);                                                              \
+  template void hipBackendNormalEq<T>(SymbolicCtx&, const NormalEqMap&, int32_t, const T* const*,               \
+                                      const T* const*, T* const*, int64_t, int64_t, bool);
+BSP_INSTANTIATE_EXTENSIONS(double)
+BSP_INSTANTIATE_EXTENSIONS(float)
+#undef BSP_INSTANTIATE_EXTENSIONS
+
+void hipBackendFreeAssembly(HipAssemblyDev* dev) { delete dev; }
 void hipBackendFreeNormalEq(HipNormalEqDev* dev) { delete dev; }
 
 }  // namespace BaSpaCho

@@ -477,187 +477,21 @@ template void Solver::addMvFrom<float>(const float*, int64_t, const float*, int6
 template void Solver::pseudoFactorFrom<double>(double*, int64_t, bool) const;
 template void Solver::pseudoFactorFrom<float>(float*, int64_t, bool) const;
 
-// the data of a selected inversion: one factor, or a batch of distinct factors (two members aliasing
-// one buffer would race).  Checked before any device work.
-template <typename T>
-static void checkSelInvData(T* data) {
-  if (data == nullptr) throw std::runtime_error("selectedInverse: the data pointer is NULL");
-}
-template <typename T>
-static void checkSelInvData(std::vector<T*>* data) {
-  if (data == nullptr) throw std::runtime_error("selectedInverse: the batch is NULL");
-  if (data->empty()) throw std::runtime_error("selectedInverse: the batch is empty");
-  std::vector<std::pair<T*, int64_t>> sorted;
-  sorted.reserve(data->size());
-  for (int64_t q = 0; q < (int64_t)data->size(); q++) {
-    if ((*data)[q] == nullptr) {
-      throw std::runtime_error("selectedInverse: the data pointer of batch member " + std::to_string(q) +
-                               " is NULL");
-    }
-    sorted.emplace_back((*data)[q], q);
-  }
-  std::sort(sorted.begin(), sorted.end());
-  for (size_t i = 1; i < sorted.size(); i++) {
-    if (sorted[i].first == sorted[i - 1].first) {
-      throw std::runtime_error("selectedInverse: batch members " + std::to_string(sorted[i - 1].second) +
-                               " and " + std::to_string(sorted[i].second) +
-                               " are the same pointer (two members must not share a buffer)");
-    }
-  }
-}
-template <typename T>
-static void runSelInv(SymbolicCtx& sym, T* data) {
-  hipBackendSelectedInverse(sym, data);
-}
-template <typename T>
-static void runSelInv(SymbolicCtx& sym, std::vector<T*>* data) {
-  hipBackendSelectedInverse(sym, *data);
-}
-
-template <typename T>
-void Solver::selectedInverse(T* data) const {
-  checkSelInvData(data);
-  if (canFactorUpTo < factorSkel.numSpans()) {
-    throw std::runtime_error(
-        "selectedInverse: this Solver can only factor up to span " + std::to_string(canFactorUpTo) +
-        " (fill added for the given elimination ranges only); the selected inverse needs a complete "
-        "factor");
-  }
-  runSelInv(*symCtx, data);
-}
-
-template void Solver::selectedInverse<double>(double*) const;
-template void Solver::selectedInverse<float>(float*) const;
-template void Solver::selectedInverse<std::vector<double*>>(std::vector<double*>*) const;
-template void Solver::selectedInverse<std::vector<float*>>(std::vector<float*>*) const;
-
-// ---- gradients on the pattern of L -------------------------------------------------------------
-static void checkCompleteFactor(const char* what, int64_t canFactorUpTo, int64_t numSpans) {
+// ---- extension operations on the device --------------------------------------------------------
+// Every public method is a pair: one member given by its pointers, or a batch given by vectors.  Both
+// go through one run... helper per operation, which checks the arguments before any device work and
+// hands host arrays of device pointers to the backend (hip_backend.h).  The checks they share:
+static void checkCompleteFactor(const char* what, int64_t canFactorUpTo, int64_t numSpans,
+                                const char* who = "it") {
   if (canFactorUpTo < numSpans) {
     throw std::runtime_error(std::string(what) + ": this Solver can only factor up to span " +
                              std::to_string(canFactorUpTo) +
-                             " (fill added for the given elimination ranges only); it needs a complete factor");
+                             " (fill added for the given elimination ranges only); " + who +
+                             " needs a complete factor");
   }
 }
 
-template <typename T>
-void Solver::logDet(const T* factor, T* devOut) const {
-  if (factor == nullptr) throw std::runtime_error("logDet: the factor pointer is NULL");
-  if (devOut == nullptr) throw std::runtime_error("logDet: the output pointer is NULL");
-  checkCompleteFactor("logDet", canFactorUpTo, factorSkel.numSpans());
-  hipBackendLogDet<T>(*symCtx, &factor, 1, true, devOut);
-}
-
-template <typename T>
-void Solver::logDet(const std::vector<T*>& factors, T* devOut) const {
-  if (factors.empty()) throw std::runtime_error("logDet: the batch is empty");
-  for (size_t q = 0; q < factors.size(); q++) {
-    if (factors[q] == nullptr) {
-      throw std::runtime_error("logDet: the factor pointer of batch member " + std::to_string(q) + " is NULL");
-    }
-  }
-  if (devOut == nullptr) throw std::runtime_error("logDet: the output pointer is NULL");
-  checkCompleteFactor("logDet", canFactorUpTo, factorSkel.numSpans());
-  std::vector<const T*> c(factors.begin(), factors.end());
-  hipBackendLogDet<T>(*symCtx, c.data(), (int64_t)c.size(), false, devOut);
-}
-
-// the arguments of patternGrad, checked before any device work (single call: batch 1)
-template <typename T>
-static void checkPatternGrad(size_t batch, const std::vector<T*>& Z, const T* zScale,
-                             const std::vector<T*>& U, const std::vector<T*>& V, int64_t stride,
-                             int nRHS, const std::vector<T*>& out, int64_t order) {
-  const auto members = [batch](const char* name, const std::vector<T*>& v) {
-    if (v.size() != batch) {
-      throw std::runtime_error(std::string("patternGrad: ") + name + " has " + std::to_string(v.size()) +
-                               " pointers for a batch of " + std::to_string(batch));
-    }
-    for (size_t q = 0; q < v.size(); q++) {
-      if (v[q] == nullptr) {
-        throw std::runtime_error(std::string("patternGrad: the ") + name + " pointer of batch member " +
-                                 std::to_string(q) + " is NULL");
-      }
-    }
-  };
-  if (batch == 0) throw std::runtime_error("patternGrad: the batch is empty");
-  members("out", out);
-  if (Z.empty() && U.empty() && V.empty()) {
-    throw std::runtime_error("patternGrad: neither Z nor U / V given (nothing to compute)");
-  }
-  if (!Z.empty()) {
-    members("Z", Z);
-    if (zScale == nullptr) throw std::runtime_error("patternGrad: Z given without its device scale (NULL)");
-  }
-  if (U.empty() != V.empty()) throw std::runtime_error("patternGrad: U and V must be given together");
-  if (!U.empty()) {
-    members("U", U);
-    members("V", V);
-    if (nRHS < 1) throw std::runtime_error("patternGrad: nRHS = " + std::to_string(nRHS) + " < 1");
-    if (stride < order) {
-      throw std::runtime_error("patternGrad: stride " + std::to_string(stride) + " < order " +
-                               std::to_string(order));
-    }
-  }
-}
-
-template <typename T>
-static void runPatternGrad(SymbolicCtx& sym, bool single, const std::vector<T*>& Z, const T* zScale,
-                           const std::vector<T*>& U, const std::vector<T*>& V, int64_t stride, int nRHS,
-                           T alpha, const std::vector<T*>& out) {
-  std::vector<const T*> z(Z.begin(), Z.end()), u(U.begin(), U.end()), v(V.begin(), V.end());
-  HipGradArgs<T> a;
-  a.batch = (int64_t)out.size();
-  a.single = single;
-  a.z = z.empty() ? nullptr : z.data();
-  a.zScale = zScale;
-  a.u = u.empty() ? nullptr : u.data();
-  a.v = v.empty() ? nullptr : v.data();
-  a.ld = stride;
-  a.nRHS = u.empty() ? 0 : nRHS;
-  a.alpha = alpha;
-  a.out = out.data();
-  hipBackendPatternGrad<T>(sym, a);
-}
-
-template <typename T>
-void Solver::patternGrad(const T* Z, const T* zScale, const T* U, const T* V, int64_t stride, int nRHS,
-                         T alpha, T* out) const {
-  if (out == nullptr) throw std::runtime_error("patternGrad: the output pointer is NULL");
-  if ((U == nullptr) != (V == nullptr)) throw std::runtime_error("patternGrad: U and V must be given together");
-  const auto one = [](const T* p) { return p ? std::vector<T*>{const_cast<T*>(p)} : std::vector<T*>{}; };
-  const std::vector<T*> z = one(Z), u = one(U), v = one(V), o{out};
-  checkPatternGrad(1, z, zScale, u, v, stride, nRHS, o, order());
-  checkCompleteFactor("patternGrad", canFactorUpTo, factorSkel.numSpans());
-  runPatternGrad(*symCtx, true, z, zScale, u, v, stride, nRHS, alpha, o);
-}
-
-template <typename T>
-void Solver::patternGrad(const std::vector<T*>& Z, const T* zScale, const std::vector<T*>& U,
-                         const std::vector<T*>& V, int64_t stride, int nRHS, T alpha,
-                         const std::vector<T*>& out) const {
-  checkPatternGrad(out.size(), Z, zScale, U, V, stride, nRHS, out, order());
-  checkCompleteFactor("patternGrad", canFactorUpTo, factorSkel.numSpans());
-  runPatternGrad(*symCtx, false, Z, zScale, U, V, stride, nRHS, alpha, out);
-}
-
-template void Solver::logDet<double>(const double*, double*) const;
-template void Solver::logDet<float>(const float*, float*) const;
-template void Solver::logDet<double>(const std::vector<double*>&, double*) const;
-template void Solver::logDet<float>(const std::vector<float*>&, float*) const;
-template void Solver::patternGrad<double>(const double*, const double*, const double*, const double*, int64_t,
-                                          int, double, double*) const;
-template void Solver::patternGrad<float>(const float*, const float*, const float*, const float*, int64_t, int,
-                                         float, float*) const;
-template void Solver::patternGrad<double>(const std::vector<double*>&, const double*,
-                                          const std::vector<double*>&, const std::vector<double*>&, int64_t,
-                                          int, double, const std::vector<double*>&) const;
-template void Solver::patternGrad<float>(const std::vector<float*>&, const float*, const std::vector<float*>&,
-                                         const std::vector<float*>&, int64_t, int, float,
-                                         const std::vector<float*>&) const;
-
-// ---- reverse mode of the factor and of the triangular solves ------------------------------------
-// outputs (`outBytes` each) must not overlap one another nor any input (`inBytes` each); checked before
-// any device work
+// outputs (`outBytes` each) must not overlap one another nor any input (`inBytes` each)
 template <typename T>
 static void checkNoOverlap(const char* what, const std::vector<T*>& outs, size_t outBytes,
                            const std::vector<const T*>& ins, size_t inBytes) {
@@ -689,6 +523,7 @@ static void checkNoOverlap(const char* what, const std::vector<T*>& outs, size_t
   }
 }
 
+// `v` names one non-NULL pointer per batch member
 template <typename T>
 static void checkMembers(const char* what, const char* name, const std::vector<T*>& v, size_t batch) {
   if (v.size() != batch) {
@@ -701,6 +536,131 @@ static void checkMembers(const char* what, const char* name, const std::vector<T
                                std::to_string(q) + " is NULL");
     }
   }
+}
+
+// the members as pointers to const: what the backend takes for an argument it only reads
+template <typename T>
+static std::vector<const T*> constView(const std::vector<T*>& v) {
+  return std::vector<const T*>(v.begin(), v.end());
+}
+
+// the pointer of a single call as a batch of one
+template <typename T>
+static std::vector<T*> one(const T* p) {
+  return {const_cast<T*>(p)};
+}
+
+// ---- selected inversion: distinct factors (two members aliasing one buffer would race) ------------
+template <typename T>
+static void runSelInv(const Solver& s, SymbolicCtx& sym, bool single, const std::vector<T*>& data) {
+  const char* what = "selectedInverse";
+  if (data.empty()) throw std::runtime_error("selectedInverse: the batch is empty");
+  checkMembers(what, "data", data, data.size());
+  std::vector<std::pair<T*, size_t>> sorted;
+  for (size_t q = 0; q < data.size(); q++) sorted.emplace_back(data[q], q);
+  std::sort(sorted.begin(), sorted.end());
+  for (size_t i = 1; i < sorted.size(); i++) {
+    if (sorted[i].first == sorted[i - 1].first) {
+      throw std::runtime_error("selectedInverse: batch members " + std::to_string(sorted[i - 1].second) +
+                               " and " + std::to_string(sorted[i].second) +
+                               " are the same pointer (two members must not share a buffer)");
+    }
+  }
+  checkCompleteFactor(what, s.canFactorUpToSpan(), s.skel().numSpans(), "the selected inverse");
+  hipBackendSelectedInverse<T>(sym, data.data(), (int64_t)data.size(), single);
+}
+template <typename T>
+static void runSelInv(const Solver& s, SymbolicCtx& sym, T* data) {
+  if (data == nullptr) throw std::runtime_error("selectedInverse: the data pointer is NULL");
+  runSelInv(s, sym, true, one(data));
+}
+template <typename T>
+static void runSelInv(const Solver& s, SymbolicCtx& sym, std::vector<T*>* data) {
+  if (data == nullptr) throw std::runtime_error("selectedInverse: the batch is NULL");
+  runSelInv(s, sym, false, *data);
+}
+
+template <typename T>
+void Solver::selectedInverse(T* data) const {
+  runSelInv(*this, *symCtx, data);
+}
+
+// ---- gradients on the pattern of L -------------------------------------------------------------
+template <typename T>
+static void runLogDet(const Solver& s, SymbolicCtx& sym, bool single, const std::vector<T*>& factors, T* devOut) {
+  const char* what = "logDet";
+  if (factors.empty()) throw std::runtime_error("logDet: the batch is empty");
+  checkMembers(what, "factor", factors, factors.size());
+  if (devOut == nullptr) throw std::runtime_error("logDet: the output pointer is NULL");
+  checkCompleteFactor(what, s.canFactorUpToSpan(), s.skel().numSpans());
+  hipBackendLogDet<T>(sym, constView(factors).data(), (int64_t)factors.size(), single, devOut);
+}
+
+template <typename T>
+void Solver::logDet(const T* factor, T* devOut) const {
+  if (factor == nullptr) throw std::runtime_error("logDet: the factor pointer is NULL");
+  runLogDet(*this, *symCtx, true, one(factor), devOut);
+}
+
+template <typename T>
+void Solver::logDet(const std::vector<T*>& factors, T* devOut) const {
+  runLogDet(*this, *symCtx, false, factors, devOut);
+}
+
+// Z and U / V may be empty vectors (not given); the batch is the size of `out`
+template <typename T>
+static void runPatternGrad(const Solver& s, SymbolicCtx& sym, bool single, const std::vector<T*>& Z,
+                           const T* zScale, const std::vector<T*>& U, const std::vector<T*>& V, int64_t stride,
+                           int nRHS, T alpha, const std::vector<T*>& out) {
+  const char* what = "patternGrad";
+  const size_t batch = out.size();
+  if (batch == 0) throw std::runtime_error("patternGrad: the batch is empty");
+  checkMembers(what, "out", out, batch);
+  if (Z.empty() && U.empty() && V.empty()) {
+    throw std::runtime_error("patternGrad: neither Z nor U / V given (nothing to compute)");
+  }
+  if (!Z.empty()) {
+    checkMembers(what, "Z", Z, batch);
+    if (zScale == nullptr) throw std::runtime_error("patternGrad: Z given without its device scale (NULL)");
+  }
+  if (U.empty() != V.empty()) throw std::runtime_error("patternGrad: U and V must be given together");
+  if (!U.empty()) {
+    checkMembers(what, "U", U, batch);
+    checkMembers(what, "V", V, batch);
+    if (nRHS < 1) throw std::runtime_error("patternGrad: nRHS = " + std::to_string(nRHS) + " < 1");
+    if (stride < s.order()) {
+      throw std::runtime_error("patternGrad: stride " + std::to_string(stride) + " < order " +
+                               std::to_string(s.order()));
+    }
+  }
+  checkCompleteFactor(what, s.canFactorUpToSpan(), s.skel().numSpans());
+  const std::vector<const T*> z = constView(Z), u = constView(U), v = constView(V);
+  HipGradArgs<T> a;
+  a.z = z.empty() ? nullptr : z.data();
+  a.zScale = zScale;
+  a.u = u.empty() ? nullptr : u.data();
+  a.v = v.empty() ? nullptr : v.data();
+  a.ld = stride;
+  a.nRHS = u.empty() ? 0 : nRHS;
+  a.alpha = alpha;
+  a.out = out.data();
+  hipBackendPatternGrad<T>(sym, a, (int64_t)batch, single);
+}
+
+template <typename T>
+void Solver::patternGrad(const T* Z, const T* zScale, const T* U, const T* V, int64_t stride, int nRHS,
+                         T alpha, T* out) const {
+  if (out == nullptr) throw std::runtime_error("patternGrad: the output pointer is NULL");
+  if ((U == nullptr) != (V == nullptr)) throw std::runtime_error("patternGrad: U and V must be given together");
+  const auto opt = [](const T* p) { return p ? one(p) : std::vector<T*>{}; };
+  runPatternGrad(*this, *symCtx, true, opt(Z), zScale, opt(U), opt(V), stride, nRHS, alpha, one(out));
+}
+
+template <typename T>
+void Solver::patternGrad(const std::vector<T*>& Z, const T* zScale, const std::vector<T*>& U,
+                         const std::vector<T*>& V, int64_t stride, int nRHS, T alpha,
+                         const std::vector<T*>& out) const {
+  runPatternGrad(*this, *symCtx, false, Z, zScale, U, V, stride, nRHS, alpha, out);
 }
 
 template <typename T>
@@ -717,14 +677,12 @@ static void runPatternOuter(const Solver& s, SymbolicCtx& sym, bool single, cons
     throw std::runtime_error("patternOuter: stride " + std::to_string(stride) + " < order " +
                              std::to_string(s.order()));
   }
-  std::vector<const T*> in(U.begin(), U.end());
-  in.insert(in.end(), V.begin(), V.end());
+  const std::vector<const T*> u = constView(U), v = constView(V);
+  std::vector<const T*> in = u;
+  in.insert(in.end(), v.begin(), v.end());
   checkNoOverlap(what, out, s.dataSize() * sizeof(T), in, (stride * (nRHS - 1) + s.order()) * sizeof(T));
   checkCompleteFactor(what, s.canFactorUpToSpan(), s.skel().numSpans());
-  std::vector<const T*> u(U.begin(), U.end()), v(V.begin(), V.end());
   HipGradArgs<T> a;
-  a.batch = (int64_t)out.size();
-  a.single = single;
   a.u = u.data();
   a.v = v.data();
   a.ld = stride;
@@ -732,13 +690,12 @@ static void runPatternOuter(const Solver& s, SymbolicCtx& sym, bool single, cons
   a.alpha = alpha;
   a.out = out.data();
   a.outer = true;
-  hipBackendPatternGrad<T>(sym, a);
+  hipBackendPatternGrad<T>(sym, a, (int64_t)out.size(), single);
 }
 
 template <typename T>
 void Solver::patternOuter(const T* U, const T* V, int64_t stride, int nRHS, T alpha, T* out) const {
-  runPatternOuter(*this, *symCtx, true, std::vector<T*>{const_cast<T*>(U)}, std::vector<T*>{const_cast<T*>(V)},
-                  stride, nRHS, alpha, std::vector<T*>{out});
+  runPatternOuter(*this, *symCtx, true, one(U), one(V), stride, nRHS, alpha, one(out));
 }
 
 template <typename T>
@@ -747,31 +704,8 @@ void Solver::patternOuter(const std::vector<T*>& U, const std::vector<T*>& V, in
   runPatternOuter(*this, *symCtx, false, U, V, stride, nRHS, alpha, out);
 }
 
-template <typename T>
-static void runFactorAdjoint(const Solver& s, SymbolicCtx& sym, bool single, const std::vector<T*>& L,
-                             const std::vector<T*>& grad) {
-  const char* what = "factorAdjoint";
-  if (grad.empty()) throw std::runtime_error("factorAdjoint: the batch is empty");
-  checkMembers(what, "grad", grad, grad.size());
-  checkMembers(what, "L", L, grad.size());
-  const size_t bytes = s.dataSize() * sizeof(T);
-  checkNoOverlap(what, grad, bytes, std::vector<const T*>(L.begin(), L.end()), bytes);
-  checkCompleteFactor(what, s.canFactorUpToSpan(), s.skel().numSpans());
-  std::vector<const T*> l(L.begin(), L.end());
-  hipBackendFactorAdjoint<T>(sym, l.data(), grad.data(), (int64_t)grad.size(), single);
-}
-
-template <typename T>
-void Solver::factorAdjoint(const T* L, T* grad) const {
-  runFactorAdjoint(*this, *symCtx, true, std::vector<T*>{const_cast<T*>(L)}, std::vector<T*>{grad});
-}
-
-template <typename T>
-void Solver::factorAdjoint(const std::vector<T*>& L, const std::vector<T*>& grad) const {
-  runFactorAdjoint(*this, *symCtx, false, L, grad);
-}
-
-// ---- reverse-mode sweep of the partial factor and its dense Schur complement ----
+// ---- reverse-mode sweep of the factor, of the partial factor and its dense
+// ---- Schur complement (section 16) ----------------------------------------------------------------
 // the lump of a span that factorUpTo accepts as its end; anything else throws before any device work
 int64_t Solver::partialCutLump(const char* what, int64_t spanIndex) const {
   const int64_t nSpans = factorSkel.numSpans();
@@ -796,28 +730,39 @@ int64_t Solver::partialCutLump(const char* what, int64_t spanIndex) const {
   return lump;
 }
 
+// the sweep of the factor up to spanIndex; factorAdjoint is the cut behind the last span (`name`: what
+// the operation calls its factor argument)
 template <typename T>
-static void runFactorAdjointUpTo(const Solver& s, SymbolicCtx& sym, bool single, const std::vector<T*>& P,
-                                 const std::vector<T*>& grad, int64_t spanIndex) {
-  const char* what = "factorAdjointUpTo";
-  if (grad.empty()) throw std::runtime_error("factorAdjointUpTo: the batch is empty");
+static void runFactorAdjoint(const Solver& s, SymbolicCtx& sym, const char* what, const char* name, bool single,
+                             const std::vector<T*>& P, const std::vector<T*>& grad, int64_t spanIndex) {
+  if (grad.empty()) throw std::runtime_error(std::string(what) + ": the batch is empty");
   checkMembers(what, "grad", grad, grad.size());
-  checkMembers(what, "P", P, grad.size());
+  checkMembers(what, name, P, grad.size());
+  const std::vector<const T*> p = constView(P);
   const size_t bytes = s.dataSize() * sizeof(T);
-  checkNoOverlap(what, grad, bytes, std::vector<const T*>(P.begin(), P.end()), bytes);
+  checkNoOverlap(what, grad, bytes, p, bytes);
   const int64_t lump = s.partialCutLump(what, spanIndex);
-  std::vector<const T*> p(P.begin(), P.end());
   hipBackendFactorAdjointUpTo<T>(sym, p.data(), grad.data(), (int64_t)grad.size(), single, lump);
 }
 
 template <typename T>
+void Solver::factorAdjoint(const T* L, T* grad) const {
+  runFactorAdjoint(*this, *symCtx, "factorAdjoint", "L", true, one(L), one(grad), factorSkel.numSpans());
+}
+
+template <typename T>
+void Solver::factorAdjoint(const std::vector<T*>& L, const std::vector<T*>& grad) const {
+  runFactorAdjoint(*this, *symCtx, "factorAdjoint", "L", false, L, grad, factorSkel.numSpans());
+}
+
+template <typename T>
 void Solver::factorAdjointUpTo(const T* P, T* grad, int64_t spanIndex) const {
-  runFactorAdjointUpTo(*this, *symCtx, true, std::vector<T*>{const_cast<T*>(P)}, std::vector<T*>{grad}, spanIndex);
+  runFactorAdjoint(*this, *symCtx, "factorAdjointUpTo", "P", true, one(P), one(grad), spanIndex);
 }
 
 template <typename T>
 void Solver::factorAdjointUpTo(const std::vector<T*>& P, const std::vector<T*>& grad, int64_t spanIndex) const {
-  runFactorAdjointUpTo(*this, *symCtx, false, P, grad, spanIndex);
+  runFactorAdjoint(*this, *symCtx, "factorAdjointUpTo", "P", false, P, grad, spanIndex);
 }
 
 // toDense: in = layout buffers, out = dense m x m; else in = dense gradients, out = layout buffers
@@ -832,16 +777,14 @@ static void runSchurDense(const Solver& s, SymbolicCtx& sym, const char* what, b
   const int64_t m = s.order() - s.skel().spanStart[spanIndex];
   if (m == 0) throw std::runtime_error(std::string(what) + ": no span behind span " + std::to_string(spanIndex));
   const size_t dataBytes = s.dataSize() * sizeof(T), denseBytes = (size_t)m * m * sizeof(T);
-  checkNoOverlap(what, out, toDense ? denseBytes : dataBytes, std::vector<const T*>(in.begin(), in.end()),
-                 toDense ? dataBytes : denseBytes);
-  std::vector<const T*> i(in.begin(), in.end());
+  const std::vector<const T*> i = constView(in);
+  checkNoOverlap(what, out, toDense ? denseBytes : dataBytes, i, toDense ? dataBytes : denseBytes);
   hipBackendSchurDense<T>(sym, i.data(), out.data(), (int64_t)out.size(), single, lump, dest, toDense);
 }
 
 template <typename T>
 void Solver::schurComplement(const T* P, int64_t spanIndex, T* out, const int32_t* dest) const {
-  runSchurDense(*this, *symCtx, "schurComplement", true, std::vector<T*>{const_cast<T*>(P)}, std::vector<T*>{out},
-                spanIndex, dest, true);
+  runSchurDense(*this, *symCtx, "schurComplement", true, one(P), one(out), spanIndex, dest, true);
 }
 template <typename T>
 void Solver::schurComplement(const std::vector<T*>& P, int64_t spanIndex, const std::vector<T*>& out,
@@ -850,38 +793,13 @@ void Solver::schurComplement(const std::vector<T*>& P, int64_t spanIndex, const 
 }
 template <typename T>
 void Solver::schurComplementAdjoint(const T* gradDense, int64_t spanIndex, T* gradData, const int32_t* dest) const {
-  runSchurDense(*this, *symCtx, "schurComplementAdjoint", true, std::vector<T*>{const_cast<T*>(gradDense)},
-                std::vector<T*>{gradData}, spanIndex, dest, false);
+  runSchurDense(*this, *symCtx, "schurComplementAdjoint", true, one(gradDense), one(gradData), spanIndex, dest, false);
 }
 template <typename T>
 void Solver::schurComplementAdjoint(const std::vector<T*>& gradDense, int64_t spanIndex,
                                     const std::vector<T*>& gradData, const int32_t* dest) const {
   runSchurDense(*this, *symCtx, "schurComplementAdjoint", false, gradDense, gradData, spanIndex, dest, false);
 }
-
-#define BSP_INSTANTIATE_PARTIAL_ADJOINT(T)                                                                    \
-  template void Solver::factorAdjointUpTo<T>(const T*, T*, int64_t) const;                                    \
-  template void Solver::factorAdjointUpTo<T>(const std::vector<T*>&, const std::vector<T*>&, int64_t) const;  \
-  template void Solver::schurComplement<T>(const T*, int64_t, T*, const int32_t*) const;                      \
-  template void Solver::schurComplement<T>(const std::vector<T*>&, int64_t, const std::vector<T*>&,           \
-                                           const int32_t*) const;                                             \
-  template void Solver::schurComplementAdjoint<T>(const T*, int64_t, T*, const int32_t*) const;               \
-  template void Solver::schurComplementAdjoint<T>(const std::vector<T*>&, int64_t, const std::vector<T*>&,    \
-                                                  const int32_t*) const;
-BSP_INSTANTIATE_PARTIAL_ADJOINT(double)
-BSP_INSTANTIATE_PARTIAL_ADJOINT(float)
-#undef BSP_INSTANTIATE_PARTIAL_ADJOINT
-
-template void Solver::patternOuter<double>(const double*, const double*, int64_t, int, double, double*) const;
-template void Solver::patternOuter<float>(const float*, const float*, int64_t, int, float, float*) const;
-template void Solver::patternOuter<double>(const std::vector<double*>&, const std::vector<double*>&, int64_t, int,
-                                           double, const std::vector<double*>&) const;
-template void Solver::patternOuter<float>(const std::vector<float*>&, const std::vector<float*>&, int64_t, int,
-                                          float, const std::vector<float*>&) const;
-template void Solver::factorAdjoint<double>(const double*, double*) const;
-template void Solver::factorAdjoint<float>(const float*, float*) const;
-template void Solver::factorAdjoint<double>(const std::vector<double*>&, const std::vector<double*>&) const;
-template void Solver::factorAdjoint<float>(const std::vector<float*>&, const std::vector<float*>&) const;
 
 // ---- assembly of coordinate entries -----------------------------------------------------------
 std::vector<int64_t> Solver::scalarPermutation() const {
@@ -944,18 +862,6 @@ void Solver::assembleAdjoint(const AssemblyMap& map, const std::vector<const T*>
                              const std::vector<T*>& gradValues) const {
   runAssembly<T>("assembleAdjoint", this, *symCtx, map, gradData, gradValues, false, true);
 }
-template void Solver::assemble<double>(const AssemblyMap&, const double*, double*) const;
-template void Solver::assemble<float>(const AssemblyMap&, const float*, float*) const;
-template void Solver::assemble<double>(const AssemblyMap&, const std::vector<const double*>&,
-                                       const std::vector<double*>&) const;
-template void Solver::assemble<float>(const AssemblyMap&, const std::vector<const float*>&,
-                                      const std::vector<float*>&) const;
-template void Solver::assembleAdjoint<double>(const AssemblyMap&, const double*, double*) const;
-template void Solver::assembleAdjoint<float>(const AssemblyMap&, const float*, float*) const;
-template void Solver::assembleAdjoint<double>(const AssemblyMap&, const std::vector<const double*>&,
-                                              const std::vector<double*>&) const;
-template void Solver::assembleAdjoint<float>(const AssemblyMap&, const std::vector<const float*>&,
-                                             const std::vector<float*>&) const;
 
 // ---- normal equations of a sparse Jacobian -------------------------------------------------------
 template <typename T>
@@ -1007,12 +913,36 @@ void Solver::normalEq(const NormalEqMap& map, int32_t op, const std::vector<cons
   hipBackendNormalEq<T>(*symCtx, map, op, values.data(), hasX ? x.data() : nullptr, out.data(), q,
                         (int64_t)values.size(), single);
 }
-template void Solver::normalEq<double>(const NormalEqMap&, int32_t, const std::vector<const double*>&,
-                                       const std::vector<const double*>&, const std::vector<double*>&, int64_t,
-                                       bool) const;
-template void Solver::normalEq<float>(const NormalEqMap&, int32_t, const std::vector<const float*>&,
-                                      const std::vector<const float*>&, const std::vector<float*>&, int64_t,
-                                      bool) const;
+// one single / batch pair per operation
+#define BSP_INSTANTIATE_EXTENSIONS(T)                                                                          \
+  using BspVec_##T = const std::vector<T*>&;                                                                   \
+  using BspCVec_##T = const std::vector<const T*>&;                                                            \
+  template void Solver::selectedInverse<T>(T*) const;                                                          \
+  template void Solver::selectedInverse<std::vector<T*>>(std::vector<T*>*) const;                              \
+  template void Solver::logDet<T>(const T*, T*) const;                                                         \
+  template void Solver::logDet<T>(BspVec_##T, T*) const;                                                       \
+  template void Solver::patternGrad<T>(const T*, const T*, const T*, const T*, int64_t, int, T, T*) const;     \
+  template void Solver::patternGrad<T>(BspVec_##T, const T*, BspVec_##T, BspVec_##T, int64_t, int, T,          \
+                                       BspVec_##T) const;                                                      \
+  template void Solver::patternOuter<T>(const T*, const T*, int64_t, int, T, T*) const;                        \
+  template void Solver::patternOuter<T>(BspVec_##T, BspVec_##T, int64_t, int, T, BspVec_##T) const;            \
+  template void Solver::factorAdjoint<T>(const T*, T*) const;                                                  \
+  template void Solver::factorAdjoint<T>(BspVec_##T, BspVec_##T) const;                                        \
+  template void Solver::factorAdjointUpTo<T>(const T*, T*, int64_t) const;                                     \
+  template void Solver::factorAdjointUpTo<T>(BspVec_##T, BspVec_##T, int64_t) const;                           \
+  template void Solver::schurComplement<T>(const T*, int64_t, T*, const int32_t*) const;                       \
+  template void Solver::schurComplement<T>(BspVec_##T, int64_t, BspVec_##T, const int32_t*) const;             \
+  template void Solver::schurComplementAdjoint<T>(const T*, int64_t, T*, const int32_t*) const;                \
+  template void Solver::schurComplementAdjoint<T>(BspVec_##T, int64_t, BspVec_##T, const int32_t*) const;      \
+  template void Solver::assemble<T>(const AssemblyMap&, const T*, T*) const;                                   \
+  template void Solver::assemble<T>(const AssemblyMap&, BspCVec_##T, BspVec_##T) const;                        \
+  template void Solver::assembleAdjoint<T>(const AssemblyMap&, const T*, T*) const;                            \
+  template void Solver::assembleAdjoint<T>(const AssemblyMap&, BspCVec_##T, BspVec_##T) const;                 \
+  template void Solver::normalEq<T>(const NormalEqMap&, int32_t, BspCVec_##T, BspCVec_##T, BspVec_##T,         \
+                                    int64_t, bool) const;
+BSP_INSTANTIATE_EXTENSIONS(double)
+BSP_INSTANTIATE_EXTENSIONS(float)
+#undef BSP_INSTANTIATE_EXTENSIONS
 
 #define BSP_INSTANTIATE(T)                                                                     \
   template void Solver::factor<T>(T*, bool) const;                                             \
