@@ -148,6 +148,17 @@ int bsp_device_accessor(bsp_solver* s, const int64_t* out_device_arrays[8]);
 
 void bsp_set_stream(bsp_solver* s, void* stream);
 
+/* Buffer edges, for every bsp_factor_*, bsp_solve_*, bsp_add_mv_from_*, bsp_pseudo_factor_from_* and
+   bsp_selected_inverse_* entry below, as for the gradient entries further down (DESIGN.md section 5,
+   "Buffer edges"; tests/test_buffer_edges_gpu.py):
+   - the strictly-upper elements of the square diagonal blocks of a matrix operand are ignored on input,
+     whatever they hold (NaN and Inf included).  A factor leaves them unspecified; bsp_selected_inverse_*
+     writes them (the diagonal blocks of Z are full);
+   - an operand declared const (dev_mat of the solves and of addMvFrom, dev_in) is only read;
+   - a vector block is read and written on its first `order` rows of each of the nrhs columns only: the
+     rows from `order` to `stride` of a column are neither read nor written;
+   - nothing outside the dataSize() elements of a matrix operand and the (nrhs - 1) * stride + order
+     elements of a vector block is read or written, and a pointer needs the alignment of one element only. */
 /* Solver::factor<double|float>  Solver.h:60-61, Solver.cpp:149-151 */
 int bsp_factor_f64(bsp_solver* s, double* dev_data);
 int bsp_factor_f32(bsp_solver* s, float* dev_data);
@@ -190,7 +201,8 @@ int bsp_do_elimination_f64(bsp_solver* s, double* dev_data, int64_t elim_range_i
 int bsp_do_elimination_f32(bsp_solver* s, float* dev_data, int64_t elim_range_index);
 
 /* Solver::solve / solveL / solveLt  Solver.h:64-73 (vectors in internal order, column-major
-   order x nRHS with leading dimension `stride`) */
+   order x nRHS with leading dimension `stride` >= order; dev_mat is only read, its strictly-upper
+   diagonal-block elements are ignored, the rows order .. stride of every column are left alone) */
 int bsp_solve_f64(bsp_solver* s, const double* dev_mat, double* dev_vec, int64_t stride,
                   int32_t nrhs);
 int bsp_solve_l_f64(bsp_solver* s, const double* dev_mat, double* dev_vec, int64_t stride,
@@ -227,7 +239,8 @@ int bsp_pseudo_factor_from_f32(bsp_solver* s, float* dev_data, int64_t span_inde
    restricted to the block pattern of L overwrites L in the factor's layout: every lump's diagonal
    block is written full and symmetric (both triangles), every off-diagonal block keeps its stored
    orientation, so bsp_diag_block_offset / bsp_block_offset (and its `flipped` flag) read Z as they
-   read L.  Entries of A^-1 outside the pattern are not computed.  Runs on the bsp_set_stream stream,
+   read L.  Entries of A^-1 outside the pattern are not computed.  The strictly-upper elements of L's
+   diagonal blocks are ignored on input (they are overwritten by Z).  Runs on the bsp_set_stream stream,
    no host synchronisation (the first call builds the plan); the result is bitwise reproducible.
    No GPU or a NULL dev_data: non-zero return, bsp_last_error() says why. */
 int bsp_selected_inverse_f64(bsp_solver* s, double* dev_data);
