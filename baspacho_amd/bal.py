@@ -307,19 +307,26 @@ class DevicePipeline:
     def _p(t):
         return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
-    def linearize(self):
-        """residuals and Jacobians of every observation (bsp_bal_linearize_f64)"""
+    def _stream(self, stream):
+        """the stream of a launch: `stream` if given (torch.cuda.Stream or raw hipStream_t address), else
+        what the solver's setStream() was last given, looked up at call time; None = the default stream"""
+        s = self.solver._stream if stream is None else stream
+        return ctypes.c_void_p(0 if s is None else getattr(s, "cuda_stream", s))
+
+    def linearize(self, stream=None):
+        """residuals and Jacobians of every observation (bsp_bal_linearize_f64), on the solver's stream
+        or on `stream`"""
         from . import _check
         fn = self.lib.bsp_bal_linearize_f64 if self.param == "bal9" else self.lib.bsp_bal_linearize_se3_f64
         _check(fn(
             ctypes.c_int64(self.n_obs), self._p(self.obs_cam), self._p(self.obs_pt), self._p(self.obs_xy),
             self._p(self.cams), self._p(self.pts), self._p(self.res), self._p(self.Jc), self._p(self.Jp),
-            ctypes.c_void_p(0)))
+            self._stream(stream)))
         return self.res
 
-    def fill_hessian(self, data, grad=None, lam=0.0, dbg=None):
+    def fill_hessian(self, data, grad=None, lam=0.0, dbg=None, stream=None):
         """data (zeroed by the caller) += J^T J through the device accessor, grad += J^T r,
-        LM damping (bsp_bal_fill_hessian_*)"""
+        LM damping (bsp_bal_fill_hessian_*), on the solver's stream or on `stream`"""
         import torch
         from . import _check
         f32 = data.dtype == torch.float32
@@ -329,8 +336,8 @@ class DevicePipeline:
                 self._p(self.Jp), self._p(self.res), lam_c, self._p(data), self._p(grad))
         if self.param == "se3":
             fn = self.lib.bsp_bal_fill_hessian_se3_f32 if f32 else self.lib.bsp_bal_fill_hessian_se3_f64
-            _check(fn(*head, ctypes.c_void_p(0)))
+            _check(fn(*head, self._stream(stream)))
         else:
             fn = self.lib.bsp_bal_fill_hessian_f32 if f32 else self.lib.bsp_bal_fill_hessian_f64
-            _check(fn(*head, self._p(dbg), ctypes.c_void_p(0)))
+            _check(fn(*head, self._p(dbg), self._stream(stream)))
         return data

@@ -84,6 +84,49 @@ __device__ __forceinline__ Dual scale(const Dual& a, double s, double ds_dv) {
   return r;
 }
 
+// a(x) = sin(sqrt x) / sqrt x = sum (-x)^k / (2k+1)!,  b(x) = (1 - cos(sqrt x)) / x = sum (-x)^k / (2k+2)!
+// and their derivatives in x = theta^2.  The closed forms of the derivatives,
+//   a' = (theta cos(theta) - sin(theta)) / (2 theta^3),  b' = (theta sin(theta) - 2 (1 - cos(theta))) / (2 theta^4),
+// cancel: their relative errors are about 3 eps / x and 12 eps / x.  Below the cut a and b are their
+// degree-6 polynomials (truncation x^7 / 15! relative) and a', b' the exact derivatives of those, six
+// terms each, truncated at 42 x^6 / 15! and 168 x^6 / 16! relative.  The two error curves cross at
+// x = 0.19 (a') and x = 0.29 (b'); the cut is x = 0.25 (theta = 0.5), where the closed forms are off by
+// 1.3e-15 and 5.3e-15 and the series by 7.8e-15 and 1.9e-15 -- on terms that enter the Jacobian scaled by
+// x / 3 or less.  Above the cut b = 2 sin^2(theta / 2) / theta^2, which does not cancel at all.
+constexpr double kRotationSeriesCut = 0.25;
+__device__ __forceinline__ void rotationCoefficients(double x, double& a, double& b, double& da,
+                                                     double& db) {
+  if (x >= kRotationSeriesCut) {
+    const double th = sqrt(x), s = sin(th), c = cos(th), sh = sin(0.5 * th);
+    a = s / th;
+    b = 2.0 * sh * sh / x;
+    da = (th * c - s) / (2.0 * th * x);
+    db = (th * s - 4.0 * sh * sh) / (2.0 * x * x);
+  } else {
+    // 1 / (2k+1)! and 1 / (2k+2)!, k = 0..6
+    constexpr double ca[7] = {1.0, 1.0 / 6, 1.0 / 120, 1.0 / 5040, 1.0 / 362880, 1.0 / 39916800,
+                              1.0 / 6227020800.0};
+    constexpr double cb[7] = {1.0 / 2, 1.0 / 24, 1.0 / 720, 1.0 / 40320, 1.0 / 3628800, 1.0 / 479001600,
+                              1.0 / 87178291200.0};
+    const double y = -x;
+    a = ca[6];
+    b = cb[6];
+    da = 6.0 * ca[6];
+    db = 6.0 * cb[6];
+#pragma unroll
+    for (int k = 5; k >= 0; k--) {
+      a = a * y + ca[k];
+      b = b * y + cb[k];
+      if (k >= 1) {
+        da = da * y + k * ca[k];
+        db = db * y + k * cb[k];
+      }
+    }
+    da = -da;  // d/dx of sum c_k (-x)^k = -sum k c_k (-x)^(k-1)
+    db = -db;
+  }
+}
+
 // residual (2) and its derivatives for one observation; camera = [r(3), t(3), f, k1, k2]
 __device__ __forceinline__ void reproject(const double* cam, const double* pt, const double* xy,
                                           Dual (&res)[2]) {
@@ -95,25 +138,20 @@ __device__ __forceinline__ void reproject(const double* cam, const double* pt, c
     X[i] = variable(pt[i], 9 + i);
   }
   const Dual f = variable(cam[6], 6), k1 = variable(cam[7], 7), k2 = variable(cam[8], 8);
-  // Rodrigues rotation of X by the axis-angle vector w
+  // Rodrigues rotation of X by the axis-angle vector w, through smooth functions of x = theta^2:
+  //   R X = X + a (w x X) + b (w x (w x X)),  a = sin(theta) / theta,  b = (1 - cos(theta)) / theta^2.
+  // No 1 / theta enters the dual path (the axis w / theta has derivatives of size 1 / theta, whose
+  // rounding errors made the rotation columns lose accuracy like eps / theta).
   const Dual th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+  double a, b, da, db;  // a(x), b(x) and their derivatives in x
+  rotationCoefficients(th2.v, a, b, da, db);
+  const Dual A = scale(th2, a, da), B = scale(th2, b, db);
+  const Dual wX[3] = {w[1] * X[2] - w[2] * X[1], w[2] * X[0] - w[0] * X[2], w[0] * X[1] - w[1] * X[0]};
+  const Dual wwX[3] = {w[1] * wX[2] - w[2] * wX[1], w[2] * wX[0] - w[0] * wX[2],
+                       w[0] * wX[1] - w[1] * wX[0]};
   Dual P[3];
-  if (th2.v > 1e-20) {
-    const double th = sqrt(th2.v);
-    const Dual theta = scale(th2, th, 0.5 / th);
-    const Dual c = scale(theta, cos(th), -sin(th)), s = scale(theta, sin(th), cos(th));
-    Dual k[3];
 #pragma unroll
-    for (int i = 0; i < 3; i++) k[i] = w[i] / theta;
-    const Dual kx[3] = {k[1] * X[2] - k[2] * X[1], k[2] * X[0] - k[0] * X[2], k[0] * X[1] - k[1] * X[0]};
-    const Dual kdot = (k[0] * X[0] + k[1] * X[1] + k[2] * X[2]) * (constant(1.0) - c);
-#pragma unroll
-    for (int i = 0; i < 3; i++) P[i] = X[i] * c + kx[i] * s + k[i] * kdot;
-  } else {  // first-order: R X = X + w x X
-    P[0] = X[0] + (w[1] * X[2] - w[2] * X[1]);
-    P[1] = X[1] + (w[2] * X[0] - w[0] * X[2]);
-    P[2] = X[2] + (w[0] * X[1] - w[1] * X[0]);
-  }
+  for (int i = 0; i < 3; i++) P[i] = X[i] + A * wX[i] + B * wwX[i];
 #pragma unroll
   for (int i = 0; i < 3; i++) P[i] = P[i] + t[i];
   const Dual zero = constant(0.0);

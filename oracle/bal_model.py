@@ -48,6 +48,31 @@ class Dual:
         return Dual(s, ds[..., None] * self.d)
 
 
+ROTATION_SERIES_CUT = 0.25
+_CA = [1.0, 1.0 / 6, 1.0 / 120, 1.0 / 5040, 1.0 / 362880, 1.0 / 39916800, 1.0 / 6227020800]
+_CB = [1.0 / 2, 1.0 / 24, 1.0 / 720, 1.0 / 40320, 1.0 / 3628800, 1.0 / 479001600, 1.0 / 87178291200]
+
+
+def rotation_coefficients(x):
+    """a(x) = sin(sqrt x) / sqrt x, b(x) = (1 - cos(sqrt x)) / x and their derivatives in x = theta^2:
+    closed forms at x >= 0.25 (b by the half angle), degree-6 polynomials and their exact derivatives
+    below -- the restatement of rotationCoefficients in csrc/bal_pipeline.hip, where the cut is derived"""
+    x = np.asarray(x, dtype=np.float64)
+    big = x >= ROTATION_SERIES_CUT
+    xs = np.where(big, x, 1.0)
+    th = np.sqrt(xs)
+    s, c, sh = np.sin(th), np.cos(th), np.sin(0.5 * th)
+    closed = (s / th, 2.0 * sh * sh / xs, (th * c - s) / (2.0 * th * xs), (th * s - 4.0 * sh * sh) / (2.0 * xs * xs))
+    y = -np.where(big, 0.0, x)
+    a, b = np.full_like(x, _CA[6]), np.full_like(x, _CB[6])
+    da, db = 6.0 * a, 6.0 * b
+    for k in range(5, -1, -1):
+        a, b = a * y + _CA[k], b * y + _CB[k]
+        if k >= 1:
+            da, db = da * y + k * _CA[k], db * y + k * _CB[k]
+    return tuple(np.where(big, cl, se) for cl, se in zip(closed, (a, b, -da, -db)))
+
+
 def linearize(cams, pts, xy):
     """cams (n, 9), pts (n, 3), xy (n, 2) per observation -> res (n, 2), Jc (n, 2, 9), Jp (n, 2, 3)"""
     n = len(cams)
@@ -55,16 +80,15 @@ def linearize(cams, pts, xy):
     t = [Dual.var(cams[:, 3 + i], 3 + i) for i in range(3)]
     X = [Dual.var(pts[:, i], 9 + i) for i in range(3)]
     f, k1, k2 = Dual.var(cams[:, 6], 6), Dual.var(cams[:, 7], 7), Dual.var(cams[:, 8], 8)
+    # R X = X + a (w x X) + b (w x (w x X)) with a = sin(th) / th and b = (1 - cos(th)) / th^2 as smooth
+    # functions of x = th^2: no 1 / th in the dual path (csrc/bal_pipeline.hip, rotationCoefficients)
     th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2]
-    assert np.all(th2.v > 1e-20), "oracle: zero rotations are not part of the test scenes"
-    th = np.sqrt(th2.v)
-    theta = th2.fn(th, 0.5 / th)
-    c, s = theta.fn(np.cos(th), -np.sin(th)), theta.fn(np.sin(th), np.cos(th))
-    k = [wi / theta for wi in w]
-    kx = [k[1] * X[2] - k[2] * X[1], k[2] * X[0] - k[0] * X[2], k[0] * X[1] - k[1] * X[0]]
+    a, b, da, db = rotation_coefficients(th2.v)
+    A, Bc = th2.fn(a, da), th2.fn(b, db)
+    wX = [w[1] * X[2] - w[2] * X[1], w[2] * X[0] - w[0] * X[2], w[0] * X[1] - w[1] * X[0]]
+    wwX = [w[1] * wX[2] - w[2] * wX[1], w[2] * wX[0] - w[0] * wX[2], w[0] * wX[1] - w[1] * wX[0]]
     one = Dual.const(np.ones(n))
-    kdot = (k[0] * X[0] + k[1] * X[1] + k[2] * X[2]) * (one - c)
-    P = [X[i] * c + kx[i] * s + k[i] * kdot + t[i] for i in range(3)]
+    P = [X[i] + A * wX[i] + Bc * wwX[i] + t[i] for i in range(3)]
     zero = Dual.const(np.zeros(n))
     px, py = (zero - P[0]) / P[2], (zero - P[1]) / P[2]
     r2 = px * px + py * py
