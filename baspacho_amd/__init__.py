@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["Settings", "Solver", "Assembly", "NormalEquations", "create_solver", "SparseStructure", "BackendHip", "BackendCuda",
+__all__ = ["Settings", "Solver", "FactorizationError", "Assembly", "NormalEquations", "create_solver", "SparseStructure", "BackendHip", "BackendCuda",
            "BackendRef", "BackendFast", "AddFillComplete", "AddFillForAutoElims",
            "AddFillForGivenElims", "AddFillNone"]
 
@@ -203,6 +203,17 @@ def _call(lib, name, batched, sfx, *args):
     """call `name` + ["batched_"] + sfx, the single or the batched entry of one operation; raises the
     library's error"""
     _check(getattr(lib, name + ("batched_" if batched else "") + sfx)(*args))
+
+
+class FactorizationError(RuntimeError):
+    """A factor broke down and the regularised retries ran out (Solver.factorRegularized).  `status` is
+    the decoded record of the last try of the (first) failing matrix, `info` what factorRegularized
+    would have returned"""
+
+    def __init__(self, message, status, info=None):
+        super().__init__(message)
+        self.status = status
+        self.info = info
 
 
 class Solver:
@@ -596,6 +607,164 @@ class Solver:
         _call(self._lib, "bsp_log_det_", batched, _suffix(ds[0]), self._h, _ptr_arg(ds, batched),
               ctypes.c_void_p(_ptr_of(out)), *_count(ds, batched))
         return out
+
+    # ---- status of a factor, damping, regularised retry -----------------
+    def _span_range(self, what, spanBegin, spanEnd):
+        spanEnd = self.numSpans() if spanEnd is None else int(spanEnd)
+        spanBegin = int(spanBegin)
+        if not 0 <= spanBegin <= spanEnd <= self.numSpans():
+            raise ValueError("%s: the span range [%d, %d) is not inside [0, %d]" % (what, spanBegin, spanEnd,
+                                                                                  self.numSpans()))
+        return spanBegin, spanEnd
+
+    def _torch_stream(self, device):
+        """the stream of setStream() as a torch stream of `device` (None: the default stream)"""
+        import torch
+        st = self._stream
+        if st is None or (isinstance(st, int) and st == 0):
+            return torch.cuda.default_stream(device)
+        if isinstance(st, int):
+            return torch.cuda.ExternalStream(st, device=device)
+        return st
+
+    def factorStatus(self, data, spanBegin=0, spanEnd=None):
+        """extension: the status record of the stored diagonals of the internal scalars of the spans
+        [spanBegin, spanEnd) of `data` (bsp_factor_status_*): a device int64 tensor [4] =
+        {lowest bad internal scalar or -1, number of bad diagonals, bits of the float64 minimum over the
+        good diagonals (+inf: none), bits of the float64 maximum (0.0: none)}; a diagonal is good when it
+        is positive and finite.  `data` is only read.  Enqueued on the solver's stream without
+        synchronising: readFactorStatus() decodes it.  After factor() the range is all spans, after
+        factorUpTo(span) [0, span), after factorFrom(span) [span, numSpans()); on an unfactored matrix
+        the record describes diag(A).  A list/tuple of tensors (one dtype) = a batch: [B, 4], member q
+        bitwise the single call.  The record is written on the solver's stream (setStream): a caller
+        that reads it with torch on another stream orders the two itself, as for logDet();
+        readFactorStatus() waits for the solver's stream."""
+        import torch
+        b, e = self._span_range("factorStatus", spanBegin, spanEnd)
+        batched, (ds,) = self._same_kind("factorStatus", "data", data)
+        for t in ds:
+            self._check_data(t)
+        out = torch.empty((len(ds), 4) if batched else (4,), dtype=torch.int64, device=ds[0].device)
+        _call(self._lib, "bsp_factor_status_", batched, _suffix(ds[0]), self._h, _ptr_arg(ds, batched),
+              ctypes.c_int64(b), ctypes.c_int64(e), ctypes.c_void_p(_ptr_of(out)), *_count(ds, batched))
+        return out
+
+    def readFactorStatus(self, t):
+        """the record(s) of factorStatus() decoded on the host (this synchronises: one read of 32 bytes
+        per matrix).  A dict {ok, first, param, offsetInParam, count, minDiag, maxDiag}, or a list of
+        them for [B, 4]: `first` is the lowest bad internal scalar (-1 when ok), `param` the caller's
+        parameter that holds it and `offsetInParam` its place inside it (None when ok), `count` the
+        number of bad diagonals, minDiag / maxDiag the range of the good ones (inf / 0.0 without any)."""
+        if t.is_cuda:
+            self._torch_stream(t.device).synchronize()  # the record is written on the solver's stream
+        w = t.detach().cpu().numpy().astype(np.int64)
+        if w.ndim not in (1, 2) or w.shape[-1] != 4:
+            raise ValueError("readFactorStatus: expected an int64 tensor [4] or [B, 4], got shape %s" % (w.shape,))
+        ss = self.skel()["spanStart"]
+        if getattr(self, "_span_to_param", None) is None:
+            self._span_to_param = np.argsort(self.paramToSpan())  # (host, once: the inverse of paramToSpan())
+        span_to_param = self._span_to_param
+
+        def decode(r):
+            first, count = int(r[0]), int(r[1])
+            mn, mx = (float(x) for x in r[2:4].copy().view(np.float64))
+            param = off = None
+            if first >= 0:
+                span = int(np.searchsorted(ss, first, side="right")) - 1
+                param, off = int(span_to_param[span]), first - int(ss[span])
+            return {"ok": count == 0, "first": first, "param": param, "offsetInParam": off, "count": count,
+                    "minDiag": mn, "maxDiag": mx}
+
+        return decode(w) if w.ndim == 1 else [decode(r) for r in w]
+
+    def dampDiagonal(self, data, alpha, beta, spanBegin=0, spanEnd=None):
+        """extension: diagonal <- (diagonal * (1 + alpha)) + beta on the device, in place, over the
+        internal scalars of the spans [spanBegin, spanEnd) (bsp_damp_*); every operation is rounded in
+        the data's dtype (no fused multiply-add): bitwise the numpy statement on scalars of that dtype.
+        alpha and beta are floats or device tensors (0-dim or [1]; [B] for a list/tuple of tensors, one
+        pair per member): as tensors they are read on the device, so a loop can chain calls without
+        synchronising.  No other element of `data` is touched.  Not differentiable (sparse.hessian's
+        damping is).  The pairs are packed into one device array on the solver's stream (setStream),
+        where the kernel reads it; alpha / beta tensors produced on another stream are the caller's to
+        order before the call, like `data`."""
+        import torch
+        b, e = self._span_range("dampDiagonal", spanBegin, spanEnd)
+        batched, (ds,) = self._same_kind("dampDiagonal", "data", data)
+        for t in ds:
+            self._check_data(t)
+        n, dt, dev = len(ds), ds[0].dtype, ds[0].device
+        for name, v in (("alpha", alpha), ("beta", beta)):
+            if isinstance(v, torch.Tensor) and (v.device != dev or v.numel() not in (1, n)):
+                raise ValueError("dampDiagonal: %s must be a float or a tensor of 1 or %d values on %s, got "
+                                 "shape %s on %s" % (name, n, dev, tuple(v.shape), v.device))
+        # on the solver's stream: the array is written, read by the kernel and released in stream order
+        with torch.cuda.stream(self._torch_stream(dev)):
+            cols = [v.detach().to(dt).reshape(-1).expand(n) if isinstance(v, torch.Tensor)
+                    else torch.full((n,), float(v), dtype=dt, device=dev) for v in (alpha, beta)]
+            ab = torch.stack(cols, dim=1).contiguous()  # [n, 2]: alpha, beta of member q at [2 q], [2 q + 1]
+        _call(self._lib, "bsp_damp_", batched, _suffix(ds[0]), self._h, _ptr_arg(ds, batched),
+              ctypes.c_int64(b), ctypes.c_int64(e), ctypes.c_void_p(_ptr_of(ab)), *_count(ds, batched))
+        return data
+
+    def factorRegularized(self, A, out=None, alpha=0.0, beta0=None, growth=10.0, maxRetries=8):
+        """extension: factor() with a status check and a damped retry, all on the device.  `A` (a
+        tensor, or a list/tuple = a batch) is never written; the factor goes to `out` (allocated when
+        None).  Try 0: out.copy_(A); factor(out); status.  Retry t >= 1: out.copy_(A);
+        dampDiagonal(out, alpha, beta0 * growth**(t-1)); factor(out); status.  Each try reads 32 bytes
+        per member from the device.  Of a batch only the members that failed are tried again (as a
+        smaller batch); a member that passes at try 0 holds exactly what factor() of the list gives.
+        beta0=None: 8 * eps(dtype) * maxDiag(A) per member, maxDiag read with factorStatus(A) on the
+        UNFACTORED matrix -- the scan only reads diagonals, so there it gives the range of diag(A) (1.0
+        stands in when A has no good diagonal; a matrix with a bad diagonal can never factor undamped).
+        The copies run on the solver's stream (setStream), in order with the kernels; `A` written on
+        another stream is the caller's to order before the call.
+        Returns (out, info): info = {retries, alpha, beta, status} of the accepted try (beta = 0.0 and
+        alpha = 0.0 at try 0), a list of them for a batch.  Raises FactorizationError, which carries
+        the last status, when a member still fails after `maxRetries` retries."""
+        import torch
+        batched = isinstance(A, (list, tuple))
+        if out is None:
+            out = [torch.empty_like(a) for a in A] if batched else torch.empty_like(A)
+        batched, (As, outs) = self._same_kind("factorRegularized", "A and out", A, out)
+        for t in As + outs:
+            self._check_data(t)
+        n = len(As)
+        eps = float(torch.finfo(As[0].dtype).eps)
+        if beta0 is None:
+            st = self.readFactorStatus(self.factorStatus(list(As)))
+            betas0 = [8.0 * eps * (s["maxDiag"] if s["maxDiag"] > 0.0 else 1.0) for s in st]
+        else:
+            betas0 = [float(beta0)] * n
+        infos = [None] * n
+        pending = list(range(n))
+        for t in range(int(maxRetries) + 1):
+            po = [outs[q] for q in pending]
+            with torch.cuda.stream(self._torch_stream(As[0].device)):
+                for q in pending:
+                    outs[q].copy_(As[q])
+            betas = [0.0 if t == 0 else betas0[q] * float(growth) ** (t - 1) for q in pending]
+            if t > 0:
+                dt, dev = po[0].dtype, po[0].device
+                self.dampDiagonal(po if batched else po[0], torch.full((len(po),), float(alpha), dtype=dt, device=dev),
+                                  torch.tensor(betas, dtype=torch.float64).to(dt).to(dev))
+            self.factor(po if batched else po[0])
+            sts = self.readFactorStatus(self.factorStatus(po))
+            failed = []
+            for q, b, s in zip(pending, betas, sts):
+                infos[q] = {"retries": t, "alpha": float(alpha) if t else 0.0, "beta": b, "status": s}
+                if not s["ok"]:
+                    failed.append(q)
+            pending = failed
+            if not pending:
+                return out, (infos if batched else infos[0])
+        q = pending[0]
+        raise FactorizationError(
+            "factorRegularized: %s not positive definite after %d retries (last beta %g): the first bad pivot is "
+            "internal scalar %d (param %s, offset %s), %d bad diagonals"
+            % ("batch member %d is" % q if batched else "the matrix is", int(maxRetries), infos[q]["beta"],
+               infos[q]["status"]["first"], infos[q]["status"]["param"], infos[q]["status"]["offsetInParam"],
+               infos[q]["status"]["count"]),
+            infos[q]["status"], infos if batched else infos[0])
 
     def patternGrad(self, out, Z=None, zScale=None, U=None, V=None, nRHS=1, alpha=1.0, stride=None):
         """extension: the write-only gradient projection on the pattern of L (bsp_pattern_grad_*).

@@ -533,6 +533,26 @@ static void schurDenseBatched(bsp_solver* s, const T* const* in, int64_t span, T
     s->solver->schurComplementAdjoint(i, span, o, dest);
   }
 }
+template <typename T>
+static void factorStatusBatched(bsp_solver* s, const T* const* ptrs, int64_t b, int64_t e, int64_t* out, int32_t batch) {
+  s->solver->factorStatus(hostArray<T*>("factorStatus", "data", ptrs, batch), b, e, out);
+}
+template <typename T>
+static void dampBatched(bsp_solver* s, T* const* ptrs, int64_t b, int64_t e, const T* ab, int32_t batch) {
+  s->solver->dampDiagonal(hostArray<T*>("dampDiagonal", "data", ptrs, batch), b, e, ab);
+}
+#define BSP_STATUS_API(SFX, T)                                                                                   \
+  int bsp_factor_status_##SFX(bsp_solver* s, const T* d, int64_t b, int64_t e, int64_t* out)                     \
+      BSP_BODY(s->solver->factorStatus(d, b, e, out))                                                            \
+  int bsp_factor_status_batched_##SFX(bsp_solver* s, const T* const* d, int64_t b, int64_t e, int64_t* out,      \
+                                      int32_t batch) BSP_BODY(factorStatusBatched(s, d, b, e, out, batch))       \
+  int bsp_damp_##SFX(bsp_solver* s, T* d, int64_t b, int64_t e, const T* ab)                                     \
+      BSP_BODY(s->solver->dampDiagonal(d, b, e, ab))                                                             \
+  int bsp_damp_batched_##SFX(bsp_solver* s, T* const* d, int64_t b, int64_t e, const T* ab, int32_t batch)       \
+      BSP_BODY(dampBatched(s, d, b, e, ab, batch))
+BSP_STATUS_API(f64, double)
+BSP_STATUS_API(f32, float)
+#undef BSP_STATUS_API
 #define BSP_PATTERN_API(SFX, T)                                                                                  \
   int bsp_selected_inverse_##SFX(bsp_solver* s, T* d) BSP_BODY(s->solver->selectedInverse(d))                    \
   int bsp_selected_inverse_batched_##SFX(bsp_solver* s, T* const* ptrs, int32_t batch)                           \

@@ -127,6 +127,18 @@ struct HipGradArgs {
 };
 template <typename T>
 void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a, int64_t batch, bool single);
+// Status of a factor and damping of the diagonal (hip_status_kernels.h), over the
+// stored diagonals of the internal scalars [spanStart[spanBegin], spanStart[spanEnd]).
+// factorStatus: out + 4 q = {lowest bad scalar or -1, bad diagonals, bits of the double min and max over
+// the good ones} of data[q], which is only read (out: device array of 4 * batch words).
+template <typename T>
+void hipBackendFactorStatus(SymbolicCtx& sym, const T* const* data, int64_t batch, bool single, int64_t spanBegin,
+                            int64_t spanEnd, int64_t* out);
+// dampDiagonal: d <- (d (1 + alpha)) + beta in place, rounded in T after every operation; alphaBeta:
+// device array of 2 * batch values, alpha and beta of member q at [2 q] and [2 q + 1].
+template <typename T>
+void hipBackendDampDiagonal(SymbolicCtx& sym, T* const* data, int64_t batch, bool single, int64_t spanBegin,
+                            int64_t spanEnd, const T* alphaBeta);
 // Reverse-mode sweep of the factor (hip_chol_adjoint_kernels.h; DESIGN.md sections 15 and 16): P[q] holds
 // the factor of the lumps < upToLump with the Schur complement behind them and is only read; grad[q]
 // holds Lbar before the cut and Sbar behind it and is overwritten by the data gradient.  upToLump =

@@ -24,6 +24,7 @@
 #include "hip_grad_kernels.h"
 #include "hip_assembly_kernels.h"
 #include "hip_normal_eq_kernels.h"
+#include "hip_status_kernels.h"
 #include "mat_ops.h"
 
 namespace BaSpaCho {
@@ -532,10 +533,11 @@ struct FlagOff {
 // selected-inversion plan (hip_plan.h, SelInvPlanHost) on the device, with its scratch
 // work lists of the gradient kernels (hip_grad_kernels.h), built once per structure: the patternGrad
 // tiles of every lump column and, for logDet's first pass, the lump of the first diagonal element of
-// every workgroup.  `part` holds logDet's partial sums, nParts per matrix of a chunk.
+// every workgroup.  `part` holds logDet's partial sums, nParts per matrix of a chunk; `statPart` the
+// partial records of factorStatus (hip_status_kernels.h), which reads the same firstLump table.
 struct GradDev {
-  DevBuf tiles, firstLump, part;
-  int64_t nTiles = 0, nParts = 0, partSlices = 0;
+  DevBuf tiles, firstLump, part, statPart;
+  int64_t nTiles = 0, nParts = 0, partSlices = 0, statSlices = 0;
   vector<int64_t> lumpFirstTile;  // host: first tile of every lump (tiles never cross lumps), then nTiles
   void build(const CoalescedBlockMatrixSkel& sk) {
     vector<hipk::GradTile> tl;
@@ -591,6 +593,15 @@ struct GradDev {
     part.release();
     part.resize((size_t)std::max<int64_t>(nParts * n, 1) * sizeof(double));
     partSlices = n;
+  }
+  // the same for the partial records of factorStatus
+  void reserveStat(int64_t n) {
+    if (n <= statSlices) return;
+    if (statSlices > 0) hipCHECK(hipDeviceSynchronize());
+    statSlices = 0;
+    statPart.release();
+    statPart.resize((size_t)std::max<int64_t>(nParts * n, 1) * sizeof(hipk::StatusPart));
+    statSlices = n;
   }
 };
 
@@ -1020,6 +1031,49 @@ struct HipSymbolicCtx : SymbolicCtx {
             sk, g.firstLump.as<int32_t>(), skel.order(), (int)g.nParts, f.at(q0), part);
       }
       hipk::logDetFinal<T><<<dim3(1, nm), 256, 0, stream>>>(part, (int)g.nParts, out + q0);
+    });
+  }
+
+  // ---- factor status and damping of the diagonal (hip_status_kernels.h) -------
+  // the records of `batch` buffers over the internal scalars [g0, g1): two launches per chunk, chunks as
+  // logDet's, the partial records of a chunk in GradDev::statPart
+  template <typename T>
+  void factorStatus(const T* const* data, int64_t batch, bool single, int64_t spanBegin, int64_t spanEnd,
+                    int64_t* out) {
+    checkDevice();
+    GradDev& g = gradPlan();
+    const hipk::SkelDev sk = skelDev();
+    const int64_t g0 = skel.spanStart[spanBegin], g1 = skel.spanStart[spanEnd];
+    const int64_t b0 = g0 / hipk::kLogDetChunk;
+    const int64_t nParts = g1 > g0 ? (g1 + hipk::kLogDetChunk - 1) / hipk::kLogDetChunk - b0 : 0;
+    BASPACHO_CHECK_LE(b0 + nParts, g.nParts);
+    const int64_t chunk = std::min(batch, kMaxGridY);
+    g.reserveStat(chunk);
+    const BatchPtrs<const T> d = stage(data, batch, single);
+    hipk::StatusPart* part = reinterpret_cast<hipk::StatusPart*>(g.statPart.ptr);
+    forChunks(batch, chunk, [&](int64_t q0, unsigned nm) {
+      if (nParts > 0) {
+        hipk::factorStatusPartial<T><<<dim3((unsigned)nParts, nm), 256, 0, stream>>>(
+            sk, g.firstLump.as<int32_t>(), g0, g1, b0, (int)nParts, d.at(q0), part);
+      }
+      hipk::factorStatusFinal<<<dim3(1, nm), 256, 0, stream>>>(part, (int)nParts, out + 4 * q0);
+    });
+  }
+
+  // diagonal <- diagonal (1 + alpha) + beta on the internal scalars [g0, g1) of `batch` buffers, alpha
+  // and beta of member q at ab[2 q], ab[2 q + 1] on the device: one launch per chunk
+  template <typename T>
+  void dampDiagonal(T* const* data, int64_t batch, bool single, int64_t spanBegin, int64_t spanEnd, const T* ab) {
+    checkDevice();
+    GradDev& g = gradPlan();
+    const hipk::SkelDev sk = skelDev();
+    const int64_t g0 = skel.spanStart[spanBegin], g1 = skel.spanStart[spanEnd];
+    if (g1 <= g0) return;
+    const int64_t base = g0 - g0 % 256, wgs = (g1 - base + 255) / 256;
+    const BatchPtrs<T> d = stage(data, batch, single);
+    forChunks(batch, kMaxGridY, [&](int64_t q0, unsigned nm) {
+      hipk::dampDiagonal<T><<<dim3((unsigned)wgs, nm), 256, 0, stream>>>(sk, g.firstLump.as<int32_t>(), g0, g1, base,
+                                                                         d.at(q0), ab + 2 * q0);
     });
   }
 
@@ -3041,6 +3095,16 @@ void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a, int64_t ba
   hipCtx(sym).patternGrad(a, batch, single);
 }
 template <typename T>
+void hipBackendFactorStatus(SymbolicCtx& sym, const T* const* data, int64_t batch, bool single, int64_t spanBegin,
+                            int64_t spanEnd, int64_t* out) {
+  hipCtx(sym).factorStatus(data, batch, single, spanBegin, spanEnd, out);
+}
+template <typename T>
+void hipBackendDampDiagonal(SymbolicCtx& sym, T* const* data, int64_t batch, bool single, int64_t spanBegin,
+                            int64_t spanEnd, const T* alphaBeta) {
+  hipCtx(sym).dampDiagonal(data, batch, single, spanBegin, spanEnd, alphaBeta);
+}
+template <typename T>
 void hipBackendFactorAdjointUpTo(SymbolicCtx& sym, const T* const* P, T* const* grad, int64_t batch, bool single,
                                  int64_t upToLump) {
   hipCtx(sym).factorAdjointUpTo(P, grad, batch, single, upToLump);
@@ -3065,6 +3129,9 @@ void hipBackendNormalEq(SymbolicCtx& sym, const NormalEqMap& map, int32_t op, co
   template void hipBackendSelectedInverse<T>(SymbolicCtx&, T* const*, int64_t, bool);                           \
   template void hipBackendLogDet<T>(SymbolicCtx&, const T* const*, int64_t, bool, T*);                          \
   template void hipBackendPatternGrad<T>(SymbolicCtx&, const HipGradArgs<T>&, int64_t, bool);                   \
+  template void hipBackendFactorStatus<T>(SymbolicCtx&, const T* const*, int64_t, bool, int64_t, int64_t,       \
+                                          int64_t*);                                                            \
+  template void hipBackendDampDiagonal<T>(SymbolicCtx&, T* const*, int64_t, bool, int64_t, int64_t, const T*);  \
   template void hipBackendFactorAdjointUpTo<T>(SymbolicCtx&, const T* const*, T* const*, int64_t, bool, int64_t); \
   template void hipBackendSchurDense<T>(SymbolicCtx&, const T* const*, T* const*, int64_t, bool, int64_t,       \
                                         const int32_t*, bool);                                                  \

@@ -607,6 +607,61 @@ void Solver::logDet(const std::vector<T*>& factors, T* devOut) const {
   runLogDet(*this, *symCtx, false, factors, devOut);
 }
 
+// ---- status of a factor, damping of the diagonal ---------------------------------------------------
+static void checkSpanRange(const char* what, int64_t spanBegin, int64_t spanEnd, int64_t numSpans) {
+  if (spanBegin < 0 || spanBegin > spanEnd || spanEnd > numSpans) {
+    throw std::runtime_error(std::string(what) + ": the span range [" + std::to_string(spanBegin) + ", " +
+                             std::to_string(spanEnd) + ") is not inside [0, " + std::to_string(numSpans) + "]");
+  }
+}
+
+template <typename T>
+static void runFactorStatus(const Solver& s, SymbolicCtx& sym, bool single, const std::vector<T*>& data,
+                            int64_t spanBegin, int64_t spanEnd, int64_t* devOut) {
+  const char* what = "factorStatus";
+  if (data.empty()) throw std::runtime_error("factorStatus: the batch is empty");
+  checkMembers(what, "data", data, data.size());
+  if (devOut == nullptr) throw std::runtime_error("factorStatus: the output pointer is NULL");
+  checkSpanRange(what, spanBegin, spanEnd, s.skel().numSpans());
+  hipBackendFactorStatus<T>(sym, constView(data).data(), (int64_t)data.size(), single, spanBegin, spanEnd, devOut);
+}
+
+template <typename T>
+void Solver::factorStatus(const T* data, int64_t spanBegin, int64_t spanEnd, int64_t* devOut) const {
+  if (data == nullptr) throw std::runtime_error("factorStatus: the data pointer is NULL");
+  runFactorStatus(*this, *symCtx, true, one(data), spanBegin, spanEnd, devOut);
+}
+
+template <typename T>
+void Solver::factorStatus(const std::vector<T*>& data, int64_t spanBegin, int64_t spanEnd, int64_t* devOut) const {
+  runFactorStatus(*this, *symCtx, false, data, spanBegin, spanEnd, devOut);
+}
+
+template <typename T>
+static void runDampDiagonal(const Solver& s, SymbolicCtx& sym, bool single, const std::vector<T*>& data,
+                            int64_t spanBegin, int64_t spanEnd, const T* devAlphaBeta) {
+  const char* what = "dampDiagonal";
+  if (data.empty()) throw std::runtime_error("dampDiagonal: the batch is empty");
+  checkMembers(what, "data", data, data.size());
+  if (devAlphaBeta == nullptr) throw std::runtime_error("dampDiagonal: the alpha / beta pointer is NULL");
+  checkSpanRange(what, spanBegin, spanEnd, s.skel().numSpans());
+  // in place: two members on one buffer would be damped twice, in a race
+  checkNoOverlap<T>(what, data, (size_t)s.dataSize() * sizeof(T), {}, 0);
+  hipBackendDampDiagonal<T>(sym, data.data(), (int64_t)data.size(), single, spanBegin, spanEnd, devAlphaBeta);
+}
+
+template <typename T>
+void Solver::dampDiagonal(T* data, int64_t spanBegin, int64_t spanEnd, const T* devAlphaBeta) const {
+  if (data == nullptr) throw std::runtime_error("dampDiagonal: the data pointer is NULL");
+  runDampDiagonal(*this, *symCtx, true, one(data), spanBegin, spanEnd, devAlphaBeta);
+}
+
+template <typename T>
+void Solver::dampDiagonal(const std::vector<T*>& data, int64_t spanBegin, int64_t spanEnd,
+                          const T* devAlphaBeta) const {
+  runDampDiagonal(*this, *symCtx, false, data, spanBegin, spanEnd, devAlphaBeta);
+}
+
 // Z and U / V may be empty vectors (not given); the batch is the size of `out`
 template <typename T>
 static void runPatternGrad(const Solver& s, SymbolicCtx& sym, bool single, const std::vector<T*>& Z,
@@ -921,6 +976,10 @@ void Solver::normalEq(const NormalEqMap& map, int32_t op, const std::vector<cons
   template void Solver::selectedInverse<std::vector<T*>>(std::vector<T*>*) const;                              \
   template void Solver::logDet<T>(const T*, T*) const;                                                         \
   template void Solver::logDet<T>(BspVec_##T, T*) const;                                                       \
+  template void Solver::factorStatus<T>(const T*, int64_t, int64_t, int64_t*) const;                           \
+  template void Solver::factorStatus<T>(BspVec_##T, int64_t, int64_t, int64_t*) const;                         \
+  template void Solver::dampDiagonal<T>(T*, int64_t, int64_t, const T*) const;                                 \
+  template void Solver::dampDiagonal<T>(BspVec_##T, int64_t, int64_t, const T*) const;                         \
   template void Solver::patternGrad<T>(const T*, const T*, const T*, const T*, int64_t, int, T, T*) const;     \
   template void Solver::patternGrad<T>(BspVec_##T, const T*, BspVec_##T, BspVec_##T, int64_t, int, T,          \
                                        BspVec_##T) const;                                                      \

@@ -97,6 +97,29 @@ class Solver {
   void logDet(const T* factor, T* devOut) const;
   template <typename T>
   void logDet(const std::vector<T*>& factors, T* devOut) const;
+  // extension: the status of a factor and damping of the diagonal, on the device (DESIGN.md section 18;
+  // hip_status_kernels.h).  Both walk the stored diagonals of the internal scalars of the spans
+  // [spanBegin, spanEnd), 0 <= spanBegin <= spanEnd <= numSpans (the range need not sit on a lump
+  // boundary: [0, span) after factorUpTo(span), [span, numSpans) after factorFrom(span)), on the stream
+  // of setStream() without host synchronisation.  NULL pointers, an empty batch and a range outside
+  // the spans are refused before any device work.
+  //
+  // factorStatus: a diagonal is good when it is positive and finite in T.  devOut[0..3] (8-byte words) =
+  // {lowest bad internal scalar or -1, number of bad diagonals, bits of the double minimum over the good
+  // ones (+inf: none), bits of the double maximum (0.0: none)}; `data` is only read.  After a factor()
+  // whose first failing pivot is column k, devOut[0] = k: the columns before k do not depend on A_kk.
+  // Batch form: devOut + 4 q for data[q], bitwise the single call.
+  template <typename T>
+  void factorStatus(const T* data, int64_t spanBegin, int64_t spanEnd, int64_t* devOut) const;
+  template <typename T>
+  void factorStatus(const std::vector<T*>& data, int64_t spanBegin, int64_t spanEnd, int64_t* devOut) const;
+  // dampDiagonal: d <- (d (1 + alpha)) + beta in place, each operation rounded in T; alpha =
+  // devAlphaBeta[0], beta = devAlphaBeta[1] are DEVICE values.  Batch form: devAlphaBeta[2 q], [2 q + 1]
+  // for data[q]; members that overlap are refused.
+  template <typename T>
+  void dampDiagonal(T* data, int64_t spanBegin, int64_t spanEnd, const T* devAlphaBeta) const;
+  template <typename T>
+  void dampDiagonal(const std::vector<T*>& data, int64_t spanBegin, int64_t spanEnd, const T* devAlphaBeta) const;
   // patternGrad: writes, for every stored element e = (i, j) (out is never read),
   //   i > j: out_e = zScale[0] 2 Z_e + alpha sum_k (U_ik V_jk + V_ik U_jk)
   //   i = j: out_e = zScale[0] Z_e   + alpha sum_k U_ik V_ik

@@ -12,6 +12,7 @@
 
     jpat = S.JacobianPattern(jrows, jcols, m, n)   # once per Jacobian pattern: solver + normal-equations maps
     x = S.lstsq(jpat, jvalues, r, damping=(a, b))  # x = (J^T J + D)^-1 J^T r, D = a diag(J^T J) + b I
+    st = S.check_positive_definite(pat, values)    # factor status: ok, or the caller's scalar of the first bad pivot
     data, g = S.normal_equations(jpat, jvalues, r) # H = J^T J in the layout and g = J^T r
 
 The matrix is given by entries (rows[k], cols[k], values[k]) in the caller's scalar order: A_ij = A_ji =
@@ -43,7 +44,7 @@ from . import autograd as _ag
 from .autograd import _OnCurrentStream
 
 __all__ = ["SymmetricPattern", "JacobianPattern", "assemble", "solve", "logdet", "solve_logdet", "sample", "marginalize",
-           "hessian", "jt_vec", "j_vec", "normal_equations", "lstsq"]
+           "hessian", "jt_vec", "j_vec", "normal_equations", "lstsq", "check_positive_definite"]
 
 
 def _host_i64(a):
@@ -481,3 +482,37 @@ def lstsq(jpat, jvalues, r, damping=None):
     data, g = normal_equations(jpat, jvalues, r, damping)
     dim = jvalues.dim() - 1
     return jpat.fromInternal(_ag.solve(jpat.solver, data, jpat.toInternal(g, dim)), dim)
+
+
+# ---- status of the factor ---------------------------------------------------
+def check_positive_definite(pattern, values, damping=None):
+    """Assembles and factors A(values), and returns the decoded status of the factor
+    (Solver.readFactorStatus: ok, first, param, offsetInParam, count, minDiag, maxDiag) with one more
+    key, `scalar`: the CALLER's index of the first failing pivot (None when ok), through the inverse of
+    scalarPermutation().  The factor stops being meaningful at the first bad pivot in the solver's
+    internal order, so `scalar` is the internally-first failure, not the smallest caller index.  A list
+    of dicts for a batch [B, nnz].  With a JacobianPattern, `values` are the Jacobian's, A = J^T J, and
+    damping = (alpha, beta) (floats or device tensors) is applied on the device first: diag <- diag (1 +
+    alpha) + beta.  Synchronises (it reads 32 bytes per matrix); not differentiable."""
+    what = "check_positive_definite"
+    jac = isinstance(pattern, JacobianPattern)
+    _check_values(pattern, values, what, _Pattern)
+    if damping is not None and not jac:
+        raise ValueError("%s: damping goes with a JacobianPattern" % what)
+    sol = pattern.solver
+    v = values.detach().contiguous()
+    with _OnCurrentStream(sol, v.device):
+        data = pattern.normal_eq.hessian(v) if jac else pattern.assembly.assemble(v)
+        members = list(data) if v.dim() == 2 else data
+        if damping is not None:
+            try:
+                alpha, beta = damping
+            except (TypeError, ValueError):
+                raise TypeError("%s: damping must be a pair (alpha, beta), got %r" % (what, damping)) from None
+            sol.dampDiagonal(members, alpha, beta)
+        sol.factor(members)
+        status = sol.readFactorStatus(sol.factorStatus(members))
+    # _to_internal = argsort(scalarPermutation()) is indexed by the INTERNAL scalar and gives the caller's
+    for st in status if isinstance(status, list) else [status]:
+        st["scalar"] = int(pattern._to_internal[st["first"]]) if st["first"] >= 0 else None
+    return status

@@ -271,6 +271,49 @@ int bsp_log_det_f64(bsp_solver* s, const double* dev_factor, double* dev_out);
 int bsp_log_det_f32(bsp_solver* s, const float* dev_factor, float* dev_out);
 int bsp_log_det_batched_f64(bsp_solver* s, const double* const* dev_factors, double* dev_out, int32_t batch);
 int bsp_log_det_batched_f32(bsp_solver* s, const float* const* dev_factors, float* dev_out, int32_t batch);
+/* Extension (no counterpart in the reference): the status of a factor and damping of the diagonal, on
+   the device.  Both walk the stored diagonal elements of the internal scalars of
+   the spans [span_begin, span_end), 0 <= span_begin <= span_end <= numSpans.  The range need not sit on
+   a lump boundary: [0, numSpans) after factor(), [0, span) after factorUpTo(span), [span, numSpans)
+   after factorFrom(span).  They run on the bsp_set_stream stream without host synchronisation (the first
+   call uploads the work list).  A NULL pointer, an empty batch or a range outside the spans: non-zero
+   return before any device work, bsp_last_error() says why.
+   bsp_factor_status_*: a diagonal d is GOOD when d > 0 and d is finite in its type, BAD otherwise (NaN,
+   +-Inf, 0, -0, negative).  dev_out holds four 8-byte words per matrix:
+     w[0]  the lowest bad internal scalar of the range, -1 when there is none
+     w[1]  the number of bad diagonals of the range
+     w[2]  the bit pattern of the double minimum over the good diagonals, +inf when there is none
+     w[3]  the bit pattern of the double maximum over the good diagonals, 0.0 when there is none
+   (float widens exactly; an empty range gives {-1, 0, +inf, 0.0}).  dev_data is only read and nothing but
+   dev_out is written; the record is exact and batch member q (dev_out + 4 q, dev_data a HOST array of
+   device pointers) is bitwise the single call.  The contract of w[0]:
+     1. it is the lowest internal scalar whose stored diagonal is not finite and positive;
+     2. the columns that precede k in the internal order do not depend on A_kk;
+     3. so after a factor() whose first failing pivot is column k, w[0] = k.
+   The scan only reads diagonals, so on an UNFACTORED matrix it gives the range of diag(A), and a
+   necessary condition: a matrix with a bad diagonal cannot factor. */
+int bsp_factor_status_f64(bsp_solver* s, const double* dev_data, int64_t span_begin, int64_t span_end,
+                          int64_t* dev_out);
+int bsp_factor_status_f32(bsp_solver* s, const float* dev_data, int64_t span_begin, int64_t span_end,
+                          int64_t* dev_out);
+int bsp_factor_status_batched_f64(bsp_solver* s, const double* const* dev_data, int64_t span_begin,
+                                  int64_t span_end, int64_t* dev_out, int32_t batch);
+int bsp_factor_status_batched_f32(bsp_solver* s, const float* const* dev_data, int64_t span_begin,
+                                  int64_t span_end, int64_t* dev_out, int32_t batch);
+/* bsp_damp_*: d <- (d * (1 + alpha)) + beta on those diagonals, in place, with three roundings in the
+   data's type (t = 1 + alpha; d = d * t; d = d + beta; no fused multiply-add): bitwise the numpy statement
+   on scalars of that type.  alpha = dev_alpha_beta[0] and beta = dev_alpha_beta[1] are DEVICE values,
+   so a loop can chain calls without synchronising; no other element of the buffer is touched.  The
+   batched form takes dev_alpha_beta[2 q], dev_alpha_beta[2 q + 1] for member q; members whose buffers
+   overlap are refused. */
+int bsp_damp_f64(bsp_solver* s, double* dev_data, int64_t span_begin, int64_t span_end,
+                 const double* dev_alpha_beta);
+int bsp_damp_f32(bsp_solver* s, float* dev_data, int64_t span_begin, int64_t span_end,
+                 const float* dev_alpha_beta);
+int bsp_damp_batched_f64(bsp_solver* s, double* const* dev_data, int64_t span_begin, int64_t span_end,
+                         const double* dev_alpha_beta, int32_t batch);
+int bsp_damp_batched_f32(bsp_solver* s, float* const* dev_data, int64_t span_begin, int64_t span_end,
+                         const float* dev_alpha_beta, int32_t batch);
 /* bsp_pattern_grad_*: a write-only pass (dev_out is never read) over every stored element e = (i, j):
      i > j:  out_e = s 2 Z_e + alpha sum_k (U_ik V_jk + V_ik U_jk)
      i = j:  out_e = s Z_e   + alpha sum_k U_ik V_ik
