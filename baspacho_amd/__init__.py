@@ -818,6 +818,21 @@ class Solver:
         _call(self._lib, "bsp_factor_adjoint_", batched, _suffix(gs[0]), self._h, _ptr_arg(ls, batched),
               _ptr_arg(gs, batched), *_count(gs, batched))
 
+    def selectedInverseAdjoint(self, L, Z, grad):
+        """extension: the reverse mode of selectedInverse(), in place in `grad`
+        (bsp_selected_inverse_adjoint_*).  `L` holds a complete factor(), `Z` what selectedInverse wrote
+        over a copy of it; both are only read.  `grad` holds df/d(slot) on entry for EVERY slot of the
+        layout as selectedInverse writes it (the strictly-upper elements of the diagonal blocks are slots
+        of their own) and Lbar = df/dL on return: the elements i >= j, exactly 0 above the diagonal, the
+        input of factorAdjoint.  Lists/tuples of tensors (one dtype, distinct
+        gradient buffers) = a batch.  The sweep adds with float atomics: results are close, not bitwise,
+        from run to run, and a batch member is close to, not bitwise, the single call."""
+        batched, (ls, zs, gs) = self._same_kind("selectedInverseAdjoint", "L, Z and grad", L, Z, grad)
+        for t in ls + zs + gs:
+            self._check_data(t)
+        _call(self._lib, "bsp_selected_inverse_adjoint_", batched, _suffix(gs[0]), self._h, _ptr_arg(ls, batched),
+              _ptr_arg(zs, batched), _ptr_arg(gs, batched), *_count(gs, batched))
+
     # ---- arguments that are one tensor each, or lists of tensors = a batch ---------------------
     def _same_kind(self, what, names, *xs):
         """(batched, [members of every x]) for arguments that are all tensors or all lists of one length"""

@@ -30,6 +30,15 @@ diagonal blocks; its backward is Solver.factorAdjoint on a clone of the incoming
 upper elements' gradient is ignored).  The half-solves' backward is one more half-solve and
 Solver.patternOuter: Lbar = -(L^-T g_y) y^T and Lbar = -x (L^-1 g_x)^T, on the elements with i >= j.
 
+Through selected inversion:
+
+    Z = BA.selected_inverse(solver, L)        # A^-1 on the pattern of L, for a factor L from cholesky()
+
+Z is what Solver.selectedInverse writes: every slot of the layout, the diagonal blocks full and symmetric.
+Its backward is Solver.selectedInverseAdjoint on a clone of the incoming gradient (every slot counts, the
+strictly-upper ones as weights of Z_ji); the gradient of L is 0 on the strictly-upper elements.  The
+sweep adds with float atomics: gradients are close, not bitwise, from run to run.
+
 Through the partial factor, `span` a span that Solver.factorUpTo accepts:
 
     P = BA.factor_up_to(solver, data, span)        # [L11 0; L21 S] in the layout
@@ -42,7 +51,7 @@ Function); solve_l_up_to's is Solver.solveLtUpTo and Solver.patternOuter with y 
 import torch
 from torch.autograd.function import once_differentiable
 
-__all__ = ["solve", "logdet", "solve_logdet", "cholesky", "solve_l", "solve_lt", "factor_up_to",
+__all__ = ["solve", "logdet", "solve_logdet", "cholesky", "solve_l", "solve_lt", "selected_inverse", "factor_up_to",
            "schur_complement", "solve_l_up_to"]
 
 
@@ -355,6 +364,43 @@ def solve_lt(solver, L, b):
     _check_rhs(solver, L, b, "solve_lt")
     _check_device(solver, "solve_lt", L, b)
     return _HalfSolve.apply(solver, L, b, False)
+
+
+# ---- through selected inversion ----------------------------------------------
+class _SelectedInverse(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver, L):
+        sel = _members if L.dim() == 2 else (lambda t: t)
+        with _OnCurrentStream(solver, L.device):
+            L = L.detach().contiguous()
+            Z = L.clone()
+            solver.selectedInverse(sel(Z))
+        ctx.solver = solver
+        ctx.save_for_backward(L, Z)
+        ctx.set_materialize_grads(False)
+        return Z
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_Z):
+        if g_Z is None or not ctx.needs_input_grad[1]:
+            return None, None
+        L, Z = ctx.saved_tensors
+        solver = ctx.solver
+        sel = _members if L.dim() == 2 else (lambda t: t)
+        with _OnCurrentStream(solver, L.device):
+            grad = g_Z.clone(memory_format=torch.contiguous_format)
+            solver.selectedInverseAdjoint(sel(L), sel(Z), sel(grad))
+        return None, grad
+
+
+def selected_inverse(solver, L):
+    """Z = A^-1 on the pattern of L = cholesky(solver, data), in the solver's layout ([dataSize] or
+    [B, dataSize]; diagonal blocks full and symmetric), differentiable in L.  Every slot of Z takes a
+    gradient; L's gradient is 0 on the strictly-upper elements of the diagonal blocks."""
+    _check_data(solver, L, "selected_inverse")
+    _check_device(solver, "selected_inverse", L)
+    return _SelectedInverse.apply(solver, L)
 
 
 # ---- through the partial factor: factor_up_to, schur_complement, solve_l_up_to (DESIGN.md section 16) ----

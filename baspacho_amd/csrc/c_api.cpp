@@ -516,6 +516,14 @@ static void factorAdjointBatched(bsp_solver* s, const T* const* l, T* const* gra
   s->solver->factorAdjoint(hostArray<T*>(what, "factor", l, batch), g);
 }
 template <typename T>
+static void selectedInverseAdjointBatched(bsp_solver* s, const T* const* l, const T* const* z, T* const* grad,
+                                          int32_t batch) {
+  const char* what = "selectedInverseAdjoint";
+  const std::vector<T*> g = hostArray<T*>(what, "gradient", grad, batch);
+  const std::vector<T*> lv = hostArray<T*>(what, "factor", l, batch);
+  s->solver->selectedInverseAdjoint(lv, hostArray<T*>(what, "Z", z, batch), g);
+}
+template <typename T>
 static void factorAdjointUpToBatched(bsp_solver* s, const T* const* p, T* const* grad, int32_t batch, int64_t span) {
   const char* what = "factorAdjointUpTo";
   const std::vector<T*> g = hostArray<T*>(what, "gradient", grad, batch);
@@ -574,7 +582,12 @@ BSP_STATUS_API(f32, float)
       BSP_BODY(patternOuterBatched(s, u, v, stride, nrhs, alpha, out, batch))                                    \
   int bsp_factor_adjoint_##SFX(bsp_solver* s, const T* l, T* grad) BSP_BODY(s->solver->factorAdjoint(l, grad))   \
   int bsp_factor_adjoint_batched_##SFX(bsp_solver* s, const T* const* l, T* const* grad, int32_t batch)          \
-      BSP_BODY(factorAdjointBatched(s, l, grad, batch))
+      BSP_BODY(factorAdjointBatched(s, l, grad, batch))                                                          \
+  int bsp_selected_inverse_adjoint_##SFX(bsp_solver* s, const T* l, const T* z, T* grad)                         \
+      BSP_BODY(s->solver->selectedInverseAdjoint(l, z, grad))                                                    \
+  int bsp_selected_inverse_adjoint_batched_##SFX(bsp_solver* s, const T* const* l, const T* const* z,            \
+                                                 T* const* grad, int32_t batch)                                  \
+      BSP_BODY(selectedInverseAdjointBatched(s, l, z, grad, batch))
 BSP_PATTERN_API(f64, double)
 BSP_PATTERN_API(f32, float)
 #undef BSP_PATTERN_API

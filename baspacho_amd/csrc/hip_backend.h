@@ -81,7 +81,7 @@ struct HipRunCounters {
   int64_t sweepMfmaLaunches = 0;   // ... of sweepLaunches: the matrix-core form for several right-hand sides
   int64_t sweepsRetired = 0;       // 1: a time-out retired the sweeps of this Solver
   int64_t sweepErrorPending = 0;   // 1: a time-out has been raised and not been reported yet
-  int64_t selinvLaunches = 0;      // kernels enqueued by selected inversion (single or batched)
+  int64_t selinvLaunches = 0;      // kernels enqueued by selected inversion and its adjoint (single or batched)
   int64_t selinvChunks = 0;        // passes over the selected-inversion levels (one per single call)
 };
 HipRunCounters hipBackendRunCounters(SymbolicCtx& sym);
@@ -147,6 +147,13 @@ void hipBackendDampDiagonal(SymbolicCtx& sym, T* const* data, int64_t batch, boo
 template <typename T>
 void hipBackendFactorAdjointUpTo(SymbolicCtx& sym, const T* const* P, T* const* grad, int64_t batch, bool single,
                                  int64_t upToLump);
+// Reverse mode of selected inversion (hip_selinv_adjoint_kernels.h): L[q] a complete
+// factor and Z[q] its selected inverse, both only read; grad[q] holds the gradient of every slot of Z and
+// is overwritten by Lbar (0 on the strictly-upper elements).  The complete selected-inversion plan, its
+// scratch and its chunks; its launches and passes count in selinvLaunches / selinvChunks.
+template <typename T>
+void hipBackendSelectedInverseAdjoint(SymbolicCtx& sym, const T* const* L, const T* const* Z, T* const* grad,
+                                      int64_t batch, bool single);
 // The trailing block of layout buffers (from lump `fromLump` on) to dense symmetric m x m matrices, m =
 // order - lumpStart[fromLump] (toDense: in = layout buffers, out = dense, every element written), or the
 // adjoint in the data-gradient convention (in = dense gradients, out = layout buffers, written whole).

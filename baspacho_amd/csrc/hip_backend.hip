@@ -19,6 +19,7 @@
 #include "hip_solve_wide.h"
 #include "hip_sweep_mfma.h"
 #include "hip_tail_kernel.h"
+#include "hip_selinv_adjoint_kernels.h"
 #include "hip_selinv_kernels.h"
 #include "hip_chol_adjoint_kernels.h"
 #include "hip_grad_kernels.h"
@@ -1190,6 +1191,75 @@ struct HipSymbolicCtx : SymbolicCtx {
       }
       hipk::cholAdjDiag<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, lref, gref, w.linv, w.Wp, w.st);
     }
+  }
+
+  // ---- reverse mode of selected inversion (hip_selinv_adjoint_kernels.h) -------
+  // L[q] a complete factor, Z[q] its selected inverse (both read only); grad[q]: the gradient of every
+  // slot of Z on entry, Lbar on return.  The complete plan, its scratch and its chunks, the levels taken
+  // from the last to the first.
+  template <typename T>
+  void selectedInverseAdjoint(const T* const* L, const T* const* Z, T* const* G, int64_t batch, bool single) {
+    checkDevice();
+    SelInvDev& d = selInvPlan();
+    const int64_t chunk = selInvChunk(d, batch);
+    const BatchPtrs<const T> l = stage(L, batch, single), z = stage(Z, batch, single);
+    const BatchPtrs<T> gr = stage(G, batch, single);
+    forChunks(batch, chunk, [&](int64_t q0, unsigned nm) { selInvAdjLevels<T>(d, l.at(q0), z.at(q0), gr.at(q0), nm); });
+  }
+
+  // one pass over the selected-inversion levels, last level first, for `nMats` matrices (gridDim.y), in
+  // scratch slices 0 .. nMats-1.  selinvDiagInverse and selinvZrrTimesU run as they are: the first reads
+  // L, the second multiplies Z_RR by the S_RI that selinvAdjStage left in U (neither writes its data).
+  // A level of one node has one writer per slot of the scatter: no atomics there.
+  template <typename T>
+  void selInvAdjLevels(const SelInvDev& d, hipk::DataRef<const T> lref, hipk::DataRef<const T> zref,
+                       hipk::DataRef<T> gref, unsigned nMats) {
+    const hipk::SkelDev sk = skelDev();
+    const SelInvDev::View<T> w = d.view<T>();
+    const hipk::DataRef<T> lmut{const_cast<T*>(lref.single), const_cast<T* const*>(lref.many)};
+    const hipk::DataRef<T> zmut{const_cast<T*>(zref.single), const_cast<T* const*>(zref.many)};
+    int64_t launches = 0;
+    for (auto it = d.host.levels.rbegin(); it != d.host.levels.rend(); ++it) {
+      const SelInvLevel& L = *it;
+      if (L.smallEnd > L.smallBegin) {
+        hipk::selinvAdjSmallLumps<T><<<dim3((unsigned)(L.smallEnd - L.smallBegin), nMats), 64, 0, stream>>>(
+            d.smalls.as<SelInvSmall>() + L.smallBegin, sk, lref, zref, gref);
+        launches++;
+      }
+      const unsigned nNodes = (unsigned)(L.nodeEnd - L.nodeBegin);
+      if (nNodes == 0) continue;
+      const SelInvNode* nd = w.nodes + L.nodeBegin;
+      hipk::selinvDiagInverse<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, lmut, w.linv, w.dd, w.st);
+      const unsigned nTiles = (unsigned)(L.tileEnd - L.tileBegin);
+      if (nTiles > 0) {
+        const unsigned nZ = (unsigned)(L.zEnd - L.zBegin);
+        hipk::selinvAdjStage<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, w.tiles + L.tileBegin, lref, gref, w.linv,
+                                                                         w.U, w.P, w.Wp, w.st);
+        // workgroups per task: one per 64 source rows of the level's longest chunk, at most 8
+        int maxChunk = 0;
+        for (int64_t n = L.nodeBegin; n < L.nodeEnd; n++) maxChunk = std::max(maxChunk, (int)d.host.nodes[n].kChunk);
+        const dim3 sgrid(nZ, nMats, (unsigned)std::min(8, std::max(1, (maxChunk + 63) / 64)));
+        if (nNodes == 1) {
+          hipk::selinvAdjScatter<T, false><<<sgrid, 256, 0, stream>>>(
+              nd, w.zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(), d.pairOff.as<int64_t>(),
+              d.pairStr.as<int32_t>(), gref, w.P, w.Wp, w.st);
+        } else {
+          hipk::selinvAdjScatter<T, true><<<sgrid, 256, 0, stream>>>(
+              nd, w.zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(), d.pairOff.as<int64_t>(),
+              d.pairStr.as<int32_t>(), gref, w.P, w.Wp, w.st);
+        }
+        hipk::selinvZrrTimesU<T><<<dim3(nZ, nMats), 256, 0, stream>>>(
+            nd, w.zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(), d.pairOff.as<int64_t>(),
+            d.pairStr.as<int32_t>(), zmut, w.U, w.P, w.st);
+        hipk::selinvAdjReduce<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, w.tiles + L.tileBegin, lref, zref, gref,
+                                                                          w.linv, w.P, w.Wp, w.st);
+        launches += 4;
+      }
+      hipk::selinvAdjDiag<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, gref, w.linv, w.Wp, w.st);
+      launches += 2;
+    }
+    counters.selinvLaunches += launches;
+    counters.selinvChunks++;
   }
 
   // matrices per chunk of a batched pass over plan `d`, with the scratch grown to it: min(batch, 65535
@@ -3110,6 +3180,11 @@ void hipBackendFactorAdjointUpTo(SymbolicCtx& sym, const T* const* P, T* const* 
   hipCtx(sym).factorAdjointUpTo(P, grad, batch, single, upToLump);
 }
 template <typename T>
+void hipBackendSelectedInverseAdjoint(SymbolicCtx& sym, const T* const* L, const T* const* Z, T* const* grad,
+                                      int64_t batch, bool single) {
+  hipCtx(sym).selectedInverseAdjoint(L, Z, grad, batch, single);
+}
+template <typename T>
 void hipBackendSchurDense(SymbolicCtx& sym, const T* const* in, T* const* out, int64_t batch, bool single,
                           int64_t fromLump, const int32_t* dest, bool toDense) {
   hipCtx(sym).schurDense(in, out, batch, single, fromLump, dest, toDense);
@@ -3133,6 +3208,8 @@ void hipBackendNormalEq(SymbolicCtx& sym, const NormalEqMap& map, int32_t op, co
                                           int64_t*);                                                            \
   template void hipBackendDampDiagonal<T>(SymbolicCtx&, T* const*, int64_t, bool, int64_t, int64_t, const T*);  \
   template void hipBackendFactorAdjointUpTo<T>(SymbolicCtx&, const T* const*, T* const*, int64_t, bool, int64_t); \
+  template void hipBackendSelectedInverseAdjoint<T>(SymbolicCtx&, const T* const*, const T* const*, T* const*,  \
+                                                    int64_t, bool);                                             \
   template void hipBackendSchurDense<T>(SymbolicCtx&, const T* const*, T* const*, int64_t, bool, int64_t,       \
                                         const int32_t*, bool);                                                  \
   template void hipBackendAssemble<T>(SymbolicCtx&, const AssemblyMap&, const T* const*, T* const*, int64_t,    \

@@ -820,6 +820,35 @@ void Solver::factorAdjointUpTo(const std::vector<T*>& P, const std::vector<T*>& 
   runFactorAdjoint(*this, *symCtx, "factorAdjointUpTo", "P", false, P, grad, spanIndex);
 }
 
+// ---- reverse mode of selected inversion ------------------------------------
+template <typename T>
+static void runSelInvAdjoint(const Solver& s, SymbolicCtx& sym, bool single, const std::vector<T*>& L,
+                             const std::vector<T*>& Z, const std::vector<T*>& grad) {
+  const char* what = "selectedInverseAdjoint";
+  if (grad.empty()) throw std::runtime_error(std::string(what) + ": the batch is empty");
+  checkMembers(what, "grad", grad, grad.size());
+  checkMembers(what, "L", L, grad.size());
+  checkMembers(what, "Z", Z, grad.size());
+  const std::vector<const T*> l = constView(L), z = constView(Z);
+  std::vector<const T*> in = l;
+  in.insert(in.end(), z.begin(), z.end());
+  const size_t bytes = s.dataSize() * sizeof(T);
+  checkNoOverlap(what, grad, bytes, in, bytes);
+  checkCompleteFactor(what, s.canFactorUpToSpan(), s.skel().numSpans());
+  hipBackendSelectedInverseAdjoint<T>(sym, l.data(), z.data(), grad.data(), (int64_t)grad.size(), single);
+}
+
+template <typename T>
+void Solver::selectedInverseAdjoint(const T* L, const T* Z, T* grad) const {
+  runSelInvAdjoint(*this, *symCtx, true, one(L), one(Z), one(grad));
+}
+
+template <typename T>
+void Solver::selectedInverseAdjoint(const std::vector<T*>& L, const std::vector<T*>& Z,
+                                    const std::vector<T*>& grad) const {
+  runSelInvAdjoint(*this, *symCtx, false, L, Z, grad);
+}
+
 // toDense: in = layout buffers, out = dense m x m; else in = dense gradients, out = layout buffers
 template <typename T>
 static void runSchurDense(const Solver& s, SymbolicCtx& sym, const char* what, bool single,
@@ -987,6 +1016,8 @@ void Solver::normalEq(const NormalEqMap& map, int32_t op, const std::vector<cons
   template void Solver::patternOuter<T>(BspVec_##T, BspVec_##T, int64_t, int, T, BspVec_##T) const;            \
   template void Solver::factorAdjoint<T>(const T*, T*) const;                                                  \
   template void Solver::factorAdjoint<T>(BspVec_##T, BspVec_##T) const;                                        \
+  template void Solver::selectedInverseAdjoint<T>(const T*, const T*, T*) const;                               \
+  template void Solver::selectedInverseAdjoint<T>(BspVec_##T, BspVec_##T, BspVec_##T) const;                   \
   template void Solver::factorAdjointUpTo<T>(const T*, T*, int64_t) const;                                     \
   template void Solver::factorAdjointUpTo<T>(BspVec_##T, BspVec_##T, int64_t) const;                           \
   template void Solver::schurComplement<T>(const T*, int64_t, T*, const int32_t*) const;                       \

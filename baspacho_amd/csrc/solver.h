@@ -157,6 +157,19 @@ class Solver {
   template <typename T>
   void factorAdjoint(const std::vector<T*>& L, const std::vector<T*>& grad) const;
 
+  // extension: reverse mode of selectedInverse() (hip_selinv_adjoint_kernels.h).
+  // `L` holds a complete factor(), `Z` what selectedInverse wrote over a copy of it; both are only read.
+  // `grad` holds df/d(slot) on entry for EVERY slot of the layout as selectedInverse writes it (the
+  // strictly-upper elements of the diagonal blocks are slots of their own) and Lbar = df/dL on return:
+  // the elements i >= j, exactly 0 above the diagonal -- the input of factorAdjoint.  Stream, batch form
+  // and chunks as factorAdjoint.  The scatter of the sweep adds with float atomics: results are close,
+  // not bitwise, from run to run.  Refused before any device work: NULL pointers, an empty batch,
+  // gradient buffers that overlap each other, a factor or a Z, a Solver that cannot factor completely.
+  template <typename T>
+  void selectedInverseAdjoint(const T* L, const T* Z, T* grad) const;
+  template <typename T>
+  void selectedInverseAdjoint(const std::vector<T*>& L, const std::vector<T*>& Z, const std::vector<T*>& grad) const;
+
   // extension: reverse-mode sweep of factorUpTo().  `P` holds factorUpTo(spanIndex)
   // of A(d): [L11 0; L21 S], S = A22 - A21 A11^-1 A12 on the spans from spanIndex on; it is only read.
   // `grad` holds df/dP_e on entry for every stored element i >= j (Lbar on the columns before the cut,

@@ -7,6 +7,8 @@
     x, ld = S.solve_logdet(pat, values, b)         # both, one factor
     data = S.assemble(pat, values)                 # the solver's layout, for baspacho_amd.autograd
     x = S.sample(pat, values, z, mu)               # x = mu + L^-T z: Cov(x) = A^-1
+    c = S.covariance(pat, values)                  # (A^-1)[rows[k], cols[k]] for every entry k
+    v = S.marginal_variances(pat, values)          # diag(A^-1) in the caller's order
     pat = S.SymmetricPattern(rows, cols, n, keep=kept)     # kept scalars ordered last
     Sk, rk = S.marginalize(pat, values, b)         # marginal precision / information of the kept scalars
 
@@ -31,6 +33,11 @@ repeated; H = J^T J is formed on the device straight in t
 fixed summation order.  hessian / jt_vec / j_vec / normal_equations / lstsq are differentiable in the
 Jacobian values and the vectors, and in the two damping factors when they are tensors.
 
+covariance and marginal_variances read A^-1 on the pattern from a selected inversion of the factor
+(assemble -> cholesky -> selected_inverse -> a gather) and are differentiable in
+values; their backward sweep adds with float atomics, so gradients are close, not bitwise, from run to
+run.
+
 marginalize eliminates every scalar outside `keep`: S = A22 - A21 A11^-1 A12 and
 r = b2 - A21 A11^-1 b1 with block 2 the kept scalars, rows and columns in the order of `keep`.  inv(S) is
 the `keep` block of inv(A): S and r are the precision and the information vector of the marginal.
@@ -44,6 +51,7 @@ from . import autograd as _ag
 from .autograd import _OnCurrentStream
 
 __all__ = ["SymmetricPattern", "JacobianPattern", "assemble", "solve", "logdet", "solve_logdet", "sample", "marginalize",
+           "covariance", "marginal_variances",
            "hessian", "jt_vec", "j_vec", "normal_equations", "lstsq", "check_positive_definite"]
 
 
@@ -121,6 +129,7 @@ class _Pattern:
         if key not in self._dev:
             src = {"to_internal": self._to_internal, "to_user": self._to_user,
                    "diag": getattr(self, "_diag", None), "jrows": getattr(self, "_jrows", None),
+                   "diag_user": getattr(self, "_diag_user", None),
                    "jcols": getattr(self, "_jcols", None),
                    "keep_internal": getattr(self, "_keep_internal", None),
                    "keep_dest": getattr(self, "_keep_dest", None)}[which]
@@ -167,6 +176,8 @@ class SymmetricPattern(_Pattern):
         self.assembly = self.solver.assembly(rows, cols, triangle)
         self.nnz = len(rows)
         self._init_order()
+        # layout offset of the diagonal element of every scalar, in the caller's order
+        self._diag_user = self.solver.diagOffsets()[self._to_user]
 
     @staticmethod
     def from_torch(A, param_sizes=None, settings=None, triangle="lower"):
@@ -320,6 +331,48 @@ def sample(pattern, values, z, mu=None):
     L = _ag.cholesky(pattern.solver, assemble(pattern, values))
     x = pattern.fromInternal(_ag.solve_lt(pattern.solver, L, pattern.toInternal(z, dim)), dim)
     return x if mu is None else mu + x
+
+
+class _GatherEntries(torch.autograd.Function):
+    """the layout read at the entries (Assembly.adjoint: 0 for skipped entries); its backward is the
+    assembly itself, which sums the gradients of the duplicates into their one slot"""
+
+    @staticmethod
+    def forward(ctx, asm, data):
+        with _OnCurrentStream(asm.solver, data.device):
+            out = asm.adjoint(data.detach().contiguous())
+        ctx.asm = asm
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if g is None or not ctx.needs_input_grad[1]:
+            return None, None
+        asm = ctx.asm
+        with _OnCurrentStream(asm.solver, g.device):
+            gd = asm.assemble(g.contiguous())
+        return None, gd
+
+
+def _selected_inverse(pattern, values):
+    sol = pattern.solver
+    return _ag.selected_inverse(sol, _ag.cholesky(sol, assemble(pattern, values)))
+
+
+def covariance(pattern, values):
+    """c[k] = (A(values)^-1)[rows[k], cols[k]] for every entry k of the pattern, in the caller's order:
+    [nnz], or [B, nnz] for a batch.  Duplicates all receive the value; entries the assembly skips (the
+    upper half of a "full" pattern) get 0 and no gradient.  Differentiable in values."""
+    _check_values(pattern, values, "covariance")
+    return _GatherEntries.apply(pattern.assembly, _selected_inverse(pattern, values))
+
+
+def marginal_variances(pattern, values):
+    """diag(A(values)^-1) in the caller's order: [n], or [B, n] for a batch.  Differentiable in values."""
+    _check_values(pattern, values, "marginal_variances")
+    return _selected_inverse(pattern, values).index_select(-1, pattern._index("diag_user", values.device))
 
 
 def marginalize(pattern, values, b=None):

@@ -366,6 +366,25 @@ int bsp_factor_adjoint_batched_f64(bsp_solver* s, const double* const* dev_l, do
                                    int32_t batch);
 int bsp_factor_adjoint_batched_f32(bsp_solver* s, const float* const* dev_l, float* const* dev_grad,
                                    int32_t batch);
+/* bsp_selected_inverse_adjoint_*: the reverse mode of bsp_selected_inverse_* (DESIGN.md section 19).  dev_l
+   holds a complete factor(), dev_z what bsp_selected_inverse_* wrote over a copy of it; both are only
+   read.  dev_grad holds df/d(slot) on entry for EVERY slot of the layout as bsp_selected_inverse_* writes
+   it -- the strictly-upper elements of the diagonal blocks hold Z_ji and are slots of their own -- and
+   Lbar = df/dL on return: the stored elements with i >= j, exactly 0 on the strictly-upper elements.
+   That is the input of bsp_factor_adjoint_*; the two in a row give the projection of -Z S Z in
+   bsp_pattern_grad_*'s convention, S the symmetrised slot weights (S_ij = S_ji = half the sum of dev_grad
+   over the slots holding Z_ij or Z_ji, S_ii the diagonal slot).  Plan, scratch and chunks of
+   bsp_selected_inverse_*; the cost is one to two times its cost.  The sweep adds into shared slots with
+   native float atomics: results are close, NOT bitwise, from run to run, and a batch member is close
+   to, not bitwise, the single call.  The batched form takes HOST arrays of `batch` device pointers.
+   dev_grad overlapping a dev_l, a dev_z or another member's dev_grad, a NULL pointer, batch <= 0 or a
+   solver that cannot factor completely: non-zero return before any device work. */
+int bsp_selected_inverse_adjoint_f64(bsp_solver* s, const double* dev_l, const double* dev_z, double* dev_grad);
+int bsp_selected_inverse_adjoint_f32(bsp_solver* s, const float* dev_l, const float* dev_z, float* dev_grad);
+int bsp_selected_inverse_adjoint_batched_f64(bsp_solver* s, const double* const* dev_l, const double* const* dev_z,
+                                             double* const* dev_grad, int32_t batch);
+int bsp_selected_inverse_adjoint_batched_f32(bsp_solver* s, const float* const* dev_l, const float* const* dev_z,
+                                             float* const* dev_grad, int32_t batch);
 /* bsp_factor_adjoint_up_to_*: the reverse-mode sweep of bsp_factor_up_to_* (DESIGN.md section 16).  dev_p
    holds factorUpTo(span) of A(d) -- the factor L11, L21 on the columns before the cut and the Schur
    complement S = A22 - A21 A11^-1 A12 behind it -- and is only read.  dev_grad holds df/dP_e on entry
@@ -635,9 +654,10 @@ typedef struct bsp_run_counters {
   int64_t solve_wide_launches;  /* backward elimination passes with the right-hand sides across the lanes */
   int64_t inv_reused;           /* backward passes that found the inverted diagonal blocks of their forward pass */
   int64_t potrf_folded_levels;  /* tree levels whose potrf launch was folded into their trsm launch */
-  int64_t selinv_launches;      /* kernels enqueued by selected inversion (single or batched) */
+  int64_t selinv_launches;      /* kernels enqueued by selected inversion and by its adjoint
+                                   (bsp_selected_inverse_adjoint_*), single or batched */
   int64_t selinv_chunks;        /* passes over the selected-inversion levels: 1 per single call, 1 per
-                                   chunk of a batched call */
+                                   chunk of a batched call (the adjoint's passes count here too) */
 } bsp_run_counters;
 int bsp_run_counters_get(bsp_solver* s, bsp_run_counters* out);
 
