@@ -40,7 +40,7 @@ class _CSettings(ctypes.Structure):
                 ("computation_model", ctypes.POINTER(ctypes.c_double))]
 
 
-_HIP_OPTION_INTS = ["lookahead", "due_stream", "split_k", "gather_max_pairs", "gather_overlap",
+_HIP_OPTION_INTS = ["lookahead", "due_stream", "split_k", "gather_max_pairs",
                     "sub_batch_min", "sub_batches", "tail_blocks", "lazy_plan", "block_solve", "solve_inv",
                     "solve_sweep", "sweep_min_width", "solve_wide", "chain_contraction", "dense_merge", "expected_batch"]
 _HIP_OPTION_REALS = ["lookahead_min_gf", "bulk_ahead", "level_cost_us"]
@@ -48,7 +48,9 @@ _HIP_OPTION_REALS = ["lookahead_min_gf", "bulk_ahead", "level_cost_us"]
 
 class _CHipOptions(ctypes.Structure):
     """bsp_hip_options (include/baspacho_amd.h): negative / NaN = the library's default"""
-    _fields_ = [(n, ctypes.c_int32) for n in _HIP_OPTION_INTS] + [(n, ctypes.c_double) for n in _HIP_OPTION_REALS]
+    # (gather_overlap: ignored by the library, kept for ABI stability; a slot, not an option)
+    _fields_ = [(n, ctypes.c_int32) for n in _HIP_OPTION_INTS[:4] + ["gather_overlap"] + _HIP_OPTION_INTS[4:]] + \
+               [(n, ctypes.c_double) for n in _HIP_OPTION_REALS]
 
 
 class _CPlanStats(ctypes.Structure):
@@ -970,7 +972,8 @@ class Solver:
         launched / timed out, split-K lists used, sub-batches enqueued, lookahead forks"""
         st = _CRunCounters()
         _check(self._lib.bsp_run_counters_get(self._h, ctypes.byref(st)))
-        return {n: getattr(st, n) for n, _ in _CRunCounters._fields_}
+        # (gather_chunks_overlapped only keeps the layout of bsp_run_counters: always 0)
+        return {n: getattr(st, n) for n, _ in _CRunCounters._fields_ if n != "gather_chunks_overlapped"}
 
     def factorProfiled(self, data, in_situ=False, busy=False):
         """one factor() with every launch bracketed by HIP events; returns {kernel class: (total

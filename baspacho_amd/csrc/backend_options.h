@@ -16,7 +16,6 @@ struct HipBackendOptions {
   int32_t dueStream = -1;         // 0: one auxiliary stream (BSP_DUE_STREAM)
   int32_t splitK = -1;            // 0: no split-K tile lists (BSP_SPLIT_K)
   int32_t gatherMaxPairs = -1;    // pairs per gather item (BSP_GATHER_MAX_PAIRS)
-  int32_t gatherOverlap = -1;     // 1: gather chunks beside the dense chain (BSP_GATHER_OVERLAP)
   int32_t subBatchMin = -1;       // batches of at least this many as concurrent sub-batches; 0: never (BSP_SUB_BATCH_MIN)
   int32_t subBatches = -1;        // ... this many parts (BSP_SUB_BATCHES)
   int32_t tailBlocks = -1;        // outer blocks of a wide root lump factored by the persistent tail; 0: off (BSP_TAIL_BLOCKS)

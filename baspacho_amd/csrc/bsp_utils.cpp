@@ -88,7 +88,6 @@ void HipBackendOptions::applyEnv() {
   flag("BSP_DUE_STREAM", dueStream);
   flag("BSP_SPLIT_K", splitK);
   num("BSP_GATHER_MAX_PAIRS", gatherMaxPairs, 8);
-  flag("BSP_GATHER_OVERLAP", gatherOverlap);
   num("BSP_SUB_BATCH_MIN", subBatchMin, 0);
   num("BSP_SUB_BATCHES", subBatches, 2);
   num("BSP_TAIL_BLOCKS", tailBlocks, 0);

@@ -74,7 +74,6 @@ int bsp_create_solver_opts(const bsp_settings* st, const bsp_hip_options* ho, in
     options.dueStream = ho->due_stream;
     options.splitK = ho->split_k;
     options.gatherMaxPairs = ho->gather_max_pairs;
-    options.gatherOverlap = ho->gather_overlap;
     options.subBatchMin = ho->sub_batch_min;
     options.subBatches = ho->sub_batches;
     options.tailBlocks = ho->tail_blocks;
@@ -993,7 +992,7 @@ int bsp_run_counters_get(bsp_solver* s, bsp_run_counters* out) {
   out->lookahead_forks = c.lookaheadForks;
   out->sweeps_retired = c.sweepsRetired;
   out->sweep_error_pending = c.sweepErrorPending;
-  out->gather_chunks_overlapped = c.gatherChunksOverlapped;
+  out->gather_chunks_overlapped = 0;
   out->tail_launches = c.tailLaunches;
   out->sweep_mfma_launches = c.sweepMfmaLaunches;
   out->solve_wide_launches = c.solveWideLaunches;

@@ -73,7 +73,6 @@ struct HipRunCounters {
   int64_t splitListsUsed = 0;      // update launches that took a split-K tile list
   int64_t subBatchesEnqueued = 0;  // sub-batches enqueued on their own stream
   int64_t lookaheadForks = 0;      // lookahead launches handed to the auxiliary streams
-  int64_t gatherChunksOverlapped = 0;  // sparse-elimination gather chunks launched beside the dense chain
   int64_t tailLaunches = 0;        // persistent tail launches (hip_tail_kernel.h)
   int64_t solveWideLaunches = 0;   // backward elimination passes of hip_solve_wide.h
   int64_t invReused = 0;           // backward passes that reused the inverses of their forward pass

@@ -709,7 +709,6 @@ struct HipSymbolicCtx : SymbolicCtx {
     splitK = HipBackendOptions::on(o.splitK, true);
     sweepEnabled = HipBackendOptions::on(o.solveSweep, true);
     solveWide = HipBackendOptions::on(o.solveWide, true);
-    gatherOverlap = HipBackendOptions::on(o.gatherOverlap, false);
     if (o.sweepMinWidth >= 0) sweepMinWidth = std::max(1, o.sweepMinWidth);
     lazyPlan = HipBackendOptions::on(o.lazyPlan, false);
     if (!std::isnan(o.lookaheadMinGF)) lookaheadMinFlops = 1e9 * o.lookaheadMinGF;
@@ -719,17 +718,14 @@ struct HipSymbolicCtx : SymbolicCtx {
     if (o.gatherMaxPairs >= 0) planOpts.gatherMaxPairs = std::max(8, o.gatherMaxPairs);
     if (!std::isnan(o.bulkAhead)) planOpts.bulkAhead = o.bulkAhead;
     if (o.tailBlocks >= 0) planOpts.tailBlocks = o.tailBlocks;
-    planOpts.gatherOverlap = gatherOverlap;
     planOpts.applyDeveloperEnv();
     // developer aids and experiment parameters that are not options of the product
     if (const char* e = std::getenv("BSP_TAIL_FLAGS")) tailFlags = std::atoi(e);
-    if (const char* e = std::getenv("BSP_GATHER_OVERLAP_LDS")) gatherOverlapLds = (unsigned)std::max(0, std::atoi(e));
     if (const char* e = std::getenv("BSP_SWEEP_TRACE")) sweepTraceOn = e[0] != '0';
     if (const char* e = std::getenv("BSP_SWEEP_MFMA_MIN")) sweepMfmaMinRhs = std::max(1, std::atoi(e));
     if (const char* e = std::getenv("BSP_SWEEP_MFMA_MIN_WIDTH")) sweepMfmaMinWidth = std::max(0, std::atoi(e));
     if (const char* e = std::getenv("BSP_SOLVE_WIDE_MIN")) solveWideMinRhs = std::max(2, std::atoi(e));
     if (const char* e = std::getenv("BSP_POTRF_IN_TRSM")) potrfInTrsm = e[0] != '0';
-    if (const char* e = std::getenv("BSP_TAIL_IN_BATCH")) tailInBatch = e[0] != '0';
     if (const char* e = std::getenv("BSP_FOLD_MAX_TILES")) foldMaxTiles = std::min<int64_t>(DevPlan::kFoldMaxTiles, std::max(1, std::atoi(e)));
   }
 
@@ -1416,12 +1412,9 @@ struct HipSymbolicCtx : SymbolicCtx {
   HipPlanOptions planOpts;     // the plan builder's switches (BSP_DUE_STREAM, BSP_BULK_AHEAD, ...)
   double lookaheadMinFlops = HipPlanHost::kMinDeferredFlopsPerFork;  // BSP_LOOKAHEAD_MIN_GF (0: side streams whenever a plan has lookahead units)
   bool blockSolve = true;   // wide lumps: triangular solves by outer block (BSP_BLOCK_SOLVE=0: by panel)
-  bool tailInBatch = false;  // developer (BSP_TAIL_IN_BATCH=1): batches run the plan WITH the persistent tail (A/B record)
   bool potrfInTrsm = true;  // small multi-panel levels: potrf folded into the trsm launch (developer: BSP_POTRF_IN_TRSM=0)
   int64_t foldMaxTiles = 512;  // ... levels of at most this many row tiles x batch (developer: BSP_FOLD_MAX_TILES)
   bool splitK = true;       // split-K tile lists for small multi-panel levels (BSP_SPLIT_K=0: off)
-  unsigned gatherOverlapLds = 0;  // dynamic LDS of the overlapped chunks' launches (throttle; BSP_GATHER_OVERLAP_LDS)
-  bool gatherOverlap = false;  // gather chunks beside the dense chain (BSP_GATHER_OVERLAP=1; off: the plan is not chunked either)
   static constexpr int64_t splitKMaxWgs = 1024;  // ... launches of at most this many workgroups (a batch of 8: 2.26 = 2.26 ms at 1024, 2.48 at 4096)
   int subBatchMin = 16;     // batches of at least this many matrices are factored as concurrent sub-batches (BSP_SUB_BATCH_MIN; 0: never)
   int subBatchParts = 2;    // ... this many (BSP_SUB_BATCHES, at most 4, at least subBatchMin / 2 matrices each)
@@ -1464,11 +1457,7 @@ struct HipSymbolicCtx : SymbolicCtx {
   int sweepCapacity = 0;      // workgroups of a sweep launch that are resident at once (one per CU)
   size_t sweepMaxLds = 0;
   int sweepAttr[2] = {0, 0};  // per value size (8, 4): 0 not tried, 1 ready, -1 failed
-  struct RunCounters {
-    int64_t sweepLaunches = 0, sweepTimeouts = 0, splitListsUsed = 0, subBatchesEnqueued = 0,
-            lookaheadForks = 0, gatherChunksOverlapped = 0, tailLaunches = 0, sweepMfmaLaunches = 0, invReused = 0, solveWideLaunches = 0, potrfFoldedLevels = 0;
-    int64_t selinvLaunches = 0, selinvChunks = 0;
-  } counters;
+  HipRunCounters counters;  // (the two derived fields are filled in by hipBackendRunCounters)
   // a timed-out persistent launch (solve sweep, factor tail) is reported ONCE, by the next factor()
   // or solve() on this Solver; the persistent kernels are then retired for good
   void checkAsyncError() {
@@ -1666,21 +1655,12 @@ struct HipNumericCtx : NumericCtx<T> {
     // applies the rest from memory
     int extraApplied = 0;
     bool extraBroken = false;
-    // gather overlap: chunks each stream has already waited for (events of one stream complete in order)
-    const bool chunks = &levels == &plan.host.levels && !gatherChunkDone.empty();
-    int waitedExec = 0, waitedDue = 0, waitedSide = 0;
     hipEvent_t lastOpt = nullptr;  // the most recent optional lookahead launch (side stream)
-    auto waitChunk = [&](hipStream_t st, int& waited, int32_t chunk) {
-      if (!chunks || chunk <= waited || chunk >= (int32_t)gatherChunkDone.size()) return;
-      hipCHECK(hipStreamWaitEvent(st, gatherChunkDone[chunk], 0));
-      waited = chunk;
-    };
     for (size_t li = 0; li < levels.size(); li++) {
       const LevelRange& lr = levels[li];
       const unsigned nP = (unsigned)(lr.panelEnd - lr.panelBegin);
       const unsigned nT = (unsigned)(lr.trsmEnd - lr.trsmBegin);
       const bool direct = lr.directPanel >= 0;
-      waitChunk(sym.stream, waitedExec, lr.gatherNow);
       if (lr.tail) {
         if (lr.tail == 1) {
           // PERSISTENT TAIL (hip_tail_kernel.h): everything the lookahead streams still owe to these
@@ -1815,53 +1795,44 @@ struct HipNumericCtx : NumericCtx<T> {
         //  whose "now" tiles ran 3x faster alone than beside freshly started bulk tiles; with the
         //  deadline-ordered units the side stream is busy either way and the earlier fork wins)
         hipEvent_t fork = sym.eventFromPool();
+        const hipStream_t side = sym.sideStream();
         hipCHECK(hipEventRecord(fork, sym.stream));
-        hipCHECK(hipStreamWaitEvent(sym.sideStream(), fork, 0));
+        hipCHECK(hipStreamWaitEvent(side, fork, 0));
         sym.counters.lookaheadForks++;
         // first the tiles the next block's own update must wait for, then (event) the rest:
         // the side stream keeps running them while the chain goes on, and the next block's
         // deferred tiles queue up right behind
+        // (one auxiliary stream: the due units simply go ahead of the optional ones on it)
+        hipStream_t due = side;
+        unsigned dueLds = sym.bulkExtraLds;
         if (dueStream) {
           // due units on their own stream, beside the optional ones (both accumulate with atomics
           // where they can meet: hip_plan.cpp, pushUnit).  They must not overtake the optional
           // units forked two blocks ago, whose far columns are plain read-modify-write.
-          hipStream_t due = sym.dueSideStream();
+          due = sym.dueSideStream();
+          dueLds = sym.dueExtraLds;
           hipCHECK(hipStreamWaitEvent(due, fork, 0));
-          waitChunk(due, waitedDue, lr.gatherDue);
-          waitChunk(sym.sideStream(), waitedSide, lr.gatherOpt);
           if (lr.flushDue && lastOpt) hipCHECK(hipStreamWaitEvent(due, lastOpt, 0));
           const int64_t f2 = lr.optWaitLevel;
           if (f2 >= 0 && optDone[f2]) hipCHECK(hipStreamWaitEvent(due, optDone[f2], 0));
-          if (lr.defMid > lr.defBegin) {
-            timer.begin(kProfUpdate, due);
-            launchUpdate(plan, lr.defBegin, lr.defMid, ref, due, nullptr, 0, sym.dueExtraLds, sideMask);
-            timer.end();
-          }
-          defDone[li] = sym.eventFromPool();
-          hipCHECK(hipEventRecord(defDone[li], due));
-          if (lr.defEnd > lr.defMid) {
-            timer.begin(kProfUpdate, sym.sideStream());
-            launchUpdate(plan, lr.defMid, lr.defEnd, ref, sym.sideStream(), nullptr, 0, sym.bulkExtraLds, sideMask);
-            timer.end();
-            optDone[li] = sym.eventFromPool();
-            hipCHECK(hipEventRecord(optDone[li], sym.sideStream()));
-            lastOpt = optDone[li];
-          }
-          sideUsed = dueUsed = true;
-          return;
+          dueUsed = true;
         }
-        waitChunk(sym.sideStream(), waitedSide, std::max(lr.gatherDue, lr.gatherOpt));
         if (lr.defMid > lr.defBegin) {
-          timer.begin(kProfUpdate, sym.sideStream());
-          launchUpdate(plan, lr.defBegin, lr.defMid, ref, sym.sideStream(), nullptr, 0, sym.bulkExtraLds, sideMask);
+          timer.begin(kProfUpdate, due);
+          launchUpdate(plan, lr.defBegin, lr.defMid, ref, due, nullptr, 0, dueLds, sideMask);
           timer.end();
         }
         defDone[li] = sym.eventFromPool();
-        hipCHECK(hipEventRecord(defDone[li], sym.sideStream()));
+        hipCHECK(hipEventRecord(defDone[li], due));
         if (lr.defEnd > lr.defMid) {
-          timer.begin(kProfUpdate, sym.sideStream());
-          launchUpdate(plan, lr.defMid, lr.defEnd, ref, sym.sideStream(), nullptr, 0, sym.bulkExtraLds, sideMask);
+          timer.begin(kProfUpdate, side);
+          launchUpdate(plan, lr.defMid, lr.defEnd, ref, side, nullptr, 0, sym.bulkExtraLds, sideMask);
           timer.end();
+          if (dueStream) {
+            optDone[li] = sym.eventFromPool();
+            hipCHECK(hipEventRecord(optDone[li], side));
+            lastOpt = optDone[li];
+          }
         }
         sideUsed = true;
       };
@@ -1965,10 +1936,6 @@ struct HipNumericCtx : NumericCtx<T> {
       hipCHECK(hipEventRecord(join, sym.dueSideStream()));
       hipCHECK(hipStreamWaitEvent(sym.stream, join, 0));
     }
-    if (chunks) {  // (the last level waited for the last chunk already; a plan without levels did not)
-      waitChunk(sym.stream, waitedExec, (int32_t)gatherChunkDone.size() - 1);
-      gatherChunkDone.clear();
-    }
   }
 
   void launchElim(DevPlan& plan, const ElimRangePlan& er, hipk::DataRef<BT> ref,
@@ -2006,41 +1973,12 @@ struct HipNumericCtx : NumericCtx<T> {
     }
     if (er.useGather) {
       const int64_t nItems = er.itemEnd - er.itemBegin;
-      // (extraLds: overlapped chunks may be throttled to fewer workgroups per CU, BSP_GATHER_OVERLAP_LDS)
-      auto gatherRange = [&](int64_t b, int64_t e, hipStream_t st, unsigned extraLds = 0) {
-        if (e <= b) return;
-        timer.begin(kProfElimUpdate, st);
-        hipk::elimGatherMfma<BT><<<dim3((unsigned)((e - b + 3) / 4), gy), 256, extraLds, st>>>(
-            plan.elimItems.as<ElimGatherItem>() + b, plan.elimPairOffJ.as<uint32_t>(),
-            plan.elimPairOffI.as<uint32_t>(), ref, (int)(e - b));
+      if (nItems > 0) {
+        timer.begin(kProfElimUpdate);
+        hipk::elimGatherMfma<BT><<<dim3((unsigned)((nItems + 3) / 4), gy), 256, 0, sym.stream>>>(
+            plan.elimItems.as<ElimGatherItem>() + er.itemBegin, plan.elimPairOffJ.as<uint32_t>(),
+            plan.elimPairOffI.as<uint32_t>(), ref, (int)nItems);
         timer.end();
-      };
-      gatherChunkDone.clear();
-      if (!er.chunkItemPtr.empty()) {
-        // GATHER OVERLAP (hip_plan.h, ElimRangePlan::chunkItemPtr): chunk 0 here, the others on a
-        // stream of their own beside the dense chain, one event per chunk; launchLevels makes every
-        // dense launch wait for the chunk of the last column block it touches
-        const size_t nChunks = er.chunkItemPtr.size() - 1;
-        const bool overlap = er.overlapLump >= 0 && sym.gatherOverlap && lookaheadOn() &&
-                             plan.host.lookaheadPays(batchSize, sym.lookaheadMinFlops);
-        if (overlap) {
-          hipStream_t gs = sym.streams().batch[0];
-          hipEvent_t factored = sym.eventFromPool();
-          hipCHECK(hipEventRecord(factored, sym.stream));
-          hipCHECK(hipStreamWaitEvent(gs, factored, 0));
-          gatherRange(er.chunkItemPtr[0], er.chunkItemPtr[1], sym.stream);
-          gatherChunkDone.assign(nChunks, nullptr);
-          for (size_t c = 1; c < nChunks; c++) {
-            gatherRange(er.chunkItemPtr[c], er.chunkItemPtr[c + 1], gs, sym.gatherOverlapLds);
-            gatherChunkDone[c] = sym.eventFromPool();
-            hipCHECK(hipEventRecord(gatherChunkDone[c], gs));
-          }
-          sym.counters.gatherChunksOverlapped += (int64_t)nChunks - 1;
-        } else {
-          for (size_t c = 0; c < nChunks; c++) gatherRange(er.chunkItemPtr[c], er.chunkItemPtr[c + 1], sym.stream);
-        }
-      } else {
-        gatherRange(er.itemBegin, er.itemBegin + nItems, sym.stream);
       }
       const int64_t nWide = er.ldsEnd - er.ldsBegin;
       if (nWide > 0) {
@@ -2130,7 +2068,7 @@ struct HipNumericCtx : NumericCtx<T> {
   virtual void factorRange(T* data, int64_t startLump, int64_t upToLump) override {
     sym.checkAsyncError();
     DevPlan* planPtr = &sym.planFor(sym.sparseElimRanges, startLump, upToLump, /*tag=*/0);
-    if (batchSize > 1 && planPtr->host.hasTail && !sym.tailInBatch) {
+    if (batchSize > 1 && planPtr->host.hasTail) {
       planPtr = &sym.planFor(sym.sparseElimRanges, startLump, upToLump, /*tag=*/2);
     }
     DevPlan& plan = *planPtr;
@@ -2290,9 +2228,6 @@ struct HipNumericCtx : NumericCtx<T> {
   HipSymbolicCtx& sym;
   int batchSize;
   int subBatchBase = 0, subBatchTotal = 0;  // enqueueFactor: the sub-batch being enqueued
-  // gather overlap: events of the gather chunks of THIS factor call that run beside the dense chain
-  // (launchElim -> launchLevels; [0] is null: chunk 0 runs on the execution stream)
-  vector<hipEvent_t> gatherChunkDone;
   int64_t tempBufSize = 0;
   DevBuf temp, spanToChainOffset;  // per-op boundary only (saveSyrkGemm / prepareAssemble)
   vector<std::unique_ptr<DevPlan>> opPlans;
@@ -3077,20 +3012,7 @@ int hipBackendReadSweepTrace(SymbolicCtx& sym, long long* out, int maxBlocks) {
 HipRunCounters hipBackendRunCounters(SymbolicCtx& sym) {
   HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
   BASPACHO_CHECK_NOTNULL(h);
-  HipRunCounters c;
-  c.sweepLaunches = h->counters.sweepLaunches;
-  c.sweepTimeouts = h->counters.sweepTimeouts;
-  c.splitListsUsed = h->counters.splitListsUsed;
-  c.subBatchesEnqueued = h->counters.subBatchesEnqueued;
-  c.lookaheadForks = h->counters.lookaheadForks;
-  c.gatherChunksOverlapped = h->counters.gatherChunksOverlapped;
-  c.tailLaunches = h->counters.tailLaunches;
-  c.sweepMfmaLaunches = h->counters.sweepMfmaLaunches;
-  c.solveWideLaunches = h->counters.solveWideLaunches;
-  c.invReused = h->counters.invReused;
-  c.potrfFoldedLevels = h->counters.potrfFoldedLevels;
-  c.selinvLaunches = h->counters.selinvLaunches;
-  c.selinvChunks = h->counters.selinvChunks;
+  HipRunCounters c = h->counters;
   c.sweepsRetired = h->sweepBroken ? 1 : 0;
   c.sweepErrorPending = (h->sweepHostErr && *reinterpret_cast<volatile unsigned*>(h->sweepHostErr)) ? 1 : 0;
   return c;

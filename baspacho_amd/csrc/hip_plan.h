@@ -152,9 +152,6 @@ struct LevelRange {
   // due-stream mode: level whose OPTIONAL lookahead units (forked two outer blocks earlier: plain
   // read-modify-write on far columns) must be complete before this level's due units start; -1
   int64_t optWaitLevel = -1;
-  // gather overlap (ElimRangePlan::chunkItemPtr): chunk that must be complete before this level's
-  // own launches / its due lookahead units / its optional ones; -1: none
-  int32_t gatherNow = -1, gatherDue = -1, gatherOpt = -1;
   // persistent tail: 1 = this level's panel is the first of a tail (the launch factors tailPanels
   // panels from here, after a join with the lookahead streams), 2 = a panel inside a tail (nothing to launch)
   int32_t tail = 0, tailPanels = 0;
@@ -187,9 +184,6 @@ constexpr int kGatherMaxElems = 256;   // rows*cols handled per wave (4 per lane
 // drained WAS the kernel's tail: BAL-871 1.73 ms at 2048, 1.49 at 512, 1.43 at 128, 1.42 at 64
 // (BSP_GATHER_MAX_PAIRS overrides; 2048+ restores the atomic-free, deterministic form).
 constexpr int kGatherMaxPairs = 64;  // default of HipPlanOptions::gatherMaxPairs (round 4: 128 -> 64, -0.05 ms on BAL-871)
-constexpr uint32_t kGatherChunkElems = 0xffffffffu;  // optional slicing of the source columns into
-                                                     // cache-sized passes: measured 2x SLOWER on
-                                                     // BAL-871 (more items + atomics), so disabled
 
 // One eliminated lump as the small-lump factor kernel wants it: everything behind one 16-byte load
 // instead of a chain of dependent skeleton lookups (the column is one dense (n + rows) x n block:
@@ -215,16 +209,6 @@ struct ElimRangePlan {
                                       // elements (3x3 parameters): 7 items per wave
   int64_t ldsBegin = 0, ldsEnd = 0;   // items wider or taller than 16: LDS-staged kernel (K2g);
                                       // [itemBegin, itemEnd) go to the MFMA kernel (K2m)
-  // OVERLAP WITH THE DENSE PHASE (round 6).  When every target of the range's gather lies in ONE wide
-  // lump that is the whole dense part of the plan (a Schur complement whose cameras merged into one
-  // lump), the MFMA items are grouped into CHUNKS of target column blocks (kOuterWidth columns each),
-  // first columns first: chunk 0 runs on the execution stream, the others on a stream of their own
-  // BESIDE the dense chain, and every dense launch waits (event) for the chunk of the last column
-  // block it touches -- LevelRange::gatherNow / gatherDue / gatherOpt.  No atomics: a target block is
-  // never worked on from both sides.
-  std::vector<int64_t> chunkItemPtr;     // [chunks + 1], into elimItems; empty: one launch
-  std::vector<int32_t> chunkOfColBlock;  // chunk of every outer column block of the target lump
-  int64_t overlapLump = -1;
 };
 
 // Every switch the plan builder honours, resolved ONCE when a SymbolicCtx is created (from
@@ -237,10 +221,6 @@ struct HipPlanOptions {
   bool planTiming = false;    // BSP_TIMING: stderr laps of the gather plan
   int32_t gatherMaxPairs = kGatherMaxPairs;  // BSP_GATHER_MAX_PAIRS
   double bulkAhead = 0.8;     // BSP_BULK_AHEAD (round 4: 0.6 -> 0.8, -0.04 ms on BAL-871; profiles/r04_ab_plan_knobs.txt)
-  bool gatherOverlap = false; // BSP_GATHER_OVERLAP=1: gather chunks beside the dense chain (measured: no gain, profiles/r06_ab_gather_overlap.txt)
-  int32_t overlapFirst = 2;   // column blocks in chunk 0 (BSP_GATHER_OVERLAP_FIRST)
-  int32_t overlapStep = 3;    // ... in every later chunk (BSP_GATHER_OVERLAP_STEP)
-  int32_t overlapMinBlocks = 8;  // narrowest target lump, in column blocks
   // PERSISTENT TAIL (hip_tail_kernel.h): the last tailBlocks outer blocks of a lump that has nothing
   // below it and is at least tailMinBlocks blocks wide are factored by ONE flag-synchronised launch
   // (BSP_TAIL_BLOCKS; 0: the level schedule to the end)
@@ -255,7 +235,7 @@ struct HipPlanOptions {
   bool tailWholeNarrow = true;  // a narrow root lump that follows other levels: the whole lump (developer: BSP_TAIL_WHOLE=0)
   int32_t tailNarrowMin = 2;  // (developer: BSP_TAIL_NARROW_MIN; tailBlocks = 0 switches every tail off)
   int32_t solveSortWindow = 16;  // lumps per sorting window of the backward elimination lists (= a workgroup; developer: BSP_SOLVE_SORT_WINDOW)
-  void applyDeveloperEnv();  // BSP_TIMING, chunk sizes of the gather-overlap experiment
+  void applyDeveloperEnv();  // BSP_TIMING and the fields marked "developer" above
 };
 
 struct HipPlanHost {

@@ -56,7 +56,7 @@ typedef struct bsp_hip_options {
   int32_t due_stream;        /* 0: one auxiliary stream */
   int32_t split_k;           /* 0: no split-K tile lists */
   int32_t gather_max_pairs;  /* pairs per sparse-elimination gather item */
-  int32_t gather_overlap;    /* 1: gather chunks beside the dense chain (measured: no gain) */
+  int32_t gather_overlap;    /* ignored (kept for ABI stability) */
   int32_t sub_batch_min;     /* batches of at least this many as concurrent sub-batches; 0: never */
   int32_t sub_batches;       /* ... this many parts */
   int32_t tail_blocks;       /* outer blocks of a wide root lump for the persistent tail launch; 0: off */
@@ -648,7 +648,7 @@ typedef struct bsp_run_counters {
   int64_t lookahead_forks;      /* lookahead launches handed to the auxiliary streams */
   int64_t sweeps_retired;       /* 1: a time-out retired the sweeps of this solver */
   int64_t sweep_error_pending;  /* 1: a time-out has been raised and not been reported yet */
-  int64_t gather_chunks_overlapped; /* sparse-elimination gather chunks launched beside the dense chain */
+  int64_t gather_chunks_overlapped; /* always 0 (kept for ABI stability) */
   int64_t tail_launches;        /* persistent tail launches (csrc/hip_tail_kernel.h) */
   int64_t sweep_mfma_launches;  /* ... of sweep_launches: the matrix-core form (several right-hand sides) */
   int64_t solve_wide_launches;  /* backward elimination passes with the right-hand sides across the lanes */

@@ -71,7 +71,7 @@ def lump_over_lump(top, below, top_span=8, below_span=7, hip_options=None):
     return sol
 
 
-def affine_plane_cameras(p, pt_size, cam_size, extra=0, extra_size=7, hip_options=None):
+def affine_plane_cameras(p, pt_size, cam_size, extra=0, extra_size=7):
     """bundle-adjustment shape: p * p cameras (the points of the affine plane over Z_p) and one point
     per line of that plane (p * p + p points, eliminated as the range [0, points)), seen by the p
     cameras on its line.  Every pair of cameras shares exactly one point, so the cameras form one dense
@@ -88,7 +88,7 @@ def affine_plane_cameras(p, pt_size, cam_size, extra=0, extra_size=7, hip_option
     cols += [set(range(q, n)) for q in range(extra0, n)]
     sizes = np.concatenate([np.full(P, pt_size, dtype=np.int64), np.full(C, cam_size, dtype=np.int64),
                             np.full(extra, extra_size, dtype=np.int64)])
-    return B.create_solver(B.Settings(hipOptions=hip_options), sizes, T.columns_to_structure(cols), [0, P],
+    return B.create_solver(B.Settings(), sizes, T.columns_to_structure(cols), [0, P],
                            list(range(extra0, n)))
 
 

@@ -35,6 +35,36 @@ def test_cpu_backends_are_refused():
     B.create_solver(B.Settings(backend=B.BackendCuda), ps, ss)  # alias of the HIP engine
 
 
+def test_retired_option_keeps_its_slot_and_is_not_an_option():
+    """gather_overlap / gather_chunks_overlapped are ABI slots only: the two mirrored structures keep
+    the layout of the C header, the defaults still fill every integer slot, and the option key is
+    refused like any unknown one"""
+    import ctypes
+    hdr = open(os.path.join(ROOT, "include", "baspacho_amd.h")).read()
+
+    def fields(struct):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), hdr, re.S).group(1)
+        return re.findall(r"^\s*(int32_t|int64_t|double)\s+(\w+);", body, re.M)
+
+    opts, ctrs = fields("bsp_hip_options"), fields("bsp_run_counters")
+    ints = [n for t, n in opts if t == "int32_t"]
+    assert [t for t, _ in opts] == ["int32_t"] * 17 + ["double"] * 3, opts
+    assert [t for t, _ in ctrs] == ["int64_t"] * 15, ctrs
+    assert "gather_overlap" in ints and "gather_chunks_overlapped" in [n for _, n in ctrs]
+    assert [n for n, _ in B._CHipOptions._fields_] == [n for _, n in opts]
+    assert [n for n, _ in B._CRunCounters._fields_] == [n for _, n in ctrs]
+    # 17 int32 = 68 bytes, padded to the doubles' alignment
+    assert ctypes.sizeof(B._CHipOptions) == (17 * 4 + 7) // 8 * 8 + 3 * 8
+    assert ctypes.sizeof(B._CRunCounters) == 15 * 8
+    ho = B._CHipOptions()
+    _lib.load().bsp_hip_options_default(ctypes.byref(ho))
+    assert [getattr(ho, n) for n in ints] == [-1] * 17
+    sol, ps, ss = solver_random(57)
+    with pytest.raises(ValueError, match="unknown backend option 'gather_overlap'"):
+        B.create_solver(B.Settings(hipOptions={"gather_overlap": 1}), ps, ss)
+    assert "gather_chunks_overlapped" not in sol.runCounters()
+
+
 def test_accessor_matches_skeleton():
     """AccessorTest: blockOffset/diagBlockOffset through the permutation, incl. flipped blocks"""
     sol, ps, ss = solver_random(63)

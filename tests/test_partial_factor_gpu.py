@@ -7,8 +7,8 @@ cross-cut updates that leave the Schur complement S = A22 - L21 L21^T in the tra
 trailing entries that no cross-cut product reaches bitwise unchanged), factorFrom on top of it against
 the full factor and one solve, and factorFrom alone on data whose leading columns are NaN against the
 Cholesky factor of A22.  The structures take the plan's range-dependent paths: the persistent tail,
-lookahead, split-K, folded potrf, batches and sub-batches, the gather overlap, elimination ranges and
-incomplete fill; the run counters assert that each path was taken."""
+lookahead, split-K, folded potrf, batches and sub-batches, one wide camera lump fed by the MFMA gather,
+elimination ranges and incomplete fill; the run counters assert that each switched path was taken."""
 import numpy as np
 import pytest
 
@@ -238,44 +238,38 @@ def test_blocks_over_separator_split(monkeypatch, switch, on, dtype):
             k.check_factor(d.cpu().numpy(), (env, on, bs, q))
 
 
-# ---- gather overlap ---------------------------------------------------------------------------
-
-GATHER = {"gather_overlap": 1}
-
+# ---- one wide camera lump behind the MFMA gather ------------------------------------------------
 
 @pytest.mark.parametrize("dtype", DTYPES)
-def test_gather_overlap_full_factor(dtype):
-    """121 cameras of 16 (one dense lump of 8 outer blocks, every target block an MFMA gather item):
-    factor() overlaps the gather chunks with the dense chain"""
-    sol = affine_plane_cameras(11, 3, 16, hip_options=GATHER)
+def test_camera_lump_full_factor(dtype):
+    """121 cameras of 16: one dense lump of 8 outer blocks, every target block one of more than 4096
+    MFMA gather items"""
+    sol = affine_plane_cameras(11, 3, 16)
     assert sol.numLumps() == int(sol.sparseEliminationRanges()[-1]) + 1
     kf = known_factor_data(sol, 12, dtype)
     dev = to_dev(kf.data)
-    took = counter_delta(sol, "gather_chunks_overlapped", lambda: sol.factor(dev))
-    assert took > 0, took
-    kf.check_factor(dev.cpu().numpy(), "gather overlap, factor")
-    _solve_check(kf, dev, 2, 3, "gather overlap")
+    sol.factor(dev)
+    kf.check_factor(dev.cpu().numpy(), "camera lump, factor")
+    _solve_check(kf, dev, 2, 3, "camera lump")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-def test_gather_overlap_up_to_camera_lump(dtype):
-    """the same cameras with dense lumps behind them: the full factor's plan has more than one dense
-    lump and declines the overlap; factorUpTo(camera lump + 1) has exactly one and takes it"""
-    sol = affine_plane_cameras(11, 3, 16, extra=10, hip_options=GATHER)
+def test_camera_lump_up_to_and_from(dtype):
+    """the same cameras with dense lumps behind them: the full factor, then factorUpTo(camera lump + 1),
+    whose plan ends with the camera lump, and factorFrom on top of it"""
+    sol = affine_plane_cameras(11, 3, 16, extra=10)
     cams = int(sol.sparseEliminationRanges()[-1])
     assert sol.numLumps() >= cams + 2
     span = _span_of_lump(sol, cams + 1)
     kf = known_factor_data(sol, 13, dtype)
     dev = to_dev(kf.data)
-    took = counter_delta(sol, "gather_chunks_overlapped", lambda: sol.factor(dev))
-    assert took == 0, took
-    kf.check_factor(dev.cpu().numpy(), "gather overlap declined, factor")
+    sol.factor(dev)
+    kf.check_factor(dev.cpu().numpy(), "camera lump and trailing lumps, factor")
     dev = to_dev(kf.data)
-    took = counter_delta(sol, "gather_chunks_overlapped", lambda: sol.factorUpTo(dev, span))
-    assert took > 0, took
-    kf.check_partial(dev.cpu().numpy(), _bar(sol, span), "gather overlap, factorUpTo")
+    sol.factorUpTo(dev, span)
+    kf.check_partial(dev.cpu().numpy(), _bar(sol, span), "camera lump, factorUpTo")
     sol.factorFrom(dev, span)
-    kf.check_factor(dev.cpu().numpy(), "gather overlap, factorFrom")
+    kf.check_factor(dev.cpu().numpy(), "camera lump, factorFrom")
 
 
 # ---- batches ----------------------------------------------------------------------------------
