@@ -54,7 +54,7 @@ def load():
     lib.bsp_last_error.restype = ctypes.c_char_p
     lib.bsp_version.restype = ctypes.c_char_p
     for name in ["bsp_order", "bsp_data_size", "bsp_num_spans", "bsp_num_lumps",
-                 "bsp_can_factor_up_to_span", "bsp_span_vector_offset"]:
+                 "bsp_can_factor_up_to_span", "bsp_span_vector_offset", "bsp_bal_sum_scratch_len"]:
         getattr(lib, name).restype = ctypes.c_int64
     lib.bsp_factor_flops.restype = ctypes.c_double
     _lib = lib

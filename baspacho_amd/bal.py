@@ -280,15 +280,86 @@ def lm_optimize(prob, solver, max_iters=50, lam=1e-5, log=None):
     return prob, hist
 
 
+def lm_optimize_device(prob, solver, max_iters=50, lam=1e-5, loss=None, log=None):
+    """lm_optimize with the whole iteration resident on the device: one DevicePipeline for the run, H, g,
+    step, rho and the sum scratch reused, the candidate retracted (apply_step) and its cost evaluated
+    (cost) by device kernels, and ONE device-to-host read per iteration, the 3-element tensor
+    [cost, new_cost, 0.5 g.step] every decision is taken from.  Same lambda schedule, acceptance and
+    stopping rules as lm_optimize, line for line.  loss: None, ("huber", a) or ("cauchy", a) -- the robust
+    loss of the reference's optimizer (examples/SoftLoss.h; H += rho' J^T J, g += rho' J^T r, cost =
+    rho / 2); the costs in the history are then robust costs.  `solver` must have 6-wide camera blocks.
+    Everything runs on the solver's stream.  Returns (problem, cost history)."""
+    import torch
+    pipe = DevicePipeline(prob, solver, param="se3", loss=loss)
+    dev, n = pipe.res.device, solver.order()
+    H = torch.empty(solver.dataSize(), dtype=torch.float64, device=dev)
+    g = torch.empty(n, dtype=torch.float64, device=dev)
+    step = torch.empty_like(g)
+    trip = torch.empty(3, dtype=torch.float64, device=dev)   # cost, new_cost, 0.5 g.step
+    hist = []
+    last_failed = last_ok = last_good = 0
+    with torch.cuda.stream(solver._torch_stream(dev)):
+        for i in range(max_iters):
+            pipe.linearize()
+            pipe.apply_loss()
+            pipe.cost_linearized(out=trip[0:1])
+            H.zero_()
+            g.zero_()
+            pipe.fill_hessian(H, g, lam)
+            step.copy_(g)
+            solver.factor(H)
+            solver.solve(H, step, n, 1)
+            cams, pts = pipe.apply_step(step)
+            pipe.cost(cams, pts, out=trip[1:2])
+            torch.dot(g, step, out=trip[2])
+            trip[2].mul_(0.5)
+            cost, new_cost, model_red = trip.tolist()   # the iteration's only device-to-host read
+            bad, good = new_cost > cost, new_cost < cost * 0.999
+            hist.append((cost, new_cost, lam))
+            if log:
+                log("[%d] cost %.3e -> %.3e lambda %.1e" % (i, cost, new_cost, lam))
+            if bad:
+                last_failed = i
+                if lam > 1e8 or i > last_ok + 15:
+                    break
+                lam *= 3
+                continue
+            pipe.set_params(cams, pts)
+            last_ok = i
+            if good:
+                last_good = i
+            rel_red = (cost - new_cost) / model_red if model_red != 0 else 0.0
+            if rel_red > 0.6:
+                lam *= 0.6
+            elif rel_red < 0.4:
+                lam *= 1.3
+            if i >= last_good + 3 and i >= last_failed + 3:
+                break
+    return pipe.to_problem(), hist
+
+
+LOSS_KINDS = {"huber": 1, "cauchy": 2}   # bsp_bal_loss_f64's kind; 0 = trivial (loss=None)
+
+
 class DevicePipeline:
     """problem data resident on the GPU + the two device stages of a Gauss-Newton / LM iteration.
     param = "bal9": cameras are the 9 parameters of a BAL file (BAL_bench's block size, derivatives
     by dual numbers); param = "se3": the reference optimizer's parameterisation (6-wide SE3-tangent
-    camera blocks, calibration fixed, closed-form Jacobians of BaAtLarge.h:56-150)"""
+    camera blocks, calibration fixed, closed-form Jacobians of BaAtLarge.h:56-150).
+    loss = None, ("huber", a) or ("cauchy", a): the robust loss apply_loss() and cost() use
+    (examples/SoftLoss.h); None leaves every other method as it is without one."""
 
-    def __init__(self, prob, solver, device="cuda", param="bal9"):
+    def __init__(self, prob, solver, device="cuda", param="bal9", loss=None):
         import torch
         assert param in ("bal9", "se3")
+        if loss is None:
+            self.loss_kind, self.loss_a = 0, 1.0
+        else:
+            name, a = loss
+            if name not in LOSS_KINDS:
+                raise ValueError("loss must be None, ('huber', a) or ('cauchy', a), got %r" % (loss,))
+            self.loss_kind, self.loss_a = LOSS_KINDS[name], float(a)
+        self.rho = self._cand_res = self._cand_rho = self._sum_scratch = None
         self.param = param
         self.cam_size = 9 if param == "bal9" else 6
         self.prob, self.solver = prob, solver
@@ -341,3 +412,90 @@ class DevicePipeline:
             fn = self.lib.bsp_bal_fill_hessian_f32 if f32 else self.lib.bsp_bal_fill_hessian_f64
             _check(fn(*head, self._p(dbg), self._stream(stream)))
         return data
+
+    # ---- the rest of an LM iteration (bsp_bal_residuals / loss / sum / apply_step); like the two stages
+    # above, every launch goes to the stream _stream() resolves and nothing synchronises the host
+    def _empty(self, n):
+        import torch
+        return torch.empty(n, dtype=torch.float64, device=self.res.device)
+
+    def residuals(self, cams=None, pts=None, out=None, stream=None):
+        """the residuals alone (2 per observation) at `cams` / `pts`, the pipeline's own by default, into
+        `out` (a new tensor by default): what linearize() leaves in res, without the Jacobians"""
+        from . import _check
+        out = self._empty(2 * self.n_obs) if out is None else out
+        fn = self.lib.bsp_bal_residuals_f64 if self.param == "bal9" else self.lib.bsp_bal_residuals_se3_f64
+        _check(fn(
+            ctypes.c_int64(self.n_obs), self._p(self.obs_cam), self._p(self.obs_pt), self._p(self.obs_xy),
+            self._p(self.cams if cams is None else cams), self._p(self.pts if pts is None else pts),
+            self._p(out), self._stream(stream)))
+        return out
+
+    def _loss(self, res, Jc, Jp, rho, stream):
+        from . import _check
+        _check(self.lib.bsp_bal_loss_f64(
+            ctypes.c_int64(self.n_obs), ctypes.c_int32(self.cam_size), ctypes.c_int32(self.loss_kind),
+            ctypes.c_double(self.loss_a), self._p(res), self._p(Jc), self._p(Jp), self._p(rho),
+            self._stream(stream)))
+        return rho
+
+    def _sum(self, x, scale, out, stream):
+        import torch
+        from . import _check
+        n = x.numel()
+        need = int(self.lib.bsp_bal_sum_scratch_len(ctypes.c_int64(n)))
+        if self._sum_scratch is None or self._sum_scratch.numel() < need:
+            self._sum_scratch = self._empty(need)
+        out = torch.empty((), dtype=torch.float64, device=x.device) if out is None else out
+        _check(self.lib.bsp_bal_sum_f64(ctypes.c_int64(n), self._p(x), ctypes.c_double(scale),
+                                        self._p(self._sum_scratch), self._p(out), self._stream(stream)))
+        return out.reshape(())
+
+    def apply_loss(self, stream=None):
+        """after linearize(): rho (one per observation) of the squared residuals into self.rho and, for a
+        robust loss, res / Jc / Jp scaled in place by sqrt(rho') so that fill_hessian accumulates
+        rho' J^T J and rho' J^T r (observations with rho' == 1 are not rewritten)"""
+        if self.rho is None or self.rho.numel() != self.n_obs:
+            self.rho = self._empty(self.n_obs)
+        return self._loss(self.res, self.Jc, self.Jp, self.rho, stream)
+
+    def cost_linearized(self, out=None, stream=None):
+        """0.5 * sum of self.rho (apply_loss), a 0-dim device tensor (or `out`, one element)"""
+        return self._sum(self.rho, 0.5, out, stream)
+
+    def cost(self, cams=None, pts=None, out=None, stream=None):
+        """0.5 * sum rho(|r|^2) at `cams` / `pts` (the pipeline's own by default) from the residual-only
+        kernel (computeCost, BaAtLargeOptimizer.cpp:54-63, with the loss): a 0-dim device tensor (or
+        `out`, one element).  res / Jc / Jp / rho of the linearisation are left alone."""
+        if self._cand_res is None or self._cand_res.numel() != 2 * self.n_obs:
+            self._cand_res, self._cand_rho = self._empty(2 * self.n_obs), self._empty(self.n_obs)
+        self.residuals(cams, pts, out=self._cand_res, stream=stream)
+        self._loss(self._cand_res, None, None, self._cand_rho, stream)
+        return self._sum(self._cand_rho, 0.5, out, stream)
+
+    def apply_step(self, step, stream=None):
+        """applyStep (BaAtLargeOptimizer.cpp:173-184) of `step` (the solver's internal order: what
+        solve() leaves in the gradient buffer) as NEW tensors (cams, pts); the pipeline's own parameters
+        stay, so rejecting the step costs nothing.  bal9: parameters minus step; se3: points minus step,
+        T_W_C <- exp(-step) T_W_C (rotation vector of length <= pi), calibration copied.  (With a side
+        stream on the solver, call under torch.cuda.stream(...) of that stream, as for any tensor that is
+        allocated here and used there.)"""
+        import torch
+        from . import _check
+        cams, pts = torch.empty_like(self.cams), torch.empty_like(self.pts)
+        fn = self.lib.bsp_bal_apply_step_f64 if self.param == "bal9" else self.lib.bsp_bal_apply_step_se3_f64
+        _check(fn(self.solver._h, ctypes.c_int64(self.prob.num_pts), ctypes.c_int64(self.prob.num_cams),
+                  self._p(self.cams), self._p(self.pts), self._p(step), self._p(cams), self._p(pts),
+                  self._stream(stream)))
+        return cams, pts
+
+    def set_params(self, cams, pts):
+        """make (cams, pts) -- device tensors, e.g. what apply_step returned -- the pipeline's parameters"""
+        assert cams.numel() == self.cams.numel() and pts.numel() == self.pts.numel()
+        self.cams, self.pts = cams, pts
+
+    def to_problem(self):
+        """the pipeline's parameters downloaded into a BalProblem (waits for the solver's stream)"""
+        self.solver._torch_stream(self.cams.device).synchronize()
+        return BalProblem(self.cams.cpu().numpy(), self.pts.cpu().numpy(), self.prob.obs_cam, self.prob.obs_pt,
+                          self.prob.obs_xy)

@@ -30,4 +30,47 @@ void balFillHessian(const PermutedCoalescedAccessor& acc, int camSize, int64_t n
                     const double* Jp, const double* res, T lambda, T* data, T* grad, int64_t* dbg,
                     void* stream);
 
+// ---- the rest of a Levenberg-Marquardt iteration ("LM step on the device").
+// All pointers are device memory, everything is fp64; nothing here uses atomics, synchronises the host
+// or allocates, and every launch goes to `stream`.
+
+// the residuals alone, res[2 nObs], in plain doubles: what balLinearize / balLinearizeSe3 write to res
+// (the SE3 form with the same behind-the-camera rule: camPt.z > 0.01 gives exactly (25, 0))
+void balResiduals(int64_t numObs, const int64_t* obsCam, const int64_t* obsPt, const double* obsXy,
+                  const double* cams, const double* pts, double* res, void* stream);
+void balResidualsSe3(int64_t numObs, const int64_t* obsCam, const int64_t* obsPt, const double* obsXy,
+                     const double* cams, const double* pts, double* res, void* stream);
+
+// Robust loss (examples/SoftLoss.h jet2, examples/Optimizer.h computeSingleGradHess): per observation
+// s = r0^2 + r1^2, rho[o] = rho(s), w = rho'(s).
+//   kind 0 trivial: (s, 1);  1 Huber: s > a^2 ? (2 a sqrt(s) - a^2, a / sqrt(s)) : (s, 1);
+//   2 Cauchy: (a^2 log1p(s / a^2), 1 / (1 + s / a^2))
+// With Jc and Jp given (both or neither), the observation's 2 residuals and its 2 x camSize and 2 x 3
+// Jacobian rows are multiplied in place by sqrt(w), so that balFillHessian accumulates w J^T J and
+// w J^T r (no second-order term, as in the reference); the words of an observation with w == 1 are not
+// written.  With Jc = Jp = NULL only rho is written (res is read only).  Throws, before any launch, for
+// an unknown kind or an `a` that is not finite and positive.
+void balLoss(int64_t numObs, int camSize, int kind, double a, double* res, double* Jc, double* Jp,
+             double* rho, void* stream);
+
+// out[0] = scale * sum_{i < n} x[i] in a fixed order (bitwise reproducible), +0.0 for n == 0.
+// scratch: balSumScratchLen(n) = ceil(n / 2048) doubles.  Order: chunk b = x[2048 b, 2048 (b + 1));
+// thread sums T[t] = ((0 + x[2048 b + t]) + x[2048 b + 256 + t]) + .. (8 terms, those below n); fold
+// for s = 128, 64, .. 1: T[t] += T[t + s] for t < s; part[b] = T[0].  Then the same with
+// T[t] = ((0 + part[t]) + part[t + 256]) + .. and out[0] = scale * T[0].
+int64_t balSumScratchLen(int64_t n);
+void balSum(int64_t n, const double* x, double scale, double* scratch, double* out, void* stream);
+
+// applyStep of the reference's optimizer (BaAtLargeOptimizer.cpp:173-184), out of place: camsOut /
+// ptsOut must not overlap cams / pts / step.  `step` is in the solver's internal order (what solve()
+// leaves in the gradient buffer); parameter p's slice starts at acc.paramStart(p), points first, cameras
+// after.  ptsOut = pts - step.  balApplyStep: all 9 camera parameters minus their slice.
+// balApplyStepSe3: T <- exp(-step) T with step = (u, w), translation first; rotations composed as unit
+// quaternions and returned as an axis-angle vector with |w| <= pi; (f, k1, k2) copied.
+void balApplyStep(const PermutedCoalescedAccessor& acc, int64_t numPts, int64_t numCams, const double* cams,
+                  const double* pts, const double* step, double* camsOut, double* ptsOut, void* stream);
+void balApplyStepSe3(const PermutedCoalescedAccessor& acc, int64_t numPts, int64_t numCams,
+                     const double* cams, const double* pts, const double* step, double* camsOut,
+                     double* ptsOut, void* stream);
+
 }  // namespace BaSpaCho

@@ -9,6 +9,7 @@
 // derivatives come from forward-mode dual numbers, so there is no hand-derived Jacobian to get wrong.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -352,7 +353,348 @@ __global__ __launch_bounds__(256) void balDampKernel(PermutedCoalescedAccessor a
   }
 }
 
+// ---- the rest of a Levenberg-Marquardt iteration: candidate cost, robust loss, retraction ----------
+// (conventions, summation order, tolerances and resource usage: DESIGN.md section 9, "LM step on the
+//  device").  None of these kernels uses atomics; every sum runs in a fixed order.
+
+// Residual of the 9-parameter camera in plain doubles: reproject() without its 12 dual parts, through
+// the same rotationCoefficients (no w / theta).
+__global__ __launch_bounds__(256) void balResidualsKernel(int64_t numObs, const int64_t* obsCam,
+                                                          const int64_t* obsPt, const double* obsXy,
+                                                          const double* cams, const double* pts,
+                                                          double* res) {
+  const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= numObs) return;
+  const double* cam = cams + 9 * obsCam[o];
+  const double* X = pts + 3 * obsPt[o];
+  const double w[3] = {cam[0], cam[1], cam[2]};
+  double a, b, da, db;
+  rotationCoefficients(w[0] * w[0] + w[1] * w[1] + w[2] * w[2], a, b, da, db);
+  const double wX[3] = {w[1] * X[2] - w[2] * X[1], w[2] * X[0] - w[0] * X[2], w[0] * X[1] - w[1] * X[0]};
+  const double wwX[3] = {w[1] * wX[2] - w[2] * wX[1], w[2] * wX[0] - w[0] * wX[2],
+                         w[0] * wX[1] - w[1] * wX[0]};
+  double P[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) P[i] = X[i] + a * wX[i] + b * wwX[i] + cam[3 + i];
+  const double inv = 1.0 / P[2], px = -P[0] * inv, py = -P[1] * inv;
+  const double r2 = px * px + py * py;
+  const double fd = cam[6] * (1.0 + r2 * (cam[7] + cam[8] * r2));
+  res[2 * o] = fd * px - obsXy[2 * o];
+  res[2 * o + 1] = fd * py - obsXy[2 * o + 1];
+}
+
+// Residual of the SE3 parameterisation: the residual part of balLinearizeSe3Kernel, statement for
+// statement (same rodriguesMatrix, same behind-the-camera rule), so that the cost of a candidate and the
+// cost at a linearisation point are the same function of the parameters.
+__global__ __launch_bounds__(256) void balResidualsSe3Kernel(int64_t numObs, const int64_t* obsCam,
+                                                             const int64_t* obsPt, const double* obsXy,
+                                                             const double* cams, const double* pts,
+                                                             double* res) {
+  const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= numObs) return;
+  const double* cam = cams + 9 * obsCam[o];
+  const double* X = pts + 3 * obsPt[o];
+  double R[3][3];
+  rodriguesMatrix(cam, R);
+  double P[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) P[i] = R[i][0] * X[0] + R[i][1] * X[1] + R[i][2] * X[2] + cam[3 + i];
+  if (P[2] > 0.01) {
+    res[2 * o] = 25.0;
+    res[2 * o + 1] = 0.0;
+    return;
+  }
+  const double f = cam[6], k1 = cam[7], k2 = cam[8];
+  const double p0 = -P[0] / P[2], p1 = -P[1] / P[2];
+  const double sq = p0 * p0 + p1 * p1;
+  const double r = 1.0 + (k1 + k2 * sq) * sq;
+  res[2 * o] = f * r * p0 - obsXy[2 * o];
+  res[2 * o + 1] = f * r * p1 - obsXy[2 * o + 1];
+}
+
+// Robust loss (examples/SoftLoss.h: jet2 of TrivialLoss / HuberLoss / CauchyLoss, applied as in
+// examples/Optimizer.h computeSingleGradHess).  A workgroup owns kBalLossTile consecutive observations.
+// Pass 1, one thread per observation: s = |r|^2, rho[o] = rho(s), sqrt(rho'(s)) into LDS.  Pass 2: the
+// tile's words of Jc, Jp and res are walked flat across the lanes (word e belongs to observation
+// e / wordsPerObs of the tile), so consecutive lanes store consecutive words; a word whose weight is
+// exactly 1 is not stored at all.  res is read in pass 1 and rewritten in pass 2 by the same workgroup
+// only, with a barrier in between.
+constexpr int kBalLossTile = 256;
+template <int CS>  // camera block width, 9 or 6
+__global__ __launch_bounds__(kBalLossTile) void balLossKernel(int64_t numObs, int kind, double a,
+                                                              double* res, double* Jc, double* Jp,
+                                                              double* rho) {
+  __shared__ double sw[kBalLossTile];
+  const int tid = threadIdx.x;
+  const int64_t o0 = (int64_t)blockIdx.x * kBalLossTile, o = o0 + tid;
+  double sq = 1.0;
+  if (o < numObs) {
+    const double r0 = res[2 * o], r1 = res[2 * o + 1];
+    const double s = r0 * r0 + r1 * r1, a2 = a * a;
+    double v = s;
+    if (kind == 1) {
+      if (s > a2) {
+        const double r = sqrt(s);
+        v = 2.0 * a * r - a2;
+        sq = sqrt(a / r);
+      }
+    } else if (kind == 2) {
+      const double x = s / a2;
+      v = a2 * log1p(x);
+      sq = sqrt(1.0 / (1.0 + x));
+    }
+    rho[o] = v;
+  }
+  if (Jc == nullptr) return;
+  sw[tid] = sq;
+  __syncthreads();
+  const int64_t left = numObs - o0;
+  const int nObs = left < kBalLossTile ? (int)left : kBalLossTile;
+  double* jc = Jc + 2 * CS * o0;
+  for (int e = tid; e < 2 * CS * nObs; e += kBalLossTile) {
+    const double f = sw[e / (2 * CS)];
+    if (f != 1.0) jc[e] *= f;
+  }
+  double* jp = Jp + 6 * o0;
+  for (int e = tid; e < 6 * nObs; e += kBalLossTile) {
+    const double f = sw[e / 6];
+    if (f != 1.0) jp[e] *= f;
+  }
+  double* rr = res + 2 * o0;
+  for (int e = tid; e < 2 * nObs; e += kBalLossTile) {
+    const double f = sw[e / 2];
+    if (f != 1.0) rr[e] *= f;
+  }
+}
+
+// Fixed-order sum, out[0] = scale * sum x, in two passes (the pattern of logDetPartial / logDetFinal).
+// Pass 1: workgroup b of 256 threads owns x[b * kBalSumChunk, (b + 1) * kBalSumChunk).  Thread t adds, in
+// this order and starting from +0.0, the elements b * kBalSumChunk + m * 256 + t, m = 0 .. 7, that exist.
+// The 256 thread sums are then folded in LDS: for s = 128, 64, .. 1, entry t < s becomes entry t + entry
+// t + s.  Entry 0 is part[b].
+// Pass 2: one workgroup.  Thread t adds part[t], part[t + 256], .. in this order from +0.0; the same fold;
+// out[0] = scale * entry 0 (+0.0 when there are no partial sums).
+constexpr int kBalSumChunk = 2048, kBalSumWidth = 256;
+__global__ __launch_bounds__(kBalSumWidth) void balSumPartial(int64_t n, const double* x, double* part) {
+  __shared__ double red[kBalSumWidth];
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+#pragma unroll
+  for (int m = 0; m < kBalSumChunk / kBalSumWidth; m++) {
+    const int64_t g = (int64_t)blockIdx.x * kBalSumChunk + m * kBalSumWidth + tid;
+    if (g < n) acc += x[g];
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = kBalSumWidth / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) part[blockIdx.x] = red[0];
+}
+
+__global__ __launch_bounds__(kBalSumWidth) void balSumFinal(int64_t nParts, const double* part,
+                                                           double scale, double* out) {
+  __shared__ double red[kBalSumWidth];
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+  for (int64_t b = tid; b < nParts; b += kBalSumWidth) acc += part[b];
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = kBalSumWidth / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) out[0] = nParts > 0 ? scale * red[0] : 0.0;
+}
+
+// c(x) = (theta - sin(theta)) / theta^3 = sum (-x)^k / (2k+3)!, x = theta^2: the second coefficient of
+// V = I + b [w]x + c [w]x^2 (Sophus::SE3d::exp).  The closed form cancels like 6 eps / x; below x = 1 the
+// nine-term series (truncation 6 x^9 / 21! = 1.2e-19 relative at the cut) replaces it.
+__device__ __forceinline__ double translationCoefficient(double x) {
+  if (x >= 1.0) {
+    const double th = sqrt(x);
+    return (th - sin(th)) / (th * x);
+  }
+  constexpr double cc[9] = {1.0 / 6,
+                            1.0 / 120,
+                            1.0 / 5040,
+                            1.0 / 362880,
+                            1.0 / 39916800,
+                            1.0 / 6227020800.0,
+                            1.0 / 1307674368000.0,
+                            1.0 / 355687428096000.0,
+                            1.0 / 121645100408832000.0};
+  const double y = -x;
+  double c = cc[8];
+#pragma unroll
+  for (int k = 7; k >= 0; k--) c = c * y + cc[k];
+  return c;
+}
+
+__device__ __forceinline__ void cross3(const double* a, const double* b, double* c) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// unit quaternion (q[0]; q[1..3]) of the axis-angle vector v, through rotationCoefficients at
+// y = (theta / 2)^2: sin(theta / 2) / theta = a(y) / 2, cos(theta / 2) = 1 - y b(y)
+__device__ __forceinline__ void quaternionOf(const double* v, double* q) {
+  const double y = 0.25 * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+  double a, b, da, db;
+  rotationCoefficients(y, a, b, da, db);
+  q[0] = 1.0 - y * b;
+#pragma unroll
+  for (int i = 0; i < 3; i++) q[1 + i] = 0.5 * a * v[i];
+}
+
+// T <- exp(-step) T of one camera (BaAtLargeOptimizer.cpp:181-182, Sophus::SE3d::exp with the
+// translation part first): d = -w, R' = exp([d]x) R(w_cam), t' = exp([d]x) t + V(d) (-u).  The rotations
+// are composed as unit quaternions and brought back to an axis-angle vector of length <= pi by
+// 2 atan2(|v|, q0) / |v|: no acos of a trace.
+__device__ __forceinline__ void retractSe3(const double* cam, const double* stp, double* out) {
+  const double d[3] = {-stp[3], -stp[4], -stp[5]}, u[3] = {-stp[0], -stp[1], -stp[2]};
+  const double* t = cam + 3;
+  // translation
+  const double x = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+  double a, b, da, db;
+  rotationCoefficients(x, a, b, da, db);
+  const double c = translationCoefficient(x);
+  double dt[3], ddt[3], du[3], ddu[3];
+  cross3(d, t, dt);
+  cross3(d, dt, ddt);
+  cross3(d, u, du);
+  cross3(d, du, ddu);
+#pragma unroll
+  for (int i = 0; i < 3; i++) out[3 + i] = (t[i] + a * dt[i] + b * ddt[i]) + (u[i] + b * du[i] + c * ddu[i]);
+  // rotation: q = q(d) * q(w_cam), normalised, q0 >= 0
+  double p[4], r[4], q[4], pr[3];
+  quaternionOf(d, p);
+  quaternionOf(cam, r);
+  cross3(p + 1, r + 1, pr);
+  q[0] = p[0] * r[0] - (p[1] * r[1] + p[2] * r[2] + p[3] * r[3]);
+#pragma unroll
+  for (int i = 0; i < 3; i++) q[1 + i] = p[0] * r[1 + i] + r[0] * p[1 + i] + pr[i];
+  const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  const double sgn = q[0] < 0.0 ? -1.0 / nrm : 1.0 / nrm;
+#pragma unroll
+  for (int i = 0; i < 4; i++) q[i] *= sgn;
+  const double n2 = q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+  double k;  // 2 atan2(|v|, q0) / |v|
+  if (n2 < 1e-8) {  // q0 > 0.99: atan(z) / z = 1 - z^2 / 3 + z^4 / 5 - (z^6 / 7 < 2e-25), z = |v| / q0
+    const double z2 = n2 / (q[0] * q[0]);
+    k = 2.0 / q[0] * (1.0 + z2 * (-1.0 / 3 + z2 * (1.0 / 5)));
+  } else {
+    const double n = sqrt(n2);
+    k = 2.0 * atan2(n, q[0]) / n;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; i++) out[i] = k * q[1 + i];
+#pragma unroll
+  for (int i = 6; i < 9; i++) out[i] = cam[i];
+}
+
+// Thread i < numPts retracts point i, thread numPts + c camera c; parameter p's slice of `step` starts
+// at acc.paramStart(p) (points first, cameras after, as in balFillKernel).
+template <bool SE3>
+__global__ __launch_bounds__(256) void balApplyStepKernel(PermutedCoalescedAccessor acc, int64_t numPts,
+                                                          int64_t numCams, const double* cams,
+                                                          const double* pts, const double* step,
+                                                          double* camsOut, double* ptsOut) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= numPts + numCams) return;
+  const double* stp = step + acc.paramStart(i);
+  if (i < numPts) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) ptsOut[3 * i + k] = pts[3 * i + k] - stp[k];
+    return;
+  }
+  const double* cam = cams + 9 * (i - numPts);
+  double* out = camsOut + 9 * (i - numPts);
+  if (SE3) {
+    retractSe3(cam, stp, out);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 9; k++) out[k] = cam[k] - stp[k];
+  }
+}
+
 }  // namespace
+
+void balResiduals(int64_t numObs, const int64_t* obsCam, const int64_t* obsPt, const double* obsXy,
+                  const double* cams, const double* pts, double* res, void* stream) {
+  if (numObs <= 0) return;
+  balResidualsKernel<<<dim3((unsigned)((numObs + 255) / 256)), 256, 0, (hipStream_t)stream>>>(
+      numObs, obsCam, obsPt, obsXy, cams, pts, res);
+  balCHECK(hipGetLastError());
+}
+
+void balResidualsSe3(int64_t numObs, const int64_t* obsCam, const int64_t* obsPt, const double* obsXy,
+                     const double* cams, const double* pts, double* res, void* stream) {
+  if (numObs <= 0) return;
+  balResidualsSe3Kernel<<<dim3((unsigned)((numObs + 255) / 256)), 256, 0, (hipStream_t)stream>>>(
+      numObs, obsCam, obsPt, obsXy, cams, pts, res);
+  balCHECK(hipGetLastError());
+}
+
+void balLoss(int64_t numObs, int camSize, int kind, double a, double* res, double* Jc, double* Jp,
+             double* rho, void* stream) {
+  if (kind < 0 || kind > 2) {
+    throw std::runtime_error("balLoss: unknown loss kind " + std::to_string(kind) +
+                             " (0 trivial, 1 Huber, 2 Cauchy)");
+  }
+  if (!(a > 0.0) || !std::isfinite(a)) {
+    throw std::runtime_error("balLoss: the loss size a must be finite and positive, got " + std::to_string(a));
+  }
+  if ((Jc == nullptr) != (Jp == nullptr)) {
+    throw std::runtime_error("balLoss: Jc and Jp must both be given or both be NULL");
+  }
+  if (Jc != nullptr && camSize != 9 && camSize != 6) {
+    throw std::runtime_error("balLoss: camera size must be 9 or 6");
+  }
+  if (numObs <= 0) return;
+  const dim3 grid((unsigned)((numObs + kBalLossTile - 1) / kBalLossTile));
+  if (camSize == 6) {
+    balLossKernel<6><<<grid, kBalLossTile, 0, (hipStream_t)stream>>>(numObs, kind, a, res, Jc, Jp, rho);
+  } else {
+    balLossKernel<9><<<grid, kBalLossTile, 0, (hipStream_t)stream>>>(numObs, kind, a, res, Jc, Jp, rho);
+  }
+  balCHECK(hipGetLastError());
+}
+
+int64_t balSumScratchLen(int64_t n) { return n > 0 ? (n + kBalSumChunk - 1) / kBalSumChunk : 0; }
+
+void balSum(int64_t n, const double* x, double scale, double* scratch, double* out, void* stream) {
+  const int64_t nParts = balSumScratchLen(n);
+  if (nParts > 0) {
+    balSumPartial<<<dim3((unsigned)nParts), kBalSumWidth, 0, (hipStream_t)stream>>>(n, x, scratch);
+  }
+  balSumFinal<<<dim3(1), kBalSumWidth, 0, (hipStream_t)stream>>>(nParts, scratch, scale, out);
+  balCHECK(hipGetLastError());
+}
+
+template <bool SE3>
+static void launchApplyStep(const PermutedCoalescedAccessor& acc, int64_t numPts, int64_t numCams,
+                            const double* cams, const double* pts, const double* step, double* camsOut,
+                            double* ptsOut, void* stream) {
+  const int64_t n = numPts + numCams;
+  if (n <= 0) return;
+  balApplyStepKernel<SE3><<<dim3((unsigned)((n + 255) / 256)), 256, 0, (hipStream_t)stream>>>(
+      acc, numPts, numCams, cams, pts, step, camsOut, ptsOut);
+  balCHECK(hipGetLastError());
+}
+
+void balApplyStep(const PermutedCoalescedAccessor& acc, int64_t numPts, int64_t numCams, const double* cams,
+                  const double* pts, const double* step, double* camsOut, double* ptsOut, void* stream) {
+  launchApplyStep<false>(acc, numPts, numCams, cams, pts, step, camsOut, ptsOut, stream);
+}
+
+void balApplyStepSe3(const PermutedCoalescedAccessor& acc, int64_t numPts, int64_t numCams,
+                     const double* cams, const double* pts, const double* step, double* camsOut,
+                     double* ptsOut, void* stream) {
+  launchApplyStep<true>(acc, numPts, numCams, cams, pts, step, camsOut, ptsOut, stream);
+}
 
 void balLinearize(int64_t numObs, const int64_t* obsCam, const int64_t* obsPt, const double* obsXy,
                   const double* cams, const double* pts, double* res, double* Jc, double* Jp,

@@ -933,6 +933,53 @@ int bsp_bal_fill_hessian_se3_f32(bsp_solver* s, int64_t numPts, int64_t numCams,
   BSP_CATCH
 }
 
+int bsp_bal_residuals_f64(int64_t numObs, const int64_t* obsCam, const int64_t* obsPt,
+                          const double* obsXy, const double* cams, const double* pts, double* res,
+                          void* stream) {
+  BSP_TRY
+  balResiduals(numObs, obsCam, obsPt, obsXy, cams, pts, res, stream);
+  BSP_CATCH
+}
+int bsp_bal_residuals_se3_f64(int64_t numObs, const int64_t* obsCam, const int64_t* obsPt,
+                              const double* obsXy, const double* cams, const double* pts, double* res,
+                              void* stream) {
+  BSP_TRY
+  balResidualsSe3(numObs, obsCam, obsPt, obsXy, cams, pts, res, stream);
+  BSP_CATCH
+}
+int bsp_bal_loss_f64(int64_t numObs, int32_t camSize, int32_t kind, double a, double* res, double* Jc,
+                     double* Jp, double* rho, void* stream) {
+  BSP_TRY
+  balLoss(numObs, camSize, kind, a, res, Jc, Jp, rho, stream);
+  BSP_CATCH
+}
+int64_t bsp_bal_sum_scratch_len(int64_t n) { return balSumScratchLen(n); }
+int bsp_bal_sum_f64(int64_t n, const double* x, double scale, double* scratch, double* out, void* stream) {
+  BSP_TRY
+  balSum(n, x, scale, scratch, out, stream);
+  BSP_CATCH
+}
+// bsp_bal_apply_step_*: the kernels read 3 (points) and 9 or 6 (cameras) words of `step` at
+// paramStart(p), so the layout is checked as for the fill
+int bsp_bal_apply_step_f64(bsp_solver* s, int64_t numPts, int64_t numCams, const double* cams,
+                           const double* pts, const double* step, double* camsOut, double* ptsOut,
+                           void* stream) {
+  BSP_TRY
+  checkBalLayout(s, numPts, numCams);
+  BASPACHO_CHECK_EQ(s->solver->order(), 3 * numPts + 9 * numCams);
+  balApplyStep(s->solver->deviceAccessor(), numPts, numCams, cams, pts, step, camsOut, ptsOut, stream);
+  BSP_CATCH
+}
+int bsp_bal_apply_step_se3_f64(bsp_solver* s, int64_t numPts, int64_t numCams, const double* cams,
+                               const double* pts, const double* step, double* camsOut, double* ptsOut,
+                               void* stream) {
+  BSP_TRY
+  checkBalLayout(s, numPts, numCams, 6);
+  BASPACHO_CHECK_EQ(s->solver->order(), 3 * numPts + 6 * numCams);
+  balApplyStepSe3(s->solver->deviceAccessor(), numPts, numCams, cams, pts, step, camsOut, ptsOut, stream);
+  BSP_CATCH
+}
+
 double bsp_factor_flops(const bsp_solver* s) { return s->solver->factorFlops(); }
 
 int64_t bsp_plan_levels(bsp_solver* s, int64_t* out, int64_t capacity) {

@@ -612,6 +612,48 @@ int bsp_bal_fill_hessian_se3_f32(bsp_solver* s, int64_t num_pts, int64_t num_cam
                                  const double* Jp, const double* res, float lambda, float* dev_data,
                                  float* dev_grad, void* stream);
 
+/* ---- The rest of a Levenberg-Marquardt iteration on the device (BaAtLargeOptimizer.cpp:54-63
+   computeCost, :173-184 applyStep, :186-234 optimize; examples/SoftLoss.h and examples/Optimizer.h
+   computeSingleGradHess for the robust loss).  All pointers are device memory, everything is fp64; no
+   entry uses atomics, synchronises the host or allocates; every launch goes to `stream`.
+   bsp_bal_residuals / bsp_bal_residuals_se3: res[2 nObs] alone, what the linearisation writes to res
+   (the SE3 form with the same rule: camPt.z > 0.01 gives exactly (25, 0)).
+   bsp_bal_loss: per observation s = r0^2 + r1^2, rho[o] = rho(s), w = rho'(s) (SoftLoss.h jet2):
+     kind 0 trivial (s, 1);  1 Huber: s > a^2 ? (2 a sqrt(s) - a^2, a / sqrt(s)) : (s, 1);
+     2 Cauchy (a^2 log1p(s / a^2), 1 / (1 + s / a^2)).
+   With Jc and Jp given (both or neither; cam_size 9 or 6) the observation's 2 residuals and its
+   2 x cam_size and 2 x 3 Jacobian rows are multiplied in place by sqrt(w): bsp_bal_fill_hessian then
+   accumulates w J^T J and w J^T r (Optimizer.h: H += rho' J^T J, g += rho' J^T r, cost = rho / 2; no
+   second-order term).  An observation with w == 1 is not rewritten.  With Jc = Jp = NULL only rho is
+   written.  An unknown kind or an `a` that is not finite and positive: non-zero return, nothing launched.
+   bsp_bal_sum: out[0] = scale * sum x[0 .. n) in a fixed order (bitwise reproducible; the order is stated
+   in csrc/bal_pipeline.h), +0.0 for n == 0.  scratch holds bsp_bal_sum_scratch_len(n) = ceil(n / 2048)
+   doubles.
+   bsp_bal_apply_step / bsp_bal_apply_step_se3: out of place, cams_out / pts_out must not overlap the
+   inputs.  `step` is in the solver's internal order (what bsp_solve leaves in the gradient buffer);
+   points first, cameras after.
+   pts_out = pts - step; bal9: every camera parameter minus its step; se3: T_W_C <- exp(-step) T_W_C with
+   step = (translation part, rotation part) (BaAtLargeOptimizer.cpp:181-182), the rotation returned as an
+   axis-angle vector of length <= pi, (f, k1, k2) copied.  A solver whose camera blocks are not 9 (6)
+   wide or whose order is not 3 num_pts + 9 (6) num_cams is refused. */
+int bsp_bal_residuals_f64(int64_t num_obs, const int64_t* obs_cam, const int64_t* obs_pt,
+                          const double* obs_xy, const double* cams, const double* pts, double* res,
+                          void* stream);
+int bsp_bal_residuals_se3_f64(int64_t num_obs, const int64_t* obs_cam, const int64_t* obs_pt,
+                              const double* obs_xy, const double* cams, const double* pts, double* res,
+                              void* stream);
+int bsp_bal_loss_f64(int64_t num_obs, int32_t cam_size, int32_t kind, double a, double* res, double* Jc,
+                     double* Jp, double* rho, void* stream);
+int64_t bsp_bal_sum_scratch_len(int64_t n);
+int bsp_bal_sum_f64(int64_t n, const double* x, double scale, double* scratch, double* out,
+                    void* stream);
+int bsp_bal_apply_step_f64(bsp_solver* s, int64_t num_pts, int64_t num_cams, const double* cams,
+                           const double* pts, const double* step, double* cams_out, double* pts_out,
+                           void* stream);
+int bsp_bal_apply_step_se3_f64(bsp_solver* s, int64_t num_pts, int64_t num_cams, const double* cams,
+                               const double* pts, const double* step, double* cams_out, double* pts_out,
+                               void* stream);
+
 /* ---- measurement helpers (no reference counterpart; Solver::printStats is the analogue) */
 /* algorithmic flops of a full factor: sum over lumps n^3/3 + r n^2 + r^2 n */
 double bsp_factor_flops(const bsp_solver* s);
