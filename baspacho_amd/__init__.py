@@ -425,6 +425,73 @@ class Solver:
         out["node"] = {f: nd[:, i].copy() for i, f in enumerate(fn)}
         return out
 
+    def _testRecords(self, call):
+        need = ctypes.c_int64(0)
+        _check(call(None, ctypes.c_int64(0), ctypes.byref(need)))
+        buf = np.empty(need.value, dtype=np.int64)
+        _check(call(buf.ctypes.data_as(_I64P), need, ctypes.byref(need)))
+        return buf
+
+    @staticmethod
+    def _testSplitRecords(buf, pos, tables):
+        """consecutive tables of `buf` from `pos` on: (name, rows, field names or None for a plain array)"""
+        out = {}
+        for name, rows, fields in tables:
+            if fields is None:
+                out[name] = buf[pos:pos + rows].copy()
+                pos += rows
+            else:
+                t = buf[pos:pos + rows * len(fields)].reshape(rows, len(fields))
+                out[name] = {f: t[:, i].copy() for i, f in enumerate(fields)}
+                pos += rows * len(fields)
+        assert pos == len(buf)
+        return out
+
+    _PANEL_FIELDS = ("diagOff", "lda", "nb", "rowsBelow", "nRest", "lumpRowBase", "lump", "vecOff")
+    _WIDE_FIELDS = ("srcOff", "tgtBase", "chainTabPtr", "lda", "K", "rowsBelow", "nRest", "lumpRowBase", "kind",
+                    "segEnd", "tgtStride", "firstChainOrd", "rowMin", "rowTile", "colTile", "atomic")
+
+    def _testLaunchTables(self):
+        """TESTING: the launch tables of the factor plan over every lump (bsp_test_launch_tables, built on
+        the host by the function the launch code uses).  {"numMainLevels", "numLevelPanels",
+        "numTrsmTasks", "numUpdTasks": int (of the plan), table name: {field: int64 array} or int64 array};
+        "levels" lists the bigLevels of every elimination range, then the plan's own levels (range -1)"""
+        buf = self._testRecords(lambda b, cap, need: self._lib.bsp_test_launch_tables(self._h, b, cap, need))
+        n = [int(v) for v in buf[:16]]
+        out = self._testSplitRecords(buf, 16, (
+            ("levels", n[0], ("range", "tail", "directPanel", "panelBegin", "panelEnd", "trsmBegin", "trsmEnd",
+                              "updBegin", "updEnd")),
+            ("levelPanelDescs", n[5], self._PANEL_FIELDS),
+            ("trsmTasksFat", n[6], ("diagOff", "lda", "nb", "rowsBelow", "rowTile")),
+            ("updTasksFat", n[7], ("srcOff", "tgtBase", "lda", "K", "rowsBelow", "segEnd", "rowTile", "colTile",
+                                   "tgtStride", "rowMin", "atomic", "fast")),
+            ("updTasksWide", n[8], self._WIDE_FIELDS),
+            ("slowPrefix", n[9], None),
+            ("updTasksSplit", n[10], self._WIDE_FIELDS),
+            ("splitRange", n[11], ("updBegin", "begin", "end")),
+            ("foldRank", n[12], None), ("foldTiles", n[13], None), ("foldPanelEnd", n[14], None),
+            ("foldDescs", n[15], self._PANEL_FIELDS)))
+        out.update(numMainLevels=n[1], numLevelPanels=n[2], numTrsmTasks=n[3], numUpdTasks=n[4])
+        return out
+
+    def _testSolveSchedule(self, withSweeps, blockSolve, inverses, sweepMinWidth=768):
+        """TESTING: the solve schedule of the same plan's own levels under the given switches
+        (bsp_test_solve_schedule).  {"numSweeps", "sweepInstStride", "maxSweepWgs", "maxSweepWgsM",
+        "maxSweepW", "maxSweepBelow": int, "levels", "items", "invPanels": {field: int64 array}}"""
+        buf = self._testRecords(lambda b, cap, need: self._lib.bsp_test_solve_schedule(
+            self._h, ctypes.c_int32(int(withSweeps)), ctypes.c_int32(int(blockSolve)), ctypes.c_int32(int(inverses)),
+            ctypes.c_int32(sweepMinWidth), b, cap, need))
+        n = [int(v) for v in buf[:9]]
+        panel = ("lump", "col", "nb", "rowsBelow")
+        out = self._testSplitRecords(buf, 9, (
+            ("levels", n[0], ("panels",) + panel),
+            ("items", n[1], ("kind", "slot", "l", "e", "w", "nBlocks", "rowsBelow", "invSlot", "xchgOff", "fwdWgs",
+                             "bwdWgs")),
+            ("invPanels", n[2], panel)))
+        out.update(numSweeps=n[3], sweepInstStride=n[4], maxSweepWgs=n[5], maxSweepWgsM=n[6], maxSweepW=n[7],
+                   maxSweepBelow=n[8])
+        return out
+
     def collectOpStats(self, on=True):
         """Solver::enableStats + per-op samples of the per-op boundary (bsp_collect_op_stats)"""
         _check(self._lib.bsp_collect_op_stats(self._h, ctypes.c_int32(1 if on else 0)))

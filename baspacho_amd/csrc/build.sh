@@ -18,7 +18,7 @@ for f in $SRCS; do
     pids+=($!)
   fi
 done
-for f in hip_backend.hip bal_pipeline.hip; do
+for f in hip_backend.hip hip_factor.hip hip_solve.hip hip_extensions.hip bal_pipeline.hip; do
   o=$BUILD/${f%.hip}.o
   OBJS="$OBJS $o"
   if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ -n "$(find . -name '*.h' -newer "$o" -print -quit)" ]; then

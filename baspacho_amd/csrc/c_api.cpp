@@ -373,6 +373,24 @@ static int selinvPlanRecords(const bsp_solver* s, bool upTo, int64_t span, int64
   BSP_CATCH
 }
 
+static void copyRecords(const std::vector<int64_t>& out, int64_t* buf, int64_t capacity, int64_t* needed) {
+  *needed = (int64_t)out.size();
+  if (buf != nullptr) std::copy(out.begin(), out.begin() + std::min(capacity, *needed), buf);
+}
+int bsp_test_launch_tables(const bsp_solver* s, int64_t* buf, int64_t capacity, int64_t* needed) {
+  BSP_TRY
+  copyRecords(hipBackendLaunchTableRecords(s->solver->internalSymbolicContext()), buf, capacity, needed);
+  BSP_CATCH
+}
+int bsp_test_solve_schedule(const bsp_solver* s, int32_t with_sweeps, int32_t block_solve, int32_t inverses,
+                            int32_t sweep_min_width, int64_t* buf, int64_t capacity, int64_t* needed) {
+  BSP_TRY
+  copyRecords(hipBackendSolveScheduleRecords(s->solver->internalSymbolicContext(), with_sweeps != 0, block_solve != 0,
+                                             inverses != 0, sweep_min_width),
+              buf, capacity, needed);
+  BSP_CATCH
+}
+
 template <typename T>
 static void doElim(bsp_solver* s, T* d, int64_t idx) {
   const auto& ranges = s->solver->sparseEliminationRanges();

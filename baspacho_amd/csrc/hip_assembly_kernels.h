@@ -16,7 +16,7 @@
 #include <cstdint>
 
 #include "assembly.h"
-#include "hip_kernels.h"
+#include "hip_device_common.h"
 
 namespace BaSpaCho {
 namespace hipk {

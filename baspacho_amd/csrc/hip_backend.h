@@ -187,4 +187,11 @@ void hipBackendFreeNormalEq(HipNormalEqDev* dev);
 
 HipPlanStats hipBackendPlanStats(SymbolicCtx& sym, int64_t startLump, int64_t upToLump);
 
+// TESTING (host only): the launch tables (buildLaunchTables, hip_plan.h) and the solve schedule of the
+// plan's own levels (buildSolveSchedule) of the plan over every lump, as the flat records of
+// include/baspacho_amd_testing.h
+std::vector<int64_t> hipBackendLaunchTableRecords(SymbolicCtx& sym);
+std::vector<int64_t> hipBackendSolveScheduleRecords(SymbolicCtx& sym, bool withSweeps, bool blockSolve, bool inverses,
+                                                    int sweepMinWidth);
+
 }  // namespace BaSpaCho

@@ -29,7 +29,7 @@
 #include <cstdint>
 
 #include "hip_grad_kernels.h"
-#include "hip_kernels.h"
+#include "hip_device_common.h"
 #include "hip_plan.h"
 #include "hip_selinv_kernels.h"
 

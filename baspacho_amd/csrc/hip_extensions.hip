@@ -1,0 +1,738 @@
+// MI355X backend, the extension operations of hip_backend.h: selected inversion and its adjoint,
+// log-det and gradients on the pattern of L, factor status and damping, the reverse-mode sweep of the
+// factor, the dense Schur complement, assembly of coordinate entries and normal equations.  Every
+// entry point stages its pointer arguments, splits the batch into chunks and enqueues the launches
+// of a chunk on the execution stream (the call path: HipSymbolicCtx::stage / forChunks).
+#include "hip_context.h"
+#include "hip_assembly_kernels.h"
+#include "hip_chol_adjoint_kernels.h"
+#include "hip_grad_kernels.h"
+#include "hip_normal_eq_kernels.h"
+#include "hip_selinv_adjoint_kernels.h"
+#include "hip_selinv_kernels.h"
+#include "hip_status_kernels.h"
+
+namespace BaSpaCho {
+
+using std::vector;
+using namespace hipb;
+
+// an assembly map on the device (assembly.h), owned by its AssemblyMap
+struct HipAssemblyDev {
+  DevBuf entryOff, tileFirst, tileLongFirst, runStart, runEntry, destLocal, longDest;
+  void upload(const AssemblyMap& m) {
+    entryOff.upload(m.entryOff);
+    tileFirst.upload(m.tileFirst);
+    tileLongFirst.upload(m.tileLongFirst);
+    runStart.upload(m.runStart);
+    runEntry.upload(m.runEntry);
+    destLocal.upload(m.destLocal);
+    longDest.upload(m.longDest);
+  }
+};
+
+// the three parts of a normal-equations map on the device (normal_eq.h), owned by its NormalEqMap
+struct HipNormalEqDev {
+  bool hasForward = false, hasAdjoint = false, hasVectors = false;
+  DevBuf tileFirst, tileLongFirst, runStart, pairA, pairB, destLocal, longDest;
+  DevBuf adjStart, adjPartner, adjDest, adjLong;
+  DevBuf colStart, colEntry, colIdx, rowStart, rowEntry, rowIdx;
+  void uploadForward(const NormalEqMap& m) {
+    tileFirst.upload(m.tileFirst);
+    tileLongFirst.upload(m.tileLongFirst);
+    runStart.upload(m.runStart);
+    pairA.upload(m.pairA);
+    pairB.upload(m.pairB);
+    destLocal.upload(m.destLocal);
+    longDest.upload(m.longDest);
+    hasForward = true;
+  }
+  void uploadAdjoint(const NormalEqMap& m) {
+    adjStart.upload(m.adjStart);
+    adjPartner.upload(m.adjPartner);
+    adjDest.upload(m.adjDest);
+    adjLong.upload(m.adjLong);
+    hasAdjoint = true;
+  }
+  void uploadVectors(const NormalEqMap& m) {
+    colStart.upload(m.colStart);
+    colEntry.upload(m.colEntry);
+    colIdx.upload(m.colIdx);
+    rowStart.upload(m.rowStart);
+    rowEntry.upload(m.rowEntry);
+    rowIdx.upload(m.rowIdx);
+    hasVectors = true;
+  }
+};
+
+namespace {
+
+// work lists of the gradient kernels (hip_grad_kernels.h), built once per structure: the patternGrad
+// tiles of every lump column and, for logDet's first pass, the lump of the first diagonal element of
+// every workgroup.  `part` holds logDet's partial sums, nParts per matrix of a chunk; `statPart` the
+// partial records of factorStatus (hip_status_kernels.h), which reads the same firstLump table.
+struct GradDev {
+  DevBuf tiles, firstLump, part, statPart;
+  int64_t nTiles = 0, nParts = 0, partSlices = 0, statSlices = 0;
+  vector<int64_t> lumpFirstTile;  // host: first tile of every lump (tiles never cross lumps), then nTiles
+  void build(const CoalescedBlockMatrixSkel& sk) {
+    vector<hipk::GradTile> tl;
+    const int64_t nLumps = sk.numLumps();
+    lumpFirstTile.clear();
+    for (int64_t l = 0; l < nLumps; l++) {
+      lumpFirstTile.push_back((int64_t)tl.size());
+      const int64_t w = sk.lumpStart[l + 1] - sk.lumpStart[l];
+      const int64_t cBeg = sk.chainColPtr[l], cEnd = sk.chainColPtr[l + 1];
+      const int64_t R = sk.chainRowsTillEnd[cEnd - 1], base = sk.chainData[cBeg];
+      for (int64_t c0 = 0; c0 < w; c0 += hipk::kGradCols) {
+        const int64_t nc = std::min<int64_t>(hipk::kGradCols, w - c0);
+        const int64_t trMax = std::min<int64_t>(hipk::kGradRows, std::max<int64_t>(1, hipk::kGradElems / nc));
+        int64_t chain = cBeg;
+        for (int64_t r0 = 0; r0 < R; r0 += trMax) {
+          const int64_t nr = std::min(trMax, R - r0);
+          while (sk.chainRowsTillEnd[chain] <= r0) chain++;
+          int64_t last = chain;
+          while (sk.chainRowsTillEnd[last] < r0 + nr) last++;
+          hipk::GradTile t{};
+          t.off = base + r0 * w + c0;
+          t.lump = (int32_t)l;
+          t.r0 = (int32_t)r0;
+          t.c0 = (int32_t)c0;
+          t.nr = (int32_t)nr;
+          t.nc = (int32_t)nc;
+          t.chain = (int32_t)chain;
+          t.chainEnd = (int32_t)(last + 1);
+          tl.push_back(t);
+        }
+      }
+    }
+    nTiles = (int64_t)tl.size();
+    lumpFirstTile.push_back(nTiles);
+    tiles.upload(tl);
+    const int64_t n = sk.order();
+    nParts = (n + hipk::kLogDetChunk - 1) / hipk::kLogDetChunk;
+    vector<int32_t> fl;
+    int64_t l = 0;
+    for (int64_t b = 0; b < nParts; b++) {
+      while (sk.lumpStart[l + 1] <= b * hipk::kLogDetChunk) l++;
+      fl.push_back((int32_t)l);
+    }
+    fl.push_back((int32_t)std::max<int64_t>(nLumps - 1, 0));
+    firstLump.upload(fl);
+  }
+  // room for the partial sums of n matrices.  Growing waits for the kernels queued by earlier calls
+  // (they may still use the old buffer); a warm solver does not grow again
+  void reservePart(int64_t n) {
+    if (n <= partSlices) return;
+    if (partSlices > 0) hipCHECK(hipDeviceSynchronize());
+    partSlices = 0;
+    part.release();
+    part.resize((size_t)std::max<int64_t>(nParts * n, 1) * sizeof(double));
+    partSlices = n;
+  }
+  // the same for the partial records of factorStatus
+  void reserveStat(int64_t n) {
+    if (n <= statSlices) return;
+    if (statSlices > 0) hipCHECK(hipDeviceSynchronize());
+    statSlices = 0;
+    statPart.release();
+    statPart.resize((size_t)std::max<int64_t>(nParts * n, 1) * sizeof(hipk::StatusPart));
+    statSlices = n;
+  }
+};
+
+// Scratch of the selected-inversion plans of one structure (the complete plan and the plans up to a
+// lump of section 16 share it; it grows to the largest).  Per-matrix slices of a plan's element counts,
+// matrix q of a batch chunk in slice q (hipk::SelInvStrides, counted in elements of T).  The buffers are
+// sized in fp64: the fp32 slices, half as many bytes each, are packed into the first half of every buffer
+struct SelInvScratch {
+  DevBuf linv, dd, U, P, Wp;
+  int64_t linvCap = 0, uCap = 0, pCap = 0, wCap = 0;  // fp64 elements allocated
+  bool allocated = false;
+  void release() {
+    allocated = false;
+    for (DevBuf* b : {&linv, &dd, &U, &P, &Wp}) b->release();
+    linvCap = uCap = pCap = wCap = 0;
+  }
+  // slices of plan `h` that fit
+  int64_t slicesFor(const SelInvPlanHost& h) const {
+    if (!allocated) return 0;
+    int64_t n = INT64_MAX;
+    const auto fit = [&n](int64_t cap, int64_t elems) {
+      if (elems > 0) n = std::min(n, cap / elems);
+    };
+    fit(linvCap, h.linvElems);
+    fit(uCap, h.uElems);
+    fit(pCap, h.pElems);
+    fit(wCap, h.wElems);
+    return n;
+  }
+  // grow the scratch to n slices of plan `h`.  Kernels queued by an earlier call (on any stream) may
+  // still use the old buffers: wait for them before freeing (as PtrRing::push does).  No slice counts as
+  // usable until all five allocations have succeeded: a failed grow (an allocation that throws) leaves
+  // nothing allocated, and the next call allocates again instead of launching on released buffers
+  void reserve(const SelInvPlanHost& h, int64_t n) {
+    if (n <= slicesFor(h)) return;
+    if (allocated) hipCHECK(hipDeviceSynchronize());
+    allocated = false;
+    for (DevBuf* b : {&linv, &dd, &U, &P, &Wp}) b->release();
+    const int64_t lc = std::max(linvCap, h.linvElems * n), uc = std::max(uCap, h.uElems * n);
+    const int64_t pc = std::max(pCap, h.pElems * n), wc = std::max(wCap, h.wElems * n);
+    linvCap = uCap = pCap = wCap = 0;
+    const auto bytes = [](int64_t elems) { return (size_t)std::max<int64_t>(elems, 1) * sizeof(double); };
+    linv.resize(bytes(lc));
+    dd.resize(bytes(lc));
+    U.resize(bytes(uc));
+    P.resize(bytes(pc));
+    Wp.resize(bytes(wc));
+    linvCap = lc, uCap = uc, pCap = pc, wCap = wc;
+    allocated = true;
+  }
+};
+
+// selected-inversion plan (hip_plan.h, SelInvPlanHost) on the device, with the shared scratch
+struct SelInvDev {
+  SelInvPlanHost host;
+  DevBuf smalls, nodes, tiles, zTasks, rowChain, rowLocal, pairOff, pairStr;
+  SelInvScratch* scratch = nullptr;
+  hipk::SelInvStrides strides() const { return {host.linvElems, host.uElems, host.pElems, host.wElems}; }
+  // fp64 bytes of one slice of every scratch buffer
+  int64_t sliceBytes() const {
+    return (2 * host.linvElems + host.uElems + host.pElems + host.wElems) * (int64_t)sizeof(double);
+  }
+  int64_t slices() const { return scratch->slicesFor(host); }
+  void reserve(int64_t n) { scratch->reserve(host, n); }
+  // what a pass over the levels hands to its kernels: the scratch as T, the plan tables, the strides
+  template <typename T>
+  struct View {
+    T *linv, *dd, *U, *P, *Wp;
+    const SelInvNode* nodes;
+    const int2* tiles;
+    const int4* zTasks;
+    hipk::SelInvStrides st;
+  };
+  template <typename T>
+  View<T> view() const {
+    const auto as = [](const DevBuf& b) { return reinterpret_cast<T*>(b.ptr); };
+    return {as(scratch->linv), as(scratch->dd), as(scratch->U), as(scratch->P), as(scratch->Wp),
+            nodes.as<SelInvNode>(), tiles.as<int2>(), zTasks.as<int4>(), strides()};
+  }
+  void upload(SelInvScratch* sc) {
+    scratch = sc;
+    smalls.upload(host.smalls);
+    nodes.upload(host.nodes);
+    tiles.upload(host.tiles);
+    zTasks.upload(host.zTasks);
+    rowChain.upload(host.rowChain);
+    rowLocal.upload(host.rowLocal);
+    pairOff.upload(host.pairOff);
+    pairStr.upload(host.pairStr);
+    reserve(1);
+  }
+};
+
+}  // namespace
+
+// the extension state of a context (HipSymbolicCtx::ext), built on first use
+struct hipb::ExtensionState {
+  std::unique_ptr<SelInvDev> selinv;  // selected-inversion plan, built on first use
+  std::map<int64_t, std::unique_ptr<SelInvDev>> selinvUpTo;  // ... up to a lump, per cut
+  SelInvScratch selinvScratch;
+  std::unique_ptr<GradDev> grad;      // work lists of logDet / patternGrad, built on first use
+};
+void hipb::ExtensionStateDelete::operator()(ExtensionState* p) const { delete p; }
+
+namespace {
+
+HipSymbolicCtx& hipCtx(SymbolicCtx& sym) {
+  HipSymbolicCtx* h = dynamic_cast<HipSymbolicCtx*>(&sym);
+  BASPACHO_CHECK_NOTNULL(h);
+  return *h;
+}
+
+ExtensionState& extState(HipSymbolicCtx& h) {
+  if (!h.ext) h.ext.reset(new ExtensionState);
+  return *h.ext;
+}
+
+// ---- gradients on the pattern of L (hip_grad_kernels.h) -------------------
+GradDev& gradPlan(HipSymbolicCtx& h) {
+  ExtensionState& x = extState(h);
+  const CoalescedBlockMatrixSkel& skel = h.skel;
+  if (!x.grad) {
+    std::unique_ptr<GradDev> p(new GradDev);
+    p->build(skel);
+    x.grad = std::move(p);
+  }
+  return *x.grad;
+}
+
+// matrices per chunk of a batched pass over plan `d`, with the scratch grown to it: min(batch, 65535
+// (gridDim.y), what half the free device memory holds in slices -- slices already held count as
+// free), at least 1, at most the testing cap
+int64_t selInvChunk(HipSymbolicCtx& h, SelInvDev& d, int64_t batch) {
+  int64_t chunk = std::min(batch, HipSymbolicCtx::kMaxGridY);
+  if (h.selInvChunkCap > 0) chunk = std::min<int64_t>(chunk, h.selInvChunkCap);
+  const int64_t slice = d.sliceBytes();
+  if (chunk > d.slices() && slice > 0) {
+    size_t freeBytes = 0, totalBytes = 0;
+    hipCHECK(hipMemGetInfo(&freeBytes, &totalBytes));
+    const int64_t fit = std::max<int64_t>(d.slices(), (int64_t)(freeBytes / 2) / slice);
+    chunk = std::max<int64_t>(1, std::min(chunk, fit));
+  }
+  d.reserve(chunk);
+  return chunk;
+}
+
+SelInvDev& selInvPlan(HipSymbolicCtx& h) {
+  ExtensionState& x = extState(h);
+  const CoalescedBlockMatrixSkel& skel = h.skel;
+  if (!x.selinv) {
+    std::unique_ptr<SelInvDev> p(new SelInvDev);
+    p->host = buildSelInvPlan(skel);
+    p->upload(&x.selinvScratch);
+    x.selinv = std::move(p);
+  }
+  return *x.selinv;
+}
+
+// the plan of the lumps < upToLump (section 16), cached per cut beside the complete one, as planFor
+// caches factor plans; all of them work in the one scratch
+SelInvDev& selInvPlanUpTo(HipSymbolicCtx& h, int64_t upToLump) {
+  ExtensionState& x = extState(h);
+  const CoalescedBlockMatrixSkel& skel = h.skel;
+  if (upToLump == skel.numLumps()) return selInvPlan(h);
+  std::unique_ptr<SelInvDev>& slot = x.selinvUpTo[upToLump];
+  if (!slot) {
+    std::unique_ptr<SelInvDev> p(new SelInvDev);
+    p->host = buildSelInvPlan(skel, upToLump);
+    p->upload(&x.selinvScratch);
+    slot = std::move(p);
+  }
+  return *slot;
+}
+
+// one pass over the levels for `nMats` matrices (gridDim.y), in scratch slices 0 .. nMats-1
+template <typename T>
+void selInvLevels(HipSymbolicCtx& h, const SelInvDev& d, hipk::DataRef<T> data, unsigned nMats) {
+  const hipStream_t stream = h.stream;
+  HipRunCounters& counters = h.counters;
+  const hipk::SkelDev sk = h.skelDev();
+  const SelInvDev::View<T> w = d.view<T>();
+  int64_t launches = 0;
+  for (const SelInvLevel& L : d.host.levels) {
+    if (L.smallEnd > L.smallBegin) {
+      hipk::selinvSmallLumps<T><<<dim3((unsigned)(L.smallEnd - L.smallBegin), nMats), 64, 0, stream>>>(
+          d.smalls.as<SelInvSmall>() + L.smallBegin, sk, data);
+      launches++;
+    }
+    const unsigned nNodes = (unsigned)(L.nodeEnd - L.nodeBegin);
+    if (nNodes == 0) continue;
+    const SelInvNode* nd = w.nodes + L.nodeBegin;
+    hipk::selinvDiagInverse<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, data, w.linv, w.dd, w.st);
+    const unsigned nTiles = (unsigned)(L.tileEnd - L.tileBegin);
+    if (nTiles > 0) {
+      hipk::selinvFormU<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, w.tiles + L.tileBegin, data, w.linv, w.U,
+                                                                    w.st);
+      hipk::selinvZrrTimesU<T><<<dim3((unsigned)(L.zEnd - L.zBegin), nMats), 256, 0, stream>>>(
+          nd, w.zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(),
+          d.pairOff.as<int64_t>(), d.pairStr.as<int32_t>(), data, w.U, w.P, w.st);
+      hipk::selinvReduceZ<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, w.tiles + L.tileBegin, data, w.U, w.P,
+                                                                      w.Wp, w.st);
+      launches += 3;
+    }
+    hipk::selinvDiagBlock<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, data, w.dd, w.Wp, w.st);
+    launches += 2;
+  }
+  counters.selinvLaunches += launches;
+  counters.selinvChunks++;
+}
+
+// one right-to-left pass over the selected-inversion levels for `nMats` matrices (gridDim.y), in
+// scratch slices 0 .. nMats-1.  selinvDiagInverse and selinvZrrTimesU run as they are: the first
+// reads L (it does not write its data), the second multiplies G_RR by the copy of L_RI in U.
+template <typename T>
+void cholAdjLevels(HipSymbolicCtx& h, const SelInvDev& d, hipk::DataRef<const T> lref, hipk::DataRef<T> gref,
+                   unsigned nMats) {
+  const hipStream_t stream = h.stream;
+  const hipk::SkelDev sk = h.skelDev();
+  const SelInvDev::View<T> w = d.view<T>();
+  const hipk::DataRef<T> lmut{const_cast<T*>(lref.single), const_cast<T* const*>(lref.many)};
+  for (const SelInvLevel& L : d.host.levels) {
+    if (L.smallEnd > L.smallBegin) {
+      hipk::cholAdjSmallLumps<T><<<dim3((unsigned)(L.smallEnd - L.smallBegin), nMats), 64, 0, stream>>>(
+          d.smalls.as<SelInvSmall>() + L.smallBegin, sk, lref, gref);
+    }
+    const unsigned nNodes = (unsigned)(L.nodeEnd - L.nodeBegin);
+    if (nNodes == 0) continue;
+    const SelInvNode* nd = w.nodes + L.nodeBegin;
+    hipk::selinvDiagInverse<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, lmut, w.linv, w.dd, w.st);
+    const unsigned nTiles = (unsigned)(L.tileEnd - L.tileBegin);
+    if (nTiles > 0) {
+      hipk::cholAdjGatherL<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, w.tiles + L.tileBegin, lref, w.U, w.st);
+      hipk::selinvZrrTimesU<T><<<dim3((unsigned)(L.zEnd - L.zBegin), nMats), 256, 0, stream>>>(
+          nd, w.zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(),
+          d.pairOff.as<int64_t>(), d.pairStr.as<int32_t>(), gref, w.U, w.P, w.st);
+      hipk::cholAdjReduce<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, w.tiles + L.tileBegin, gref, w.linv, w.U,
+                                                                      w.P, w.Wp, w.st);
+    }
+    hipk::cholAdjDiag<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, lref, gref, w.linv, w.Wp, w.st);
+  }
+}
+
+// one pass over the selected-inversion levels, last level first, for `nMats` matrices (gridDim.y), in
+// scratch slices 0 .. nMats-1.  selinvDiagInverse and selinvZrrTimesU run as they are: the first reads
+// L, the second multiplies Z_RR by the S_RI that selinvAdjStage left in U (neither writes its data).
+// A level of one node has one writer per slot of the scatter: no atomics there.
+template <typename T>
+void selInvAdjLevels(HipSymbolicCtx& h, const SelInvDev& d, hipk::DataRef<const T> lref, hipk::DataRef<const T> zref,
+                     hipk::DataRef<T> gref, unsigned nMats) {
+  const hipStream_t stream = h.stream;
+  HipRunCounters& counters = h.counters;
+  const hipk::SkelDev sk = h.skelDev();
+  const SelInvDev::View<T> w = d.view<T>();
+  const hipk::DataRef<T> lmut{const_cast<T*>(lref.single), const_cast<T* const*>(lref.many)};
+  const hipk::DataRef<T> zmut{const_cast<T*>(zref.single), const_cast<T* const*>(zref.many)};
+  int64_t launches = 0;
+  for (auto it = d.host.levels.rbegin(); it != d.host.levels.rend(); ++it) {
+    const SelInvLevel& L = *it;
+    if (L.smallEnd > L.smallBegin) {
+      hipk::selinvAdjSmallLumps<T><<<dim3((unsigned)(L.smallEnd - L.smallBegin), nMats), 64, 0, stream>>>(
+          d.smalls.as<SelInvSmall>() + L.smallBegin, sk, lref, zref, gref);
+      launches++;
+    }
+    const unsigned nNodes = (unsigned)(L.nodeEnd - L.nodeBegin);
+    if (nNodes == 0) continue;
+    const SelInvNode* nd = w.nodes + L.nodeBegin;
+    hipk::selinvDiagInverse<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, lmut, w.linv, w.dd, w.st);
+    const unsigned nTiles = (unsigned)(L.tileEnd - L.tileBegin);
+    if (nTiles > 0) {
+      const unsigned nZ = (unsigned)(L.zEnd - L.zBegin);
+      hipk::selinvAdjStage<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, w.tiles + L.tileBegin, lref, gref, w.linv,
+                                                                       w.U, w.P, w.Wp, w.st);
+      // workgroups per task: one per 64 source rows of the level's longest chunk, at most 8
+      int maxChunk = 0;
+      for (int64_t n = L.nodeBegin; n < L.nodeEnd; n++) maxChunk = std::max(maxChunk, (int)d.host.nodes[n].kChunk);
+      const dim3 sgrid(nZ, nMats, (unsigned)std::min(8, std::max(1, (maxChunk + 63) / 64)));
+      if (nNodes == 1) {
+        hipk::selinvAdjScatter<T, false><<<sgrid, 256, 0, stream>>>(
+            nd, w.zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(), d.pairOff.as<int64_t>(),
+            d.pairStr.as<int32_t>(), gref, w.P, w.Wp, w.st);
+      } else {
+        hipk::selinvAdjScatter<T, true><<<sgrid, 256, 0, stream>>>(
+            nd, w.zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(), d.pairOff.as<int64_t>(),
+            d.pairStr.as<int32_t>(), gref, w.P, w.Wp, w.st);
+      }
+      hipk::selinvZrrTimesU<T><<<dim3(nZ, nMats), 256, 0, stream>>>(
+          nd, w.zTasks + L.zBegin, d.rowChain.as<int32_t>(), d.rowLocal.as<int32_t>(), d.pairOff.as<int64_t>(),
+          d.pairStr.as<int32_t>(), zmut, w.U, w.P, w.st);
+      hipk::selinvAdjReduce<T><<<dim3(nTiles, nMats), 256, 0, stream>>>(nd, w.tiles + L.tileBegin, lref, zref, gref,
+                                                                        w.linv, w.P, w.Wp, w.st);
+      launches += 4;
+    }
+    hipk::selinvAdjDiag<T><<<dim3(nNodes, nMats), 256, 0, stream>>>(nd, gref, w.linv, w.Wp, w.st);
+    launches += 2;
+  }
+  counters.selinvLaunches += launches;
+  counters.selinvChunks++;
+}
+
+}  // namespace
+
+void hipBackendSetSelInvBatchChunk(SymbolicCtx& sym, int64_t maxMatrices) {
+  BASPACHO_CHECK_GE(maxMatrices, 0);
+  hipCtx(sym).selInvChunkCap = maxMatrices;
+}
+
+// Selected inversion of `batch` complete factors, in place (hip_selinv_kernels.h).  The plan is built
+// and uploaded on the first call; every launch goes to the execution stream, in level order, with no
+// host synchronisation.  A chunk is one pass over the levels, each matrix in its own scratch slice;
+// the scratch grows to the chunk (selInvChunk) and stays with the solver.
+template <typename T>
+void hipBackendSelectedInverse(SymbolicCtx& sym, T* const* data, int64_t batch, bool single) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  h.checkDevice();
+  SelInvDev& d = selInvPlan(h);
+  const int64_t chunk = selInvChunk(h, d, batch);
+  const BatchPtrs<T> z = h.stage(data, batch, single);
+  h.forChunks(batch, chunk, [&](int64_t q0, unsigned nm) { selInvLevels<T>(h, d, z.at(q0), nm); });
+}
+
+// ---- reverse mode of selected inversion (hip_selinv_adjoint_kernels.h) -------
+// L[q] a complete factor, Z[q] its selected inverse (both read only); grad[q]: the gradient of every
+// slot of Z on entry, Lbar on return.  The complete plan, its scratch and its chunks, the levels taken
+// from the last to the first.
+template <typename T>
+void hipBackendSelectedInverseAdjoint(SymbolicCtx& sym, const T* const* L, const T* const* Z, T* const* G,
+                                      int64_t batch, bool single) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  h.checkDevice();
+  SelInvDev& d = selInvPlan(h);
+  const int64_t chunk = selInvChunk(h, d, batch);
+  const BatchPtrs<const T> l = h.stage(L, batch, single), z = h.stage(Z, batch, single);
+  const BatchPtrs<T> gr = h.stage(G, batch, single);
+  h.forChunks(batch, chunk, [&](int64_t q0, unsigned nm) { selInvAdjLevels<T>(h, d, l.at(q0), z.at(q0), gr.at(q0), nm); });
+}
+
+// logDet of `batch` factors: two launches per chunk, the partial sums of a chunk in GradDev::part
+template <typename T>
+void hipBackendLogDet(SymbolicCtx& sym, const T* const* factors, int64_t batch, bool single, T* out) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  const CoalescedBlockMatrixSkel& skel = h.skel;
+  h.checkDevice();
+  GradDev& g = gradPlan(h);
+  const hipk::SkelDev sk = h.skelDev();
+  const int64_t chunk = std::min(batch, HipSymbolicCtx::kMaxGridY);
+  g.reservePart(chunk);
+  const BatchPtrs<const T> f = h.stage(factors, batch, single);
+  double* part = reinterpret_cast<double*>(g.part.ptr);
+  h.forChunks(batch, chunk, [&](int64_t q0, unsigned nm) {
+    if (g.nParts > 0) {
+      hipk::logDetPartial<T><<<dim3((unsigned)g.nParts, nm), 256, 0, stream>>>(
+          sk, g.firstLump.as<int32_t>(), skel.order(), (int)g.nParts, f.at(q0), part);
+    }
+    hipk::logDetFinal<T><<<dim3(1, nm), 256, 0, stream>>>(part, (int)g.nParts, out + q0);
+  });
+}
+
+// patternGrad of a.batch matrices: one launch of every tile per chunk
+template <typename T>
+void hipBackendPatternGrad(SymbolicCtx& sym, const HipGradArgs<T>& a, int64_t batch, bool single) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  GradDev& g = gradPlan(h);
+  const hipk::SkelDev sk = h.skelDev();
+  if (g.nTiles == 0) return;
+  const bool hasZ = a.z != nullptr, hasUV = a.u != nullptr;
+  const BatchPtrs<const T> z = h.stage(a.z, batch, single);
+  const BatchPtrs<const T> u = h.stage(a.u, batch, single), v = h.stage(hasUV ? a.v : nullptr, batch, single);
+  const BatchPtrs<T> o = h.stage(a.out, batch, single);
+  const int k = hasUV ? a.nRHS : 0;
+  const int kc = std::min(k, hipk::kGradK);
+  const size_t lds = k > 0 ? (size_t)(hipk::kGradRows + hipk::kGradCols) * (kc + 1) * 2 * sizeof(T) : 0;
+  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+    if (a.outer) {
+      hipk::patternGradTiles<T, true><<<dim3((unsigned)g.nTiles, nm), 256, lds, stream>>>(
+          g.tiles.as<hipk::GradTile>(), sk, hipk::DataRef<const T>{nullptr, nullptr}, nullptr, u.at(q0), v.at(q0),
+          a.ld, k, a.alpha, o.at(q0));
+    } else {
+      hipk::patternGradTiles<T><<<dim3((unsigned)g.nTiles, nm), 256, lds, stream>>>(
+          g.tiles.as<hipk::GradTile>(), sk, z.at(q0), hasZ ? a.zScale + q0 : nullptr, u.at(q0), v.at(q0), a.ld, k,
+          a.alpha, o.at(q0));
+    }
+  });
+}
+
+// ---- factor status and damping of the diagonal (hip_status_kernels.h) -------
+// the records of `batch` buffers over the internal scalars [g0, g1): two launches per chunk, chunks as
+// logDet's, the partial records of a chunk in GradDev::statPart
+template <typename T>
+void hipBackendFactorStatus(SymbolicCtx& sym, const T* const* data, int64_t batch, bool single, int64_t spanBegin,
+                            int64_t spanEnd, int64_t* out) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  const CoalescedBlockMatrixSkel& skel = h.skel;
+  h.checkDevice();
+  GradDev& g = gradPlan(h);
+  const hipk::SkelDev sk = h.skelDev();
+  const int64_t g0 = skel.spanStart[spanBegin], g1 = skel.spanStart[spanEnd];
+  const int64_t b0 = g0 / hipk::kLogDetChunk;
+  const int64_t nParts = g1 > g0 ? (g1 + hipk::kLogDetChunk - 1) / hipk::kLogDetChunk - b0 : 0;
+  BASPACHO_CHECK_LE(b0 + nParts, g.nParts);
+  const int64_t chunk = std::min(batch, HipSymbolicCtx::kMaxGridY);
+  g.reserveStat(chunk);
+  const BatchPtrs<const T> d = h.stage(data, batch, single);
+  hipk::StatusPart* part = reinterpret_cast<hipk::StatusPart*>(g.statPart.ptr);
+  h.forChunks(batch, chunk, [&](int64_t q0, unsigned nm) {
+    if (nParts > 0) {
+      hipk::factorStatusPartial<T><<<dim3((unsigned)nParts, nm), 256, 0, stream>>>(
+          sk, g.firstLump.as<int32_t>(), g0, g1, b0, (int)nParts, d.at(q0), part);
+    }
+    hipk::factorStatusFinal<<<dim3(1, nm), 256, 0, stream>>>(part, (int)nParts, out + 4 * q0);
+  });
+}
+
+// diagonal <- diagonal (1 + alpha) + beta on the internal scalars [g0, g1) of `batch` buffers, alpha
+// and beta of member q at ab[2 q], ab[2 q + 1] on the device: one launch per chunk
+template <typename T>
+void hipBackendDampDiagonal(SymbolicCtx& sym, T* const* data, int64_t batch, bool single, int64_t spanBegin,
+                            int64_t spanEnd, const T* ab) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  const CoalescedBlockMatrixSkel& skel = h.skel;
+  h.checkDevice();
+  GradDev& g = gradPlan(h);
+  const hipk::SkelDev sk = h.skelDev();
+  const int64_t g0 = skel.spanStart[spanBegin], g1 = skel.spanStart[spanEnd];
+  if (g1 <= g0) return;
+  const int64_t base = g0 - g0 % 256, wgs = (g1 - base + 255) / 256;
+  const BatchPtrs<T> d = h.stage(data, batch, single);
+  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+    hipk::dampDiagonal<T><<<dim3((unsigned)wgs, nm), 256, 0, stream>>>(sk, g.firstLump.as<int32_t>(), g0, g1, base,
+                                                                       d.at(q0), ab + 2 * q0);
+  });
+}
+
+// ---- reverse-mode sweep of the factor (DESIGN.md sections 15 and 16) -----------------------------
+// P[q] = factorUpTo of the lumps < upToLump (read only); grad[q]: Lbar before the cut and Sbar behind
+// it on entry, the data gradient on return.  Per chunk: seed the trailing lumps, run the plan of the
+// cut on the selected-inversion scratch (chunks as selectedInverse), then the final pass over every
+// tile.  upToLump = numLumps is the sweep of the complete factor: the complete plan, nothing to seed.
+template <typename T>
+void hipBackendFactorAdjointUpTo(SymbolicCtx& sym, const T* const* L, T* const* G, int64_t batch, bool single,
+                                 int64_t upToLump) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  SelInvDev& d = selInvPlanUpTo(h, upToLump);
+  GradDev& g = gradPlan(h);
+  const int64_t chunk = selInvChunk(h, d, batch);
+  const BatchPtrs<const T> l = h.stage(L, batch, single);
+  const BatchPtrs<T> gr = h.stage(G, batch, single);
+  const hipk::SkelDev sk = h.skelDev();
+  const int64_t seed0 = g.lumpFirstTile[upToLump], nSeed = g.nTiles - seed0;
+  h.forChunks(batch, chunk, [&](int64_t q0, unsigned nm) {
+    const hipk::DataRef<T> gref = gr.at(q0);
+    if (nSeed > 0) {
+      hipk::cholAdjSeedTrailing<T><<<dim3((unsigned)nSeed, nm), 256, 0, stream>>>(
+          g.tiles.as<hipk::GradTile>() + seed0, sk, gref);
+    }
+    cholAdjLevels<T>(h, d, l.at(q0), gref, nm);
+    if (g.nTiles > 0) {
+      hipk::cholAdjFinal<T><<<dim3((unsigned)g.nTiles, nm), 256, 0, stream>>>(g.tiles.as<hipk::GradTile>(), sk,
+                                                                             gref);
+    }
+  });
+}
+
+// The trailing block (from the first scalar of lump `fromLump` on) of `batch` layout buffers to dense
+// symmetric m x m matrices (toDense), or the adjoint of that in the data-gradient convention
+// (!toDense: in = dense gradients, out = layout buffers, written whole).  dest: device permutation of
+// 0 .. m-1 or NULL.  One launch per chunk.
+template <typename T>
+void hipBackendSchurDense(SymbolicCtx& sym, const T* const* in, T* const* out, int64_t batch, bool single,
+                          int64_t fromLump, const int32_t* dest, bool toDense) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  const CoalescedBlockMatrixSkel& skel = h.skel;
+  h.checkDevice();
+  const hipk::SkelDev sk = h.skelDev();
+  const int64_t bar = skel.lumpStart[fromLump], m = skel.order() - bar;
+  BASPACHO_CHECK_LT(m, (int64_t)INT32_MAX);
+  const int64_t nT = (m + hipk::kSchurTile - 1) / hipk::kSchurTile, nPairs = nT * (nT + 1) / 2;
+  BASPACHO_CHECK_LT(nPairs, (int64_t)INT32_MAX);
+  GradDev* g = toDense ? nullptr : &gradPlan(h);
+  const int64_t nWork = toDense ? nPairs : g->nTiles;
+  if (nWork == 0) return;
+  const BatchPtrs<const T> i = h.stage(in, batch, single);
+  const BatchPtrs<T> o = h.stage(out, batch, single);
+  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+    if (toDense) {
+      hipk::schurToDense<T><<<dim3((unsigned)nPairs, nm), 256, 0, stream>>>(
+          sk, skel.lumpToSpan[fromLump], skel.numSpans(), bar, m, dest, i.at(q0), o.at(q0));
+    } else {
+      hipk::schurFromDense<T><<<dim3((unsigned)g->nTiles, nm), 256, 0, stream>>>(
+          g->tiles.as<hipk::GradTile>(), sk, (int)g->lumpFirstTile[fromLump], bar, m, dest, i.at(q0), o.at(q0));
+    }
+  });
+}
+
+// ---- assembly of coordinate entries (hip_assembly_kernels.h) ---------------
+// assemble (or its adjoint) of `batch` matrices: one launch per chunk
+template <typename T>
+void hipBackendAssemble(SymbolicCtx& sym, const AssemblyMap& m, const T* const* in, T* const* out, int64_t batch,
+                        bool single, bool adjoint) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  if (m.dev == nullptr) {
+    std::unique_ptr<HipAssemblyDev> d(new HipAssemblyDev);
+    d->upload(m);
+    m.dev = d.release();
+  }
+  const HipAssemblyDev& d = *m.dev;
+  if (adjoint && m.nnz == 0) return;
+  const BatchPtrs<const T> i = h.stage(in, batch, single);
+  const BatchPtrs<T> o = h.stage(out, batch, single);
+  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+    if (adjoint) {
+      const int64_t per = hipk::kAsmThreads * hipk::kAsmAdjPer;
+      hipk::assembleAdjointEntries<T><<<dim3((unsigned)((m.nnz + per - 1) / per), nm), hipk::kAsmThreads, 0,
+                                         stream>>>(m.nnz, d.entryOff.as<int64_t>(), i.at(q0), o.at(q0));
+    } else {
+      hipk::assembleTiles<T><<<dim3((unsigned)m.numTiles, nm), hipk::kAsmThreads, 0, stream>>>(
+          m.dataSize, d.tileFirst.as<int32_t>(), d.tileLongFirst.as<int32_t>(), d.runStart.as<int32_t>(),
+          d.runEntry.as<int32_t>(), d.destLocal.as<uint16_t>(), d.longDest.as<int32_t>(), i.at(q0), o.at(q0));
+    }
+  });
+}
+
+// ---- normal equations of a sparse Jacobian (hip_normal_eq_kernels.h) --------
+// one of the four operations on `batch` members: one launch per chunk
+template <typename T>
+void hipBackendNormalEq(SymbolicCtx& sym, const NormalEqMap& m, int32_t op, const T* const* values,
+                        const T* const* x, T* const* out, int64_t q, int64_t batch, bool single) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  if (m.dev == nullptr) m.dev = new HipNormalEqDev;
+  HipNormalEqDev& d = *m.dev;
+  if (op == NormalEqHessian && !d.hasForward) d.uploadForward(m);
+  if (op == NormalEqAdjoint && !d.hasAdjoint) d.uploadAdjoint(m);
+  if ((op == NormalEqJtVec || op == NormalEqJVec) && !d.hasVectors) d.uploadVectors(m);
+  const bool jt = op == NormalEqJtVec;
+  const int64_t numRuns = jt ? m.n : m.m;
+  if (op == NormalEqAdjoint && m.nnz == 0) return;
+  if (op == NormalEqHessian && m.numTiles == 0) return;
+  if ((op == NormalEqJtVec || op == NormalEqJVec) && numRuns * q == 0) return;
+  const BatchPtrs<const T> v = h.stage(values, batch, single), xs = h.stage(x, batch, single);
+  const BatchPtrs<T> o = h.stage(out, batch, single);
+  const int64_t shortWgs = (m.nnz + hipk::kAsmThreads - 1) / hipk::kAsmThreads;
+  const int64_t numLong = (int64_t)m.adjLong.size();
+  const int64_t longWgs = (numLong + hipk::kNeqWavesPerWg - 1) / hipk::kNeqWavesPerWg;
+  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+    if (op == NormalEqHessian) {
+      hipk::normalEqTiles<T><<<dim3((unsigned)m.numTiles, nm), hipk::kAsmThreads, 0, stream>>>(
+          m.dataSize, d.tileFirst.as<int32_t>(), d.tileLongFirst.as<int32_t>(), d.runStart.as<int32_t>(),
+          d.pairA.as<int32_t>(), d.pairB.as<int32_t>(), d.destLocal.as<uint16_t>(), d.longDest.as<int32_t>(),
+          v.at(q0), o.at(q0));
+    } else if (op == NormalEqAdjoint) {
+      hipk::normalEqAdjointEntries<T><<<dim3((unsigned)(shortWgs + longWgs), nm), hipk::kAsmThreads, 0, stream>>>(
+          m.nnz, (int32_t)shortWgs, (int32_t)numLong, d.adjStart.as<int64_t>(), d.adjPartner.as<int32_t>(),
+          d.adjDest.as<int64_t>(), d.adjLong.as<int32_t>(), v.at(q0), xs.at(q0), o.at(q0));
+    } else {
+      const int64_t wgs = (numRuns * q + hipk::kAsmThreads - 1) / hipk::kAsmThreads;
+      hipk::runDotVec<T><<<dim3((unsigned)wgs, nm), hipk::kAsmThreads, 0, stream>>>(
+          numRuns, (int32_t)q, (jt ? d.colStart : d.rowStart).template as<int32_t>(),
+          (jt ? d.colEntry : d.rowEntry).template as<int32_t>(), (jt ? d.colIdx : d.rowIdx).template as<int32_t>(),
+          v.at(q0), xs.at(q0), o.at(q0));
+    }
+  });
+}
+
+#define BSP_INSTANTIATE_EXTENSIONS(T)                                                                            \
+  template void hipBackendSelectedInverse<T>(SymbolicCtx&, T* const*, int64_t, bool);                           \
+  template void hipBackendLogDet<T>(SymbolicCtx&, const T* const*, int64_t, bool, T*);                          \
+  template void hipBackendPatternGrad<T>(SymbolicCtx&, const HipGradArgs<T>&, int64_t, bool);                   \
+  template void hipBackendFactorStatus<T>(SymbolicCtx&, const T* const*, int64_t, bool, int64_t, int64_t,       \
+                                          int64_t*);                                                            \
+  template void hipBackendDampDiagonal<T>(SymbolicCtx&, T* const*, int64_t, bool, int64_t, int64_t, const T*);  \
+  template void hipBackendFactorAdjointUpTo<T>(SymbolicCtx&, const T* const*, T* const*, int64_t, bool, int64_t); \
+  template void hipBackendSelectedInverseAdjoint<T>(SymbolicCtx&, const T* const*, const T* const*, T* const*,  \
+                                                    int64_t, bool);                                             \
+  template void hipBackendSchurDense<T>(SymbolicCtx&, const T* const*, T* const*, int64_t, bool, int64_t,       \
+                                        const int32_t*, bool);                                                  \
+  template void hipBackendAssemble<T>(SymbolicCtx&, const AssemblyMap&, const T* const*, T* const*, int64_t,    \
+                                      bool, bool);                                                              \
+  template void hipBackendNormalEq<T>(SymbolicCtx&, const NormalEqMap&, int32_t, const T* const*,               \
+                                      const T* const*, T* const*, int64_t, int64_t, bool);
+BSP_INSTANTIATE_EXTENSIONS(double)
+BSP_INSTANTIATE_EXTENSIONS(float)
+#undef BSP_INSTANTIATE_EXTENSIONS
+
+void hipBackendFreeAssembly(HipAssemblyDev* dev) { delete dev; }
+void hipBackendFreeNormalEq(HipNormalEqDev* dev) { delete dev; }
+
+}  // namespace BaSpaCho

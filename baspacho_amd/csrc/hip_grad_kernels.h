@@ -30,7 +30,7 @@
 
 #include <cstdint>
 
-#include "hip_kernels.h"
+#include "hip_device_common.h"
 
 namespace BaSpaCho {
 namespace hipk {

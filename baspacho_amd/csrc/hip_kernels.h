@@ -11,42 +11,18 @@
 
 #include <cstdint>
 
+#include "hip_device_common.h"
 #include "hip_plan.h"
 
 namespace BaSpaCho {
 namespace hipk {
 
-// One matrix (single) or a batch of identical-structure matrices (many, indexed by blockIdx.y);
-// replaces the Plain/Batched policy structs of MatOpsCuda.cu:345-368.
 #ifndef BSP_BULK_AUX
 #define BSP_BULK_AUX 0  // cache policy of the bulk tile's operand loads (global_load_lds aux: 1 sc0, 2 nt, 16 sc1)
 #endif
 #ifndef BSP_TILE_PRIO
 #define BSP_TILE_PRIO 2  // s_setprio of the chain launches' tile workgroups (the potrf / trsm ones: 3)
 #endif
-
-template <typename T>
-struct DataRef {
-  T* single;
-  T* const* many;
-};
-
-// Pointers that come out of memory (the batch's pointer array) or out of a select are "generic" to
-// the compiler, and every access through them becomes a FLAT instruction, which counts against the
-// LDS counter as well: each wait for an LDS read then also waits for the global loads in flight
-// (the prefetch of the next K chunk, the operands of the next pairs ...).  The round trip through
-// the global address space tells the compiler where the data lives; accesses become global_*.
-// (a cast to the global address space and back is folded away: the pointers have to KEEP the
-// address-space type down to the access, hence GP<T> throughout the kernels)
-template <typename T>
-using GP = __attribute__((address_space(1))) T*;
-
-template <typename T>
-__device__ __forceinline__ GP<T> pickData(const DataRef<T>& d) {
-  return (GP<T>)(d.many ? d.many[blockIdx.y] : d.single);
-}
-__device__ __forceinline__ void atomicSub(GP<double> p, double v) { unsafeAtomicAdd((double*)p, -v); }
-__device__ __forceinline__ void atomicSub(GP<float> p, float v) { unsafeAtomicAdd((float*)p, -v); }
 
 // COOPERATIVE CU YIELD.  fp64 MFMA and fp64 VALU instructions go through the same pipe of a SIMD,
 // and an MFMA in flight is not pre-empted: while a bulk-update wave runs its K loop on a SIMD, every
@@ -78,54 +54,6 @@ __device__ __forceinline__ void yieldWhile(const unsigned* flag, unsigned key) {
     if ((unsigned)__builtin_amdgcn_readfirstlane((int)yieldPeek(flag)) != key) break;
   }
 }
-
-__device__ __forceinline__ void waveSync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// workgroup barrier that orders LDS traffic only: __syncthreads() also drains the vector-memory
-// counter, i.e. it waits for every global store in flight (hundreds of cycles when a kernel
-// stores to memory between barriers, as the panel Cholesky does with its finished columns)
-__device__ __forceinline__ void ldsBarrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// 1/sqrt(x): hardware estimate (v_rsq_f64 / v_rsq_f32) refined by Newton steps to full precision.
-// The library rsqrt() expands to a full-precision sqrt plus a division (hundreds of dependent
-// cycles), which sits on the serial critical path of the panel Cholesky.
-__device__ __forceinline__ double fastRsqrt(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-#pragma unroll
-  for (int it = 0; it < 2; it++) {
-    const double r = fma(-0.5 * x * y, y, 0.5);  // 0.5 - 0.5 x y^2
-    y = fma(y, r, y);
-  }
-  return y;
-}
-__device__ __forceinline__ float fastRsqrt(float x) {
-  float y = __builtin_amdgcn_rsqf(x);
-  const float r = fmaf(-0.5f * x * y, y, 0.5f);
-  return fmaf(y, r, y);
-}
-
-__device__ __forceinline__ void atomicSub(double* p, double v) { unsafeAtomicAdd(p, -v); }
-__device__ __forceinline__ void atomicSub(float* p, float v) { unsafeAtomicAdd(p, -v); }
-
-// device view of the int64 skeleton arrays (also what deviceAccessor() hands out)
-struct SkelDev {
-  const int64_t* spanStart;
-  const int64_t* spanToLump;
-  const int64_t* lumpStart;
-  const int64_t* spanOffsetInLump;
-  const int64_t* chainColPtr;
-  const int64_t* chainRowSpan;
-  const int64_t* chainData;
-  const int64_t* chainRowsTillEnd;
-  const int64_t* boardColPtr;
-  const int64_t* boardChainColOrd;
-};
 
 // ------------------------------------------------------------------------------------------
 // K1  sparse-elimination lump factor: potrf of the small diagonal block + solve of every row
@@ -401,31 +329,6 @@ __global__ __launch_bounds__(256) void elimUpdate(SkelDev sk, const int32_t* cha
     }
   }
 }
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
-typedef float float4_t __attribute__((ext_vector_type(4)));
-
-template <typename T>
-struct Mfma;
-template <>
-struct Mfma<double> {
-  using Acc = double4_t;
-  static __device__ __forceinline__ Acc run(double a, double b, Acc c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int reg) { return (lane >> 4) + 4 * reg; }
-  // inverse of (q, reg) -> row: the m with row(16 q + *, reg) == m has 4 q + reg == colOfRow(m)
-  static __device__ __forceinline__ int colOfRow(int m) { return 4 * (m & 3) + (m >> 2); }
-};
-template <>
-struct Mfma<float> {
-  using Acc = float4_t;
-  static __device__ __forceinline__ Acc run(float a, float b, Acc c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int reg) { return 4 * (lane >> 4) + reg; }
-  static __device__ __forceinline__ int colOfRow(int m) { return m; }
-};
 
 
 // ------------------------------------------------------------------------------------------
@@ -873,20 +776,6 @@ struct NoPreUpdate {
 // wave w inverts block w and writes it to dinvOut[w][16][16] -- the trsm of this panel then
 // multiplies by the inverses (trsmStages) instead of substituting.
 constexpr int kInvLd = 17;
-constexpr int kDinvSlot = 4 * 16 * 16;        // one panel's inverted diagonal blocks
-constexpr int kDinvBatchStride = 2 * kDinvSlot;  // two slots (alternating panels) per matrix
-template <typename T>
-__device__ __forceinline__ T readLaneT(T v, int srcLane);
-template <>
-__device__ __forceinline__ double readLaneT<double>(double v, int srcLane) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), srcLane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), srcLane);
-  return __hiloint2double(hi, lo);
-}
-template <>
-__device__ __forceinline__ float readLaneT<float>(float v, int srcLane) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), srcLane));
-}
 // lane n (= lane % 16, every group of 16 lanes does the same work) solves L y = e_n for the 16x16
 // lower-triangular block at Lb (row stride ldl), right-looking, in registers: y = column n of L^-1
 template <typename T>
@@ -1536,7 +1425,6 @@ __global__ __launch_bounds__(256) void trsmPanelDirect(PanelDesc pd, DataRef<T> 
 #else
 #define UPD_STAMP(slot, val)
 #endif
-constexpr int kUpdChunk = 32;  // K chunk of updateTile: 2 x 64 x 34 doubles = 35 KB LDS -> 4 WG/CU
 // PREFETCH: the next K chunk is requested before the current one is multiplied.  For launches of
 // at most ~2 rounds of workgroups (small batches, the top of an elimination tree) a tile's time is
 // its chain of dependent memory round trips -- one per K chunk -- and this overlaps them with the

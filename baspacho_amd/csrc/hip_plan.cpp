@@ -1182,4 +1182,217 @@ SelInvPlanHost buildSelInvPlan(const CoalescedBlockMatrixSkel& sk, int64_t upToL
   return p;
 }
 
+
+LaunchTables buildLaunchTables(const HipPlanHost& host) {
+  LaunchTables tab;
+  vector<int32_t>& foldRank = tab.foldRank;
+  vector<int64_t>&foldTiles = tab.foldTiles, &foldPanelEnd = tab.foldPanelEnd, &slowPrefix = tab.slowPrefix;
+  std::map<int64_t, std::pair<int64_t, int64_t>>& splitRange = tab.splitRange;
+  {
+    // the factor kernels of multi-panel levels read self-contained records (one uniform load
+    // instead of index -> descriptor); the solve kernels keep the index lists
+    vector<PanelDesc> lp(host.levelPanels.size());
+    for (size_t i = 0; i < lp.size(); i++) lp[i] = host.panels[host.levelPanels[i]];
+    vector<TrsmTaskFat> tf(host.trsmTasks.size());
+    for (size_t i = 0; i < tf.size(); i++) {
+      const PanelDesc& pd = host.panels[host.trsmTasks[i].panel];
+      tf[i] = TrsmTaskFat{pd.diagOff, pd.lda, pd.nb, pd.rowsBelow, host.trsmTasks[i].rowTile, 0, 0};
+    }
+    tab.trsmTasksFat = std::move(tf);
+    // levels whose potrf may be folded into their trsm launch
+    foldRank.assign(host.levels.size(), -1);
+    vector<std::pair<int64_t, size_t>> cand;  // (row tiles, level)
+    for (size_t li = 0; li < host.levels.size(); li++) {
+      const LevelRange& lr = host.levels[li];
+      const int64_t nT = lr.trsmEnd - lr.trsmBegin;
+      if (lr.tail || lr.directPanel >= 0 || lr.panelEnd <= lr.panelBegin || nT < 1 || nT > kFoldMaxTiles) continue;
+      bool allBelow = true;
+      for (int64_t q = lr.panelBegin; q < lr.panelEnd; q++) allBelow = allBelow && lp[q].rowsBelow > 0;
+      if (allBelow) cand.push_back({nT, li});
+    }
+    std::stable_sort(cand.begin(), cand.end());
+    vector<PanelDesc> fd;
+    foldTiles.clear();
+    foldPanelEnd.clear();
+    for (size_t k = 0; k < cand.size(); k++) {
+      const LevelRange& lr = host.levels[cand[k].second];
+      foldRank[cand[k].second] = (int32_t)k;
+      fd.insert(fd.end(), lp.begin() + lr.panelBegin, lp.begin() + lr.panelEnd);
+      foldTiles.push_back(cand[k].first);
+      foldPanelEnd.push_back((int64_t)fd.size());
+    }
+    tab.foldDescs = std::move(fd);
+    tab.levelPanelDescs = std::move(lp);
+  }
+  {
+    vector<UpdTaskFat> fat(host.updTasks.size());
+    vector<UpdTaskWide> wide(host.updTasks.size());
+    slowPrefix.assign(host.updTasks.size() + 1, 0);
+    for (size_t i = 0; i < host.updTasks.size(); i++) {
+      const UpdTask& t = host.updTasks[i];
+      const SegDesc& sd = host.segs[t.seg];
+      const SrcDesc& sr = host.srcs[sd.src];
+      UpdTaskFat& f = fat[i];
+      f.srcOff = sr.off;
+      f.tgtBase = sd.tgtBase;
+      f.lda = sr.lda;
+      f.K = sr.K;
+      f.rowsBelow = sr.rowsBelow;
+      f.segEnd = sd.q0 + sd.m;
+      f.rowTile = t.rowTile;
+      f.colTile = t.colTile;
+      f.tgtStride = sd.tgtStride;
+      f.rowMin = sd.rowMin;
+      f.atomic = t.atomic;
+      f.fast = sd.kind == kSegIntra && sr.K > 0 && sr.K % hipk::kUpdChunk == 0;
+      f.pad0 = f.pad1 = 0;
+      slowPrefix[i + 1] = slowPrefix[i] + (f.fast ? 0 : 1);
+      UpdTaskWide& w = wide[i];
+      w.srcOff = sr.off;
+      w.tgtBase = sd.tgtBase;
+      w.chainTabPtr = sd.chainTabPtr;
+      w.lda = sr.lda;
+      w.K = sr.K;
+      w.rowsBelow = sr.rowsBelow;
+      w.nRest = sr.nRest;
+      w.lumpRowBase = sr.lumpRowBase;
+      w.kind = sd.kind;
+      w.segEnd = sd.q0 + sd.m;
+      w.tgtStride = sd.tgtStride;
+      w.firstChainOrd = sd.firstChainOrd;
+      w.rowMin = sd.rowMin;
+      w.rowTile = t.rowTile;
+      w.colTile = t.colTile;
+      w.atomic = t.atomic;
+      w.pad0 = w.pad1 = w.pad2 = w.pad3 = w.pad4 = 0;
+    }
+    tab.updTasksFat = std::move(fat);
+    // SPLIT-K lists (round 5) for the multi-panel levels of latency-bound structures.  A tile of a
+    // block-wide source walks its K = 128 .. 256 columns in chunks of 32, one exposed memory round trip
+    // per chunk (1.6 us, tools/trace_upd.py): 17-19 us per launch where a level of rank-64 tiles takes
+    // 10, on a GPU that is mostly idle.  For small levels every such tile is listed again as ceil(K /
+    // 96) tiles of at most 96 source columns each that accumulate with atomics; launchLevels takes
+    // that list when the launch (tiles x batch) stays within a round of workgroups.
+    vector<UpdTaskWide> split;
+    auto addSplit = [&](const vector<LevelRange>& levels) {
+      for (const LevelRange& lr : levels) {
+        const int64_t n = lr.updEnd - lr.updBegin;
+        if (lr.directPanel >= 0 || n <= 0 || n > kSplitMaxTiles) continue;
+        int64_t extra = 0;
+        for (int64_t i = lr.updBegin; i < lr.updEnd; i++) {
+          if (wide[i].K >= kSplitMinK) extra += (wide[i].K + kSplitK - 1) / kSplitK - 1;
+        }
+        if (extra == 0 || n + extra > 2 * kSplitMaxTiles) continue;
+        const int64_t b = (int64_t)split.size();
+        for (int64_t i = lr.updBegin; i < lr.updEnd; i++) {
+          const UpdTaskWide& w = wide[i];
+          if (w.K < kSplitMinK) {
+            split.push_back(w);
+            continue;
+          }
+          for (int32_t k0 = 0; k0 < w.K; k0 += kSplitK) {
+            UpdTaskWide p = w;
+            p.srcOff = w.srcOff + k0;
+            p.K = std::min<int32_t>(kSplitK, w.K - k0);
+            p.atomic = w.atomic | 1;
+            split.push_back(p);
+          }
+        }
+        splitRange[lr.updBegin] = {b, (int64_t)split.size()};
+      }
+    };
+    for (const auto& er : host.elimRanges) addSplit(er.bigLevels);
+    addSplit(host.levels);
+    tab.updTasksSplit = std::move(split);
+    tab.updTasksWide = std::move(wide);
+  }
+  return tab;
+}
+
+// The steps of a level list.  Consecutive one-panel levels that make up one outer block of a wide
+// lump are solved as a block (2 launches per 256 columns instead of 8); withSweeps: a run of
+// one-panel levels of one lump that is at least sweepMinWidth columns wide is ONE persistent launch.
+SolveSchedule buildSolveSchedule(const HipPlanHost& plan, const vector<LevelRange>& levels,
+                                 const SolveScheduleOptions& o) {
+  SolveSchedule ent;
+  const int64_t nL = (int64_t)levels.size();
+  vector<PanelDesc>& list = ent.invPanels;
+  auto colOf = [&](const PanelDesc& p) { return p.lda - p.nRest - p.nb; };  // column inside its lump
+  for (int64_t l = 0; l < nL;) {
+    SolveSchedItem it;
+    it.l = l;
+    it.e = l + 1;
+    if (o.withSweeps && levels[l].directPanel >= 0) {
+      const PanelDesc& p0 = plan.panels[levels[l].directPanel];
+      int64_t e = l + 1;
+      int w = p0.nb;
+      while (e < nL && levels[e].directPanel >= 0) {
+        const PanelDesc& pe = plan.panels[levels[e].directPanel];
+        if (pe.lump != p0.lump || colOf(pe) != colOf(p0) + w) break;
+        if (plan.panels[levels[e - 1].directPanel].nb != kPanelWidth) break;
+        w += pe.nb;
+        e++;
+      }
+      if (w >= o.sweepMinWidth) {
+        const PanelDesc& last = plan.panels[levels[e - 1].directPanel];
+        it.kind = SolveSchedItem::kSweep;
+        it.e = e;
+        it.slot = (int32_t)list.size();
+        hipk::SweepDesc& sd = it.sweep;
+        sd.diagOff = p0.diagOff;
+        sd.lda = p0.lda;
+        sd.w = w;
+        sd.rowsBelow = last.rowsBelow;
+        sd.nRest = last.nRest;
+        sd.lumpRowBase = last.lumpRowBase;
+        sd.vecOff = p0.vecOff;
+        sd.nBlocks = (w + hipk::kSweepW - 1) / hipk::kSweepW;
+        sd.invSlot = it.slot;
+        sd.xchgOff = (int32_t)ent.sweepInstStride;
+        sd.ticketOff = 0;  // (set per call: depends on the number of instances)
+        ent.sweepInstStride += 2 * (int64_t)sd.nBlocks * hipk::kSweepW;
+        it.sweepFwdWgs = hipk::kSweepFwdGroup * sd.nBlocks +
+                         (sd.rowsBelow + hipk::kSweepFarRows - 1) / hipk::kSweepFarRows;
+        it.sweepBwdWgs = hipk::kSweepBwdGroup * sd.nBlocks;
+        ent.maxSweepWgs = std::max<int64_t>(ent.maxSweepWgs, std::max(it.sweepFwdWgs, it.sweepBwdWgs));
+        ent.maxSweepWgsM = std::max<int64_t>(ent.maxSweepWgsM,
+                                             std::max<int64_t>(it.sweepFwdWgs, hipk::kSweepFwdGroup * sd.nBlocks));
+        ent.maxSweepW = std::max(ent.maxSweepW, sd.w);
+        ent.maxSweepBelow = std::max(ent.maxSweepBelow, sd.rowsBelow);
+        ent.numSweeps++;
+        for (int64_t q = l; q < e; q++) list.push_back(plan.panels[levels[q].directPanel]);
+        ent.items.push_back(it);
+        l = e;
+        continue;
+      }
+    }
+    if (o.blockSolve && levels[l].directPanel >= 0) {
+      const PanelDesc& p0 = plan.panels[levels[l].directPanel];
+      const int c0 = colOf(p0);
+      if (c0 % kOuterWidth == 0) {
+        int64_t e = l + 1;
+        while (e < nL && levels[e].directPanel >= 0) {
+          const PanelDesc& pe = plan.panels[levels[e].directPanel];
+          const int ce = colOf(pe);
+          if (pe.lump != p0.lump || ce != c0 + (int)(e - l) * kPanelWidth || ce >= c0 + kOuterWidth) {
+            break;
+          }
+          e++;
+        }
+        it.e = e;
+      }
+    }
+    if (it.e - it.l >= 2) {
+      it.kind = SolveSchedItem::kBlockGroup;
+      if (o.inverses) {
+        it.slot = (int32_t)list.size();
+        for (int64_t q = it.l; q < it.e; q++) list.push_back(plan.panels[levels[q].directPanel]);
+      }
+    }
+    ent.items.push_back(it);
+    l = it.e;
+  }
+  return ent;
+}
+
 }  // namespace BaSpaCho

@@ -14,6 +14,8 @@
 #pragma once
 
 #include <cstdint>
+#include <map>
+#include <utility>
 #include <vector>
 
 #include "skeleton.h"
@@ -25,6 +27,47 @@ constexpr int kOuterWidth = 256;  // outer block: panels update only their own o
                                   // away; everything to its right gets ONE rank-256 update
 constexpr int kTile = 64;         // update tile (rows x cols) and trsm row tile
 constexpr int kElimSmallMax = 16; // widest lump handled by the small sparse-elim kernels
+// split-K task lists of small multi-panel levels (buildLaunchTables): levels of at most this many tiles
+constexpr int64_t kSplitMaxTiles = 512;
+// (GRID 82x82, slices of 32 / 64 / 96 / 128 / 160 columns: 1.208 / 1.149 / 1.135 / 1.140 / 1.163 against
+//  1.180 ms without; profiles/r05_ab_split_k.txt)
+constexpr int32_t kSplitMinK = 128, kSplitK = 96;
+// potrf folded into the trsm launch of small multi-panel levels: levels of at most this many row tiles
+constexpr int64_t kFoldMaxTiles = 512;
+
+// What the planner shares with the kernels, under the names the kernels know them by (SweepDesc is a
+// kernel parameter: its qualified name is part of the kernels' symbols)
+namespace hipk {
+
+constexpr int kUpdChunk = 32;  // K chunk of updateTile: 2 x 64 x 34 doubles = 35 KB LDS -> 4 WG/CU
+
+// scratch of the chain kernels (sized by the context before the first factor)
+constexpr int kDinvSlot = 4 * 16 * 16;        // one panel's inverted diagonal blocks
+constexpr int kDinvBatchStride = 2 * kDinvSlot;  // two slots (alternating panels) per matrix
+
+// geometry of the persistent solve sweeps (hip_sweep_kernels.h)
+constexpr int kSweepQ = 3;                                  // panels per block
+constexpr int kSweepW = kSweepQ * kPanelWidth;              // columns per step
+constexpr int kSweepFarRows = 48;                           // forward far tile: 3 compute waves x 16 rows
+constexpr int kSweepFarPerBlock = kSweepW / kSweepFarRows;  // 4
+constexpr int kSweepFwdGroup = kSweepFarPerBlock + 1;       // roles per block, forward
+constexpr int kSweepBwdGroup = kSweepQ + 1;                 // ... backward (3 column tiles + spine)
+
+struct SweepDesc {
+  int64_t diagOff;      // data offset of element (0, 0) of the run
+  int32_t lda;          // row stride (lump width)
+  int32_t w;            // columns of the run
+  int32_t rowsBelow;    // rows below the run (rest of the lump + its chain rows)
+  int32_t nRest;        // of which inside the lump (linear addressing)
+  int32_t lumpRowBase;  // as PanelDesc
+  int32_t vecOff;       // position of the run's first column in the vector
+  int32_t nBlocks;      // ceil(w / kSweepW)
+  int32_t invSlot;      // slot of the run's first panel in the inverse scratch
+  int32_t xchgOff;      // element offset of the run's area inside an instance's slice of the exchange buffer
+  int32_t ticketOff;    // index of the run's first ticket word (one per instance)
+};
+
+}  // namespace hipk
 
 struct PanelDesc {
   int64_t diagOff;     // data offset of the nb x nb diagonal block of the panel
@@ -350,6 +393,62 @@ struct SolveGatherPlan {
   std::vector<RangeWide> rangeWide;
 };
 SolveGatherPlan buildSolveGather(const CoalescedBlockMatrixSkel& skel, const HipPlanHost& plan);
+
+// ------------------------------------------------------------------------------------------
+// LAUNCH TABLES of a factor plan: what the launch code derives from a HipPlanHost before it uploads
+// it (self-contained task records, the split-K lists, the order in which levels fold their potrf).
+struct LaunchTables {
+  // the factor kernels of multi-panel levels read self-contained records (one uniform load
+  // instead of index -> descriptor); the solve kernels keep the index lists
+  std::vector<PanelDesc> levelPanelDescs;
+  std::vector<TrsmTaskFat> trsmTasksFat;
+  std::vector<UpdTaskFat> updTasksFat;
+  std::vector<UpdTaskWide> updTasksWide;
+  std::vector<int64_t> slowPrefix;  // tasks [0, i) that updateTileBulk cannot take
+  // split-K task lists of small multi-panel levels: level's updBegin -> [begin, end) in updTasksSplit
+  std::vector<UpdTaskWide> updTasksSplit;
+  std::map<int64_t, std::pair<int64_t, int64_t>> splitRange;
+  // POTRF FOLDED INTO THE TRSM LAUNCH of small multi-panel levels (trsmPanelPotrf, round 6): the levels
+  // of host.levels that may take it (every panel has rows below, at most kFoldMaxTiles row tiles),
+  // sorted by their number of row tiles -- the levels a call of batch b folds (tiles x b <=
+  // kFoldMaxTiles) are then a PREFIX of this order, and so are their panels' descriptors in
+  // foldDescs, which ONE potrfPanel launch at the end of the factorisation walks to store the factors
+  std::vector<PanelDesc> foldDescs;
+  std::vector<int32_t> foldRank;      // per level of host.levels: position in the sorted order, -1: not foldable
+  std::vector<int64_t> foldTiles;     // sorted order: row tiles of the level
+  std::vector<int64_t> foldPanelEnd;  // ... panels of the levels up to and including this one
+};
+LaunchTables buildLaunchTables(const HipPlanHost& host);
+
+// ------------------------------------------------------------------------------------------
+// SOLVE SCHEDULE of a level list of a plan (the plan's own levels, or an elimination range's bigLevels).
+// one step of the dense part of a solve (denseLevels): a level, a block group of a wide lump (K-B1i /
+// K-B2, two launches per 256 columns) or a whole run of one-panel levels as ONE persistent sweep
+// (hip_sweep_kernels.h)
+struct SolveSchedItem {
+  enum Kind : int32_t { kLevel = 0, kBlockGroup = 1, kSweep = 2 };
+  int32_t kind = kLevel;
+  int32_t slot = -1;  // first slot in the inverse scratch (block groups through inverses, sweeps)
+  int64_t l = 0, e = 0;  // levels [l, e)
+  hipk::SweepDesc sweep{};
+  int32_t sweepFwdWgs = 0, sweepBwdWgs = 0;
+};
+struct SolveScheduleOptions {
+  bool withSweeps = false;   // runs of one-panel levels at least sweepMinWidth wide as persistent sweeps
+  bool blockSolve = true;    // one-panel levels of an outer block as block groups
+  bool inverses = true;      // block groups through inverted diagonal blocks (they get a slot)
+  int sweepMinWidth = 768;
+};
+struct SolveSchedule {
+  std::vector<SolveSchedItem> items;
+  std::vector<PanelDesc> invPanels;  // the panels whose diagonal blocks are inverted, in slot order
+  int32_t numSweeps = 0;
+  int64_t sweepInstStride = 0;  // values per (right-hand side, batch entry) of the exchange buffer
+  int64_t maxSweepWgs = 0, maxSweepWgsM = 0;  // (M: the matrix-core sweep, hip_sweep_mfma.h)
+  int32_t maxSweepW = 0, maxSweepBelow = 0;
+};
+SolveSchedule buildSolveSchedule(const HipPlanHost& plan, const std::vector<LevelRange>& levels,
+                                 const SolveScheduleOptions& o);
 
 // ------------------------------------------------------------------------------------------
 // SELECTED INVERSION (hip_selinv_kernels.h): Z = A^-1 on the pattern of L, in place.  Lumps are taken

@@ -24,7 +24,7 @@
 
 #include <cstdint>
 
-#include "hip_kernels.h"
+#include "hip_device_common.h"
 #include "hip_plan.h"
 
 namespace BaSpaCho {

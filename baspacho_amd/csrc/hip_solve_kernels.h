@@ -6,7 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "hip_kernels.h"
+#include "hip_device_common.h"
 
 namespace BaSpaCho {
 namespace hipk {

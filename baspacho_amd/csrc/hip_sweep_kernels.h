@@ -38,27 +38,7 @@
 namespace BaSpaCho {
 namespace hipk {
 
-constexpr int kSweepQ = 3;                                  // panels per block
-constexpr int kSweepW = kSweepQ * kPanelWidth;              // columns per step
-constexpr int kSweepFarRows = 48;                           // forward far tile: 3 compute waves x 16 rows
-constexpr int kSweepFarPerBlock = kSweepW / kSweepFarRows;  // 4
-constexpr int kSweepFwdGroup = kSweepFarPerBlock + 1;       // roles per block, forward
-constexpr int kSweepBwdGroup = kSweepQ + 1;                 // ... backward (3 column tiles + spine)
 constexpr int kSweepLdsHead = 256;                          // far roles: progress word + partial sums (values)
-
-struct SweepDesc {
-  int64_t diagOff;      // data offset of element (0, 0) of the run
-  int32_t lda;          // row stride (lump width)
-  int32_t w;            // columns of the run
-  int32_t rowsBelow;    // rows below the run (rest of the lump + its chain rows)
-  int32_t nRest;        // of which inside the lump (linear addressing)
-  int32_t lumpRowBase;  // as PanelDesc
-  int32_t vecOff;       // position of the run's first column in the vector
-  int32_t nBlocks;      // ceil(w / kSweepW)
-  int32_t invSlot;      // slot of the run's first panel in the inverse scratch
-  int32_t xchgOff;      // element offset of the run's area inside an instance's slice of the exchange buffer
-  int32_t ticketOff;    // index of the run's first ticket word (one per instance)
-};
 
 struct SweepShared {
   unsigned* ctl;        // word 0: abort (armed = all ones, 0 = abort); words 1..: tickets
@@ -69,84 +49,6 @@ struct SweepShared {
   int32_t pad;
   long long* trace;     // developer aid (BSP_SWEEP_TRACE=1): per spine {start, loaded, polled, done}, 100 MHz
 };
-
-template <typename T>
-struct SweepBits;
-template <>
-struct SweepBits<double> {
-  using U = unsigned long long;
-  static constexpr U kArmed = ~0ull, kNan = 0x7ff8000000000000ull;
-};
-template <>
-struct SweepBits<float> {
-  using U = unsigned;
-  static constexpr U kArmed = ~0u, kNan = 0x7fc00000u;
-};
-
-template <typename T>
-__device__ __forceinline__ T sweepPeek(GP<const T> p) {
-  using U = typename SweepBits<T>::U;
-  const U u = __hip_atomic_load((GP<const U>)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return __builtin_bit_cast(T, u);
-}
-template <typename T>
-__device__ __forceinline__ bool sweepValid(T v) {
-  using U = typename SweepBits<T>::U;
-  return __builtin_bit_cast(U, v) != SweepBits<T>::kArmed;
-}
-template <typename T>
-__device__ __forceinline__ void sweepPublish(GP<T> p, T v) {
-  using U = typename SweepBits<T>::U;
-  U u = __builtin_bit_cast(U, v);
-  if (u == SweepBits<T>::kArmed) u = SweepBits<T>::kNan;
-  __hip_atomic_store((GP<U>)p, u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-struct SweepWatch {
-  GP<unsigned> abortWord;
-  unsigned* hostErr;
-  long long limit;
-  long long t0;
-  unsigned it;
-  __device__ __forceinline__ void reset() {
-    t0 = 0;
-    it = 0;
-  }
-  // after an unsuccessful poll: true = give up (wave-uniform)
-  __device__ __forceinline__ bool expired() {
-    if ((++it & 15u) != 0u) return false;
-    if (__hip_atomic_load(abortWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return true;
-    const long long now = (long long)wall_clock64();
-    if (t0 == 0) {
-      t0 = now;
-      return false;
-    }
-    if (now - t0 <= limit) return false;
-    __hip_atomic_store(abortWord, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(hostErr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    return true;
-  }
-};
-
-// every lane polls its own N words until all of them (in every lane) have been published
-template <typename T, int N>
-__device__ __forceinline__ bool sweepWait(GP<const T> (&p)[N], const bool (&need)[N], T (&out)[N],
-                                          SweepWatch& watch) {
-  watch.reset();
-  for (;;) {
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-      if (need[i]) {
-        out[i] = sweepPeek<T>(p[i]);
-        ok = ok && sweepValid(out[i]);
-      }
-    }
-    if (__all(ok)) return true;
-    if (watch.expired()) return false;
-    __builtin_amdgcn_s_sleep(1);
-  }
-}
 
 // ---- sum 16 per-lane values across the 64 lanes, 16 sums at once, WITHOUT the LDS crossbar ----------
 // waveSum16 (hip_solve_kernels.h) is 17 __shfl_xor = 34 ds_bpermute for doubles, a dependent chain

@@ -38,7 +38,6 @@
 #include <hip/hip_runtime.h>
 
 #include "hip_kernels.h"
-#include "hip_sweep_kernels.h"
 
 namespace BaSpaCho {
 namespace hipk {

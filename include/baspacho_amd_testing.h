@@ -33,6 +33,33 @@ int bsp_test_selinv_plan(const bsp_solver* s, int64_t* buf, int64_t capacity, in
  * span that bsp_factor_up_to_* refuses gives a non-zero return. */
 int bsp_test_selinv_plan_up_to(const bsp_solver* s, int64_t span, int64_t* buf, int64_t capacity, int64_t* needed);
 
+/* The launch tables of the factor plan over every lump (buildLaunchTables, csrc/hip_plan.cpp: what the
+ * launch code uploads beside the plan), built on the host with no device involved.  Layout (int64):
+ *   nLevels, nMainLevels, nLevelPanels, nTrsmTasks, nUpdTasks (of the plan), then the lengths of
+ *   levelPanelDescs, trsmTasksFat, updTasksFat, updTasksWide, slowPrefix, updTasksSplit, splitRange,
+ *   foldRank, foldTiles, foldPanelEnd, foldDescs;
+ *   nLevels records {elimination range or -1, tail, directPanel, panelBegin, panelEnd, trsmBegin, trsmEnd,
+ *     updBegin, updEnd}: the bigLevels of every elimination range, then the plan's own (main) levels;
+ *   levelPanelDescs {diagOff, lda, nb, rowsBelow, nRest, lumpRowBase, lump, vecOff};
+ *   trsmTasksFat {diagOff, lda, nb, rowsBelow, rowTile};
+ *   updTasksFat {srcOff, tgtBase, lda, K, rowsBelow, segEnd, rowTile, colTile, tgtStride, rowMin, atomic, fast};
+ *   updTasksWide {srcOff, tgtBase, chainTabPtr, lda, K, rowsBelow, nRest, lumpRowBase, kind, segEnd, tgtStride,
+ *     firstChainOrd, rowMin, rowTile, colTile, atomic};
+ *   slowPrefix; updTasksSplit (as updTasksWide); splitRange {updBegin, begin, end}; foldRank; foldTiles;
+ *   foldPanelEnd; foldDescs (as levelPanelDescs).
+ * buf / capacity / needed as bsp_test_selinv_plan. */
+int bsp_test_launch_tables(const bsp_solver* s, int64_t* buf, int64_t capacity, int64_t* needed);
+/* The solve schedule of the same plan's main levels (buildSolveSchedule) under the given switches.
+ * Layout (int64):
+ *   nLevels, nItems, nInvPanels, numSweeps, sweepInstStride, maxSweepWgs, maxSweepWgsM, maxSweepW, maxSweepBelow;
+ *   nLevels records {panels, lump, column inside the lump, nb, rowsBelow} (the last four of the level's
+ *     one panel, -1 for a level of several);
+ *   nItems records {kind (0 level, 1 block group, 2 sweep), slot, l, e, sweep w, nBlocks, rowsBelow, invSlot,
+ *     xchgOff, forward workgroups, backward workgroups};
+ *   nInvPanels records {lump, column inside the lump, nb, rowsBelow}. */
+int bsp_test_solve_schedule(const bsp_solver* s, int32_t with_sweeps, int32_t block_solve, int32_t inverses,
+                            int32_t sweep_min_width, int64_t* buf, int64_t capacity, int64_t* needed);
+
 /* Caps the chunk of a batched selected inversion (bsp_selected_inverse_batched_*) at `max_matrices`
  * matrices, so that tests can force several chunks on small batches; 0 = the product's rule. */
 int bsp_test_set_selinv_batch_chunk(bsp_solver* s, int32_t max_matrices);

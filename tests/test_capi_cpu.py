@@ -63,6 +63,9 @@ def test_retired_option_keeps_its_slot_and_is_not_an_option():
     with pytest.raises(ValueError, match="unknown backend option 'gather_overlap'"):
         B.create_solver(B.Settings(hipOptions={"gather_overlap": 1}), ps, ss)
     assert "gather_chunks_overlapped" not in sol.runCounters()
+    # the testing hooks that dump the host-built launch tables and solve schedule
+    for hook in ("bsp_test_launch_tables", "bsp_test_solve_schedule"):
+        assert hasattr(_lib.load(), hook), hook
 
 
 def test_accessor_matches_skeleton():
