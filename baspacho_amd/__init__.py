@@ -425,6 +425,38 @@ class Solver:
         out["node"] = {f: nd[:, i].copy() for i, f in enumerate(fn)}
         return out
 
+    def _testReachPlan(self, params):
+        """TESTING: the reach plan of `params` (caller's ids) with one Gram item per pair (i, j), i >= j,
+        of their positions (bsp_test_reach_plan, built on the host by the function inverseBlocks() uses).
+        {"cutLump", "cutSpan", "numCols": int, "queries": [{"span", "lump", "col0", "width", "reach":
+        int64 array (truncated at the cut)}], "groups": [{"query", "col0", "k", "row0", "len",
+        "firstLump"}], "items": [{"i", "j", "colP", "nP", "colQ", "nQ", "outOff", "rows", "ranges":
+        [(begin, end)] internal scalars}], "units": [(column, row)]}"""
+        prm = _i64(list(params))
+        buf = self._testRecords(lambda b, cap, need: self._lib.bsp_test_reach_plan(
+            self._h, ctypes.c_int64(len(prm)), prm.ctypes.data_as(_I64P), b, cap, need))
+        cut, cut_span, ncols, nq, ng, ni, nu = (int(x) for x in buf[:7])
+        pos = 7
+        out = {"cutLump": cut, "cutSpan": cut_span, "numCols": ncols, "queries": [], "groups": [], "items": []}
+        for _ in range(nq):
+            span, lump, col0, width, ln = (int(x) for x in buf[pos:pos + 5])
+            out["queries"].append({"span": span, "lump": lump, "col0": col0, "width": width,
+                                   "reach": buf[pos + 5:pos + 5 + ln].copy()})
+            pos += 5 + ln
+        for _ in range(ng):
+            out["groups"].append(dict(zip(("query", "col0", "k", "row0", "len", "firstLump"),
+                                          (int(x) for x in buf[pos:pos + 6]))))
+            pos += 6
+        for _ in range(ni):
+            it = dict(zip(("i", "j", "colP", "nP", "colQ", "nQ", "outOff", "rows"), (int(x) for x in buf[pos:pos + 8])))
+            nr = int(buf[pos + 8])
+            it["ranges"] = [(int(a), int(b)) for a, b in buf[pos + 9:pos + 9 + 2 * nr].reshape(nr, 2)]
+            out["items"].append(it)
+            pos += 9 + 2 * nr
+        out["units"] = [(int(a), int(b)) for a, b in buf[pos:pos + 2 * nu].reshape(nu, 2)]
+        assert pos + 2 * nu == len(buf)
+        return out
+
     def _testRecords(self, call):
         need = ctypes.c_int64(0)
         _check(call(None, ctypes.c_int64(0), ctypes.byref(need)))
@@ -901,6 +933,104 @@ class Solver:
             self._check_data(t)
         _call(self._lib, "bsp_selected_inverse_adjoint_", batched, _suffix(gs[0]), self._h, _ptr_arg(ls, batched),
               _ptr_arg(zs, batched), _ptr_arg(gs, batched), *_count(gs, batched))
+
+    # ---- blocks of A^-1 anywhere, by reach solves -----------------------
+    INVERSE_BLOCKS_MAX_COLUMNS = 512  # most columns of the distinct params of one bsp_inverse_blocks_* call
+
+    def _param_sizes(self, what, params):
+        params = [int(p) for p in params]
+        num = self.numSpans()
+        for p in params:
+            if p < 0 or p >= num:
+                raise IndexError("%s: parameter %d out of range [0, %d)" % (what, p, num))
+        ss, p2s = self.skel()["spanStart"], self.paramToSpan()
+        return params, [int(ss[p2s[p] + 1] - ss[p2s[p]]) for p in params]
+
+    def _reach_out(self, what, L, out, numel, shape):
+        """the output of a reach operation: a fresh tensor, or the caller's contiguous `out` of numel elements"""
+        import torch
+        if out is None:
+            return torch.empty(shape, dtype=L.dtype, device=L.device)
+        if out.dtype != L.dtype or out.device != L.device or out.numel() != numel or not out.is_contiguous():
+            raise ValueError("%s: out must be a contiguous %s tensor of %d elements on %s" % (what, L.dtype, numel,
+                                                                                          L.device))
+        return out.view(shape)
+
+    def halfInverseColumns(self, L, params, out=None):
+        """extension: W = L^-1 E for the unit columns E of the caller's params, stacked in the order
+        given: a device tensor [m, order()] (row c = column c of L^-1 E, in internal order).  `L` holds a
+        complete factor() and is only read.  Only the lumps on each column's reach are visited
+        (bsp_reach_solve_l_*); enqueued on the solver's stream.  out: a contiguous
+        tensor of m * order() elements to write instead of a fresh one."""
+        self._check_data(L)
+        params, sizes = self._param_sizes("halfInverseColumns", params)
+        W = self._reach_out("halfInverseColumns", L, out, sum(sizes) * self.order(), (sum(sizes), self.order()))
+        if W.numel() == 0:
+            return W
+        prm = _i64(params)
+        _check(getattr(self._lib, "bsp_reach_solve_l_" + _suffix(L))(
+            self._h, ctypes.c_void_p(_ptr_of(L)), ctypes.c_int64(len(params)), prm.ctypes.data_as(_I64P),
+            ctypes.c_void_p(_ptr_of(W))))
+        return W
+
+    def inverseColumns(self, L, params):
+        """extension: the columns of A^-1 of the caller's params, stacked in the order given: a device
+        tensor [m, order()], rows of A^-1 in internal order (halfInverseColumns, then solveLt)."""
+        X = self.halfInverseColumns(L, params)
+        if X.shape[0] > 0:
+            self.solveLt(L, X, stride=self.order(), nRHS=X.shape[0])
+        return X
+
+    def inverseBlocks(self, L, pairs, out=None):
+        """extension: the blocks A^-1[P, Q] of the pairs (P, Q) of caller's params, on or off the block
+        pattern of L: a device tensor [K, n, n] when every block has one shape, else a list of [n_P, n_Q]
+        tensors.  `L` holds a complete factor() and is only read (bsp_inverse_blocks_*; DESIGN.md section
+        20).  The pairs run in chunks whose distinct params hold at most INVERSE_BLOCKS_MAX_COLUMNS (512)
+        columns (a single pair may exceed it), which bounds the solver's workspace at 512 x order()
+        values.  Enqueued on the solver's stream; bitwise reproducible.  out: a contiguous tensor that
+        holds the blocks one after the other, to write instead of a fresh one."""
+        self._check_data(L)
+        pairs = [(int(p), int(q)) for p, q in pairs]
+        _, rs = self._param_sizes("inverseBlocks", [p for p, _ in pairs])
+        _, cs = self._param_sizes("inverseBlocks", [q for _, q in pairs])
+        offs = np.zeros(len(pairs) + 1, dtype=np.int64)
+        np.cumsum([a * b for a, b in zip(rs, cs)], out=offs[1:])
+        out = self._reach_out("inverseBlocks", L, out, int(offs[-1]), (int(offs[-1]),))
+        fn = getattr(self._lib, "bsp_inverse_blocks_" + _suffix(L))
+        k0 = 0
+        while k0 < len(pairs):
+            seen, cols, k1 = set(), 0, k0
+            while k1 < len(pairs):
+                add = sum(w for prm, w in {pairs[k1][0]: rs[k1], pairs[k1][1]: cs[k1]}.items() if prm not in seen)
+                if k1 > k0 and cols + add > self.INVERSE_BLOCKS_MAX_COLUMNS:
+                    break
+                seen.update(pairs[k1])
+                cols += add
+                k1 += 1
+            rp, cp = _i64([p for p, _ in pairs[k0:k1]]), _i64([q for _, q in pairs[k0:k1]])
+            o = np.ascontiguousarray(offs[k0:k1 + 1])
+            _check(fn(self._h, ctypes.c_void_p(_ptr_of(L)), ctypes.c_int64(k1 - k0), rp.ctypes.data_as(_I64P),
+                      cp.ctypes.data_as(_I64P), ctypes.c_void_p(_ptr_of(out)), o.ctypes.data_as(_I64P)))
+            k0 = k1
+        if len(pairs) > 0 and len(set(zip(rs, cs))) == 1:
+            return out.view(len(pairs), rs[0], cs[0])
+        return [out[int(offs[k]):int(offs[k + 1])].view(rs[k], cs[k]) for k in range(len(pairs))]
+
+    def jointMarginal(self, L, params):
+        """extension: the dense symmetric covariance [m, m] of the stacked caller's params, A^-1 on their
+        rows and columns: the blocks (P, Q) with P at or behind Q in `params` from inverseBlocks, mirrored
+        (symmetric to the last bit)."""
+        import torch
+        params, sizes = self._param_sizes("jointMarginal", params)
+        start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        pairs = [(i, j) for i in range(len(params)) for j in range(i + 1)]
+        blocks = self.inverseBlocks(L, [(params[i], params[j]) for i, j in pairs])
+        C = torch.empty((int(start[-1]), int(start[-1])), dtype=L.dtype, device=L.device)
+        for (i, j), b in zip(pairs, blocks):
+            C[start[i]:start[i + 1], start[j]:start[j + 1]] = b
+            if i != j:
+                C[start[j]:start[j + 1], start[i]:start[i + 1]] = b.t()
+        return C
 
     # ---- arguments that are one tensor each, or lists of tensors = a batch ---------------------
     def _same_kind(self, what, names, *xs):

@@ -11,6 +11,7 @@
 
 #include "assembly.h"
 #include "normal_eq.h"
+#include "reach.h"
 #include "bal_pipeline.h"
 #include "../../include/baspacho_amd_testing.h"
 #include "computation_model.h"
@@ -608,6 +609,63 @@ BSP_STATUS_API(f32, float)
 BSP_PATTERN_API(f64, double)
 BSP_PATTERN_API(f32, float)
 #undef BSP_PATTERN_API
+// ---- blocks of A^-1 by reach solves ---------------------------------------------------------------
+static std::vector<int64_t> hostIds(const char* what, const char* name, const int64_t* p, int64_t n) {
+  if (n < 0) throw std::runtime_error(std::string(what) + ": the number of " + name + " is negative");
+  if (n > 0 && p == nullptr) throw std::runtime_error(std::string(what) + ": the array of " + name + " is NULL");
+  return std::vector<int64_t>(p, p + n);
+}
+#define BSP_REACH_API(SFX, T)                                                                                    \
+  int bsp_reach_solve_l_##SFX(bsp_solver* s, const T* l, int64_t n, const int64_t* params, T* w)                 \
+      BSP_BODY(s->solver->reachSolveL(l, hostIds("reachSolveL", "params", params, n), w))                        \
+  int bsp_inverse_blocks_##SFX(bsp_solver* s, const T* l, int64_t n, const int64_t* rp, const int64_t* cp,       \
+                               T* out, const int64_t* offs)                                                      \
+      BSP_BODY(s->solver->inverseBlocks(l, hostIds("inverseBlocks", "row params", rp, n),                        \
+                                        hostIds("inverseBlocks", "column params", cp, n), out,                   \
+                                        hostIds("inverseBlocks", "output offsets", offs, n < 0 ? n : n + 1)))
+BSP_REACH_API(f64, double)
+BSP_REACH_API(f32, float)
+#undef BSP_REACH_API
+
+// the reach plan of `params` (caller's ids) with one Gram item per pair i >= j of them
+int bsp_test_reach_plan(const bsp_solver* s, int64_t num_params, const int64_t* params, int64_t* buf,
+                        int64_t capacity, int64_t* needed) {
+  BSP_TRY
+  const std::vector<int64_t> prm = hostIds("bsp_test_reach_plan", "params", params, num_params);
+  std::vector<int64_t> pr, pc;
+  for (int64_t i = 0; i < num_params; i++) {
+    for (int64_t j = 0; j <= i; j++) {
+      pr.push_back(i);
+      pc.push_back(j);
+    }
+  }
+  const ReachPlan p = s->solver->reachPlan("bsp_test_reach_plan", prm, pr, pc);
+  std::vector<int64_t> out = {p.cutLump, p.cutSpan, p.numCols, (int64_t)p.querySpan.size(), (int64_t)p.groups.size(),
+                              (int64_t)p.items.size(), (int64_t)p.unitCol.size()};
+  for (size_t q = 0; q < p.querySpan.size(); q++) {
+    out.insert(out.end(), {p.querySpan[q], p.queryLump[q], p.queryCol0[q], p.queryWidth[q],
+                           (int64_t)(p.queryListEnd[q] - p.queryListBegin[q])});
+    for (int32_t i = p.queryListBegin[q]; i < p.queryListEnd[q]; i++) out.push_back(p.reachLumps[i]);
+  }
+  for (const ReachGroup& g : p.groups) {
+    out.insert(out.end(), {(int64_t)g.query, (int64_t)g.col0, (int64_t)g.k, g.row0, (int64_t)(g.listEnd - g.listBegin),
+                           g.listEnd > g.listBegin ? (int64_t)p.reachLumps[g.listBegin] : -1});
+  }
+  for (size_t k = 0; k < p.items.size(); k++) {
+    const GramItem& it = p.items[k];
+    out.insert(out.end(), {pr[k], pc[k], (int64_t)it.colP, (int64_t)it.nP, (int64_t)it.colQ, (int64_t)it.nQ, it.outOff,
+                           it.rows, (int64_t)(it.rangeEnd - it.rangeBegin)});
+    for (int32_t r = it.rangeBegin; r < it.rangeEnd; r++) {
+      const int64_t len = (r + 1 < it.rangeEnd ? p.rangePrefix[r + 1] : it.rows) - p.rangePrefix[r];
+      out.insert(out.end(), {p.rangeStart[r], p.rangeStart[r] + len});
+    }
+  }
+  for (size_t i = 0; i < p.unitCol.size(); i++) out.insert(out.end(), {p.unitCol[i], p.unitRow[i]});
+  *needed = (int64_t)out.size();
+  if (buf != nullptr) std::copy(out.begin(), out.begin() + std::min(capacity, *needed), buf);
+  BSP_CATCH
+}
+
 #define BSP_PARTIAL_ADJOINT_API(SFX, T)                                                                          \
   int bsp_factor_adjoint_up_to_##SFX(bsp_solver* s, const T* p, T* grad, int64_t span)                           \
       BSP_BODY(s->solver->factorAdjointUpTo(p, grad, span))                                                      \

@@ -185,6 +185,21 @@ void hipBackendNormalEq(SymbolicCtx& sym, const NormalEqMap& map, int32_t op, co
                         const T* const* x, T* const* out, int64_t q, int64_t batch, bool single);
 void hipBackendFreeNormalEq(HipNormalEqDev* dev);
 
+// Reach solves (hip_reach_kernels.h), one matrix, plan from buildReachPlan (reach.h).
+// reachSolveL: W (numCols x order, column-major, leading dimension order) <- the unit columns of the
+// queries solved through the lumps of their reach below the plan's cut; the caller then runs
+// solveLFrom(cutSpan) over all columns.  L is a complete factor and only read.
+// gramBlocks: out + item.outOff <- W_P^T W_Q (row-major) for every item of the plan, written once, W read.
+// reachWorkspace: device room for `elems` values kept with the context (inverseBlocks' W); growing it
+// waits for the device.  The tables of a call travel through a ring on the execution stream.
+struct ReachPlan;
+template <typename T>
+void hipBackendReachSolveL(SymbolicCtx& sym, const ReachPlan& plan, const T* L, T* W);
+template <typename T>
+void hipBackendGramBlocks(SymbolicCtx& sym, const ReachPlan& plan, const T* W, T* out);
+template <typename T>
+T* hipBackendReachWorkspace(SymbolicCtx& sym, int64_t elems);
+
 HipPlanStats hipBackendPlanStats(SymbolicCtx& sym, int64_t startLump, int64_t upToLump);
 
 // TESTING (host only): the launch tables (buildLaunchTables, hip_plan.h) and the solve schedule of the

@@ -178,15 +178,19 @@ struct PtrRing {
     dev.release();
     slotBytes = 0;
   }
+  // slots of at least `bytes`.  Growing (the first call, or a larger array than ever before) waits for
+  // the device and allocates all slots anew: kSlots x the largest array seen stay pinned
+  void reserve(size_t bytes) {
+    if (bytes <= slotBytes) return;
+    if (slotBytes) hipCHECK(hipDeviceSynchronize());
+    release();
+    slotBytes = (std::max<size_t>(bytes, 512) + 255) & ~size_t(255);
+    hipCHECK(hipHostMalloc((void**)&host, slotBytes * kSlots, hipHostMallocDefault));
+    dev.resize(slotBytes * kSlots);
+    for (int i = 0; i < kSlots; i++) hipCHECK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+  }
   const void* push(const void* src, size_t bytes, hipStream_t stream) {
-    if (bytes > slotBytes) {  // (first call, or a larger batch than ever before)
-      if (slotBytes) hipCHECK(hipDeviceSynchronize());
-      release();
-      slotBytes = (std::max<size_t>(bytes, 512) + 255) & ~size_t(255);
-      hipCHECK(hipHostMalloc((void**)&host, slotBytes * kSlots, hipHostMallocDefault));
-      dev.resize(slotBytes * kSlots);
-      for (int i = 0; i < kSlots; i++) hipCHECK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-    }
+    reserve(bytes);
     const int s = next;
     next = (next + 1) % kSlots;
     if (used[s]) hipCHECK(hipEventSynchronize(ev[s]));

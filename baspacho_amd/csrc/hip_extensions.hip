@@ -8,6 +8,7 @@
 #include "hip_chol_adjoint_kernels.h"
 #include "hip_grad_kernels.h"
 #include "hip_normal_eq_kernels.h"
+#include "hip_reach_kernels.h"
 #include "hip_selinv_adjoint_kernels.h"
 #include "hip_selinv_kernels.h"
 #include "hip_status_kernels.h"
@@ -231,6 +232,41 @@ struct SelInvDev {
   }
 };
 
+// Reach solves (hip_reach_kernels.h): the tables of a call travel through a ring
+// of their own (a plan is built per call: its queries are the call's), and inverseBlocks keeps its W here.
+// The ring is sized for both blobs of a call before the call queues anything (hipBackendReachSolveL), so
+// it never grows between the kernels of one call; a call with larger tables than any before waits for the
+// device at its beginning, as a larger W does, and 32 slots of the largest blob seen stay pinned.
+struct ReachDev {
+  PtrRing ring;
+  DevBuf W;
+  // room for `bytes` of W.  Growing waits for the kernels queued by earlier calls, as the other scratch does
+  void* reserve(size_t bytes) {
+    if (bytes > W.bytes) {
+      if (W.bytes > 0) hipCHECK(hipDeviceSynchronize());
+      W.resize(bytes);
+    }
+    return W.ptr;
+  }
+};
+
+// several host tables as one blob, every table at a multiple of 16 bytes
+struct TableBlob {
+  vector<char> bytes;
+  // the size of a blob of `size` bytes after add(v)
+  template <typename U>
+  static size_t sizeWith(size_t size, const vector<U>& v) {
+    return ((size + 15) & ~size_t(15)) + v.size() * sizeof(U);
+  }
+  template <typename U>
+  size_t add(const vector<U>& v) {
+    const size_t off = (bytes.size() + 15) & ~size_t(15);
+    bytes.resize(sizeWith(bytes.size(), v));
+    if (!v.empty()) std::memcpy(bytes.data() + off, v.data(), v.size() * sizeof(U));
+    return off;
+  }
+};
+
 }  // namespace
 
 // the extension state of a context (HipSymbolicCtx::ext), built on first use
@@ -239,6 +275,7 @@ struct hipb::ExtensionState {
   std::map<int64_t, std::unique_ptr<SelInvDev>> selinvUpTo;  // ... up to a lump, per cut
   SelInvScratch selinvScratch;
   std::unique_ptr<GradDev> grad;      // work lists of logDet / patternGrad, built on first use
+  ReachDev reach;
 };
 void hipb::ExtensionStateDelete::operator()(ExtensionState* p) const { delete p; }
 
@@ -712,6 +749,67 @@ void hipBackendNormalEq(SymbolicCtx& sym, const NormalEqMap& m, int32_t op, cons
   });
 }
 
+// ---- reach solves (hip_reach_kernels.h) ---------------------------------------
+// W (numCols x order, column-major) <- the unit columns of the plan's queries, solved through the lumps
+// of their reach below the cut: one memset, the unit entries of the queries behind the cut, one launch
+// of a workgroup per column group.  The caller runs solveLFrom(cutSpan) on W afterwards.
+template <typename T>
+void hipBackendReachSolveL(SymbolicCtx& sym, const ReachPlan& p, const T* L, T* W) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  const int64_t order = h.skel.order();
+  if (p.numCols == 0 || order == 0) return;
+  ReachDev& r = extState(h).reach;
+  const hipk::SkelDev sk = h.skelDev();
+  TableBlob blob;
+  const size_t oGroups = blob.add(p.groups), oLumps = blob.add(p.reachLumps);
+  const size_t oCol = blob.add(p.unitCol), oRow = blob.add(p.unitRow);
+  // room for the tables of hipBackendGramBlocks too: the ring does not grow in the middle of a call
+  const size_t gramBytes =
+      TableBlob::sizeWith(TableBlob::sizeWith(TableBlob::sizeWith(0, p.items), p.rangeStart), p.rangePrefix);
+  r.ring.reserve(std::max(blob.bytes.size(), gramBytes));
+  hipCHECK(hipMemsetAsync(W, 0, (size_t)p.numCols * order * sizeof(T), stream));
+  if (blob.bytes.empty()) return;
+  const char* d = reinterpret_cast<const char*>(r.ring.push(blob.bytes.data(), blob.bytes.size(), stream));
+  const int64_t nUnits = (int64_t)p.unitCol.size();
+  if (nUnits > 0) {
+    hipk::reachUnits<T><<<dim3((unsigned)((nUnits + 255) / 256)), 256, 0, stream>>>(
+        reinterpret_cast<const int64_t*>(d + oCol), reinterpret_cast<const int64_t*>(d + oRow), nUnits, W, order);
+  }
+  if (!p.groups.empty()) {
+    hipk::reachSolveL<T><<<dim3((unsigned)p.groups.size()), 256, 0, stream>>>(
+        reinterpret_cast<const ReachGroup*>(d + oGroups), reinterpret_cast<const int32_t*>(d + oLumps), sk,
+        hipk::DataRef<const T>{L, nullptr}, W, order);
+  }
+  hipCHECK(hipGetLastError());
+}
+
+// out[item.outOff ..] = W_P^T W_Q for every item of the plan: one launch of a workgroup per item
+template <typename T>
+void hipBackendGramBlocks(SymbolicCtx& sym, const ReachPlan& p, const T* W, T* out) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  if (p.items.empty()) return;
+  ReachDev& r = extState(h).reach;
+  TableBlob blob;
+  const size_t oItems = blob.add(p.items), oStart = blob.add(p.rangeStart), oPrefix = blob.add(p.rangePrefix);
+  const char* d = reinterpret_cast<const char*>(r.ring.push(blob.bytes.data(), blob.bytes.size(), stream));
+  hipk::gramBlocks<T><<<dim3((unsigned)p.items.size()), 256, 0, stream>>>(
+      reinterpret_cast<const GramItem*>(d + oItems), reinterpret_cast<const int64_t*>(d + oStart),
+      reinterpret_cast<const int64_t*>(d + oPrefix), W, h.skel.order(), out);
+  hipCHECK(hipGetLastError());
+}
+
+// the W workspace of inverseBlocks, kept with the extension state: room for `elems` values of T
+template <typename T>
+T* hipBackendReachWorkspace(SymbolicCtx& sym, int64_t elems) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  h.checkDevice();
+  return reinterpret_cast<T*>(extState(h).reach.reserve((size_t)std::max<int64_t>(elems, 1) * sizeof(T)));
+}
+
 #define BSP_INSTANTIATE_EXTENSIONS(T)                                                                            \
   template void hipBackendSelectedInverse<T>(SymbolicCtx&, T* const*, int64_t, bool);                           \
   template void hipBackendLogDet<T>(SymbolicCtx&, const T* const*, int64_t, bool, T*);                          \
@@ -727,7 +825,10 @@ void hipBackendNormalEq(SymbolicCtx& sym, const NormalEqMap& m, int32_t op, cons
   template void hipBackendAssemble<T>(SymbolicCtx&, const AssemblyMap&, const T* const*, T* const*, int64_t,    \
                                       bool, bool);                                                              \
   template void hipBackendNormalEq<T>(SymbolicCtx&, const NormalEqMap&, int32_t, const T* const*,               \
-                                      const T* const*, T* const*, int64_t, int64_t, bool);
+                                      const T* const*, T* const*, int64_t, int64_t, bool);                      \
+  template void hipBackendReachSolveL<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                         \
+  template void hipBackendGramBlocks<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                          \
+  template T* hipBackendReachWorkspace<T>(SymbolicCtx&, int64_t);
 BSP_INSTANTIATE_EXTENSIONS(double)
 BSP_INSTANTIATE_EXTENSIONS(float)
 #undef BSP_INSTANTIATE_EXTENSIONS

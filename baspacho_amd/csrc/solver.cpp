@@ -9,11 +9,13 @@
 #include <algorithm>
 #include <iostream>
 #include <numeric>
+#include <unordered_map>
 #include <chrono>
 #include <cstdlib>
 
 #include "assembly.h"
 #include "normal_eq.h"
+#include "reach.h"
 #include "computation_model.h"
 #include "elimination_tree.h"
 #include "hip_backend.h"
@@ -997,6 +999,84 @@ void Solver::normalEq(const NormalEqMap& map, int32_t op, const std::vector<cons
   hipBackendNormalEq<T>(*symCtx, map, op, values.data(), hasX ? x.data() : nullptr, out.data(), q,
                         (int64_t)values.size(), single);
 }
+// ---- blocks of A^-1 by reach solves (reach.h) --------------------------------
+ReachPlan Solver::reachPlan(const char* what, const std::vector<int64_t>& params, const std::vector<int64_t>& pairRow,
+                            const std::vector<int64_t>& pairCol, const std::vector<int64_t>& outOffsets) const {
+  checkCompleteFactor(what, canFactorUpTo, factorSkel.numSpans(), "a reach solve");
+  const int64_t numParams = (int64_t)permutation.size();
+  std::vector<int64_t> spans;
+  for (size_t i = 0; i < params.size(); i++) {
+    if (params[i] < 0 || params[i] >= numParams) {
+      throw std::runtime_error(std::string(what) + ": param " + std::to_string(params[i]) + " (position " +
+                               std::to_string(i) + ") is not in [0, " + std::to_string(numParams) + ")");
+    }
+    spans.push_back(permutation[params[i]]);
+  }
+  try {
+    return buildReachPlan(factorSkel, sparseElimRanges, spans, pairRow, pairCol, outOffsets);
+  } catch (const std::runtime_error& e) {
+    throw std::runtime_error(std::string(what) + ": " + e.what());
+  }
+}
+
+// W <- L^-1 E for the plan's queries: the reach kernel below the cut, solveLFrom behind it
+template <typename T>
+static void runReachSolve(const Solver& s, SymbolicCtx& sym, const ReachPlan& plan, const T* L, T* W) {
+  hipBackendReachSolveL<T>(sym, plan, L, W);
+  if (plan.numCols > 0 && plan.cutLump < s.skel().numLumps()) {
+    s.solveLFrom(L, plan.cutSpan, W, s.order(), (int)plan.numCols);
+  }
+}
+
+template <typename T>
+void Solver::reachSolveL(const T* L, const std::vector<int64_t>& params, T* W) const {
+  const char* what = "reachSolveL";
+  if (L == nullptr) throw std::runtime_error("reachSolveL: the factor pointer is NULL");
+  if (W == nullptr) throw std::runtime_error("reachSolveL: the output pointer is NULL");
+  const ReachPlan plan = reachPlan(what, params, {}, {});
+  runReachSolve(*this, *symCtx, plan, L, W);
+}
+
+template <typename T>
+void Solver::inverseBlocks(const T* L, const std::vector<int64_t>& rowParams, const std::vector<int64_t>& colParams,
+                           T* out, const std::vector<int64_t>& outOffsets) const {
+  const char* what = "inverseBlocks";
+  if (L == nullptr) throw std::runtime_error("inverseBlocks: the factor pointer is NULL");
+  if (out == nullptr) throw std::runtime_error("inverseBlocks: the output pointer is NULL");
+  if (rowParams.size() != colParams.size()) {
+    throw std::runtime_error("inverseBlocks: " + std::to_string(rowParams.size()) + " row params for " +
+                             std::to_string(colParams.size()) + " column params");
+  }
+  if (outOffsets.size() != rowParams.size() + 1) {
+    throw std::runtime_error("inverseBlocks: the output offsets must hold numPairs + 1 entries");
+  }
+  for (size_t k = 0; k < rowParams.size(); k++) {
+    if (outOffsets[k] < 0 || outOffsets[k + 1] < outOffsets[k]) {
+      throw std::runtime_error("inverseBlocks: the output offsets must be non-negative and ascending");
+    }
+  }
+  // the distinct params, in the order of their first appearance
+  std::vector<int64_t> params, pairRow, pairCol;
+  std::unordered_map<int64_t, int64_t> index;
+  const auto indexOf = [&](int64_t prm) {
+    auto it = index.find(prm);
+    if (it == index.end()) {
+      it = index.emplace(prm, (int64_t)params.size()).first;
+      params.push_back(prm);
+    }
+    return it->second;
+  };
+  for (size_t k = 0; k < rowParams.size(); k++) {
+    pairRow.push_back(indexOf(rowParams[k]));
+    pairCol.push_back(indexOf(colParams[k]));
+  }
+  const ReachPlan plan = reachPlan(what, params, pairRow, pairCol, outOffsets);
+  if (plan.items.empty()) return;
+  T* W = hipBackendReachWorkspace<T>(*symCtx, plan.numCols * order());
+  runReachSolve(*this, *symCtx, plan, L, W);
+  hipBackendGramBlocks<T>(*symCtx, plan, W, out);
+}
+
 // one single / batch pair per operation
 #define BSP_INSTANTIATE_EXTENSIONS(T)                                                                          \
   using BspVec_##T = const std::vector<T*>&;                                                                   \
@@ -1029,7 +1109,10 @@ void Solver::normalEq(const NormalEqMap& map, int32_t op, const std::vector<cons
   template void Solver::assembleAdjoint<T>(const AssemblyMap&, const T*, T*) const;                            \
   template void Solver::assembleAdjoint<T>(const AssemblyMap&, BspCVec_##T, BspVec_##T) const;                 \
   template void Solver::normalEq<T>(const NormalEqMap&, int32_t, BspCVec_##T, BspCVec_##T, BspVec_##T,         \
-                                    int64_t, bool) const;
+                                    int64_t, bool) const;                                                      \
+  template void Solver::reachSolveL<T>(const T*, const std::vector<int64_t>&, T*) const;                       \
+  template void Solver::inverseBlocks<T>(const T*, const std::vector<int64_t>&, const std::vector<int64_t>&,   \
+                                         T*, const std::vector<int64_t>&) const;
 BSP_INSTANTIATE_EXTENSIONS(double)
 BSP_INSTANTIATE_EXTENSIONS(float)
 #undef BSP_INSTANTIATE_EXTENSIONS

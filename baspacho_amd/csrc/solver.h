@@ -18,6 +18,7 @@ namespace BaSpaCho {
 
 struct AssemblyMap;
 struct NormalEqMap;
+struct ReachPlan;
 
 class Solver {
  public:
@@ -235,6 +236,30 @@ class Solver {
   template <typename T>
   void normalEq(const NormalEqMap& map, int32_t op, const std::vector<const T*>& values,
                 const std::vector<const T*>& x, const std::vector<T*>& out, int64_t q, bool single) const;
+  // extension: blocks of A^-1 anywhere, on or off the pattern of L, by reach solves (DESIGN.md section 20;
+  // reach.h, hip_reach_kernels.h).  `L` holds a complete factor() and is only read; params are the
+  // caller's param ids (repeats allowed).  Both run on the stream of setStream() without host
+  // synchronisation and refuse NULL pointers, ids out of range and a Solver that cannot factor completely
+  // before any device work.
+  //
+  // reachSolveL: W = L^-1 E, E the unit columns of the params stacked in the order given (m columns in
+  // all); W is m x order(), column-major with leading dimension order(), rows in internal order, every
+  // element written.  Only the lumps on each column's reach are visited, then the trailing wide lumps
+  // by solveLFrom over all columns.
+  template <typename T>
+  void reachSolveL(const T* L, const std::vector<int64_t>& params, T* W) const;
+  // inverseBlocks: block k = A^-1[rowParams[k], colParams[k]], row-major at out + outOffsets[k]
+  // (outOffsets: numPairs + 1 entries, block k inside [outOffsets[k], outOffsets[k + 1])); every block is
+  // written once, bitwise reproducibly.  W = L^-1 E of the distinct params lives in a workspace kept with
+  // the Solver (distinct columns x order() values; it grows on demand, which waits for the device).
+  template <typename T>
+  void inverseBlocks(const T* L, const std::vector<int64_t>& rowParams, const std::vector<int64_t>& colParams,
+                     T* out, const std::vector<int64_t>& outOffsets) const;
+  // the plan reachSolveL / inverseBlocks run for these queries (host only): params as above, pairs as
+  // indices into params
+  ReachPlan reachPlan(const char* what, const std::vector<int64_t>& params, const std::vector<int64_t>& pairRow,
+                      const std::vector<int64_t>& pairCol, const std::vector<int64_t>& outOffsets = {}) const;
+
   // scalarPermutation()[i] = internal index of the caller's scalar i (params in param order, each
   // at the start of its span)
   std::vector<int64_t> scalarPermutation() const;

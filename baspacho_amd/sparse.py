@@ -9,6 +9,8 @@
     x = S.sample(pat, values, z, mu)               # x = mu + L^-T z: Cov(x) = A^-1
     c = S.covariance(pat, values)                  # (A^-1)[rows[k], cols[k]] for every entry k
     v = S.marginal_variances(pat, values)          # diag(A^-1) in the caller's order
+    c = S.cross_covariance(pat, values, i, j)      # (A^-1)[i[k], j[k]] for ANY scalar pairs, on or off the pattern
+    C = S.joint_covariance(pat, values, idx)       # the dense [k, k] block of A^-1 on the scalars idx
     pat = S.SymmetricPattern(rows, cols, n, keep=kept)     # kept scalars ordered last
     Sk, rk = S.marginalize(pat, values, b)         # marginal precision / information of the kept scalars
 
@@ -38,6 +40,11 @@ covariance and marginal_variances read A^-1 on the pattern from a selected inver
 values; their backward sweep adds with float atomics, so gradients are close, not bitwise, from run to
 run.
 
+cross_covariance and joint_covariance read entries of A^-1 anywhere, from forward solves over the reach of
+the queried params alone (assemble -> factor -> Solver.inverseBlocks -> a gather), for
+one matrix; they are differentiable in values, and their backward (columns of A^-1, then
+Solver.patternGrad) is bitwise reproducible.
+
 marginalize eliminates every scalar outside `keep`: S = A22 - A21 A11^-1 A12 and
 r = b2 - A21 A11^-1 b1 with block 2 the kept scalars, rows and columns in the order of `keep`.  inv(S) is
 the `keep` block of inv(A): S and r are the precision and the information vector of the marginal.
@@ -51,7 +58,7 @@ from . import autograd as _ag
 from .autograd import _OnCurrentStream
 
 __all__ = ["SymmetricPattern", "JacobianPattern", "assemble", "solve", "logdet", "solve_logdet", "sample", "marginalize",
-           "covariance", "marginal_variances",
+           "covariance", "marginal_variances", "cross_covariance", "joint_covariance",
            "hessian", "jt_vec", "j_vec", "normal_equations", "lstsq", "check_positive_definite"]
 
 
@@ -373,6 +380,109 @@ def marginal_variances(pattern, values):
     """diag(A(values)^-1) in the caller's order: [n], or [B, n] for a batch.  Differentiable in values."""
     _check_values(pattern, values, "marginal_variances")
     return _selected_inverse(pattern, values).index_select(-1, pattern._index("diag_user", values.device))
+
+
+# ---- entries of A^-1 anywhere, by reach solves (DESIGN.md section 20) ------------------------------
+_CROSS_BACKWARD_CHUNK = 256  # pairs per patternGrad call of the backward: U and V hold 2 x 256 x order values
+
+
+class _CrossCovariance(torch.autograd.Function):
+    """c[k] = (A(data)^-1)[rows[k], cols[k]], rows / cols internal scalars given as (param, offset) pairs.
+    Backward: with x_i = A^-1 e_i, the data gradient of sum_k g_k e_i^T A^-1 e_j is patternGrad's formula
+    with U = g_k x_{i_k}, V = x_{j_k}, alpha = -1."""
+
+    @staticmethod
+    def forward(ctx, solver, data, prm_i, off_i, prm_j, off_j, sizes):
+        with _OnCurrentStream(solver, data.device):
+            L = _ag._factor(solver, data)
+            key = prm_i * len(sizes) + prm_j
+            uniq, inv = np.unique(key, return_inverse=True)
+            pairs = [(int(u // len(sizes)), int(u % len(sizes))) for u in uniq]
+            offs = np.concatenate([[0], np.cumsum([sizes[p] * sizes[q] for p, q in pairs])]).astype(np.int64)
+            flat = torch.empty(int(offs[-1]), dtype=data.dtype, device=data.device)
+            if len(pairs):
+                solver.inverseBlocks(L, pairs, out=flat)
+            at = offs[inv] + off_i * sizes[prm_j] + off_j
+            c = flat.index_select(0, torch.from_numpy(at).to(data.device))
+        ctx.solver, ctx.q = solver, (prm_i, off_i, prm_j, off_j, sizes)
+        ctx.save_for_backward(L)
+        ctx.set_materialize_grads(False)
+        return c
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        none = (None,) * 7
+        if g is None or not ctx.needs_input_grad[1]:
+            return none
+        solver, (L,) = ctx.solver, ctx.saved_tensors
+        prm_i, off_i, prm_j, off_j, sizes = ctx.q
+        g = g.contiguous()
+        total = None
+        with _OnCurrentStream(solver, L.device):
+            for k0 in range(0, len(prm_i), _CROSS_BACKWARD_CHUNK):
+                k1 = min(k0 + _CROSS_BACKWARD_CHUNK, len(prm_i))
+                prm = np.unique(np.concatenate([prm_i[k0:k1], prm_j[k0:k1]]))
+                col0 = np.zeros(len(sizes), dtype=np.int64)
+                col0[prm] = np.concatenate([[0], np.cumsum(sizes[prm])])[:-1]
+                X = solver.inverseColumns(L, prm.tolist())  # [columns of prm, order], internal order
+                ci = torch.from_numpy(col0[prm_i[k0:k1]] + off_i[k0:k1]).to(L.device)
+                cj = torch.from_numpy(col0[prm_j[k0:k1]] + off_j[k0:k1]).to(L.device)
+                U = (X.index_select(0, ci) * g[k0:k1, None]).contiguous()
+                V = X.index_select(0, cj).contiguous()
+                part = torch.empty_like(L)  # patternGrad writes and never adds
+                solver.patternGrad(part, U=U, V=V, nRHS=k1 - k0, alpha=-1.0)
+                total = part if total is None else total.add_(part)
+        if total is None:
+            total = torch.zeros_like(L)
+        return (None, total) + (None,) * 5
+
+
+def _scalar_queries(pattern, idx, what, name):
+    """(param, offset inside the param) of caller-order scalar indices"""
+    idx = _host_i64(idx)
+    if np.any(idx < 0) or np.any(idx >= pattern.n):
+        raise ValueError("%s: %s must hold scalar indices in [0, %d)" % (what, name, pattern.n))
+    starts = np.concatenate([[0], np.cumsum(pattern.param_sizes)])
+    prm = np.searchsorted(starts, idx, side="right") - 1
+    return prm.astype(np.int64), (idx - starts[prm]).astype(np.int64)
+
+
+def _check_single(pattern, values, what):
+    _check_values(pattern, values, what)
+    if values.dim() != 1:
+        raise ValueError("%s: one matrix at a time: values must be [%d], got the batch shape %s"
+                         % (what, pattern.nnz, tuple(values.shape)))
+    _ag._check_device(pattern.solver, what, values)
+
+
+def cross_covariance(pattern, values, rows, cols):
+    """c[k] = (A(values)^-1)[rows[k], cols[k]] for any scalar pairs in the caller's order, on or off the
+    pattern: [K].  rows / cols: host integer arrays (or tensors) of one length.  One matrix: a batch
+    [B, nnz] is refused.  Differentiable in values."""
+    what = "cross_covariance"
+    _check_single(pattern, values, what)
+    pi, oi = _scalar_queries(pattern, rows, what, "rows")
+    pj, oj = _scalar_queries(pattern, cols, what, "cols")
+    if len(pi) != len(pj):
+        raise ValueError("%s: %d rows for %d cols" % (what, len(pi), len(pj)))
+    return _CrossCovariance.apply(pattern.solver, assemble(pattern, values), pi, oi, pj, oj, pattern.param_sizes)
+
+
+def joint_covariance(pattern, values, idx):
+    """the dense symmetric block [k, k] of A(values)^-1 on the caller-order scalars idx (host integer array
+    or tensor), symmetric to the last bit: the pairs a >= b by cross_covariance, mirrored.  One matrix: a
+    batch [B, nnz] is refused.  Differentiable in values."""
+    what = "joint_covariance"
+    _check_single(pattern, values, what)
+    idx = _host_i64(idx)
+    _scalar_queries(pattern, idx, what, "idx")
+    k = len(idx)
+    a, b = np.tril_indices(k)
+    c = cross_covariance(pattern, values, idx[a], idx[b])
+    where = np.zeros((k, k), dtype=np.int64)
+    where[a, b] = where[b, a] = np.arange(len(a))
+    return c.index_select(0, torch.from_numpy(where.ravel()).to(values.device)).view(k, k)
 
 
 def marginalize(pattern, values, b=None):

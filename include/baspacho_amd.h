@@ -239,10 +239,11 @@ int bsp_pseudo_factor_from_f32(bsp_solver* s, float* dev_data, int64_t span_inde
    restricted to the block pattern of L overwrites L in the factor's layout: every lump's diagonal
    block is written full and symmetric (both triangles), every off-diagonal block keeps its stored
    orientation, so bsp_diag_block_offset / bsp_block_offset (and its `flipped` flag) read Z as they
-   read L.  Entries of A^-1 outside the pattern are not computed.  The strictly-upper elements of L's
-   diagonal blocks are ignored on input (they are overwritten by Z).  Runs on the bsp_set_stream stream,
-   no host synchronisation (the first call builds the plan); the result is bitwise reproducible.
-   No GPU or a NULL dev_data: non-zero return, bsp_last_error() says why. */
+   read L.  Entries of A^-1 outside the pattern are not computed here (bsp_inverse_blocks_* does).
+   The strictly-upper elements of L's diagonal blocks are ignored on input (they are overwritten by
+   Z).  Runs on the bsp_set_stream stream, no host synchronisation (the first call builds the plan);
+   the result is bitwise reproducible.  No GPU or a NULL dev_data: non-zero return, bsp_last_error()
+   says why. */
 int bsp_selected_inverse_f64(bsp_solver* s, double* dev_data);
 int bsp_selected_inverse_f32(bsp_solver* s, float* dev_data);
 /* Solver::selectedInverse<std::vector<T*>>: the same for `batch` complete factors of this solver
@@ -255,6 +256,33 @@ int bsp_selected_inverse_f32(bsp_solver* s, float* dev_data);
    device work, bsp_last_error() says why. */
 int bsp_selected_inverse_batched_f64(bsp_solver* s, double* const* dev_ptrs, int32_t batch);
 int bsp_selected_inverse_batched_f32(bsp_solver* s, float* const* dev_ptrs, int32_t batch);
+/* Extension (no counterpart in the reference): blocks of A^-1 anywhere, on or off the pattern of L, by
+   reach solves.  (A^-1)_ij = (L^-1 e_i) . (L^-1 e_j), and L^-1 e_i is nonzero only
+   on the lumps reachable from i's lump through the rows of L: a forward solve visits those alone.
+   dev_l holds a complete factor() of this solver and is only read; params are the CALLER's param ids in
+   a HOST array (repeats allowed).  Both run on the bsp_set_stream stream and are bitwise reproducible.
+   They do not synchronise with the host, with two exceptions, both at the beginning of a call, before
+   it queues anything: a call whose work tables (reach lists, groups, Gram row ranges) are larger than
+   those of any earlier call on this solver waits for the device and allocates its staging slots anew
+   (32 pinned host slots and 32 device slots of the largest tables seen stay with the solver), and so
+   does a bsp_inverse_blocks_* call that needs a larger workspace than any before.  A solver that
+   cannot factor completely (AddFillForGivenElims), a NULL pointer or an id out of range: non-zero
+   return before any device work.
+   bsp_reach_solve_l_*: dev_w = L^-1 E, E the unit columns of the params stacked in the order given, m
+   columns in all: m x bsp_order values, column-major with leading dimension bsp_order, rows in
+   internal order, every element written.
+   bsp_inverse_blocks_*: block k = A^-1[row_params[k], col_params[k]], row-major at dev_out +
+   out_offsets[k] (HOST array of num_pairs + 1 ascending offsets; block k must fit before
+   out_offsets[k + 1]).  L^-1 E of the distinct params goes to a workspace kept with the solver
+   (distinct columns x bsp_order values; growing it waits for the device). */
+int bsp_reach_solve_l_f64(bsp_solver* s, const double* dev_l, int64_t num_params, const int64_t* params,
+                          double* dev_w);
+int bsp_reach_solve_l_f32(bsp_solver* s, const float* dev_l, int64_t num_params, const int64_t* params,
+                          float* dev_w);
+int bsp_inverse_blocks_f64(bsp_solver* s, const double* dev_l, int64_t num_pairs, const int64_t* row_params,
+                           const int64_t* col_params, double* dev_out, const int64_t* out_offsets);
+int bsp_inverse_blocks_f32(bsp_solver* s, const float* dev_l, int64_t num_pairs, const int64_t* row_params,
+                           const int64_t* col_params, float* dev_out, const int64_t* out_offsets);
 /* Extension (no counterpart in the reference): gradients on the block pattern of L, for autograd
    (DESIGN.md section 13).  Data is this solver's numeric layout and vectors are in its internal order,
    as for bsp_solve_*.  A(d) is the symmetric matrix with A_ij = A_ji = d_e for every stored element

@@ -33,6 +33,19 @@ int bsp_test_selinv_plan(const bsp_solver* s, int64_t* buf, int64_t capacity, in
  * span that bsp_factor_up_to_* refuses gives a non-zero return. */
 int bsp_test_selinv_plan_up_to(const bsp_solver* s, int64_t span, int64_t* buf, int64_t capacity, int64_t* needed);
 
+/* The reach plan (buildReachPlan, csrc/reach.cpp: the plan bsp_reach_solve_l_* / bsp_inverse_blocks_* run)
+ * of `params` (caller's ids, HOST array) with one Gram item per pair (i, j), i >= j, of their positions,
+ * built on the host with no device involved.  Layout (int64):
+ *   cutLump, cutSpan, numCols, nQueries, nGroups, nItems, nUnits,
+ *   nQueries records {span, lump, col0, width, len, len lumps of the reach (truncated at the cut)},
+ *   nGroups records {query, col0, k, row0, len of its list, first lump of its list or -1},
+ *   nItems records {i, j, colP, nP, colQ, nQ, outOff, rows, nRanges, nRanges pairs [begin, end) of
+ *     internal scalars},
+ *   nUnits pairs {column, row}: the unit entries of the queries at or beyond the cut.
+ * buf / capacity / needed as bsp_test_selinv_plan. */
+int bsp_test_reach_plan(const bsp_solver* s, int64_t num_params, const int64_t* params, int64_t* buf,
+                        int64_t capacity, int64_t* needed);
+
 /* The launch tables of the factor plan over every lump (buildLaunchTables, csrc/hip_plan.cpp: what the
  * launch code uploads beside the plan), built on the host with no device involved.  Layout (int64):
  *   nLevels, nMainLevels, nLevelPanels, nTrsmTasks, nUpdTasks (of the plan), then the lengths of
