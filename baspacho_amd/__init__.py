@@ -395,6 +395,13 @@ class Solver:
         (bsp_test_set_selinv_batch_chunk); 0 = the product's rule"""
         _check(self._lib.bsp_test_set_selinv_batch_chunk(self._h, ctypes.c_int32(max_matrices)))
 
+    def _testPtrRingSlotBytes(self):
+        """TESTING, read-only: bytes of one slot of the pointer ring of batched calls
+        (bsp_test_ptr_ring_slot_bytes); 0 before the first batched call"""
+        out = ctypes.c_int64(0)
+        _check(self._lib.bsp_test_ptr_ring_slot_bytes(self._h, ctypes.byref(out)))
+        return int(out.value)
+
     _SELINV_SMALL_FIELDS = ("lump", "level", "n", "r", "k")
     _SELINV_NODE_FIELDS = ("lump", "level", "c0", "w", "r", "nRest", "kChunk", "nk", "nTiles", "tileBase")
 

@@ -831,6 +831,12 @@ int bsp_test_set_selinv_batch_chunk(bsp_solver* s, int32_t max_matrices) {
   hipBackendSetSelInvBatchChunk(s->solver->internalSymbolicContext(), max_matrices);
   BSP_CATCH
 }
+int bsp_test_ptr_ring_slot_bytes(bsp_solver* s, int64_t* out) {
+  BSP_TRY
+  if (out == nullptr) throw std::runtime_error("bsp_test_ptr_ring_slot_bytes: out is NULL");
+  *out = hipBackendPtrRingSlotBytes(s->solver->internalSymbolicContext());
+  BSP_CATCH
+}
 int bsp_pseudo_factor_from_f64(bsp_solver* s, double* d, int64_t span) {
   BSP_TRY
   s->solver->pseudoFactorFrom(d, span);

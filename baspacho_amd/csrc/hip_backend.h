@@ -105,6 +105,8 @@ template <typename T>
 void hipBackendSelectedInverse(SymbolicCtx& sym, T* const* data, int64_t batch, bool single);
 // TESTING: at most `maxMatrices` matrices per chunk of a pass over the selected-inversion levels (0: no cap)
 void hipBackendSetSelInvBatchChunk(SymbolicCtx& sym, int64_t maxMatrices);
+// TESTING, read-only: bytes of one slot of the pointer ring of batched calls (0 before the first batched call)
+int64_t hipBackendPtrRingSlotBytes(SymbolicCtx& sym);
 
 // Gradients on the pattern of L (hip_grad_kernels.h).
 // logDet: out[q] = 2 sum_i log L_ii of the complete factor factors[q] (out: device array of `batch`).

@@ -481,6 +481,8 @@ void hipBackendSetSelInvBatchChunk(SymbolicCtx& sym, int64_t maxMatrices) {
   hipCtx(sym).selInvChunkCap = maxMatrices;
 }
 
+int64_t hipBackendPtrRingSlotBytes(SymbolicCtx& sym) { return (int64_t)hipCtx(sym).fac.ptrRing.slotBytes; }
+
 // Selected inversion of `batch` complete factors, in place (hip_selinv_kernels.h).  The plan is built
 // and uploaded on the first call; every launch goes to the execution stream, in level order, with no
 // host synchronisation.  A chunk is one pass over the levels, each matrix in its own scratch slice;

@@ -77,6 +77,12 @@ int bsp_test_solve_schedule(const bsp_solver* s, int32_t with_sweeps, int32_t bl
  * matrices, so that tests can force several chunks on small batches; 0 = the product's rule. */
 int bsp_test_set_selinv_batch_chunk(bsp_solver* s, int32_t max_matrices);
 
+/* Read-only: *out = bytes of one slot of the ring that carries the pointer arrays of batched calls to the
+ * device (PtrRing, csrc/hip_context.h): 0 before the first batched call, 512 up to 64 pointers, then the
+ * largest array seen rounded up to 256.  A change between two calls shows that the ring's growth path
+ * (wait for the device, free every slot, allocate anew) ran in between (tests/test_history_gpu.py). */
+int bsp_test_ptr_ring_slot_bytes(bsp_solver* s, int64_t* out);
+
 /* Developer aid: with BSP_SWEEP_TRACE=1 in the environment when the solver is created, every spine
  * workgroup of a persistent solve sweep stamps {start, operands on chip, inputs arrived, x published}
  * (wall clock, 100 MHz); this reads the stamps of the LAST sweep, 4 values per block. */

@@ -92,6 +92,19 @@ def affine_plane_cameras(p, pt_size, cam_size, extra=0, extra_size=7):
                            list(range(extra0, n)))
 
 
+def reach_widths():
+    """a chain of lumps of width 1, 16, 63, 64 (below the cut of the reach plan), 65 (the cut) and 7 (behind
+    it), each coupled to the next two; spans of width 1, 16 and 17, lumps of several spans"""
+    from selinv_ref import SkelBuilder
+    b = SkelBuilder()
+    lumps = [b.lump([1]), b.lump([16]), b.lump([17, 5, 16, 1, 24]), b.lump([7, 17, 40]), b.lump([30, 35]),
+             b.lump([4, 3])]
+    for i, l in enumerate(lumps):
+        if lumps[i + 1:i + 3]:
+            b.couple(l, *lumps[i + 1:i + 3])
+    return b.solver()
+
+
 def counter_delta(sol, name, fn):
     before = sol.runCounters()[name]
     fn()

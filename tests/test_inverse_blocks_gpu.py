@@ -15,6 +15,7 @@ import baspacho_amd as B
 from baspacho_amd import testing as T
 from buffer_edges import framed, poison_upper
 from helpers import solver_random, spd_data, to_dev
+from kf_structures import reach_widths
 from selinv_ref import SkelBuilder, dense_reference
 
 pytestmark = pytest.mark.gpu
@@ -28,16 +29,7 @@ DTYPES = [np.float64, np.float32]
 
 
 # ---- structures ----------------------------------------------------------------------------------
-def _widths():
-    """a chain of lumps of width 1, 16, 63, 64 (below the cut), 65 (the cut) and 7 (behind it), each
-    coupled to the next two; spans of width 1, 16 and 17, lumps of several spans"""
-    b = SkelBuilder()
-    lumps = [b.lump([1]), b.lump([16]), b.lump([17, 5, 16, 1, 24]), b.lump([7, 17, 40]), b.lump([30, 35]),
-             b.lump([4, 3])]
-    for i, l in enumerate(lumps):
-        if lumps[i + 1:i + 3]:
-            b.couple(l, *lumps[i + 1:i + 3])
-    return b.solver()
+_widths = reach_widths  # (kf_structures.py: shared with tests/test_history_gpu.py)
 
 
 def _forest():
