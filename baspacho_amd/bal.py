@@ -280,7 +280,7 @@ def lm_optimize(prob, solver, max_iters=50, lam=1e-5, log=None):
     return prob, hist
 
 
-def lm_optimize_device(prob, solver, max_iters=50, lam=1e-5, loss=None, log=None):
+def lm_optimize_device(prob, solver, max_iters=50, lam=1e-5, loss=None, log=None, ordered_fill=False):
     """lm_optimize with the whole iteration resident on the device: one DevicePipeline for the run, H, g,
     step, rho and the sum scratch reused, the candidate retracted (apply_step) and its cost evaluated
     (cost) by device kernels, and ONE device-to-host read per iteration, the 3-element tensor
@@ -288,7 +288,9 @@ def lm_optimize_device(prob, solver, max_iters=50, lam=1e-5, loss=None, log=None
     stopping rules as lm_optimize, line for line.  loss: None, ("huber", a) or ("cauchy", a) -- the robust
     loss of the reference's optimizer (examples/SoftLoss.h; H += rho' J^T J, g += rho' J^T r, cost =
     rho / 2); the costs in the history are then robust costs.  `solver` must have 6-wide camera blocks.
-    Everything runs on the solver's stream.  Returns (problem, cost history)."""
+    ordered_fill=True assembles H and g with fill_hessian_ordered (no atomics: the same bits on every run)
+    instead of fill_hessian; nothing else changes.  Everything runs on the solver's stream.  Returns
+    (problem, cost history)."""
     import torch
     pipe = DevicePipeline(prob, solver, param="se3", loss=loss)
     dev, n = pipe.res.device, solver.order()
@@ -305,7 +307,10 @@ def lm_optimize_device(prob, solver, max_iters=50, lam=1e-5, loss=None, log=None
             pipe.cost_linearized(out=trip[0:1])
             H.zero_()
             g.zero_()
-            pipe.fill_hessian(H, g, lam)
+            if ordered_fill:
+                pipe.fill_hessian_ordered(H, g, lam)
+            else:
+                pipe.fill_hessian(H, g, lam)
             step.copy_(g)
             solver.factor(H)
             solver.solve(H, step, n, 1)
@@ -340,6 +345,69 @@ def lm_optimize_device(prob, solver, max_iters=50, lam=1e-5, loss=None, log=None
 
 LOSS_KINDS = {"huber": 1, "cauchy": 2}   # bsp_bal_loss_f64's kind; 0 = trivial (loss=None)
 
+_I64P = ctypes.POINTER(ctypes.c_int64)
+
+
+class BalFillPlan:
+    """the host plan of the ordered Hessian fill (bsp_bal_fill_plan_create, csrc/bal_fill_plan.h): the
+    observations grouped by point and by camera, the (point, camera) pairs with their blocks, and the camera
+    lists cut into chunks.  obs_cam / obs_pt are host arrays; observations with an index out of range are
+    left out.  Built without a GPU; keeps its solver alive."""
+
+    INFO_KEYS = ("kept", "skipped", "pairs", "chunks", "C", "W", "max_pt_list", "max_cam_list", "scratch_len",
+                 "host_bytes", "device_bytes", "cam_size")
+
+    def __init__(self, solver, cam_size, num_pts, num_cams, obs_cam, obs_pt, num_obs=None):
+        from . import _check
+        self._lib = _lib.load()
+        self._h = None
+        oc = np.ascontiguousarray(obs_cam, dtype=np.int64)
+        op = np.ascontiguousarray(obs_pt, dtype=np.int64)
+        if oc.ndim != 1 or oc.shape != op.shape:
+            raise ValueError("BalFillPlan: obs_cam and obs_pt must be one-dimensional and of one length")
+        n = len(oc) if num_obs is None else int(num_obs)
+        h = ctypes.c_void_p()
+        _check(self._lib.bsp_bal_fill_plan_create(
+            solver._h, ctypes.c_int32(cam_size), ctypes.c_int64(num_pts), ctypes.c_int64(num_cams),
+            ctypes.c_int64(n), oc.ctypes.data_as(_I64P), op.ctypes.data_as(_I64P), ctypes.byref(h)))
+        self._h = h
+        self.solver, self.cam_size, self.num_obs = solver, int(cam_size), n
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.bsp_bal_fill_plan_destroy(h)
+
+    def info(self):
+        """figures of the plan (bsp_bal_fill_plan_info): kept / skipped observations, pairs, chunks, the
+        chunk length C and lanes per element W of the build, the longest point and camera list, the scratch
+        length in doubles, and its bytes on the host and on the device"""
+        from . import _check
+        out = (ctypes.c_int64 * 12)()
+        _check(self._lib.bsp_bal_fill_plan_info(self._h, out))
+        return dict(zip(self.INFO_KEYS, [int(x) for x in out]))
+
+    def _testTables(self):
+        """TESTING: every table of the plan as int64 arrays (bsp_test_bal_fill_plan)"""
+        from . import _check
+        need = ctypes.c_int64(0)
+        _check(self._lib.bsp_test_bal_fill_plan(self._h, None, ctypes.c_int64(0), ctypes.byref(need)))
+        buf = np.empty(need.value, dtype=np.int64)
+        _check(self._lib.bsp_test_bal_fill_plan(self._h, buf.ctypes.data_as(_I64P), need, ctypes.byref(need)))
+        keys = ("numPts", "numCams", "camSize", "kept", "skipped", "nPairs", "nChunks", "C", "W", "scratchLen")
+        out = dict(zip(keys, (int(x) for x in buf[:10])))
+        npt, nc, kept, nq, nk = out["numPts"], out["numCams"], out["kept"], out["nPairs"], out["nChunks"]
+        pos = 10
+        for name, rows in (("ptPtr", npt + 1), ("ptObs", kept), ("pairPtr", nq + 1), ("pairCam", nq),
+                           ("pairPt", nq), ("pairOff", nq), ("pairStride", nq), ("pairFlip", nq),
+                           ("camPtr", nc + 1), ("camObs", kept), ("camChunkPtr", nc + 1), ("chunkCam", nk),
+                           ("chunkBegin", nk), ("chunkEnd", nk), ("ptDiagOff", npt), ("ptDiagStride", npt),
+                           ("ptStart", npt), ("camDiagOff", nc), ("camDiagStride", nc), ("camStart", nc)):
+            out[name] = buf[pos:pos + rows].copy()
+            pos += rows
+        assert pos == len(buf)
+        return out
+
 
 class DevicePipeline:
     """problem data resident on the GPU + the two device stages of a Gauss-Newton / LM iteration.
@@ -359,7 +427,7 @@ class DevicePipeline:
             if name not in LOSS_KINDS:
                 raise ValueError("loss must be None, ('huber', a) or ('cauchy', a), got %r" % (loss,))
             self.loss_kind, self.loss_a = LOSS_KINDS[name], float(a)
-        self.rho = self._cand_res = self._cand_rho = self._sum_scratch = None
+        self.rho = self._cand_res = self._cand_rho = self._sum_scratch = self._fill_plan = None
         self.param = param
         self.cam_size = 9 if param == "bal9" else 6
         self.prob, self.solver = prob, solver
@@ -411,6 +479,31 @@ class DevicePipeline:
         else:
             fn = self.lib.bsp_bal_fill_hessian_f32 if f32 else self.lib.bsp_bal_fill_hessian_f64
             _check(fn(*head, self._p(dbg), self._stream(stream)))
+        return data
+
+    def fill_plan(self):
+        """the BalFillPlan of prob's observation list for this solver, built on first use and kept"""
+        if self._fill_plan is None:
+            self._fill_plan = BalFillPlan(self.solver, self.cam_size, self.prob.num_pts, self.prob.num_cams,
+                                          self.prob.obs_cam, self.prob.obs_pt)
+        return self._fill_plan
+
+    def fill_hessian_ordered(self, data, grad=None, lam=0.0, stream=None):
+        """fill_hessian without atomics (bsp_bal_fill_ordered_*): the same contract, with every sum taken in
+        the order the plan fixes, so that data and grad are the same bits on every run.  The plan is built
+        on the host from prob's observation list on first use (fill_plan()); Jc / Jp / res must hold those
+        observations.  On the solver's stream or on `stream`."""
+        import torch
+        from . import _check
+        plan = self.fill_plan()
+        if plan.num_obs != self.n_obs:
+            raise ValueError("fill_hessian_ordered: the plan holds %d observations, the pipeline %d"
+                             % (plan.num_obs, self.n_obs))
+        f32 = data.dtype == torch.float32
+        fn = self.lib.bsp_bal_fill_ordered_f32 if f32 else self.lib.bsp_bal_fill_ordered_f64
+        _check(fn(self.solver._h, plan._h, self._p(self.Jc), self._p(self.Jp), self._p(self.res),
+                  ctypes.c_float(lam) if f32 else ctypes.c_double(lam), self._p(data), self._p(grad),
+                  self._stream(stream)))
         return data
 
     # ---- the rest of an LM iteration (bsp_bal_residuals / loss / sum / apply_step); like the two stages

@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "accessor.h"
+#include "bal_fill_plan.h"
 
 namespace BaSpaCho {
 
@@ -29,6 +30,34 @@ void balFillHessian(const PermutedCoalescedAccessor& acc, int camSize, int64_t n
                     int64_t numObs, const int64_t* obsCam, const int64_t* obsPt, const double* Jc,
                     const double* Jp, const double* res, T lambda, T* data, T* grad, int64_t* dbg,
                     void* stream);
+
+// ---- ordered fill: the contract of balFillHessian (data += J^T J on the blocks the observations map
+// to, diagonal blocks in full, off-diagonal blocks once and transposed where the accessor says so; grad
+// += J^T r, grad may be NULL; then d <- d (1 + lambda) + 1e-3 lambda on every diagonal entry unless
+// lambda == 0) without atomics: every sum is taken in an order that the plan alone fixes
+// (bal_fill_plan.h), so data and grad are the same bits on every run and every device.  Launches go to
+// `stream`; nothing synchronises the host.  The first call with a plan uploads its tables (one
+// allocation, one blocking copy); later calls allocate nothing.  The chunk partials live in the plan's
+// own scratch, so one plan serves one call at a time (calls on one stream are ordered).
+//
+// SUMMATION ORDER.  J0, J1 are the two residual rows of an observation, r0, r1 its residuals; fl() is
+// one fp64 rounding and nothing is fused.
+//   term of observation o for columns a, b:   fl(fl(J0a * J0b) + fl(J1a * J1b))
+//   gradient term of column a:                fl(fl(J0a * r0) + fl(J1a * r1))
+//   pair block (camera c, point p), element (i, j): S = +0.0, then S = fl(S + term(Jc_i, Jp_j)) over the
+//     pair's run of ptObs, in list order
+//   point block element (i, j) and point gradient entry i: the same left fold over the point's list
+//     ptObs[ptPtr[p] .. ptPtr[p + 1])
+//   camera block element (a, b), a >= b, and camera gradient entry a: for every chunk of the camera's
+//     list, lane l < W = kBalFillLanes folds the terms at the chunk positions l, l + W, l + 2 W, .. from
+//     +0.0; then for h = W / 2, .., 1: T[l] = fl(T[l] + T[l + h]) for l < h; the chunk's partial is T[0].
+//     S = +0.0, then S = fl(S + partial) over the camera's chunks in chunk order.  Element (b, a) gets
+//     the sum of (a, b) (fl(x * y) == fl(y * x), so it is its own sum too).
+//   applied once per element: data[e] = data[e] + (T)S in T arithmetic (likewise grad); an element no
+//     kept observation maps to is not written.
+template <typename T>
+void balFillOrdered(const BalFillPlan& plan, const double* Jc, const double* Jp, const double* res, T lambda,
+                    T* data, T* grad, void* stream);
 
 // ---- the rest of a Levenberg-Marquardt iteration ("LM step on the device").
 // All pointers are device memory, everything is fp64; nothing here uses atomics, synchronises the host

@@ -9,13 +9,19 @@
 // derivatives come from forward-mode dual numbers, so there is no hand-derived Jacobian to get wrong.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <memory>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "accessor.h"
+#include "bal_fill_kernels.h"
 #include "bal_pipeline.h"
+#include "solver.h"
 
 namespace BaSpaCho {
 
@@ -738,5 +744,115 @@ template void balFillHessian<double>(const PermutedCoalescedAccessor&, int, int6
 template void balFillHessian<float>(const PermutedCoalescedAccessor&, int, int64_t, int64_t, int64_t,
                                     const int64_t*, const int64_t*, const double*, const double*,
                                     const double*, float, float*, float*, int64_t*, void*);
+
+// ---- ordered fill (bal_fill_plan.h, bal_fill_kernels.h) ------------------------------------------------
+// The device copy of a plan: one allocation that holds every table the kernels read, each 16-byte
+// aligned, and the scratch of the chunk partials behind them.
+struct BalFillPlanDev {
+  void* blob = nullptr;
+  balfill::Tables tables;
+  ~BalFillPlanDev() {
+    if (blob) (void)hipFree(blob);
+  }
+};
+
+void balFillPlanFreeDevice(BalFillPlanDev* dev) { delete dev; }
+
+namespace {
+
+struct BlobBuilder {
+  std::vector<char> bytes;
+  template <typename U>
+  size_t add(const std::vector<U>& v) {
+    const size_t at = (bytes.size() + 15) / 16 * 16;
+    bytes.resize(at + v.size() * sizeof(U));
+    if (!v.empty()) std::memcpy(bytes.data() + at, v.data(), v.size() * sizeof(U));
+    return at;
+  }
+};
+
+const balfill::Tables& uploadedTables(const BalFillPlan& m) {
+  if (m.dev != nullptr) return m.dev->tables;
+  BlobBuilder b;
+  const size_t oPtPtr = b.add(m.ptPtr), oPtObs = b.add(m.ptObs), oPairPtr = b.add(m.pairPtr);
+  const size_t oPairStride = b.add(m.pairStride), oPairFlip = b.add(m.pairFlip), oPairOff = b.add(m.pairOff);
+  const size_t oCamObs = b.add(m.camObs), oCamChunkPtr = b.add(m.camChunkPtr), oChunkCam = b.add(m.chunkCam);
+  const size_t oChunkBegin = b.add(m.chunkBegin), oChunkEnd = b.add(m.chunkEnd);
+  const size_t oPtDiagOff = b.add(m.ptDiagOff), oCamDiagOff = b.add(m.camDiagOff), oPtStart = b.add(m.ptStart);
+  const size_t oCamStart = b.add(m.camStart), oPtDiagStride = b.add(m.ptDiagStride);
+  const size_t oCamDiagStride = b.add(m.camDiagStride);
+  const size_t oPart = (b.bytes.size() + 15) / 16 * 16;
+  std::unique_ptr<BalFillPlanDev> d(new BalFillPlanDev);
+  balCHECK(hipMalloc(&d->blob, oPart + std::max<size_t>((size_t)m.scratchLen() * sizeof(double), 16)));
+  if (!b.bytes.empty()) balCHECK(hipMemcpy(d->blob, b.bytes.data(), b.bytes.size(), hipMemcpyHostToDevice));
+  char* base = static_cast<char*>(d->blob);
+  auto i32 = [base](size_t o) { return reinterpret_cast<const int32_t*>(base + o); };
+  auto i64 = [base](size_t o) { return reinterpret_cast<const int64_t*>(base + o); };
+  balfill::Tables& t = d->tables;
+  t.ptPtr = i32(oPtPtr);
+  t.ptObs = i32(oPtObs);
+  t.pairPtr = i32(oPairPtr);
+  t.pairStride = i32(oPairStride);
+  t.pairFlip = i32(oPairFlip);
+  t.pairOff = i64(oPairOff);
+  t.camObs = i32(oCamObs);
+  t.camChunkPtr = i32(oCamChunkPtr);
+  t.chunkCam = i32(oChunkCam);
+  t.chunkBegin = i32(oChunkBegin);
+  t.chunkEnd = i32(oChunkEnd);
+  t.ptDiagOff = i64(oPtDiagOff);
+  t.camDiagOff = i64(oCamDiagOff);
+  t.ptStart = i64(oPtStart);
+  t.camStart = i64(oCamStart);
+  t.ptDiagStride = i32(oPtDiagStride);
+  t.camDiagStride = i32(oCamDiagStride);
+  t.part = reinterpret_cast<double*>(base + oPart);
+  m.dev = d.release();
+  return m.dev->tables;
+}
+
+unsigned gridFor(int64_t threads) { return (unsigned)((threads + balfill::kThreads - 1) / balfill::kThreads); }
+
+template <typename T, int CS>
+void launchFillOrdered(const BalFillPlan& m, const balfill::Tables& t, const double* Jc, const double* Jp,
+                       const double* res, T* data, T* grad, hipStream_t s) {
+  using namespace balfill;
+  if (m.numPairs() > 0) {
+    balFillPairs<T, CS><<<dim3(gridFor(m.numPairs() * 3 * CS)), kThreads, 0, s>>>(m.numPairs(), t, Jc, Jp, data);
+  }
+  if (m.numKept > 0) {
+    balFillPoints<T><<<dim3(gridFor(m.numPts * 12)), kThreads, 0, s>>>(m.numPts, t, Jp, res, data, grad);
+    balFillCamChunks<CS><<<dim3((unsigned)m.numChunks()), kThreads, 0, s>>>(t, Jc, res);
+    balFillCamFold<T, CS><<<dim3(gridFor(m.numCams * Partial<CS>::kWords)), kThreads, 0, s>>>(m.numCams, t, data,
+                                                                                             grad);
+  }
+}
+
+}  // namespace
+
+template <typename T>
+void balFillOrdered(const BalFillPlan& plan, const double* Jc, const double* Jp, const double* res, T lambda,
+                    T* data, T* grad, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (plan.numKept > 0) {
+    const balfill::Tables& t = uploadedTables(plan);
+    if (plan.camSize == 6) {
+      launchFillOrdered<T, 6>(plan, t, Jc, Jp, res, data, grad, s);
+    } else {
+      launchFillOrdered<T, 9>(plan, t, Jc, Jp, res, data, grad, s);
+    }
+  }
+  const int64_t numParams = plan.numPts + plan.numCams;
+  if (lambda != T(0) && numParams > 0) {
+    balDampKernel<T><<<dim3((unsigned)((numParams + 255) / 256)), 256, 0, s>>>(plan.solver->deviceAccessor(),
+                                                                              numParams, lambda, data);
+  }
+  balCHECK(hipGetLastError());
+}
+
+template void balFillOrdered<double>(const BalFillPlan&, const double*, const double*, const double*, double,
+                                     double*, double*, void*);
+template void balFillOrdered<float>(const BalFillPlan&, const double*, const double*, const double*, float, float*,
+                                    float*, void*);
 
 }  // namespace BaSpaCho

@@ -1015,6 +1015,84 @@ int bsp_bal_fill_hessian_se3_f32(bsp_solver* s, int64_t numPts, int64_t numCams,
   BSP_CATCH
 }
 
+// ---- ordered fill (bal_fill_plan.h): a plan per problem, then the fill without atomics
+struct bsp_bal_fill_plan {
+  std::unique_ptr<BalFillPlan> plan;
+};
+
+int bsp_bal_fill_plan_create(bsp_solver* s, int32_t camSize, int64_t numPts, int64_t numCams, int64_t numObs,
+                             const int64_t* obsCam, const int64_t* obsPt, bsp_bal_fill_plan** out) {
+  BSP_TRY
+  if (s == nullptr || out == nullptr) throw std::runtime_error("bsp_bal_fill_plan_create: NULL solver or output");
+  std::unique_ptr<bsp_bal_fill_plan> p(new bsp_bal_fill_plan);
+  p->plan = createBalFillPlan(*s->solver, camSize, numPts, numCams, numObs, obsCam, obsPt);
+  *out = p.release();
+  BSP_CATCH
+}
+void bsp_bal_fill_plan_destroy(bsp_bal_fill_plan* p) { delete p; }
+int bsp_bal_fill_plan_info(const bsp_bal_fill_plan* p, int64_t out[12]) {
+  BSP_TRY
+  if (p == nullptr || out == nullptr) throw std::runtime_error("bsp_bal_fill_plan_info: NULL argument");
+  const BalFillPlan& m = *p->plan;
+  const int64_t v[12] = {m.numKept,    m.numSkipped, m.numPairs(),   m.numChunks(), kBalFillChunk,    kBalFillLanes,
+                         m.maxPtList,  m.maxCamList, m.scratchLen(), m.hostBytes(), m.deviceBytes(), m.camSize};
+  std::copy(v, v + 12, out);
+  BSP_CATCH
+}
+template <typename T>
+static void balFillOrderedRun(bsp_solver* s, const bsp_bal_fill_plan* p, const double* Jc, const double* Jp,
+                              const double* res, T lambda, T* data, T* grad, void* stream) {
+  const std::string what = "bsp_bal_fill_ordered: ";
+  if (s == nullptr) throw std::runtime_error(what + "the solver is NULL");
+  if (p == nullptr) throw std::runtime_error(what + "the plan is NULL");
+  const BalFillPlan& m = *p->plan;
+  if (m.solver != s->solver.get()) throw std::runtime_error(what + "the plan was built for another solver");
+  if (data == nullptr) throw std::runtime_error(what + "data is NULL");
+  if (m.numObs > 0 && (Jc == nullptr || Jp == nullptr || res == nullptr)) {
+    throw std::runtime_error(what + "Jc, Jp or res is NULL");
+  }
+  balFillOrdered<T>(m, Jc, Jp, res, lambda, data, grad, stream);
+}
+int bsp_bal_fill_ordered_f64(bsp_solver* s, const bsp_bal_fill_plan* p, const double* Jc, const double* Jp,
+                             const double* res, double lambda, double* data, double* grad, void* stream)
+    BSP_BODY(balFillOrderedRun<double>(s, p, Jc, Jp, res, lambda, data, grad, stream))
+int bsp_bal_fill_ordered_f32(bsp_solver* s, const bsp_bal_fill_plan* p, const double* Jc, const double* Jp,
+                             const double* res, float lambda, float* data, float* grad, void* stream)
+    BSP_BODY(balFillOrderedRun<float>(s, p, Jc, Jp, res, lambda, data, grad, stream))
+
+// the plan's tables for the CPU tests (layout: include/baspacho_amd_testing.h)
+int bsp_test_bal_fill_plan(const bsp_bal_fill_plan* p, int64_t* buf, int64_t capacity, int64_t* needed) {
+  BSP_TRY
+  if (p == nullptr || needed == nullptr) throw std::runtime_error("bsp_test_bal_fill_plan: NULL argument");
+  const BalFillPlan& m = *p->plan;
+  std::vector<int64_t> v = {m.numPts,       m.numCams,     m.camSize,     m.numKept,     m.numSkipped,
+                            m.numPairs(),   m.numChunks(), kBalFillChunk, kBalFillLanes, m.scratchLen()};
+  auto put = [&v](const auto& a) { v.insert(v.end(), a.begin(), a.end()); };
+  put(m.ptPtr);
+  put(m.ptObs);
+  put(m.pairPtr);
+  put(m.pairCam);
+  put(m.pairPt);
+  put(m.pairOff);
+  put(m.pairStride);
+  put(m.pairFlip);
+  put(m.camPtr);
+  put(m.camObs);
+  put(m.camChunkPtr);
+  put(m.chunkCam);
+  put(m.chunkBegin);
+  put(m.chunkEnd);
+  put(m.ptDiagOff);
+  put(m.ptDiagStride);
+  put(m.ptStart);
+  put(m.camDiagOff);
+  put(m.camDiagStride);
+  put(m.camStart);
+  *needed = (int64_t)v.size();
+  if (buf != nullptr) std::copy(v.begin(), v.begin() + std::min<int64_t>(capacity, *needed), buf);
+  BSP_CATCH
+}
+
 int bsp_bal_residuals_f64(int64_t numObs, const int64_t* obsCam, const int64_t* obsPt,
                           const double* obsXy, const double* cams, const double* pts, double* res,
                           void* stream) {

@@ -682,6 +682,38 @@ int bsp_bal_apply_step_se3_f64(bsp_solver* s, int64_t num_pts, int64_t num_cams,
                                const double* pts, const double* step, double* cams_out, double* pts_out,
                                void* stream);
 
+/* ---- Ordered Hessian fill: the contract of the bsp_bal_fill_hessian entries without atomics, so that data
+   and grad are the same bits on every run and every device (the summation order is stated in
+   csrc/bal_pipeline.h and DESIGN.md section 9).
+   bsp_bal_fill_plan_create builds the plan once per problem on the host (no device work) from HOST
+   arrays obs_cam / obs_pt of num_obs entries; cam_size is 9 or 6.  An observation whose camera or point
+   index is out of range is left out (and counted), as the atomic fill skips it.  It fails, with
+   bsp_last_error(), for num_obs >= 2^31, for a solver that does not have num_pts parameters of size 3
+   followed by num_cams of size cam_size (order 3 num_pts + cam_size num_cams), and for an observation
+   whose block the solver does not store.  A plan belongs to the solver it was built on and must be
+   destroyed before it.
+   bsp_bal_fill_plan_info: out[12] = kept observations, skipped observations, (point, camera) pairs,
+   chunks of the camera lists, chunk length C, lanes per element W, longest point list, longest camera
+   list, scratch length (doubles), bytes of the plan on the host, bytes on the device (tables + scratch),
+   cam_size.
+   bsp_bal_fill_ordered: Jc[nObs][2][cam_size], Jp[nObs][2][3], res[nObs][2] are fp64 device arrays of the
+   num_obs observations the plan was built from; data += J^T J, grad += J^T r (grad may be NULL), then the
+   damping d <- d (1 + lambda) + 1e-3 lambda of every diagonal entry unless lambda == 0.  Every launch goes
+   to `stream`; no atomics, no host synchronisation; the first call with a plan uploads its tables (one
+   allocation, one blocking copy), later calls allocate nothing.  The partial sums live in the plan, so one
+   plan serves one call at a time.  A NULL solver, plan, data, Jc, Jp or res, or a plan built on another
+   solver: non-zero return, nothing launched. */
+typedef struct bsp_bal_fill_plan bsp_bal_fill_plan;
+int bsp_bal_fill_plan_create(bsp_solver* s, int32_t cam_size, int64_t num_pts, int64_t num_cams, int64_t num_obs,
+                             const int64_t* obs_cam, const int64_t* obs_pt, bsp_bal_fill_plan** out);
+void bsp_bal_fill_plan_destroy(bsp_bal_fill_plan* p);
+int bsp_bal_fill_plan_info(const bsp_bal_fill_plan* p, int64_t out[12]);
+int bsp_bal_fill_ordered_f64(bsp_solver* s, const bsp_bal_fill_plan* p, const double* Jc, const double* Jp,
+                             const double* res, double lambda, double* dev_data, double* dev_grad,
+                             void* stream);
+int bsp_bal_fill_ordered_f32(bsp_solver* s, const bsp_bal_fill_plan* p, const double* Jc, const double* Jp,
+                             const double* res, float lambda, float* dev_data, float* dev_grad, void* stream);
+
 /* ---- measurement helpers (no reference counterpart; Solver::printStats is the analogue) */
 /* algorithmic flops of a full factor: sum over lumps n^3/3 + r n^2 + r^2 n */
 double bsp_factor_flops(const bsp_solver* s);

@@ -83,6 +83,15 @@ int bsp_test_set_selinv_batch_chunk(bsp_solver* s, int32_t max_matrices);
  * (wait for the device, free every slot, allocate anew) ran in between (tests/test_history_gpu.py). */
 int bsp_test_ptr_ring_slot_bytes(bsp_solver* s, int64_t* out);
 
+/* The tables of an ordered-fill plan (csrc/bal_fill_plan.h), copied out for the CPU tests.  Layout (int64):
+ *   numPts, numCams, camSize, kept, skipped, nPairs, nChunks, C, W, scratchLen;
+ *   ptPtr[numPts + 1], ptObs[kept], pairPtr[nPairs + 1], pairCam, pairPt, pairOff, pairStride,
+ *   pairFlip [nPairs each], camPtr[numCams + 1], camObs[kept], camChunkPtr[numCams + 1], chunkCam,
+ *   chunkBegin, chunkEnd [nChunks each], ptDiagOff, ptDiagStride, ptStart [numPts each], camDiagOff,
+ *   camDiagStride, camStart [numCams each].
+ * buf / capacity / needed as bsp_test_selinv_plan. */
+int bsp_test_bal_fill_plan(const bsp_bal_fill_plan* p, int64_t* buf, int64_t capacity, int64_t* needed);
+
 /* Developer aid: with BSP_SWEEP_TRACE=1 in the environment when the solver is created, every spine
  * workgroup of a persistent solve sweep stamps {start, operands on chip, inputs arrived, x published}
  * (wall clock, 100 MHz); this reads the stamps of the LAST sweep, 4 values per block. */

@@ -10,8 +10,10 @@ camera blocks; --problem bal871 takes the BAL-871 stand-in of bench.py instead (
 time runs from the previous iteration's log line (taken after the loop's last host read, so the device is
 idle) to its own, and the median over the iterations of the timed run is reported.  Beside them the device-
 event times of the four new stages (residual-only kernel, loss with the scaling pass, the two-pass sum, the
-retraction), warmed up, median of --reps, and for the loss its bytes over its time against the HBM peak.  One
-JSON line.
+retraction), warmed up, median of --reps, and for the loss its bytes over its time against the HBM peak.  The
+Hessian fill is timed in its parts: the zeroing of H and g alone, the atomic fill alone and, where the library has
+it, the ordered fill alone (bsp_bal_fill_ordered_*), the wall time per iteration of lm_optimize_device with
+ordered_fill=True, and the one-time build of the plan on the host with its size.  One JSON line.
 
     python tools/bal_lm_time.py [--problem balsmall|bal871] [--iters 10] [--reps 7] [--loss huber:2.0]
 """
@@ -75,6 +77,16 @@ def main():
         rec[name + "_iterations"] = len(hist)
         rec[name + "_final_cost"] = hist[-1][1] if hist[-1][1] <= hist[-1][0] else hist[-1][0]
     rec["device_over_host_loop"] = round(rec["lm_optimize_device_iter_ms"] / rec["lm_optimize_iter_ms"], 4)
+    # the ordered fill is timed where the loaded library has it (a parent build loaded through BSP_LIB_PATH has not)
+    ordered = hasattr(bal._lib.load(), "bsp_bal_fill_ordered_f64")
+    if ordered:
+        run = lambda log: bal.lm_optimize_device(prob, sol, max_iters=a.iters, log=log, ordered_fill=True)
+        _iteration_times(run)
+        ms, hist = _iteration_times(run)
+        rec["lm_optimize_device_ordered_iter_ms"] = round(float(np.median(ms)), 3)
+        rec["lm_optimize_device_ordered_iter_ms_min_max"] = [round(float(ms.min()), 3), round(float(ms.max()), 3)]
+        rec["lm_optimize_device_ordered_iterations"] = len(hist)
+        rec["lm_optimize_device_ordered_final_cost"] = hist[-1][1] if hist[-1][1] <= hist[-1][0] else hist[-1][0]
 
     kind, size = a.loss.split(":")
     pipe = bal.DevicePipeline(prob, sol, param="se3", loss=(kind, float(size)))
@@ -114,6 +126,26 @@ def main():
         pipe.fill_hessian(H, g, 1e-5)
     restore()
     rec["zero_fill_hessian_ms"] = timed(fill, a.warmup, a.reps)
+    rec["zero_ms"] = timed(lambda: (H.zero_(), g.zero_()), a.warmup, a.reps)
+    # the fills alone: they add to what H and g hold, which only grows (1e30 is far away in these few passes)
+    rec["fill_hessian_ms"] = timed(lambda: pipe.fill_hessian(H, g, 1e-5), a.warmup, a.reps)
+    if ordered:
+        t0 = time.perf_counter()
+        plan = pipe.fill_plan()
+        rec["fill_plan_build_ms"] = round((time.perf_counter() - t0) * 1e3, 2)
+        rec["fill_plan"] = plan.info()
+
+        def fill_ordered():
+            H.zero_(), g.zero_()
+            pipe.fill_hessian_ordered(H, g, 1e-5)
+        rec["zero_fill_hessian_ordered_ms"] = timed(fill_ordered, a.warmup, a.reps)
+        rec["fill_hessian_ordered_ms"] = timed(lambda: pipe.fill_hessian_ordered(H, g, 1e-5), a.warmup, a.reps)
+        fill_ordered()
+        Ho, go = H.clone(), g.clone()
+        fill_ordered()
+        rec["ordered_fill_repeats_bitwise"] = bool(torch.equal(H, Ho) and torch.equal(g, go))
+        fill()
+        rec["ordered_vs_atomic_max_rel"] = float(((H - Ho).abs().max() / Ho.abs().max()).item())
     fill()
     Hf = H.clone()
 
