@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["Settings", "Solver", "FactorizationError", "Assembly", "NormalEquations", "create_solver", "SparseStructure", "BackendHip", "BackendCuda",
+__all__ = ["Settings", "Solver", "FactorizationError", "Assembly", "NormalEquations", "SymProduct", "create_solver", "SparseStructure", "BackendHip", "BackendCuda",
            "BackendRef", "BackendFast", "AddFillComplete", "AddFillForAutoElims",
            "AddFillForGivenElims", "AddFillNone"]
 
@@ -1136,6 +1136,13 @@ class Solver:
         No (row, col) may repeat.  See NormalEquations."""
         return NormalEquations(self, rows, cols, m)
 
+    # ---- products with a matrix given as entries (DESIGN.md section 21) ---------------------
+    def symProduct(self, rows, cols, triangle="lower"):
+        """extension: the map of the products with the symmetric matrix of the coordinate entries
+        (rows[k], cols[k]) in the caller's scalar order (bsp_sym_product_create), built once on the
+        host; triangle as for assembly().  See SymProduct."""
+        return SymProduct(self, rows, cols, triangle)
+
     def diagOffsets(self):
         """extension: int64 array [order()], the layout offsets of the diagonal elements in internal
         order (what damp() touches)"""
@@ -1451,6 +1458,115 @@ class NormalEquations:
     def jVec(self, values, v, out=None):
         """v [n] or [n, q] (leading B when values are batched) -> J v, [m] / [m, q] (bsp_normal_eq_j_vec_*)"""
         return self._run("jVec", "bsp_normal_eq_j_vec_", values, v, self.n, self.m, out)
+
+
+class SymProduct:
+    """extension: products with the symmetric matrix A of the coordinate entries
+    (rows[k], cols[k], values[k]) in the caller's scalar order, taken straight from the entries: the solver's
+    layout is never built.  Built by Solver.symProduct(); keeps its solver alive.  A is the matrix
+    Solver.assembly() builds from the same entries (same triangle and index rules).  mv: A x; outer: the
+    gradient of the values of sum(g * (A x)).  Sums run in a fixed order with every product rounded first
+    (bitwise the numpy restatement); each part of the map is uploaded by the first call that needs it;
+    everything runs on the solver's stream without synchronising."""
+
+    def __init__(self, solver, rows, cols, triangle="lower"):
+        if triangle not in _TRIANGLES:
+            raise ValueError("symProduct: triangle must be 'lower' or 'full', got %r" % (triangle,))
+        self._lib = solver._lib
+        self._h = None
+        r, c = _host_indices(rows, "rows"), _host_indices(cols, "cols")
+        if len(r) != len(c):
+            raise ValueError("symProduct: %d rows for %d cols" % (len(r), len(c)))
+        h = ctypes.c_void_p()
+        _check(self._lib.bsp_sym_product_create(solver._h, ctypes.c_int64(len(r)), r.ctypes.data_as(_I64P),
+                                                c.ctypes.data_as(_I64P), ctypes.c_int32(_TRIANGLES[triangle]),
+                                                ctypes.byref(h)))
+        self._h = h
+        self.solver = solver
+        self.nnz = len(r)
+        self.n = solver.order()
+        self.triangle = triangle
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.bsp_sym_product_destroy(h)
+
+    def info(self):
+        """figures of the map (bsp_sym_product_info)"""
+        out = (ctypes.c_int64 * 6)()
+        _check(self._lib.bsp_sym_product_info(self._h, out))
+        keys = ["nnz", "kept", "terms", "max_row", "long_rows", "device_bytes"]
+        return dict(zip(keys, [int(x) for x in out]))
+
+    def rowTable(self):
+        """(row_start, entry, index): the terms of row i are (entry[t], index[t]), t in [row_start[i],
+        row_start[i + 1]); int32 arrays of order() + 1, info()["terms"] and info()["terms"] values"""
+        T = self.info()["terms"]
+        start = np.empty(self.n + 1, dtype=np.int32)
+        entry, index = np.empty(T, dtype=np.int32), np.empty(T, dtype=np.int32)
+        _check(self._lib.bsp_sym_product_row_table(self._h, start.ctypes.data_as(_I32P),
+                                                   entry.ctypes.data_as(_I32P), index.ctypes.data_as(_I32P)))
+        return start, entry, index
+
+    def _run(self, name, fn, a, a_what, x, out, batched):
+        """a: values [nnz] / [B, nnz] (mv) or g, shaped like x (outer); x [n] / [n, q], or those with a
+        leading B when `batched`; out [.., n(, q)] (mv) or [.., nnz] (outer)"""
+        import torch
+        for what, t in ((a_what, a), ("x", x)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s: %s must be a torch.Tensor, got %s" % (name, what, type(t).__name__))
+        if x.dtype != a.dtype or x.device != a.device:
+            raise TypeError("%s: x is %s on %s, %s is %s on %s" % (name, x.dtype, x.device, a_what, a.dtype, a.device))
+        sfx = _suffix(a)
+        mv = a_what == "values"
+        if mv and (a.dim() != (2 if batched else 1) or a.shape[-1] != self.nnz):
+            raise ValueError("%s: values must be [%d] or [B, %d], got shape %s"
+                             % (name, self.nnz, self.nnz, tuple(a.shape)))
+        if not mv and a.shape != x.shape:
+            raise ValueError("%s: g has shape %s, x has %s" % (name, tuple(a.shape), tuple(x.shape)))
+        lo = 1 if batched else 0
+        if x.dim() not in (lo + 1, lo + 2) or x.shape[lo] != self.n or (mv and x.shape[:lo] != a.shape[:lo]):
+            raise ValueError("%s: x must be %s with n = %d, got shape %s" % (
+                name, "[B, n] or [B, n, q]" if batched else "[n] or [n, q]", self.n, tuple(x.shape)))
+        if batched and x.shape[0] == 0:
+            raise ValueError("%s: empty batch" % name)
+        has_q = x.dim() == lo + 2
+        q = x.shape[-1] if has_q else 1
+        if q < 1:
+            raise ValueError("%s: x has no vectors" % name)
+        shape = tuple(x.shape) if mv else tuple(x.shape[:lo]) + (self.nnz,)
+        if out is None:
+            out = torch.empty(shape, dtype=a.dtype, device=a.device)
+        elif tuple(out.shape) != shape or out.dtype != a.dtype or out.device != a.device:
+            raise ValueError("%s: out must be %s %s on %s, got %s %s on %s" % (
+                name, shape, a.dtype, a.device, tuple(out.shape), out.dtype, out.device))
+        ts = [a, x, out]
+        for t in ts:
+            _ptr_of(t)  # device memory, contiguous
+        ptrs = [_ptr_arg(t.unbind(0) if batched else [t], batched) for t in ts]
+        _call(self._lib, fn, batched, sfx, self.solver._h, self._h, ptrs[0], ptrs[1], ctypes.c_int64(q), ptrs[2],
+              *_count(out, batched))
+        return out
+
+    def mv(self, values, x, out=None):
+        """values [nnz] or [B, nnz] (device, float64 / float32); x [n] or [n, q] in the caller's order (leading
+        B when values are batched) -> A x, shaped like x: every element written, +0 for a row without terms
+        (bsp_sym_product_mv_*)"""
+        import torch
+        return self._run("mv", "bsp_sym_product_mv_", values, "values", x, out,
+                         isinstance(values, torch.Tensor) and values.dim() == 2)
+
+    def outer(self, g, x, out=None, batched=None):
+        """g and x of one shape, [n] or [n, q], or those with a leading B -> the gradient of the values of
+        sum(g * (A x)), [nnz] / [B, nnz]: sum_j g[r, j] x[c, j] (+ g[c, j] x[r, j] off the diagonal) at entry
+        k = (r, c), 0 for skipped entries, the full value for every duplicate (bsp_sym_product_outer_*).
+        Three dimensions are a batch, one is not; two are [n, q] unless batched=True or `out` is [B, nnz]"""
+        import torch
+        if batched is None:
+            dims = x.dim() if isinstance(x, torch.Tensor) else 0
+            batched = dims == 3 or (dims == 2 and isinstance(out, torch.Tensor) and out.dim() == 2)
+        return self._run("outer", "bsp_sym_product_outer_", g, "g", x, out, bool(batched))
 
 
 def probe_mfma_f64_tflops():

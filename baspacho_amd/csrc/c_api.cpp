@@ -11,6 +11,7 @@
 
 #include "assembly.h"
 #include "normal_eq.h"
+#include "sym_product.h"
 #include "reach.h"
 #include "bal_pipeline.h"
 #include "../../include/baspacho_amd_testing.h"
@@ -818,6 +819,67 @@ static void normalEqRun(bsp_solver* s, const bsp_normal_eq* e, int32_t op, const
 BSP_NORMAL_EQ_API(f64, double)
 BSP_NORMAL_EQ_API(f32, float)
 #undef BSP_NORMAL_EQ_API
+struct bsp_sym_product {
+  std::unique_ptr<SymProductMap> map;
+};
+
+int bsp_sym_product_create(bsp_solver* s, int64_t nnz, const int64_t* rows, const int64_t* cols, int32_t triangle,
+                           bsp_sym_product** out) {
+  BSP_TRY
+  if (s == nullptr || out == nullptr) throw std::runtime_error("bsp_sym_product_create: NULL solver or output");
+  std::unique_ptr<bsp_sym_product> p(new bsp_sym_product);
+  p->map = createSymProductMap(*s->solver, nnz, rows, cols, triangle);
+  *out = p.release();
+  BSP_CATCH
+}
+void bsp_sym_product_destroy(bsp_sym_product* p) { delete p; }
+int bsp_sym_product_info(const bsp_sym_product* p, int64_t out[6]) {
+  BSP_TRY
+  if (p == nullptr || out == nullptr) throw std::runtime_error("bsp_sym_product_info: NULL argument");
+  const SymProductMap& m = *p->map;
+  const int64_t v[6] = {m.nnz, m.kept, m.numTerms(), m.maxRow, (int64_t)m.longRows.size(),
+                        m.rowDeviceBytes() + m.entryDeviceBytes()};
+  std::copy(v, v + 6, out);
+  BSP_CATCH
+}
+int bsp_sym_product_row_table(const bsp_sym_product* p, int32_t* row_start, int32_t* entry, int32_t* index) {
+  BSP_TRY
+  if (p == nullptr) throw std::runtime_error("bsp_sym_product_row_table: the map is NULL");
+  const SymProductMap& m = *p->map;
+  if (row_start == nullptr || (m.numTerms() > 0 && (entry == nullptr || index == nullptr))) {
+    throw std::runtime_error("bsp_sym_product_row_table: an output array is NULL");
+  }
+  std::copy(m.rowStart.begin(), m.rowStart.end(), row_start);
+  std::copy(m.termEntry.begin(), m.termEntry.end(), entry);
+  std::copy(m.termIdx.begin(), m.termIdx.end(), index);
+  BSP_CATCH
+}
+template <typename T>
+static void symProductRun(bsp_solver* s, const bsp_sym_product* p, int32_t op, const T* const* a, const T* const* x,
+                          T* const* out, int64_t q, int32_t batch, bool single) {
+  const std::string what = op == SymProductMv ? "symProductMv" : "symProductOuter";
+  if (s == nullptr) throw std::runtime_error(what + ": the solver is NULL");
+  if (p == nullptr) throw std::runtime_error(what + ": the map is NULL");
+  const std::vector<const T*> as = hostArray<const T*>(what, nullptr, a, batch);
+  const std::vector<const T*> xs = hostArray<const T*>(what, nullptr, x, batch);
+  const std::vector<T*> o = hostArray<T*>(what, nullptr, out, batch);
+  s->solver->symProduct<T>(*p->map, op, as, xs, o, q, single);
+}
+#define BSP_SYM_PRODUCT_API(SFX, T)                                                                              \
+  int bsp_sym_product_mv_##SFX(bsp_solver* s, const bsp_sym_product* p, const T* v, const T* x, int64_t q,       \
+                               T* out) BSP_BODY(symProductRun<T>(s, p, SymProductMv, &v, &x, &out, q, 1, true))  \
+  int bsp_sym_product_mv_batched_##SFX(bsp_solver* s, const bsp_sym_product* p, const T* const* v,               \
+                                       const T* const* x, int64_t q, T* const* out, int32_t batch)               \
+      BSP_BODY(symProductRun<T>(s, p, SymProductMv, v, x, out, q, batch, false))                                 \
+  int bsp_sym_product_outer_##SFX(bsp_solver* s, const bsp_sym_product* p, const T* g, const T* x, int64_t q,    \
+                                  T* out)                                                                        \
+      BSP_BODY(symProductRun<T>(s, p, SymProductOuter, &g, &x, &out, q, 1, true))                                \
+  int bsp_sym_product_outer_batched_##SFX(bsp_solver* s, const bsp_sym_product* p, const T* const* g,            \
+                                          const T* const* x, int64_t q, T* const* out, int32_t batch)            \
+      BSP_BODY(symProductRun<T>(s, p, SymProductOuter, g, x, out, q, batch, false))
+BSP_SYM_PRODUCT_API(f64, double)
+BSP_SYM_PRODUCT_API(f32, float)
+#undef BSP_SYM_PRODUCT_API
 int bsp_scalar_permutation(const bsp_solver* s, int64_t* out) {
   BSP_TRY
   if (out == nullptr) throw std::runtime_error("bsp_scalar_permutation: out is NULL");

@@ -187,6 +187,18 @@ void hipBackendNormalEq(SymbolicCtx& sym, const NormalEqMap& map, int32_t op, co
                         const T* const* x, T* const* out, int64_t q, int64_t batch, bool single);
 void hipBackendFreeNormalEq(HipNormalEqDev* dev);
 
+// Products with a symmetric matrix given as entries (hip_sym_product_kernels.h).
+// Each part of the map is uploaded on the first call that needs it and kept in map.dev.
+//   SymProductMv:     out = A x ([n, q] each) from a = values (nnz) and b = x ([n, q])
+//   SymProductOuter:  out = gradient of the values (nnz) from a = g and b = x ([n, q] both)
+struct SymProductMap;
+struct HipSymProductDev;
+enum SymProductOp : int32_t { SymProductMv = 0, SymProductOuter = 1 };
+template <typename T>
+void hipBackendSymProduct(SymbolicCtx& sym, const SymProductMap& map, int32_t op, const T* const* a,
+                          const T* const* b, T* const* out, int64_t q, int64_t batch, bool single);
+void hipBackendFreeSymProduct(HipSymProductDev* dev);
+
 // Reach solves (hip_reach_kernels.h), one matrix, plan from buildReachPlan (reach.h).
 // reachSolveL: W (numCols x order, column-major, leading dimension order) <- the unit columns of the
 // queries solved through the lumps of their reach below the plan's cut; the caller then runs

@@ -1,6 +1,7 @@
 // MI355X backend, the extension operations of hip_backend.h: selected inversion and its adjoint,
 // log-det and gradients on the pattern of L, factor status and damping, the reverse-mode sweep of the
-// factor, the dense Schur complement, assembly of coordinate entries and normal equations.  Every
+// factor, the dense Schur complement, assembly of coordinate entries, normal equations and products
+// with a matrix given as entries.  Every
 // entry point stages its pointer arguments, splits the batch into chunks and enqueues the launches
 // of a chunk on the execution stream (the call path: HipSymbolicCtx::stage / forChunks).
 #include "hip_context.h"
@@ -12,6 +13,7 @@
 #include "hip_selinv_adjoint_kernels.h"
 #include "hip_selinv_kernels.h"
 #include "hip_status_kernels.h"
+#include "hip_sym_product_kernels.h"
 
 namespace BaSpaCho {
 
@@ -63,6 +65,24 @@ struct HipNormalEqDev {
     rowEntry.upload(m.rowEntry);
     rowIdx.upload(m.rowIdx);
     hasVectors = true;
+  }
+};
+
+// the two parts of a symmetric-product map on the device (sym_product.h), owned by its SymProductMap
+struct HipSymProductDev {
+  bool hasRows = false, hasEntries = false;
+  DevBuf rowStart, termEntry, termIdx, longRows, entRow, entCol;
+  void uploadRows(const SymProductMap& m) {
+    rowStart.upload(m.rowStart);
+    termEntry.upload(m.termEntry);
+    termIdx.upload(m.termIdx);
+    longRows.upload(m.longRows);
+    hasRows = true;
+  }
+  void uploadEntries(const SymProductMap& m) {
+    entRow.upload(m.entRow);
+    entCol.upload(m.entCol);
+    hasEntries = true;
   }
 };
 
@@ -751,6 +771,40 @@ void hipBackendNormalEq(SymbolicCtx& sym, const NormalEqMap& m, int32_t op, cons
   });
 }
 
+// ---- products with a matrix given as entries (hip_sym_product_kernels.h) ------
+// mv (a = values, b = x, out = A x) or outer (a = g, b = x, out = the gradient of the values) on `batch`
+// members: one launch per chunk
+template <typename T>
+void hipBackendSymProduct(SymbolicCtx& sym, const SymProductMap& m, int32_t op, const T* const* a, const T* const* b,
+                          T* const* out, int64_t q, int64_t batch, bool single) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  BASPACHO_CHECK_LT(q, (int64_t)INT32_MAX);
+  if (m.dev == nullptr) m.dev = new HipSymProductDev;
+  HipSymProductDev& d = *m.dev;
+  if (op == SymProductMv && !d.hasRows) d.uploadRows(m);
+  if (op == SymProductOuter && !d.hasEntries) d.uploadEntries(m);
+  if (op == SymProductMv ? m.n * q == 0 : m.nnz == 0) return;
+  const BatchPtrs<const T> as = h.stage(a, batch, single), bs = h.stage(b, batch, single);
+  const BatchPtrs<T> o = h.stage(out, batch, single);
+  const int64_t shortWgs = (m.n * q + hipk::kAsmThreads - 1) / hipk::kAsmThreads;
+  const int64_t longWaves = (int64_t)m.longRows.size() * q;
+  const int64_t longWgs = (longWaves + hipk::kNeqWavesPerWg - 1) / hipk::kNeqWavesPerWg;
+  const int64_t outerWgs = (m.nnz + hipk::kAsmThreads - 1) / hipk::kAsmThreads;
+  BASPACHO_CHECK_LT(shortWgs + longWgs, (int64_t)INT32_MAX);
+  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+    if (op == SymProductMv) {
+      hipk::symProductMv<T><<<dim3((unsigned)(shortWgs + longWgs), nm), hipk::kAsmThreads, 0, stream>>>(
+          m.n, (int32_t)q, (int32_t)shortWgs, longWaves, d.rowStart.as<int32_t>(), d.termEntry.as<int32_t>(),
+          d.termIdx.as<int32_t>(), d.longRows.as<int32_t>(), as.at(q0), bs.at(q0), o.at(q0));
+    } else {
+      hipk::symProductOuter<T><<<dim3((unsigned)outerWgs, nm), hipk::kAsmThreads, 0, stream>>>(
+          m.nnz, (int32_t)q, d.entRow.as<int32_t>(), d.entCol.as<int32_t>(), as.at(q0), bs.at(q0), o.at(q0));
+    }
+  });
+}
+
 // ---- reach solves (hip_reach_kernels.h) ---------------------------------------
 // W (numCols x order, column-major) <- the unit columns of the plan's queries, solved through the lumps
 // of their reach below the cut: one memset, the unit entries of the queries behind the cut, one launch
@@ -828,6 +882,8 @@ T* hipBackendReachWorkspace(SymbolicCtx& sym, int64_t elems) {
                                       bool, bool);                                                              \
   template void hipBackendNormalEq<T>(SymbolicCtx&, const NormalEqMap&, int32_t, const T* const*,               \
                                       const T* const*, T* const*, int64_t, int64_t, bool);                      \
+  template void hipBackendSymProduct<T>(SymbolicCtx&, const SymProductMap&, int32_t, const T* const*,           \
+                                        const T* const*, T* const*, int64_t, int64_t, bool);                    \
   template void hipBackendReachSolveL<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                         \
   template void hipBackendGramBlocks<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                          \
   template T* hipBackendReachWorkspace<T>(SymbolicCtx&, int64_t);
@@ -837,5 +893,6 @@ BSP_INSTANTIATE_EXTENSIONS(float)
 
 void hipBackendFreeAssembly(HipAssemblyDev* dev) { delete dev; }
 void hipBackendFreeNormalEq(HipNormalEqDev* dev) { delete dev; }
+void hipBackendFreeSymProduct(HipSymProductDev* dev) { delete dev; }
 
 }  // namespace BaSpaCho

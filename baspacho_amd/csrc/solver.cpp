@@ -16,6 +16,7 @@
 #include "assembly.h"
 #include "normal_eq.h"
 #include "reach.h"
+#include "sym_product.h"
 #include "computation_model.h"
 #include "elimination_tree.h"
 #include "hip_backend.h"
@@ -999,6 +1000,52 @@ void Solver::normalEq(const NormalEqMap& map, int32_t op, const std::vector<cons
   hipBackendNormalEq<T>(*symCtx, map, op, values.data(), hasX ? x.data() : nullptr, out.data(), q,
                         (int64_t)values.size(), single);
 }
+// ---- products with a matrix given as entries (sym_product.h) -------------------
+template <typename T>
+void Solver::symProduct(const SymProductMap& map, int32_t op, const std::vector<const T*>& a,
+                        const std::vector<const T*>& x, const std::vector<T*>& out, int64_t q, bool single) const {
+  if (op != SymProductMv && op != SymProductOuter) {
+    throw std::runtime_error("symProduct: unknown operation " + std::to_string(op));
+  }
+  const bool mv = op == SymProductMv;
+  const char* what = mv ? "symProductMv" : "symProductOuter";
+  const auto fail = [what](const std::string& m) { throw std::runtime_error(std::string(what) + ": " + m); };
+  if (map.solver != this) fail("the map was built on another solver");
+  if (a.empty()) fail("the batch is empty");
+  if (a.size() != out.size() || x.size() != a.size()) {
+    fail("the batch has " + std::to_string(a.size()) + " " + (mv ? "values" : "gradients") + ", " +
+         std::to_string(x.size()) + " vectors and " + std::to_string(out.size()) + " outputs");
+  }
+  if (q < 1) fail("q = " + std::to_string(q) + " vectors; at least one is needed");
+  if (q >= INT32_MAX) fail("q = " + std::to_string(q) + " vectors is outside [1, 2^31 - 1)");
+  // element counts of the three sides; a side of size 0 is never touched and may be NULL
+  const int64_t nA = mv ? map.nnz : map.n * q, nX = map.n * q, nOut = mv ? map.n * q : map.nnz;
+  const char* aName = mv ? "values" : "gradient";
+  const char* outName = mv ? "output" : "gradient-of-values";
+  const auto overlap = [](const T* p, int64_t np, const T* r, int64_t nr) {
+    return p != nullptr && r != nullptr && np > 0 && nr > 0 && p < r + nr && r < p + np;
+  };
+  std::unordered_set<const T*> seen;
+  for (size_t b = 0; b < a.size(); b++) {
+    const std::string member = " pointer of batch member " + std::to_string(b);
+    if (a[b] == nullptr && nA > 0) fail(std::string("the ") + aName + member + " is NULL");
+    if (x[b] == nullptr && nX > 0) fail("the vector" + member + " is NULL");
+    if (out[b] == nullptr) {
+      if (nOut == 0) continue;
+      fail(std::string("the ") + outName + member + " is NULL");
+    }
+    if (!seen.insert(out[b]).second) fail(std::string("the ") + outName + member + " repeats an earlier member's");
+  }
+  for (size_t b = 0; b < a.size(); b++) {
+    const std::string member = " pointer of batch member " + std::to_string(b);
+    if (overlap(out[b], nOut, a[b], nA)) fail(std::string("the ") + outName + member + " aliases its " + aName);
+    if (overlap(out[b], nOut, x[b], nX)) fail(std::string("the ") + outName + member + " aliases its vector");
+    if (seen.count(a[b]) || seen.count(x[b])) {  // an output of one member that is an input of another
+      fail("an input pointer of batch member " + std::to_string(b) + " is also an output of the batch");
+    }
+  }
+  hipBackendSymProduct<T>(*symCtx, map, op, a.data(), x.data(), out.data(), q, (int64_t)a.size(), single);
+}
 // ---- blocks of A^-1 by reach solves (reach.h) --------------------------------
 ReachPlan Solver::reachPlan(const char* what, const std::vector<int64_t>& params, const std::vector<int64_t>& pairRow,
                             const std::vector<int64_t>& pairCol, const std::vector<int64_t>& outOffsets) const {
@@ -1108,6 +1155,8 @@ void Solver::inverseBlocks(const T* L, const std::vector<int64_t>& rowParams, co
   template void Solver::assemble<T>(const AssemblyMap&, BspCVec_##T, BspVec_##T) const;                        \
   template void Solver::assembleAdjoint<T>(const AssemblyMap&, const T*, T*) const;                            \
   template void Solver::assembleAdjoint<T>(const AssemblyMap&, BspCVec_##T, BspVec_##T) const;                 \
+  template void Solver::symProduct<T>(const SymProductMap&, int32_t, BspCVec_##T, BspCVec_##T, BspVec_##T,     \
+                                      int64_t, bool) const;                                                    \
   template void Solver::normalEq<T>(const NormalEqMap&, int32_t, BspCVec_##T, BspCVec_##T, BspVec_##T,         \
                                     int64_t, bool) const;                                                      \
   template void Solver::reachSolveL<T>(const T*, const std::vector<int64_t>&, T*) const;                       \

@@ -18,6 +18,7 @@ namespace BaSpaCho {
 
 struct AssemblyMap;
 struct NormalEqMap;
+struct SymProductMap;
 struct ReachPlan;
 
 class Solver {
@@ -236,6 +237,21 @@ class Solver {
   template <typename T>
   void normalEq(const NormalEqMap& map, int32_t op, const std::vector<const T*>& values,
                 const std::vector<const T*>& x, const std::vector<T*>& out, int64_t q, bool single) const;
+  // extension: products with the symmetric matrix of coordinate entries, without its layout (DESIGN.md
+  // section 21; sym_product.h).  `map` comes from createSymProductMap(*this, ...); op is a SymProductOp
+  // (hip_backend.h); member b of the batch uses a[b], x[b] and out[b], x and g [order(), q] row-major:
+  //   SymProductMv:    out = A x ([n, q], every element written) from a = values (nnz) and x
+  //   SymProductOuter: out[k] = sum_j g[r, j] x[c, j] (+ g[c, j] x[r, j] off the diagonal), (r, c) the
+  //                    position of entry k, 0 for a skipped entry, from a = g and x: the gradient of the
+  //                    values of sum(g * (A x)), the same for every duplicate
+  // single = true: one member handed to the kernels directly; member b is bitwise the single call either
+  // way.  Runs on the stream of setStream() without host synchronisation (the first call of a kind
+  // uploads its part of the map).  A map of another Solver, an empty batch, q < 1, a NULL pointer (a side
+  // of size 0 may be NULL), a repeated output pointer or an output that overlaps an input are refused
+  // before any device work.
+  template <typename T>
+  void symProduct(const SymProductMap& map, int32_t op, const std::vector<const T*>& a,
+                  const std::vector<const T*>& x, const std::vector<T*>& out, int64_t q, bool single) const;
   // extension: blocks of A^-1 anywhere, on or off the pattern of L, by reach solves (DESIGN.md section 20;
   // reach.h, hip_reach_kernels.h).  `L` holds a complete factor() and is only read; params are the
   // caller's param ids (repeats allowed).  Both run on the stream of setStream() without host

@@ -14,6 +14,11 @@
     pat = S.SymmetricPattern(rows, cols, n, keep=kept)     # kept scalars ordered last
     Sk, rk = S.marginalize(pat, values, b)         # marginal precision / information of the kept scalars
 
+    y = S.matvec(pat, values, x)                   # y = A x straight from the entries: the layout is never built
+    q = S.quad_form(pat, values, x)                # x^T A x
+    lp = S.log_prob(pat, values, x, mu)            # log N(x; mu, A^-1): the Gaussian whose precision is A
+    x = S.solve_refined(pat, values, b, iters=3)   # fp32 factor + fp64 refinement on the entries' A x
+
     jpat = S.JacobianPattern(jrows, jcols, m, n)   # once per Jacobian pattern: solver + normal-equations maps
     x = S.lstsq(jpat, jvalues, r, damping=(a, b))  # x = (J^T J + D)^-1 J^T r, D = a diag(J^T J) + b I
     st = S.check_positive_definite(pat, values)    # factor status: ok, or the caller's scalar of the first bad pivot
@@ -45,6 +50,12 @@ the queried params alone (assemble -> factor -> Solver.inv
 one matrix; they are differentiable in values, and their backward (columns of A^-1, then
 Solver.patternGrad) is bitwise reproducible.
 
+matvec, quad_form and log_prob multiply by A straight from the entries (DESIGN.md section 21:
+SymmetricPattern.product, built on first use): no layout, no fill, a fixed summation order, gradients for
+values and the vectors.  solve_refined factors the fp32 layout once and corrects the solution with fp64
+residuals b - A x from the fp64 entries; the fp64 layout is never allocated, and its backward needs neither
+patternGrad nor the assembly adjoint.
+
 marginalize eliminates every scalar outside `keep`: S = A22 - A21 A11^-1 A12 and
 r = b2 - A21 A11^-1 b1 with block 2 the kept scalars, rows and columns in the order of `keep`.  inv(S) is
 the `keep` block of inv(A): S and r are the precision and the information vector of the marginal.
@@ -59,7 +70,8 @@ from .autograd import _OnCurrentStream
 
 __all__ = ["SymmetricPattern", "JacobianPattern", "assemble", "solve", "logdet", "solve_logdet", "sample", "marginalize",
            "covariance", "marginal_variances", "cross_covariance", "joint_covariance",
-           "hessian", "jt_vec", "j_vec", "normal_equations", "lstsq", "check_positive_definite"]
+           "hessian", "jt_vec", "j_vec", "normal_equations", "lstsq", "check_positive_definite",
+           "matvec", "quad_form", "log_prob", "solve_refined"]
 
 
 def _host_i64(a):
@@ -182,9 +194,19 @@ class SymmetricPattern(_Pattern):
         self._init_solver(ss, settings, keep, param_of)
         self.assembly = self.solver.assembly(rows, cols, triangle)
         self.nnz = len(rows)
+        self.triangle = triangle
+        self._entries = (rows, cols)
+        self._product = None
         self._init_order()
         # layout offset of the diagonal element of every scalar, in the caller's order
         self._diag_user = self.solver.diagOffsets()[self._to_user]
+
+    @property
+    def product(self):
+        """the SymProduct of the entries, built on first use"""
+        if self._product is None:
+            self._product = self.solver.symProduct(self._entries[0], self._entries[1], self.triangle)
+        return self._product
 
     @staticmethod
     def from_torch(A, param_sizes=None, settings=None, triangle="lower"):
@@ -645,6 +667,158 @@ def lstsq(jpat, jvalues, r, damping=None):
     data, g = normal_equations(jpat, jvalues, r, damping)
     dim = jvalues.dim() - 1
     return jpat.fromInternal(_ag.solve(jpat.solver, data, jpat.toInternal(g, dim)), dim)
+
+
+# ---- products with A straight from the entries ------------------------------
+class _MatVec(torch.autograd.Function):
+    """y = A(values) x from the entries.  A is symmetric: the gradient of x is A g, the same kernel on the
+    incoming gradient; that of values[k] is g_r x_c + g_c x_r at the entry's (r, c) (g_r x_r on the
+    diagonal), summed over the vectors: SymProduct.outer."""
+
+    @staticmethod
+    def forward(ctx, pattern, values, x):
+        prod = pattern.product
+        v, xc = values.detach().contiguous(), x.detach().contiguous()
+        with _OnCurrentStream(prod.solver, v.device):
+            out = prod.mv(v, xc)
+        ctx.prod = prod
+        ctx.save_for_backward(v, xc)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None
+        prod, (v, x) = ctx.prod, ctx.saved_tensors
+        g = g.contiguous()
+        gv = gx = None
+        with _OnCurrentStream(prod.solver, g.device):
+            if ctx.needs_input_grad[1]:
+                gv = prod.outer(g, x, batched=v.dim() == 2)
+            if ctx.needs_input_grad[2]:
+                gx = prod.mv(v, g)
+        return None, gv, gx
+
+
+def _check_x(pattern, values, x, what, name="x"):
+    dim = _check_b(pattern, values, x, what)
+    if x.dtype != values.dtype:
+        raise TypeError("%s: %s has dtype %s, values have %s" % (what, name, x.dtype, values.dtype))
+    if values.dim() == 2 and x.shape[0] != values.shape[0]:
+        raise ValueError("%s: batch sizes differ: values hold %d matrices, %s holds %d"
+                         % (what, values.shape[0], name, x.shape[0]))
+    if x.dim() == dim + 2 and x.shape[-1] < 1:
+        raise ValueError("%s: %s has no vectors" % (what, name))
+    return dim
+
+
+def matvec(pattern, values, x):
+    """y = A(values) x in the caller's order, shaped like solve's b ([n] or [n, k], leading B when batched),
+    straight from the entries: the layout is never assembled.  Differentiable in values and x."""
+    _check_values(pattern, values, "matvec")
+    _check_x(pattern, values, x, "matvec")
+    return _MatVec.apply(pattern, values, x)
+
+
+def quad_form(pattern, values, x):
+    """sum_i x_i (A(values) x)_i: a 0-dim tensor for x [n], [k] for x [n, k], with a leading B when
+    batched.  Differentiable in values and x."""
+    _check_values(pattern, values, "quad_form")
+    dim = _check_x(pattern, values, x, "quad_form")
+    return (x * _MatVec.apply(pattern, values, x)).sum(dim)
+
+
+def log_prob(pattern, values, x, mu=None):
+    """log N(x; mu, A(values)^-1) = 0.5 logdet(pattern, values) - 0.5 quad_form(pattern, values, x - mu)
+    - 0.5 n log(2 pi): the log-density of the Gaussian whose precision is A, mean mu (0 when None).  x (and mu)
+    are shaped like solve's b; the result has the shape of quad_form.  Differentiable in values, x and mu."""
+    _check_values(pattern, values, "log_prob")
+    dim = _check_x(pattern, values, x, "log_prob")
+    if mu is not None:
+        if not isinstance(mu, torch.Tensor) or mu.shape != x.shape or mu.dtype != x.dtype:
+            raise ValueError("log_prob: mu must be a tensor of x's shape %s and dtype %s" % (tuple(x.shape), x.dtype))
+    d = x if mu is None else x - mu
+    ld = logdet(pattern, values)
+    qf = quad_form(pattern, values, d)
+    if qf.dim() > ld.dim():
+        ld = ld.unsqueeze(-1)
+    return 0.5 * ld - 0.5 * qf - 0.5 * pattern.n * float(np.log(2.0 * np.pi))
+
+
+def _refine(pattern, L32, v, b, iters):
+    """x = the fp32 solve of b through the factor L32, then `iters` corrections x += solve32(b - A x) with
+    the residual in fp64 from the fp64 entries v; b and x in the caller's order, fp64"""
+    sol, prod = pattern.solver, pattern.product
+    batched = v.dim() == 2
+    dim = 1 if batched else 0
+
+    def solve32(r):
+        rt = _ag._to_cols(pattern.toInternal(r.float(), dim), batched)
+        _ag._solve_cols(sol, L32, rt)
+        return pattern.fromInternal(_ag._from_cols(rt, r.shape), dim).double()
+
+    x = solve32(b)
+    for _ in range(iters):
+        x = x + solve32(b - prod.mv(v, x.contiguous()))
+    return x.contiguous()
+
+
+class _SolveRefined(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pattern, values, b, iters):
+        sol = pattern.solver
+        v = values.detach().contiguous()
+        with _OnCurrentStream(sol, v.device):
+            L32 = pattern.assembly.assemble(v.float())
+            sol.factor(_ag._members(L32) if L32.dim() == 2 else L32)
+            x = _refine(pattern, L32, v, b.detach(), iters)
+        ctx.pattern, ctx.iters = pattern, iters
+        ctx.save_for_backward(L32, v, x)
+        ctx.set_materialize_grads(False)
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if g is None or not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+            return None, None, None, None
+        pattern, (L32, v, x) = ctx.pattern, ctx.saved_tensors
+        gv = None
+        with _OnCurrentStream(pattern.solver, g.device):
+            gb = _refine(pattern, L32, v, g.contiguous(), ctx.iters)  # A is symmetric: the same loop, the same factor
+            if ctx.needs_input_grad[1]:
+                gv = pattern.product.outer(gb, x, batched=v.dim() == 2).neg_()
+        return None, gv, gb if ctx.needs_input_grad[2] else None, None
+
+
+def solve_refined(pattern, values, b, iters=3):
+    """x = A(values)^-1 b in the caller's order from an fp32 factor and fp64 iterative refinement: values and
+    b are float64 (any other dtype is a TypeError).  values.float() is assembled into an fp32 layout and
+    factored once; x starts as the fp32 solve of b and is corrected `iters` times by x += solve32(b - A x),
+    the residual in fp64 straight from the fp64 entries (matvec's kernel).  The iteration count is fixed and
+    nothing is read back to the host; the fp64 layout is never allocated, so the factor takes half the
+    memory of solve's.  Differentiable in values and b: b's gradient is the same loop on the incoming
+    gradient with the saved fp32 factor, and the gradient of values is -outer(gb, x) read at the entries.
+
+    A factor that breaks down in fp32 (a matrix that is not positive definite once rounded to fp32, or too
+    ill-conditioned for it) yields non-finite values, as solve does; nothing inside detects it.
+    check_positive_definite(pattern, values.float()) is the caller's tool for that."""
+    what = "solve_refined"
+    _check_values(pattern, values, what)
+    dim = _check_b(pattern, values, b, what)
+    if values.dtype != torch.float64 or b.dtype != torch.float64:
+        raise TypeError("%s: values and b must be float64, got %s and %s" % (what, values.dtype, b.dtype))
+    if values.dim() == 2 and b.shape[0] != values.shape[0]:
+        raise ValueError("%s: batch sizes differ: values hold %d matrices, b holds %d"
+                         % (what, values.shape[0], b.shape[0]))
+    if b.dim() == dim + 2 and b.shape[-1] < 1:
+        raise ValueError("%s: b has no right-hand sides" % what)
+    if not isinstance(iters, int) or isinstance(iters, bool) or iters < 0:
+        raise ValueError("%s: iters must be an integer >= 0, got %r" % (what, iters))
+    _ag._check_device(pattern.solver, what, values, b)
+    return _SolveRefined.apply(pattern, values, b, iters)
 
 
 # ---- status of the factor (DESIGN.md section 18) ---------------------------------------------------

@@ -575,6 +575,62 @@ int bsp_normal_eq_j_vec_f32(bsp_solver* s, const bsp_normal_eq* e, const float* 
                             int64_t q, float* dev_out);
 int bsp_normal_eq_j_vec_batched_f32(bsp_solver* s, const bsp_normal_eq* e, const float* const* dev_values,
                                     const float* const* dev_v, int64_t q, float* const* dev_out, int32_t batch);
+/* Extension (no counterpart in the reference): products with the symmetric matrix A given as coordinate
+   entries (rows[k], cols[k], values[k]) in the caller's scalar order, taken straight from the entries:
+   the solver's layout is never built.
+   - `triangle` and the index rules are those of bsp_assembly_create: an index outside [0, order) is
+     refused, BSP_TRIANGLE_LOWER refuses row < col and BSP_TRIANGLE_FULL skips it, so A is the matrix the
+     assembly builds: A_ij = A_ji = sum of the values of the kept entries at (i, j), i >= j.  Whether the
+     solver stores the element does not matter here.
+   - The term list of scalar i holds, in ascending k, (k, cols[k]) for every kept entry with rows[k] == i
+     and (k, rows[k]) for every kept entry with cols[k] == i and rows[k] != i; duplicates stay separate
+     terms.  0 <= nnz < 2^31 and the term count must be below 2^31.
+   bsp_sym_product_create builds the map once on the host (no device work) and fails, with
+   bsp_last_error() naming the first offending entry and its (row, col), or stating the term count when it
+   is too large.  The map has two parts, each uploaded by the first call that needs it (row lists: mv;
+   entry lists: outer) and kept until bsp_sym_product_destroy.  A map belongs to the solver it was built
+   on and must be destroyed before that solver. */
+typedef struct bsp_sym_product bsp_sym_product;
+int bsp_sym_product_create(bsp_solver* s, int64_t nnz, const int64_t* rows, const int64_t* cols, int32_t triangle,
+                           bsp_sym_product** out);
+void bsp_sym_product_destroy(bsp_sym_product* p);
+/* figures of the map: out[0] nnz, [1] kept entries, [2] terms, [3] most terms in one row, [4] rows summed by
+   a whole wave (more than 64 terms), [5] device bytes of both parts once uploaded */
+int bsp_sym_product_info(const bsp_sym_product* p, int64_t out[6]);
+/* host copy of the term lists: the terms of row i are (entry[t], index[t]), t in [row_start[i],
+   row_start[i + 1]) (order + 1 starts; out[2] values in entry and in index) */
+int bsp_sym_product_row_table(const bsp_sym_product* p, int32_t* row_start, int32_t* entry, int32_t* index);
+/* bsp_sym_product_mv_*: dev_out = A dev_x, both [order, q] row-major, q >= 1 vectors.  dev_out[i, j] = the
+   terms (k, idx) of row i folded in list order from +0: s = s + dev_values[k] * dev_x[idx, j], the product
+   rounded in the value type before it is added.  EVERY element of dev_out is written exactly once (+0 for
+   a row without terms); dev_out is never read.
+   bsp_sym_product_outer_*: dev_grad_values[k] = sum over j ascending of t_j, t_j = dev_g[r, j] * dev_x[c, j]
+   (+ dev_g[c, j] * dev_x[r, j] when r != c), (r, c) = (rows[k], cols[k]); 0 for a skipped entry.  This is
+   the gradient of the entry values of sum(dev_g * (A dev_x)), the same for every duplicate (the convention
+   of bsp_assemble_adjoint_*).  dev_g and dev_x are [order, q].
+   All run on the stream of bsp_set_stream without atomics, memsets or host synchronisation; results are
+   bitwise reproducible and batch member b (HOST arrays of `batch` device pointers) is bitwise the single
+   call.  Operands need the alignment of their element type only.  An empty batch, a NULL array or member (a
+   side of size 0 may be NULL), q < 1, a repeated output pointer, an output that aliases an input, or a map
+   built on another solver: non-zero return before any device work. */
+int bsp_sym_product_mv_f64(bsp_solver* s, const bsp_sym_product* p, const double* dev_values, const double* dev_x,
+                           int64_t q, double* dev_out);
+int bsp_sym_product_mv_batched_f64(bsp_solver* s, const bsp_sym_product* p, const double* const* dev_values,
+                                   const double* const* dev_x, int64_t q, double* const* dev_out, int32_t batch);
+int bsp_sym_product_outer_f64(bsp_solver* s, const bsp_sym_product* p, const double* dev_g, const double* dev_x,
+                              int64_t q, double* dev_grad_values);
+int bsp_sym_product_outer_batched_f64(bsp_solver* s, const bsp_sym_product* p, const double* const* dev_g,
+                                      const double* const* dev_x, int64_t q, double* const* dev_grad_values,
+                                      int32_t batch);
+int bsp_sym_product_mv_f32(bsp_solver* s, const bsp_sym_product* p, const float* dev_values, const float* dev_x,
+                           int64_t q, float* dev_out);
+int bsp_sym_product_mv_batched_f32(bsp_solver* s, const bsp_sym_product* p, const float* const* dev_values,
+                                   const float* const* dev_x, int64_t q, float* const* dev_out, int32_t batch);
+int bsp_sym_product_outer_f32(bsp_solver* s, const bsp_sym_product* p, const float* dev_g, const float* dev_x,
+                              int64_t q, float* dev_grad_values);
+int bsp_sym_product_outer_batched_f32(bsp_solver* s, const bsp_sym_product* p, const float* const* dev_g,
+                                      const float* const* dev_x, int64_t q, float* const* dev_grad_values,
+                                      int32_t batch);
 /* out[i_user] = i_internal (order values): the caller's scalar i in the solver's internal vector order
    (param p at spanStart[paramToSpan[p]], its scalars in order) */
 int bsp_scalar_permutation(const bsp_solver* s, int64_t* out);
