@@ -1267,7 +1267,59 @@ def _host_indices(a, name):
     return _i64(a)
 
 
-class Assembly:
+class _EntryMap:
+    """what Assembly, NormalEquations and SymProduct share: the handle of the host map that
+    bsp_<_C>_create builds from (rows, cols), its figures, and the tail of every device call"""
+    _C = None    # the map's C entries are bsp_<_C>_create, bsp_<_C>_destroy and bsp_<_C>_info
+    _KEYS = ()   # the figures of bsp_<_C>_info, in its order
+
+    def _create(self, op, solver, rows, cols, before=(), after=()):
+        """builds the map; `before` / `after`: the C arguments before nnz and behind cols"""
+        self._lib = solver._lib
+        self._h = None
+        r, c = _host_indices(rows, "rows"), _host_indices(cols, "cols")
+        if len(r) != len(c):
+            raise ValueError("%s: %d rows for %d cols" % (op, len(r), len(c)))
+        h = ctypes.c_void_p()
+        _check(getattr(self._lib, "bsp_%s_create" % self._C)(
+            solver._h, *before, ctypes.c_int64(len(r)), r.ctypes.data_as(_I64P), c.ctypes.data_as(_I64P), *after,
+            ctypes.byref(h)))
+        self._h = h
+        self.solver = solver
+        self.nnz = len(r)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            getattr(self._lib, "bsp_%s_destroy" % self._C)(h)
+
+    def info(self):
+        """figures of the map (bsp_<_C>_info)"""
+        out = (ctypes.c_int64 * len(self._KEYS))()
+        _check(getattr(self._lib, "bsp_%s_info" % self._C)(self._h, out))
+        return dict(zip(self._KEYS, [int(x) for x in out]))
+
+    def _launch(self, name, fn, sfx, ins, shape, out, batched, q=None):
+        """the tail of an operation on the device tensors `ins`: `out` allocated or checked against `shape`,
+        every tensor in device memory and contiguous, then the single or the batched entry `fn`"""
+        import torch
+        ref = ins[0]
+        shape = tuple(shape)
+        if out is None:
+            out = torch.empty(shape, dtype=ref.dtype, device=ref.device)
+        elif tuple(out.shape) != shape or out.dtype != ref.dtype or out.device != ref.device:
+            raise ValueError("%s: out must be %s %s on %s, got %s %s on %s" % (
+                name, shape, ref.dtype, ref.device, tuple(out.shape), out.dtype, out.device))
+        ts = list(ins) + [out]
+        for t in ts:
+            _ptr_of(t)  # device memory, contiguous
+        ptrs = [_ptr_arg(t.unbind(0) if batched else [t], batched) for t in ts]
+        qa = [] if q is None else [ctypes.c_int64(q)]
+        _call(self._lib, fn, batched, sfx, self.solver._h, self._h, *ptrs[:-1], *qa, ptrs[-1], *_count(out, batched))
+        return out
+
+
+class Assembly(_EntryMap):
     """extension: the host map from coordinate entries (rows[k], cols[k]) in the
     caller's scalar order to a Solver's numeric layout, and the device kernels that use it.  Built by
     Solver.assembly(); keeps its solver alive.  A_ij = A_ji = sum of the values of the entries at
@@ -1275,40 +1327,20 @@ class Assembly:
     assemble / adjoint call uploads the map to the device; both run on the solver's stream without
     synchronising."""
 
+    _C = "assembly"
+    _KEYS = ("nnz", "kept", "elements", "max_run", "long_runs", "tiles", "device_bytes")
+
     def __init__(self, solver, rows, cols, triangle="lower"):
         if triangle not in _TRIANGLES:
             raise ValueError("assembly: triangle must be 'lower' or 'full', got %r" % (triangle,))
-        self._lib = solver._lib
-        self._h = None
-        r, c = _host_indices(rows, "rows"), _host_indices(cols, "cols")
-        if len(r) != len(c):
-            raise ValueError("assembly: %d rows for %d cols" % (len(r), len(c)))
-        h = ctypes.c_void_p()
-        _check(self._lib.bsp_assembly_create(solver._h, ctypes.c_int64(len(r)), r.ctypes.data_as(_I64P),
-                                             c.ctypes.data_as(_I64P), ctypes.c_int32(_TRIANGLES[triangle]),
-                                             ctypes.byref(h)))
-        self._h = h
-        self.solver = solver
-        self.nnz = len(r)
+        self._create("assembly", solver, rows, cols, after=(ctypes.c_int32(_TRIANGLES[triangle]),))
         self.triangle = triangle
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.bsp_assembly_destroy(h)
 
     def entryOffsets(self):
         """int64 array [nnz]: the layout offset of every entry, -1 for a skipped one"""
         out = np.empty(self.nnz, dtype=np.int64)
         _check(self._lib.bsp_assembly_entry_offsets(self._h, out.ctypes.data_as(_I64P)))
         return out
-
-    def info(self):
-        """figures of the map (bsp_assembly_info)"""
-        out = (ctypes.c_int64 * 7)()
-        _check(self._lib.bsp_assembly_info(self._h, out))
-        keys = ["nnz", "kept", "elements", "max_run", "long_runs", "tiles", "device_bytes"]
-        return dict(zip(keys, [int(x) for x in out]))
 
     def _run(self, name, x, n_in, n_out, out, adjoint):
         import torch
@@ -1318,19 +1350,8 @@ class Assembly:
             raise ValueError("%s: expected [%d] or [B, %d], got shape %s" % (name, n_in, n_in, tuple(x.shape)))
         if x.dim() == 2 and x.shape[0] == 0:
             raise ValueError("%s: empty batch" % name)
-        sfx = _suffix(x)
-        shape = x.shape[:-1] + (n_out,)
-        if out is None:
-            out = torch.empty(shape, dtype=x.dtype, device=x.device)
-        elif out.shape != shape or out.dtype != x.dtype or out.device != x.device:
-            raise ValueError("%s: out must be %s %s on %s, got %s %s on %s" % (
-                name, tuple(shape), x.dtype, x.device, tuple(out.shape), out.dtype, out.device))
-        _ptr_of(x), _ptr_of(out)  # device memory, contiguous
-        batched = x.dim() == 2
-        xs, outs = (x.unbind(0), out.unbind(0)) if batched else ([x], [out])
-        _call(self._lib, "bsp_assemble_adjoint_" if adjoint else "bsp_assemble_", batched, sfx, self.solver._h, self._h,
-              _ptr_arg(xs, batched), _ptr_arg(outs, batched), *_count(xs, batched))
-        return out
+        return self._launch(name, "bsp_assemble_adjoint_" if adjoint else "bsp_assemble_", _suffix(x), [x],
+                            x.shape[:-1] + (n_out,), out, x.dim() == 2)
 
     def assemble(self, values, out=None):
         """values [nnz] or [B, nnz] (device, float64 / float32) -> the layout [dataSize] / [B, dataSize]:
@@ -1346,7 +1367,7 @@ class Assembly:
 _I32P = ctypes.POINTER(ctypes.c_int32)
 
 
-class NormalEquations:
+class NormalEquations(_EntryMap):
     """extension: the host maps from the entries (rows[k], cols[k]) of an m x n
     Jacobian J (n = the solver's order(), caller's scalar order, no position repeated) to the solver's
     layout, and the device kernels that use them.  Built by Solver.normalEquations(); keeps its solver
@@ -1355,33 +1376,14 @@ class NormalEquations:
     (bitwise the numpy restatement); each part of the map is uploaded by the first call that needs it;
     everything runs on the solver's stream without synchronising."""
 
+    _C = "normal_eq"
+    _KEYS = ("nnz", "pairs", "destinations", "max_run", "long_runs", "tiles", "forward_bytes", "adjoint_bytes",
+             "vector_bytes", "adjoint_terms")
+
     def __init__(self, solver, rows, cols, m):
-        self._lib = solver._lib
-        self._h = None
-        r, c = _host_indices(rows, "rows"), _host_indices(cols, "cols")
-        if len(r) != len(c):
-            raise ValueError("normalEquations: %d rows for %d cols" % (len(r), len(c)))
-        h = ctypes.c_void_p()
-        _check(self._lib.bsp_normal_eq_create(solver._h, ctypes.c_int64(int(m)), ctypes.c_int64(len(r)),
-                                              r.ctypes.data_as(_I64P), c.ctypes.data_as(_I64P), ctypes.byref(h)))
-        self._h = h
-        self.solver = solver
-        self.nnz = len(r)
+        self._create("normalEquations", solver, rows, cols, before=(ctypes.c_int64(int(m)),))
         self.m = int(m)
         self.n = solver.order()
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.bsp_normal_eq_destroy(h)
-
-    def info(self):
-        """figures of the maps (bsp_normal_eq_info)"""
-        out = (ctypes.c_int64 * 10)()
-        _check(self._lib.bsp_normal_eq_info(self._h, out))
-        keys = ["nnz", "pairs", "destinations", "max_run", "long_runs", "tiles", "forward_bytes", "adjoint_bytes",
-                "vector_bytes", "adjoint_terms"]
-        return dict(zip(keys, [int(x) for x in out]))
 
     def pairTable(self):
         """(ka, kb, offset) of every pair in run order: int32, int32, int64 arrays of info()["pairs"]"""
@@ -1425,19 +1427,7 @@ class NormalEquations:
                 shape = lead + (out_rows,) + ((q,) if x.dim() == len(lead) + 2 else ())
             else:
                 shape = lead + (out_rows,)
-        if out is None:
-            out = torch.empty(shape, dtype=values.dtype, device=values.device)
-        elif tuple(out.shape) != shape or out.dtype != values.dtype or out.device != values.device:
-            raise ValueError("%s: out must be %s %s on %s, got %s %s on %s" % (
-                name, shape, values.dtype, values.device, tuple(out.shape), out.dtype, out.device))
-        ts = [t for t in (values, x, out) if t is not None]
-        for t in ts:
-            _ptr_of(t)  # device memory, contiguous
-        ptrs = [_ptr_arg(t.unbind(0) if batched else [t], batched) for t in ts]
-        qa = [] if q is None else [ctypes.c_int64(q)]
-        _call(self._lib, fn, batched, sfx, self.solver._h, self._h, *ptrs[:-1], *qa, ptrs[-1],
-              *_count(values, batched))
-        return out
+        return self._launch(name, fn, sfx, [values] if x is None else [values, x], shape, out, batched, q)
 
     def hessian(self, values, out=None):
         """values [nnz] or [B, nnz] (device, float64 / float32) -> H = J^T J in the layout, [dataSize] /
@@ -1460,7 +1450,7 @@ class NormalEquations:
         return self._run("jVec", "bsp_normal_eq_j_vec_", values, v, self.n, self.m, out)
 
 
-class SymProduct:
+class SymProduct(_EntryMap):
     """extension: products with the symmetric matrix A of the coordinate entries
     (rows[k], cols[k], values[k]) in the caller's scalar order, taken straight from the entries: the solver's
     layout is never built.  Built by Solver.symProduct(); keeps its solver alive.  A is the matrix
@@ -1469,35 +1459,15 @@ class SymProduct:
     (bitwise the numpy restatement); each part of the map is uploaded by the first call that needs it;
     everything runs on the solver's stream without synchronising."""
 
+    _C = "sym_product"
+    _KEYS = ("nnz", "kept", "terms", "max_row", "long_rows", "device_bytes")
+
     def __init__(self, solver, rows, cols, triangle="lower"):
         if triangle not in _TRIANGLES:
             raise ValueError("symProduct: triangle must be 'lower' or 'full', got %r" % (triangle,))
-        self._lib = solver._lib
-        self._h = None
-        r, c = _host_indices(rows, "rows"), _host_indices(cols, "cols")
-        if len(r) != len(c):
-            raise ValueError("symProduct: %d rows for %d cols" % (len(r), len(c)))
-        h = ctypes.c_void_p()
-        _check(self._lib.bsp_sym_product_create(solver._h, ctypes.c_int64(len(r)), r.ctypes.data_as(_I64P),
-                                                c.ctypes.data_as(_I64P), ctypes.c_int32(_TRIANGLES[triangle]),
-                                                ctypes.byref(h)))
-        self._h = h
-        self.solver = solver
-        self.nnz = len(r)
+        self._create("symProduct", solver, rows, cols, after=(ctypes.c_int32(_TRIANGLES[triangle]),))
         self.n = solver.order()
         self.triangle = triangle
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.bsp_sym_product_destroy(h)
-
-    def info(self):
-        """figures of the map (bsp_sym_product_info)"""
-        out = (ctypes.c_int64 * 6)()
-        _check(self._lib.bsp_sym_product_info(self._h, out))
-        keys = ["nnz", "kept", "terms", "max_row", "long_rows", "device_bytes"]
-        return dict(zip(keys, [int(x) for x in out]))
 
     def rowTable(self):
         """(row_start, entry, index): the terms of row i are (entry[t], index[t]), t in [row_start[i],
@@ -1536,18 +1506,7 @@ class SymProduct:
         if q < 1:
             raise ValueError("%s: x has no vectors" % name)
         shape = tuple(x.shape) if mv else tuple(x.shape[:lo]) + (self.nnz,)
-        if out is None:
-            out = torch.empty(shape, dtype=a.dtype, device=a.device)
-        elif tuple(out.shape) != shape or out.dtype != a.dtype or out.device != a.device:
-            raise ValueError("%s: out must be %s %s on %s, got %s %s on %s" % (
-                name, shape, a.dtype, a.device, tuple(out.shape), out.dtype, out.device))
-        ts = [a, x, out]
-        for t in ts:
-            _ptr_of(t)  # device memory, contiguous
-        ptrs = [_ptr_arg(t.unbind(0) if batched else [t], batched) for t in ts]
-        _call(self._lib, fn, batched, sfx, self.solver._h, self._h, ptrs[0], ptrs[1], ctypes.c_int64(q), ptrs[2],
-              *_count(out, batched))
-        return out
+        return self._launch(name, fn, sfx, [a, x], shape, out, batched, q)
 
     def mv(self, values, x, out=None):
         """values [nnz] or [B, nnz] (device, float64 / float32); x [n] or [n, q] in the caller's order (leading

@@ -5,26 +5,9 @@
 #include <stdexcept>
 #include <string>
 
-#include "entry_map.h"
-#include "hip_backend.h"
 #include "solver.h"
 
 namespace BaSpaCho {
-
-AssemblyMap::~AssemblyMap() {
-  if (dev) hipBackendFreeAssembly(dev);
-}
-
-int64_t AssemblyMap::deviceBytes() const {
-  return (int64_t)(entryOff.size() * sizeof(int64_t) + runStart.size() * sizeof(int32_t) +
-                   runEntry.size() * sizeof(int32_t) + tileFirst.size() * sizeof(int32_t) +
-                   destLocal.size() * sizeof(uint16_t) + longDest.size() * sizeof(int32_t) +
-                   tileLongFirst.size() * sizeof(int32_t));
-}
-
-static std::string entryName(int64_t k, int64_t i, int64_t j) {
-  return "entry " + std::to_string(k) + " at (" + std::to_string(i) + ", " + std::to_string(j) + ")";
-}
 
 std::unique_ptr<AssemblyMap> createAssemblyMap(const Solver& solver, int64_t nnz, const int64_t* rows,
                                                const int64_t* cols, int32_t triangle) {
@@ -32,12 +15,8 @@ std::unique_ptr<AssemblyMap> createAssemblyMap(const Solver& solver, int64_t nnz
     throw std::runtime_error("assembly: unknown triangle mode " + std::to_string(triangle) +
                              " (0: lower, 1: full)");
   }
-  if (nnz < 0 || nnz >= (int64_t(1) << 31)) {
-    throw std::runtime_error("assembly: nnz = " + std::to_string(nnz) + " is outside [0, 2^31)");
-  }
-  if (nnz > 0 && (rows == nullptr || cols == nullptr)) {
-    throw std::runtime_error("assembly: the row or column array is NULL");
-  }
+  checkBelow2p31("assembly", "nnz", nnz);
+  checkEntryArrays("assembly", nnz, rows, cols);
   std::unique_ptr<AssemblyMap> m(new AssemblyMap);
   m->solver = &solver;
   m->triangle = triangle;
@@ -77,8 +56,7 @@ std::unique_ptr<AssemblyMap> createAssemblyMap(const Solver& solver, int64_t nnz
   const int64_t* off = m->entryOff.data();
   sortByOffset(kept, m->runEntry, m->numTiles, [off](int32_t k) { return off[k]; });
   const int32_t* runEntry = m->runEntry.data();
-  buildTileRuns((int64_t)m->runEntry.size(), m->numTiles, [off, runEntry](int64_t x) { return off[runEntry[x]]; },
-                TileRuns{m->dest, m->runStart, m->tileFirst, m->destLocal, m->longDest, m->tileLongFirst, m->maxRun});
+  m->tiles.build((int64_t)m->runEntry.size(), m->numTiles, [off, runEntry](int64_t x) { return off[runEntry[x]]; });
   return m;
 }
 

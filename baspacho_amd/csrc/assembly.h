@@ -1,7 +1,7 @@
 // Assembly of a symmetric matrix given as coordinate entries (row, col, value) in the caller's scalar
 // order into a Solver's numeric layout.  The map from entries to layout offsets
 // is built once on the host (this file, no device work); the kernels that use it are in
-// hip_assembly_kernels.h, launched by hip_backend.hip.
+// hip_ordered_sum.h, launched by hip_extensions.hip.
 //
 // CONVENTIONS.  Scalar index i of the caller belongs to param p at local position r, from the prefix
 // sums of the param sizes in param order.  The symmetric matrix is defined by its lower triangle:
@@ -17,49 +17,31 @@
 #include <memory>
 #include <vector>
 
+#include "entry_map.h"
+
 namespace BaSpaCho {
 
-class Solver;
-struct HipAssemblyDev;  // the map on the device (hip_backend.hip), uploaded on first use
-
 enum AssemblyTriangle : int32_t { AssemblyLower = 0, AssemblyFull = 1 };
-
-// layout elements per workgroup of the assemble kernel; runs longer than kAssemblyLongRun entries are
-// summed by a whole wave instead of one lane
-constexpr int64_t kAssemblyTile = 2048;
-constexpr int32_t kAssemblyLongRun = 64;
 
 struct AssemblyMap {
   const Solver* solver = nullptr;  // the solver whose layout the map targets
   int32_t triangle = AssemblyLower;
   int64_t nnz = 0, dataSize = 0, numTiles = 0;
-  int64_t maxRun = 0;  // most entries summed into one element
 
   std::vector<int64_t> entryOff;  // per entry: layout offset, -1 when skipped
 
-  // destination-sorted form (forward pass): the unique destinations in ascending offset; the entries
-  // of destination u are runEntry[runStart[u] .. runStart[u + 1]), in ascending entry index
-  std::vector<int64_t> dest;
-  std::vector<int32_t> runStart;
+  // destination-sorted form (forward pass): the entries of destination u are runEntry[tiles.runStart[u]
+  // .. tiles.runStart[u + 1]), in ascending entry index
   std::vector<int32_t> runEntry;
-  // tile index: destinations [tileFirst[t], tileFirst[t + 1]) lie in layout tile t (kAssemblyTile
-  // elements); destLocal[u] = dest[u] - tile base.  longDest lists the destinations whose runs are
-  // longer than kAssemblyLongRun, ascending; those of tile t are [tileLongFirst[t], tileLongFirst[t + 1])
-  std::vector<int32_t> tileFirst;
-  std::vector<uint16_t> destLocal;
-  std::vector<int32_t> longDest;
-  std::vector<int32_t> tileLongFirst;
+  TileRuns tiles;
 
-  mutable HipAssemblyDev* dev = nullptr;
-
-  AssemblyMap() = default;
-  AssemblyMap(const AssemblyMap&) = delete;
-  AssemblyMap& operator=(const AssemblyMap&) = delete;
-  ~AssemblyMap();
+  mutable HipEntryMapDevPtr dev;
 
   int64_t numKept() const { return (int64_t)runEntry.size(); }
   // bytes the map takes on the device once uploaded
-  int64_t deviceBytes() const;
+  int64_t deviceBytes() const {
+    return (int64_t)(entryOff.size() * sizeof(int64_t) + runEntry.size() * sizeof(int32_t)) + tiles.deviceBytes();
+  }
 };
 
 // Builds the map of `nnz` entries (rows[k], cols[k]) for `solver`.  Throws, naming the first offending

@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "bal_fill_plan.h"
+#include "hip_ordered_sum.h"
 
 namespace BaSpaCho {
 namespace balfill {
@@ -28,18 +29,12 @@ struct Tables {
   double* part;  // scratch: partialWords() doubles per chunk
 };
 
-// fl(fl(a0 * b0) + fl(a1 * b1)) and fl(s + v): hipcc contracts a * b + c into an fma by default, which
-// would round once where the documented order rounds three times
+// fl(fl(a0 * b0) + fl(a1 * b1)) and fl(s + v), every operation rounded on its own (rmul / radd: an fma
+// would round once where the documented order rounds three times)
 __device__ __forceinline__ double term(double a0, double b0, double a1, double b1) {
-#pragma clang fp contract(off)
-  const double p0 = a0 * b0;
-  const double p1 = a1 * b1;
-  return p0 + p1;
+  return hipk::radd(hipk::rmul(a0, b0), hipk::rmul(a1, b1));
 }
-__device__ __forceinline__ double add(double s, double v) {
-#pragma clang fp contract(off)
-  return s + v;
-}
+__device__ __forceinline__ double add(double s, double v) { return hipk::radd(s, v); }
 
 constexpr int kThreads = 256;
 

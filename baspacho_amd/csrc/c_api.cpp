@@ -711,8 +711,8 @@ int bsp_assembly_info(const bsp_assembly* a, int64_t out[7]) {
   BSP_TRY
   if (a == nullptr || out == nullptr) throw std::runtime_error("bsp_assembly_info: NULL argument");
   const AssemblyMap& m = *a->map;
-  const int64_t v[7] = {m.nnz, m.numKept(), (int64_t)m.dest.size(), m.maxRun, (int64_t)m.longDest.size(),
-                        m.numTiles, m.deviceBytes()};
+  const int64_t v[7] = {m.nnz, m.numKept(), (int64_t)m.tiles.dest.size(), m.tiles.maxRun,
+                        (int64_t)m.tiles.longDest.size(), m.numTiles, m.deviceBytes()};
   std::copy(v, v + 7, out);
   BSP_CATCH
 }
@@ -762,9 +762,9 @@ int bsp_normal_eq_info(const bsp_normal_eq* e, int64_t out[10]) {
   BSP_TRY
   if (e == nullptr || out == nullptr) throw std::runtime_error("bsp_normal_eq_info: NULL argument");
   const NormalEqMap& m = *e->map;
-  const int64_t v[10] = {m.nnz, m.numPairs, (int64_t)m.dest.size(), m.maxRun, (int64_t)m.longDest.size(),
-                         m.numTiles, m.forwardDeviceBytes(), m.adjointDeviceBytes(), m.vectorDeviceBytes(),
-                         m.numAdjointTerms()};
+  const int64_t v[10] = {m.nnz, m.numPairs, (int64_t)m.tiles.dest.size(), m.tiles.maxRun,
+                         (int64_t)m.tiles.longDest.size(), m.numTiles, m.forwardDeviceBytes(), m.adjointDeviceBytes(),
+                         m.vectorDeviceBytes(), m.numAdjointTerms()};
   std::copy(v, v + 10, out);
   BSP_CATCH
 }
@@ -777,8 +777,8 @@ int bsp_normal_eq_pair_table(const bsp_normal_eq* e, int32_t* ka, int32_t* kb, i
   }
   std::copy(m.pairA.begin(), m.pairA.end(), ka);
   std::copy(m.pairB.begin(), m.pairB.end(), kb);
-  for (size_t u = 0; u < m.dest.size(); u++) {
-    std::fill(offset + m.runStart[u], offset + m.runStart[u + 1], m.dest[u]);
+  for (size_t u = 0; u < m.tiles.dest.size(); u++) {
+    std::fill(offset + m.tiles.runStart[u], offset + m.tiles.runStart[u + 1], m.tiles.dest[u]);
   }
   BSP_CATCH
 }
@@ -837,7 +837,7 @@ int bsp_sym_product_info(const bsp_sym_product* p, int64_t out[6]) {
   BSP_TRY
   if (p == nullptr || out == nullptr) throw std::runtime_error("bsp_sym_product_info: NULL argument");
   const SymProductMap& m = *p->map;
-  const int64_t v[6] = {m.nnz, m.kept, m.numTerms(), m.maxRow, (int64_t)m.longRows.size(),
+  const int64_t v[6] = {m.nnz, m.kept, m.numTerms(), m.rows.maxRun, (int64_t)m.rows.longRuns.size(),
                         m.rowDeviceBytes() + m.entryDeviceBytes()};
   std::copy(v, v + 6, out);
   BSP_CATCH
@@ -849,9 +849,9 @@ int bsp_sym_product_row_table(const bsp_sym_product* p, int32_t* row_start, int3
   if (row_start == nullptr || (m.numTerms() > 0 && (entry == nullptr || index == nullptr))) {
     throw std::runtime_error("bsp_sym_product_row_table: an output array is NULL");
   }
-  std::copy(m.rowStart.begin(), m.rowStart.end(), row_start);
-  std::copy(m.termEntry.begin(), m.termEntry.end(), entry);
-  std::copy(m.termIdx.begin(), m.termIdx.end(), index);
+  std::copy(m.rows.start.begin(), m.rows.start.end(), row_start);
+  std::copy(m.rows.entry.begin(), m.rows.entry.end(), entry);
+  std::copy(m.rows.idx.begin(), m.rows.idx.end(), index);
   BSP_CATCH
 }
 template <typename T>

@@ -1,18 +1,38 @@
-// Host pieces shared by the maps that send caller-order scalar pairs to a Solver's numeric layout:
-// assembly.cpp (coordinate entries) and normal_eq.cpp (pairs of Jacobian entries,
-// section 17).  The stored lower element of a scalar pair, the stable counting sort, and the
-// destination-sorted runs with their tile index.  Header only, no device work.
+// Host pieces shared by the maps that turn caller-order entries into ordered sums on the device:
+// assembly.cpp (coordinate entries), normal_eq.cpp (pairs of Jacobian entries,
+// section 17) and sym_product.cpp (row lists, section 21).  The stored lower element of a scalar pair,
+// the stable counting sort, the destination-sorted runs with their tile index (TileRuns), items grouped
+// into runs by a key (RunList), the checks of the caller's arrays and the handle of a map's device
+// copy.  Header only, no device work; the kernels that sum the runs are in hip_ordered_sum.h.
 #pragma once
 
 #include <algorithm>
 #include <cstdint>
+#include <memory>
+#include <numeric>
+#include <stdexcept>
+#include <string>
 #include <tuple>
 #include <vector>
 
-#include "assembly.h"
 #include "solver.h"
 
 namespace BaSpaCho {
+
+// layout elements per workgroup of the tile kernel; runs longer than kAssemblyLongRun items are summed
+// by a whole wave instead of one lane
+constexpr int64_t kAssemblyTile = 2048;
+constexpr int32_t kAssemblyLongRun = 64;
+constexpr bool isLongRun(int64_t len) { return len > kAssemblyLongRun; }
+
+// a map's tables on the device (hip_extensions.hip), each uploaded by the first call that needs it and
+// freed with the map
+struct HipEntryMapDev;
+void hipBackendFreeEntryMap(HipEntryMapDev* dev);
+struct HipEntryMapDevFree {
+  void operator()(HipEntryMapDev* dev) const { hipBackendFreeEntryMap(dev); }
+};
+using HipEntryMapDevPtr = std::unique_ptr<HipEntryMapDev, HipEntryMapDevFree>;
 
 // stable counting sort of idx by key(idx) in [0, numKeys)
 template <typename Key>
@@ -69,43 +89,101 @@ static void sortByOffset(std::vector<int32_t>& items, std::vector<int32_t>& sort
   countingSort(byLocal, sorted, numTiles, [off](int32_t k) { return off(k) / kAssemblyTile; });
 }
 
-// the destination-sorted form of items sorted by offset (off(x): offset of the x-th sorted item): the
-// unique destinations ascending, run starts, the tile index with destLocal and the long-run list
+// the destination-sorted form of items sorted by offset: the unique destinations in ascending offset; the
+// items of destination u are the sorted items [runStart[u], runStart[u + 1]).  Tile index: destinations
+// [tileFirst[t], tileFirst[t + 1]) lie in layout tile t (kAssemblyTile elements); destLocal[u] = dest[u] -
+// tile base.  longDest lists the destinations whose runs are longer than kAssemblyLongRun, ascending;
+// those of tile t are [tileLongFirst[t], tileLongFirst[t + 1])
 struct TileRuns {
-  std::vector<int64_t>& dest;
-  std::vector<int32_t>& runStart;
-  std::vector<int32_t>& tileFirst;
-  std::vector<uint16_t>& destLocal;
-  std::vector<int32_t>& longDest;
-  std::vector<int32_t>& tileLongFirst;
-  int64_t& maxRun;
+  std::vector<int64_t> dest;
+  std::vector<int32_t> runStart;
+  std::vector<int32_t> tileFirst;
+  std::vector<uint16_t> destLocal;
+  std::vector<int32_t> longDest;
+  std::vector<int32_t> tileLongFirst;
+  int64_t maxRun = 0;  // most items summed into one element
+
+  // off(x): offset of the x-th sorted item
+  template <typename Off>
+  void build(int64_t numSorted, int64_t numTiles, Off off) {
+    tileFirst.assign(numTiles + 1, 0);
+    tileLongFirst.assign(numTiles + 1, 0);
+    for (int64_t x = 0; x < numSorted; x++) {
+      const int64_t o = off(x);
+      if (x == 0 || o != dest.back()) {
+        dest.push_back(o);
+        runStart.push_back((int32_t)x);
+        destLocal.push_back((uint16_t)(o & (kAssemblyTile - 1)));
+        tileFirst[o / kAssemblyTile + 1]++;
+      }
+    }
+    runStart.push_back((int32_t)numSorted);
+    const int64_t numDest = (int64_t)dest.size();
+    for (int64_t u = 0; u < numDest; u++) {
+      const int64_t len = runStart[u + 1] - runStart[u];
+      maxRun = std::max(maxRun, len);
+      if (isLongRun(len)) {
+        longDest.push_back((int32_t)u);
+        tileLongFirst[dest[u] / kAssemblyTile + 1]++;
+      }
+    }
+    for (int64_t b = 0; b < numTiles; b++) {
+      tileFirst[b + 1] += tileFirst[b];
+      tileLongFirst[b + 1] += tileLongFirst[b];
+    }
+  }
+  // bytes on the device once uploaded (dest stays on the host)
+  int64_t deviceBytes() const {
+    return (int64_t)((runStart.size() + tileFirst.size() + longDest.size() + tileLongFirst.size()) * sizeof(int32_t) +
+                     destLocal.size() * sizeof(uint16_t));
+  }
 };
-template <typename Off>
-static void buildTileRuns(int64_t numSorted, int64_t numTiles, Off off, TileRuns t) {
-  t.tileFirst.assign(numTiles + 1, 0);
-  t.tileLongFirst.assign(numTiles + 1, 0);
-  for (int64_t x = 0; x < numSorted; x++) {
-    const int64_t o = off(x);
-    if (x == 0 || o != t.dest.back()) {
-      t.dest.push_back(o);
-      t.runStart.push_back((int32_t)x);
-      t.destLocal.push_back((uint16_t)(o & (kAssemblyTile - 1)));
-      t.tileFirst[o / kAssemblyTile + 1]++;
+
+// items grouped into runs by a key: the items of run u are (entry[t], idx[t]), t in [start[u],
+// start[u + 1]), in the order the items were given.  longRuns (when asked for) lists the runs of more
+// than kAssemblyLongRun items, which a whole wave sums
+struct RunList {
+  std::vector<int32_t> start, entry, idx, longRuns;
+  int64_t maxRun = 0;  // most items in one run
+
+  // item t in [0, numItems) goes to run key(t) in [0, numKeys) as (entryOf(t), idxOf(t))
+  template <typename Key, typename Entry, typename Idx>
+  void build(int64_t numItems, int64_t numKeys, Key key, Entry entryOf, Idx idxOf, bool wantLong) {
+    std::vector<int32_t> ids(numItems), sorted;
+    std::iota(ids.begin(), ids.end(), 0);
+    countingSort(ids, sorted, numKeys, key);
+    start.assign(numKeys + 1, 0);
+    for (int32_t t : ids) start[key(t) + 1]++;
+    for (int64_t u = 0; u < numKeys; u++) start[u + 1] += start[u];
+    entry.resize(numItems);
+    idx.resize(numItems);
+    for (int64_t t = 0; t < numItems; t++) {
+      entry[t] = (int32_t)entryOf(sorted[t]);
+      idx[t] = (int32_t)idxOf(sorted[t]);
+    }
+    for (int64_t u = 0; u < numKeys; u++) {
+      const int64_t len = start[u + 1] - start[u];
+      maxRun = std::max(maxRun, len);
+      if (wantLong && isLongRun(len)) longRuns.push_back((int32_t)u);
     }
   }
-  t.runStart.push_back((int32_t)numSorted);
-  const int64_t numDest = (int64_t)t.dest.size();
-  for (int64_t u = 0; u < numDest; u++) {
-    const int64_t len = t.runStart[u + 1] - t.runStart[u];
-    t.maxRun = std::max(t.maxRun, len);
-    if (len > kAssemblyLongRun) {
-      t.longDest.push_back((int32_t)u);
-      t.tileLongFirst[t.dest[u] / kAssemblyTile + 1]++;
-    }
+  int64_t deviceBytes() const {
+    return (int64_t)((start.size() + entry.size() + idx.size() + longRuns.size()) * sizeof(int32_t));
   }
-  for (int64_t b = 0; b < numTiles; b++) {
-    t.tileFirst[b + 1] += t.tileFirst[b];
-    t.tileLongFirst[b + 1] += t.tileLongFirst[b];
+};
+
+// ---- what every map says about its input: `op` is the map's name in the message
+static inline std::string entryName(int64_t k, int64_t i, int64_t j) {
+  return "entry " + std::to_string(k) + " at (" + std::to_string(i) + ", " + std::to_string(j) + ")";
+}
+static inline void checkBelow2p31(const char* op, const char* what, int64_t v) {
+  if (v < 0 || v >= (int64_t(1) << 31)) {
+    throw std::runtime_error(std::string(op) + ": " + what + " = " + std::to_string(v) + " is outside [0, 2^31)");
+  }
+}
+static inline void checkEntryArrays(const char* op, int64_t nnz, const int64_t* rows, const int64_t* cols) {
+  if (nnz > 0 && (rows == nullptr || cols == nullptr)) {
+    throw std::runtime_error(std::string(op) + ": the row or column array is NULL");
   }
 }
 

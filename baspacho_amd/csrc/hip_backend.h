@@ -163,41 +163,38 @@ template <typename T>
 void hipBackendSchurDense(SymbolicCtx& sym, const T* const* in, T* const* out, int64_t batch, bool single,
                           int64_t fromLump, const int32_t* dest, bool toDense);
 
-// Assembly of coordinate entries into the layout (hip_assembly_kernels.h).  The
-// map is uploaded on the first call and kept in map.dev.
+// The operations on entry maps (hip_ordered_sum.h).  The tables of a map are kept in map.dev, which is
+// freed with the map (hipBackendFreeEntryMap, declared in entry_map.h).
+//
+// Assembly of coordinate entries into the layout.  The map is uploaded on the
+// first call.
 // assemble: in = values (nnz each), out = data (dataSize each); adjoint: in = gradients of the data,
 // out = gradients of the values.
 struct AssemblyMap;
-struct HipAssemblyDev;
 template <typename T>
 void hipBackendAssemble(SymbolicCtx& sym, const AssemblyMap& map, const T* const* in, T* const* out,
                         int64_t batch, bool single, bool adjoint);
-void hipBackendFreeAssembly(HipAssemblyDev* dev);
 
-// Normal equations of a sparse Jacobian (hip_normal_eq_kernels.h).  Each part of
-// the map is uploaded on the first call that needs it and kept in map.dev.
+// Normal equations of a sparse Jacobian.  Each part of the map is uploaded on
+// the first call that needs it.
 //   NormalEqHessian:  out = data (dataSize each) from values;  x unused
 //   NormalEqAdjoint:  out = gradients of the values from values and x = gradients of the data
 //   NormalEqJtVec:    out = J^T x ([n, q] each) from values and x ([m, q]);  NormalEqJVec: out = J x
 struct NormalEqMap;
-struct HipNormalEqDev;
 enum NormalEqOp : int32_t { NormalEqHessian = 0, NormalEqAdjoint = 1, NormalEqJtVec = 2, NormalEqJVec = 3 };
 template <typename T>
 void hipBackendNormalEq(SymbolicCtx& sym, const NormalEqMap& map, int32_t op, const T* const* values,
                         const T* const* x, T* const* out, int64_t q, int64_t batch, bool single);
-void hipBackendFreeNormalEq(HipNormalEqDev* dev);
 
-// Products with a symmetric matrix given as entries (hip_sym_product_kernels.h).
-// Each part of the map is uploaded on the first call that needs it and kept in map.dev.
+// Products with a symmetric matrix given as entries.  Each part of the map is
+// uploaded on the first call that needs it.
 //   SymProductMv:     out = A x ([n, q] each) from a = values (nnz) and b = x ([n, q])
 //   SymProductOuter:  out = gradient of the values (nnz) from a = g and b = x ([n, q] both)
 struct SymProductMap;
-struct HipSymProductDev;
 enum SymProductOp : int32_t { SymProductMv = 0, SymProductOuter = 1 };
 template <typename T>
 void hipBackendSymProduct(SymbolicCtx& sym, const SymProductMap& map, int32_t op, const T* const* a,
                           const T* const* b, T* const* out, int64_t q, int64_t batch, bool single);
-void hipBackendFreeSymProduct(HipSymProductDev* dev);
 
 // Reach solves (hip_reach_kernels.h), one matrix, plan from buildReachPlan (reach.h).
 // reachSolveL: W (numCols x order, column-major, leading dimension order) <- the unit columns of the

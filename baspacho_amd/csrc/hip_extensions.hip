@@ -5,86 +5,41 @@
 // entry point stages its pointer arguments, splits the batch into chunks and enqueues the launches
 // of a chunk on the execution stream (the call path: HipSymbolicCtx::stage / forChunks).
 #include "hip_context.h"
-#include "hip_assembly_kernels.h"
 #include "hip_chol_adjoint_kernels.h"
 #include "hip_grad_kernels.h"
-#include "hip_normal_eq_kernels.h"
+#include "hip_ordered_sum.h"
 #include "hip_reach_kernels.h"
 #include "hip_selinv_adjoint_kernels.h"
 #include "hip_selinv_kernels.h"
 #include "hip_status_kernels.h"
-#include "hip_sym_product_kernels.h"
+#include "normal_eq.h"
+#include "sym_product.h"
 
 namespace BaSpaCho {
 
 using std::vector;
 using namespace hipb;
 
-// an assembly map on the device (assembly.h), owned by its AssemblyMap
-struct HipAssemblyDev {
-  DevBuf entryOff, tileFirst, tileLongFirst, runStart, runEntry, destLocal, longDest;
-  void upload(const AssemblyMap& m) {
-    entryOff.upload(m.entryOff);
-    tileFirst.upload(m.tileFirst);
-    tileLongFirst.upload(m.tileLongFirst);
-    runStart.upload(m.runStart);
-    runEntry.upload(m.runEntry);
-    destLocal.upload(m.destLocal);
-    longDest.upload(m.longDest);
+// the tables of an entry map on the device (entry_map.h), owned by the map.  A host table is uploaded
+// by the first call that asks for it and found again by its address inside the map
+struct HipEntryMapDev {
+  std::map<const void*, DevBuf> tables;
+  template <typename U>
+  const U* get(const vector<U>& v) {
+    auto it = tables.find(&v);
+    if (it == tables.end()) {
+      DevBuf b;
+      b.upload(v);
+      it = tables.emplace(&v, std::move(b)).first;
+    }
+    return it->second.template as<U>();
+  }
+  static HipEntryMapDev& of(HipEntryMapDevPtr& dev) {
+    if (!dev) dev.reset(new HipEntryMapDev);
+    return *dev;
   }
 };
-
-// the three parts of a normal-equations map on the device (normal_eq.h), owned by its NormalEqMap
-struct HipNormalEqDev {
-  bool hasForward = false, hasAdjoint = false, hasVectors = false;
-  DevBuf tileFirst, tileLongFirst, runStart, pairA, pairB, destLocal, longDest;
-  DevBuf adjStart, adjPartner, adjDest, adjLong;
-  DevBuf colStart, colEntry, colIdx, rowStart, rowEntry, rowIdx;
-  void uploadForward(const NormalEqMap& m) {
-    tileFirst.upload(m.tileFirst);
-    tileLongFirst.upload(m.tileLongFirst);
-    runStart.upload(m.runStart);
-    pairA.upload(m.pairA);
-    pairB.upload(m.pairB);
-    destLocal.upload(m.destLocal);
-    longDest.upload(m.longDest);
-    hasForward = true;
-  }
-  void uploadAdjoint(const NormalEqMap& m) {
-    adjStart.upload(m.adjStart);
-    adjPartner.upload(m.adjPartner);
-    adjDest.upload(m.adjDest);
-    adjLong.upload(m.adjLong);
-    hasAdjoint = true;
-  }
-  void uploadVectors(const NormalEqMap& m) {
-    colStart.upload(m.colStart);
-    colEntry.upload(m.colEntry);
-    colIdx.upload(m.colIdx);
-    rowStart.upload(m.rowStart);
-    rowEntry.upload(m.rowEntry);
-    rowIdx.upload(m.rowIdx);
-    hasVectors = true;
-  }
-};
-
-// the two parts of a symmetric-product map on the device (sym_product.h), owned by its SymProductMap
-struct HipSymProductDev {
-  bool hasRows = false, hasEntries = false;
-  DevBuf rowStart, termEntry, termIdx, longRows, entRow, entCol;
-  void uploadRows(const SymProductMap& m) {
-    rowStart.upload(m.rowStart);
-    termEntry.upload(m.termEntry);
-    termIdx.upload(m.termIdx);
-    longRows.upload(m.longRows);
-    hasRows = true;
-  }
-  void uploadEntries(const SymProductMap& m) {
-    entRow.upload(m.entRow);
-    entCol.upload(m.entCol);
-    hasEntries = true;
-  }
-};
+void hipBackendFreeEntryMap(HipEntryMapDev* dev) { delete dev; }
 
 namespace {
 
@@ -698,111 +653,154 @@ void hipBackendSchurDense(SymbolicCtx& sym, const T* const* in, T* const* out, i
   });
 }
 
-// ---- assembly of coordinate entries (hip_assembly_kernels.h) ---------------
+// ---- ordered sums over entry maps (hip_ordered_sum.h, DESIGN.md sections 14, 17 and 21) -----------
+namespace {
+
+// the tile kernel over the runs `t` of a map with `numTiles` tiles of `dataSize` layout elements
+struct TileLaunch {
+  int64_t dataSize, numTiles;
+  const int32_t *tileFirst, *tileLongFirst, *runStart;
+  const uint16_t* destLocal;
+  const int32_t* longDest;
+  TileLaunch(HipEntryMapDev& d, const TileRuns& t, int64_t dataSize, int64_t numTiles)
+      : dataSize(dataSize), numTiles(numTiles), tileFirst(d.get(t.tileFirst)),
+        tileLongFirst(d.get(t.tileLongFirst)), runStart(d.get(t.runStart)), destLocal(d.get(t.destLocal)),
+        longDest(d.get(t.longDest)) {}
+  template <typename T, typename Term>
+  void operator()(hipStream_t stream, const Term& term, hipk::DataRef<T> out, unsigned nm) const {
+    hipk::orderedSumTiles<T><<<dim3((unsigned)numTiles, nm), hipk::kAsmThreads, 0, stream>>>(
+        dataSize, tileFirst, tileLongFirst, runStart, destLocal, longDest, term, out);
+  }
+};
+
+// the run kernel over `numRuns` runs and q vectors: one thread per output, then one wave per (long
+// run, vector) of the `numLong` runs of longRuns (NULL: no long list, every run by one lane)
+template <typename Start>
+struct RunLaunch {
+  int64_t numRuns, q, shortWgs, longWaves, longWgs;
+  const Start* start;
+  const int32_t *longRuns, *entry = nullptr, *idx = nullptr;  // entry, idx: those of a RunList
+  RunLaunch(int64_t numRuns, int64_t q, const Start* start, const int32_t* longRuns, int64_t numLong)
+      : numRuns(numRuns), q(q), shortWgs((numRuns * q + hipk::kAsmThreads - 1) / hipk::kAsmThreads),
+        longWaves(numLong * q), longWgs((longWaves + hipk::kAsmWavesPerWg - 1) / hipk::kAsmWavesPerWg),
+        start(start), longRuns(longRuns) {
+    BASPACHO_CHECK_LT(shortWgs + longWgs, (int64_t)INT32_MAX);
+  }
+  template <typename T, typename Term>
+  void operator()(hipStream_t stream, const Term& term, hipk::DataRef<T> out, unsigned nm) const {
+    hipk::orderedSumRuns<T><<<dim3((unsigned)(shortWgs + longWgs), nm), hipk::kAsmThreads, 0, stream>>>(
+        numRuns, (int32_t)q, (int32_t)shortWgs, longWaves, start, longRuns, term, out);
+  }
+};
+RunLaunch<int32_t> runLaunch(HipEntryMapDev& d, const RunList& r, int64_t q, bool withLong) {
+  RunLaunch<int32_t> l((int64_t)r.start.size() - 1, q, d.get(r.start), withLong ? d.get(r.longRuns) : nullptr,
+                       withLong ? (int64_t)r.longRuns.size() : 0);
+  l.entry = d.get(r.entry);
+  l.idx = d.get(r.idx);
+  return l;
+}
+
+// stages the operands (b may be NULL) and calls launch(a, b, out, members) for every chunk of the batch
+template <typename T, typename Launch>
+void forOperandChunks(HipSymbolicCtx& h, const T* const* a, const T* const* b, T* const* out, int64_t batch,
+                      bool single, Launch launch) {
+  const BatchPtrs<const T> as = h.stage(a, batch, single), bs = h.stage(b, batch, single);
+  const BatchPtrs<T> o = h.stage(out, batch, single);
+  h.forChunks(batch, HipSymbolicCtx::kMaxGridY,
+              [&](int64_t q0, unsigned nm) { launch(as.at(q0), bs.at(q0), o.at(q0), nm); });
+}
+
+}  // namespace
+
 // assemble (or its adjoint) of `batch` matrices: one launch per chunk
 template <typename T>
 void hipBackendAssemble(SymbolicCtx& sym, const AssemblyMap& m, const T* const* in, T* const* out, int64_t batch,
                         bool single, bool adjoint) {
+  using In = hipk::DataRef<const T>;
+  using Out = hipk::DataRef<T>;
   HipSymbolicCtx& h = hipCtx(sym);
   const hipStream_t stream = h.stream;
   h.checkDevice();
-  if (m.dev == nullptr) {
-    std::unique_ptr<HipAssemblyDev> d(new HipAssemblyDev);
-    d->upload(m);
-    m.dev = d.release();
-  }
-  const HipAssemblyDev& d = *m.dev;
+  // the whole map with the first call, whichever direction it takes
+  HipEntryMapDev& d = HipEntryMapDev::of(m.dev);
+  const int64_t* entryOff = d.get(m.entryOff);
+  const int32_t* runEntry = d.get(m.runEntry);
+  const TileLaunch tiles(d, m.tiles, m.dataSize, m.numTiles);
   if (adjoint && m.nnz == 0) return;
-  const BatchPtrs<const T> i = h.stage(in, batch, single);
-  const BatchPtrs<T> o = h.stage(out, batch, single);
-  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+  const int64_t per = hipk::kAsmThreads * hipk::kAsmAdjPer;
+  forOperandChunks<T>(h, in, nullptr, out, batch, single, [&](In i, In, Out o, unsigned nm) {
     if (adjoint) {
-      const int64_t per = hipk::kAsmThreads * hipk::kAsmAdjPer;
       hipk::assembleAdjointEntries<T><<<dim3((unsigned)((m.nnz + per - 1) / per), nm), hipk::kAsmThreads, 0,
-                                         stream>>>(m.nnz, d.entryOff.as<int64_t>(), i.at(q0), o.at(q0));
+                                         stream>>>(m.nnz, entryOff, i, o);
     } else {
-      hipk::assembleTiles<T><<<dim3((unsigned)m.numTiles, nm), hipk::kAsmThreads, 0, stream>>>(
-          m.dataSize, d.tileFirst.as<int32_t>(), d.tileLongFirst.as<int32_t>(), d.runStart.as<int32_t>(),
-          d.runEntry.as<int32_t>(), d.destLocal.as<uint16_t>(), d.longDest.as<int32_t>(), i.at(q0), o.at(q0));
+      tiles(stream, hipk::EntryTerm<T>{runEntry, i}, o, nm);
     }
   });
 }
 
-// ---- normal equations of a sparse Jacobian (hip_normal_eq_kernels.h) --------
-// one of the four operations on `batch` members: one launch per chunk
+// one of the four operations of the normal equations on `batch` members: one launch per chunk
 template <typename T>
 void hipBackendNormalEq(SymbolicCtx& sym, const NormalEqMap& m, int32_t op, const T* const* values,
                         const T* const* x, T* const* out, int64_t q, int64_t batch, bool single) {
+  using In = hipk::DataRef<const T>;
+  using Out = hipk::DataRef<T>;
   HipSymbolicCtx& h = hipCtx(sym);
   const hipStream_t stream = h.stream;
   h.checkDevice();
-  if (m.dev == nullptr) m.dev = new HipNormalEqDev;
-  HipNormalEqDev& d = *m.dev;
-  if (op == NormalEqHessian && !d.hasForward) d.uploadForward(m);
-  if (op == NormalEqAdjoint && !d.hasAdjoint) d.uploadAdjoint(m);
-  if ((op == NormalEqJtVec || op == NormalEqJVec) && !d.hasVectors) d.uploadVectors(m);
-  const bool jt = op == NormalEqJtVec;
-  const int64_t numRuns = jt ? m.n : m.m;
-  if (op == NormalEqAdjoint && m.nnz == 0) return;
-  if (op == NormalEqHessian && m.numTiles == 0) return;
-  if ((op == NormalEqJtVec || op == NormalEqJVec) && numRuns * q == 0) return;
-  const BatchPtrs<const T> v = h.stage(values, batch, single), xs = h.stage(x, batch, single);
-  const BatchPtrs<T> o = h.stage(out, batch, single);
-  const int64_t shortWgs = (m.nnz + hipk::kAsmThreads - 1) / hipk::kAsmThreads;
-  const int64_t numLong = (int64_t)m.adjLong.size();
-  const int64_t longWgs = (numLong + hipk::kNeqWavesPerWg - 1) / hipk::kNeqWavesPerWg;
-  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
-    if (op == NormalEqHessian) {
-      hipk::normalEqTiles<T><<<dim3((unsigned)m.numTiles, nm), hipk::kAsmThreads, 0, stream>>>(
-          m.dataSize, d.tileFirst.as<int32_t>(), d.tileLongFirst.as<int32_t>(), d.runStart.as<int32_t>(),
-          d.pairA.as<int32_t>(), d.pairB.as<int32_t>(), d.destLocal.as<uint16_t>(), d.longDest.as<int32_t>(),
-          v.at(q0), o.at(q0));
-    } else if (op == NormalEqAdjoint) {
-      hipk::normalEqAdjointEntries<T><<<dim3((unsigned)(shortWgs + longWgs), nm), hipk::kAsmThreads, 0, stream>>>(
-          m.nnz, (int32_t)shortWgs, (int32_t)numLong, d.adjStart.as<int64_t>(), d.adjPartner.as<int32_t>(),
-          d.adjDest.as<int64_t>(), d.adjLong.as<int32_t>(), v.at(q0), xs.at(q0), o.at(q0));
-    } else {
-      const int64_t wgs = (numRuns * q + hipk::kAsmThreads - 1) / hipk::kAsmThreads;
-      hipk::runDotVec<T><<<dim3((unsigned)wgs, nm), hipk::kAsmThreads, 0, stream>>>(
-          numRuns, (int32_t)q, (jt ? d.colStart : d.rowStart).template as<int32_t>(),
-          (jt ? d.colEntry : d.rowEntry).template as<int32_t>(), (jt ? d.colIdx : d.rowIdx).template as<int32_t>(),
-          v.at(q0), xs.at(q0), o.at(q0));
-    }
-  });
+  HipEntryMapDev& d = HipEntryMapDev::of(m.dev);
+  if (op == NormalEqHessian) {
+    const TileLaunch tiles(d, m.tiles, m.dataSize, m.numTiles);
+    const int32_t *pairA = d.get(m.pairA), *pairB = d.get(m.pairB);
+    if (m.numTiles == 0) return;
+    forOperandChunks<T>(h, values, x, out, batch, single, [&](In v, In, Out o, unsigned nm) {
+      tiles(stream, hipk::PairTerm<T>{pairA, pairB, v}, o, nm);
+    });
+  } else if (op == NormalEqAdjoint) {
+    const RunLaunch<int64_t> runs(m.nnz, 1, d.get(m.adjStart), d.get(m.adjLong), (int64_t)m.adjLong.size());
+    const int64_t* adjDest = d.get(m.adjDest);
+    const int32_t* adjPartner = d.get(m.adjPartner);
+    if (m.nnz == 0) return;
+    forOperandChunks<T>(h, values, x, out, batch, single, [&](In v, In g, Out o, unsigned nm) {
+      runs(stream, hipk::AdjointTerm<T>{adjDest, adjPartner, g, v}, o, nm);
+    });
+  } else {
+    // both lists with the first product, whichever it is
+    const RunLaunch<int32_t> byCol = runLaunch(d, m.cols, q, false), byRow = runLaunch(d, m.rows, q, false);
+    const RunLaunch<int32_t>& runs = op == NormalEqJtVec ? byCol : byRow;
+    if (runs.numRuns * q == 0) return;
+    forOperandChunks<T>(h, values, x, out, batch, single, [&](In v, In xv, Out o, unsigned nm) {
+      runs(stream, hipk::DotTerm<T>{runs.entry, runs.idx, v, xv}, o, nm);
+    });
+  }
 }
 
-// ---- products with a matrix given as entries (hip_sym_product_kernels.h) ------
 // mv (a = values, b = x, out = A x) or outer (a = g, b = x, out = the gradient of the values) on `batch`
 // members: one launch per chunk
 template <typename T>
 void hipBackendSymProduct(SymbolicCtx& sym, const SymProductMap& m, int32_t op, const T* const* a, const T* const* b,
                           T* const* out, int64_t q, int64_t batch, bool single) {
+  using In = hipk::DataRef<const T>;
+  using Out = hipk::DataRef<T>;
   HipSymbolicCtx& h = hipCtx(sym);
   const hipStream_t stream = h.stream;
   h.checkDevice();
   BASPACHO_CHECK_LT(q, (int64_t)INT32_MAX);
-  if (m.dev == nullptr) m.dev = new HipSymProductDev;
-  HipSymProductDev& d = *m.dev;
-  if (op == SymProductMv && !d.hasRows) d.uploadRows(m);
-  if (op == SymProductOuter && !d.hasEntries) d.uploadEntries(m);
-  if (op == SymProductMv ? m.n * q == 0 : m.nnz == 0) return;
-  const BatchPtrs<const T> as = h.stage(a, batch, single), bs = h.stage(b, batch, single);
-  const BatchPtrs<T> o = h.stage(out, batch, single);
-  const int64_t shortWgs = (m.n * q + hipk::kAsmThreads - 1) / hipk::kAsmThreads;
-  const int64_t longWaves = (int64_t)m.longRows.size() * q;
-  const int64_t longWgs = (longWaves + hipk::kNeqWavesPerWg - 1) / hipk::kNeqWavesPerWg;
-  const int64_t outerWgs = (m.nnz + hipk::kAsmThreads - 1) / hipk::kAsmThreads;
-  BASPACHO_CHECK_LT(shortWgs + longWgs, (int64_t)INT32_MAX);
-  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
-    if (op == SymProductMv) {
-      hipk::symProductMv<T><<<dim3((unsigned)(shortWgs + longWgs), nm), hipk::kAsmThreads, 0, stream>>>(
-          m.n, (int32_t)q, (int32_t)shortWgs, longWaves, d.rowStart.as<int32_t>(), d.termEntry.as<int32_t>(),
-          d.termIdx.as<int32_t>(), d.longRows.as<int32_t>(), as.at(q0), bs.at(q0), o.at(q0));
-    } else {
-      hipk::symProductOuter<T><<<dim3((unsigned)outerWgs, nm), hipk::kAsmThreads, 0, stream>>>(
-          m.nnz, (int32_t)q, d.entRow.as<int32_t>(), d.entCol.as<int32_t>(), as.at(q0), bs.at(q0), o.at(q0));
-    }
-  });
+  HipEntryMapDev& d = HipEntryMapDev::of(m.dev);
+  if (op == SymProductMv) {
+    const RunLaunch<int32_t> rows = runLaunch(d, m.rows, q, true);
+    if (m.n * q == 0) return;
+    forOperandChunks<T>(h, a, b, out, batch, single, [&](In v, In xv, Out o, unsigned nm) {
+      rows(stream, hipk::DotTerm<T>{rows.entry, rows.idx, v, xv}, o, nm);
+    });
+  } else {
+    const int32_t *entRow = d.get(m.entRow), *entCol = d.get(m.entCol);
+    if (m.nnz == 0) return;
+    const int64_t wgs = (m.nnz + hipk::kAsmThreads - 1) / hipk::kAsmThreads;
+    forOperandChunks<T>(h, a, b, out, batch, single, [&](In g, In xv, Out o, unsigned nm) {
+      hipk::symProductOuter<T><<<dim3((unsigned)wgs, nm), hipk::kAsmThreads, 0, stream>>>(m.nnz, (int32_t)q, entRow,
+                                                                                          entCol, g, xv, o);
+    });
+  }
 }
 
 // ---- reach solves (hip_reach_kernels.h) ---------------------------------------
@@ -890,9 +888,5 @@ T* hipBackendReachWorkspace(SymbolicCtx& sym, int64_t elems) {
 BSP_INSTANTIATE_EXTENSIONS(double)
 BSP_INSTANTIATE_EXTENSIONS(float)
 #undef BSP_INSTANTIATE_EXTENSIONS
-
-void hipBackendFreeAssembly(HipAssemblyDev* dev) { delete dev; }
-void hipBackendFreeNormalEq(HipNormalEqDev* dev) { delete dev; }
-void hipBackendFreeSymProduct(HipSymProductDev* dev) { delete dev; }
 
 }  // namespace BaSpaCho

@@ -31,7 +31,7 @@
 #include <cstdint>
 
 #include "hip_grad_kernels.h"
-#include "hip_normal_eq_kernels.h"
+#include "hip_ordered_sum.h"
 
 namespace BaSpaCho {
 namespace hipk {

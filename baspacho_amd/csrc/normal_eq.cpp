@@ -6,59 +6,15 @@
 #include <stdexcept>
 #include <string>
 
-#include "entry_map.h"
-#include "hip_backend.h"
 #include "solver.h"
 
 namespace BaSpaCho {
 
-NormalEqMap::~NormalEqMap() {
-  if (dev) hipBackendFreeNormalEq(dev);
-}
-
-int64_t NormalEqMap::forwardDeviceBytes() const {
-  return (int64_t)(runStart.size() * sizeof(int32_t) + pairA.size() * sizeof(int32_t) +
-                   pairB.size() * sizeof(int32_t) + tileFirst.size() * sizeof(int32_t) +
-                   destLocal.size() * sizeof(uint16_t) + longDest.size() * sizeof(int32_t) +
-                   tileLongFirst.size() * sizeof(int32_t));
-}
-
-int64_t NormalEqMap::adjointDeviceBytes() const {
-  return (int64_t)(adjStart.size() * sizeof(int64_t) + adjPartner.size() * sizeof(int32_t) +
-                   adjDest.size() * sizeof(int64_t) + adjLong.size() * sizeof(int32_t));
-}
-
-int64_t NormalEqMap::vectorDeviceBytes() const {
-  return (int64_t)((colStart.size() + colEntry.size() + colIdx.size() + rowStart.size() + rowEntry.size() +
-                    rowIdx.size()) *
-                   sizeof(int32_t));
-}
-
-static std::string entryName(int64_t k, int64_t i, int64_t j) {
-  return "entry " + std::to_string(k) + " at (" + std::to_string(i) + ", " + std::to_string(j) + ")";
-}
-
-// the entries grouped by key (ascending k inside a group): starts [numKeys + 1] and the entry list
-static void groupEntries(const std::vector<int32_t>& in, int64_t numKeys, const int64_t* key,
-                         std::vector<int32_t>& start, std::vector<int32_t>& list) {
-  countingSort(in, list, numKeys, [key](int32_t k) { return key[k]; });
-  start.assign(numKeys + 1, 0);
-  for (int32_t k : in) start[key[k] + 1]++;
-  for (int64_t b = 0; b < numKeys; b++) start[b + 1] += start[b];
-}
-
 std::unique_ptr<NormalEqMap> createNormalEqMap(const Solver& solver, int64_t m, int64_t nnz, const int64_t* rows,
                                                const int64_t* cols) {
-  const int64_t lim = int64_t(1) << 31;
-  if (nnz < 0 || nnz >= lim) {
-    throw std::runtime_error("normal equations: nnz = " + std::to_string(nnz) + " is outside [0, 2^31)");
-  }
-  if (m < 0 || m >= lim) {
-    throw std::runtime_error("normal equations: m = " + std::to_string(m) + " is outside [0, 2^31)");
-  }
-  if (nnz > 0 && (rows == nullptr || cols == nullptr)) {
-    throw std::runtime_error("normal equations: the row or column array is NULL");
-  }
+  checkBelow2p31("normal equations", "nnz", nnz);
+  checkBelow2p31("normal equations", "m", m);
+  checkEntryArrays("normal equations", nnz, rows, cols);
   std::unique_ptr<NormalEqMap> q(new NormalEqMap);
   const int64_t n = solver.order();
   q->solver = &solver;
@@ -77,23 +33,17 @@ std::unique_ptr<NormalEqMap> createNormalEqMap(const Solver& solver, int64_t m, 
   }
 
   // vector lists: entries by column and by row, ascending k inside each
-  std::vector<int32_t> all(nnz);
-  std::iota(all.begin(), all.end(), 0);
-  groupEntries(all, n, cols, q->colStart, q->colEntry);
-  groupEntries(all, m, rows, q->rowStart, q->rowEntry);
-  std::vector<int32_t>().swap(all);
-  q->colIdx.resize(nnz);
-  q->rowIdx.resize(nnz);
-  for (int64_t x = 0; x < nnz; x++) {
-    q->colIdx[x] = (int32_t)rows[q->colEntry[x]];
-    q->rowIdx[x] = (int32_t)cols[q->rowEntry[x]];
-  }
+  const auto rowOf = [rows](int32_t k) { return rows[k]; };
+  const auto colOf = [cols](int32_t k) { return cols[k]; };
+  const auto self = [](int32_t k) { return k; };
+  q->cols.build(nnz, n, colOf, self, rowOf, false);
+  q->rows.build(nnz, m, rowOf, self, colOf, false);
 
   // repeated (row, col): the entries by (row, col, k) -- the column lists, stably by row -- hold the
   // repeats of one position side by side; the first repeated entry is the smallest second-of-a-pair
   {
     std::vector<int32_t> byRowCol;
-    countingSort(q->colEntry, byRowCol, m, [rows](int32_t k) { return rows[k]; });
+    countingSort(q->cols.entry, byRowCol, m, rowOf);
     int64_t first = -1, earlier = -1;
     for (int64_t x = 1; x < nnz; x++) {
       const int32_t a = byRowCol[x - 1], b = byRowCol[x];
@@ -120,10 +70,10 @@ std::unique_ptr<NormalEqMap> createNormalEqMap(const Solver& solver, int64_t m, 
   // P before anything of its size exists (sum d = nnz < 2^31, so the sum of d (d + 1) / 2 fits int64)
   int64_t P = 0;
   for (int64_t i = 0; i < m; i++) {
-    const int64_t d = q->rowStart[i + 1] - q->rowStart[i];
+    const int64_t d = q->rows.start[i + 1] - q->rows.start[i];
     P += d * (d + 1) / 2;
   }
-  if (P >= lim) {
+  if (P >= (int64_t(1) << 31)) {
     throw std::runtime_error("normal equations: the Jacobian rows give P = " + std::to_string(P) +
                              " pairs of entries, outside [0, 2^31)");
   }
@@ -142,9 +92,9 @@ std::unique_ptr<NormalEqMap> createNormalEqMap(const Solver& solver, int64_t m, 
   q->adjDest.reserve(2 * P);
   for (int64_t k = 0; k < nnz; k++) {
     const int64_t i = rows[k], ck = cols[k];
-    for (int32_t x = q->rowStart[i]; x < q->rowStart[i + 1]; x++) {
-      const int32_t k2 = q->rowEntry[x];
-      const int64_t c2 = q->rowIdx[x];
+    for (int32_t x = q->rows.start[i]; x < q->rows.start[i + 1]; x++) {
+      const int32_t k2 = q->rows.entry[x];
+      const int64_t c2 = q->rows.idx[x];
       const int64_t off = loc.offset(std::max(ck, c2), std::min(ck, c2));
       if (off < 0) {
         throw std::runtime_error("normal equations: " + entryName(k, i, ck) + " and entry " + std::to_string(k2) +
@@ -165,7 +115,7 @@ std::unique_ptr<NormalEqMap> createNormalEqMap(const Solver& solver, int64_t m, 
       }
     }
     q->adjStart[k + 1] = (int64_t)q->adjPartner.size();
-    if (q->adjStart[k + 1] - q->adjStart[k] > kAssemblyLongRun) q->adjLong.push_back((int32_t)k);
+    if (isLongRun(q->adjStart[k + 1] - q->adjStart[k])) q->adjLong.push_back((int32_t)k);
   }
 
   // pairs by (offset, ka), then runs, tile index, long runs
@@ -180,8 +130,7 @@ std::unique_ptr<NormalEqMap> createNormalEqMap(const Solver& solver, int64_t m, 
     q->pairB[x] = pb[sorted[x]];
   }
   const int32_t* srt = sorted.data();
-  buildTileRuns(P, q->numTiles, [off, srt](int64_t x) { return off[srt[x]]; },
-                TileRuns{q->dest, q->runStart, q->tileFirst, q->destLocal, q->longDest, q->tileLongFirst, q->maxRun});
+  q->tiles.build(P, q->numTiles, [off, srt](int64_t x) { return off[srt[x]]; });
   return q;
 }
 

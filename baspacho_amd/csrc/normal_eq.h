@@ -1,7 +1,7 @@
 // Normal equations of a sparse Jacobian, H = J^T J in a Solver's numeric layout, g = J^T r and y = J v
 // (DESIGN.md section 17).  The maps from Jacobian entries to the layout are built once on the host
-// (this file, no device work); the kernels that use them are in hip_normal_eq_kernels.h, launched by
-// hip_backend.hip.
+// (this file, no device work); the kernels that use them are in hip_ordered_sum.h, launched by
+// hip_extensions.hip.
 //
 // CONVENTIONS.  J is m x n (n = the solver's order), given as entries (rows[k], cols[k], values[k]) in
 // the caller's scalar order, no (row, col) repeated.  Every unordered pair of entries of one Jacobian
@@ -23,24 +23,15 @@
 
 namespace BaSpaCho {
 
-class Solver;
-struct HipNormalEqDev;  // the three parts of the map on the device (hip_backend.hip), each uploaded on first use
-
 struct NormalEqMap {
   const Solver* solver = nullptr;  // the solver whose layout the map targets
   int64_t m = 0, n = 0, nnz = 0, dataSize = 0, numTiles = 0;
   int64_t numPairs = 0;  // P = sum over rows of d (d + 1) / 2
-  int64_t maxRun = 0;    // most pairs summed into one element
 
   // forward form, destination-sorted as in AssemblyMap: the pairs of destination u are
-  // (pairA[x], pairB[x]), x in [runStart[u], runStart[u + 1]), in ascending pairA
-  std::vector<int64_t> dest;
-  std::vector<int32_t> runStart;
+  // (pairA[x], pairB[x]), x in [tiles.runStart[u], tiles.runStart[u + 1]), in ascending pairA
   std::vector<int32_t> pairA, pairB;
-  std::vector<int32_t> tileFirst;
-  std::vector<uint16_t> destLocal;
-  std::vector<int32_t> longDest;
-  std::vector<int32_t> tileLongFirst;
+  TileRuns tiles;
 
   // adjoint form: the terms of entry k are (adjPartner[t], adjDest[t]), t in [adjStart[k],
   // adjStart[k + 1]), in ascending partner (the self-pair twice); adjLong lists the entries with more
@@ -50,24 +41,22 @@ struct NormalEqMap {
   std::vector<int64_t> adjDest;
   std::vector<int32_t> adjLong;
 
-  // vector lists: the entries of column c are colEntry[colStart[c] .. colStart[c + 1]) in ascending
-  // k, colIdx their rows; the entries of row i are rowEntry[rowStart[i] .. rowStart[i + 1]), rowIdx
-  // their columns
-  std::vector<int32_t> colStart, colEntry, colIdx;
-  std::vector<int32_t> rowStart, rowEntry, rowIdx;
+  // vector lists: the entries of column c in ascending k with their rows (cols), the entries of row i
+  // with their columns (rows); neither has a long list: one lane sums a run of any length
+  RunList cols, rows;
 
-  mutable HipNormalEqDev* dev = nullptr;
-
-  NormalEqMap() = default;
-  NormalEqMap(const NormalEqMap&) = delete;
-  NormalEqMap& operator=(const NormalEqMap&) = delete;
-  ~NormalEqMap();
+  mutable HipEntryMapDevPtr dev;
 
   int64_t numAdjointTerms() const { return (int64_t)adjPartner.size(); }
   // bytes each part takes on the device once uploaded
-  int64_t forwardDeviceBytes() const;
-  int64_t adjointDeviceBytes() const;
-  int64_t vectorDeviceBytes() const;
+  int64_t forwardDeviceBytes() const {
+    return (int64_t)((pairA.size() + pairB.size()) * sizeof(int32_t)) + tiles.deviceBytes();
+  }
+  int64_t adjointDeviceBytes() const {
+    return (int64_t)((adjStart.size() + adjDest.size()) * sizeof(int64_t) +
+                     (adjPartner.size() + adjLong.size()) * sizeof(int32_t));
+  }
+  int64_t vectorDeviceBytes() const { return cols.deviceBytes() + rows.deviceBytes(); }
 };
 
 // Builds the map of the m x order() Jacobian with entries (rows[k], cols[k]) for `solver`.  Throws,

@@ -899,35 +899,85 @@ std::vector<int64_t> Solver::scalarPermutation() const {
   return out;
 }
 
-// checks the arguments before any device work, then runs the batch.  `vals` is the nnz-sized side
-// (values forward, gradValues backward), `lay` the dataSize-sized one
+// One side of an operation on an entry map: what its pointers are called in a message about one of them
+// (`name`) and about their number (`counted`), one pointer per batch member, the elements behind each
+// pointer, and whether the operation writes them (the last side does).  A side of 0 elements is never
+// touched and may be NULL.
+template <typename T>
+struct OpSide {
+  const char *name, *counted;
+  const T* const* ptrs;
+  size_t members;
+  int64_t elems;
+  bool output;
+};
+
+// The argument check of assemble, normalEq and symProduct, before any device work.  Faults are reported
+// in this order: a map of another solver; an empty batch; sides of different member counts; `fault`, the
+// caller's own finding about its scalar arguments (empty: none); then, member by member, a NULL pointer
+// (the sides in the order given) and an output that repeats an earlier member's; then, with `aliasing`,
+// member by member, an output that overlaps an input of its member (the inputs in the order given) and
+// an input that is the output of any member.
+template <typename T>
+static void checkOpArguments(const char* what, const char* mapName, bool sameSolver,
+                             const std::vector<OpSide<T>>& sides, const std::string& fault, bool aliasing) {
+  const auto fail = [what](const std::string& m) { throw std::runtime_error(std::string(what) + ": " + m); };
+  const auto pointerOf = [](const OpSide<T>& s, size_t b) {
+    return std::string("the ") + s.name + " pointer of batch member " + std::to_string(b);
+  };
+  const size_t members = sides[0].members;
+  const OpSide<T>& out = sides.back();
+  if (!sameSolver) fail(std::string("the ") + mapName + " was built on another solver");
+  if (members == 0) fail("the batch is empty");
+  bool sameCount = true;
+  std::string counts;
+  for (size_t i = 0; i < sides.size(); i++) {
+    sameCount = sameCount && sides[i].members == members;
+    counts += (i == 0 ? "" : i + 1 == sides.size() ? " and " : ", ") + std::to_string(sides[i].members) + " " +
+              sides[i].counted;
+  }
+  if (!sameCount) fail("the batch has " + counts);
+  if (!fault.empty()) fail(fault);
+  std::unordered_set<const T*> seen;
+  for (size_t b = 0; b < members; b++) {
+    for (const OpSide<T>& s : sides) {
+      if (s.ptrs[b] == nullptr && s.elems > 0) fail(pointerOf(s, b) + " is NULL");
+    }
+    if (out.ptrs[b] != nullptr && !seen.insert(out.ptrs[b]).second) {
+      fail(pointerOf(out, b) + " repeats an earlier member's");
+    }
+  }
+  if (!aliasing) return;
+  const auto overlap = [](const T* a, int64_t na, const T* b, int64_t nb) {
+    return a != nullptr && b != nullptr && na > 0 && nb > 0 && a < b + nb && b < a + na;
+  };
+  for (size_t b = 0; b < members; b++) {
+    for (const OpSide<T>& s : sides) {
+      if (!s.output && overlap(out.ptrs[b], out.elems, s.ptrs[b], s.elems)) {
+        fail(pointerOf(out, b) + " aliases its " + s.name);
+      }
+    }
+    for (const OpSide<T>& s : sides) {
+      if (!s.output && seen.count(s.ptrs[b])) {
+        fail("an input pointer of batch member " + std::to_string(b) + " is also an output of the batch");
+      }
+    }
+  }
+}
+
+// `in` is values forward and gradData backward, `out` data forward and gradValues backward.  With nnz = 0
+// the nnz-sized side may be NULL; the layout side must be given even when the layout is empty.  Aliasing
+// is not checked
 template <typename T>
 static void runAssembly(const char* what, const Solver* self, SymbolicCtx& sym, const AssemblyMap& map,
                         const std::vector<const T*>& in, const std::vector<T*>& out, bool single, bool adjoint) {
-  const auto fail = [what](const std::string& m) { throw std::runtime_error(std::string(what) + ": " + m); };
-  if (map.solver != self) fail("the assembly was built on another solver");
-  if (in.empty()) fail("the batch is empty");
-  if (in.size() != out.size()) {
-    fail("the batch has " + std::to_string(in.size()) + " inputs and " + std::to_string(out.size()) + " outputs");
-  }
-  const char* inName = adjoint ? "gradient-of-data" : "values";
-  const char* outName = adjoint ? "gradient-of-values" : "data";
-  // with nnz = 0 the nnz-sized side is never touched and may be NULL
-  const bool inOptional = !adjoint && map.nnz == 0, outOptional = adjoint && map.nnz == 0;
-  std::unordered_set<const T*> seen;
-  for (size_t q = 0; q < in.size(); q++) {
-    if (in[q] == nullptr && !inOptional) {
-      fail(std::string("the ") + inName + " pointer of batch member " + std::to_string(q) + " is NULL");
-    }
-    if (out[q] == nullptr) {
-      if (outOptional) continue;
-      fail(std::string("the ") + outName + " pointer of batch member " + std::to_string(q) + " is NULL");
-    }
-    if (!seen.insert(out[q]).second) {
-      fail(std::string("the ") + outName + " pointer of batch member " + std::to_string(q) +
-           " repeats an earlier member's");
-    }
-  }
+  const int64_t nLayout = std::max<int64_t>(map.dataSize, 1);
+  checkOpArguments<T>(what, "assembly", map.solver == self,
+                      {{adjoint ? "gradient-of-data" : "values", "inputs", in.data(), in.size(),
+                        adjoint ? nLayout : map.nnz, false},
+                       {adjoint ? "gradient-of-values" : "data", "outputs", out.data(), out.size(),
+                        adjoint ? map.nnz : nLayout, true}},
+                      "", false);
   hipBackendAssemble<T>(sym, map, in.data(), out.data(), (int64_t)in.size(), single, adjoint);
 }
 
@@ -956,47 +1006,17 @@ void Solver::normalEq(const NormalEqMap& map, int32_t op, const std::vector<cons
                       const std::vector<const T*>& x, const std::vector<T*>& out, int64_t q, bool single) const {
   static const char* names[4] = {"normalEqHessian", "normalEqHessianAdjoint", "normalEqJtVec", "normalEqJVec"};
   if (op < 0 || op > 3) throw std::runtime_error("normalEq: unknown operation " + std::to_string(op));
-  const char* what = names[op];
-  const auto fail = [what](const std::string& m) { throw std::runtime_error(std::string(what) + ": " + m); };
-  if (map.solver != this) fail("the map was built on another solver");
-  if (values.empty()) fail("the batch is empty");
-  const bool hasX = op != NormalEqHessian;
-  if (values.size() != out.size() || (hasX && x.size() != values.size())) {
-    fail("the batch has " + std::to_string(values.size()) + " values, " + std::to_string(x.size()) + " inputs and " +
-         std::to_string(out.size()) + " outputs");
+  const bool hasX = op != NormalEqHessian, adj = op == NormalEqAdjoint, jt = op == NormalEqJtVec;
+  std::vector<OpSide<T>> sides = {{"values", "values", values.data(), values.size(), map.nnz, false}};
+  if (hasX) {
+    sides.push_back({adj ? "gradient-of-data" : "vector", "inputs", x.data(), x.size(),
+                     adj ? map.dataSize : jt ? map.m * q : map.n * q, false});
   }
-  if (hasX && op != NormalEqAdjoint && q < 1) fail("q = " + std::to_string(q) + " vectors; at least one is needed");
-  // element counts of the three sides; a side of size 0 is never touched and may be NULL
-  const int64_t nX = op == NormalEqAdjoint ? map.dataSize : op == NormalEqJtVec ? map.m * q : map.n * q;
-  const int64_t nOut = op == NormalEqHessian   ? map.dataSize
-                       : op == NormalEqAdjoint ? map.nnz
-                       : op == NormalEqJtVec   ? map.n * q
-                                               : map.m * q;
-  const char* xName = op == NormalEqAdjoint ? "gradient-of-data" : "vector";
-  const char* outName = op == NormalEqHessian ? "data" : op == NormalEqAdjoint ? "gradient-of-values" : "output";
-  const auto overlap = [](const T* a, int64_t na, const T* b, int64_t nb) {
-    return a != nullptr && b != nullptr && na > 0 && nb > 0 && a < b + nb && b < a + na;
-  };
-  std::unordered_set<const T*> seen;
-  for (size_t b = 0; b < values.size(); b++) {
-    const std::string member = " pointer of batch member " + std::to_string(b);
-    if (values[b] == nullptr && map.nnz > 0) fail("the values" + member + " is NULL");
-    if (hasX && x[b] == nullptr && nX > 0) fail(std::string("the ") + xName + member + " is NULL");
-    if (out[b] == nullptr) {
-      if (nOut == 0) continue;
-      fail(std::string("the ") + outName + member + " is NULL");
-    }
-    if (!seen.insert(out[b]).second) fail(std::string("the ") + outName + member + " repeats an earlier member's");
-    if (overlap(out[b], nOut, values[b], map.nnz)) fail(std::string("the ") + outName + member + " aliases its values");
-    if (hasX && overlap(out[b], nOut, x[b], nX)) {
-      fail(std::string("the ") + outName + member + " aliases its " + xName);
-    }
-  }
-  for (size_t b = 0; b < values.size(); b++) {  // an output of one member that is an input of another
-    if (seen.count(values[b]) || (hasX && seen.count(x[b]))) {
-      fail("an input pointer of batch member " + std::to_string(b) + " is also an output of the batch");
-    }
-  }
+  sides.push_back({!hasX ? "data" : adj ? "gradient-of-values" : "output", "outputs", out.data(), out.size(),
+                   !hasX ? map.dataSize : adj ? map.nnz : jt ? map.n * q : map.m * q, true});
+  const bool badQ = hasX && !adj && q < 1;
+  checkOpArguments<T>(names[op], "map", map.solver == this, sides,
+                      badQ ? "q = " + std::to_string(q) + " vectors; at least one is needed" : "", true);
   hipBackendNormalEq<T>(*symCtx, map, op, values.data(), hasX ? x.data() : nullptr, out.data(), q,
                         (int64_t)values.size(), single);
 }
@@ -1008,42 +1028,16 @@ void Solver::symProduct(const SymProductMap& map, int32_t op, const std::vector<
     throw std::runtime_error("symProduct: unknown operation " + std::to_string(op));
   }
   const bool mv = op == SymProductMv;
-  const char* what = mv ? "symProductMv" : "symProductOuter";
-  const auto fail = [what](const std::string& m) { throw std::runtime_error(std::string(what) + ": " + m); };
-  if (map.solver != this) fail("the map was built on another solver");
-  if (a.empty()) fail("the batch is empty");
-  if (a.size() != out.size() || x.size() != a.size()) {
-    fail("the batch has " + std::to_string(a.size()) + " " + (mv ? "values" : "gradients") + ", " +
-         std::to_string(x.size()) + " vectors and " + std::to_string(out.size()) + " outputs");
-  }
-  if (q < 1) fail("q = " + std::to_string(q) + " vectors; at least one is needed");
-  if (q >= INT32_MAX) fail("q = " + std::to_string(q) + " vectors is outside [1, 2^31 - 1)");
-  // element counts of the three sides; a side of size 0 is never touched and may be NULL
-  const int64_t nA = mv ? map.nnz : map.n * q, nX = map.n * q, nOut = mv ? map.n * q : map.nnz;
-  const char* aName = mv ? "values" : "gradient";
-  const char* outName = mv ? "output" : "gradient-of-values";
-  const auto overlap = [](const T* p, int64_t np, const T* r, int64_t nr) {
-    return p != nullptr && r != nullptr && np > 0 && nr > 0 && p < r + nr && r < p + np;
-  };
-  std::unordered_set<const T*> seen;
-  for (size_t b = 0; b < a.size(); b++) {
-    const std::string member = " pointer of batch member " + std::to_string(b);
-    if (a[b] == nullptr && nA > 0) fail(std::string("the ") + aName + member + " is NULL");
-    if (x[b] == nullptr && nX > 0) fail("the vector" + member + " is NULL");
-    if (out[b] == nullptr) {
-      if (nOut == 0) continue;
-      fail(std::string("the ") + outName + member + " is NULL");
-    }
-    if (!seen.insert(out[b]).second) fail(std::string("the ") + outName + member + " repeats an earlier member's");
-  }
-  for (size_t b = 0; b < a.size(); b++) {
-    const std::string member = " pointer of batch member " + std::to_string(b);
-    if (overlap(out[b], nOut, a[b], nA)) fail(std::string("the ") + outName + member + " aliases its " + aName);
-    if (overlap(out[b], nOut, x[b], nX)) fail(std::string("the ") + outName + member + " aliases its vector");
-    if (seen.count(a[b]) || seen.count(x[b])) {  // an output of one member that is an input of another
-      fail("an input pointer of batch member " + std::to_string(b) + " is also an output of the batch");
-    }
-  }
+  const std::string fault = q < 1            ? "q = " + std::to_string(q) + " vectors; at least one is needed"
+                            : q >= INT32_MAX ? "q = " + std::to_string(q) + " vectors is outside [1, 2^31 - 1)"
+                                             : "";
+  checkOpArguments<T>(mv ? "symProductMv" : "symProductOuter", "map", map.solver == this,
+                      {{mv ? "values" : "gradient", mv ? "values" : "gradients", a.data(), a.size(),
+                        mv ? map.nnz : map.n * q, false},
+                       {"vector", "vectors", x.data(), x.size(), map.n * q, false},
+                       {mv ? "output" : "gradient-of-values", "outputs", out.data(), out.size(),
+                        mv ? map.n * q : map.nnz, true}},
+                      fault, true);
   hipBackendSymProduct<T>(*symCtx, map, op, a.data(), x.data(), out.data(), q, (int64_t)a.size(), single);
 }
 // ---- blocks of A^-1 by reach solves (reach.h) --------------------------------

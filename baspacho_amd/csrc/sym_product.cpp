@@ -6,27 +6,9 @@
 #include <stdexcept>
 #include <string>
 
-#include "entry_map.h"
-#include "hip_backend.h"
 #include "solver.h"
 
 namespace BaSpaCho {
-
-SymProductMap::~SymProductMap() {
-  if (dev) hipBackendFreeSymProduct(dev);
-}
-
-int64_t SymProductMap::rowDeviceBytes() const {
-  return (int64_t)((rowStart.size() + termEntry.size() + termIdx.size() + longRows.size()) * sizeof(int32_t));
-}
-
-int64_t SymProductMap::entryDeviceBytes() const {
-  return (int64_t)((entRow.size() + entCol.size()) * sizeof(int32_t));
-}
-
-static std::string entryName(int64_t k, int64_t i, int64_t j) {
-  return "entry " + std::to_string(k) + " at (" + std::to_string(i) + ", " + std::to_string(j) + ")";
-}
 
 std::unique_ptr<SymProductMap> createSymProductMap(int64_t n, int64_t nnz, const int64_t* rows, const int64_t* cols,
                                                    int32_t triangle) {
@@ -35,15 +17,9 @@ std::unique_ptr<SymProductMap> createSymProductMap(int64_t n, int64_t nnz, const
     throw std::runtime_error("symmetric product: unknown triangle mode " + std::to_string(triangle) +
                              " (0: lower, 1: full)");
   }
-  if (nnz < 0 || nnz >= lim) {
-    throw std::runtime_error("symmetric product: nnz = " + std::to_string(nnz) + " is outside [0, 2^31)");
-  }
-  if (n < 0 || n >= lim) {
-    throw std::runtime_error("symmetric product: order n = " + std::to_string(n) + " is outside [0, 2^31)");
-  }
-  if (nnz > 0 && (rows == nullptr || cols == nullptr)) {
-    throw std::runtime_error("symmetric product: the row or column array is NULL");
-  }
+  checkBelow2p31("symmetric product", "nnz", nnz);
+  checkBelow2p31("symmetric product", "order n", n);
+  checkEntryArrays("symmetric product", nnz, rows, cols);
   std::unique_ptr<SymProductMap> m(new SymProductMap);
   m->triangle = triangle;
   m->n = n;
@@ -95,25 +71,8 @@ std::unique_ptr<SymProductMap> createSymProductMap(int64_t n, int64_t nnz, const
       tIdx.push_back(i);
     }
   }
-  std::vector<int32_t> ids(T), sorted;
-  std::iota(ids.begin(), ids.end(), 0);
-  const int32_t* key = tRow.data();
-  countingSort(ids, sorted, n, [key](int32_t t) { return key[t]; });
-  std::vector<int32_t>().swap(ids);
-  m->rowStart.assign(n + 1, 0);
-  for (int32_t r : tRow) m->rowStart[r + 1]++;
-  for (int64_t i = 0; i < n; i++) m->rowStart[i + 1] += m->rowStart[i];
-  m->termEntry.resize(T);
-  m->termIdx.resize(T);
-  for (int64_t t = 0; t < T; t++) {
-    m->termEntry[t] = tEntry[sorted[t]];
-    m->termIdx[t] = tIdx[sorted[t]];
-  }
-  for (int64_t i = 0; i < n; i++) {
-    const int64_t len = m->rowStart[i + 1] - m->rowStart[i];
-    m->maxRow = std::max(m->maxRow, len);
-    if (len > kAssemblyLongRun) m->longRows.push_back((int32_t)i);
-  }
+  m->rows.build(T, n, [&](int32_t t) { return tRow[t]; }, [&](int32_t t) { return tEntry[t]; },
+                [&](int32_t t) { return tIdx[t]; }, true);
   return m;
 }
 

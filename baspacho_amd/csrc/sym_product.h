@@ -1,7 +1,7 @@
 // Products with a symmetric matrix given as coordinate entries, without its layout (DESIGN.md section
 // 21): y = A x straight from the entry values, and the gradient of the values of such a product.  The
 // map is built once on the host (this file, no device work); the kernels that use it are in
-// hip_sym_product_kernels.h, launched by hip_extensions.hip.
+// hip_ordered_sum.h, launched by hip_extensions.hip.
 //
 // CONVENTIONS.  A is n x n (n = the solver's order), given as entries (rows[k], cols[k], values[k]) in
 // the caller's scalar order, under the index rules of the assembly (assembly.h): an index out of range
@@ -22,35 +22,23 @@
 
 namespace BaSpaCho {
 
-class Solver;
-struct HipSymProductDev;  // the two parts of the map on the device (hip_extensions.hip), each uploaded on first use
-
 struct SymProductMap {
   const Solver* solver = nullptr;  // the solver the map was built for (its order, its stream)
   int32_t triangle = AssemblyLower;
   int64_t n = 0, nnz = 0, kept = 0;
-  int64_t maxRow = 0;  // most terms in one row
 
-  // row lists: the terms of row i are (termEntry[t], termIdx[t]), t in [rowStart[i], rowStart[i + 1]),
-  // in ascending entry index; longRows lists the rows with more than kAssemblyLongRun terms, which a
-  // whole wave sums
-  std::vector<int32_t> rowStart, termEntry, termIdx;
-  std::vector<int32_t> longRows;
+  // row lists: the terms of row i in ascending entry index, with the list of the long rows
+  RunList rows;
 
   // entry lists: (entRow[k], entCol[k]) of every entry, entRow[k] = -1 for a skipped one
   std::vector<int32_t> entRow, entCol;
 
-  mutable HipSymProductDev* dev = nullptr;
+  mutable HipEntryMapDevPtr dev;
 
-  SymProductMap() = default;
-  SymProductMap(const SymProductMap&) = delete;
-  SymProductMap& operator=(const SymProductMap&) = delete;
-  ~SymProductMap();
-
-  int64_t numTerms() const { return (int64_t)termEntry.size(); }
+  int64_t numTerms() const { return (int64_t)rows.entry.size(); }
   // bytes each part takes on the device once uploaded
-  int64_t rowDeviceBytes() const;
-  int64_t entryDeviceBytes() const;
+  int64_t rowDeviceBytes() const { return rows.deviceBytes(); }
+  int64_t entryDeviceBytes() const { return (int64_t)((entRow.size() + entCol.size()) * sizeof(int32_t)); }
 };
 
 // Builds the map of the entries (rows[k], cols[k]) for a matrix of order n; triangle as for
