@@ -464,6 +464,24 @@ class Solver:
         assert pos + 2 * nu == len(buf)
         return out
 
+    def _testFactorProductPlan(self):
+        """TESTING: the plan of mulL / mulLt (bsp_test_factor_product_plan, built on the host by the
+        function the products use).  {"partElems": int; int64 arrays "spanChainPtr", "spanChain",
+        "spanChainLump", "spanLong", "longRows", "smallColLump", "smallCol", "hugeSpans", "hugeWidePtr",
+        "hugeWide"; "tasks": {"dataOff", "lump", "w", "c0", "nc", "rBeg", "rEnd", "chain", "part"}, "folds":
+        {"col0", "nc", "part0", "numChunks"}: one int64 array per field}"""
+        buf = self._testRecords(lambda b, cap, need: self._lib.bsp_test_factor_product_plan(self._h, b, cap, need))
+        ns, nc, nl, nt, nf, nsm, part, nh, nhw = (int(x) for x in buf[:9])
+        out = self._testSplitRecords(buf, 9, [
+            ("spanChainPtr", ns + 1, None), ("spanChain", nc, None), ("spanChainLump", nc, None),
+            ("spanLong", ns, None), ("longRows", nl, None),
+            ("tasks", nt, ("dataOff", "lump", "w", "c0", "nc", "rBeg", "rEnd", "chain", "part")),
+            ("folds", nf, ("col0", "nc", "part0", "numChunks")),
+            ("smallColLump", nsm, None), ("smallCol", nsm, None),
+            ("hugeSpans", nh, None), ("hugeWidePtr", nh + 1, None), ("hugeWide", nhw, None)])
+        out["partElems"] = part
+        return out
+
     def _testRecords(self, call):
         need = ctypes.c_int64(0)
         _check(call(None, ctypes.c_int64(0), ctypes.byref(need)))
@@ -606,6 +624,44 @@ class Solver:
 
     def solveLt(self, mat, vec, stride=None, nRHS=1):
         self._solve("bsp_solve_lt_", mat, vec, stride, nRHS)
+
+    # ---- products with the factor -----------------------------------------
+    def _factor_product(self, what, which, L, x, out, stride, nRHS):
+        import torch
+        if out is None:
+            if isinstance(x, (list, tuple)):
+                out = [torch.empty_like(t) for t in x]
+            else:
+                out = torch.empty_like(x)
+        batched, (ls, xs, outs) = self._same_kind(what, "L, x and out", L, x, out)
+        for t in ls:
+            self._check_data(t)
+        if stride is None:
+            stride = self.order()
+        need = stride * (nRHS - 1) + self.order()
+        for t in xs + outs:
+            if nRHS >= 1 and t.numel() < need:
+                raise ValueError("%s: a vector block of %d elements is too short for nRHS = %d at stride %d"
+                                 % (what, t.numel(), nRHS, stride))
+        _call(self._lib, "bsp_factor_product_", batched, _suffix(ls[0]), self._h, _ptr_arg(ls, batched),
+              ctypes.c_int32(which), _ptr_arg(xs, batched), ctypes.c_int64(stride), _ptr_arg(outs, batched),
+              ctypes.c_int64(stride), ctypes.c_int32(nRHS), *_count(outs, batched))
+        return out
+
+    def mulL(self, L, x, out=None, stride=None, nRHS=1):
+        """extension: out = L x on the device (bsp_factor_product_*, which = 0).  `L`: a buffer in the
+        numeric layout, of which only the stored elements i >= j are read (a factor(), or any data); x
+        and out: order x nRHS, column-major with leading dimension `stride` (default order()), e.g.
+        tensors [nRHS, order], in internal order as for solve().  L and x are only read; every element
+        of out is written once, none is read (out=None: a new tensor like x).  Sums run in an order
+        fixed by the structure, without atomics: results are bitwise reproducible, column k is bitwise
+        the call on that column alone, and lists/tuples of tensors = a batch whose member q is bitwise
+        the single call.  Returns out."""
+        return self._factor_product("mulL", 0, L, x, out, stride, nRHS)
+
+    def mulLt(self, L, x, out=None, stride=None, nRHS=1):
+        """extension: out = L^T x on the device (bsp_factor_product_*, which = 1); arguments as mulL."""
+        return self._factor_product("mulLt", 1, L, x, out, stride, nRHS)
 
     def _solve_partial(self, which, mat, span_index, vec, stride, nrhs):
         if stride is None:

@@ -30,6 +30,14 @@ diagonal blocks; its backward is Solver.factorAdjoint on a clone of the incoming
 upper elements' gradient is ignored).  The half-solves' backward is one more half-solve and
 Solver.patternOuter: Lbar = -(L^-T g_y) y^T and Lbar = -x (L^-1 g_x)^T, on the elements with i >= j.
 
+Products with the factor, the inverse maps of the half-solves:
+
+    y = BA.mul_l(solver, L, x)                # y = L x, e.g. a sample x = mu + L z with covariance A
+    w = BA.mul_lt(solver, L, x)               # w = L^T x, e.g. the whitened residual L^T (x - mu)
+
+Their backward is the other product (xbar = L^T ybar, xbar = L ybar) and Solver.patternOuter: Lbar = ybar x^T
+and Lbar = x ybar^T, on the elements with i >= j.
+
 Through selected inversion:
 
     Z = BA.selected_inverse(solver, L)        # A^-1 on the pattern of L, for a factor L from cholesky()
@@ -52,7 +60,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 __all__ = ["solve", "logdet", "solve_logdet", "cholesky", "solve_l", "solve_lt", "selected_inverse", "factor_up_to",
-           "schur_complement", "solve_l_up_to"]
+           "schur_complement", "solve_l_up_to", "mul_l", "mul_lt"]
 
 
 class _OnCurrentStream:
@@ -364,6 +372,74 @@ def solve_lt(solver, L, b):
     _check_rhs(solver, L, b, "solve_lt")
     _check_device(solver, "solve_lt", L, b)
     return _HalfSolve.apply(solver, L, b, False)
+
+
+# ---- products with the factor: mul_l, mul_lt ---------------------------------
+def _product(solver, lower, L, vt):
+    """a fresh L vt (lower) or L^T vt ([.., k, n])"""
+    n, k = vt.shape[-1], vt.shape[-2]
+    sel = _members if L.dim() == 2 else (lambda t: t)
+    out = torch.empty_like(vt)
+    (solver.mulL if lower else solver.mulLt)(sel(L), sel(vt), out=sel(out), stride=n, nRHS=k)
+    return out
+
+
+class _FactorProduct(torch.autograd.Function):
+    """y = L x (lower = True) or y = L^T x (lower = False)"""
+
+    @staticmethod
+    def forward(ctx, solver, L, x, lower):
+        batched = L.dim() == 2
+        with _OnCurrentStream(solver, L.device):
+            L = L.detach().contiguous()
+            xt = _to_cols(x.detach(), batched)
+            yt = _product(solver, lower, L, xt)
+        ctx.solver, ctx.lower, ctx.x_shape = solver, lower, x.shape
+        ctx.save_for_backward(L, xt)
+        ctx.set_materialize_grads(False)
+        return _from_cols(yt, x.shape)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_y):
+        if g_y is None:
+            return None, None, None, None
+        solver = ctx.solver
+        L, xt = ctx.saved_tensors
+        batched = L.dim() == 2
+        need_L, need_x = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        grad_L = grad_x = None
+        if not (need_L or need_x):
+            return None, None, None, None
+        with _OnCurrentStream(solver, L.device):
+            gt = _to_cols(g_y, batched)
+            if need_x:  # xbar = L^T ybar (y = L x) or L ybar (y = L^T x)
+                grad_x = _from_cols(_product(solver, not ctx.lower, L, gt), ctx.x_shape)
+            if need_L:
+                grad_L = torch.empty_like(L)
+                # Lbar = ybar x^T (y = L x) or x ybar^T (y = L^T x), on the elements i >= j
+                U, V = (gt, xt) if ctx.lower else (xt, gt)
+                sel = _members if batched else (lambda t: t)
+                solver.patternOuter(sel(grad_L), sel(U), sel(V), nRHS=gt.shape[-2], alpha=1.0, stride=gt.shape[-1])
+        return None, grad_L, grad_x, None
+
+
+def mul_l(solver, L, x):
+    """y = L x for L in the solver's layout (the elements i >= j; e.g. from cholesky()), differentiable in
+    L and x (x as b for solve)"""
+    _check_data(solver, L, "mul_l")
+    _check_rhs(solver, L, x, "mul_l")
+    _check_device(solver, "mul_l", L, x)
+    return _FactorProduct.apply(solver, L, x, True)
+
+
+def mul_lt(solver, L, x):
+    """y = L^T x for L in the solver's layout (the elements i >= j; e.g. from cholesky()), differentiable
+    in L and x (x as b for solve), e.g. the whitened residual w = L^T (x - mu)"""
+    _check_data(solver, L, "mul_lt")
+    _check_rhs(solver, L, x, "mul_lt")
+    _check_device(solver, "mul_lt", L, x)
+    return _FactorProduct.apply(solver, L, x, False)
 
 
 # ---- through selected inversion (DESIGN.md section 19) ----------------------------------------------

@@ -10,6 +10,7 @@
 #include <unordered_set>
 
 #include "assembly.h"
+#include "factor_product_plan.h"
 #include "normal_eq.h"
 #include "sym_product.h"
 #include "reach.h"
@@ -627,6 +628,47 @@ static std::vector<int64_t> hostIds(const char* what, const char* name, const in
 BSP_REACH_API(f64, double)
 BSP_REACH_API(f32, float)
 #undef BSP_REACH_API
+
+// ---- products with the factor -------------------------------------------------------------------------
+// which = 0: mulL, 1: mulLt, on one member (L, In, Out pointers) or a batch (vectors of them)
+template <typename L, typename In, typename Out>
+static void factorProduct(bsp_solver* s, const L& l, int32_t which, const In& in, int64_t inStride, const Out& out,
+                          int64_t outStride, int32_t nrhs) {
+  if (which == 0) {
+    s->solver->mulL(l, in, inStride, out, outStride, nrhs);
+  } else if (which == 1) {
+    s->solver->mulLt(l, in, inStride, out, outStride, nrhs);
+  } else {
+    throw std::runtime_error("factorProduct: which = " + std::to_string(which) + " is neither 0 (L x) nor 1 (L^T x)");
+  }
+}
+template <typename T>
+static void factorProductBatched(bsp_solver* s, const T* const* l, int32_t which, const T* const* in, int64_t inStride,
+                                 T* const* out, int64_t outStride, int32_t nrhs, int32_t batch) {
+  const char* what = "factorProduct";
+  const std::vector<T*> o = hostArray<T*>(what, "output", out, batch);
+  const std::vector<T*> i = hostArray<T*>(what, "input", in, batch);
+  factorProduct(s, hostArray<T*>(what, "factor", l, batch), which, i, inStride, o, outStride, nrhs);
+}
+#define BSP_FACTOR_PRODUCT_API(SFX, T)                                                                           \
+  int bsp_factor_product_##SFX(bsp_solver* s, const T* l, int32_t which, const T* in, int64_t in_stride, T* out, \
+                               int64_t out_stride, int32_t nrhs)                                                 \
+      BSP_BODY(factorProduct(s, l, which, in, in_stride, out, out_stride, nrhs))                                 \
+  int bsp_factor_product_batched_##SFX(bsp_solver* s, const T* const* l, int32_t which, const T* const* in,      \
+                                       int64_t in_stride, T* const* out, int64_t out_stride, int32_t nrhs,       \
+                                       int32_t batch)                                                            \
+      BSP_BODY(factorProductBatched<T>(s, l, which, in, in_stride, out, out_stride, nrhs, batch))
+BSP_FACTOR_PRODUCT_API(f64, double)
+BSP_FACTOR_PRODUCT_API(f32, float)
+#undef BSP_FACTOR_PRODUCT_API
+
+int bsp_test_factor_product_plan(const bsp_solver* s, int64_t* buf, int64_t capacity, int64_t* needed) {
+  BSP_TRY
+  const std::vector<int64_t> out = factorProductPlanRecords(buildFactorProductPlan(s->solver->skel()));
+  *needed = (int64_t)out.size();
+  if (buf != nullptr) std::copy(out.begin(), out.begin() + std::min(capacity, *needed), buf);
+  BSP_CATCH
+}
 
 // the reach plan of `params` (caller's ids) with one Gram item per pair i >= j of them
 int bsp_test_reach_plan(const bsp_solver* s, int64_t num_params, const int64_t* params, int64_t* buf,

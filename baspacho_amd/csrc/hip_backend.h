@@ -211,6 +211,15 @@ void hipBackendGramBlocks(SymbolicCtx& sym, const ReachPlan& plan, const T* W, T
 template <typename T>
 T* hipBackendReachWorkspace(SymbolicCtx& sym, int64_t elems);
 
+// Products with the factor (hip_factor_product.h): y[q] = L[q] x[q], or L[q]^T x[q]
+// when `transposed`.  L[q] is a buffer in the numeric layout of which the elements i >= j are read; x[q]
+// and y[q] are order x nRHS, column-major with leading dimensions ldx and ldy, in internal order.  Every
+// element of y is written once, none is read; sums run in an order fixed by the skeleton, without
+// atomics.  The plan (factor_product_plan.h) is built and uploaded by the first call.
+template <typename T>
+void hipBackendFactorProduct(SymbolicCtx& sym, const T* const* L, bool transposed, const T* const* x, int64_t ldx,
+                             T* const* y, int64_t ldy, int nRHS, int64_t batch, bool single);
+
 HipPlanStats hipBackendPlanStats(SymbolicCtx& sym, int64_t startLump, int64_t upToLump);
 
 // TESTING (host only): the launch tables (buildLaunchTables, hip_plan.h) and the solve schedule of the

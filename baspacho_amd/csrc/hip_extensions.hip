@@ -1,11 +1,12 @@
 // MI355X backend, the extension operations of hip_backend.h: selected inversion and its adjoint,
 // log-det and gradients on the pattern of L, factor status and damping, the reverse-mode sweep of the
-// factor, the dense Schur complement, assembly of coordinate entries, normal equations and products
-// with a matrix given as entries.  Every
+// factor, the dense Schur complement, assembly of coordinate entries, normal equations, products
+// with a matrix given as entries and products with the factor.  Every
 // entry point stages its pointer arguments, splits the batch into chunks and enqueues the launches
 // of a chunk on the execution stream (the call path: HipSymbolicCtx::stage / forChunks).
 #include "hip_context.h"
 #include "hip_chol_adjoint_kernels.h"
+#include "hip_factor_product.h"
 #include "hip_grad_kernels.h"
 #include "hip_ordered_sum.h"
 #include "hip_reach_kernels.h"
@@ -225,6 +226,49 @@ struct ReachDev {
   }
 };
 
+// Products with the factor (hip_factor_product.h): the plan of the structure on
+// the device, and the partial sums of the split strips of y = L^T x, partElems per (member of a chunk,
+// right-hand side)
+struct FactorProductState {
+  FactorProductPlan host;
+  DevBuf spanChainPtr, spanChain, spanChainLump, rowToSpan, spanLong, longRows, hugeSpans, hugeWidePtr, hugeWide,
+      ltTasks, ltFolds, smallColLump, smallCol, part;
+  int64_t partSlabs = 0;
+  void build(const CoalescedBlockMatrixSkel& sk) {
+    host = buildFactorProductPlan(sk);
+    spanChainPtr.upload(host.spanChainPtr);
+    spanChain.upload(host.spanChain);
+    spanChainLump.upload(host.spanChainLump);
+    rowToSpan.upload(host.rowToSpan);
+    spanLong.upload(host.spanLong);
+    longRows.upload(host.longRows);
+    hugeSpans.upload(host.hugeSpans);
+    hugeWidePtr.upload(host.hugeWidePtr);
+    hugeWide.upload(host.hugeWide);
+    ltTasks.upload(host.ltTasks);
+    ltFolds.upload(host.ltFolds);
+    smallColLump.upload(host.smallColLump);
+    smallCol.upload(host.smallCol);
+  }
+  hipk::FactorProductDev dev() const {
+    return {spanChainPtr.as<int32_t>(), spanChain.as<int32_t>(), spanChainLump.as<int32_t>(),
+            rowToSpan.as<int32_t>(),    spanLong.as<int32_t>(),  longRows.as<int32_t>(),
+            hugeSpans.as<int32_t>(),    hugeWidePtr.as<int32_t>(), hugeWide.as<int32_t>(),
+            ltTasks.as<LtTask>(),       ltFolds.as<LtFold>(),    smallColLump.as<int32_t>(),
+            smallCol.as<int32_t>()};
+  }
+  // room for the partial sums of n (member, right-hand side) pairs, sized in fp64.  Growing waits for
+  // the kernels queued by earlier calls, as the other scratch does
+  void reservePart(int64_t n) {
+    if (n <= partSlabs || host.partElems == 0) return;
+    if (partSlabs > 0) hipCHECK(hipDeviceSynchronize());
+    partSlabs = 0;
+    part.release();
+    part.resize((size_t)(host.partElems * n) * sizeof(double));
+    partSlabs = n;
+  }
+};
+
 // several host tables as one blob, every table at a multiple of 16 bytes
 struct TableBlob {
   vector<char> bytes;
@@ -251,6 +295,7 @@ struct hipb::ExtensionState {
   SelInvScratch selinvScratch;
   std::unique_ptr<GradDev> grad;      // work lists of logDet / patternGrad, built on first use
   ReachDev reach;
+  std::unique_ptr<FactorProductState> factorProduct;  // plan of mulL / mulLt, built on first use
 };
 void hipb::ExtensionStateDelete::operator()(ExtensionState* p) const { delete p; }
 
@@ -864,6 +909,70 @@ T* hipBackendReachWorkspace(SymbolicCtx& sym, int64_t elems) {
   return reinterpret_cast<T*>(extState(h).reach.reserve((size_t)std::max<int64_t>(elems, 1) * sizeof(T)));
 }
 
+// ---- products with the factor (hip_factor_product.h) ---------------------------
+// y[q] = L[q] x[q] (transposed: L[q]^T x[q]) for `batch` members.  The plan is built and uploaded by the
+// first product, whichever it is.  A chunk is one launch (two when y = L x has huge spans or y = L^T x
+// has split strips), members on
+// gridDim.y and groups of right-hand sides on gridDim.z; chunks are bounded by the partial sums they need
+template <typename T>
+void hipBackendFactorProduct(SymbolicCtx& sym, const T* const* L, bool transposed, const T* const* x, int64_t ldx,
+                             T* const* y, int64_t ldy, int nRHS, int64_t batch, bool single) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  ExtensionState& ext = extState(h);
+  if (!ext.factorProduct) {
+    std::unique_ptr<FactorProductState> p(new FactorProductState);
+    p->build(h.skel);
+    ext.factorProduct = std::move(p);
+  }
+  FactorProductState& st = *ext.factorProduct;
+  const int64_t order = h.skel.order();
+  if (order == 0) return;
+  BASPACHO_CHECK_LE(nRHS, 65535);
+  const hipk::SkelDev sk = h.skelDev();
+  const hipk::FactorProductDev pl = st.dev();
+  const unsigned zGroups = (unsigned)((nRHS + hipk::kFpRhs - 1) / hipk::kFpRhs);
+  // members per chunk: at most 256 MB of partial sums (fp64), at least one member
+  int64_t chunk = std::min(batch, HipSymbolicCtx::kMaxGridY);
+  if (transposed && st.host.partElems > 0) {
+    const int64_t perMember = st.host.partElems * nRHS * (int64_t)sizeof(double);
+    chunk = std::max<int64_t>(1, std::min(chunk, ((int64_t)256 << 20) / perMember));
+    st.reservePart(chunk * nRHS);
+  }
+  const BatchPtrs<const T> ls = h.stage(L, batch, single), xs = h.stage(x, batch, single);
+  const BatchPtrs<T> ys = h.stage(y, batch, single);
+  const int64_t shortWgs = (order + hipk::kFpThreads - 1) / hipk::kFpThreads;
+  const int64_t numLong = (int64_t)st.host.longRows.size();
+  const int64_t longWgs = (numLong + hipk::kFpWaves - 1) / hipk::kFpWaves;
+  const int64_t numTasks = (int64_t)st.host.ltTasks.size(), numSmall = (int64_t)st.host.smallCol.size();
+  const int64_t smallWgs = (numSmall + hipk::kFpThreads - 1) / hipk::kFpThreads;
+  const int64_t numFolds = (int64_t)st.host.ltFolds.size(), numHuge = (int64_t)st.host.hugeSpans.size();
+  BASPACHO_CHECK_LT(shortWgs + longWgs, (int64_t)INT32_MAX);
+  BASPACHO_CHECK_LT(numTasks + smallWgs, (int64_t)INT32_MAX);
+  h.forChunks(batch, chunk, [&](int64_t q0, unsigned nm) {
+    const hipk::FactorProductArgs<T> a{ls.at(q0), xs.at(q0), ys.at(q0), ldx, ldy, (int32_t)nRHS};
+    if (!transposed) {
+      hipk::factorProductLx<T><<<dim3((unsigned)(shortWgs + longWgs), nm, zGroups), hipk::kFpThreads, 0, stream>>>(
+          pl, sk, (int32_t)order, (int32_t)shortWgs, (int32_t)numLong, a);
+      if (numHuge > 0) {
+        hipk::factorProductLxSpans<T><<<dim3((unsigned)numHuge, nm, zGroups), hipk::kFpSpanThreads, 0, stream>>>(pl, sk,
+                                                                                                                a);
+      }
+      return;
+    }
+    T* part = reinterpret_cast<T*>(st.part.ptr);
+    hipk::factorProductLt<T><<<dim3((unsigned)(numTasks + smallWgs), nm, zGroups), hipk::kFpThreads, 0, stream>>>(
+        pl, sk, (int32_t)numTasks, (int32_t)numSmall, a, part, st.host.partElems);
+    if (numFolds > 0) {
+      hipk::factorProductLtFold<T><<<dim3((unsigned)((numFolds * 64 + hipk::kFpThreads - 1) / hipk::kFpThreads), nm,
+                                          (unsigned)nRHS),
+                                     hipk::kFpThreads, 0, stream>>>(pl.ltFolds, (int32_t)numFolds, a.y, ldy,
+                                                                    (int32_t)nRHS, part, st.host.partElems);
+    }
+  });
+}
+
 #define BSP_INSTANTIATE_EXTENSIONS(T)                                                                            \
   template void hipBackendSelectedInverse<T>(SymbolicCtx&, T* const*, int64_t, bool);                           \
   template void hipBackendLogDet<T>(SymbolicCtx&, const T* const*, int64_t, bool, T*);                          \
@@ -884,7 +993,9 @@ T* hipBackendReachWorkspace(SymbolicCtx& sym, int64_t elems) {
                                         const T* const*, T* const*, int64_t, int64_t, bool);                    \
   template void hipBackendReachSolveL<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                         \
   template void hipBackendGramBlocks<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                          \
-  template T* hipBackendReachWorkspace<T>(SymbolicCtx&, int64_t);
+  template T* hipBackendReachWorkspace<T>(SymbolicCtx&, int64_t);                                               \
+  template void hipBackendFactorProduct<T>(SymbolicCtx&, const T* const*, bool, const T* const*, int64_t,       \
+                                           T* const*, int64_t, int, int64_t, bool);
 BSP_INSTANTIATE_EXTENSIONS(double)
 BSP_INSTANTIATE_EXTENSIONS(float)
 #undef BSP_INSTANTIATE_EXTENSIONS

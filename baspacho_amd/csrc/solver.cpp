@@ -1118,8 +1118,56 @@ void Solver::inverseBlocks(const T* L, const std::vector<int64_t>& rowParams, co
   hipBackendGramBlocks<T>(*symCtx, plan, W, out);
 }
 
+// ---- products with the factor ------------------------------------------------
+template <typename T>
+static void runFactorProduct(const Solver& s, SymbolicCtx& sym, bool single, const char* what, bool transposed,
+                             const std::vector<T*>& L, const std::vector<T*>& x, int64_t inStride,
+                             const std::vector<T*>& y, int64_t outStride, int nRHS) {
+  if (y.empty()) throw std::runtime_error(std::string(what) + ": the batch is empty");
+  checkMembers(what, "output", y, y.size());
+  checkMembers(what, "input", x, y.size());
+  checkMembers(what, "factor", L, y.size());
+  if (nRHS < 1) throw std::runtime_error(std::string(what) + ": nRHS = " + std::to_string(nRHS) + " < 1");
+  if (nRHS > 65535) throw std::runtime_error(std::string(what) + ": nRHS = " + std::to_string(nRHS) + " > 65535");
+  if (inStride < s.order() || outStride < s.order()) {
+    throw std::runtime_error(std::string(what) + ": stride " + std::to_string(std::min(inStride, outStride)) +
+                             " < order " + std::to_string(s.order()));
+  }
+  const std::vector<const T*> ls = constView(L), xs = constView(x);
+  const size_t outBytes = (size_t)(outStride * (nRHS - 1) + s.order()) * sizeof(T);
+  checkNoOverlap(what, y, outBytes, xs, (size_t)(inStride * (nRHS - 1) + s.order()) * sizeof(T));
+  checkNoOverlap(what, y, outBytes, ls, (size_t)s.dataSize() * sizeof(T));
+  hipBackendFactorProduct<T>(sym, ls.data(), transposed, xs.data(), inStride, y.data(), outStride, nRHS,
+                             (int64_t)y.size(), single);
+}
+
+template <typename T>
+void Solver::mulL(const T* L, const T* x, int64_t inStride, T* y, int64_t outStride, int nRHS) const {
+  runFactorProduct(*this, *symCtx, true, "mulL", false, one(L), one(x), inStride, one(y), outStride, nRHS);
+}
+template <typename T>
+void Solver::mulL(const std::vector<T*>& L, const std::vector<T*>& x, int64_t inStride, const std::vector<T*>& y,
+                  int64_t outStride, int nRHS) const {
+  runFactorProduct(*this, *symCtx, false, "mulL", false, L, x, inStride, y, outStride, nRHS);
+}
+template <typename T>
+void Solver::mulLt(const T* L, const T* x, int64_t inStride, T* y, int64_t outStride, int nRHS) const {
+  runFactorProduct(*this, *symCtx, true, "mulLt", true, one(L), one(x), inStride, one(y), outStride, nRHS);
+}
+template <typename T>
+void Solver::mulLt(const std::vector<T*>& L, const std::vector<T*>& x, int64_t inStride, const std::vector<T*>& y,
+                   int64_t outStride, int nRHS) const {
+  runFactorProduct(*this, *symCtx, false, "mulLt", true, L, x, inStride, y, outStride, nRHS);
+}
+
 // one single / batch pair per operation
 #define BSP_INSTANTIATE_EXTENSIONS(T)                                                                          \
+  template void Solver::mulL<T>(const T*, const T*, int64_t, T*, int64_t, int) const;                          \
+  template void Solver::mulL<T>(const std::vector<T*>&, const std::vector<T*>&, int64_t,                       \
+                                const std::vector<T*>&, int64_t, int) const;                                   \
+  template void Solver::mulLt<T>(const T*, const T*, int64_t, T*, int64_t, int) const;                         \
+  template void Solver::mulLt<T>(const std::vector<T*>&, const std::vector<T*>&, int64_t,                      \
+                                 const std::vector<T*>&, int64_t, int) const;                                  \
   using BspVec_##T = const std::vector<T*>&;                                                                   \
   using BspCVec_##T = const std::vector<const T*>&;                                                            \
   template void Solver::selectedInverse<T>(T*) const;                                                          \

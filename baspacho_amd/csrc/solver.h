@@ -276,6 +276,27 @@ class Solver {
   ReachPlan reachPlan(const char* what, const std::vector<int64_t>& params, const std::vector<int64_t>& pairRow,
                       const std::vector<int64_t>& pairCol, const std::vector<int64_t>& outOffsets = {}) const;
 
+  // extension: products with the factor (hip_factor_product.h).  mulL: y = L x,
+  // mulLt: y = L^T x, L the lower triangle of `L`: a buffer in this Solver's numeric layout of which only
+  // the stored elements i >= j are read (a factor(), or any other data).  x and y are order() x nRHS,
+  // column-major with leading dimensions inStride and outStride, in internal order (as for solve()).  x
+  // and L are only read; every element of y is written exactly once and none is read.  Sums run in an
+  // order fixed by the structure, without atomics: two runs are bitwise equal, column k of a call is
+  // bitwise the call on that column alone, member q of a batch is bitwise the single call.  Both run on
+  // the stream of setStream() without host synchronisation (the first call uploads the plan).  Refused
+  // before any device work: NULL pointers, an empty batch, nRHS < 1, a stride below order(), an output
+  // that overlaps an input or another output.
+  template <typename T>
+  void mulL(const T* L, const T* x, int64_t inStride, T* y, int64_t outStride, int nRHS) const;
+  template <typename T>
+  void mulL(const std::vector<T*>& L, const std::vector<T*>& x, int64_t inStride, const std::vector<T*>& y,
+            int64_t outStride, int nRHS) const;
+  template <typename T>
+  void mulLt(const T* L, const T* x, int64_t inStride, T* y, int64_t outStride, int nRHS) const;
+  template <typename T>
+  void mulLt(const std::vector<T*>& L, const std::vector<T*>& x, int64_t inStride, const std::vector<T*>& y,
+             int64_t outStride, int nRHS) const;
+
   // scalarPermutation()[i] = internal index of the caller's scalar i (params in param order, each
   // at the start of its span)
   std::vector<int64_t> scalarPermutation() const;

@@ -7,6 +7,8 @@
     x, ld = S.solve_logdet(pat, values, b)         # both, one factor
     data = S.assemble(pat, values)                 # the solver's layout, for baspacho_amd.autograd
     x = S.sample(pat, values, z, mu)               # x = mu + L^-T z: Cov(x) = A^-1
+    w = S.whiten(pat, values, x, mu)               # w = L^T (x - mu): |w|^2 = (x - mu)^T A (x - mu); undoes sample
+    x = S.sample_cov(pat, values, z, mu)           # x = mu + L z: Cov(x) = A
     c = S.covariance(pat, values)                  # (A^-1)[rows[k], cols[k]] for every entry k
     v = S.marginal_variances(pat, values)          # diag(A^-1) in the caller's order
     c = S.cross_covariance(pat, values, i, j)      # (A^-1)[i[k], j[k]] for ANY scalar pairs, on or off the pattern
@@ -27,7 +29,8 @@
 The matrix is given by entries (rows[k], cols[k], values[k]) in the caller's scalar order: A_ij = A_ji =
 the sum of the values of the entries at (i, j), i >= j.  `values` is [nnz] or a
 batch [B, nnz] of matrices of one pattern; `b` and `x` are in the caller's order, [n] or [n, k], with a
-leading B when batched.  Gradients go to `values` and `b` (and to `z` and `mu` for sample).
+leading B when batched.  Gradients go to `values` and `b` (and to `z` / `x` and `mu` for sample, whiten
+and sample_cov, whose products with the factor are DESIGN.md section 22).
 
 Each function composes the assembly kernel (whose backward is its adjoint), baspacho_amd.autograd's
 solve / logdet / solve_logdet and a permutation of the vectors.  Everything runs on
@@ -71,7 +74,7 @@ from .autograd import _OnCurrentStream
 __all__ = ["SymmetricPattern", "JacobianPattern", "assemble", "solve", "logdet", "solve_logdet", "sample", "marginalize",
            "covariance", "marginal_variances", "cross_covariance", "joint_covariance",
            "hessian", "jt_vec", "j_vec", "normal_equations", "lstsq", "check_positive_definite",
-           "matvec", "quad_form", "log_prob", "solve_refined"]
+           "matvec", "quad_form", "log_prob", "solve_refined", "whiten", "sample_cov"]
 
 
 def _host_i64(a):
@@ -359,6 +362,37 @@ def sample(pattern, values, z, mu=None):
             raise ValueError("sample: mu must be a tensor of z's shape %s" % (tuple(z.shape),))
     L = _ag.cholesky(pattern.solver, assemble(pattern, values))
     x = pattern.fromInternal(_ag.solve_lt(pattern.solver, L, pattern.toInternal(z, dim)), dim)
+    return x if mu is None else mu + x
+
+
+def _check_mu(z, mu, what, name):
+    if mu is not None:
+        if not isinstance(mu, torch.Tensor) or mu.shape != z.shape:
+            raise ValueError("%s: mu must be a tensor of %s's shape %s" % (what, name, tuple(z.shape)))
+
+
+def whiten(pattern, values, x, mu=None):
+    """w = P^T L^T P (x - mu) in the caller's order, P and L as for sample: the whitened residual of the
+    Gaussian with precision A(values), so that w.square().sum(-1) (over the n scalars) is the quadratic
+    form (x - mu)^T A (x - mu), and whiten(sample(z, mu), mu) = z.  x (and mu) are shaped like solve's b;
+    differentiable in values, x and mu"""
+    _check_values(pattern, values, "whiten")
+    dim = _check_b(pattern, values, x, "whiten")
+    _check_mu(x, mu, "whiten", "x")
+    L = _ag.cholesky(pattern.solver, assemble(pattern, values))
+    r = x if mu is None else x - mu
+    return pattern.fromInternal(_ag.mul_lt(pattern.solver, L, pattern.toInternal(r, dim)), dim)
+
+
+def sample_cov(pattern, values, z, mu=None):
+    """x = mu + P^T L (P z) in the caller's order, P and L as for sample, so that Cov(x) = A for z ~ N(0, I):
+    a sample of the Gaussian whose COVARIANCE is the sparse matrix.  z (and mu) are shaped like solve's b;
+    differentiable in values, z and mu"""
+    _check_values(pattern, values, "sample_cov")
+    dim = _check_b(pattern, values, z, "sample_cov")
+    _check_mu(z, mu, "sample_cov", "z")
+    L = _ag.cholesky(pattern.solver, assemble(pattern, values))
+    x = pattern.fromInternal(_ag.mul_l(pattern.solver, L, pattern.toInternal(z, dim)), dim)
     return x if mu is None else mu + x
 
 

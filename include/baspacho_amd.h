@@ -283,6 +283,30 @@ int bsp_inverse_blocks_f64(bsp_solver* s, const double* dev_l, int64_t num_pairs
                            const int64_t* col_params, double* dev_out, const int64_t* out_offsets);
 int bsp_inverse_blocks_f32(bsp_solver* s, const float* dev_l, int64_t num_pairs, const int64_t* row_params,
                            const int64_t* col_params, float* dev_out, const int64_t* out_offsets);
+/* Extension (no counterpart in the reference): products with the factor.
+   dev_out = L dev_in (which = 0) or L^T dev_in (which = 1), L the lower triangle of dev_l: a buffer in
+   this solver's numeric layout of which only the stored elements i >= j are read (the strictly-upper
+   elements of the diagonal blocks never are); it need not hold a factor.  dev_in and dev_out are
+   bsp_order x nrhs, column-major with leading dimensions in_stride and out_stride, in internal order,
+   as for bsp_solve_*.  dev_l and dev_in are only read; every element of dev_out is written exactly
+   once and none is read (no memset needed; the padding between columns is left alone).  Every sum runs
+   in an order fixed by the structure, without atomics: two runs are bitwise equal, column k of a call
+   is bitwise the call on that column alone, member q of a batch is bitwise the single call.  Runs on
+   the bsp_set_stream stream without host synchronisation; the first call builds and uploads the plan,
+   and a y = L^T x call that needs more room for partial sums than any before waits for the device.
+   Batched forms: HOST arrays of `batch` device pointers.  Non-zero return before any device work: a
+   NULL pointer, an empty batch, which not 0 or 1, nrhs < 1 (or > 65535), a stride below bsp_order, an
+   output that overlaps an input (dev_in == dev_out included) or another output. */
+int bsp_factor_product_f64(bsp_solver* s, const double* dev_l, int32_t which, const double* dev_in, int64_t in_stride,
+                           double* dev_out, int64_t out_stride, int32_t nrhs);
+int bsp_factor_product_f32(bsp_solver* s, const float* dev_l, int32_t which, const float* dev_in, int64_t in_stride,
+                           float* dev_out, int64_t out_stride, int32_t nrhs);
+int bsp_factor_product_batched_f64(bsp_solver* s, const double* const* dev_l, int32_t which,
+                                   const double* const* dev_in, int64_t in_stride, double* const* dev_out,
+                                   int64_t out_stride, int32_t nrhs, int32_t batch);
+int bsp_factor_product_batched_f32(bsp_solver* s, const float* const* dev_l, int32_t which,
+                                   const float* const* dev_in, int64_t in_stride, float* const* dev_out,
+                                   int64_t out_stride, int32_t nrhs, int32_t batch);
 /* Extension (no counterpart in the reference): gradients on the block pattern of L, for autograd
    (DESIGN.md section 13).  Data is this solver's numeric layout and vectors are in its internal order,
    as for bsp_solve_*.  A(d) is the symmetric matrix with A_ij = A_ji = d_e for every stored element

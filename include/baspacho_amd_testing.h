@@ -46,6 +46,20 @@ int bsp_test_selinv_plan_up_to(const bsp_solver* s, int64_t span, int64_t* buf, 
 int bsp_test_reach_plan(const bsp_solver* s, int64_t num_params, const int64_t* params, int64_t* buf,
                         int64_t capacity, int64_t* needed);
 
+/* The plan of the products with the factor (buildFactorProductPlan, csrc/factor_product_plan.cpp: the
+ * plan bsp_factor_product_* run), built on the host with no device involved.  Layout (int64):
+ *   nSpans, nChains, nLongRows, nTasks, nFolds, nSmallCols, partElems, nHugeSpans, nHugeWide,
+ *   spanChainPtr (nSpans + 1), spanChain (nChains: the chains sorted by row span), spanChainLump (nChains:
+ *   the column lump of each), spanLong (nSpans: 0 = rows one per lane, 1 = one per wave, 2 = the span per
+ *   workgroup), longRows (nLongRows: the rows of the spans of kind 1),
+ *   nTasks records {dataOff, lump, w, c0, nc, rBeg, rEnd, chain, part},
+ *   nFolds records {col0, nc, part0, numChunks},
+ *   smallColLump (nSmallCols), smallCol (nSmallCols),
+ *   hugeSpans (nHugeSpans: the spans of kind 2), hugeWidePtr (nHugeSpans + 1), hugeWide (nHugeWide: positions
+ *   in spanChain of the chains of lumps of more than 16 columns, per huge span).
+ * buf / capacity / needed as bsp_test_selinv_plan. */
+int bsp_test_factor_product_plan(const bsp_solver* s, int64_t* buf, int64_t capacity, int64_t* needed);
+
 /* The launch tables of the factor plan over every lump (buildLaunchTables, csrc/hip_plan.cpp: what the
  * launch code uploads beside the plan), built on the host with no device involved.  Layout (int64):
  *   nLevels, nMainLevels, nLevelPanels, nTrsmTasks, nUpdTasks (of the plan), then the lengths of
