@@ -841,6 +841,107 @@ class Solver:
 
         return decode(w) if w.ndim == 1 else [decode(r) for r in w]
 
+    # ---- error bounds; none of these is differentiable -------------------
+    def _col_reduce(self, what, fn, a, b, batched):
+        import torch
+        ts = [a] if b is None else [a, b]
+        for t in ts:
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s: expected torch.Tensors, got %s" % (what, type(t).__name__))
+            _ptr_of(t)
+        batched = bool(batched) or a.dim() == 3
+        if b is not None and (b.shape != a.shape or b.dtype != a.dtype or b.device != a.device):
+            raise ValueError("%s: the operands differ: %s %s on %s and %s %s on %s" % (
+                what, tuple(a.shape), a.dtype, a.device, tuple(b.shape), b.dtype, b.device))
+        lo = 1 if batched else 0
+        if a.dim() not in (lo + 1, lo + 2):
+            raise ValueError("%s: expected %s, got shape %s" % (
+                what, "[B, n] or [B, n, q]" if batched else "[n] or [n, q]", tuple(a.shape)))
+        if batched and a.shape[0] == 0:
+            raise ValueError("%s: empty batch" % what)
+        has_q = a.dim() == lo + 2
+        n, q = a.shape[lo], (a.shape[-1] if has_q else 1)
+        if q < 1:
+            raise ValueError("%s: no columns" % what)
+        out = torch.empty(tuple(a.shape[:lo]) + ((q,) if has_q else ()), dtype=torch.float64, device=a.device)
+        ptrs = [_ptr_arg(t.unbind(0) if batched else [t], batched) for t in ts]
+        _call(self._lib, fn, batched, _suffix(a), self._h, *ptrs, ctypes.c_int64(n), ctypes.c_int64(q),
+              ctypes.c_void_p(_ptr_of(out)), *_count(a, batched))
+        return out
+
+    def maxRatio(self, r, d, batched=False):
+        """extension: max_i ratio(|r[i, j]|, d[i, j]) per column as a float64 device tensor (bsp_max_ratio_*):
+        r and d [n] -> [], [n, q] -> [q], with a leading B when `batched` (three dimensions always are a
+        batch).  ratio is 0 when r == 0 and +inf when d == 0 and r != 0; a NaN in either operand makes the
+        column's result NaN.  Computed in double for both precisions, two passes, no atomics; bitwise the
+        numpy statement.  Enqueued on the solver's stream; the first call that needs more partials than any
+        before on this Solver allocates them, which waits for the device, later ones do not synchronise."""
+        return self._col_reduce("maxRatio", "bsp_max_ratio_", r, d, batched)
+
+    def colMax(self, a, batched=False):
+        """extension: max_i a[i, j] per column as a float64 device tensor, NaN if any element is, -inf for no
+        rows (bsp_col_max_*); shapes as for maxRatio."""
+        return self._col_reduce("colMax", "bsp_col_max_", a, None, batched)
+
+    NORM_EST_STOPS = ("none", "order one", "repeated sign vector", "no increase", "pass limit", "same column",
+                      "non-finite")
+
+    def invNorm1(self, L, scale=None, return_state=False):
+        """extension: an estimate of ||A^-1||_1 for the matrix whose complete factor() is `L`, as a float64
+        device tensor [] (a list/tuple of factors = a batch: [B]); with scale = D (a device vector of order()
+        values in INTERNAL order, or a list of them) of ||D A^-1 D||_1 (bsp_inv_norm1_*).  Hager's estimator
+        in Higham's form: a lower bound, almost always within a factor 3.  A fixed schedule of 10 solve()
+        calls with one right-hand side on the solver's stream, nothing read back; the workspace is kept with
+        this Solver and allocated by the first call of a size.  return_state=True: (estimate, state), state
+        the int64 device record [12] / [B, 12] that readNormEstState() decodes.  A factor that broke down
+        gives a non-finite estimate.  Not differentiable."""
+        import torch
+        what = "invNorm1"
+        if scale is None:
+            batched, (ls,) = self._same_kind(what, "L", L)
+            ds = None
+        else:
+            batched, (ls, ds) = self._same_kind(what, "L and scale", L, scale)
+            for t in ds:
+                if t.numel() != self.order():
+                    raise ValueError("%s: scale has %d elements, the order is %d" % (what, t.numel(), self.order()))
+        for t in ls:
+            self._check_data(t)
+        sfx, dev, nb = _suffix(ls[0]), ls[0].device, len(ls)
+        need = ctypes.c_int64(0)
+        _check(getattr(self._lib, "bsp_inv_norm1_work_bytes_" + sfx)(self._h, ctypes.byref(need)))
+        # one workspace per Solver, grown to the largest need so far
+        work = getattr(self, "_norm_est_work", None)
+        if work is None or work.device != dev or work.numel() < need.value * nb + 16:
+            work = self._norm_est_work = torch.empty(need.value * nb + 16, dtype=torch.uint8, device=dev)
+        wptr = (work.data_ptr() + 15) // 16 * 16
+        state = torch.empty((nb, 12) if batched else (12,), dtype=torch.int64, device=dev)
+        out = torch.empty((nb,) if batched else (), dtype=torch.float64, device=dev)
+        _call(self._lib, "bsp_inv_norm1_", batched, sfx, self._h, _ptr_arg(ls, batched), _ptr_arg(ds, batched),
+              ctypes.c_void_p(wptr), ctypes.c_void_p(_ptr_of(state)), ctypes.c_void_p(_ptr_of(out)),
+              *_count(ls, batched))
+        return (out, state) if return_state else out
+
+    def readNormEstState(self, t):
+        """the state record(s) of invNorm1(return_state=True) decoded on the host (this synchronises, like
+        readFactorStatus).  A dict {est, j, passes, stop, stopReason, altWon, js, alt}, or a list of them for
+        [B, 12]: est the estimate, passes how many vectors were measured (1 .. 5), stop the reason code and
+        stopReason its name (NORM_EST_STOPS), altWon whether the alternating vector's value won, js the j
+        chosen after every pass (internal scalars), alt the alternating vector's value."""
+        if t.is_cuda:
+            self._torch_stream(t.device).synchronize()
+        w = t.detach().cpu().numpy().astype(np.int64)
+        if w.ndim not in (1, 2) or w.shape[-1] != 12:
+            raise ValueError("readNormEstState: expected an int64 tensor [12] or [B, 12], got shape %s" % (w.shape,))
+
+        def decode(r):
+            f = r.copy().view(np.float64)
+            return {"est": float(f[0]), "j": int(r[1]), "passes": int(r[2]), "stop": int(r[3]),
+                    "stopReason": self.NORM_EST_STOPS[int(r[3])], "altWon": bool(r[4]),
+                    "js": [int(x) for x in r[5:10] if x >= 0], "alt": float(f[10])}
+
+        return decode(w) if w.ndim == 1 else [decode(r) for r in w]
+
     def dampDiagonal(self, data, alpha, beta, spanBegin=0, spanEnd=None):
         """extension: diagonal <- (diagonal * (1 + alpha)) + beta on the device, in place, over the
         internal scalars of the spans [spanBegin, spanEnd) (bsp_damp_*); every operation is rounded in
@@ -1355,17 +1456,22 @@ class _EntryMap:
         _check(getattr(self._lib, "bsp_%s_info" % self._C)(self._h, out))
         return dict(zip(self._KEYS, [int(x) for x in out]))
 
+    @staticmethod
+    def _alloc_out(name, ref, shape, out):
+        """`out` allocated like `ref` with `shape`, or checked against them"""
+        import torch
+        shape = tuple(shape)
+        if out is None:
+            return torch.empty(shape, dtype=ref.dtype, device=ref.device)
+        if tuple(out.shape) != shape or out.dtype != ref.dtype or out.device != ref.device:
+            raise ValueError("%s: out must be %s %s on %s, got %s %s on %s" % (
+                name, shape, ref.dtype, ref.device, tuple(out.shape), out.dtype, out.device))
+        return out
+
     def _launch(self, name, fn, sfx, ins, shape, out, batched, q=None):
         """the tail of an operation on the device tensors `ins`: `out` allocated or checked against `shape`,
         every tensor in device memory and contiguous, then the single or the batched entry `fn`"""
-        import torch
-        ref = ins[0]
-        shape = tuple(shape)
-        if out is None:
-            out = torch.empty(shape, dtype=ref.dtype, device=ref.device)
-        elif tuple(out.shape) != shape or out.dtype != ref.dtype or out.device != ref.device:
-            raise ValueError("%s: out must be %s %s on %s, got %s %s on %s" % (
-                name, shape, ref.dtype, ref.device, tuple(out.shape), out.dtype, out.device))
+        out = self._alloc_out(name, ins[0], shape, out)
         ts = list(ins) + [out]
         for t in ts:
             _ptr_of(t)  # device memory, contiguous
@@ -1538,6 +1644,11 @@ class SymProduct(_EntryMap):
     def _run(self, name, fn, a, a_what, x, out, batched):
         """a: values [nnz] / [B, nnz] (mv) or g, shaped like x (outer); x [n] / [n, q], or those with a
         leading B when `batched`; out [.., n(, q)] (mv) or [.., nnz] (outer)"""
+        sfx, shape, q = self._operands(name, a, a_what, x, batched)
+        return self._launch(name, fn, sfx, [a, x], shape, out, batched, q)
+
+    def _operands(self, name, a, a_what, x, batched):
+        """the checks of _run's operands: (suffix of the entry, shape of the output, q)"""
         import torch
         for what, t in ((a_what, a), ("x", x)):
             if not isinstance(t, torch.Tensor):
@@ -1562,7 +1673,7 @@ class SymProduct(_EntryMap):
         if q < 1:
             raise ValueError("%s: x has no vectors" % name)
         shape = tuple(x.shape) if mv else tuple(x.shape[:lo]) + (self.nnz,)
-        return self._launch(name, fn, sfx, [a, x], shape, out, batched, q)
+        return sfx, shape, q
 
     def mv(self, values, x, out=None):
         """values [nnz] or [B, nnz] (device, float64 / float32); x [n] or [n, q] in the caller's order (leading
@@ -1582,6 +1693,41 @@ class SymProduct(_EntryMap):
             dims = x.dim() if isinstance(x, torch.Tensor) else 0
             batched = dims == 3 or (dims == 2 and isinstance(out, torch.Tensor) and out.dim() == 2)
         return self._run("outer", "bsp_sym_product_outer_", g, "g", x, out, bool(batched))
+
+    # ---- error bounds; not differentiable ------------------------------------
+    def absMv(self, values, x, out=None):
+        """|A| |x|, shaped like x: row i is the terms |values[k]| * |x[idx]| of mv's list folded in the same
+        order from +0, duplicates as separate terms, so that cancelling duplicates do not shrink it
+        (bsp_sym_product_abs_mv_*).  Arguments as for mv; every element written.  Not differentiable."""
+        import torch
+        return self._run("absMv", "bsp_sym_product_abs_mv_", values, "values", x, out,
+                         isinstance(values, torch.Tensor) and values.dim() == 2)
+
+    def residual(self, values, x, b, out=None):
+        """(r, d) of x as a solution of A x = b, both shaped like x, from ONE pass over mv's row lists
+        (bsp_sym_product_residual_*): r = b - A x, bitwise b - mv(values, x), and d = |A| |x| + |b|, the
+        Oettli-Prager denominator (absMv's terms, then |b| added).  values, x as for mv, b shaped like x;
+        out: a pair (r, d) of tensors to write.  Every element of both is written.  Not differentiable."""
+        import torch
+        name = "residual"
+        if not isinstance(b, torch.Tensor):
+            raise TypeError("%s: b must be a torch.Tensor, got %s" % (name, type(b).__name__))
+        batched = isinstance(values, torch.Tensor) and values.dim() == 2
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+            raise ValueError("%s: out must be a pair (r, d) of tensors" % name)
+        if isinstance(x, torch.Tensor) and (b.shape != x.shape or b.dtype != x.dtype or b.device != x.device):
+            raise ValueError("%s: b must be %s %s on %s like x, got %s %s on %s" % (
+                name, tuple(x.shape), x.dtype, x.device, tuple(b.shape), b.dtype, b.device))
+        sfx, shape, q = self._operands(name, values, "values", x, batched)
+        r, d = (None, None) if out is None else out
+        r, d = self._alloc_out(name, x, shape, r), self._alloc_out(name, x, shape, d)
+        ts = (values, x, b, r, d)
+        for t in ts:
+            _ptr_of(t)  # device memory, contiguous
+        ptrs = [_ptr_arg(t.unbind(0) if batched else [t], batched) for t in ts]
+        _call(self._lib, "bsp_sym_product_residual_", batched, sfx, self.solver._h, self._h, *ptrs[:3],
+              ctypes.c_int64(q), ptrs[3], ptrs[4], *_count(d, batched))
+        return r, d
 
 
 def probe_mfma_f64_tflops():

@@ -922,6 +922,80 @@ static void symProductRun(bsp_solver* s, const bsp_sym_product* p, int32_t op, c
 BSP_SYM_PRODUCT_API(f64, double)
 BSP_SYM_PRODUCT_API(f32, float)
 #undef BSP_SYM_PRODUCT_API
+
+// ---- error bounds --------------------------------------------------------------
+// residual (b, r given) or absMv (b, r NULL)
+template <typename T>
+static void symResidualRun(bsp_solver* s, const bsp_sym_product* p, bool hasB, const T* const* v, const T* const* x,
+                           const T* const* b, T* const* r, T* const* d, int64_t q, int32_t batch, bool single) {
+  const std::string what = hasB ? "symProductResidual" : "symProductAbsMv";
+  if (s == nullptr) throw std::runtime_error(what + ": the solver is NULL");
+  if (p == nullptr) throw std::runtime_error(what + ": the map is NULL");
+  const std::vector<const T*> vs = hostArray<const T*>(what, nullptr, v, batch);
+  const std::vector<const T*> xs = hostArray<const T*>(what, nullptr, x, batch);
+  const std::vector<T*> ds = hostArray<T*>(what, nullptr, d, batch);
+  std::vector<const T*> bs;
+  std::vector<T*> rs;
+  if (hasB) {
+    bs = hostArray<const T*>(what, nullptr, b, batch);
+    rs = hostArray<T*>(what, nullptr, r, batch);
+  }
+  s->solver->symResidual<T>(*p->map, vs, xs, bs, rs, ds, q, single);
+}
+// maxRatio (b given) or colMax (b NULL)
+template <typename T>
+static void colMaxRun(bsp_solver* s, bool ratio, const T* const* a, const T* const* b, int64_t n, int64_t q,
+                      double* out, int32_t batch, bool single) {
+  const std::string what = ratio ? "maxRatio" : "colMax";
+  if (s == nullptr) throw std::runtime_error(what + ": the solver is NULL");
+  const std::vector<const T*> as = hostArray<const T*>(what, nullptr, a, batch);
+  const std::vector<const T*> bs = ratio ? hostArray<const T*>(what, nullptr, b, batch) : std::vector<const T*>{};
+  s->solver->colMax<T>(as, bs, n, q, out, single);
+}
+template <typename T>
+static void invNorm1Run(bsp_solver* s, const T* const* L, const T* const* D, void* work, int64_t* state, double* out,
+                        int32_t batch, bool single) {
+  const std::string what = "invNorm1Estimate";
+  if (s == nullptr) throw std::runtime_error(what + ": the solver is NULL");
+  const std::vector<const T*> ls = hostArray<const T*>(what, "factor", L, batch);
+  const std::vector<const T*> ds = D ? hostArray<const T*>(what, "scale", D, batch) : std::vector<const T*>{};
+  s->solver->invNorm1Estimate<T>(ls, ds, work, state, out, single);
+}
+#define BSP_ERROR_BOUNDS_API(SFX, T)                                                                             \
+  int bsp_sym_product_residual_##SFX(bsp_solver* s, const bsp_sym_product* p, const T* v, const T* x, const T* b, \
+                                     int64_t q, T* r, T* d)                                                      \
+      BSP_BODY(symResidualRun<T>(s, p, true, &v, &x, &b, &r, &d, q, 1, true))                                    \
+  int bsp_sym_product_residual_batched_##SFX(bsp_solver* s, const bsp_sym_product* p, const T* const* v,         \
+                                             const T* const* x, const T* const* b, int64_t q, T* const* r,       \
+                                             T* const* d, int32_t batch)                                         \
+      BSP_BODY(symResidualRun<T>(s, p, true, v, x, b, r, d, q, batch, false))                                    \
+  int bsp_sym_product_abs_mv_##SFX(bsp_solver* s, const bsp_sym_product* p, const T* v, const T* x, int64_t q,   \
+                                   T* out)                                                                       \
+      BSP_BODY(symResidualRun<T>(s, p, false, &v, &x, nullptr, nullptr, &out, q, 1, true))                       \
+  int bsp_sym_product_abs_mv_batched_##SFX(bsp_solver* s, const bsp_sym_product* p, const T* const* v,           \
+                                           const T* const* x, int64_t q, T* const* out, int32_t batch)           \
+      BSP_BODY(symResidualRun<T>(s, p, false, v, x, nullptr, nullptr, out, q, batch, false))                     \
+  int bsp_max_ratio_##SFX(bsp_solver* s, const T* r, const T* d, int64_t n, int64_t q, double* out)              \
+      BSP_BODY(colMaxRun<T>(s, true, &r, &d, n, q, out, 1, true))                                                \
+  int bsp_max_ratio_batched_##SFX(bsp_solver* s, const T* const* r, const T* const* d, int64_t n, int64_t q,     \
+                                  double* out, int32_t batch)                                                    \
+      BSP_BODY(colMaxRun<T>(s, true, r, d, n, q, out, batch, false))                                             \
+  int bsp_col_max_##SFX(bsp_solver* s, const T* a, int64_t n, int64_t q, double* out)                            \
+      BSP_BODY(colMaxRun<T>(s, false, &a, nullptr, n, q, out, 1, true))                                          \
+  int bsp_col_max_batched_##SFX(bsp_solver* s, const T* const* a, int64_t n, int64_t q, double* out,             \
+                                int32_t batch) BSP_BODY(colMaxRun<T>(s, false, a, nullptr, n, q, out, batch, false)) \
+  int bsp_inv_norm1_work_bytes_##SFX(const bsp_solver* s, int64_t* out) BSP_BODY({                               \
+    if (s == nullptr || out == nullptr) throw std::runtime_error("bsp_inv_norm1_work_bytes: NULL argument");     \
+    *out = s->solver->invNorm1WorkBytes<T>();                                                                    \
+  })                                                                                                             \
+  int bsp_inv_norm1_##SFX(bsp_solver* s, const T* L, const T* D, void* work, int64_t* state, double* out)        \
+      BSP_BODY(invNorm1Run<T>(s, &L, D ? &D : nullptr, work, state, out, 1, true))                               \
+  int bsp_inv_norm1_batched_##SFX(bsp_solver* s, const T* const* L, const T* const* D, void* work,               \
+                                  int64_t* state, double* out, int32_t batch)                                    \
+      BSP_BODY(invNorm1Run<T>(s, L, D, work, state, out, batch, false))
+BSP_ERROR_BOUNDS_API(f64, double)
+BSP_ERROR_BOUNDS_API(f32, float)
+#undef BSP_ERROR_BOUNDS_API
 int bsp_scalar_permutation(const bsp_solver* s, int64_t* out) {
   BSP_TRY
   if (out == nullptr) throw std::runtime_error("bsp_scalar_permutation: out is NULL");

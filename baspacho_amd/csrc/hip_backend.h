@@ -196,6 +196,39 @@ template <typename T>
 void hipBackendSymProduct(SymbolicCtx& sym, const SymProductMap& map, int32_t op, const T* const* a,
                           const T* const* b, T* const* out, int64_t q, int64_t batch, bool single);
 
+// Error bounds.
+//   symResidual:  r = b - A x and d = |A| |x| + |b| ([n, q] each) over the row lists of SymProductMv, in
+//                 one pass; b and r NULL: d = |A| |x| alone
+//   colMax:       out[member q + j] (double) = max over the n rows of ratio(|a[i, j]|, b[i, j]), or of
+//                 a[i, j] when b is NULL (hip_norm_est_kernels.h)
+//   normEstStep:  one step of Solver::invNorm1Estimate on the work areas of `batch` matrices, which sit
+//                 normEstWorkBytes apart from `work` on: x (order values of T), xi (order values), then,
+//                 normEstPartOffset bytes from x, the partials of the reductions.  D is read by
+//                 NormEstScale alone; out by NormEstAltSum alone
+template <typename T>
+void hipBackendSymResidual(SymbolicCtx& sym, const SymProductMap& map, const T* const* values, const T* const* x,
+                           const T* const* b, T* const* r, T* const* d, int64_t q, int64_t batch, bool single);
+template <typename T>
+void hipBackendColMax(SymbolicCtx& sym, const T* const* a, const T* const* b, int64_t n, int64_t q, double* out,
+                      int64_t batch, bool single);
+enum NormEstStep : int32_t {
+  NormEstStart = 0,      // x = 1 / n, the state record reset
+  NormEstUnit = 1,       // x = e_j, j from the record
+  NormEstAltVector = 2,  // x = the alternating vector
+  NormEstScale = 3,      // x <- D x
+  NormEstSum = 4,        // ||x||_1, the sign comparison, xi = x = sgn(x), the decision of the pass
+  NormEstArgMax = 5,     // j = argmax |x| (x holding z), the same-column test
+  NormEstAltSum = 6      // ||x||_1 of the alternating solve weighed in, the estimate written
+};
+inline int64_t normEstPartOffset(int64_t order, int64_t elemBytes) { return (2 * order * elemBytes + 15) & ~int64_t(15); }
+inline int64_t normEstWorkBytes(int64_t order, int64_t elemBytes) {
+  const int64_t parts = (order + 1023) / 1024;
+  return normEstPartOffset(order, elemBytes) + (parts > 0 ? parts : 1) * 16;
+}
+template <typename T>
+void hipBackendNormEstStep(SymbolicCtx& sym, int32_t step, void* work, const T* const* D, int64_t* state,
+                           double* out, int64_t batch, bool single);
+
 // Reach solves (hip_reach_kernels.h), one matrix, plan from buildReachPlan (reach.h).
 // reachSolveL: W (numCols x order, column-major, leading dimension order) <- the unit columns of the
 // queries solved through the lumps of their reach below the plan's cut; the caller then runs

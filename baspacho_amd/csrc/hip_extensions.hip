@@ -8,6 +8,7 @@
 #include "hip_chol_adjoint_kernels.h"
 #include "hip_factor_product.h"
 #include "hip_grad_kernels.h"
+#include "hip_norm_est_kernels.h"
 #include "hip_ordered_sum.h"
 #include "hip_reach_kernels.h"
 #include "hip_selinv_adjoint_kernels.h"
@@ -296,6 +297,20 @@ struct hipb::ExtensionState {
   std::unique_ptr<GradDev> grad;      // work lists of logDet / patternGrad, built on first use
   ReachDev reach;
   std::unique_ptr<FactorProductState> factorProduct;  // plan of mulL / mulLt, built on first use
+  // partials of maxRatio / colMax (hip_norm_est_kernels.h).  Growing waits for the kernels queued by
+  // earlier calls, as GradDev::reservePart does; a warm solver does not grow again
+  DevBuf redPart;
+  int64_t redParts = 0;
+  hipk::RedPart* reserveRedParts(int64_t n) {
+    if (n > redParts) {
+      if (redParts > 0) hipCHECK(hipDeviceSynchronize());
+      redParts = 0;
+      redPart.release();
+      redPart.resize((size_t)std::max<int64_t>(n, 1) * sizeof(hipk::RedPart));
+      redParts = n;
+    }
+    return reinterpret_cast<hipk::RedPart*>(redPart.ptr);
+  }
 };
 void hipb::ExtensionStateDelete::operator()(ExtensionState* p) const { delete p; }
 
@@ -848,6 +863,114 @@ void hipBackendSymProduct(SymbolicCtx& sym, const SymProductMap& m, int32_t op, 
   }
 }
 
+// ---- error bounds (hip_ordered_sum.h, hip_norm_est_kernels.h) ------------------
+// r = b - A x and d = |A| |x| + |b| (b given), or d = |A| |x| alone (b, r NULL), on `batch` members: one
+// launch per chunk over the row lists of mv
+template <typename T>
+void hipBackendSymResidual(SymbolicCtx& sym, const SymProductMap& m, const T* const* values, const T* const* x,
+                           const T* const* b, T* const* r, T* const* d, int64_t q, int64_t batch, bool single) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  BASPACHO_CHECK_LT(q, (int64_t)INT32_MAX);
+  HipEntryMapDev& dv = HipEntryMapDev::of(m.dev);
+  const RunLaunch<int32_t> rows = runLaunch(dv, m.rows, q, true);
+  if (m.n * q == 0) return;
+  const BatchPtrs<const T> vs = h.stage(values, batch, single), xs = h.stage(x, batch, single);
+  const BatchPtrs<const T> bs = h.stage(b, batch, single);
+  const BatchPtrs<T> rs = h.stage(r, batch, single), ds = h.stage(d, batch, single);
+  const dim3 block(hipk::kAsmThreads);
+  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+    const dim3 grid((unsigned)(rows.shortWgs + rows.longWgs), nm);
+    if (b != nullptr) {
+      hipk::symProductResidual<T, true><<<grid, block, 0, stream>>>(
+          rows.numRuns, (int32_t)q, (int32_t)rows.shortWgs, rows.longWaves, rows.start, rows.longRuns, rows.entry,
+          rows.idx, vs.at(q0), xs.at(q0), bs.at(q0), rs.at(q0), ds.at(q0));
+    } else {
+      hipk::symProductResidual<T, false><<<grid, block, 0, stream>>>(
+          rows.numRuns, (int32_t)q, (int32_t)rows.shortWgs, rows.longWaves, rows.start, rows.longRuns, rows.entry,
+          rows.idx, vs.at(q0), xs.at(q0), bs.at(q0), rs.at(q0), ds.at(q0));
+    }
+  });
+}
+
+// out[member q + j] = max over the n rows of ratio(|a[i, j]|, b[i, j]) (b given) or of a[i, j] (b NULL),
+// in double: two launches per chunk, the partials of a chunk in ExtensionState::redPart
+template <typename T>
+void hipBackendColMax(SymbolicCtx& sym, const T* const* a, const T* const* b, int64_t n, int64_t q, double* out,
+                      int64_t batch, bool single) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  BASPACHO_CHECK_LT(q, (int64_t)INT32_MAX);
+  const int64_t nParts = (n + hipk::kRedChunk - 1) / hipk::kRedChunk;
+  BASPACHO_CHECK_LT(nParts * q, (int64_t)INT32_MAX);
+  const int64_t chunk = std::min(batch, HipSymbolicCtx::kMaxGridY);
+  hipk::RedPart* part = extState(h).reserveRedParts(chunk * q * nParts);
+  const BatchPtrs<const T> as = h.stage(a, batch, single), bs = h.stage(b, batch, single);
+  const double start = b != nullptr ? 0.0 : -std::numeric_limits<double>::infinity();
+  h.forChunks(batch, chunk, [&](int64_t q0, unsigned nm) {
+    if (nParts > 0) {
+      const dim3 grid((unsigned)(nParts * q), nm);
+      if (b != nullptr) {
+        hipk::colMaxPartial<T, true><<<grid, hipk::kRedThreads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts,
+                                                                             as.at(q0), bs.at(q0), part);
+      } else {
+        hipk::colMaxPartial<T, false><<<grid, hipk::kRedThreads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts,
+                                                                              as.at(q0), bs.at(q0), part);
+      }
+    }
+    hipk::colMaxFinal<<<dim3((unsigned)q, nm), hipk::kRedThreads, 0, stream>>>((int32_t)q, (int32_t)nParts, start,
+                                                                             part, out + q0 * q);
+  });
+}
+
+// one step of the 1-norm estimate (NormEstStep) on `batch` matrices whose work areas sit `stride` bytes
+// apart from `work` on (normEstWorkBytes, hip_backend.h): one or two launches per chunk
+template <typename T>
+void hipBackendNormEstStep(SymbolicCtx& sym, int32_t step, void* work, const T* const* D, int64_t* state,
+                           double* out, int64_t batch, bool single) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  const int64_t n = h.skel.order();
+  const int64_t stride = normEstWorkBytes(n, sizeof(T)), partOff = normEstPartOffset(n, sizeof(T));
+  const int64_t nParts = (n + hipk::kRedChunk - 1) / hipk::kRedChunk;
+  const unsigned wgs = (unsigned)((n + hipk::kRedThreads - 1) / hipk::kRedThreads);
+  BASPACHO_CHECK_LT(nParts, (int64_t)INT32_MAX);
+  const BatchPtrs<const T> ds = h.stage(step == NormEstScale ? D : nullptr, batch, single);
+  const int threads = hipk::kRedThreads;
+  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+    const hipk::NormEstWork w{static_cast<char*>(work) + q0 * stride, stride, partOff};
+    hipk::NormEstState* st = reinterpret_cast<hipk::NormEstState*>(state) + q0;
+    const dim3 perElem(wgs, nm), perChunk((unsigned)nParts, nm), perMatrix(1, nm);
+    switch (step) {
+      case NormEstStart:
+      case NormEstUnit:
+      case NormEstAltVector:
+        hipk::normEstWrite<T><<<perElem, threads, 0, stream>>>(n, step - NormEstStart, w, st);
+        break;
+      case NormEstScale:
+        hipk::normEstScale<T><<<perElem, threads, 0, stream>>>(n, w, ds.at(q0));
+        break;
+      case NormEstSum:
+        hipk::normEstSumPartial<T, true><<<perChunk, threads, 0, stream>>>(n, w);
+        hipk::normEstSumFinal<<<perMatrix, threads, 0, stream>>>(n, (int32_t)nParts, false, w, st, out + q0);
+        break;
+      case NormEstAltSum:
+        hipk::normEstSumPartial<T, false><<<perChunk, threads, 0, stream>>>(n, w);
+        hipk::normEstSumFinal<<<perMatrix, threads, 0, stream>>>(n, (int32_t)nParts, true, w, st, out + q0);
+        break;
+      case NormEstArgMax:
+        hipk::normEstArgMaxPartial<T><<<perChunk, threads, 0, stream>>>(n, w);
+        hipk::normEstArgMaxFinal<T><<<perMatrix, threads, 0, stream>>>(n, (int32_t)nParts, w, st);
+        break;
+      default:
+        throw std::runtime_error("invNorm1Estimate: unknown step " + std::to_string(step));
+    }
+  });
+}
+
 // ---- reach solves (hip_reach_kernels.h) ---------------------------------------
 // W (numCols x order, column-major) <- the unit columns of the plan's queries, solved through the lumps
 // of their reach below the cut: one memset, the unit entries of the queries behind the cut, one launch
@@ -991,6 +1114,12 @@ void hipBackendFactorProduct(SymbolicCtx& sym, const T* const* L, bool transpose
                                       const T* const*, T* const*, int64_t, int64_t, bool);                      \
   template void hipBackendSymProduct<T>(SymbolicCtx&, const SymProductMap&, int32_t, const T* const*,           \
                                         const T* const*, T* const*, int64_t, int64_t, bool);                    \
+  template void hipBackendSymResidual<T>(SymbolicCtx&, const SymProductMap&, const T* const*, const T* const*,  \
+                                         const T* const*, T* const*, T* const*, int64_t, int64_t, bool);        \
+  template void hipBackendColMax<T>(SymbolicCtx&, const T* const*, const T* const*, int64_t, int64_t, double*,  \
+                                    int64_t, bool);                                                             \
+  template void hipBackendNormEstStep<T>(SymbolicCtx&, int32_t, void*, const T* const*, int64_t*, double*,      \
+                                         int64_t, bool);                                                        \
   template void hipBackendReachSolveL<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                         \
   template void hipBackendGramBlocks<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                          \
   template T* hipBackendReachWorkspace<T>(SymbolicCtx&, int64_t);                                               \

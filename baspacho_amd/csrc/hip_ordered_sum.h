@@ -13,6 +13,8 @@
 //   assembleAdjointEntries: grad_values[k] = grad_data[entryOff[k]], 0 where entryOff[k] = -1.
 //   symProductOuter:        out[k] = sum over j ascending of g[r, j] * x[c, j] (+ g[c, j] * x[r, j] when
 //                           r != c), (r, c) the position of entry k; 0 for a skipped entry.
+//   symProductResidual:     r = b - A x and d = |A| |x| + |b| over the row lists of A x, in one pass with
+//                           two accumulators (section 23); without b: d = |A| |x|.
 //
 // A run of at most kAssemblyLongRun terms is summed by one lane (sumRunByLane); a longer one by a wave
 // that loads 64 terms at a time and folds them in lane order through readlane (sumRunByWave): the same
@@ -266,6 +268,72 @@ __global__ void __launch_bounds__(kAsmThreads)
     for (int32_t j = 0; j < q; j++) s = radd(s, rmul(g[r0 + j], x[c0 + j]));
   }
   out[k] = s;
+}
+
+__device__ __forceinline__ double absValue(double v) { return __builtin_fabs(v); }
+__device__ __forceinline__ float absValue(float v) { return __builtin_fabsf(v); }
+
+// The residual of A x = b and its scale over the row lists of a SymProductMap, in
+// one pass over the lists with two accumulators: with s the terms rmul(values[k], x[idx, j]) of row i
+// and t the terms rmul(|values[k]|, |x[idx, j]|), both folded in list order from +0,
+//   kHasB:  r[i, j] = radd(b[i, j], -s) and d[i, j] = radd(|b[i, j]|, t);
+//   !kHasB: d[i, j] = t (|A| |x|; b and r are not touched).
+// The launch shape is orderedSumRuns' (workgroups [0, shortWgs): one thread per output, the rows of
+// longRuns left out; from shortWgs on: one wave per (long row, j), two foldLanes per 64 terms).  Every
+// element of r and d is written exactly once and neither is read.
+template <typename T, bool kHasB>
+__global__ void __launch_bounds__(kAsmThreads)
+    symProductResidual(int64_t numRuns, int32_t q, int32_t shortWgs, int64_t numLongWaves,
+                       const int32_t* __restrict__ start, const int32_t* __restrict__ longRuns,
+                       const int32_t* __restrict__ entry, const int32_t* __restrict__ idx, DataRef<const T> vref,
+                       DataRef<const T> xref, DataRef<const T> bref, DataRef<T> rref, DataRef<T> dref) {
+  const GP<const T> v = pickData(vref), x = pickData(xref);
+  const GP<const T> b = kHasB ? pickData(bref) : GP<const T>(nullptr);
+  const GP<T> r = kHasB ? pickData(rref) : GP<T>(nullptr);
+  const GP<T> d = pickData(dref);
+  T s = 0, t = 0;
+  int64_t at;
+  if ((int32_t)blockIdx.x < shortWgs) {
+    at = (int64_t)blockIdx.x * kAsmThreads + threadIdx.x;
+    if (at >= numRuns * q) return;
+    const int64_t u = at / q;
+    const int32_t j = (int32_t)(at - u * q);
+    const int32_t r0 = start[u], r1 = start[u + 1];
+    if (isLongRun(r1 - r0)) return;
+    for (int32_t p = r0; p < r1; p++) {
+      const T a = v[entry[p]], w = x[(int64_t)idx[p] * q + j];
+      s = radd(s, rmul(a, w));
+      t = radd(t, rmul(absValue(a), absValue(w)));
+    }
+  } else {
+    const int lane = threadIdx.x & 63;
+    const int64_t w = ((int64_t)blockIdx.x - shortWgs) * kAsmWavesPerWg + (int)(threadIdx.x >> 6);
+    if (w >= numLongWaves) return;
+    const int32_t l = waveUniform((int32_t)(w / q));
+    const int32_t j = waveUniform((int32_t)(w - (int64_t)l * q));
+    const int32_t u = waveUniform(longRuns[l]);
+    const int32_t r0 = waveUniform(start[u]), r1 = waveUniform(start[u + 1]);
+    for (int32_t c = r0; c < r1; c += 64) {
+      const int cnt = r1 - c < 64 ? (int)(r1 - c) : 64;
+      T ps = 0, pt = 0;
+      if (lane < cnt) {
+        const T a = v[entry[c + lane]], xv = x[(int64_t)idx[c + lane] * q + j];
+        ps = rmul(a, xv);
+        pt = rmul(absValue(a), absValue(xv));
+      }
+      s = foldLanes(s, ps, cnt);
+      t = foldLanes(t, pt, cnt);
+    }
+    if (lane != 0) return;
+    at = (int64_t)u * q + j;
+  }
+  if (kHasB) {
+    const T bv = b[at];
+    r[at] = radd(bv, -s);
+    d[at] = radd(absValue(bv), t);
+  } else {
+    d[at] = t;
+  }
 }
 
 }  // namespace hipk

@@ -1040,6 +1040,170 @@ void Solver::symProduct(const SymProductMap& map, int32_t op, const std::vector<
                       fault, true);
   hipBackendSymProduct<T>(*symCtx, map, op, a.data(), x.data(), out.data(), q, (int64_t)a.size(), single);
 }
+// ---- error bounds -------------------------------------------------------------
+static std::string badVectorCount(int64_t q) {
+  return q < 1            ? "q = " + std::to_string(q) + " vectors; at least one is needed"
+         : q >= INT32_MAX ? "q = " + std::to_string(q) + " vectors is outside [1, 2^31 - 1)"
+                          : "";
+}
+
+template <typename T>
+void Solver::symResidual(const SymProductMap& map, const std::vector<const T*>& values,
+                         const std::vector<const T*>& x, const std::vector<const T*>& b, const std::vector<T*>& r,
+                         const std::vector<T*>& d, int64_t q, bool single) const {
+  const bool hasB = !b.empty() || !r.empty();
+  const char* what = hasB ? "symProductResidual" : "symProductAbsMv";
+  const std::string fault = badVectorCount(q);
+  const int64_t nq = map.n * q;
+  std::vector<OpSide<T>> ins = {{"values", "values", values.data(), values.size(), map.nnz, false},
+                                {"vector", "vectors", x.data(), x.size(), nq, false}};
+  if (hasB) ins.push_back({"right-hand side", "right-hand sides", b.data(), b.size(), nq, false});
+  const std::vector<const T*> rc(r.begin(), r.end()), dc(d.begin(), d.end());
+  if (hasB) {
+    std::vector<OpSide<T>> sides = ins;
+    sides.push_back({"scale", "scale outputs", dc.data(), dc.size(), nq, false});
+    sides.push_back({"residual", "residual outputs", rc.data(), rc.size(), nq, true});
+    checkOpArguments<T>(what, "map", map.solver == this, sides, fault, true);
+  }
+  // (the second output against the inputs and, as an input of this check, against the first)
+  std::vector<OpSide<T>> sides = ins;
+  if (hasB) sides.push_back({"residual", "residual outputs", rc.data(), rc.size(), nq, false});
+  sides.push_back({hasB ? "scale" : "output", hasB ? "scale outputs" : "outputs", dc.data(), dc.size(), nq, true});
+  checkOpArguments<T>(what, "map", map.solver == this, sides, fault, true);
+  hipBackendSymResidual<T>(*symCtx, map, values.data(), x.data(), hasB ? b.data() : nullptr,
+                           hasB ? r.data() : nullptr, d.data(), q, (int64_t)values.size(), single);
+}
+
+template <typename T>
+void Solver::colMax(const std::vector<const T*>& a, const std::vector<const T*>& b, int64_t n, int64_t q,
+                    double* devOut, bool single) const {
+  const bool ratio = !b.empty();
+  const std::string what = ratio ? "maxRatio" : "colMax";
+  const auto fail = [&](const std::string& m) { throw std::runtime_error(what + ": " + m); };
+  if (a.empty()) fail("the batch is empty");
+  if (ratio && b.size() != a.size()) {
+    fail("the batch has " + std::to_string(a.size()) + " numerators and " + std::to_string(b.size()) + " denominators");
+  }
+  if (n < 0) fail("n = " + std::to_string(n) + " rows");
+  const std::string fault = badVectorCount(q);
+  if (!fault.empty()) fail(fault);
+  if (devOut == nullptr) fail("the output pointer is NULL");
+  const char* o0 = reinterpret_cast<const char*>(devOut);
+  const char* o1 = o0 + a.size() * (size_t)q * sizeof(double);
+  const auto checkSide = [&](const std::vector<const T*>& v, const char* name) {
+    for (size_t m = 0; m < v.size(); m++) {
+      if (v[m] == nullptr && n > 0) {
+        fail(std::string("the ") + name + " pointer of batch member " + std::to_string(m) + " is NULL");
+      }
+      const char* p0 = reinterpret_cast<const char*>(v[m]);
+      if (n > 0 && p0 < o1 && o0 < p0 + (size_t)(n * q) * sizeof(T)) {
+        fail(std::string("the output aliases the ") + name + " of batch member " + std::to_string(m));
+      }
+    }
+  };
+  checkSide(a, ratio ? "numerator" : "input");
+  checkSide(b, "denominator");
+  hipBackendColMax<T>(*symCtx, a.data(), ratio ? b.data() : nullptr, n, q, devOut, (int64_t)a.size(), single);
+}
+
+template <typename T>
+int64_t Solver::invNorm1WorkBytes() const {
+  return normEstWorkBytes(order(), sizeof(T));
+}
+
+template <typename T>
+void Solver::invNorm1Estimate(const std::vector<const T*>& L, const std::vector<const T*>& D, void* work,
+                              int64_t* devState, double* devOut, bool single) const {
+  const char* what = "invNorm1Estimate";
+  const auto fail = [&](const std::string& m) { throw std::runtime_error(std::string(what) + ": " + m); };
+  checkCompleteFactor(what, canFactorUpTo, factorSkel.numSpans());
+  const int64_t n = order(), batch = (int64_t)L.size();
+  if (batch == 0) fail("the batch is empty");
+  if (n < 1) fail("the order is 0");
+  const bool scaled = !D.empty();
+  if (scaled && D.size() != L.size()) {
+    fail("the batch has " + std::to_string(L.size()) + " factors and " + std::to_string(D.size()) + " scale vectors");
+  }
+  if (work == nullptr) fail("the workspace pointer is NULL");
+  if (reinterpret_cast<uintptr_t>(work) % 16 != 0) fail("the workspace is not 16-byte aligned");
+  if (devState == nullptr) fail("the state pointer is NULL");
+  if (devOut == nullptr) fail("the output pointer is NULL");
+  const int64_t stride = invNorm1WorkBytes<T>();
+  char* w0 = static_cast<char*>(work);
+  const char* w1 = w0 + batch * stride;
+  const auto overlapsWork = [&](const void* p, size_t bytes) {
+    const char* c = static_cast<const char*>(p);
+    return c < w1 && w0 < c + bytes;
+  };
+  for (int64_t m = 0; m < batch; m++) {
+    if (L[m] == nullptr) fail("the factor pointer of batch member " + std::to_string(m) + " is NULL");
+    if (scaled && D[m] == nullptr) fail("the scale pointer of batch member " + std::to_string(m) + " is NULL");
+    if (overlapsWork(L[m], (size_t)dataSize() * sizeof(T))) {
+      fail("the workspace aliases the factor of batch member " + std::to_string(m));
+    }
+    if (scaled && overlapsWork(D[m], (size_t)n * sizeof(T))) {
+      fail("the workspace aliases the scale vector of batch member " + std::to_string(m));
+    }
+  }
+  const size_t stateBytes = (size_t)batch * 12 * sizeof(int64_t), outBytes = (size_t)batch * sizeof(double);
+  if (overlapsWork(devState, stateBytes)) fail("the workspace aliases the state");
+  if (overlapsWork(devOut, outBytes)) fail("the workspace aliases the output");
+  const char* s0 = reinterpret_cast<const char*>(devState);
+  const char* o0 = reinterpret_cast<const char*>(devOut);
+  if (o0 < s0 + stateBytes && s0 < o0 + outBytes) fail("the output aliases the state");
+  // the two outputs against the inputs (the same factor or scale vector in several members is allowed)
+  const auto overlapsOutputs = [&](const void* p, size_t bytes) -> const char* {
+    const char* c = static_cast<const char*>(p);
+    if (c < s0 + stateBytes && s0 < c + bytes) return "state";
+    if (c < o0 + outBytes && o0 < c + bytes) return "output";
+    return nullptr;
+  };
+  for (int64_t m = 0; m < batch; m++) {
+    if (const char* o = overlapsOutputs(L[m], (size_t)dataSize() * sizeof(T))) {
+      fail(std::string("the ") + o + " aliases the factor of batch member " + std::to_string(m));
+    }
+    if (scaled) {
+      if (const char* o = overlapsOutputs(D[m], (size_t)n * sizeof(T))) {
+        fail(std::string("the ") + o + " aliases the scale vector of batch member " + std::to_string(m));
+      }
+    }
+  }
+
+  std::vector<T*> mats(batch), vecs(batch);
+  for (int64_t m = 0; m < batch; m++) {
+    mats[m] = const_cast<T*>(L[m]);
+    vecs[m] = reinterpret_cast<T*>(w0 + m * stride);
+  }
+  const auto step = [&](int32_t s) {
+    hipBackendNormEstStep<T>(*symCtx, s, work, scaled ? D.data() : nullptr, devState, devOut, batch, single);
+  };
+  const auto applyInverse = [&]() {  // x <- [D] A^-1 [D] x
+    if (scaled) step(NormEstScale);
+    if (single) {
+      solve<T>(mats[0], vecs[0], n, 1);
+    } else {
+      solve(&mats, &vecs, n, 1);
+    }
+    if (scaled) step(NormEstScale);
+  };
+  step(NormEstStart);
+  applyInverse();
+  step(NormEstSum);
+  applyInverse();
+  step(NormEstArgMax);
+  for (int pass = 2; pass <= 5; pass++) {
+    step(NormEstUnit);
+    applyInverse();
+    step(NormEstSum);
+    if (pass == 5) break;
+    applyInverse();
+    step(NormEstArgMax);
+  }
+  step(NormEstAltVector);
+  applyInverse();
+  step(NormEstAltSum);
+}
+
 // ---- blocks of A^-1 by reach solves (reach.h) --------------------------------
 ReachPlan Solver::reachPlan(const char* what, const std::vector<int64_t>& params, const std::vector<int64_t>& pairRow,
                             const std::vector<int64_t>& pairCol, const std::vector<int64_t>& outOffsets) const {
@@ -1201,6 +1365,11 @@ void Solver::mulLt(const std::vector<T*>& L, const std::vector<T*>& x, int64_t i
                                       int64_t, bool) const;                                                    \
   template void Solver::normalEq<T>(const NormalEqMap&, int32_t, BspCVec_##T, BspCVec_##T, BspVec_##T,         \
                                     int64_t, bool) const;                                                      \
+  template void Solver::symResidual<T>(const SymProductMap&, BspCVec_##T, BspCVec_##T, BspCVec_##T, BspVec_##T, \
+                                       BspVec_##T, int64_t, bool) const;                                       \
+  template void Solver::colMax<T>(BspCVec_##T, BspCVec_##T, int64_t, int64_t, double*, bool) const;            \
+  template int64_t Solver::invNorm1WorkBytes<T>() const;                                                       \
+  template void Solver::invNorm1Estimate<T>(BspCVec_##T, BspCVec_##T, void*, int64_t*, double*, bool) const;   \
   template void Solver::reachSolveL<T>(const T*, const std::vector<int64_t>&, T*) const;                       \
   template void Solver::inverseBlocks<T>(const T*, const std::vector<int64_t>&, const std::vector<int64_t>&,   \
                                          T*, const std::vector<int64_t>&) const;

@@ -252,6 +252,40 @@ class Solver {
   template <typename T>
   void symProduct(const SymProductMap& map, int32_t op, const std::vector<const T*>& a,
                   const std::vector<const T*>& x, const std::vector<T*>& out, int64_t q, bool single) const;
+  // extension: error bounds (hip_ordered_sum.h, hip_norm_est_kernels.h).  All run on
+  // the stream of setStream() without host synchronisation, and refuse before any device work a map of
+  // another Solver, an empty batch, q < 1, a NULL pointer, a repeated output pointer and an output that
+  // overlaps an input or another output.
+  //
+  // symResidual: over the row lists of SymProductMv, in one pass, r[i, j] = b[i, j] - s, s the terms
+  // values[k] * x[idx, j] of row i folded in list order from +0 (bitwise b - mv(values, x)), and d[i, j] =
+  // |b[i, j]| + t, t the terms |values[k]| * |x[idx, j]| folded the same way: (|A| |x| + |b|)_i with
+  // duplicates as separate terms.  x, b, r, d are [order(), q] row-major; every element of r and d is
+  // written once, neither is read.  With b and r empty: d = |A| |x| alone.
+  template <typename T>
+  void symResidual(const SymProductMap& map, const std::vector<const T*>& values, const std::vector<const T*>& x,
+                   const std::vector<const T*>& b, const std::vector<T*>& r, const std::vector<T*>& d, int64_t q,
+                   bool single) const;
+  // colMax: devOut[member q + j] = max over i < n of a[i, j] as a double (-inf for n == 0); with b:
+  // maxRatio, the max of ratio(|a[i, j]|, b[i, j]) in double (0 for n == 0), where ratio is 0 when a == 0,
+  // +inf when b == 0 and a != 0, and a NaN in either operand makes the column's result NaN.  a and b are
+  // [n, q] row-major and only read.  The partials of the first pass are kept with the Solver; a call that
+  // needs more of them than any before allocates them, which waits for the device.
+  template <typename T>
+  void colMax(const std::vector<const T*>& a, const std::vector<const T*>& b, int64_t n, int64_t q,
+              double* devOut, bool single) const;
+  // invNorm1Estimate: devOut[m] = an estimate of ||A^-1||_1 (a lower bound, almost always within a factor
+  // 3) for the matrix whose complete factor() is L[m]; with D (one device vector of order() values in
+  // internal order per member) of ||D A^-1 D||_1.  Hager's estimator in Higham's form on a fixed schedule
+  // of 10 solve() calls with one right-hand side, nothing read back: devState holds the 12-word state
+  // record of every matrix (hip_norm_est_kernels.h).  `work` is the caller's: invNorm1WorkBytes<T>() bytes
+  // per member, 16-byte aligned, members one after the other; nothing is allocated.  A factor that broke
+  // down gives a non-finite estimate.  Refuses a Solver that cannot factor completely and order() == 0.
+  template <typename T>
+  int64_t invNorm1WorkBytes() const;
+  template <typename T>
+  void invNorm1Estimate(const std::vector<const T*>& L, const std::vector<const T*>& D, void* work,
+                        int64_t* devState, double* devOut, bool single) const;
   // extension: blocks of A^-1 anywhere, on or off the pattern of L, by reach solves (DESIGN.md section 20;
   // reach.h, hip_reach_kernels.h).  `L` holds a complete factor() and is only read; params are the
   // caller's param ids (repeats allowed).  Both run on the stream of setStream() without host

@@ -20,6 +20,9 @@
     q = S.quad_form(pat, values, x)                # x^T A x
     lp = S.log_prob(pat, values, x, mu)            # log N(x; mu, A^-1): the Gaussian whose precision is A
     x = S.solve_refined(pat, values, b, iters=3)   # fp32 factor + fp64 refinement on the entries' A x
+    x, info = S.solve_refined(pat, values, b, iters=6, tol=1e-14, return_info=True)  # checked refinement
+    e = S.backward_error(pat, values, x, b)        # max_i |b - A x|_i / (|A| |x| + |b|)_i per right-hand side
+    k = S.cond_estimate(pat, values, scaled=True)  # kappa_1 of the Jacobi-scaled matrix, from the factor
 
     jpat = S.JacobianPattern(jrows, jcols, m, n)   # once per Jacobian pattern: solver + normal-equations maps
     x = S.lstsq(jpat, jvalues, r, damping=(a, b))  # x = (J^T J + D)^-1 J^T r, D = a diag(J^T J) + b I
@@ -74,7 +77,9 @@ from .autograd import _OnCurrentStream
 __all__ = ["SymmetricPattern", "JacobianPattern", "assemble", "solve", "logdet", "solve_logdet", "sample", "marginalize",
            "covariance", "marginal_variances", "cross_covariance", "joint_covariance",
            "hessian", "jt_vec", "j_vec", "normal_equations", "lstsq", "check_positive_definite",
-           "matvec", "quad_form", "log_prob", "solve_refined", "whiten", "sample_cov"]
+           "matvec", "quad_form", "log_prob", "solve_refined", "whiten", "sample_cov",
+           # error bounds: none of these is differentiable
+           "residual", "backward_error", "norm1", "cond_estimate"]
 
 
 def _host_i64(a):
@@ -781,64 +786,110 @@ def log_prob(pattern, values, x, mu=None):
     return 0.5 * ld - 0.5 * qf - 0.5 * pattern.n * float(np.log(2.0 * np.pi))
 
 
-def _refine(pattern, L32, v, b, iters):
+def _berr(pattern, r, d, batched):
+    """max_i |r_i| / d_i per column of residual's (r, d): [] / [k], with a leading B for a batch"""
+    return pattern.solver.maxRatio(r, d, batched=batched)
+
+
+def _refine(pattern, L32, v, b, iters, tol=None, want_info=False):
     """x = the fp32 solve of b through the factor L32, then `iters` corrections x += solve32(b - A x) with
-    the residual in fp64 from the fp64 entries v; b and x in the caller's order, fp64"""
+    the residual in fp64 from the fp64 entries v; b and x in the caller's order, fp64.  With tol, a column
+    whose backward error is <= tol before a correction keeps its x (a mask on the device).  want_info:
+    (x, berr of x, corrections per column) from one more residual pass"""
     sol, prod = pattern.solver, pattern.product
     batched = v.dim() == 2
     dim = 1 if batched else 0
+    has_k = b.dim() == dim + 2
 
     def solve32(r):
         rt = _ag._to_cols(pattern.toInternal(r.float(), dim), batched)
         _ag._solve_cols(sol, L32, rt)
         return pattern.fromInternal(_ag._from_cols(rt, r.shape), dim).double()
 
+    b = b.contiguous()
     x = solve32(b)
+    count = None
+    if want_info:
+        count = torch.zeros(b.shape[:dim] + (b.shape[-1:] if has_k else ()), dtype=torch.int64, device=b.device)
     for _ in range(iters):
-        x = x + solve32(b - prod.mv(v, x.contiguous()))
-    return x.contiguous()
+        r, d = prod.residual(v, x.contiguous(), b)
+        if tol is None:
+            x = x + solve32(r)
+            if want_info:
+                count += 1
+            continue
+        active = _berr(pattern, r, d, batched) > tol
+        x = torch.where(active.unsqueeze(-2 if has_k else -1), x + solve32(r), x)
+        if want_info:
+            count += active
+    x = x.contiguous()
+    if not want_info:
+        return x
+    r, d = prod.residual(v, x, b)
+    return x, _berr(pattern, r, d, batched), count
 
 
 class _SolveRefined(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pattern, values, b, iters):
+    def forward(ctx, pattern, values, b, iters, tol=None, want_info=False):
         sol = pattern.solver
         v = values.detach().contiguous()
         with _OnCurrentStream(sol, v.device):
             L32 = pattern.assembly.assemble(v.float())
-            sol.factor(_ag._members(L32) if L32.dim() == 2 else L32)
-            x = _refine(pattern, L32, v, b.detach(), iters)
+            members = _ag._members(L32) if L32.dim() == 2 else L32
+            sol.factor(members)
+            if want_info:
+                status = sol.factorStatus(members)
+                x, berr, count = _refine(pattern, L32, v, b.detach(), iters, tol, True)
+            else:
+                x = _refine(pattern, L32, v, b.detach(), iters, tol)
         ctx.pattern, ctx.iters = pattern, iters
         ctx.save_for_backward(L32, v, x)
         ctx.set_materialize_grads(False)
-        return x
+        if not want_info:
+            return x
+        ctx.mark_non_differentiable(berr, count, status)
+        return x, berr, count, status
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g):
+    def backward(ctx, g, *_):
         if g is None or not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
-            return None, None, None, None
+            return None, None, None, None, None, None
         pattern, (L32, v, x) = ctx.pattern, ctx.saved_tensors
         gv = None
         with _OnCurrentStream(pattern.solver, g.device):
             gb = _refine(pattern, L32, v, g.contiguous(), ctx.iters)  # A is symmetric: the same loop, the same factor
             if ctx.needs_input_grad[1]:
                 gv = pattern.product.outer(gb, x, batched=v.dim() == 2).neg_()
-        return None, gv, gb if ctx.needs_input_grad[2] else None, None
+        return None, gv, gb if ctx.needs_input_grad[2] else None, None, None, None
 
 
-def solve_refined(pattern, values, b, iters=3):
+def solve_refined(pattern, values, b, iters=3, tol=None, return_info=False):
     """x = A(values)^-1 b in the caller's order from an fp32 factor and fp64 iterative refinement: values and
     b are float64 (any other dtype is a TypeError).  values.float() is assembled into an fp32 layout and
     factored once; x starts as the fp32 solve of b and is corrected `iters` times by x += solve32(b - A x),
-    the residual in fp64 straight from the fp64 entries (matvec's kernel).  The iteration count is fixed and
-    nothing is read back to the host; the fp64 layout is never allocated, so the factor takes half the
-    memory of solve's.  Differentiable in values and b: b's gradient is the same loop on the incoming
-    gradient with the saved fp32 factor, and the gradient of values is -outer(gb, x) read at the entries.
+    the residual in fp64 straight from the fp64 entries (SymProduct.residual: bitwise b - matvec).  Nothing
+    is read back to the host; the fp64 layout is never allocated, so the factor takes half the memory of
+    solve's.  Differentiable in values and b: b's gradient is the same loop (always `iters` passes) on the
+    incoming gradient with the saved fp32 factor, and the gradient of values is -outer(gb, x) read at the
+    entries.
+
+    tol: `iters` becomes the largest number of corrections.  Before every correction the componentwise
+    backward error max_i |b - A x|_i / (|A| |x| + |b|)_i of every column is taken on the device, and a column
+    at or below tol keeps its x from then on: a mask on the update, still without a read-back (the queued
+    work is the same; DESIGN.md section 23 says what that costs).
+
+    return_info=True: (x, info) at the cost of one more residual pass; info holds device tensors: "berr",
+    the backward error of the returned x per column ([] / [k], leading B for a batch); "corrections", int64
+    of the same shape, how many corrections each column took; "factor_status", the record of the fp32 factor
+    from Solver.factorStatus ([4] / [B, 4]; Solver.readFactorStatus decodes it).
 
     A factor that breaks down in fp32 (a matrix that is not positive definite once rounded to fp32, or too
-    ill-conditioned for it) yields non-finite values, as solve does; nothing inside detects it.
-    check_positive_definite(pattern, values.float()) is the caller's tool for that."""
+    ill-conditioned for it) yields non-finite values, as solve does, and a refinement that stagnates returns
+    its last iterate.  The library now detects both: info["factor_status"] decodes to ok = False for the
+    first, info["berr"] stays above the tolerance (with corrections == iters) for the second; what to do
+    about it (solve in fp64, regularise) is the caller's decision."""
     what = "solve_refined"
     _check_values(pattern, values, what)
     dim = _check_b(pattern, values, b, what)
@@ -851,8 +902,100 @@ def solve_refined(pattern, values, b, iters=3):
         raise ValueError("%s: b has no right-hand sides" % what)
     if not isinstance(iters, int) or isinstance(iters, bool) or iters < 0:
         raise ValueError("%s: iters must be an integer >= 0, got %r" % (what, iters))
+    if tol is not None and (isinstance(tol, bool) or not isinstance(tol, (int, float)) or not tol >= 0):
+        raise ValueError("%s: tol must be None or a number >= 0, got %r" % (what, tol))
     _ag._check_device(pattern.solver, what, values, b)
-    return _SolveRefined.apply(pattern, values, b, iters)
+    if not return_info:
+        return _SolveRefined.apply(pattern, values, b, iters, None if tol is None else float(tol), False)
+    x, berr, count, status = _SolveRefined.apply(pattern, values, b, iters, None if tol is None else float(tol), True)
+    return x, {"berr": berr, "corrections": count, "factor_status": status}
+
+
+# ---- error bounds; none of these is differentiable ---------------------------
+def _detached(pattern, values, what):
+    _check_values(pattern, values, what)
+    return values.detach().contiguous()
+
+
+def residual(pattern, values, x, b):
+    """(r, d) of x as a solution of A(values) x = b, in the caller's order and shaped like b: r = b - A x,
+    bitwise b - matvec(pattern, values, x), and d = |A| |x| + |b| with duplicates as separate terms, both from
+    one pass over the entries (SymProduct.residual).  Not differentiable."""
+    what = "residual"
+    v = _detached(pattern, values, what)
+    _check_x(pattern, values, x, what)
+    _check_x(pattern, values, b, what, "b")
+    if b.shape != x.shape:
+        raise ValueError("%s: b has shape %s, x has %s" % (what, tuple(b.shape), tuple(x.shape)))
+    with _OnCurrentStream(pattern.solver, v.device):
+        return pattern.product.residual(v, x.detach().contiguous(), b.detach().contiguous())
+
+
+def backward_error(pattern, values, x, b):
+    """the componentwise backward error of x as a solution of A(values) x = b, max_i |b - A x|_i / (|A| |x| +
+    |b|)_i per right-hand side: a float64 device tensor [] for b [n], [k] for [n, k], with a leading B for a
+    batch.  It is the smallest eps for which (A + dA) x = b + db with |dA| <= eps |A| and |db| <= eps |b|
+    (Oettli-Prager); 0 / 0 counts as 0, a non-zero residual over a zero denominator as +inf, and a NaN
+    anywhere in the column gives NaN.  Not differentiable."""
+    r, d = residual(pattern, values, x, b)
+    with _OnCurrentStream(pattern.solver, r.device):
+        return _berr(pattern, r, d, values.dim() == 2)
+
+
+def _jacobi_scale(pattern, data):
+    """s = 1 / sqrt(diag A) in the caller's order from the assembled layout `data` ([dataSize] or [B, ..])"""
+    return 1.0 / torch.sqrt(data.index_select(-1, pattern._index("diag_user", data.device)))
+
+
+def _norm1(pattern, v, s):
+    """max_i (|A| 1)_i, or max_i s_i (|A| s)_i with the scale s ([n] / [B, n], caller's order)"""
+    sol, prod = pattern.solver, pattern.product
+    batched = v.dim() == 2
+    if s is None:
+        w = prod.absMv(v, torch.ones(v.shape[:-1] + (pattern.n,), dtype=v.dtype, device=v.device))
+    else:
+        w = s * prod.absMv(v, s.contiguous())
+    return sol.colMax(w, batched=batched)
+
+
+def norm1(pattern, values, scaled=False):
+    """||A(values)||_1 = max_i (|A| 1)_i from the entries (duplicates as separate terms: an upper bound of the
+    norm where duplicates cancel), a float64 device tensor [] or [B].  scaled=True: max_i s_i (|A| s)_i with
+    s = 1 / sqrt(diag A), the 1-norm of the Jacobi-scaled matrix S A S; the matrix itself is never scaled
+    (the diagonal is read from the assembled layout).  Not differentiable."""
+    v = _detached(pattern, values, "norm1")
+    with _OnCurrentStream(pattern.solver, v.device):
+        s = _jacobi_scale(pattern, pattern.assembly.assemble(v)) if scaled else None
+        return _norm1(pattern, v, s)
+
+
+def cond_estimate(pattern, values, scaled=False, return_info=False):
+    """An estimate of the 1-norm condition number kappa_1(A) = ||A||_1 ||A^-1||_1 of A(values): assembles,
+    factors, and returns norm1 * Solver.invNorm1 as a float64 device tensor [] or [B] (a lower bound, almost
+    always within a factor 3 of the truth).  scaled=True estimates kappa_1(S A S), S = diag(A)^-1/2: the
+    number that bounds the error of a Cholesky solve (van der Sluis), where the raw kappa_1(A) of a badly
+    scaled matrix says nothing.  return_info=True: (estimate, info), info = {"state": the estimator's
+    state record (Solver.readNormEstState), "factor_status": the factor's (Solver.readFactorStatus)} as device
+    tensors.  A factor that broke down gives a non-finite estimate; nothing is read back.  Not
+    differentiable."""
+    what = "cond_estimate"
+    v = _detached(pattern, values, what)
+    _ag._check_device(pattern.solver, what, v)
+    sol = pattern.solver
+    batched = v.dim() == 2
+    with _OnCurrentStream(sol, v.device):
+        L = pattern.assembly.assemble(v)
+        s = _jacobi_scale(pattern, L) if scaled else None
+        members = _ag._members(L) if batched else L
+        sol.factor(members)
+        status = sol.factorStatus(members)
+        D = None
+        if scaled:  # (S A S)^-1 = D A^-1 D with D = S^-1 = sqrt(diag A)
+            D = pattern.toInternal(1.0 / s, 1 if batched else 0).contiguous()
+            D = _ag._members(D) if batched else D
+        inv, state = sol.invNorm1(members, scale=D, return_state=True)
+        est = _norm1(pattern, v, s) * inv
+    return (est, {"state": state, "factor_status": status}) if return_info else est
 
 
 # ---- status of the factor (DESIGN.md section 18) ---------------------------------------------------

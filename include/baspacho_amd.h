@@ -655,6 +655,81 @@ int bsp_sym_product_outer_f32(bsp_solver* s, const bsp_sym_product* p, const flo
 int bsp_sym_product_outer_batched_f32(bsp_solver* s, const bsp_sym_product* p, const float* const* dev_g,
                                       const float* const* dev_x, int64_t q, float* const* dev_grad_values,
                                       int32_t batch);
+/* EXTENSIONS without a counterpart in the reference: error bounds on the device.
+   All run on the stream of bsp_set_stream without atomics or memsets, and without host synchronisation after
+   the first call of a size (the map's upload, the partials of bsp_max_ratio_* / bsp_col_max_*); member b of a
+   batched call is bitwise the single call.  Refused before any device work, non-zero return: a NULL
+   solver, map, array or member (a side of size 0 may be NULL), an empty batch, q < 1, a repeated output
+   pointer, an output that aliases an input or another output, a map built on another solver.
+
+   bsp_sym_product_residual_*: over the row lists of bsp_sym_product_mv_*, in ONE pass with two
+   accumulators: dev_r[i, j] = dev_b[i, j] + (-s), s the terms dev_values[k] * dev_x[idx, j] of row i folded
+   in list order from +0 (bitwise dev_b - mv); dev_d[i, j] = |dev_b[i, j]| + t, t the terms |dev_values[k]| *
+   |dev_x[idx, j]| folded the same way: (|A| |x| + |b|)_i, the Oettli-Prager denominator, duplicates as
+   separate terms.  Every product is rounded before it is added.  dev_x, dev_b, dev_r, dev_d are [order, q]
+   row-major; every element of dev_r and dev_d is written exactly once, neither is read.
+   bsp_sym_product_abs_mv_*: dev_out = |A| |dev_x| alone, the same kernel without dev_b. */
+int bsp_sym_product_residual_f64(bsp_solver* s, const bsp_sym_product* p, const double* dev_values,
+                                 const double* dev_x, const double* dev_b, int64_t q, double* dev_r, double* dev_d);
+int bsp_sym_product_residual_batched_f64(bsp_solver* s, const bsp_sym_product* p, const double* const* dev_values,
+                                         const double* const* dev_x, const double* const* dev_b, int64_t q,
+                                         double* const* dev_r, double* const* dev_d, int32_t batch);
+int bsp_sym_product_abs_mv_f64(bsp_solver* s, const bsp_sym_product* p, const double* dev_values, const double* dev_x,
+                               int64_t q, double* dev_out);
+int bsp_sym_product_abs_mv_batched_f64(bsp_solver* s, const bsp_sym_product* p, const double* const* dev_values,
+                                       const double* const* dev_x, int64_t q, double* const* dev_out, int32_t batch);
+int bsp_sym_product_residual_f32(bsp_solver* s, const bsp_sym_product* p, const float* dev_values, const float* dev_x,
+                                 const float* dev_b, int64_t q, float* dev_r, float* dev_d);
+int bsp_sym_product_residual_batched_f32(bsp_solver* s, const bsp_sym_product* p, const float* const* dev_values,
+                                         const float* const* dev_x, const float* const* dev_b, int64_t q,
+                                         float* const* dev_r, float* const* dev_d, int32_t batch);
+int bsp_sym_product_abs_mv_f32(bsp_solver* s, const bsp_sym_product* p, const float* dev_values, const float* dev_x,
+                               int64_t q, float* dev_out);
+int bsp_sym_product_abs_mv_batched_f32(bsp_solver* s, const bsp_sym_product* p, const float* const* dev_values,
+                                       const float* const* dev_x, int64_t q, float* const* dev_out, int32_t batch);
+/* bsp_max_ratio_*: dev_out[j] (double, [q]; [batch, q] batched) = max over i < n of ratio(|dev_r[i, j]|,
+   dev_d[i, j]) computed in double for both precisions: 0 when r == 0, +inf when d == 0 and r != 0, the
+   quotient otherwise; a NaN in either operand (or inf / inf) makes the column's result NaN; 0 for n == 0.
+   bsp_col_max_*: dev_out[j] = max over i < n of dev_a[i, j] as a double, NaN if any is; -inf for n == 0.
+   Arrays are [n, q] row-major and only read.  Two passes (partials per workgroup kept with the solver, then
+   one workgroup per result); max does not depend on the order, so results are bitwise the numpy
+   statement.  The partials take 16 bytes per 1024 rows, column and member of a chunk; a call that needs more
+   of them than any call before on this solver allocates them, which WAITS FOR THE DEVICE (and cannot be part
+   of a stream capture); every later call of that size or below runs without host synchronisation. */
+int bsp_max_ratio_f64(bsp_solver* s, const double* dev_r, const double* dev_d, int64_t n, int64_t q, double* dev_out);
+int bsp_max_ratio_batched_f64(bsp_solver* s, const double* const* dev_r, const double* const* dev_d, int64_t n,
+                              int64_t q, double* dev_out, int32_t batch);
+int bsp_col_max_f64(bsp_solver* s, const double* dev_a, int64_t n, int64_t q, double* dev_out);
+int bsp_col_max_batched_f64(bsp_solver* s, const double* const* dev_a, int64_t n, int64_t q, double* dev_out,
+                            int32_t batch);
+int bsp_max_ratio_f32(bsp_solver* s, const float* dev_r, const float* dev_d, int64_t n, int64_t q, double* dev_out);
+int bsp_max_ratio_batched_f32(bsp_solver* s, const float* const* dev_r, const float* const* dev_d, int64_t n,
+                              int64_t q, double* dev_out, int32_t batch);
+int bsp_col_max_f32(bsp_solver* s, const float* dev_a, int64_t n, int64_t q, double* dev_out);
+int bsp_col_max_batched_f32(bsp_solver* s, const float* const* dev_a, int64_t n, int64_t q, double* dev_out,
+                            int32_t batch);
+/* bsp_inv_norm1_*: dev_out[m] (double) = an estimate of ||A^-1||_1 for the matrix whose complete bsp_factor is
+   dev_L (a lower bound, almost always within a factor 3); with dev_D (order values in internal order per
+   member; NULL: none) of ||D A^-1 D||_1.  Hager's estimator in Higham's form on a fixed schedule of 10
+   bsp_solve calls with one right-hand side; nothing is read back.  dev_state receives 12 8-byte words per
+   matrix: [0] bits of the estimate (double), [1] the last j, [2] vectors measured (1 .. 5), [3] stop reason
+   (0 none, 1 order 1, 2 repeated sign vector, 3 no increase, 4 pass limit, 5 same column again, 6 a
+   non-finite vector), [4] 1 when the alternating vector's value won, [5 .. 9] the j chosen after pass
+   1 .. 5 (-1: none), [10] bits of the alternating vector's value, [11] 0.
+   WORKSPACE, LAPACK style: dev_work is the caller's, 16-byte aligned, bsp_inv_norm1_work_bytes_* bytes per
+   member (two vectors of order values, rounded up to 16 bytes, plus 16 bytes per 1024 scalars of the order,
+   at least 16), members one after the other.  Nothing is allocated inside the call.  Also refused: a solver
+   that can only factor up to a span, order 0, a workspace that is NULL, misaligned or aliases an operand. */
+int bsp_inv_norm1_work_bytes_f64(const bsp_solver* s, int64_t* out);
+int bsp_inv_norm1_work_bytes_f32(const bsp_solver* s, int64_t* out);
+int bsp_inv_norm1_f64(bsp_solver* s, const double* dev_L, const double* dev_D, void* dev_work, int64_t* dev_state,
+                      double* dev_out);
+int bsp_inv_norm1_batched_f64(bsp_solver* s, const double* const* dev_L, const double* const* dev_D, void* dev_work,
+                              int64_t* dev_state, double* dev_out, int32_t batch);
+int bsp_inv_norm1_f32(bsp_solver* s, const float* dev_L, const float* dev_D, void* dev_work, int64_t* dev_state,
+                      double* dev_out);
+int bsp_inv_norm1_batched_f32(bsp_solver* s, const float* const* dev_L, const float* const* dev_D, void* dev_work,
+                              int64_t* dev_state, double* dev_out, int32_t batch);
 /* out[i_user] = i_internal (order values): the caller's scalar i in the solver's internal vector order
    (param p at spanStart[paramToSpan[p]], its scalars in order) */
 int bsp_scalar_permutation(const bsp_solver* s, int64_t* out);
