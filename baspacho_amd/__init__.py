@@ -1641,6 +1641,25 @@ class SymProduct(_EntryMap):
                                                    entry.ctypes.data_as(_I32P), index.ctypes.data_as(_I32P)))
         return start, entry, index
 
+    def cgPrecondTable(self, kind):
+        """the host plan of a built-in preconditioner of the conjugate gradient, kind
+        "jacobi" or "block_jacobi" (the solver's params; one wider than 32 scalars is refused): (block_start,
+        item_start, entry, pos, info).  The items of block b are (entry[t], pos[t]), t in [item_start[b],
+        item_start[b + 1]), in ascending entry index: the kept entries (i, j), i >= j, inside the block, pos =
+        (i - s) w + (j - s); info = {blocks, items, inverse_elems, max_width}.  Host work only."""
+        kinds = {"jacobi": 1, "block_jacobi": 2}
+        if kind not in kinds:
+            raise ValueError("cgPrecondTable: kind must be 'jacobi' or 'block_jacobi', got %r" % (kind,))
+        k = ctypes.c_int32(kinds[kind])
+        out = (ctypes.c_int64 * 4)()
+        _check(self._lib.bsp_cg_precond_info(self._h, k, out))
+        nb, items = int(out[0]), int(out[1])
+        bs, st = np.empty(nb + 1, dtype=np.int32), np.empty(nb + 1, dtype=np.int32)
+        entry, pos = np.empty(items, dtype=np.int32), np.empty(items, dtype=np.int32)
+        _check(self._lib.bsp_cg_precond_table(self._h, k, bs.ctypes.data_as(_I32P), st.ctypes.data_as(_I32P),
+                                              entry.ctypes.data_as(_I32P), pos.ctypes.data_as(_I32P)))
+        return bs, st, entry, pos, {"blocks": nb, "items": items, "inverse_elems": int(out[2]), "max_width": int(out[3])}
+
     def _run(self, name, fn, a, a_what, x, out, batched):
         """a: values [nnz] / [B, nnz] (mv) or g, shaped like x (outer); x [n] / [n, q], or those with a
         leading B when `batched`; out [.., n(, q)] (mv) or [.., nnz] (outer)"""

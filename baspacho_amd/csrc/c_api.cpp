@@ -996,6 +996,120 @@ static void invNorm1Run(bsp_solver* s, const T* const* L, const T* const* D, voi
 BSP_ERROR_BOUNDS_API(f64, double)
 BSP_ERROR_BOUNDS_API(f32, float)
 #undef BSP_ERROR_BOUNDS_API
+// ---- preconditioned conjugate gradient ------------------------------------------
+int bsp_cg_state_words(int64_t* out) {
+  BSP_TRY
+  if (out == nullptr) throw std::runtime_error("bsp_cg_state_words: out is NULL");
+  *out = 12;
+  BSP_CATCH
+}
+int bsp_cg_work_bytes(const bsp_solver* s, int64_t n, int64_t q, int64_t* out) {
+  BSP_TRY
+  if (s == nullptr || out == nullptr) throw std::runtime_error("bsp_cg_work_bytes: NULL argument");
+  *out = s->solver->cgWorkBytes(n, q);
+  BSP_CATCH
+}
+int bsp_cg_precond_info(const bsp_sym_product* p, int32_t kind, int64_t out[4]) {
+  BSP_TRY
+  if (p == nullptr || out == nullptr) throw std::runtime_error("bsp_cg_precond_info: NULL argument");
+  const CgPrecondPlan& pl = cgPrecondPlan(*p->map, kind);
+  const int64_t v[4] = {pl.numBlocks, pl.numItems(), pl.inverseElems(), pl.maxWidth};
+  std::copy(v, v + 4, out);
+  BSP_CATCH
+}
+int bsp_cg_precond_table(const bsp_sym_product* p, int32_t kind, int32_t* block_start, int32_t* item_start,
+                         int32_t* entry, int32_t* pos) {
+  BSP_TRY
+  if (p == nullptr) throw std::runtime_error("bsp_cg_precond_table: the map is NULL");
+  const CgPrecondPlan& pl = cgPrecondPlan(*p->map, kind);
+  if (block_start == nullptr || item_start == nullptr || (pl.numItems() > 0 && (entry == nullptr || pos == nullptr))) {
+    throw std::runtime_error("bsp_cg_precond_table: an output array is NULL");
+  }
+  std::copy(pl.blockStart.begin(), pl.blockStart.end(), block_start);
+  std::copy(pl.itemStart.begin(), pl.itemStart.end(), item_start);
+  std::copy(pl.itemEntry.begin(), pl.itemEntry.end(), entry);
+  std::copy(pl.itemPos.begin(), pl.itemPos.end(), pos);
+  BSP_CATCH
+}
+template <typename T>
+static void cgRun(bsp_solver* s, const bsp_sym_product* p, int32_t op, int32_t kind, bool plain, int64_t n, int64_t q,
+                  const T* const* in0, const T* const* in1, T* const* out0, T* const* out1, double tol,
+                  int64_t maxSteps, void* work, int64_t* state, int64_t* status, int32_t batch, bool single) {
+  if (s == nullptr) throw std::runtime_error("cg: the solver is NULL");
+  CgArgs<T> a;
+  a.op = op;
+  a.kind = kind;
+  a.plain = plain;
+  a.map = p ? p->map.get() : nullptr;
+  a.n = op == CgBuild && p ? p->map->n : n;
+  a.q = q;
+  a.in0 = in0;
+  a.in1 = in1;
+  a.out0 = out0;
+  a.out1 = out1;
+  a.tol = tol;
+  a.maxSteps = maxSteps;
+  a.work = work;
+  a.state = state;
+  a.status = status;
+  s->solver->cg<T>(a, batch, single);
+}
+#define BSP_CG_API(SFX, T)                                                                                       \
+  int bsp_cg_init_##SFX(bsp_solver* s, int64_t n, int64_t q, const T* b, T* x, T* r, double tol,                 \
+                        int64_t max_steps, int32_t plain, void* work, int64_t* state)                            \
+      BSP_BODY(cgRun<T>(s, nullptr, CgInit, 0, plain != 0, n, q, &b, nullptr, &x, &r, tol, max_steps, work,      \
+                        state, nullptr, 1, true))                                                                \
+  int bsp_cg_init_batched_##SFX(bsp_solver* s, int64_t n, int64_t q, const T* const* b, T* const* x,             \
+                                T* const* r, double tol, int64_t max_steps, int32_t plain, void* work,           \
+                                int64_t* state, int32_t batch)                                                   \
+      BSP_BODY(cgRun<T>(s, nullptr, CgInit, 0, plain != 0, n, q, b, nullptr, x, r, tol, max_steps, work, state,  \
+                        nullptr, batch, false))                                                                  \
+  int bsp_cg_alpha_##SFX(bsp_solver* s, int64_t n, int64_t q, const T* p, const T* ap, void* work,               \
+                         int64_t* state)                                                                         \
+      BSP_BODY(cgRun<T>(s, nullptr, CgAlpha, 0, false, n, q, &p, &ap, nullptr, nullptr, 0, 0, work, state,       \
+                        nullptr, 1, true))                                                                       \
+  int bsp_cg_alpha_batched_##SFX(bsp_solver* s, int64_t n, int64_t q, const T* const* p, const T* const* ap,     \
+                                 void* work, int64_t* state, int32_t batch)                                      \
+      BSP_BODY(cgRun<T>(s, nullptr, CgAlpha, 0, false, n, q, p, ap, nullptr, nullptr, 0, 0, work, state,         \
+                        nullptr, batch, false))                                                                  \
+  int bsp_cg_update_##SFX(bsp_solver* s, int64_t n, int64_t q, const T* p, const T* ap, T* x, T* r,              \
+                          int32_t plain, void* work, int64_t* state)                                             \
+      BSP_BODY(cgRun<T>(s, nullptr, CgUpdate, 0, plain != 0, n, q, &p, &ap, &x, &r, 0, 0, work, state, nullptr,  \
+                        1, true))                                                                                \
+  int bsp_cg_update_batched_##SFX(bsp_solver* s, int64_t n, int64_t q, const T* const* p, const T* const* ap,    \
+                                  T* const* x, T* const* r, int32_t plain, void* work, int64_t* state,           \
+                                  int32_t batch)                                                                 \
+      BSP_BODY(cgRun<T>(s, nullptr, CgUpdate, 0, plain != 0, n, q, p, ap, x, r, 0, 0, work, state, nullptr,      \
+                        batch, false))                                                                           \
+  int bsp_cg_precond_##SFX(bsp_solver* s, const bsp_sym_product* m, int32_t kind, int64_t n, int64_t q,          \
+                           const T* minv, const T* r, T* z, void* work, int64_t* state)                          \
+      BSP_BODY(cgRun<T>(s, m, CgPrecond, kind, false, n, q, &minv, &r, &z, nullptr, 0, 0, work, state, nullptr,  \
+                        1, true))                                                                                \
+  int bsp_cg_precond_batched_##SFX(bsp_solver* s, const bsp_sym_product* m, int32_t kind, int64_t n, int64_t q,  \
+                                   const T* const* minv, const T* const* r, T* const* z, void* work,             \
+                                   int64_t* state, int32_t batch)                                                \
+      BSP_BODY(cgRun<T>(s, m, CgPrecond, kind, false, n, q, minv, r, z, nullptr, 0, 0, work, state, nullptr,     \
+                        batch, false))                                                                           \
+  int bsp_cg_direction_##SFX(bsp_solver* s, int64_t n, int64_t q, const T* z, T* p, int32_t plain, void* work,   \
+                             int64_t* state)                                                                     \
+      BSP_BODY(cgRun<T>(s, nullptr, CgDirection, 0, plain != 0, n, q, &z, nullptr, &p, nullptr, 0, 0, work,      \
+                        state, nullptr, 1, true))                                                                \
+  int bsp_cg_direction_batched_##SFX(bsp_solver* s, int64_t n, int64_t q, const T* const* z, T* const* p,        \
+                                     int32_t plain, void* work, int64_t* state, int32_t batch)                   \
+      BSP_BODY(cgRun<T>(s, nullptr, CgDirection, 0, plain != 0, n, q, z, nullptr, p, nullptr, 0, 0, work, state, \
+                        nullptr, batch, false))                                                                  \
+  int bsp_cg_precond_build_##SFX(bsp_solver* s, const bsp_sym_product* m, int32_t kind, const T* values,         \
+                                 T* minv, void* work, int64_t* status)                                           \
+      BSP_BODY(cgRun<T>(s, m, CgBuild, kind, false, 0, 1, &values, nullptr, &minv, nullptr, 0, 0, work, nullptr, \
+                        status, 1, true))                                                                        \
+  int bsp_cg_precond_build_batched_##SFX(bsp_solver* s, const bsp_sym_product* m, int32_t kind,                  \
+                                         const T* const* values, T* const* minv, void* work, int64_t* status,    \
+                                         int32_t batch)                                                          \
+      BSP_BODY(cgRun<T>(s, m, CgBuild, kind, false, 0, 1, values, nullptr, minv, nullptr, 0, 0, work, nullptr,   \
+                        status, batch, false))
+BSP_CG_API(f64, double)
+BSP_CG_API(f32, float)
+#undef BSP_CG_API
 int bsp_scalar_permutation(const bsp_solver* s, int64_t* out) {
   BSP_TRY
   if (out == nullptr) throw std::runtime_error("bsp_scalar_permutation: out is NULL");

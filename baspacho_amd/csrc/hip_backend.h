@@ -229,6 +229,43 @@ template <typename T>
 void hipBackendNormEstStep(SymbolicCtx& sym, int32_t step, void* work, const T* const* D, int64_t* state,
                            double* out, int64_t batch, bool single);
 
+// Preconditioned conjugate gradient (hip_cg_kernels.h): one piece of an iteration on
+// `batch` matrices with q right-hand sides each.  Vectors are [n, q] row-major; state holds 12 words per
+// (matrix, right-hand side); the work areas sit cgWorkBytes(n, q) apart from `work` on: the partials of
+// the dot products, then, cgBadOffset bytes in, the bad-pivot words of a preconditioner build.
+//   CgInit:       in0 = b; out0 = x, out1 = r (= b - A x, the caller's): the records reset, bb, rr, the
+//                 columns of a zero b cleared; `plain` also starts rz
+//   CgAlpha:      in0 = p, in1 = Ap: pAp, alpha
+//   CgUpdate:     in0 = p, in1 = Ap; out0 = x, out1 = r: x += alpha p, r -= alpha Ap, rr, the iteration
+//                 counted, the stop test; `plain` (no preconditioner) also writes beta
+//   CgPrecond:    in0 = the preconditioner's values (kinds 1, 2), in1 = r; out0 = z (kind 0: only read):
+//                 z = M^-1 r, rz, beta
+//   CgDirection:  in0 = z (r when plain); out0 = p: p = z + beta p
+//   CgBuild:      in0 = the entry values; out0 = the preconditioner's values; status: 2 words per matrix
+enum CgOp : int32_t { CgInit = 0, CgAlpha = 1, CgUpdate = 2, CgPrecond = 3, CgDirection = 4, CgBuild = 5 };
+template <typename T>
+struct CgArgs {
+  int32_t op = CgInit, kind = 0;  // kind: CgPrecondKind (sym_product.h)
+  bool plain = false;
+  int64_t n = 0, q = 1, maxSteps = 0;
+  double tol = 0.0;
+  const SymProductMap* map = nullptr;  // CgPrecond of kinds 1 and 2, CgBuild
+  const T* const* in0 = nullptr;
+  const T* const* in1 = nullptr;
+  T* const* out0 = nullptr;
+  T* const* out1 = nullptr;
+  void* work = nullptr;
+  int64_t* state = nullptr;
+  int64_t* status = nullptr;
+};
+inline int64_t cgBadOffset(int64_t n, int64_t q) {
+  const int64_t parts = (n + 1023) / 1024;
+  return q * (parts > 0 ? parts : 1) * 16;
+}
+inline int64_t cgWorkBytes(int64_t n, int64_t q) { return cgBadOffset(n, q) + ((4 * (n > 0 ? n : 1) + 15) & ~int64_t(15)); }
+template <typename T>
+void hipBackendCg(SymbolicCtx& sym, const CgArgs<T>& a, int64_t batch, bool single);
+
 // Reach solves (hip_reach_kernels.h), one matrix, plan from buildReachPlan (reach.h).
 // reachSolveL: W (numCols x order, column-major, leading dimension order) <- the unit columns of the
 // queries solved through the lumps of their reach below the plan's cut; the caller then runs

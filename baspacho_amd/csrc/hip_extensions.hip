@@ -5,6 +5,7 @@
 // entry point stages its pointer arguments, splits the batch into chunks and enqueues the launches
 // of a chunk on the execution stream (the call path: HipSymbolicCtx::stage / forChunks).
 #include "hip_context.h"
+#include "hip_cg_kernels.h"
 #include "hip_chol_adjoint_kernels.h"
 #include "hip_factor_product.h"
 #include "hip_grad_kernels.h"
@@ -971,6 +972,108 @@ void hipBackendNormEstStep(SymbolicCtx& sym, int32_t step, void* work, const T* 
   });
 }
 
+// ---- preconditioned conjugate gradient (hip_cg_kernels.h) ------------------------
+// one piece of an iteration (CgOp) on `batch` matrices: one to four launches per chunk, nothing allocated
+// but the tables of a preconditioner plan, which the first call that needs them uploads
+static_assert(hipk::kCgMaxBlock == kCgMaxBlockWidth, "the build kernel's LDS holds the widest block of the plan");
+template <typename T>
+void hipBackendCg(SymbolicCtx& sym, const CgArgs<T>& a, int64_t batch, bool single) {
+  using In = hipk::DataRef<const T>;
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  const int64_t n = a.n, q = a.q;
+  const int64_t nParts = (n + hipk::kRedChunk - 1) / hipk::kRedChunk;
+  BASPACHO_CHECK_LT(q, (int64_t)INT32_MAX);
+  BASPACHO_CHECK_LT(nParts * q, (int64_t)INT32_MAX);
+  const int64_t perElemWgs = (n * q + hipk::kRedThreads - 1) / hipk::kRedThreads;
+  BASPACHO_CHECK_LT(perElemWgs, (int64_t)INT32_MAX);
+  const int64_t stride = cgWorkBytes(n, q), badOff = cgBadOffset(n, q);
+  const bool builtIn = a.kind == CgJacobi || a.kind == CgBlockJacobi;
+  hipk::CgPrecondDev pl{};
+  int64_t numBlocks = 0;
+  if ((a.op == CgPrecond && builtIn) || a.op == CgBuild) {
+    const CgPrecondPlan& plan = cgPrecondPlan(*a.map, a.kind);
+    HipEntryMapDev& d = HipEntryMapDev::of(a.map->dev);
+    pl = {d.get(plan.blockStart), d.get(plan.blockOff),  d.get(plan.scalarBlock),
+          d.get(plan.itemStart),  d.get(plan.itemEntry), d.get(plan.itemPos)};
+    numBlocks = plan.numBlocks;
+  }
+  const BatchPtrs<const T> i0 = h.stage(a.in0, batch, single), i1 = h.stage(a.in1, batch, single);
+  const BatchPtrs<T> o0 = h.stage(a.out0, batch, single), o1 = h.stage(a.out1, batch, single);
+  const int threads = hipk::kRedThreads;
+  const double tol2 = a.tol * a.tol;
+  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+    const hipk::CgWork w{static_cast<char*>(a.work) + q0 * stride, stride, badOff};
+    hipk::CgState* st = reinterpret_cast<hipk::CgState*>(a.state) + q0 * q;
+    const dim3 perChunk((unsigned)(nParts * q), nm), perColumn((unsigned)q, nm), perElem((unsigned)perElemWgs, nm);
+    const In out1c{o1.at(q0).single, (const T* const*)o1.at(q0).many};
+    const auto fold = [&](int32_t kind) {
+      hipk::cgFold<<<perColumn, threads, 0, stream>>>((int32_t)q, (int32_t)nParts, kind, a.plain, tol2, a.maxSteps, w,
+                                                     st);
+    };
+    const auto dot = [&](In x, In y, bool always) {
+      if (nParts > 0) {
+        hipk::cgDotPartial<T><<<perChunk, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, x, y, w, st, always);
+      }
+    };
+    switch (a.op) {
+      case CgInit:
+        dot(i0.at(q0), i0.at(q0), true);
+        fold(hipk::CgFoldBB);
+        if (perElemWgs > 0) hipk::cgStart<T><<<perElem, threads, 0, stream>>>(n, (int32_t)q, o0.at(q0), o1.at(q0), st);
+        dot(out1c, out1c, false);
+        fold(hipk::CgFoldRR0);
+        break;
+      case CgAlpha:
+        dot(i0.at(q0), i1.at(q0), false);
+        fold(hipk::CgFoldAlpha);
+        break;
+      case CgUpdate:
+        if (nParts > 0) {
+          hipk::cgUpdateXR<T><<<perChunk, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, i0.at(q0), i1.at(q0),
+                                                                o0.at(q0), o1.at(q0), w, st);
+        }
+        fold(hipk::CgFoldRR);
+        break;
+      case CgPrecond:
+        if (nParts > 0) {
+          if (a.kind == CgJacobi) {
+            hipk::cgPrecond<T, 1><<<perChunk, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, pl, i0.at(q0),
+                                                                    i1.at(q0), o0.at(q0), w, st);
+          } else if (a.kind == CgBlockJacobi) {
+            hipk::cgPrecond<T, 2><<<perChunk, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, pl, i0.at(q0),
+                                                                    i1.at(q0), o0.at(q0), w, st);
+          } else {
+            hipk::cgPrecond<T, 0><<<perChunk, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, pl, i0.at(q0),
+                                                                    i1.at(q0), o0.at(q0), w, st);
+          }
+        }
+        fold(hipk::CgFoldBeta);
+        break;
+      case CgDirection:
+        if (perElemWgs > 0) {
+          hipk::cgDirection<T><<<perElem, threads, 0, stream>>>(n, (int32_t)q, i0.at(q0), o0.at(q0), st);
+        }
+        break;
+      case CgBuild:
+        if (numBlocks > 0) {
+          if (a.kind == CgJacobi) {
+            hipk::cgJacobiBuild<T><<<dim3((unsigned)((n + threads - 1) / threads), nm), threads, 0, stream>>>(
+                n, pl, i0.at(q0), o0.at(q0), w);
+          } else {
+            hipk::cgBlockBuild<T><<<dim3((unsigned)numBlocks, nm), hipk::kCgBuildThreads, 0, stream>>>(pl, i0.at(q0),
+                                                                                                      o0.at(q0), w);
+          }
+        }
+        hipk::cgPrecondStatus<<<dim3(1, nm), threads, 0, stream>>>(numBlocks, pl, w, a.status + 2 * q0);
+        break;
+      default:
+        throw std::runtime_error("cg: unknown operation " + std::to_string(a.op));
+    }
+  });
+}
+
 // ---- reach solves (hip_reach_kernels.h) ---------------------------------------
 // W (numCols x order, column-major) <- the unit columns of the plan's queries, solved through the lumps
 // of their reach below the cut: one memset, the unit entries of the queries behind the cut, one launch
@@ -1120,6 +1223,7 @@ void hipBackendFactorProduct(SymbolicCtx& sym, const T* const* L, bool transpose
                                     int64_t, bool);                                                             \
   template void hipBackendNormEstStep<T>(SymbolicCtx&, int32_t, void*, const T* const*, int64_t*, double*,      \
                                          int64_t, bool);                                                        \
+  template void hipBackendCg<T>(SymbolicCtx&, const CgArgs<T>&, int64_t, bool);                                 \
   template void hipBackendReachSolveL<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                         \
   template void hipBackendGramBlocks<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                          \
   template T* hipBackendReachWorkspace<T>(SymbolicCtx&, int64_t);                                               \

@@ -1204,6 +1204,108 @@ void Solver::invNorm1Estimate(const std::vector<const T*>& L, const std::vector<
   step(NormEstAltSum);
 }
 
+// ---- preconditioned conjugate gradient ----------------------------------------
+int64_t Solver::cgWorkBytes(int64_t n, int64_t q) const {
+  if (n < 0 || n >= (int64_t(1) << 31) || q < 1 || q >= INT32_MAX) {
+    throw std::runtime_error("cgWorkBytes: n = " + std::to_string(n) + ", q = " + std::to_string(q) +
+                             " is outside [0, 2^31) x [1, 2^31 - 1)");
+  }
+  return BaSpaCho::cgWorkBytes(n, q);
+}
+
+template <typename T>
+void Solver::cg(const CgArgs<T>& a, int64_t batch, bool single) const {
+  static const char* names[6] = {"cgInit", "cgAlpha", "cgUpdate", "cgPrecond", "cgDirection", "cgPrecondBuild"};
+  if (a.op < 0 || a.op > CgBuild) throw std::runtime_error("cg: unknown operation " + std::to_string(a.op));
+  const std::string what = names[a.op];
+  const auto fail = [&](const std::string& m) { throw std::runtime_error(what + ": " + m); };
+  const bool builtIn = a.kind == CgJacobi || a.kind == CgBlockJacobi;
+  const bool usesMap = a.op == CgBuild || (a.op == CgPrecond && builtIn);
+  if ((a.op == CgBuild && !builtIn) || (a.op == CgPrecond && !builtIn && a.kind != CgGiven)) {
+    fail("unknown preconditioner kind " + std::to_string(a.kind) + " (0: the caller's z, 1: jacobi, 2: block_jacobi)");
+  }
+  if (usesMap) {
+    if (a.map == nullptr) fail("the map is NULL");
+    if (a.map->solver != this) fail("the map was built on another solver");
+    if (a.map->n != a.n) {
+      fail("n = " + std::to_string(a.n) + ", the map's order is " + std::to_string(a.map->n));
+    }
+  }
+  if (batch < 1) fail("the batch is empty");
+  if (a.n < 0 || a.n >= (int64_t(1) << 31)) fail("n = " + std::to_string(a.n) + " is outside [0, 2^31)");
+  const std::string fault = badVectorCount(a.q);
+  if (!fault.empty()) fail(fault);
+  const int64_t nq = a.n * a.q, parts = (a.n + 1023) / 1024;
+  if (nq >= (int64_t(1) << 40) || parts * a.q >= INT32_MAX) fail("n q = " + std::to_string(nq) + " is too large");
+  if (a.op == CgInit) {
+    if (!(a.tol >= 0.0)) fail("tol = " + std::to_string(a.tol) + "; it must be >= 0");
+    if (a.maxSteps < 0) fail("max_steps = " + std::to_string(a.maxSteps) + "; it must be >= 0");
+  }
+  if (a.work == nullptr) fail("the workspace pointer is NULL");
+  if (reinterpret_cast<uintptr_t>(a.work) % 16 != 0) fail("the workspace is not 16-byte aligned");
+  if (a.op == CgBuild ? a.status == nullptr : a.state == nullptr) {
+    fail(a.op == CgBuild ? "the status pointer is NULL" : "the state pointer is NULL");
+  }
+  // the operands of the piece: (name, pointers, elements, written)
+  struct Slot {
+    const char* name;
+    const T* const* ptrs;
+    int64_t elems;
+    bool written;
+  };
+  const int64_t invElems = usesMap ? cgPrecondPlan(*a.map, a.kind).inverseElems() : 0;
+  const auto c = [](T* const* p) { return const_cast<const T* const*>(p); };
+  std::vector<Slot> slots;
+  switch (a.op) {
+    case CgInit: slots = {{"right-hand side", a.in0, nq, false}, {"x", c(a.out0), nq, true}, {"r", c(a.out1), nq, true}}; break;
+    case CgAlpha: slots = {{"p", a.in0, nq, false}, {"Ap", a.in1, nq, false}}; break;
+    case CgUpdate:
+      slots = {{"p", a.in0, nq, false}, {"Ap", a.in1, nq, false}, {"x", c(a.out0), nq, true}, {"r", c(a.out1), nq, true}};
+      break;
+    case CgPrecond:
+      if (builtIn) slots.push_back({"preconditioner", a.in0, invElems, false});
+      slots.push_back({"r", a.in1, nq, false});
+      slots.push_back({"z", c(a.out0), nq, builtIn});
+      break;
+    case CgDirection: slots = {{a.plain ? "r" : "z", a.in0, nq, false}, {"p", c(a.out0), nq, true}}; break;
+    default: slots = {{"values", a.in0, a.map->nnz, false}, {"preconditioner", c(a.out0), invElems, true}}; break;
+  }
+  struct Region {
+    const char *begin, *end;
+    bool written;
+    std::string name;
+  };
+  std::vector<Region> regions;
+  for (const Slot& s : slots) {
+    if (s.ptrs == nullptr) fail(std::string("the ") + s.name + " pointers are NULL");
+    for (int64_t m = 0; m < batch; m++) {
+      if (s.elems == 0) continue;
+      if (s.ptrs[m] == nullptr) fail(std::string("the ") + s.name + " pointer of batch member " + std::to_string(m) + " is NULL");
+      const char* p = reinterpret_cast<const char*>(s.ptrs[m]);
+      regions.push_back({p, p + s.elems * (int64_t)sizeof(T), s.written,
+                         std::string(s.name) + " of batch member " + std::to_string(m)});
+    }
+  }
+  const char* w0 = static_cast<const char*>(a.work);
+  regions.push_back({w0, w0 + batch * BaSpaCho::cgWorkBytes(a.n, a.q), true, "workspace"});
+  if (a.op == CgBuild) {
+    const char* s0 = reinterpret_cast<const char*>(a.status);
+    regions.push_back({s0, s0 + batch * 16, true, "status"});
+  } else {
+    const char* s0 = reinterpret_cast<const char*>(a.state);
+    regions.push_back({s0, s0 + batch * a.q * 96, true, "state"});
+  }
+  std::sort(regions.begin(), regions.end(), [](const Region& x, const Region& y) { return x.begin < y.begin; });
+  const Region *widest = nullptr, *widestWritten = nullptr;  // the regions so far that end last
+  for (const Region& r : regions) {
+    if (widestWritten != nullptr && r.begin < widestWritten->end) fail("the " + widestWritten->name + " aliases the " + r.name);
+    if (r.written && widest != nullptr && r.begin < widest->end) fail("the " + r.name + " aliases the " + widest->name);
+    if (widest == nullptr || r.end > widest->end) widest = &r;
+    if (r.written && (widestWritten == nullptr || r.end > widestWritten->end)) widestWritten = &r;
+  }
+  hipBackendCg<T>(*symCtx, a, batch, single);
+}
+
 // ---- blocks of A^-1 by reach solves (reach.h) --------------------------------
 ReachPlan Solver::reachPlan(const char* what, const std::vector<int64_t>& params, const std::vector<int64_t>& pairRow,
                             const std::vector<int64_t>& pairCol, const std::vector<int64_t>& outOffsets) const {
@@ -1370,6 +1472,7 @@ void Solver::mulLt(const std::vector<T*>& L, const std::vector<T*>& x, int64_t i
   template void Solver::colMax<T>(BspCVec_##T, BspCVec_##T, int64_t, int64_t, double*, bool) const;            \
   template int64_t Solver::invNorm1WorkBytes<T>() const;                                                       \
   template void Solver::invNorm1Estimate<T>(BspCVec_##T, BspCVec_##T, void*, int64_t*, double*, bool) const;   \
+  template void Solver::cg<T>(const CgArgs<T>&, int64_t, bool) const;                                          \
   template void Solver::reachSolveL<T>(const T*, const std::vector<int64_t>&, T*) const;                       \
   template void Solver::inverseBlocks<T>(const T*, const std::vector<int64_t>&, const std::vector<int64_t>&,   \
                                          T*, const std::vector<int64_t>&) const;

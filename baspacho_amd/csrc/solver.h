@@ -19,6 +19,8 @@ namespace BaSpaCho {
 struct AssemblyMap;
 struct NormalEqMap;
 struct SymProductMap;
+template <typename T>
+struct CgArgs;
 struct ReachPlan;
 
 class Solver {
@@ -286,6 +288,20 @@ class Solver {
   template <typename T>
   void invNorm1Estimate(const std::vector<const T*>& L, const std::vector<const T*>& D, void* work,
                         int64_t* devState, double* devOut, bool single) const;
+  // extension: the pieces of a preconditioned conjugate gradient on the device (DESIGN.md section 24;
+  // hip_cg_kernels.h).  `a` (CgArgs, hip_backend.h) names the piece (CgOp) and its operands: vectors [n, q]
+  // row-major, one pointer per batch member; `state`, 12 words per (member, right-hand side), members one
+  // after the other; `work`, the caller's, cgWorkBytes() per member, 16-byte aligned; `status` (CgBuild), 2
+  // words per member.  n is the caller's (the operator need not be this Solver's matrix), except for the
+  // built-in preconditioners, whose map must be this Solver's and of order n.  The product A p between
+  // CgDirection and CgAlpha is the caller's.  Stopped columns are left bitwise unchanged by every piece.
+  // Runs on the stream of setStream(), nothing is allocated (the first use of a preconditioner uploads its
+  // plan) and nothing read back.  Refused before any device work: an empty batch, n or q out of range, a NULL
+  // or misaligned workspace, a NULL pointer, a map of another Solver or order, a negative or NaN tolerance or
+  // step limit, and a written operand (workspace and records included) that overlaps any other operand.
+  int64_t cgWorkBytes(int64_t n, int64_t q) const;
+  template <typename T>
+  void cg(const CgArgs<T>& a, int64_t batch, bool single) const;
   // extension: blocks of A^-1 anywhere, on or off the pattern of L, by reach solves (DESIGN.md section 20;
   // reach.h, hip_reach_kernels.h).  `L` holds a complete factor() and is only read; params are the
   // caller's param ids (repeats allowed).  Both run on the stream of setStream() without host

@@ -83,4 +83,83 @@ std::unique_ptr<SymProductMap> createSymProductMap(const Solver& solver, int64_t
   return m;
 }
 
+// ---- the built-in preconditioners of the conjugate gradient --------------------
+std::unique_ptr<CgPrecondPlan> createCgPrecondPlan(const SymProductMap& map, int32_t kind,
+                                                   const std::vector<int64_t>& blockSizes) {
+  if (kind != CgJacobi && kind != CgBlockJacobi) {
+    throw std::runtime_error("cg preconditioner: unknown kind " + std::to_string(kind) +
+                             " (1: jacobi, 2: block_jacobi)");
+  }
+  std::unique_ptr<CgPrecondPlan> p(new CgPrecondPlan);
+  p->kind = kind;
+  p->n = map.n;
+  if (kind == CgJacobi) {
+    p->blockStart.resize(map.n + 1);
+    std::iota(p->blockStart.begin(), p->blockStart.end(), 0);
+  } else {
+    int64_t at = 0;
+    p->blockStart.push_back(0);
+    for (size_t b = 0; b < blockSizes.size(); b++) {
+      const int64_t w = blockSizes[b];
+      if (w < 1) throw std::runtime_error("cg preconditioner: param " + std::to_string(b) + " has size " + std::to_string(w));
+      if (w > kCgMaxBlockWidth) {
+        throw std::runtime_error("cg preconditioner: param " + std::to_string(b) + " has " + std::to_string(w) +
+                                 " scalars; block_jacobi takes blocks of at most " +
+                                 std::to_string(kCgMaxBlockWidth));
+      }
+      at += w;
+      p->blockStart.push_back((int32_t)std::min<int64_t>(at, INT32_MAX));
+    }
+    if (at != map.n) {
+      throw std::runtime_error("cg preconditioner: the params hold " + std::to_string(at) + " scalars, the order is " +
+                               std::to_string(map.n));
+    }
+  }
+  p->numBlocks = (int64_t)p->blockStart.size() - 1;
+  p->scalarBlock.resize(map.n);
+  p->blockOff.assign(p->numBlocks + 1, 0);
+  for (int64_t b = 0; b < p->numBlocks; b++) {
+    const int64_t w = p->blockStart[b + 1] - p->blockStart[b];
+    p->maxWidth = std::max(p->maxWidth, w);
+    p->blockOff[b + 1] = p->blockOff[b] + w * w;
+    std::fill(p->scalarBlock.begin() + p->blockStart[b], p->scalarBlock.begin() + p->blockStart[b + 1], (int32_t)b);
+  }
+  // the kept entries inside a diagonal block, in ascending entry index, then stably by block
+  std::vector<int32_t> items;
+  for (int64_t k = 0; k < map.nnz; k++) {
+    const int32_t i = map.entRow[k], j = map.entCol[k];
+    if (i >= 0 && p->scalarBlock[i] == p->scalarBlock[j]) items.push_back((int32_t)k);
+  }
+  RunList runs;
+  const auto entryOf = [&](int32_t t) { return items[t]; };
+  runs.build((int64_t)items.size(), p->numBlocks, [&](int32_t t) { return p->scalarBlock[map.entRow[items[t]]]; },
+             entryOf,
+             [&](int32_t t) {
+               const int32_t k = items[t], b = p->scalarBlock[map.entRow[k]], s = p->blockStart[b];
+               return (map.entRow[k] - s) * (p->blockStart[b + 1] - s) + (map.entCol[k] - s);
+             },
+             false);
+  p->itemStart = std::move(runs.start);
+  p->itemEntry = std::move(runs.entry);
+  p->itemPos = std::move(runs.idx);
+  return p;
+}
+
+const CgPrecondPlan& cgPrecondPlan(const SymProductMap& map, int32_t kind) {
+  if (kind != CgJacobi && kind != CgBlockJacobi) {
+    throw std::runtime_error("cg preconditioner: unknown kind " + std::to_string(kind) +
+                             " (1: jacobi, 2: block_jacobi)");
+  }
+  if (!map.cgPlans[kind]) {
+    std::vector<int64_t> sizes;
+    if (kind == CgBlockJacobi) {
+      if (map.solver == nullptr) throw std::runtime_error("cg preconditioner: the map has no solver to take params from");
+      const ScalarLocator loc(*map.solver);
+      for (size_t b = 0; b + 1 < loc.userStart.size(); b++) sizes.push_back(loc.userStart[b + 1] - loc.userStart[b]);
+    }
+    map.cgPlans[kind] = createCgPrecondPlan(map, kind, sizes);
+  }
+  return *map.cgPlans[kind];
+}
+
 }  // namespace BaSpaCho

@@ -22,6 +22,24 @@
 
 namespace BaSpaCho {
 
+// The plan of a built-in preconditioner of the conjugate gradient: the diagonal
+// blocks of A and the entries that land in each.  CgJacobi: every scalar is a block of width 1.
+// CgBlockJacobi: the blocks are the solver's params, in the caller's order.  The items of block b are
+// (itemEntry[t], itemPos[t]), t in [itemStart[b], itemStart[b + 1]), in ascending entry index: the kept
+// entry k at (i, j), i >= j, both in block b, with itemPos = (i - s) w + (j - s), s the block's first
+// scalar and w its width.  The inverse of block b takes the elements [blockOff[b], blockOff[b + 1]) of
+// the preconditioner's values, row-major.
+enum CgPrecondKind : int32_t { CgGiven = 0, CgJacobi = 1, CgBlockJacobi = 2 };
+constexpr int64_t kCgMaxBlockWidth = 32;
+struct CgPrecondPlan {
+  int32_t kind = CgJacobi;
+  int64_t n = 0, numBlocks = 0, maxWidth = 0;
+  std::vector<int32_t> blockStart, scalarBlock, itemStart, itemEntry, itemPos;
+  std::vector<int64_t> blockOff;
+  int64_t inverseElems() const { return blockOff.empty() ? 0 : blockOff.back(); }
+  int64_t numItems() const { return (int64_t)itemEntry.size(); }
+};
+
 struct SymProductMap {
   const Solver* solver = nullptr;  // the solver the map was built for (its order, its stream)
   int32_t triangle = AssemblyLower;
@@ -34,6 +52,9 @@ struct SymProductMap {
   std::vector<int32_t> entRow, entCol;
 
   mutable HipEntryMapDevPtr dev;
+
+  // the preconditioner plans, built by the first call that asks for one (cgPrecondPlan)
+  mutable std::unique_ptr<CgPrecondPlan> cgPlans[3];
 
   int64_t numTerms() const { return (int64_t)rows.entry.size(); }
   // bytes each part takes on the device once uploaded
@@ -51,5 +72,13 @@ std::unique_ptr<SymProductMap> createSymProductMap(int64_t n, int64_t nnz, const
 // ... for `solver`: n = solver.order(), and the map runs on that solver alone
 std::unique_ptr<SymProductMap> createSymProductMap(const Solver& solver, int64_t nnz, const int64_t* rows,
                                                    const int64_t* cols, int32_t triangle);
+
+// The plan of `kind` (CgJacobi or CgBlockJacobi) over the entries of `map`, from blocks of `blockSizes`
+// scalars in the caller's order (they sum to map.n; ignored for CgJacobi).  Throws for a block wider than
+// kCgMaxBlockWidth, naming it.  Host only: one counting sort.
+std::unique_ptr<CgPrecondPlan> createCgPrecondPlan(const SymProductMap& map, int32_t kind,
+                                                   const std::vector<int64_t>& blockSizes);
+// ... of the map's solver (its params), cached in the map
+const CgPrecondPlan& cgPrecondPlan(const SymProductMap& map, int32_t kind);
 
 }  // namespace BaSpaCho

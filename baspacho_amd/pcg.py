@@ -127,3 +127,42 @@ class PCG:
             p = z + (rz_new / rz) * p
             rz = rz_new
         return it, res
+
+
+class DevicePCG:
+    """PCG with its scalars on the device: the interface of PCG, the kernels of
+    sparse.solve_cg.  alpha, beta, the residual norms and the stop test live in a state record that the
+    kernels read; the iterations are queued in chunks of `check_every`, and the host reads the stop word once
+    per chunk (check_every=None: max_steps iterations, one read at the end for the return value).  The
+    operator and the preconditioner are the caller's callables, so TrailingOperator and the preconditioner
+    classes above work unchanged; one of them must carry the Solver whose stream the kernels run on (an
+    attribute `solver`), or pass solver=.  solve(x, b) overwrites x, starting from 0 like PCG.solve, and
+    returns (iterations, relative residual); `info` then holds the decoded state record."""
+
+    def __init__(self, apply_inv_m, apply_a, wanted_residual=1e-10, max_steps=100, check_every=8, solver=None):
+        from . import cg as _cg
+        _cg.check_settings("DevicePCG", wanted_residual, max_steps, check_every)
+        self.apply_inv_m, self.apply_a = apply_inv_m, apply_a
+        self.wanted_residual, self.max_steps, self.check_every = wanted_residual, max_steps, check_every
+        self.solver = solver or getattr(apply_a, "solver", None) or getattr(apply_inv_m, "solver", None)
+        if self.solver is None:
+            raise TypeError("DevicePCG: neither apply_a nor apply_inv_m has a `solver`; pass solver=")
+        self.info = None
+
+    def solve(self, x, b):
+        from . import cg as _cg
+        from .autograd import _OnCurrentStream
+        if x.dim() != 1 or x.shape != b.shape or x.dtype != b.dtype or x.device != b.device or not x.is_contiguous():
+            raise ValueError("DevicePCG.solve: x and b must be contiguous vectors of one shape, dtype and device")
+        n = x.shape[0]
+        x.zero_()
+        b2, x2 = b.contiguous().reshape(n, 1), x.reshape(n, 1)
+        r2 = b2.clone()
+        m = None if isinstance(self.apply_inv_m, IdentityPrecond) else \
+            (lambda r: self.apply_inv_m(r.reshape(n)).reshape(n, 1))
+        with _OnCurrentStream(self.solver, x.device):
+            run = _cg.CgRun(self.solver, b2, x2, r2, lambda p, ap: self.apply_a(p.reshape(n)).reshape(n, 1), m,
+                            self.wanted_residual, self.max_steps).run(self.check_every)
+            relres = run.relres()
+        self.info = _cg.read_state(run.state)[0]
+        return self.info["iterations"], float(relres[0])

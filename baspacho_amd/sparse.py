@@ -23,6 +23,7 @@
     x, info = S.solve_refined(pat, values, b, iters=6, tol=1e-14, return_info=True)  # checked refinement
     e = S.backward_error(pat, values, x, b)        # max_i |b - A x|_i / (|A| |x| + |b|)_i per right-hand side
     k = S.cond_estimate(pat, values, scaled=True)  # kappa_1 of the Jacobi-scaled matrix, from the factor
+    x = S.solve_cg(pat, values, b, precond="block_jacobi", tol=1e-10)  # device-resident PCG, no layout, no factor
 
     jpat = S.JacobianPattern(jrows, jcols, m, n)   # once per Jacobian pattern: solver + normal-equations maps
     x = S.lstsq(jpat, jvalues, r, damping=(a, b))  # x = (J^T J + D)^-1 J^T r, D = a diag(J^T J) + b I
@@ -66,11 +67,13 @@ marginalize eliminates every scalar outside `keep`: S = A
 r = b2 - A21 A11^-1 b1 with block 2 the kept scalars, rows and columns in the order of `keep`.  inv(S) is
 the `keep` block of inv(A): S and r are the precision and the information vector of the marginal.
 """
+import ctypes
+
 import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import Settings, SparseStructure, create_solver
+from . import Settings, SparseStructure, create_solver, _call, _count, _ptr_arg, _suffix
 from . import autograd as _ag
 from .autograd import _OnCurrentStream
 
@@ -79,7 +82,9 @@ __all__ = ["SymmetricPattern", "JacobianPattern", "assemble", "solve", "logdet",
            "hessian", "jt_vec", "j_vec", "normal_equations", "lstsq", "check_positive_definite",
            "matvec", "quad_form", "log_prob", "solve_refined", "whiten", "sample_cov",
            # error bounds: none of these is differentiable
-           "residual", "backward_error", "norm1", "cond_estimate"]
+           "residual", "backward_error", "norm1", "cond_estimate",
+           # conjugate gradient from the entries
+           "solve_cg"]
 
 
 def _host_i64(a):
@@ -909,6 +914,156 @@ def solve_refined(pattern, values, b, iters=3, tol=None, return_info=False):
         return _SolveRefined.apply(pattern, values, b, iters, None if tol is None else float(tol), False)
     x, berr, count, status = _SolveRefined.apply(pattern, values, b, iters, None if tol is None else float(tol), True)
     return x, {"berr": berr, "corrections": count, "factor_status": status}
+
+
+# ---- conjugate gradient from the entries ---------------------------------------
+def _cg_run(pattern, v, b, precond, tol, max_steps, check_every, x0, cache):
+    """the iteration of solve_cg on detached, contiguous operands: (x shaped like b, the CgRun).  `cache`
+    keeps what the preconditioner built from v, for the backward pass"""
+    from . import cg as _cg
+    sol, prod = pattern.solver, pattern.product
+    batched = v.dim() == 2
+    dim = 1 if batched else 0
+    has_k = b.dim() == dim + 2
+    shape3 = tuple(b.shape) if has_k else tuple(b.shape) + (1,)
+    b3 = b.contiguous().reshape(shape3)
+    if x0 is None:
+        x3, r3 = torch.zeros_like(b3), b3.clone()
+    else:
+        x3 = x0.detach().contiguous().reshape(shape3).clone()
+        r3 = prod.residual(v, x3, b3)[0]  # bitwise b - A x0
+    q = shape3[-1]
+    mv_args = {}
+
+    def apply_a(p, ap):
+        if "a" not in mv_args:  # the operands never move: their pointers are taken once
+            mv_args["a"] = [_ptr_arg(t.unbind(0) if batched else [t], batched) for t in (v, p, ap)]
+        pv, pp, pa = mv_args["a"]
+        _call(prod._lib, "bsp_sym_product_mv_", batched, _suffix(v), sol._h, prod._h, pv, pp, ctypes.c_int64(q), pa,
+              *_count(v, batched))
+        return ap
+
+    pc = None
+    if precond in ("jacobi", "block_jacobi"):
+        if precond not in cache:
+            cache[precond] = _cg.Preconditioner(prod, precond, v)
+        pc = cache[precond]
+    elif precond == "factor32":
+        if "L32" not in cache:
+            L32 = pattern.assembly.assemble(v.float())
+            sol.factor(_ag._members(L32) if batched else L32)
+            cache["L32"] = L32
+        L32 = cache["L32"]
+
+        def pc(r):
+            rr = r if has_k else r.reshape(b.shape)
+            rt = _ag._to_cols(pattern.toInternal(rr.float(), dim), batched)
+            _ag._solve_cols(sol, L32, rt)
+            return pattern.fromInternal(_ag._from_cols(rt, rr.shape), dim).double().reshape(shape3)
+    elif precond is not None:
+        def pc(r):
+            z = precond(r if has_k else r.reshape(b.shape))
+            if not isinstance(z, torch.Tensor) or z.shape != b.shape:
+                raise ValueError("solve_cg: the preconditioner must return a tensor of shape %s" % (tuple(b.shape),))
+            return z.reshape(shape3)
+    run = _cg.CgRun(sol, b3, x3, r3, apply_a, pc, tol, max_steps).run(check_every)
+    return x3.reshape(b.shape), run
+
+
+class _SolveCG(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pattern, values, b, precond, tol, max_steps, check_every, x0):
+        v = values.detach().contiguous()
+        cache = {}
+        with _OnCurrentStream(pattern.solver, v.device):
+            x, run = _cg_run(pattern, v, b.detach(), precond, tol, max_steps, check_every, x0, cache)
+            has_k = b.dim() == v.dim() + 1
+            info = [t if has_k else t.squeeze(-1) for t in (run.iterations(), run.stop(), run.relres())]
+            info.append(run.state if has_k else run.state.squeeze(-2))
+            built = cache.get(precond) if isinstance(precond, str) else None
+            status = built.status if built is not None and hasattr(built, "status") else torch.empty(0, device=v.device)
+        ctx.pattern, ctx.cache, ctx.settings = pattern, cache, (precond, tol, max_steps, check_every)
+        ctx.save_for_backward(v, x)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*info, status)
+        return (x, *info, status)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, *_):
+        if g is None or not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+            return (None,) * 8
+        pattern, (v, x) = ctx.pattern, ctx.saved_tensors
+        precond, tol, max_steps, check_every = ctx.settings
+        gv = None
+        with _OnCurrentStream(pattern.solver, g.device):
+            # A is symmetric: the same iteration, the same preconditioner, on the incoming gradient
+            gb, _ = _cg_run(pattern, v, g.contiguous(), precond, tol, max_steps, check_every, None, ctx.cache)
+            if ctx.needs_input_grad[1]:
+                gv = pattern.product.outer(gb, x, batched=v.dim() == 2).neg_()
+        return (None, gv, gb if ctx.needs_input_grad[2] else None) + (None,) * 5
+
+
+def solve_cg(pattern, values, b, precond="block_jacobi", tol=1e-10, max_steps=100, check_every=8, x0=None,
+             return_info=False):
+    """x = A(values)^-1 b in the caller's order by preconditioned conjugate gradient, straight from the
+    entries: A p is matvec's kernel, the layout is never allocated (except for "factor32"), and the scalars of
+    the iteration (alpha, beta, the residual norms, the stop reason) live in a state record on the device that
+    the kernels read.  values [nnz] / [B, nnz], b [n] / [n, k] with a leading B for a batch, float64 or
+    float32: every (matrix, right-hand side) is a problem of its own and stops on its own, when
+    |r|^2 <= tol^2 |b|^2 for the recurrence residual r (converged), after max_steps iterations, on a breakdown
+    (p.Ap or r.z not > 0: A or the preconditioner is not positive definite), on a non-finite sum, or at once
+    for a zero b (x = 0).  A stopped problem is frozen by the kernels.
+
+    precond: None; "jacobi" (z_i = r_i / A_ii); "block_jacobi" (the inverses of the diagonal blocks of the
+    pattern's params, at most 32 scalars each: a ValueError names a wider one), both built and applied on the
+    device; "factor32" (float64 only: the fp32 layout is assembled and factored once and z = the fp32 solve of
+    r, as in solve_refined: the mixed-precision pattern, with an iteration instead of a fixed number of
+    corrections); or a callable r -> z on tensors shaped like b that enqueues device work.
+
+    Iterations are queued in chunks of check_every; after each chunk the host reads the stop words once and
+    stops queuing when no problem runs.  check_every=None queues max_steps iterations without any read.  The
+    result is bitwise the same for every check_every.  x0: the start, shaped like b (default 0).
+
+    return_info=True: (x, info), info = device tensors "iterations", "stop" (0 running .. 5 zero right-hand
+    side, baspacho_amd.cg.STOPS) and "relres" = sqrt(rr / bb) of the recurrence residual, shaped [] / [k] with a
+    leading B for a batch, "state", the int64 records themselves ([.., 12]; baspacho_amd.cg.read_state decodes
+    them), and for a built-in preconditioner "precond_status", int64 [2] / [B, 2] = {the
+    caller's scalar of the lowest bad pivot of the preconditioner or -1, the number of bad blocks}.
+
+    Differentiable in values and b (x0 gets no gradient): b's gradient is solve_cg of the incoming gradient
+    with the same settings and the same preconditioner, that of values is -outer(gb, x); both are as exact as
+    the two solves.  Runs on the current torch stream; no stream capture."""
+    from . import cg as _cg
+    what = "solve_cg"
+    _check_values(pattern, values, what)
+    dim = _check_x(pattern, values, b, what, "b")
+    _cg.check_settings(what, tol, max_steps, check_every)
+    if x0 is not None:
+        if not isinstance(x0, torch.Tensor) or x0.shape != b.shape or x0.dtype != b.dtype or x0.device != b.device:
+            raise ValueError("%s: x0 must be a %s tensor of b's shape %s on %s" % (what, b.dtype, tuple(b.shape), b.device))
+    if isinstance(precond, str):
+        if precond not in ("jacobi", "block_jacobi", "factor32"):
+            raise ValueError("%s: precond must be None, 'jacobi', 'block_jacobi', 'factor32' or a callable, got %r"
+                             % (what, precond))
+        if precond == "factor32" and values.dtype != torch.float64:
+            raise TypeError("%s: precond 'factor32' needs float64 values and b, got %s" % (what, values.dtype))
+        if precond == "block_jacobi" and int(pattern.param_sizes.max(initial=0)) > _cg.MAX_BLOCK:
+            p = int(np.argmax(pattern.param_sizes > _cg.MAX_BLOCK))
+            raise ValueError("%s: param %d has %d scalars; 'block_jacobi' takes params of at most %d"
+                             % (what, p, int(pattern.param_sizes[p]), _cg.MAX_BLOCK))
+    elif precond is not None and not callable(precond):
+        raise ValueError("%s: precond must be None, 'jacobi', 'block_jacobi', 'factor32' or a callable, got %r"
+                         % (what, precond))
+    _ag._check_device(pattern.solver, what, values, b)
+    x, iters, stop, relres, state, status = _SolveCG.apply(pattern, values, b, precond, float(tol), max_steps,
+                                                           check_every, x0)
+    if not return_info:
+        return x
+    info = {"iterations": iters, "stop": stop, "relres": relres, "state": state}
+    if precond in ("jacobi", "block_jacobi"):
+        info["precond_status"] = status
+    return x, info
 
 
 # ---- error bounds (DESIGN.md section 23); none of these is differentiable ---------------------------

@@ -730,6 +730,104 @@ int bsp_inv_norm1_f32(bsp_solver* s, const float* dev_L, const float* dev_D, voi
                       double* dev_out);
 int bsp_inv_norm1_batched_f32(bsp_solver* s, const float* const* dev_L, const float* const* dev_D, void* dev_work,
                               int64_t* dev_state, double* dev_out, int32_t batch);
+/* EXTENSION without a counterpart in the reference's library (its examples/PCG.cpp is caller-side): the
+   pieces of a preconditioned conjugate gradient whose scalars stay on the device.
+   One problem per (matrix, right-hand side): vectors are [n, q] row-major, dev_state holds
+   bsp_cg_state_words = 12 8-byte words per problem, problem j of member m at (m q + j) 12: [0] iterations,
+   [1] stop reason (0 running, 1 converged: rr <= tol^2 bb, 2 step limit, 3 breakdown: p.Ap or r.z not > 0,
+   4 a non-finite sum, 5 zero right-hand side), then the doubles [2] rz, [3] pAp, [4] rr, [5] bb = b.b,
+   [6] alpha, [7] beta, [8] tol^2, then [9] the step limit, [10], [11] 0.  Every piece reads its scalars from
+   the records and leaves x, r, p, z and the record of a stopped problem bitwise unchanged; nothing is read
+   back by the library, so the caller may queue any number of iterations and look at the stop words when it
+   likes.  One iteration is: Ap = A p (the caller's: bsp_sym_product_mv_* or any operator); alpha; update;
+   precond; direction (with plain = 1, no preconditioner: alpha; update; direction with dev_z = dev_r).
+     init:       dev_x holds the start, dev_r = b - A x for it (both the caller's): the records are reset,
+                 bb and rr taken, the problems of a zero b cleared (x = r = 0).  Then precond and direction
+                 (plain: direction alone) give the first p.
+     alpha:      pAp = p.Ap, alpha = rz / pAp
+     update:     x += alpha p, r -= alpha Ap and rr = r.r of the new r in one pass; the iteration is counted
+                 and the stop test made
+     precond:    kind 0: dev_z is the caller's M^-1 r and only read; kind 1 (Jacobi) and 2 (block-Jacobi over
+                 the solver's params, at most 32 scalars each): dev_z = M^-1 dev_r from dev_minv, which
+                 bsp_cg_precond_build_* wrote.  With rz = r.z of the same pass: beta = rz / rz(old)
+     direction:  p = z + beta p
+     precond_build: dev_minv (bsp_cg_precond_info's third figure elements per member) from the entry values:
+                 the diagonal blocks summed in ascending entry index, factored and inverted in double, stored
+                 in the data type.  dev_status receives 2 words per member: the caller's scalar of the lowest
+                 bad pivot (not positive and finite) or -1, and the number of bad blocks; a bad block's
+                 inverse is the zero matrix.
+   Dot products are taken in double for both precisions, in the two-pass order of bsp_max_ratio_* with every
+   product rounded before it is added; the vector updates round every product in the data type.  No
+   atomics; member b of a batched call is bitwise the single call.  WORKSPACE: dev_work is the caller's,
+   16-byte aligned, bsp_cg_work_bytes bytes per member (16 bytes per 1024 rows and right-hand side, at least
+   16 per right-hand side, plus 4 bytes per row rounded up to 16), members one after the other; nothing is
+   allocated inside a call (the first use of a built-in preconditioner uploads its tables).  Refused before any
+   device work: NULL arguments, an empty batch, n or q out of range, a misaligned workspace, a map of another
+   solver or order, and a written operand that overlaps any other operand, workspace and records included.
+   bsp_cg_precond_info: out = {blocks, items, elements of the inverse, widest block};
+   bsp_cg_precond_table: the plan's tables (host only): block_start [blocks + 1], item_start [blocks + 1],
+   and per item its entry and its position (i - s) w + (j - s) inside its block. */
+int bsp_cg_state_words(int64_t* out);
+int bsp_cg_work_bytes(const bsp_solver* s, int64_t n, int64_t q, int64_t* out);
+int bsp_cg_precond_info(const bsp_sym_product* p, int32_t kind, int64_t out[4]);
+int bsp_cg_precond_table(const bsp_sym_product* p, int32_t kind, int32_t* block_start, int32_t* item_start,
+                         int32_t* entry, int32_t* pos);
+int bsp_cg_init_f64(bsp_solver* s, int64_t n, int64_t q, const double* dev_b, double* dev_x, double* dev_r, double tol,
+                    int64_t max_steps, int32_t plain, void* dev_work, int64_t* dev_state);
+int bsp_cg_init_batched_f64(bsp_solver* s, int64_t n, int64_t q, const double* const* dev_b, double* const* dev_x,
+                            double* const* dev_r, double tol, int64_t max_steps, int32_t plain, void* dev_work,
+                            int64_t* dev_state, int32_t batch);
+int bsp_cg_alpha_f64(bsp_solver* s, int64_t n, int64_t q, const double* dev_p, const double* dev_ap, void* dev_work,
+                     int64_t* dev_state);
+int bsp_cg_alpha_batched_f64(bsp_solver* s, int64_t n, int64_t q, const double* const* dev_p,
+                             const double* const* dev_ap, void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_cg_update_f64(bsp_solver* s, int64_t n, int64_t q, const double* dev_p, const double* dev_ap, double* dev_x,
+                      double* dev_r, int32_t plain, void* dev_work, int64_t* dev_state);
+int bsp_cg_update_batched_f64(bsp_solver* s, int64_t n, int64_t q, const double* const* dev_p,
+                              const double* const* dev_ap, double* const* dev_x, double* const* dev_r, int32_t plain,
+                              void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_cg_precond_f64(bsp_solver* s, const bsp_sym_product* p, int32_t kind, int64_t n, int64_t q,
+                       const double* dev_minv, const double* dev_r, double* dev_z, void* dev_work, int64_t* dev_state);
+int bsp_cg_precond_batched_f64(bsp_solver* s, const bsp_sym_product* p, int32_t kind, int64_t n, int64_t q,
+                               const double* const* dev_minv, const double* const* dev_r, double* const* dev_z,
+                               void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_cg_direction_f64(bsp_solver* s, int64_t n, int64_t q, const double* dev_z, double* dev_p, int32_t plain,
+                         void* dev_work, int64_t* dev_state);
+int bsp_cg_direction_batched_f64(bsp_solver* s, int64_t n, int64_t q, const double* const* dev_z, double* const* dev_p,
+                                 int32_t plain, void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_cg_precond_build_f64(bsp_solver* s, const bsp_sym_product* p, int32_t kind, const double* dev_values,
+                             double* dev_minv, void* dev_work, int64_t* dev_status);
+int bsp_cg_precond_build_batched_f64(bsp_solver* s, const bsp_sym_product* p, int32_t kind,
+                                     const double* const* dev_values, double* const* dev_minv, void* dev_work,
+                                     int64_t* dev_status, int32_t batch);
+int bsp_cg_init_f32(bsp_solver* s, int64_t n, int64_t q, const float* dev_b, float* dev_x, float* dev_r, double tol,
+                    int64_t max_steps, int32_t plain, void* dev_work, int64_t* dev_state);
+int bsp_cg_init_batched_f32(bsp_solver* s, int64_t n, int64_t q, const float* const* dev_b, float* const* dev_x,
+                            float* const* dev_r, double tol, int64_t max_steps, int32_t plain, void* dev_work,
+                            int64_t* dev_state, int32_t batch);
+int bsp_cg_alpha_f32(bsp_solver* s, int64_t n, int64_t q, const float* dev_p, const float* dev_ap, void* dev_work,
+                     int64_t* dev_state);
+int bsp_cg_alpha_batched_f32(bsp_solver* s, int64_t n, int64_t q, const float* const* dev_p,
+                             const float* const* dev_ap, void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_cg_update_f32(bsp_solver* s, int64_t n, int64_t q, const float* dev_p, const float* dev_ap, float* dev_x,
+                      float* dev_r, int32_t plain, void* dev_work, int64_t* dev_state);
+int bsp_cg_update_batched_f32(bsp_solver* s, int64_t n, int64_t q, const float* const* dev_p,
+                              const float* const* dev_ap, float* const* dev_x, float* const* dev_r, int32_t plain,
+                              void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_cg_precond_f32(bsp_solver* s, const bsp_sym_product* p, int32_t kind, int64_t n, int64_t q,
+                       const float* dev_minv, const float* dev_r, float* dev_z, void* dev_work, int64_t* dev_state);
+int bsp_cg_precond_batched_f32(bsp_solver* s, const bsp_sym_product* p, int32_t kind, int64_t n, int64_t q,
+                               const float* const* dev_minv, const float* const* dev_r, float* const* dev_z,
+                               void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_cg_direction_f32(bsp_solver* s, int64_t n, int64_t q, const float* dev_z, float* dev_p, int32_t plain,
+                         void* dev_work, int64_t* dev_state);
+int bsp_cg_direction_batched_f32(bsp_solver* s, int64_t n, int64_t q, const float* const* dev_z, float* const* dev_p,
+                                 int32_t plain, void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_cg_precond_build_f32(bsp_solver* s, const bsp_sym_product* p, int32_t kind, const float* dev_values,
+                             float* dev_minv, void* dev_work, int64_t* dev_status);
+int bsp_cg_precond_build_batched_f32(bsp_solver* s, const bsp_sym_product* p, int32_t kind,
+                                     const float* const* dev_values, float* const* dev_minv, void* dev_work,
+                                     int64_t* dev_status, int32_t batch);
 /* out[i_user] = i_internal (order values): the caller's scalar i in the solver's internal vector order
    (param p at spanStart[paramToSpan[p]], its scalars in order) */
 int bsp_scalar_permutation(const bsp_solver* s, int64_t* out);
