@@ -1110,6 +1110,115 @@ static void cgRun(bsp_solver* s, const bsp_sym_product* p, int32_t op, int32_t k
 BSP_CG_API(f64, double)
 BSP_CG_API(f32, float)
 #undef BSP_CG_API
+// ---- the Lanczos recurrence -----------------------------------------------------
+int bsp_lanczos_state_words(int64_t* out) {
+  BSP_TRY
+  if (out == nullptr) throw std::runtime_error("bsp_lanczos_state_words: out is NULL");
+  *out = 12;
+  BSP_CATCH
+}
+int bsp_lanczos_work_bytes(const bsp_solver* s, int64_t n, int64_t q, int64_t kmax, int64_t* out) {
+  BSP_TRY
+  if (s == nullptr || out == nullptr) throw std::runtime_error("bsp_lanczos_work_bytes: NULL argument");
+  *out = s->solver->lanczosWorkBytes(n, q, kmax);
+  BSP_CATCH
+}
+template <typename T>
+static void lanczosRun(bsp_solver* s, int32_t op, int64_t n, int64_t q, int64_t kmax, const T* const* vec,
+                       T* const* basis, int64_t slotStride, int64_t slots, int64_t slot, int64_t prev, int64_t count,
+                       bool fold, double breakdown, double* coef, void* work, int64_t* state, int32_t batch,
+                       bool single) {
+  if (s == nullptr) throw std::runtime_error("lanczos: the solver is NULL");
+  LanczosArgs<T> a;
+  a.op = op;
+  a.fold = fold;
+  a.n = n;
+  a.q = q;
+  a.kmax = kmax;
+  a.slots = slots;
+  a.slotStride = slotStride;
+  a.slot = slot;
+  a.prev = prev;
+  a.count = count;
+  a.breakdown = breakdown;
+  a.vec = const_cast<T* const*>(vec);  // (written by LzUpdate and LzSubtract only, whose entries take T*)
+  a.basis = basis;
+  a.coef = coef;
+  a.work = work;
+  a.state = state;
+  s->solver->lanczos<T>(a, batch, single);
+}
+#define BSP_LZ_HEAD bsp_solver *s, int64_t n, int64_t q, int64_t kmax
+#define BSP_LZ_BASIS(P) P basis, int64_t slot_stride, int64_t slots
+#define BSP_LANCZOS_API(SFX, T)                                                                                   \
+  int bsp_lanczos_init_##SFX(BSP_LZ_HEAD, const T* v0, BSP_LZ_BASIS(T*), int64_t slot, double breakdown,           \
+                             void* work, int64_t* state)                                                           \
+      BSP_BODY(lanczosRun<T>(s, LzInit, n, q, kmax, &v0, &basis, slot_stride, slots, slot, 0, 0, false, breakdown, \
+                             nullptr, work, state, 1, true))                                                       \
+  int bsp_lanczos_init_batched_##SFX(BSP_LZ_HEAD, const T* const* v0, BSP_LZ_BASIS(T* const*), int64_t slot,       \
+                                     double breakdown, void* work, int64_t* state, int32_t batch)                  \
+      BSP_BODY(lanczosRun<T>(s, LzInit, n, q, kmax, v0, basis, slot_stride, slots, slot, 0, 0, false, breakdown,   \
+                             nullptr, work, state, batch, false))                                                  \
+  int bsp_lanczos_alpha_##SFX(BSP_LZ_HEAD, const T* w, BSP_LZ_BASIS(const T*), int64_t slot, void* work,           \
+                              int64_t* state) {                                                                    \
+    T* bm = const_cast<T*>(basis);                                                                                 \
+    BSP_TRY lanczosRun<T>(s, LzAlpha, n, q, kmax, &w, &bm, slot_stride, slots, slot, 0, 0, false, 0, nullptr,      \
+                          work, state, 1, true);                                                                   \
+    BSP_CATCH                                                                                                      \
+  }                                                                                                                \
+  int bsp_lanczos_alpha_batched_##SFX(BSP_LZ_HEAD, const T* const* w, BSP_LZ_BASIS(const T* const*), int64_t slot, \
+                                      void* work, int64_t* state, int32_t batch)                                   \
+      BSP_BODY(lanczosRun<T>(s, LzAlpha, n, q, kmax, w, (T* const*)basis, slot_stride, slots, slot, 0, 0, false,   \
+                             0, nullptr, work, state, batch, false))                                               \
+  int bsp_lanczos_update_##SFX(BSP_LZ_HEAD, T* w, BSP_LZ_BASIS(const T*), int64_t slot, int64_t prev,              \
+                               int32_t fold, double* coef, void* work, int64_t* state) {                           \
+    T* bm = const_cast<T*>(basis);                                                                                 \
+    const T* wc = w;                                                                                               \
+    BSP_TRY lanczosRun<T>(s, LzUpdate, n, q, kmax, &wc, &bm, slot_stride, slots, slot, prev, 0, fold != 0, 0,      \
+                          coef, work, state, 1, true);                                                             \
+    BSP_CATCH                                                                                                      \
+  }                                                                                                                \
+  int bsp_lanczos_update_batched_##SFX(BSP_LZ_HEAD, T* const* w, BSP_LZ_BASIS(const T* const*), int64_t slot,      \
+                                       int64_t prev, int32_t fold, double* coef, void* work, int64_t* state,       \
+                                       int32_t batch)                                                              \
+      BSP_BODY(lanczosRun<T>(s, LzUpdate, n, q, kmax, (const T* const*)w, (T* const*)basis, slot_stride, slots,    \
+                             slot, prev, 0, fold != 0, 0, coef, work, state, batch, false))                        \
+  int bsp_lanczos_project_##SFX(BSP_LZ_HEAD, const T* w, BSP_LZ_BASIS(const T*), int64_t count, void* work,        \
+                                int64_t* state) {                                                                  \
+    T* bm = const_cast<T*>(basis);                                                                                 \
+    BSP_TRY lanczosRun<T>(s, LzProject, n, q, kmax, &w, &bm, slot_stride, slots, 0, 0, count, false, 0, nullptr,   \
+                          work, state, 1, true);                                                                   \
+    BSP_CATCH                                                                                                      \
+  }                                                                                                                \
+  int bsp_lanczos_project_batched_##SFX(BSP_LZ_HEAD, const T* const* w, BSP_LZ_BASIS(const T* const*),             \
+                                        int64_t count, void* work, int64_t* state, int32_t batch)                  \
+      BSP_BODY(lanczosRun<T>(s, LzProject, n, q, kmax, w, (T* const*)basis, slot_stride, slots, 0, 0, count,       \
+                             false, 0, nullptr, work, state, batch, false))                                        \
+  int bsp_lanczos_subtract_##SFX(BSP_LZ_HEAD, T* w, BSP_LZ_BASIS(const T*), int64_t count, int32_t fold,           \
+                                 double* coef, void* work, int64_t* state) {                                       \
+    T* bm = const_cast<T*>(basis);                                                                                 \
+    const T* wc = w;                                                                                               \
+    BSP_TRY lanczosRun<T>(s, LzSubtract, n, q, kmax, &wc, &bm, slot_stride, slots, 0, 0, count, fold != 0, 0,      \
+                          coef, work, state, 1, true);                                                             \
+    BSP_CATCH                                                                                                      \
+  }                                                                                                                \
+  int bsp_lanczos_subtract_batched_##SFX(BSP_LZ_HEAD, T* const* w, BSP_LZ_BASIS(const T* const*), int64_t count,   \
+                                         int32_t fold, double* coef, void* work, int64_t* state, int32_t batch)    \
+      BSP_BODY(lanczosRun<T>(s, LzSubtract, n, q, kmax, (const T* const*)w, (T* const*)basis, slot_stride, slots,  \
+                             0, 0, count, fold != 0, 0, coef, work, state, batch, false))                          \
+  int bsp_lanczos_normalize_##SFX(BSP_LZ_HEAD, const T* w, BSP_LZ_BASIS(T*), int64_t slot, void* work,             \
+                                  int64_t* state)                                                                  \
+      BSP_BODY(lanczosRun<T>(s, LzNormalize, n, q, kmax, &w, &basis, slot_stride, slots, slot, 0, 0, false, 0,     \
+                             nullptr, work, state, 1, true))                                                       \
+  int bsp_lanczos_normalize_batched_##SFX(BSP_LZ_HEAD, const T* const* w, BSP_LZ_BASIS(T* const*), int64_t slot,   \
+                                          void* work, int64_t* state, int32_t batch)                               \
+      BSP_BODY(lanczosRun<T>(s, LzNormalize, n, q, kmax, w, basis, slot_stride, slots, slot, 0, 0, false, 0,       \
+                             nullptr, work, state, batch, false))
+BSP_LANCZOS_API(f64, double)
+BSP_LANCZOS_API(f32, float)
+#undef BSP_LANCZOS_API
+#undef BSP_LZ_BASIS
+#undef BSP_LZ_HEAD
 int bsp_scalar_permutation(const bsp_solver* s, int64_t* out) {
   BSP_TRY
   if (out == nullptr) throw std::runtime_error("bsp_scalar_permutation: out is NULL");

@@ -266,6 +266,40 @@ inline int64_t cgWorkBytes(int64_t n, int64_t q) { return cgBadOffset(n, q) + ((
 template <typename T>
 void hipBackendCg(SymbolicCtx& sym, const CgArgs<T>& a, int64_t batch, bool single);
 
+// The Lanczos recurrence (hip_lanczos_kernels.h): one piece of a step on `batch`
+// matrices with q start vectors each.  Vectors are [n, q] row-major; slot s of a member's basis is the
+// vector at basis + s slotStride; state holds 12 words and coef 2 kmax doubles per (matrix, start vector);
+// the work areas sit lanczosWorkBytes(n, q, kmax) apart from `work` on.  `fold` (LzUpdate, LzSubtract): the
+// piece is the last that writes w, so the fold of ww that ends the step is queued behind it.
+//   LzInit:       vec = v0 (read): the records reset, vv, slot `slot` = v0 / sqrt(vv)
+//   LzAlpha:      vec = w (read): alpha = slot `slot` . w
+//   LzUpdate:     vec = w: w -= alpha v_j (slot `slot`) + beta v_{j-1} (slot `prev`), the partials of w.w
+//   LzProject:    vec = w (read): c_i = slot i . w, i < count
+//   LzSubtract:   vec = w: w -= sum_i c_i slot i, i < count ascending, the partials of w.w
+//   LzNormalize:  vec = w (read): slot `slot` = w / beta
+enum LanczosOp : int32_t { LzInit = 0, LzAlpha = 1, LzUpdate = 2, LzProject = 3, LzSubtract = 4, LzNormalize = 5 };
+template <typename T>
+struct LanczosArgs {
+  int32_t op = LzInit;
+  bool fold = false;
+  int64_t n = 0, q = 1, kmax = 1, slots = 0, slotStride = 0, slot = 0, prev = 0, count = 0;
+  double breakdown = 0.0;
+  T* const* vec = nullptr;
+  T* const* basis = nullptr;
+  double* coef = nullptr;
+  void* work = nullptr;
+  int64_t* state = nullptr;
+};
+inline int64_t lanczosProjOffset(int64_t n, int64_t q, int64_t kmax) {
+  const int64_t parts = (n + 1023) / 1024;
+  return q * kmax * (parts > 0 ? parts : 1) * 16;
+}
+inline int64_t lanczosWorkBytes(int64_t n, int64_t q, int64_t kmax) {
+  return lanczosProjOffset(n, q, kmax) + ((8 * q * kmax + 15) & ~int64_t(15));
+}
+template <typename T>
+void hipBackendLanczos(SymbolicCtx& sym, const LanczosArgs<T>& a, int64_t batch, bool single);
+
 // Reach solves (hip_reach_kernels.h), one matrix, plan from buildReachPlan (reach.h).
 // reachSolveL: W (numCols x order, column-major, leading dimension order) <- the unit columns of the
 // queries solved through the lumps of their reach below the plan's cut; the caller then runs

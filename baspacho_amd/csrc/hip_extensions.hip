@@ -9,6 +9,7 @@
 #include "hip_chol_adjoint_kernels.h"
 #include "hip_factor_product.h"
 #include "hip_grad_kernels.h"
+#include "hip_lanczos_kernels.h"
 #include "hip_norm_est_kernels.h"
 #include "hip_ordered_sum.h"
 #include "hip_reach_kernels.h"
@@ -1074,6 +1075,87 @@ void hipBackendCg(SymbolicCtx& sym, const CgArgs<T>& a, int64_t batch, bool sing
   });
 }
 
+// ---- the Lanczos recurrence (hip_lanczos_kernels.h) ------------------------------
+// one piece of a step (LanczosOp) on `batch` matrices: one to three launches per chunk, nothing allocated
+template <typename T>
+void hipBackendLanczos(SymbolicCtx& sym, const LanczosArgs<T>& a, int64_t batch, bool single) {
+  using In = hipk::DataRef<const T>;
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  const int64_t n = a.n, q = a.q, kmax = a.kmax;
+  const int64_t nParts = (n + hipk::kRedChunk - 1) / hipk::kRedChunk;
+  BASPACHO_CHECK_LT(q, (int64_t)INT32_MAX);
+  BASPACHO_CHECK_LT(nParts * q, (int64_t)INT32_MAX);
+  BASPACHO_CHECK_LT(kmax * q, (int64_t)INT32_MAX);
+  const int64_t perElemWgs = (n * q + hipk::kRedThreads - 1) / hipk::kRedThreads;
+  BASPACHO_CHECK_LT(perElemWgs, (int64_t)INT32_MAX);
+  const int64_t stride = lanczosWorkBytes(n, q, kmax), projOff = lanczosProjOffset(n, q, kmax);
+  const BatchPtrs<T> vec = h.stage(a.vec, batch, single), basis = h.stage(a.basis, batch, single);
+  const int threads = hipk::kRedThreads;
+  const double thr2 = a.breakdown * a.breakdown;
+  const int64_t slotOff = a.slot * a.slotStride, prevOff = a.prev * a.slotStride;
+  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+    const hipk::CgWork w{static_cast<char*>(a.work) + q0 * stride, stride, projOff};
+    hipk::LzState* st = reinterpret_cast<hipk::LzState*>(a.state) + q0 * q;
+    double* coef = a.coef ? a.coef + q0 * q * 2 * kmax : nullptr;
+    const dim3 perChunk((unsigned)(nParts * q), nm), perColumn((unsigned)q, nm), perElem((unsigned)perElemWgs, nm);
+    const In vecIn{vec.at(q0).single, (const T* const*)vec.at(q0).many};
+    const In basisIn{basis.at(q0).single, (const T* const*)basis.at(q0).many};
+    const auto fold = [&](int32_t kind) {
+      hipk::lzFold<<<perColumn, threads, 0, stream>>>((int32_t)q, (int32_t)nParts, kind, thr2, kmax, w, st, coef);
+    };
+    switch (a.op) {
+      case LzInit:
+        if (nParts > 0) {
+          hipk::cgDotPartial<T><<<perChunk, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, vecIn, vecIn, w,
+                                                                  nullptr, true);  // (always: no record is read)
+        }
+        fold(hipk::LzFoldVV);
+        if (perElemWgs > 0) {
+          hipk::lzNormalize<T><<<perElem, threads, 0, stream>>>(n, (int32_t)q, true, vecIn, basis.at(q0), slotOff, st);
+        }
+        break;
+      case LzAlpha:
+        if (nParts > 0) {
+          hipk::lzDotPartial<T><<<perChunk, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, basisIn, slotOff,
+                                                                  vecIn, w, st);
+        }
+        fold(hipk::LzFoldAlpha);
+        break;
+      case LzUpdate:
+        if (nParts > 0) {
+          hipk::lzUpdate<T><<<perChunk, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, basisIn, slotOff, prevOff,
+                                                              vec.at(q0), w, st);
+        }
+        if (a.fold) fold(hipk::LzFoldStep);
+        break;
+      case LzProject:
+        if (nParts > 0) {
+          hipk::lzProjectPartial<T><<<perChunk, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, (int32_t)a.count,
+                                                                      basisIn, a.slotStride, vecIn, w, st);
+        }
+        hipk::lzProjectFold<<<dim3((unsigned)(a.count * q), nm), threads, 0, stream>>>((int32_t)q, (int32_t)nParts,
+                                                                                        kmax, w, st);
+        break;
+      case LzSubtract:
+        if (nParts > 0) {
+          hipk::lzSubtract<T><<<perChunk, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, (int32_t)a.count, kmax,
+                                                                basisIn, a.slotStride, vec.at(q0), w, st);
+        }
+        if (a.fold) fold(hipk::LzFoldStep);
+        break;
+      case LzNormalize:
+        if (perElemWgs > 0) {
+          hipk::lzNormalize<T><<<perElem, threads, 0, stream>>>(n, (int32_t)q, false, vecIn, basis.at(q0), slotOff, st);
+        }
+        break;
+      default:
+        throw std::runtime_error("lanczos: unknown operation " + std::to_string(a.op));
+    }
+  });
+}
+
 // ---- reach solves (hip_reach_kernels.h) ---------------------------------------
 // W (numCols x order, column-major) <- the unit columns of the plan's queries, solved through the lumps
 // of their reach below the cut: one memset, the unit entries of the queries behind the cut, one launch
@@ -1224,6 +1306,7 @@ void hipBackendFactorProduct(SymbolicCtx& sym, const T* const* L, bool transpose
   template void hipBackendNormEstStep<T>(SymbolicCtx&, int32_t, void*, const T* const*, int64_t*, double*,      \
                                          int64_t, bool);                                                        \
   template void hipBackendCg<T>(SymbolicCtx&, const CgArgs<T>&, int64_t, bool);                                 \
+  template void hipBackendLanczos<T>(SymbolicCtx&, const LanczosArgs<T>&, int64_t, bool);                       \
   template void hipBackendReachSolveL<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                         \
   template void hipBackendGramBlocks<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                          \
   template T* hipBackendReachWorkspace<T>(SymbolicCtx&, int64_t);                                               \

@@ -1306,6 +1306,73 @@ void Solver::cg(const CgArgs<T>& a, int64_t batch, bool single) const {
   hipBackendCg<T>(*symCtx, a, batch, single);
 }
 
+// ---- the Lanczos recurrence ---------------------------------------------------
+static void checkLanczosSizes(const std::string& what, int64_t n, int64_t q, int64_t kmax) {
+  const auto fail = [&](const std::string& m) { throw std::runtime_error(what + ": " + m); };
+  if (n < 0 || n >= (int64_t(1) << 31)) fail("n = " + std::to_string(n) + " is outside [0, 2^31)");
+  if (q < 1 || q >= INT32_MAX) fail("q = " + std::to_string(q) + " is outside [1, 2^31 - 1)");
+  if (kmax < 1 || kmax > (int64_t(1) << 20)) fail("kmax = " + std::to_string(kmax) + " is outside [1, 2^20]");
+  const int64_t parts = (n + 1023) / 1024;
+  if (n * q >= (int64_t(1) << 40) || parts * q >= INT32_MAX || kmax * q >= INT32_MAX ||
+      (parts > 0 ? parts : 1) * q * kmax >= (int64_t(1) << 40)) {
+    fail("n q = " + std::to_string(n * q) + " with kmax = " + std::to_string(kmax) + " is too large");
+  }
+}
+
+int64_t Solver::lanczosWorkBytes(int64_t n, int64_t q, int64_t kmax) const {
+  checkLanczosSizes("lanczosWorkBytes", n, q, kmax);
+  return BaSpaCho::lanczosWorkBytes(n, q, kmax);
+}
+
+template <typename T>
+void Solver::lanczos(const LanczosArgs<T>& a, int64_t batch, bool single) const {
+  static const char* names[6] = {"lanczosInit",    "lanczosAlpha",    "lanczosUpdate",
+                                 "lanczosProject", "lanczosSubtract", "lanczosNormalize"};
+  if (a.op < 0 || a.op > LzNormalize) throw std::runtime_error("lanczos: unknown operation " + std::to_string(a.op));
+  const std::string what = names[a.op];
+  const auto fail = [&](const std::string& m) { throw std::runtime_error(what + ": " + m); };
+  if (batch < 1) fail("the batch is empty");
+  checkLanczosSizes(what, a.n, a.q, a.kmax);
+  const int64_t nq = a.n * a.q;
+  if (a.slots < 1) fail("slots = " + std::to_string(a.slots) + "; the basis needs at least one slot");
+  if (a.slotStride < nq) {
+    fail("the slot stride " + std::to_string(a.slotStride) + " is below n q = " + std::to_string(nq));
+  }
+  const auto checkSlot = [&](const char* name, int64_t s) {
+    if (s < 0 || s >= a.slots) {
+      fail(std::string("the ") + name + " slot " + std::to_string(s) + " is outside the basis of " +
+           std::to_string(a.slots) + " slots");
+    }
+  };
+  if (a.op == LzProject || a.op == LzSubtract) {
+    if (a.count < 1 || a.count > a.slots || a.count > a.kmax) {
+      fail("count = " + std::to_string(a.count) + " is outside [1, min(slots, kmax)] = [1, " +
+           std::to_string(std::min(a.slots, a.kmax)) + "]");
+    }
+  } else {
+    checkSlot(a.op == LzInit || a.op == LzNormalize ? "output" : "current", a.slot);
+    if (a.op == LzUpdate) checkSlot("previous", a.prev);
+  }
+  if (a.op == LzInit && !(a.breakdown >= 0.0)) {
+    fail("breakdown = " + std::to_string(a.breakdown) + "; it must be >= 0");
+  }
+  if (a.work == nullptr) fail("the workspace pointer is NULL");
+  if (reinterpret_cast<uintptr_t>(a.work) % 16 != 0) fail("the workspace is not 16-byte aligned");
+  if (a.state == nullptr) fail("the state pointer is NULL");
+  const bool folds = (a.op == LzUpdate || a.op == LzSubtract) && a.fold;
+  if (folds && a.coef == nullptr) fail("the coefficient pointer is NULL");
+  const char* vecName = a.op == LzInit ? "start vector" : "w";
+  if (a.vec == nullptr) fail(std::string("the ") + vecName + " pointers are NULL");
+  if (a.basis == nullptr) fail("the basis pointers are NULL");
+  for (int64_t m = 0; m < batch; m++) {
+    if (nq > 0 && a.vec[m] == nullptr) {
+      fail(std::string("the ") + vecName + " pointer of batch member " + std::to_string(m) + " is NULL");
+    }
+    if (nq > 0 && a.basis[m] == nullptr) fail("the basis pointer of batch member " + std::to_string(m) + " is NULL");
+  }
+  hipBackendLanczos<T>(*symCtx, a, batch, single);
+}
+
 // ---- blocks of A^-1 by reach solves (reach.h) --------------------------------
 ReachPlan Solver::reachPlan(const char* what, const std::vector<int64_t>& params, const std::vector<int64_t>& pairRow,
                             const std::vector<int64_t>& pairCol, const std::vector<int64_t>& outOffsets) const {
@@ -1473,6 +1540,7 @@ void Solver::mulLt(const std::vector<T*>& L, const std::vector<T*>& x, int64_t i
   template int64_t Solver::invNorm1WorkBytes<T>() const;                                                       \
   template void Solver::invNorm1Estimate<T>(BspCVec_##T, BspCVec_##T, void*, int64_t*, double*, bool) const;   \
   template void Solver::cg<T>(const CgArgs<T>&, int64_t, bool) const;                                          \
+  template void Solver::lanczos<T>(const LanczosArgs<T>&, int64_t, bool) const;                                \
   template void Solver::reachSolveL<T>(const T*, const std::vector<int64_t>&, T*) const;                       \
   template void Solver::inverseBlocks<T>(const T*, const std::vector<int64_t>&, const std::vector<int64_t>&,   \
                                          T*, const std::vector<int64_t>&) const;

@@ -21,6 +21,8 @@ struct NormalEqMap;
 struct SymProductMap;
 template <typename T>
 struct CgArgs;
+template <typename T>
+struct LanczosArgs;
 struct ReachPlan;
 
 class Solver {
@@ -302,6 +304,18 @@ class Solver {
   int64_t cgWorkBytes(int64_t n, int64_t q) const;
   template <typename T>
   void cg(const CgArgs<T>& a, int64_t batch, bool single) const;
+  // extension: the pieces of the Lanczos recurrence on the device (DESIGN.md section 25;
+  // hip_lanczos_kernels.h).  `a` (LanczosArgs, hip_backend.h) names the piece (LanczosOp) and its operands:
+  // the vector [n, q] row-major and the basis (slot s at basis + s slotStride elements, `slots` of them), one
+  // pointer each per batch member; `state`, 12 words, and `coef`, 2 kmax doubles, per (member, start vector),
+  // members one after the other; `work`, the caller's, lanczosWorkBytes() per member, 16-byte aligned.  The
+  // product w = A v_j before LzAlpha is the caller's.  Stopped columns are left bitwise unchanged by every
+  // piece.  Runs on the stream of setStream(), nothing is allocated and nothing read back.  Refused before any
+  // device work: an empty batch, n, q or kmax out of range, a slot or a count outside the basis, a slot
+  // stride below n q, a NULL or misaligned workspace, a NULL pointer.
+  int64_t lanczosWorkBytes(int64_t n, int64_t q, int64_t kmax) const;
+  template <typename T>
+  void lanczos(const LanczosArgs<T>& a, int64_t batch, bool single) const;
   // extension: blocks of A^-1 anywhere, on or off the pattern of L, by reach solves (DESIGN.md section 20;
   // reach.h, hip_reach_kernels.h).  `L` holds a complete factor() and is only read; params are the
   // caller's param ids (repeats allowed).  Both run on the stream of setStream() without host

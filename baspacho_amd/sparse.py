@@ -24,6 +24,10 @@
     e = S.backward_error(pat, values, x, b)        # max_i |b - A x|_i / (|A| |x| + |b|)_i per right-hand side
     k = S.cond_estimate(pat, values, scaled=True)  # kappa_1 of the Jacobi-scaled matrix, from the factor
     x = S.solve_cg(pat, values, b, precond="block_jacobi", tol=1e-10)  # device-resident PCG, no layout, no factor
+    run = S.lanczos(pat, values, v0, steps=32)     # alpha, beta, stop words (and the basis) of Lanczos runs on A
+    lo, hi = S.eig_extremes(pat, values, steps=64) # extreme eigenvalues by device-resident Lanczos, from the entries
+    k2 = S.cond2_estimate(pat, values)             # kappa_2 = lam_max / lam_min (cond_estimate gives kappa_1)
+    ld = S.logdet_slq(pat, values, probes=16)      # log det A without a factor: stochastic Lanczos quadrature
 
     jpat = S.JacobianPattern(jrows, jcols, m, n)   # once per Jacobian pattern: solver + normal-equations maps
     x = S.lstsq(jpat, jvalues, r, damping=(a, b))  # x = (J^T J + D)^-1 J^T r, D = a diag(J^T J) + b I
@@ -84,7 +88,9 @@ __all__ = ["SymmetricPattern", "JacobianPattern", "assemble", "solve", "logdet",
            # error bounds: none of these is differentiable
            "residual", "backward_error", "norm1", "cond_estimate",
            # conjugate gradient from the entries
-           "solve_cg"]
+           "solve_cg",
+           # Lanczos from the entries: only logdet_slq is differentiable
+           "lanczos", "eig_extremes", "cond2_estimate", "logdet_slq"]
 
 
 def _host_i64(a):
@@ -1064,6 +1070,306 @@ def solve_cg(pattern, values, b, precond="block_jacobi", tol=1e-10, max_steps=10
     if precond in ("jacobi", "block_jacobi"):
         info["precond_status"] = status
     return x, info
+
+
+# ---- Lanczos from the entries ----------------------------------------------------
+def _entries_operator(pattern, v, q):
+    """apply_a(x, out) of a LanczosRun: out = A(v) x by the entries' product, the pointers of out taken once"""
+    sol, prod = pattern.solver, pattern.product
+    batched = v.dim() == 2
+    pv = _ptr_arg(v.unbind(0) if batched else [v], batched)
+    fixed = {}
+
+    def apply_a(x, out):
+        if "out" not in fixed:
+            fixed["out"] = _ptr_arg(out.unbind(0) if batched else [out], batched)
+        _call(prod._lib, "bsp_sym_product_mv_", batched, _suffix(v), sol._h, prod._h, pv,
+              _ptr_arg(x.unbind(0) if batched else [x], batched), ctypes.c_int64(q), fixed["out"], *_count(v, batched))
+        return out
+    return apply_a
+
+
+def _inverse_operator(pattern, v):
+    """apply_a(x, out) with out = A(v)^-1 x: assembles and factors once, every application is a solve"""
+    sol = pattern.solver
+    batched = v.dim() == 2
+    dim = 1 if batched else 0
+    L = pattern.assembly.assemble(v)
+    members = _ag._members(L) if batched else L
+    sol.factor(members)
+    status = sol.factorStatus(members)
+
+    def apply_a(x, out):
+        xt = _ag._to_cols(pattern.toInternal(x, dim), batched)
+        _ag._solve_cols(sol, L, xt)
+        out.copy_(pattern.fromInternal(_ag._from_cols(xt, x.shape), dim))
+        return out
+    return apply_a, status
+
+
+def _lanczos_start(pattern, values, v0, what, name="v0"):
+    """v0 ([n] / [n, q], or with values' leading B) as the contiguous [(B,) n, q] start of a run, and whether it
+    had the q axis"""
+    dim = _check_x(pattern, values, v0, what, name)
+    has_q = v0.dim() == dim + 2
+    v3 = v0.detach().contiguous()
+    return (v3 if has_q else v3.unsqueeze(-1)).contiguous(), has_q
+
+
+def _shared_start(values, z, n):
+    """the host probes z [n, q] as a device start [(B,) n, q] of values' dtype: a batch shares them"""
+    zt = torch.from_numpy(np.ascontiguousarray(z)).to(device=values.device, dtype=values.dtype)
+    if values.dim() == 2:
+        zt = zt.unsqueeze(0).expand(values.shape[0], n, zt.shape[-1])
+    return zt.contiguous()
+
+
+def _lanczos_run(pattern, v, v3, apply_a, steps, reorth, check_every, keep_basis, breakdown=None):
+    from . import lanczos as _lz
+    return _lz.LanczosRun(pattern.solver, v3, apply_a, steps, reorth, keep_basis, breakdown).run(check_every)
+
+
+def lanczos(pattern, values, v0, steps=32, reorth="full", check_every=None, keep_basis=False, breakdown=None):
+    """`steps` steps of the Lanczos recurrence of A(values) from the start vector(s) v0, straight from the
+    entries (A v is matvec's kernel; no layout, no factor), with the scalars of the recurrence in a state record
+    on the device.  values [nnz] / [B, nnz]; v0 [n] / [n, q] with a leading B for a batch,
+    any nonzero vectors (the run normalises them); every (matrix, start vector) is a run of its own and stops on
+    its own: after `steps` steps (at most 512), on an invariant subspace (ww <= breakdown^2 (alpha^2 +
+    beta_prev^2), breakdown 64 eps by default: the Krylov space is exhausted and the Ritz values are
+    eigenvalues), on a non-finite sum, or at once for a zero v0.  A stopped run is frozen by the kernels.
+
+    reorth "full" orthogonalises every new vector twice against all earlier ones (classical Gram-Schmidt on
+    the device: the basis of `steps` vectors is kept); None runs the plain three-term recurrence on two
+    vectors, whose Ritz values lose orthogonality and repeat once one has converged.  Steps are queued in
+    chunks of check_every with one read of the stop words per chunk; None queues all steps and reads nothing.
+    The result is bitwise the same for every check_every.
+
+    Returns a dict of device tensors shaped [] / [q] with a leading B for a batch: "alpha" and "beta" float64
+    [.., steps] (T_k = tridiag(beta_0 .. beta_{k-2}; alpha_0 .. alpha_{k-1}) for k = steps done; zero beyond),
+    "steps", "stop" (baspacho_amd.lanczos.STOPS), "state" (int64 [.., 12]; baspacho_amd.lanczos.read_state),
+    and, with reorth "full" or keep_basis, "basis" [.., steps, n(, q)] in the caller's order, v_j at index j.
+    baspacho_amd.lanczos.ritz and quadrature post-process one run's coefficients on the host.  Not
+    differentiable.  Runs on the current torch stream; no stream capture."""
+    from . import lanczos as _lz
+    what = "lanczos"
+    _check_values(pattern, values, what)
+    _lz.check_settings(what, steps, reorth, check_every, breakdown)
+    v3, has_q = _lanczos_start(pattern, values, v0, what)
+    _ag._check_device(pattern.solver, what, values, v0)
+    v = values.detach().contiguous()
+    with _OnCurrentStream(pattern.solver, v.device):
+        run = _lanczos_run(pattern, v, v3, _entries_operator(pattern, v, v3.shape[-1]), steps, reorth, check_every,
+                           keep_basis, breakdown)
+        sq = (lambda t, d: t) if has_q else (lambda t, d: t.squeeze(d))
+        out = {"alpha": sq(run.alpha(), -2), "beta": sq(run.beta(), -2), "steps": sq(run.steps_done(), -1),
+               "stop": sq(run.stop(), -1), "state": sq(run.state, -2)}
+        if run.kept:
+            basis = run.basis.movedim(0, -3)  # [slots, (B,) n, q] -> [(B,) slots, n, q]
+            out["basis"] = sq(basis, -1)
+    return out
+
+
+def _ritz_columns(run):
+    """per (member, column) of a finished run: (theta, tau, bound, steps, stop), on the host (synchronises)"""
+    from . import lanczos as _lz
+    coef = run.coef.cpu().numpy().reshape(-1, 2, run.steps)
+    state = run.state.cpu().numpy().reshape(-1, 12)
+    out = []
+    for c in range(coef.shape[0]):
+        k, stop = int(state[c, 0]), int(state[c, 1])
+        r = _lz.ritz(coef[c, 0], coef[c, 1], k) if k >= 1 and np.isfinite(coef[c, :, :k]).all() else None
+        out.append((r, k, stop))
+    return out
+
+
+def eig_extremes(pattern, values, steps=64, v0=None, seed=0, method="entries", return_info=False):
+    """(lam_min, lam_max): estimates of the extreme eigenvalues of A(values) from `steps` Lanczos steps with full
+    reorthogonalisation, Python floats, or float64 numpy arrays [B] for a batch.  v0: the
+    start vector [n] (a device tensor, shared by a batch); default: Rademacher signs from `seed`
+    (baspacho_amd.lanczos.rademacher).  method "entries": both are the extreme Ritz values of one run on A, from
+    the entries alone; Ritz values lie inside the spectrum, so lam_max is a lower and lam_min an upper bound,
+    and lam_min converges slowly when the small eigenvalues are clustered relative to the spread.  method
+    "factor": lam_min = 1 / theta_max of a second run on A^-1 (the layout is assembled and factored once, every
+    step is a solve), where the smallest eigenvalue is the best separated one.  return_info=True: (lam_min,
+    lam_max, info), info = {"bound_min", "bound_max": the residual bounds |beta_{k-1} s_{k-1,i}| of the two Ritz
+    values (for "factor", bound_min is that of theta_max of A^-1), "steps", "stop": per run}.  A run that took no
+    step or met a non-finite sum gives NaN.  Synchronises (the coefficients are read); not differentiable."""
+    from . import lanczos as _lz
+    what = "eig_extremes"
+    _check_values(pattern, values, what)
+    _lz.check_settings(what, steps, "full")
+    if method not in ("entries", "factor"):
+        raise ValueError("%s: method must be 'entries' or 'factor', got %r" % (what, method))
+    n = pattern.n
+    batched = values.dim() == 2
+    if v0 is None:
+        v3 = _shared_start(values, _lz.rademacher(n, 1, seed, values.dtype), n)
+    else:
+        if not isinstance(v0, torch.Tensor) or v0.shape != (n,):
+            raise ValueError("%s: v0 must be a tensor of shape [%d], got %r" % (what, n, getattr(v0, "shape", v0)))
+        if v0.dtype != values.dtype:
+            raise TypeError("%s: v0 has dtype %s, values have %s" % (what, v0.dtype, values.dtype))
+        v3 = v0.detach().reshape(n, 1)
+        v3 = (v3.unsqueeze(0).expand(values.shape[0], n, 1) if batched else v3).contiguous()
+    _ag._check_device(pattern.solver, what, values, v3)
+    v = values.detach().contiguous()
+    steps = min(steps, n)
+    with _OnCurrentStream(pattern.solver, v.device):
+        top = _ritz_columns(_lanczos_run(pattern, v, v3, _entries_operator(pattern, v, 1), steps, "full", None, False))
+        low = top
+        if method == "factor":
+            low = _ritz_columns(_lanczos_run(pattern, v, v3, _inverse_operator(pattern, v)[0], steps, "full", None, False))
+    nan = float("nan")
+    lam_max = np.array([r[0][-1] if r is not None else nan for r, _, _ in top])
+    bound_max = np.array([r[2][-1] if r is not None else nan for r, _, _ in top])
+    if method == "factor":
+        with np.errstate(all="ignore"):
+            lam_min = np.array([1.0 / r[0][-1] if r is not None else nan for r, _, _ in low])
+        bound_min = np.array([r[2][-1] if r is not None else nan for r, _, _ in low])
+    else:
+        lam_min = np.array([r[0][0] if r is not None else nan for r, _, _ in low])
+        bound_min = np.array([r[2][0] if r is not None else nan for r, _, _ in low])
+    pick = (lambda a: a) if batched else (lambda a: a[0].item())
+    if not return_info:
+        return pick(lam_min), pick(lam_max)
+    # per matrix {the run on A, the run for lam_min (the same one for "entries")}
+    counts = np.array([[k for _, k, _ in t] for t in (top, low)]).T
+    stops = np.array([[s for _, _, s in t] for t in (top, low)]).T
+    info = {"bound_min": pick(bound_min), "bound_max": pick(bound_max),
+            "steps": counts if batched else counts[0].tolist(), "stop": stops if batched else stops[0].tolist()}
+    return pick(lam_min), pick(lam_max), info
+
+
+def cond2_estimate(pattern, values, steps=32, method="factor", return_info=False):
+    """An estimate of the 2-norm condition number kappa_2(A) = lam_max / lam_min of A(values) from
+    eig_extremes(pattern, values, steps, method=method): a Python float, or a float64 numpy array [B].  With
+    method "entries" it is a lower bound of kappa_2, because Ritz values lie inside the spectrum (lam_max is
+    under-, lam_min overestimated), and it never decreases with `steps`; with "factor" lam_min comes from A^-1
+    and is underestimated instead, so the estimate may lie on either side of kappa_2, within the residual bounds
+    that return_info reports (eig_extremes's info), and converges in a few dozen steps.  kappa_2 bounds the
+    steps of solve_cg (about sqrt(kappa_2) log(2 / tol) / 2) and tells whether A is positive definite at all
+    (lam_min <= 0).  cond_estimate gives kappa_1 instead, from a factor and Hager's 1-norm estimator; for a
+    symmetric matrix kappa_1 / n <= kappa_2 <= n kappa_1, and kappa_1 is the number that bounds the error of a
+    factor solve in the 1-norm.  Synchronises; not differentiable."""
+    out = eig_extremes(pattern, values, steps=steps, method=method, return_info=return_info)
+    with np.errstate(all="ignore"):
+        kappa = out[1] / out[0]
+    return (kappa, out[2]) if return_info else kappa
+
+
+def _slq_forward(pattern, v, z3, steps, reorth):
+    """(estimate per member [nb], terms [nb, q], steps, stops) of the quadrature of log on the probes z3"""
+    from . import FactorizationError
+    n, q = z3.shape[-2], z3.shape[-1]
+    run = _lanczos_run(pattern, v, z3, _entries_operator(pattern, v, q), steps, reorth, None, False)
+    cols = _ritz_columns(run)
+    nb = len(cols) // q
+    terms = np.zeros((nb, q))
+    for i, (r, k, stop) in enumerate(cols):
+        m, c = divmod(i, q)
+        where = "probe %d" % c + (" of batch member %d" % m if v.dim() == 2 else "")
+        if r is None:
+            raise FactorizationError("logdet_slq: the run of %s took %d steps and stopped with '%s'"
+                                     % (where, k, _stop_name(stop)), {"probe": c, "member": m, "stop": stop})
+        theta, tau, _ = r
+        if not theta[0] > 0:
+            raise FactorizationError("logdet_slq: %s ends with the Ritz value %g <= 0: the matrix is not positive "
+                                     "definite" % (where, theta[0]), {"probe": c, "member": m, "theta_min": float(theta[0])})
+        terms[m, c] = n * float(np.sum(tau * np.log(theta)))
+    state = run.state.cpu().numpy().reshape(nb, q, 12)
+    return terms.mean(axis=1), terms, state[..., 0], state[..., 1]
+
+
+def _stop_name(stop):
+    from . import lanczos as _lz
+    return _lz.STOPS[stop] if 0 <= stop < len(_lz.STOPS) else str(stop)
+
+
+class _LogdetSLQ(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pattern, values, z3, steps, reorth, cg):
+        v = values.detach().contiguous()
+        with _OnCurrentStream(pattern.solver, v.device):
+            est, terms, k, stop = _slq_forward(pattern, v, z3, steps, reorth)
+        dev = lambda a, dt: torch.from_numpy(np.array(a)).to(device=v.device, dtype=dt)  # (0-dim stays 0-dim)
+        batched = v.dim() == 2
+        pick = (lambda a: a) if batched else (lambda a: a[0])
+        out = dev(pick(est), torch.float64)
+        info = (dev(pick(terms), torch.float64), dev(pick(k), torch.int64), dev(pick(stop), torch.int64))
+        ctx.pattern, ctx.cg = pattern, cg
+        ctx.save_for_backward(v, z3)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*info)
+        return (out, *info)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, *_):
+        if g is None or not ctx.needs_input_grad[1]:
+            return (None,) * 6
+        pattern, (v, z3) = ctx.pattern, ctx.saved_tensors
+        n, q = z3.shape[-2], z3.shape[-1]
+        kw = dict(precond="block_jacobi", tol=1e-10, max_steps=200, check_every=8)
+        kw.update(ctx.cg or {})
+        with _OnCurrentStream(pattern.solver, g.device):
+            u, _ = _cg_run(pattern, v, z3, kw["precond"], float(kw["tol"]), kw["max_steps"], kw["check_every"], None, {})
+            # A^-1 ~ (n / q) sum_c u_c z_c^T / (z_c . z_c): the gradient of the entries' values is its outer()
+            scale = (float(n) / q) / (z3 * z3).sum(dim=-2, keepdim=True)
+            gz = z3 * scale * g.to(v.dtype).reshape(g.shape + (1, 1))
+            gv = pattern.product.outer(u.contiguous(), gz.contiguous(), batched=v.dim() == 2)
+        return (None, gv) + (None,) * 4
+
+
+def logdet_slq(pattern, values, probes=16, steps=32, seed=0, z=None, reorth="full", cg=None, return_info=False):
+    """An estimate of log det A(values) without a factor, by stochastic Lanczos quadrature (DESIGN.md section
+    25): (n / q) sum_c quadrature_c(log) over q probe vectors, where quadrature_c is the `steps`-point Gauss
+    quadrature sum_i tau_i log(theta_i) of the Lanczos run started from probe c, run on the device straight from
+    the entries.  A float64 device tensor [], or [B] for a batch [B, nnz], whose members share the probes.  The
+    probes are `probes` Rademacher vectors from `seed` (baspacho_amd.lanczos.rademacher: the same seed gives the
+    same probes), or the columns of z, a host array or tensor [n, q] of any nonzero vectors: the runs normalise
+    their starts.  The identity as z gives the exact log det at steps = n (at O(n) runs: a test, not a method).
+    The error of the estimate falls as 1 / sqrt(probes); its quadrature part falls geometrically in steps at a
+    rate set by kappa_2 (cond2_estimate).  A probe whose run ends with a Ritz value <= 0 raises
+    FactorizationError, which names the probe: the matrix is not positive definite.  Synchronises (the
+    coefficients are read; the eigen-solves of the tridiagonals are host work).
+
+    return_info=True: (estimate, info), info = {"terms": the per-probe values n quadrature_c(log), [q] / [B, q],
+    whose mean is the estimate, "stderr": their standard error std(terms, ddof=1) / sqrt(q) (0 for one probe),
+    "steps", "stop": per probe}.
+
+    Differentiable in values.  The backward pass is the stochastic trace estimator on the same probes, not the
+    derivative of the forward's floating-point value: with u_c = solve_cg(A, z_c) (cg = keyword arguments of
+    solve_cg; default precond="block_jacobi", tol=1e-10, max_steps=200), grad_values = g (n / q) sum_c
+    outer(u_c, z_c) / (z_c . z_c), the entries' share of (n / q) sum_c A^-1 z_c z_c^T / |z_c|^2.  It is an unbiased
+    estimate of the true gradient, the entries' share of A^-1, for Rademacher probes, and exact (to the solves'
+    tolerance) for identity probes.  Double backward is not supported; no stream capture."""
+    from . import lanczos as _lz
+    what = "logdet_slq"
+    _check_values(pattern, values, what)
+    _lz.check_settings(what, steps, reorth)
+    n = pattern.n
+    if z is None:
+        if isinstance(probes, bool) or not isinstance(probes, int) or probes < 1:
+            raise ValueError("%s: probes must be an integer >= 1, got %r" % (what, probes))
+        zh = _lz.rademacher(n, probes, seed, np.float64)
+    else:
+        zh = z.detach().cpu().numpy() if isinstance(z, torch.Tensor) else np.asarray(z)
+        if zh.ndim != 2 or zh.shape[0] != n or zh.shape[1] < 1:
+            raise ValueError("%s: z must be [%d, q] with q >= 1, got shape %s" % (what, n, tuple(zh.shape)))
+        if zh.dtype.kind != "f":
+            raise TypeError("%s: z must be a floating-point array, got %s" % (what, zh.dtype))
+    if cg is not None and not isinstance(cg, dict):
+        raise ValueError("%s: cg must be None or a dict of solve_cg's keyword arguments, got %r" % (what, cg))
+    if cg is not None and set(cg) - {"precond", "tol", "max_steps", "check_every"}:
+        raise ValueError("%s: cg takes precond, tol, max_steps and check_every, got %s" % (what, sorted(cg)))
+    _ag._check_device(pattern.solver, what, values)
+    z3 = _shared_start(values, zh, n)
+    est, terms, k, stop = _LogdetSLQ.apply(pattern, values, z3, min(steps, n), reorth, cg)
+    if not return_info:
+        return est
+    q = z3.shape[-1]
+    stderr = terms.std(dim=-1, unbiased=True) / float(np.sqrt(q)) if q > 1 else torch.zeros_like(est)
+    return est, {"terms": terms, "stderr": stderr, "steps": k, "stop": stop}
 
 
 # ---- error bounds (DESIGN.md section 23); none of these is differentiable ---------------------------

@@ -828,6 +828,117 @@ int bsp_cg_precond_build_f32(bsp_solver* s, const bsp_sym_product* p, int32_t ki
 int bsp_cg_precond_build_batched_f32(bsp_solver* s, const bsp_sym_product* p, int32_t kind,
                                      const float* const* dev_values, float* const* dev_minv, void* dev_work,
                                      int64_t* dev_status, int32_t batch);
+/* EXTENSION without a counterpart in the reference's library: the pieces of the Lanczos recurrence with its
+   scalars on the device, for extreme eigenvalues, a 2-norm condition estimate and
+   stochastic Lanczos quadrature (log-determinants) without a factor.  One problem per (matrix, start vector):
+   vectors are [n, q] row-major; dev_basis is one array per member whose slot s is the [n, q] vector at
+   dev_basis + s slot_stride elements (slot_stride >= n q), `slots` of them; dev_state holds
+   bsp_lanczos_state_words = 12 8-byte words per problem, problem c of member m at (m q + c) 12: [0] steps done,
+   [1] stop reason (0 running, 2 step limit, 3 invariant subspace: ww <= breakdown^2 (alpha^2 + beta_prev^2),
+   4 a non-finite sum, 5 zero start vector; 1 is unused, the shared codes are bsp_cg_*'s), then the doubles
+   [2] vv = v0.v0, [3] alpha, [4] beta, [5] ww, [6] breakdown^2, then [7] kmax, [8] .. [11] 0; dev_coef holds 2 kmax
+   doubles per problem, alpha_0 .. alpha_{kmax-1} then beta_0 .. beta_{kmax-1}, zeroed by the caller: step j
+   writes entry j of both.  Every piece reads its scalars from the records and leaves the basis, dev_coef and
+   the record of a stopped problem bitwise unchanged; nothing is read back by the library, so the caller may
+   queue any number of steps and look at the stop words when it likes.  Step j is: w = A v_j (the caller's:
+   bsp_sym_product_mv_* or any operator); alpha; update; [project; subtract] twice for full
+   reorthogonalisation; normalize (not after the last step, kmax - 1: every problem has stopped).
+     init:       the records are reset (kmax, breakdown), vv = v0.v0 taken, slot `slot` = v0 T(1 / sqrt(vv));
+                 a zero v0 stops with reason 5 and writes no slot
+     alpha:      alpha_j = v_j . w, v_j = slot `slot`
+     update:     w = (w - T(alpha_j) v_j) - T(beta_{j-1}) v_{j-1}, v_{j-1} = slot `prev` (not read at step 0),
+                 with the partials of ww = w.w of the same pass
+     project:    c_i = v_i . w for the slots i = 0 .. count - 1, in one pass over w and the slots
+     subtract:   w = w - T(c_i) v_i, i = 0 .. count - 1 in this order, with the partials of ww
+     normalize:  slot `slot` = w T(1 / beta_j)
+   update and subtract take `fold`: non-zero on the last piece of the step that writes w, which then ends the
+   step: alpha_j and beta_j = sqrt(ww) stored in the record and dev_coef, the step counted, then stop 4 if
+   alpha_j or ww is not finite, stop 3 if ww <= breakdown^2 (alpha_j^2 + beta_{j-1}^2), stop 2 at kmax steps.
+   Dot products are taken in double for both precisions, in the two-pass order of bsp_cg_* with every product
+   rounded before it is added; the vector updates round every product in the data type.  No atomics; member
+   b of a batched call is bitwise the single call.  WORKSPACE: dev_work is the caller's, 16-byte aligned,
+   bsp_lanczos_work_bytes bytes per member (16 bytes per 1024 rows, start vector and step of kmax, plus 8
+   bytes per start vector and step, rounded up to 16), members one after the other; nothing is allocated
+   inside a call.  Refused before any device work: NULL arguments, an empty batch or a NULL member, n < 0,
+   q < 1, kmax < 1, a slot or count outside the basis (count also above kmax), a slot stride below n q, a
+   misaligned workspace. */
+int bsp_lanczos_state_words(int64_t* out);
+int bsp_lanczos_work_bytes(const bsp_solver* s, int64_t n, int64_t q, int64_t kmax, int64_t* out);
+int bsp_lanczos_init_f64(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const double* dev_v0, double* dev_basis,
+                         int64_t slot_stride, int64_t slots, int64_t slot, double breakdown, void* dev_work,
+                         int64_t* dev_state);
+int bsp_lanczos_init_batched_f64(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const double* const* dev_v0,
+                                 double* const* dev_basis, int64_t slot_stride, int64_t slots, int64_t slot, double
+                                 breakdown, void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_lanczos_alpha_f64(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const double* dev_w,
+                          const double* dev_basis, int64_t slot_stride, int64_t slots, int64_t slot, void* dev_work,
+                          int64_t* dev_state);
+int bsp_lanczos_alpha_batched_f64(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const double* const* dev_w,
+                                  const double* const* dev_basis, int64_t slot_stride, int64_t slots, int64_t slot,
+                                  void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_lanczos_update_f64(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, double* dev_w, const double* dev_basis,
+                           int64_t slot_stride, int64_t slots, int64_t slot, int64_t prev, int32_t fold,
+                           double* dev_coef, void* dev_work, int64_t* dev_state);
+int bsp_lanczos_update_batched_f64(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, double* const* dev_w,
+                                   const double* const* dev_basis, int64_t slot_stride, int64_t slots, int64_t slot,
+                                   int64_t prev, int32_t fold, double* dev_coef, void* dev_work, int64_t* dev_state,
+                                   int32_t batch);
+int bsp_lanczos_project_f64(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const double* dev_w,
+                            const double* dev_basis, int64_t slot_stride, int64_t slots, int64_t count, void* dev_work,
+                            int64_t* dev_state);
+int bsp_lanczos_project_batched_f64(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const double* const* dev_w,
+                                    const double* const* dev_basis, int64_t slot_stride, int64_t slots, int64_t count,
+                                    void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_lanczos_subtract_f64(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, double* dev_w,
+                             const double* dev_basis, int64_t slot_stride, int64_t slots, int64_t count, int32_t fold,
+                             double* dev_coef, void* dev_work, int64_t* dev_state);
+int bsp_lanczos_subtract_batched_f64(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, double* const* dev_w,
+                                     const double* const* dev_basis, int64_t slot_stride, int64_t slots, int64_t count,
+                                     int32_t fold, double* dev_coef, void* dev_work, int64_t* dev_state,
+                                     int32_t batch);
+int bsp_lanczos_normalize_f64(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const double* dev_w,
+                              double* dev_basis, int64_t slot_stride, int64_t slots, int64_t slot, void* dev_work,
+                              int64_t* dev_state);
+int bsp_lanczos_normalize_batched_f64(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const double* const* dev_w,
+                                      double* const* dev_basis, int64_t slot_stride, int64_t slots, int64_t slot,
+                                      void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_lanczos_init_f32(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const float* dev_v0, float* dev_basis,
+                         int64_t slot_stride, int64_t slots, int64_t slot, double breakdown, void* dev_work,
+                         int64_t* dev_state);
+int bsp_lanczos_init_batched_f32(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const float* const* dev_v0,
+                                 float* const* dev_basis, int64_t slot_stride, int64_t slots, int64_t slot,
+                                 double breakdown, void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_lanczos_alpha_f32(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const float* dev_w,
+                          const float* dev_basis, int64_t slot_stride, int64_t slots, int64_t slot, void* dev_work,
+                          int64_t* dev_state);
+int bsp_lanczos_alpha_batched_f32(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const float* const* dev_w,
+                                  const float* const* dev_basis, int64_t slot_stride, int64_t slots, int64_t slot,
+                                  void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_lanczos_update_f32(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, float* dev_w, const float* dev_basis,
+                           int64_t slot_stride, int64_t slots, int64_t slot, int64_t prev, int32_t fold,
+                           double* dev_coef, void* dev_work, int64_t* dev_state);
+int bsp_lanczos_update_batched_f32(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, float* const* dev_w,
+                                   const float* const* dev_basis, int64_t slot_stride, int64_t slots, int64_t slot,
+                                   int64_t prev, int32_t fold, double* dev_coef, void* dev_work, int64_t* dev_state,
+                                   int32_t batch);
+int bsp_lanczos_project_f32(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const float* dev_w,
+                            const float* dev_basis, int64_t slot_stride, int64_t slots, int64_t count, void* dev_work,
+                            int64_t* dev_state);
+int bsp_lanczos_project_batched_f32(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const float* const* dev_w,
+                                    const float* const* dev_basis, int64_t slot_stride, int64_t slots, int64_t count,
+                                    void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_lanczos_subtract_f32(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, float* dev_w, const float* dev_basis,
+                             int64_t slot_stride, int64_t slots, int64_t count, int32_t fold, double* dev_coef,
+                             void* dev_work, int64_t* dev_state);
+int bsp_lanczos_subtract_batched_f32(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, float* const* dev_w,
+                                     const float* const* dev_basis, int64_t slot_stride, int64_t slots, int64_t count,
+                                     int32_t fold, double* dev_coef, void* dev_work, int64_t* dev_state,
+                                     int32_t batch);
+int bsp_lanczos_normalize_f32(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const float* dev_w, float* dev_basis,
+                              int64_t slot_stride, int64_t slots, int64_t slot, void* dev_work, int64_t* dev_state);
+int bsp_lanczos_normalize_batched_f32(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const float* const* dev_w,
+                                      float* const* dev_basis, int64_t slot_stride, int64_t slots, int64_t slot,
+                                      void* dev_work, int64_t* dev_state, int32_t batch);
 /* out[i_user] = i_internal (order values): the caller's scalar i in the solver's internal vector order
    (param p at spanStart[paramToSpan[p]], its scalars in order) */
 int bsp_scalar_permutation(const bsp_solver* s, int64_t* out);
