@@ -88,7 +88,10 @@ class Frame:
     """One 1-D tensor full of the sentinel that holds the payloads of the given sizes.  Every payload has
     at least `guard` sentinel words on both sides and starts at an odd element offset from the base (the
     first guard is one word longer, and so is any later guard that would end on an even offset): a
-    payload is element-aligned and never 16-byte-aligned when the base is.
+    payload is element-aligned and never 16-byte-aligned when the base is.  With align_bytes (a multiple of
+    the element size; 16 for the work areas of the iterative pieces) every payload instead starts at a
+    multiple of align_bytes from address zero, still behind at least `guard` sentinel words; a payload of
+    exactly the documented size then has its first foreign word right behind its last own one.
 
     view(k)        the contiguous slice of payload k (what the library is handed)
     fill(k, a)     host array -> payload k, word for word
@@ -97,11 +100,16 @@ class Frame:
     assert_intact  every word outside the payloads still holds the sentinel, and the payloads named
                    read_only are bitwise what they were at seal()"""
 
-    def __init__(self, sizes, dtype, guard=GUARD, device="cuda"):
+    def __init__(self, sizes, dtype, guard=GUARD, device="cuda", align_bytes=None):
         import torch
         self.dtype = np.dtype(dtype)
         self.guard = int(guard)
         self.sizes = [int(s) for s in sizes]
+        self.align_bytes = None if align_bytes is None else int(align_bytes)
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        if self.align_bytes is not None:
+            self._init_aligned(torch, tdt, device)
+            return
         self.offsets = []
         at = 0
         for s in self.sizes:
@@ -110,12 +118,32 @@ class Frame:
             self.offsets.append(at)
             at += s
         self.total = at + self.guard
-        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
         self.base = torch.empty(self.total, dtype=tdt, device=device)
         _bits(self.base).fill_(SENTINEL_BITS[self.dtype])
         if self.base.is_cuda:
             assert self.base.data_ptr() % 512 == 0, "the allocator's alignment is not what the frame assumes"
         assert all(o % 2 == 1 for o in self.offsets) and self.offsets[0] == self.guard + 1
+        self._sealed = None
+
+    def _init_aligned(self, torch, tdt, device):
+        """the layout of align_bytes: the offsets are taken from the address the allocator returned"""
+        item = self.dtype.itemsize
+        assert self.align_bytes > 0 and self.align_bytes % item == 0, (self.align_bytes, item)
+        step = self.align_bytes // item
+        self.total = sum(self.sizes) + (len(self.sizes) + 1) * self.guard + (len(self.sizes) + 1) * step
+        self.base = torch.empty(self.total, dtype=tdt, device=device)
+        _bits(self.base).fill_(SENTINEL_BITS[self.dtype])
+        assert self.base.data_ptr() % item == 0
+        first = self.base.data_ptr() // item          # the base's address in elements
+        self.offsets = []
+        at = 0
+        for s in self.sizes:
+            at += self.guard
+            at += -(first + at) % step
+            self.offsets.append(at)
+            at += s
+        assert at + self.guard <= self.total
+        assert all((self.base.data_ptr() + o * item) % self.align_bytes == 0 for o in self.offsets)
         self._sealed = None
 
     def __len__(self):
