@@ -1219,6 +1219,48 @@ BSP_LANCZOS_API(f32, float)
 #undef BSP_LANCZOS_API
 #undef BSP_LZ_BASIS
 #undef BSP_LZ_HEAD
+// ---- combinations of basis vectors ----------------------------------------------
+template <typename T>
+static void krylovCombineRun(bsp_solver* s, int64_t n, int64_t q, int32_t nf, const T* const* basis,
+                             int64_t slotStride, int64_t slots, int64_t slot, int64_t count, int64_t first,
+                             const double* y, int64_t ldy, const int64_t* limit, T* const* out, int64_t outStride,
+                             int32_t accumulate, int32_t batch, bool single) {
+  if (s == nullptr) throw std::runtime_error("krylovCombine: the solver is NULL");
+  KrylovCombineArgs<T> a;
+  a.n = n;
+  a.q = q;
+  a.nf = nf;
+  a.slots = slots;
+  a.slotStride = slotStride;
+  a.slot = slot;
+  a.count = count;
+  a.first = first;
+  a.ldy = ldy;
+  a.outStride = outStride;
+  a.accumulate = accumulate != 0;
+  a.basis = basis;
+  a.y = y;
+  a.limit = limit;
+  a.out = out;
+  s->solver->krylovCombine<T>(a, batch, single);
+}
+#define BSP_KV_MID                                                                                            \
+  int64_t slot_stride, int64_t slots, int64_t slot, int64_t count, int64_t first, const double *y, int64_t ldy, \
+      const int64_t *limit
+#define BSP_KRYLOV_API(SFX, T)                                                                                  \
+  int bsp_krylov_combine_##SFX(bsp_solver* s, int64_t n, int64_t q, int32_t nf, const T* basis, BSP_KV_MID,     \
+                               T* out, int64_t out_stride, int32_t accumulate)                                  \
+      BSP_BODY(krylovCombineRun<T>(s, n, q, nf, &basis, slot_stride, slots, slot, count, first, y, ldy, limit,  \
+                                   &out, out_stride, accumulate, 1, true))                                      \
+  int bsp_krylov_combine_batched_##SFX(bsp_solver* s, int64_t n, int64_t q, int32_t nf, const T* const* basis,  \
+                                       BSP_KV_MID, T* const* out, int64_t out_stride, int32_t accumulate,       \
+                                       int32_t batch)                                                           \
+      BSP_BODY(krylovCombineRun<T>(s, n, q, nf, basis, slot_stride, slots, slot, count, first, y, ldy, limit,   \
+                                   out, out_stride, accumulate, batch, false))
+BSP_KRYLOV_API(f64, double)
+BSP_KRYLOV_API(f32, float)
+#undef BSP_KRYLOV_API
+#undef BSP_KV_MID
 int bsp_scalar_permutation(const bsp_solver* s, int64_t* out) {
   BSP_TRY
   if (out == nullptr) throw std::runtime_error("bsp_scalar_permutation: out is NULL");

@@ -300,6 +300,23 @@ inline int64_t lanczosWorkBytes(int64_t n, int64_t q, int64_t kmax) {
 template <typename T>
 void hipBackendLanczos(SymbolicCtx& sym, const LanczosArgs<T>& a, int64_t batch, bool single);
 
+// Combinations of basis vectors (kvCombine, hip_lanczos_kernels.h): for the nf outputs f
+// and the q columns c of every member, out_f[:, c] = (accumulate ? out_f[:, c] : +0) + sum_i T(y[c, f, i]) slot
+// (slot + i)[:, c], i = 0 .. count - 1 ascending, term i skipped (its slot not read) when first + i >= limit[c].
+// The basis is LanczosArgs's; y holds doubles [batch, q, nf, ldy] and limit int64 [batch, q], one array each;
+// output f of a member is the [n, q] array at out + f outStride.
+template <typename T>
+struct KrylovCombineArgs {
+  int64_t n = 0, q = 1, nf = 1, slots = 0, slotStride = 0, slot = 0, count = 0, first = 0, ldy = 0, outStride = 0;
+  bool accumulate = false;
+  const T* const* basis = nullptr;
+  const double* y = nullptr;
+  const int64_t* limit = nullptr;
+  T* const* out = nullptr;
+};
+template <typename T>
+void hipBackendKrylovCombine(SymbolicCtx& sym, const KrylovCombineArgs<T>& a, int64_t batch, bool single);
+
 // Reach solves (hip_reach_kernels.h), one matrix, plan from buildReachPlan (reach.h).
 // reachSolveL: W (numCols x order, column-major, leading dimension order) <- the unit columns of the
 // queries solved through the lumps of their reach below the plan's cut; the caller then runs

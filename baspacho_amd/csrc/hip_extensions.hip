@@ -1156,6 +1156,51 @@ void hipBackendLanczos(SymbolicCtx& sym, const LanczosArgs<T>& a, int64_t batch,
   });
 }
 
+// ---- combinations of basis vectors (kvCombine) -----------------------------------
+// one launch per chunk of members: a workgroup per (1024-row chunk, column), the members on gridDim.y
+template <typename T>
+void hipBackendKrylovCombine(SymbolicCtx& sym, const KrylovCombineArgs<T>& a, int64_t batch, bool single) {
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  const int64_t n = a.n, q = a.q;
+  const int64_t nParts = (n + hipk::kRedChunk - 1) / hipk::kRedChunk;
+  if (nParts == 0) return;
+  BASPACHO_CHECK_LT(q, (int64_t)INT32_MAX);
+  BASPACHO_CHECK_LT(nParts * q, (int64_t)INT32_MAX);
+  BASPACHO_CHECK_LT(a.count, (int64_t)INT32_MAX);
+  const BatchPtrs<const T> basis = h.stage(a.basis, batch, single);
+  const BatchPtrs<T> out = h.stage(a.out, batch, single);
+  const int threads = hipk::kRedThreads;
+  const int64_t slotOff = a.slot * a.slotStride;
+  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+    const dim3 grid((unsigned)(nParts * q), nm);
+    const double* y = a.y + q0 * q * a.nf * a.ldy;
+    const int64_t* limit = a.limit + q0 * q;
+    const auto launch = [&](auto nf) {
+      hipk::kvCombine<T, decltype(nf)::value><<<grid, threads, 0, stream>>>(
+          n, (int32_t)q, (int32_t)a.count, a.first, basis.at(q0), slotOff, a.slotStride, y, a.ldy, limit, out.at(q0),
+          a.outStride, a.accumulate);
+    };
+    switch (a.nf) {
+      case 1:
+        launch(std::integral_constant<int, 1>());
+        break;
+      case 2:
+        launch(std::integral_constant<int, 2>());
+        break;
+      case 3:
+        launch(std::integral_constant<int, 3>());
+        break;
+      case 4:
+        launch(std::integral_constant<int, 4>());
+        break;
+      default:
+        throw std::runtime_error("krylovCombine: nf = " + std::to_string(a.nf) + " is outside [1, 4]");
+    }
+  });
+}
+
 // ---- reach solves (hip_reach_kernels.h) ---------------------------------------
 // W (numCols x order, column-major) <- the unit columns of the plan's queries, solved through the lumps
 // of their reach below the cut: one memset, the unit entries of the queries behind the cut, one launch
@@ -1307,6 +1352,7 @@ void hipBackendFactorProduct(SymbolicCtx& sym, const T* const* L, bool transpose
                                          int64_t, bool);                                                        \
   template void hipBackendCg<T>(SymbolicCtx&, const CgArgs<T>&, int64_t, bool);                                 \
   template void hipBackendLanczos<T>(SymbolicCtx&, const LanczosArgs<T>&, int64_t, bool);                       \
+  template void hipBackendKrylovCombine<T>(SymbolicCtx&, const KrylovCombineArgs<T>&, int64_t, bool);           \
   template void hipBackendReachSolveL<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                         \
   template void hipBackendGramBlocks<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                          \
   template T* hipBackendReachWorkspace<T>(SymbolicCtx&, int64_t);                                               \

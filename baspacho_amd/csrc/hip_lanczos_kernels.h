@@ -1,7 +1,8 @@
 // The Lanczos recurrence on the device: the dot products, the fused vector updates
 // and the full reorthogonalisation of Solver::lanczos*.  The product w = A v is not here: it is the
 // caller's (symProduct's mv, or any operator).  Launched by hip_extensions.hip.  Streaming kernels: no
-// matrix cores, no persistent launch, no flags, no atomics.
+// matrix cores, no persistent launch, no flags, no atomics.  At the end: kvCombine, the combinations V y of
+// the basis vectors behind f(A) v, which reads no state record.
 //
 // CONVENTIONS are those of hip_cg_kernels.h: vectors are [n, q] row-major arrays of T, matrix blockIdx.y of
 // a batch finds its operands through pickData, column c of matrix m is one problem with its own state
@@ -285,6 +286,92 @@ __global__ void __launch_bounds__(kRedThreads)
   }
   redFold(red, acc, tid, MergeSum());
   if (tid == 0) work.part()[(int64_t)c * nParts + p] = red[0];
+}
+
+// COMBINE: out_f[:, c] = (accumulate ? out_f[:, c] : +0) + sum_i T(y[c, f, i]) v_i[:, c]
+// for the kNf outputs f of column c in one pass over the slots, v_i the slot `i` of the basis handed in (the
+// launcher has moved it to the first slot of the call).  Term i has the Lanczos index first + i and is taken
+// when first + i < limit[c]: the indices ascend, so the terms taken are the first `take` ones and no slot
+// behind them is read.  The sum runs over i ascending in T, every product rounded before it is added; which
+// terms one call holds does not change the bits of a chain of calls.  The coefficients of problem (m, c) are
+// the doubles y[((m q + c) kNf + f) ldy + i]; their address does not depend on the lane.  The thread's kLzRows
+// rows times kNf sums stay in registers; the slots are loaded kKvGroup at a time, all loads of a group ahead of
+// its additions, which keep their order.  No LDS, no atomics.  Reads take n sizeof(T) bytes per column, writes
+// kNf n sizeof(T).
+constexpr int kKvMaxOut = 4;
+// Slots per group: 4 keeps 16 loads per thread in flight; 8 costs 152 to 181 registers in double (3 to 2 waves per
+// SIMD) and spills scalar registers at 4 outputs
+constexpr int kKvGroup = 4;
+
+template <typename T, int kNf>
+__global__ void __launch_bounds__(kRedThreads)
+    kvCombine(int64_t n, int32_t q, int32_t count, int64_t first, DataRef<const T> basisref, int64_t slotOff,
+              int64_t slotStride, const double* __restrict__ y, int64_t ldy, const int64_t* __restrict__ limit,
+              DataRef<T> outref, int64_t outStride, bool accumulate) {
+  const int tid = threadIdx.x;
+  const int64_t p = blockIdx.x / q;
+  const int32_t c = (int32_t)(blockIdx.x - p * q);
+  const int64_t prob = (int64_t)blockIdx.y * q + c;
+  const int64_t room = limit[prob] - first;
+  const int32_t take = room <= 0 ? 0 : room < count ? (int32_t)room : count;  // (uniform)
+  if (take == 0 && accumulate) return;
+  const GP<const T> basis = pickData(basisref) + slotOff;
+  const GP<T> out = pickData(outref);
+  const double* yc = y + prob * kNf * ldy;
+  T acc[kNf][kLzRows];
+#pragma unroll
+  for (int f = 0; f < kNf; f++) {
+#pragma unroll
+    for (int m = 0; m < kLzRows; m++) {
+      const int64_t i = p * kRedChunk + m * kRedThreads + tid;
+      acc[f][m] = accumulate && i < n ? out[f * outStride + i * q + c] : T(0);
+    }
+  }
+  int32_t k = 0;
+  for (; k + kKvGroup <= take; k += kKvGroup) {
+    T v[kKvGroup][kLzRows];
+#pragma unroll
+    for (int g = 0; g < kKvGroup; g++) {
+      const GP<const T> vg = basis + (int64_t)(k + g) * slotStride;
+#pragma unroll
+      for (int m = 0; m < kLzRows; m++) {
+        const int64_t i = p * kRedChunk + m * kRedThreads + tid;
+        v[g][m] = i < n ? vg[i * q + c] : T(0);
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < kKvGroup; g++) {
+#pragma unroll
+      for (int f = 0; f < kNf; f++) {
+        const T yk = (T)yc[f * ldy + k + g];
+#pragma unroll
+        for (int m = 0; m < kLzRows; m++) acc[f][m] = radd(acc[f][m], rmul(yk, v[g][m]));
+      }
+    }
+  }
+  for (; k < take; k++) {
+    const GP<const T> vk = basis + (int64_t)k * slotStride;
+    T v[kLzRows];
+#pragma unroll
+    for (int m = 0; m < kLzRows; m++) {
+      const int64_t i = p * kRedChunk + m * kRedThreads + tid;
+      v[m] = i < n ? vk[i * q + c] : T(0);
+    }
+#pragma unroll
+    for (int f = 0; f < kNf; f++) {
+      const T yk = (T)yc[f * ldy + k];
+#pragma unroll
+      for (int m = 0; m < kLzRows; m++) acc[f][m] = radd(acc[f][m], rmul(yk, v[m]));
+    }
+  }
+#pragma unroll
+  for (int f = 0; f < kNf; f++) {
+#pragma unroll
+    for (int m = 0; m < kLzRows; m++) {
+      const int64_t i = p * kRedChunk + m * kRedThreads + tid;
+      if (i < n) out[f * outStride + i * q + c] = acc[f][m];
+    }
+  }
 }
 
 }  // namespace hipk

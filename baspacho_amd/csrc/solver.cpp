@@ -1373,6 +1373,42 @@ void Solver::lanczos(const LanczosArgs<T>& a, int64_t batch, bool single) const 
   hipBackendLanczos<T>(*symCtx, a, batch, single);
 }
 
+// ---- combinations of basis vectors ---------------------------------------------
+template <typename T>
+void Solver::krylovCombine(const KrylovCombineArgs<T>& a, int64_t batch, bool single) const {
+  const std::string what = "krylovCombine";
+  const auto fail = [&](const std::string& m) { throw std::runtime_error(what + ": " + m); };
+  if (batch < 1) fail("the batch is empty");
+  checkLanczosSizes(what, a.n, a.q, 1);
+  if (a.nf < 1 || a.nf > 4) fail("nf = " + std::to_string(a.nf) + " is outside [1, 4]");
+  const int64_t nq = a.n * a.q;
+  if (a.count < 1) fail("count = " + std::to_string(a.count) + "; a call combines at least one slot");
+  if (a.first < 0) fail("first = " + std::to_string(a.first) + " is negative");
+  if (a.slot < 0) fail("slot = " + std::to_string(a.slot) + " is negative");
+  if (a.slots < 1 || a.count > a.slots || a.slot > a.slots - a.count) {
+    fail("the slots " + std::to_string(a.slot) + " .. " + std::to_string(a.slot) + " + " + std::to_string(a.count) +
+         " - 1 are outside the basis of " + std::to_string(a.slots) + " slots");
+  }
+  if (a.count >= INT32_MAX) fail("count = " + std::to_string(a.count) + " is too large");
+  if (a.slotStride < nq) {
+    fail("the slot stride " + std::to_string(a.slotStride) + " is below n q = " + std::to_string(nq));
+  }
+  if (a.outStride < nq) {
+    fail("the output stride " + std::to_string(a.outStride) + " is below n q = " + std::to_string(nq));
+  }
+  if (a.ldy < a.count) fail("ldy = " + std::to_string(a.ldy) + " is below count = " + std::to_string(a.count));
+  if (a.y == nullptr) fail("the coefficient pointer is NULL");
+  if (a.limit == nullptr) fail("the limit pointer is NULL");
+  if (a.basis == nullptr) fail("the basis pointers are NULL");
+  if (a.out == nullptr) fail("the output pointers are NULL");
+  for (int64_t m = 0; m < batch; m++) {
+    if (nq > 0 && a.basis[m] == nullptr) fail("the basis pointer of batch member " + std::to_string(m) + " is NULL");
+    if (nq > 0 && a.out[m] == nullptr) fail("the output pointer of batch member " + std::to_string(m) + " is NULL");
+  }
+  if (a.n == 0) return;
+  hipBackendKrylovCombine<T>(*symCtx, a, batch, single);
+}
+
 // ---- blocks of A^-1 by reach solves (reach.h) --------------------------------
 ReachPlan Solver::reachPlan(const char* what, const std::vector<int64_t>& params, const std::vector<int64_t>& pairRow,
                             const std::vector<int64_t>& pairCol, const std::vector<int64_t>& outOffsets) const {
@@ -1541,6 +1577,7 @@ void Solver::mulLt(const std::vector<T*>& L, const std::vector<T*>& x, int64_t i
   template void Solver::invNorm1Estimate<T>(BspCVec_##T, BspCVec_##T, void*, int64_t*, double*, bool) const;   \
   template void Solver::cg<T>(const CgArgs<T>&, int64_t, bool) const;                                          \
   template void Solver::lanczos<T>(const LanczosArgs<T>&, int64_t, bool) const;                                \
+  template void Solver::krylovCombine<T>(const KrylovCombineArgs<T>&, int64_t, bool) const;                    \
   template void Solver::reachSolveL<T>(const T*, const std::vector<int64_t>&, T*) const;                       \
   template void Solver::inverseBlocks<T>(const T*, const std::vector<int64_t>&, const std::vector<int64_t>&,   \
                                          T*, const std::vector<int64_t>&) const;

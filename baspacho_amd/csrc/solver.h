@@ -23,6 +23,8 @@ template <typename T>
 struct CgArgs;
 template <typename T>
 struct LanczosArgs;
+template <typename T>
+struct KrylovCombineArgs;
 struct ReachPlan;
 
 class Solver {
@@ -316,6 +318,17 @@ class Solver {
   int64_t lanczosWorkBytes(int64_t n, int64_t q, int64_t kmax) const;
   template <typename T>
   void lanczos(const LanczosArgs<T>& a, int64_t batch, bool single) const;
+  // extension: combinations of the vectors of a basis (kvCombine, hip_lanczos_kernels.h):
+  // for the nf outputs f and the q columns c of every member, out_f[:, c] = (accumulate ? out_f[:, c] : +0) +
+  // sum_i T(y[c, f, i]) slot (slot + i)[:, c] over i = 0 .. count - 1 ascending in T, every product rounded
+  // before it is added; term i has the index first + i and is skipped, its slot not read, when first + i >=
+  // limit[c].  `a` (KrylovCombineArgs, hip_backend.h): the basis as LanczosArgs's, one pointer per member; y,
+  // doubles [batch, q, nf, ldy], and limit, int64 [batch, q], one array each; out, one pointer per member, its
+  // output f at out + f outStride.  Runs on the stream of setStream(), nothing is allocated and nothing read
+  // back.  Refused before any device work: an empty batch, n, q or nf out of range, a count below 1, a negative
+  // first, slots outside the basis, a slot or output stride below n q, ldy below count, a NULL pointer.
+  template <typename T>
+  void krylovCombine(const KrylovCombineArgs<T>& a, int64_t batch, bool single) const;
   // extension: blocks of A^-1 anywhere, on or off the pattern of L, by reach solves (DESIGN.md section 20;
   // reach.h, hip_reach_kernels.h).  `L` holds a complete factor() and is only read; params are the
   // caller's param ids (repeats allowed).  Both run on the stream of setStream() without host

@@ -939,6 +939,40 @@ int bsp_lanczos_normalize_f32(bsp_solver* s, int64_t n, int64_t q, int64_t kmax,
 int bsp_lanczos_normalize_batched_f32(bsp_solver* s, int64_t n, int64_t q, int64_t kmax, const float* const* dev_w,
                                       float* const* dev_basis, int64_t slot_stride, int64_t slots, int64_t slot,
                                       void* dev_work, int64_t* dev_state, int32_t batch);
+/* EXTENSION without a counterpart in the reference's library: combinations of the vectors of a basis (DESIGN.md
+   section 26), the tall-skinny product behind f(A) v ~ |v0| V f(T_k) e_1 from a Lanczos basis.  For each output
+   f < nf and each column c < q of every member
+     out_f[:, c] = (accumulate ? out_f[:, c] : +0) + sum_i T(y[c, f, i]) slot (slot + i)[:, c],
+   i = 0 .. count - 1 in ascending order, the arithmetic in the data type T with every product rounded before
+   it is added (the convention of bsp_lanczos_subtract_*).  Term i has the Lanczos index first + i: it is skipped,
+   and its slot not read, when first + i >= dev_limit[c].  The order is fixed so that the bits of a result do not
+   depend on how the terms are split over calls: a chain of calls with accumulate != 0 over consecutive ranges
+   gives the bits of one call over all of them.  dev_basis, slot_stride and slots are those of bsp_lanczos_*
+   (slot s is the [n, q] row-major vector at dev_basis + s slot_stride); dev_y holds doubles [q, nf, ldy], the
+   coefficient of (c, f, i) at (c nf + f) ldy + i, and for a batch [batch, q, nf, ldy], one array; dev_limit
+   holds int64 [q], for a batch [batch, q], one array; output f of a member is the [n, q] array at dev_out +
+   f out_stride.  A column with no term taken gets +0 (accumulate == 0) or is left as it is.  Every slot is read
+   once for all nf outputs: min(count, limit - first) n q sizeof(T) bytes read, nf n q sizeof(T) written.  No
+   atomics, no workspace; member b of a batched call is bitwise the single call.  Refused before any device
+   work: NULL arguments, an empty batch or a NULL member, n < 0, q < 1, nf outside 1 .. 4, count < 1, first < 0,
+   slot < 0, slot + count > slots, slot_stride < n q, out_stride < n q, ldy < count.  n == 0 succeeds without a
+   launch. */
+int bsp_krylov_combine_f64(bsp_solver* s, int64_t n, int64_t q, int32_t nf, const double* dev_basis,
+                           int64_t slot_stride, int64_t slots, int64_t slot, int64_t count, int64_t first,
+                           const double* dev_y, int64_t ldy, const int64_t* dev_limit, double* dev_out,
+                           int64_t out_stride, int32_t accumulate);
+int bsp_krylov_combine_batched_f64(bsp_solver* s, int64_t n, int64_t q, int32_t nf, const double* const* dev_basis,
+                                   int64_t slot_stride, int64_t slots, int64_t slot, int64_t count, int64_t first,
+                                   const double* dev_y, int64_t ldy, const int64_t* dev_limit,
+                                   double* const* dev_out, int64_t out_stride, int32_t accumulate, int32_t batch);
+int bsp_krylov_combine_f32(bsp_solver* s, int64_t n, int64_t q, int32_t nf, const float* dev_basis,
+                           int64_t slot_stride, int64_t slots, int64_t slot, int64_t count, int64_t first,
+                           const double* dev_y, int64_t ldy, const int64_t* dev_limit, float* dev_out,
+                           int64_t out_stride, int32_t accumulate);
+int bsp_krylov_combine_batched_f32(bsp_solver* s, int64_t n, int64_t q, int32_t nf, const float* const* dev_basis,
+                                   int64_t slot_stride, int64_t slots, int64_t slot, int64_t count, int64_t first,
+                                   const double* dev_y, int64_t ldy, const int64_t* dev_limit,
+                                   float* const* dev_out, int64_t out_stride, int32_t accumulate, int32_t batch);
 /* out[i_user] = i_internal (order values): the caller's scalar i in the solver's internal vector order
    (param p at spanStart[paramToSpan[p]], its scalars in order) */
 int bsp_scalar_permutation(const bsp_solver* s, int64_t* out);
