@@ -1660,6 +1660,25 @@ class SymProduct(_EntryMap):
                                               entry.ctypes.data_as(_I32P), pos.ctypes.data_as(_I32P)))
         return bs, st, entry, pos, {"blocks": nb, "items": items, "inverse_elems": int(out[2]), "max_width": int(out[3])}
 
+    def cgFsaiTable(self):
+        """the host plan of the "fsai" preconditioner of the conjugate gradient: a dict of
+        int32 arrays and info.  Row i of G sits on the scalars cols[row_start[i] : row_start[i + 1]], ascending,
+        i last (the 31 largest of the earlier ones when there are more); its items are (entry[t], pos[t]), t in
+        [item_start[i], item_start[i + 1]), in ascending entry index, pos = la w + lb in the row's local matrix;
+        column j of G is (col_pos[t], col_row[t]), t in [col_start[j], col_start[j + 1]), rows ascending; long_cols
+        lists the columns of more than 64 terms; info = {rows, items, elems, max_width}.  Host work only."""
+        out = (ctypes.c_int64 * 4)()
+        _check(self._lib.bsp_cg_precond_info(self._h, ctypes.c_int32(3), out))
+        n, items, elems = int(out[0]), int(out[1]), int(out[2])
+        sizes = {"row_start": n + 1, "cols": elems, "item_start": n + 1, "entry": items, "pos": items,
+                 "col_start": n + 1, "col_pos": elems, "col_row": elems, "long_cols": n}
+        t = {k: np.zeros(max(v, 1), dtype=np.int32) for k, v in sizes.items()}
+        _check(self._lib.bsp_fsai_table(self._h, *(a.ctypes.data_as(_I32P) for a in t.values())))
+        t = {k: a[:sizes[k]] for k, a in t.items()}
+        t["long_cols"] = t["long_cols"][:int((np.diff(t["col_start"]) > 64).sum())]
+        t["info"] = {"rows": n, "items": items, "elems": elems, "max_width": int(out[3])}
+        return t
+
     def _run(self, name, fn, a, a_what, x, out, batched):
         """a: values [nnz] / [B, nnz] (mv) or g, shaped like x (outer); x [n] / [n, q], or those with a
         leading B when `batched`; out [.., n(, q)] (mv) or [.., nnz] (outer)"""

@@ -9,7 +9,8 @@ import numpy as np
 from . import _call, _check, _ptr_arg, _ptr_of, _suffix
 
 STOPS = ("running", "converged", "step limit", "breakdown", "non-finite", "zero right-hand side")
-PRECOND_KINDS = {"jacobi": 1, "block_jacobi": 2}
+PRECOND_KINDS = {"jacobi": 1, "block_jacobi": 2, "fsai": 3}
+FSAI = PRECOND_KINDS["fsai"]
 MAX_BLOCK = 32  # widest param of block_jacobi
 
 
@@ -24,9 +25,10 @@ def check_settings(what, tol, max_steps, check_every):
 
 
 class Preconditioner:
-    """A built-in preconditioner (kind "jacobi" or "block_jacobi") of the SymProduct `product` for the entry
-    values [nnz] / [B, nnz], built on the device (bsp_cg_precond_build_*): `values` of the inverses, and
-    `status`, int64 [2] / [B, 2] = {the caller's scalar of the lowest bad pivot or -1, bad blocks}."""
+    """A built-in preconditioner (kind "jacobi", "block_jacobi" or "fsai") of the SymProduct `product` for the
+    entry values [nnz] / [B, nnz], built on the device (bsp_cg_precond_build_*): `values` of the inverses (of
+    the sparse factor G of the approximate inverse G^T G for "fsai"), and `status`, int64
+    [2] / [B, 2] = {the caller's scalar of the lowest bad pivot or -1, bad blocks (rows of G for "fsai")}."""
 
     def __init__(self, product, kind, values):
         import torch
@@ -73,6 +75,7 @@ class CgRun:
         self.p = torch.zeros_like(b)
         self.ap = torch.zeros_like(b)
         self.z = torch.zeros_like(b) if self.built_in else None
+        self.t = torch.zeros_like(b) if self.built_in and precond.kind == FSAI else None  # scratch: t = G r
         lead = tuple(b.shape[:-2])
         self.state = torch.zeros(lead + (self.q, 12), dtype=torch.int64, device=b.device)
         need = ctypes.c_int64(0)
@@ -103,6 +106,10 @@ class CgRun:
         """z = M^-1 r, rz and beta; returns the tensor that holds z"""
         if self.built_in:
             pc = self.precond
+            if pc.kind == FSAI:
+                _call(self._lib, "bsp_fsai_apply_", self.batched, self.sfx, self.solver._h, pc.product._h, *self._nq,
+                      *self._args("fsai", pc.values, self.r, self.t, self.z), *self._tail, *self._count)
+                return self.z
             self._piece("precond", pc.product._h, ctypes.c_int32(pc.kind), *self._nq,
                         *self._args("precond", pc.values, self.r, self.z))
             return self.z

@@ -1012,9 +1012,41 @@ int bsp_cg_work_bytes(const bsp_solver* s, int64_t n, int64_t q, int64_t* out) {
 int bsp_cg_precond_info(const bsp_sym_product* p, int32_t kind, int64_t out[4]) {
   BSP_TRY
   if (p == nullptr || out == nullptr) throw std::runtime_error("bsp_cg_precond_info: NULL argument");
+  if (kind == CgFsai) {
+    const CgFsaiPlan& fs = cgFsaiPlan(*p->map);
+    const int64_t v[4] = {fs.n, fs.numItems(), fs.elems(), fs.maxWidth};
+    std::copy(v, v + 4, out);
+    return 0;
+  }
   const CgPrecondPlan& pl = cgPrecondPlan(*p->map, kind);
   const int64_t v[4] = {pl.numBlocks, pl.numItems(), pl.inverseElems(), pl.maxWidth};
   std::copy(v, v + 4, out);
+  BSP_CATCH
+}
+int bsp_fsai_table(const bsp_sym_product* p, int32_t* row_start, int32_t* cols, int32_t* item_start, int32_t* entry,
+                      int32_t* pos, int32_t* col_start, int32_t* col_pos, int32_t* col_row, int32_t* long_cols) {
+  BSP_TRY
+  if (p == nullptr) throw std::runtime_error("bsp_fsai_table: the map is NULL");
+  const CgFsaiPlan& fs = cgFsaiPlan(*p->map);
+  if (row_start == nullptr || item_start == nullptr || col_start == nullptr ||
+      (fs.elems() > 0 && (cols == nullptr || col_pos == nullptr || col_row == nullptr || long_cols == nullptr)) ||
+      (fs.numItems() > 0 && (entry == nullptr || pos == nullptr))) {
+    throw std::runtime_error("bsp_fsai_table: an output array is NULL");
+  }
+  std::copy(fs.rowStart.begin(), fs.rowStart.end(), row_start);
+  std::copy(fs.cols.begin(), fs.cols.end(), cols);
+  std::copy(fs.itemStart.begin(), fs.itemStart.end(), item_start);
+  std::copy(fs.itemEntry.begin(), fs.itemEntry.end(), entry);
+  std::copy(fs.itemPos.begin(), fs.itemPos.end(), pos);
+  std::copy(fs.colRuns.start.begin(), fs.colRuns.start.end(), col_start);
+  std::copy(fs.colRuns.entry.begin(), fs.colRuns.entry.end(), col_pos);
+  std::copy(fs.colRuns.idx.begin(), fs.colRuns.idx.end(), col_row);
+  std::copy(fs.colRuns.longRuns.begin(), fs.colRuns.longRuns.end(), long_cols);
+  BSP_CATCH
+}
+int bsp_fsai_check_sizes(int64_t elems, int64_t items) {
+  BSP_TRY
+  checkCgFsaiSizes(elems, items);
   BSP_CATCH
 }
 int bsp_cg_precond_table(const bsp_sym_product* p, int32_t kind, int32_t* block_start, int32_t* item_start,
@@ -1090,6 +1122,15 @@ static void cgRun(bsp_solver* s, const bsp_sym_product* p, int32_t op, int32_t k
                                    int64_t* state, int32_t batch)                                                \
       BSP_BODY(cgRun<T>(s, m, CgPrecond, kind, false, n, q, minv, r, z, nullptr, 0, 0, work, state, nullptr,     \
                         batch, false))                                                                           \
+  int bsp_fsai_apply_##SFX(bsp_solver* s, const bsp_sym_product* m, int64_t n, int64_t q, const T* g,         \
+                              const T* r, T* t, T* z, void* work, int64_t* state)                               \
+      BSP_BODY(cgRun<T>(s, m, CgFsaiApply, CgFsai, false, n, q, &g, &r, &z, &t, 0, 0, work, state, nullptr, 1,   \
+                        true))                                                                                   \
+  int bsp_fsai_apply_batched_##SFX(bsp_solver* s, const bsp_sym_product* m, int64_t n, int64_t q,             \
+                                      const T* const* g, const T* const* r, T* const* t, T* const* z,           \
+                                      void* work, int64_t* state, int32_t batch)                                 \
+      BSP_BODY(cgRun<T>(s, m, CgFsaiApply, CgFsai, false, n, q, g, r, z, t, 0, 0, work, state, nullptr, batch,   \
+                        false))                                                                                  \
   int bsp_cg_direction_##SFX(bsp_solver* s, int64_t n, int64_t q, const T* z, T* p, int32_t plain, void* work,   \
                              int64_t* state)                                                                     \
       BSP_BODY(cgRun<T>(s, nullptr, CgDirection, 0, plain != 0, n, q, &z, nullptr, &p, nullptr, 0, 0, work,      \

@@ -242,14 +242,24 @@ void hipBackendNormEstStep(SymbolicCtx& sym, int32_t step, void* work, const T* 
 //                 z = M^-1 r, rz, beta
 //   CgDirection:  in0 = z (r when plain); out0 = p: p = z + beta p
 //   CgBuild:      in0 = the entry values; out0 = the preconditioner's values; status: 2 words per matrix
-enum CgOp : int32_t { CgInit = 0, CgAlpha = 1, CgUpdate = 2, CgPrecond = 3, CgDirection = 4, CgBuild = 5 };
+//   CgFsaiApply:  kind CgFsai (section 27): in0 = the values of G, in1 = r; out0 = z, out1 = t (scratch):
+//                 t = G r, z = G^T t, rz, beta
+enum CgOp : int32_t {
+  CgInit = 0,
+  CgAlpha = 1,
+  CgUpdate = 2,
+  CgPrecond = 3,
+  CgDirection = 4,
+  CgBuild = 5,
+  CgFsaiApply = 6
+};
 template <typename T>
 struct CgArgs {
   int32_t op = CgInit, kind = 0;  // kind: CgPrecondKind (sym_product.h)
   bool plain = false;
   int64_t n = 0, q = 1, maxSteps = 0;
   double tol = 0.0;
-  const SymProductMap* map = nullptr;  // CgPrecond of kinds 1 and 2, CgBuild
+  const SymProductMap* map = nullptr;  // CgPrecond of kinds 1 and 2, CgBuild, CgFsaiApply
   const T* const* in0 = nullptr;
   const T* const* in1 = nullptr;
   T* const* out0 = nullptr;

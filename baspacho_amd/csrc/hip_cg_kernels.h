@@ -1,5 +1,6 @@
 // Preconditioned conjugate gradient on the device: the dot products, the fused
-// vector updates and the two built-in preconditioners of Solver::cg*.  The product A p is not here: it
+// vector updates and the built-in preconditioners of Solver::cg* (Jacobi, block-Jacobi, and the factorised
+// sparse approximate inverse of section 27 at the end of the file).  The product A p is not here: it
 // is the caller's (symProduct's mv, or any operator).  Launched by hip_extensions.hip.  Streaming
 // kernels: no matrix cores, no persistent launch, no flags, no atomics.
 //
@@ -32,7 +33,7 @@
 //
 // THE STATUS RECORD of a built-in preconditioner: 2 8-byte words per matrix, {the caller's scalar of the
 // first bad pivot (the lowest one) or -1, the number of bad blocks}.  A block whose pivot is not a
-// positive finite number gets the zero matrix as its inverse.
+// positive finite number gets the zero matrix as its inverse (fsai: a row of G, which becomes zeros).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -383,6 +384,186 @@ __global__ void __launch_bounds__(kRedThreads)
   RedPart acc{0.0, INT64_MAX};
   for (int64_t b = tid; b < numBlocks; b += kRedThreads) {
     if (bad[b] >= 0) acc = MergeBadPivot()(acc, RedPart{1.0, (int64_t)pl.blockStart[b] + bad[b]});
+  }
+  redFold(red, acc, tid, MergeBadPivot());
+  if (tid != 0) return;
+  status[2 * (int64_t)blockIdx.y] = red[0].v > 0.0 ? red[0].k : -1;
+  status[2 * (int64_t)blockIdx.y + 1] = (int64_t)red[0].v;
+}
+
+// ---- the factorised sparse approximate inverse M^-1 = G^T G ---------------------
+constexpr int kCgFsaiMaxRow = 32;    // widest row of G
+constexpr int kCgFsaiRowsPerWg = 4;  // one wave per row
+
+// the tables of a CgFsaiPlan on the device (sym_product.h)
+struct CgFsaiDev {
+  const int32_t *rowStart, *cols;                                  // [n + 1], [elements of G]
+  const int32_t *itemStart, *itemEntry, *itemPos;                  // [n + 1], [items] x 2
+  const int32_t *colStart, *colPos, *colRow;                       // [n + 1], [elements of G] x 2
+  const int32_t *longCols, *chunkLongFirst;                        // the long columns, those of every chunk
+};
+
+// Row i of G by one wave, all in double in the wave's part of LDS: the local matrix A[S_i, S_i] (lower
+// triangle) from its items in ascending entry index, Cholesky column by column with cgBlockBuild's
+// operations, then the last row of L^-1 by back substitution: g_{w-1} = 1 / L_{w-1,w-1}, g_c = -(sum_{k >
+// c} L_kc g_k) / L_cc, k ascending from +0, every product rounded.  A bad pivot gives a row of zeros and its
+// local step in the bad word of the row.  The waves of a workgroup do not meet: only waveSync.
+template <typename T>
+__global__ void __launch_bounds__(64 * kCgFsaiRowsPerWg)
+    cgFsaiBuild(int64_t n, CgFsaiDev pl, DataRef<const T> vref, DataRef<T> gref, CgWork work) {
+  __shared__ double lds[kCgFsaiRowsPerWg][kCgFsaiMaxRow * kCgFsaiMaxRow + kCgFsaiMaxRow];
+  const int lane = threadIdx.x & 63;
+  const int wave = waveUniform((int32_t)(threadIdx.x >> 6));
+  const int64_t i = (int64_t)blockIdx.x * kCgFsaiRowsPerWg + wave;
+  if (i >= n) return;
+  double* A = lds[wave];
+  double* g = A + kCgFsaiMaxRow * kCgFsaiMaxRow;
+  const int32_t g0 = waveUniform(pl.rowStart[i]);
+  const int w = waveUniform(pl.rowStart[i + 1]) - g0;
+  const GP<const T> v = pickData(vref);
+  const GP<T> out = pickData(gref) + g0;
+  for (int e = lane; e < w * w; e += 64) A[e] = 0.0;
+  waveSync();
+  // every element is owned by one lane, which meets its entries in ascending entry index
+  const int32_t t0 = waveUniform(pl.itemStart[i]), t1 = waveUniform(pl.itemStart[i + 1]);
+  for (int32_t t = t0; t < t1; t++) {
+    const int32_t pos = pl.itemPos[t];
+    if ((pos & 63) == lane) A[pos] = radd(A[pos], (double)v[pl.itemEntry[t]]);
+  }
+  waveSync();
+  int bad = -1;
+  for (int k = 0; k < w; k++) {
+    const double d = A[k * w + k];  // (the same value in every lane: the loop stays uniform)
+    if (!(d > 0.0) || !redFinite(d)) {
+      bad = k;
+      break;
+    }
+    const double s = __builtin_sqrt(d);
+    waveSync();
+    if (lane == 0) A[k * w + k] = s;
+    for (int r = k + 1 + lane; r < w; r += 64) A[r * w + k] = A[r * w + k] / s;
+    waveSync();
+    // the trailing lower triangle: element (r, c), k < c <= r
+    for (int e = lane; e < w * w; e += 64) {
+      const int r = e / w, c = e - r * w;
+      if (c > k && c <= r) A[e] = radd(A[e], -rmul(A[r * w + k], A[c * w + k]));
+    }
+    waveSync();
+  }
+  if (bad >= 0) {
+    if (lane < w) out[lane] = T(0);
+    if (lane == 0) work.bad()[i] = bad;
+    return;
+  }
+  if (lane == 0) {
+    g[w - 1] = 1.0 / A[(w - 1) * w + (w - 1)];
+    for (int c = w - 2; c >= 0; c--) {
+      double s = 0.0;
+      for (int k = c + 1; k < w; k++) s = radd(s, rmul(A[k * w + c], g[k]));
+      g[c] = -s / A[c * w + c];
+    }
+    work.bad()[i] = -1;
+  }
+  waveSync();
+  if (lane < w) out[lane] = (T)g[lane];
+}
+
+// t = G r, one lane per (row, right-hand side): t_i = T(sum_c double(G_ic) double(r_cols[c])), c ascending
+template <typename T>
+__global__ void __launch_bounds__(kRedThreads)
+    cgFsaiLower(int64_t n, int32_t q, CgFsaiDev pl, DataRef<const T> gref, DataRef<const T> rref, DataRef<T> tref,
+                const CgState* __restrict__ state) {
+  const int64_t e = (int64_t)blockIdx.x * kRedThreads + threadIdx.x;
+  if (e >= n * q) return;
+  const int64_t i = e / q;
+  const int32_t j = (int32_t)(e - i * q);
+  if (state[(int64_t)blockIdx.y * q + j].stop != CgRunning) return;
+  const GP<const T> g = pickData(gref), r = pickData(rref);
+  const int32_t* __restrict__ cols = pl.cols;
+  const double s = sumRunByLane(pl.rowStart[i], pl.rowStart[i + 1],
+                                [=](int32_t x) { return cgProd((double)g[x], (double)r[(int64_t)cols[x] * q + j]); });
+  pickData(tref)[e] = (T)s;
+}
+
+// z = G^T t with the partials of r.z, in cgPrecond's workgroups: z_i = T(sum double(G_ki) double(t_k)) over
+// column i of G, k ascending.  The long columns of the chunk go first, one wave each (the same sequential
+// sum); then every thread takes its rows in cgPrecond's order, the short columns summed by the lane.
+template <typename T>
+__global__ void __launch_bounds__(kRedThreads)
+    cgFsaiUpper(int64_t n, int32_t q, int32_t nParts, CgFsaiDev pl, DataRef<const T> gref, DataRef<const T> tref,
+                DataRef<const T> rref, DataRef<T> zref, CgWork work, const CgState* __restrict__ state) {
+  __shared__ RedPart red[kRedThreads];
+  const int tid = threadIdx.x;
+  const int64_t c = blockIdx.x / q;
+  const int32_t j = (int32_t)(blockIdx.x - c * q);
+  if (state[(int64_t)blockIdx.y * q + j].stop != CgRunning) return;
+  const GP<const T> g = pickData(gref), t = pickData(tref), r = pickData(rref);
+  const GP<T> z = pickData(zref);
+  const int32_t* __restrict__ colPos = pl.colPos;
+  const int32_t* __restrict__ colRow = pl.colRow;
+  const auto term = [=](int32_t x) { return cgProd((double)g[colPos[x]], (double)t[(int64_t)colRow[x] * q + j]); };
+  const int lane = tid & 63;
+  const int wave = waveUniform((int32_t)(tid >> 6));
+  const int32_t l0 = pl.chunkLongFirst[c], l1 = pl.chunkLongFirst[c + 1];
+  for (int32_t l = l0 + wave; l < l1; l += kRedThreads / 64) {
+    const int32_t u = waveUniform(pl.longCols[l]);
+    const double s = sumRunByWave(waveUniform(pl.colStart[u]), waveUniform(pl.colStart[u + 1]), lane, term);
+    if (lane == 0) z[(int64_t)u * q + j] = (T)s;
+  }
+  if (l1 > l0) __syncthreads();  // (uniform) the long columns' z, read back below
+  // the thread's rows side by side, so that their loads overlap: every sum still takes its own terms in
+  // list order from +0 (sumRunByLane's sum)
+  constexpr int kRows = kRedChunk / kRedThreads;
+  int32_t r0[kRows], len[kRows], most = 0;
+  double s[kRows];
+  bool isLong[kRows];
+#pragma unroll
+  for (int m = 0; m < kRows; m++) {
+    const int64_t i = c * kRedChunk + m * kRedThreads + tid;
+    r0[m] = i < n ? pl.colStart[i] : 0;
+    len[m] = i < n ? pl.colStart[i + 1] - r0[m] : 0;
+    isLong[m] = isLongRun(len[m]);
+    if (isLong[m]) len[m] = 0;
+    most = len[m] > most ? len[m] : most;
+    s[m] = 0.0;
+  }
+  for (int32_t k = 0; k < most; k++) {
+#pragma unroll
+    for (int m = 0; m < kRows; m++) {
+      // (the load is not under the condition, so that the rows' loads are in flight together: a row that
+      // has ended reads its first term again, a valid position, and drops it)
+      const double v = term(r0[m] + (k < len[m] ? k : 0));
+      if (k < len[m]) s[m] = radd(s[m], v);
+    }
+  }
+  RedPart acc{0.0, 1};
+#pragma unroll
+  for (int m = 0; m < kRows; m++) {  // (cgChunkRows' rows, in its order)
+    const int64_t i = c * kRedChunk + m * kRedThreads + tid;
+    if (i >= n) continue;
+    const int64_t at = i * q + j;
+    T zi;
+    if (isLong[m]) {
+      zi = z[at];
+    } else {
+      zi = (T)s[m];
+      z[at] = zi;
+    }
+    acc.v = radd(acc.v, cgProd((double)r[at], (double)zi));
+  }
+  redFold(red, acc, tid, MergeSum());
+  if (tid == 0) work.part()[(int64_t)j * nParts + c] = red[0];
+}
+
+// the status record of an fsai build: the bad word of row i is the local step of its bad pivot
+__global__ void __launch_bounds__(kRedThreads)
+    cgFsaiStatus(int64_t n, CgFsaiDev pl, CgWork work, int64_t* __restrict__ status) {
+  __shared__ RedPart red[kRedThreads];
+  const int tid = threadIdx.x;
+  const int32_t* bad = work.bad();
+  RedPart acc{0.0, INT64_MAX};
+  for (int64_t i = tid; i < n; i += kRedThreads) {
+    if (bad[i] >= 0) acc = MergeBadPivot()(acc, RedPart{1.0, (int64_t)pl.cols[pl.rowStart[i] + bad[i]]});
   }
   redFold(red, acc, tid, MergeBadPivot());
   if (tid != 0) return;

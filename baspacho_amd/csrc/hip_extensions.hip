@@ -977,6 +977,8 @@ void hipBackendNormEstStep(SymbolicCtx& sym, int32_t step, void* work, const T* 
 // one piece of an iteration (CgOp) on `batch` matrices: one to four launches per chunk, nothing allocated
 // but the tables of a preconditioner plan, which the first call that needs them uploads
 static_assert(hipk::kCgMaxBlock == kCgMaxBlockWidth, "the build kernel's LDS holds the widest block of the plan");
+static_assert(hipk::kCgFsaiMaxRow == kCgFsaiMaxRow, "the build kernel's LDS holds the widest row of the plan");
+static_assert(hipk::kRedChunk == 1024, "chunkLongFirst of a CgFsaiPlan counts in chunks of 1024 scalars");
 template <typename T>
 void hipBackendCg(SymbolicCtx& sym, const CgArgs<T>& a, int64_t batch, bool single) {
   using In = hipk::DataRef<const T>;
@@ -993,12 +995,21 @@ void hipBackendCg(SymbolicCtx& sym, const CgArgs<T>& a, int64_t batch, bool sing
   const bool builtIn = a.kind == CgJacobi || a.kind == CgBlockJacobi;
   hipk::CgPrecondDev pl{};
   int64_t numBlocks = 0;
-  if ((a.op == CgPrecond && builtIn) || a.op == CgBuild) {
+  if ((a.op == CgPrecond || a.op == CgBuild) && builtIn) {
     const CgPrecondPlan& plan = cgPrecondPlan(*a.map, a.kind);
     HipEntryMapDev& d = HipEntryMapDev::of(a.map->dev);
     pl = {d.get(plan.blockStart), d.get(plan.blockOff),  d.get(plan.scalarBlock),
           d.get(plan.itemStart),  d.get(plan.itemEntry), d.get(plan.itemPos)};
     numBlocks = plan.numBlocks;
+  }
+  const bool fsai = a.kind == CgFsai && (a.op == CgBuild || a.op == CgFsaiApply);
+  hipk::CgFsaiDev fs{};
+  if (fsai) {
+    const CgFsaiPlan& plan = cgFsaiPlan(*a.map);
+    HipEntryMapDev& d = HipEntryMapDev::of(a.map->dev);
+    fs = {d.get(plan.rowStart),      d.get(plan.cols),          d.get(plan.itemStart),        d.get(plan.itemEntry),
+          d.get(plan.itemPos),       d.get(plan.colRuns.start), d.get(plan.colRuns.entry),    d.get(plan.colRuns.idx),
+          d.get(plan.colRuns.longRuns), d.get(plan.chunkLongFirst)};
   }
   const BatchPtrs<const T> i0 = h.stage(a.in0, batch, single), i1 = h.stage(a.in1, batch, single);
   const BatchPtrs<T> o0 = h.stage(a.out0, batch, single), o1 = h.stage(a.out1, batch, single);
@@ -1057,7 +1068,24 @@ void hipBackendCg(SymbolicCtx& sym, const CgArgs<T>& a, int64_t batch, bool sing
           hipk::cgDirection<T><<<perElem, threads, 0, stream>>>(n, (int32_t)q, i0.at(q0), o0.at(q0), st);
         }
         break;
+      case CgFsaiApply:
+        if (perElemWgs > 0) {
+          hipk::cgFsaiLower<T><<<perElem, threads, 0, stream>>>(n, (int32_t)q, fs, i0.at(q0), i1.at(q0), o1.at(q0), st);
+          hipk::cgFsaiUpper<T><<<perChunk, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, fs, i0.at(q0), out1c,
+                                                                  i1.at(q0), o0.at(q0), w, st);
+        }
+        fold(hipk::CgFoldBeta);
+        break;
       case CgBuild:
+        if (fsai) {
+          if (n > 0) {
+            const int64_t wgs = (n + hipk::kCgFsaiRowsPerWg - 1) / hipk::kCgFsaiRowsPerWg;
+            hipk::cgFsaiBuild<T><<<dim3((unsigned)wgs, nm), 64 * hipk::kCgFsaiRowsPerWg, 0, stream>>>(n, fs, i0.at(q0),
+                                                                                                     o0.at(q0), w);
+          }
+          hipk::cgFsaiStatus<<<dim3(1, nm), threads, 0, stream>>>(n, fs, w, a.status + 2 * q0);
+          break;
+        }
         if (numBlocks > 0) {
           if (a.kind == CgJacobi) {
             hipk::cgJacobiBuild<T><<<dim3((unsigned)((n + threads - 1) / threads), nm), threads, 0, stream>>>(

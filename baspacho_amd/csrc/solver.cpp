@@ -1215,14 +1215,21 @@ int64_t Solver::cgWorkBytes(int64_t n, int64_t q) const {
 
 template <typename T>
 void Solver::cg(const CgArgs<T>& a, int64_t batch, bool single) const {
-  static const char* names[6] = {"cgInit", "cgAlpha", "cgUpdate", "cgPrecond", "cgDirection", "cgPrecondBuild"};
-  if (a.op < 0 || a.op > CgBuild) throw std::runtime_error("cg: unknown operation " + std::to_string(a.op));
+  static const char* names[7] = {"cgInit",      "cgAlpha",        "cgUpdate",   "cgPrecond",
+                                 "cgDirection", "cgPrecondBuild", "cgFsaiApply"};
+  if (a.op < 0 || a.op > CgFsaiApply) throw std::runtime_error("cg: unknown operation " + std::to_string(a.op));
   const std::string what = names[a.op];
   const auto fail = [&](const std::string& m) { throw std::runtime_error(what + ": " + m); };
   const bool builtIn = a.kind == CgJacobi || a.kind == CgBlockJacobi;
-  const bool usesMap = a.op == CgBuild || (a.op == CgPrecond && builtIn);
-  if ((a.op == CgBuild && !builtIn) || (a.op == CgPrecond && !builtIn && a.kind != CgGiven)) {
-    fail("unknown preconditioner kind " + std::to_string(a.kind) + " (0: the caller's z, 1: jacobi, 2: block_jacobi)");
+  const bool fsai = a.kind == CgFsai && (a.op == CgBuild || a.op == CgFsaiApply);
+  const bool usesMap = a.op == CgBuild || (a.op == CgPrecond && builtIn) || a.op == CgFsaiApply;
+  if (a.op == CgPrecond && a.kind == CgFsai) {
+    fail("kind 3 (fsai) needs the scratch vector t: it is applied by bsp_fsai_apply_*");
+  }
+  if ((a.op == CgBuild && !builtIn && !fsai) || (a.op == CgPrecond && !builtIn && a.kind != CgGiven) ||
+      (a.op == CgFsaiApply && !fsai)) {
+    fail("unknown preconditioner kind " + std::to_string(a.kind) +
+         " (0: the caller's z, 1: jacobi, 2: block_jacobi, 3: fsai)");
   }
   if (usesMap) {
     if (a.map == nullptr) fail("the map is NULL");
@@ -1253,7 +1260,7 @@ void Solver::cg(const CgArgs<T>& a, int64_t batch, bool single) const {
     int64_t elems;
     bool written;
   };
-  const int64_t invElems = usesMap ? cgPrecondPlan(*a.map, a.kind).inverseElems() : 0;
+  const int64_t invElems = fsai ? cgFsaiPlan(*a.map).elems() : usesMap ? cgPrecondPlan(*a.map, a.kind).inverseElems() : 0;
   const auto c = [](T* const* p) { return const_cast<const T* const*>(p); };
   std::vector<Slot> slots;
   switch (a.op) {
@@ -1268,6 +1275,9 @@ void Solver::cg(const CgArgs<T>& a, int64_t batch, bool single) const {
       slots.push_back({"z", c(a.out0), nq, builtIn});
       break;
     case CgDirection: slots = {{a.plain ? "r" : "z", a.in0, nq, false}, {"p", c(a.out0), nq, true}}; break;
+    case CgFsaiApply:
+      slots = {{"preconditioner", a.in0, invElems, false}, {"r", a.in1, nq, false}, {"t", c(a.out1), nq, true}, {"z", c(a.out0), nq, true}};
+      break;
     default: slots = {{"values", a.in0, a.map->nnz, false}, {"preconditioner", c(a.out0), invElems, true}}; break;
   }
   struct Region {

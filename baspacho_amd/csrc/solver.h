@@ -299,6 +299,7 @@ class Solver {
   // words per member.  n is the caller's (the operator need not be this Solver's matrix), except for the
   // built-in preconditioners, whose map must be this Solver's and of order n.  The product A p between
   // CgDirection and CgAlpha is the caller's.  Stopped columns are left bitwise unchanged by every piece.
+  // CgFsaiApply (kind CgFsai, section 27) takes CgPrecond's place with a scratch vector t of its own.
   // Runs on the stream of setStream(), nothing is allocated (the first use of a preconditioner uploads its
   // plan) and nothing read back.  Refused before any device work: an empty batch, n or q out of range, a NULL
   // or misaligned workspace, a NULL pointer, a map of another Solver or order, a negative or NaN tolerance or

@@ -29,14 +29,32 @@ namespace BaSpaCho {
 // entry k at (i, j), i >= j, both in block b, with itemPos = (i - s) w + (j - s), s the block's first
 // scalar and w its width.  The inverse of block b takes the elements [blockOff[b], blockOff[b + 1]) of
 // the preconditioner's values, row-major.
-enum CgPrecondKind : int32_t { CgGiven = 0, CgJacobi = 1, CgBlockJacobi = 2 };
+enum CgPrecondKind : int32_t { CgGiven = 0, CgJacobi = 1, CgBlockJacobi = 2, CgFsai = 3 };
 constexpr int64_t kCgMaxBlockWidth = 32;
+constexpr int64_t kCgFsaiMaxRow = 32;  // widest row of the factorised sparse approximate inverse
 struct CgPrecondPlan {
   int32_t kind = CgJacobi;
   int64_t n = 0, numBlocks = 0, maxWidth = 0;
   std::vector<int32_t> blockStart, scalarBlock, itemStart, itemEntry, itemPos;
   std::vector<int64_t> blockOff;
   int64_t inverseElems() const { return blockOff.empty() ? 0 : blockOff.back(); }
+  int64_t numItems() const { return (int64_t)itemEntry.size(); }
+};
+
+// The plan of the factorised sparse approximate inverse M^-1 = G^T G, G lower
+// triangular on the pattern of the lower triangle of A.  Row i of G sits on the scalars cols[rowStart[i]
+// .. rowStart[i + 1]), ascending: i itself, last, and the scalars j < i with a kept entry at (i, j) (a zero
+// value counts, duplicates count once), only the kCgFsaiMaxRow - 1 largest of them when there are more.
+// The items of row i are (itemEntry[t], itemPos[t]), t in [itemStart[i], itemStart[i + 1]), in ascending
+// entry index: the kept entry k at (a, b), a >= b, both in the row's set, with itemPos = la w + lb, la and
+// lb the local indices of a and b and w the row's width.  Column j of G is run j of colRuns: (position in
+// the values of G, row) in ascending row, with the list of the columns of more than kAssemblyLongRun terms;
+// chunkLongFirst[c] is the first of them at or past scalar 1024 c (the chunks of the dot products).
+struct CgFsaiPlan {
+  int64_t n = 0, maxWidth = 0;
+  std::vector<int32_t> rowStart, cols, itemStart, itemEntry, itemPos, chunkLongFirst;
+  RunList colRuns;
+  int64_t elems() const { return (int64_t)cols.size(); }
   int64_t numItems() const { return (int64_t)itemEntry.size(); }
 };
 
@@ -55,6 +73,7 @@ struct SymProductMap {
 
   // the preconditioner plans, built by the first call that asks for one (cgPrecondPlan)
   mutable std::unique_ptr<CgPrecondPlan> cgPlans[3];
+  mutable std::unique_ptr<CgFsaiPlan> cgFsai;
 
   int64_t numTerms() const { return (int64_t)rows.entry.size(); }
   // bytes each part takes on the device once uploaded
@@ -80,5 +99,13 @@ std::unique_ptr<CgPrecondPlan> createCgPrecondPlan(const SymProductMap& map, int
                                                    const std::vector<int64_t>& blockSizes);
 // ... of the map's solver (its params), cached in the map
 const CgPrecondPlan& cgPrecondPlan(const SymProductMap& map, int32_t kind);
+
+// The plan of CgFsai over the entries of `map`.  The element count of G and the item count must be in [0,
+// 2^31): each is checked (and stated) by checkCgFsaiSizes before anything of its size is allocated.  Host
+// only: counting sorts, no comparison sort.
+void checkCgFsaiSizes(int64_t elems, int64_t items);
+std::unique_ptr<CgFsaiPlan> createCgFsaiPlan(const SymProductMap& map);
+// ... cached in the map
+const CgFsaiPlan& cgFsaiPlan(const SymProductMap& map);
 
 }  // namespace BaSpaCho

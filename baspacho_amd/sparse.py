@@ -960,7 +960,7 @@ def _cg_run(pattern, v, b, precond, tol, max_steps, check_every, x0, cache):
         return ap
 
     pc = None
-    if precond in ("jacobi", "block_jacobi"):
+    if precond in ("jacobi", "block_jacobi", "fsai"):
         if precond not in cache:
             cache[precond] = _cg.Preconditioner(prod, precond, v)
         pc = cache[precond]
@@ -1032,8 +1032,10 @@ def solve_cg(pattern, values, b, precond="block_jacobi", tol=1e-10, max_steps=10
     for a zero b (x = 0).  A stopped problem is frozen by the kernels.
 
     precond: None; "jacobi" (z_i = r_i / A_ii); "block_jacobi" (the inverses of the diagonal blocks of the
-    pattern's params, at most 32 scalars each: a ValueError names a wider one), both built and applied on the
-    device; "factor32" (float64 only: the fp32 layout is assembled and factored once and z = the fp32 solve of
+    pattern's params, at most 32 scalars each: a ValueError names a wider one); "fsai" (the factorised sparse
+    approximate inverse z = G^T G r, G lower triangular on the pattern of A's lower triangle with at most 32
+    scalars per row: for the ill-conditioned matrix that is not block-diagonally dominant), all three built and
+    applied on the device; "factor32" (float64 only: the fp32 layout is assembled and factored once and z = the fp32 solve of
     r, as in solve_refined: the mixed-precision pattern, with an iteration instead of a fixed number of
     corrections); or a callable r -> z on tensors shaped like b that enqueues device work.
 
@@ -1045,7 +1047,8 @@ def solve_cg(pattern, values, b, precond="block_jacobi", tol=1e-10, max_steps=10
     side, baspacho_amd.cg.STOPS) and "relres" = sqrt(rr / bb) of the recurrence residual, shaped [] / [k] with a
     leading B for a batch, "state", the int64 records themselves ([.., 12]; baspacho_amd.cg.read_state decodes
     them), and for a built-in preconditioner "precond_status", int64 [2] / [B, 2] = {the
-    caller's scalar of the lowest bad pivot of the preconditioner or -1, the number of bad blocks}.
+    caller's scalar of the lowest bad pivot of the preconditioner or -1, the number of bad blocks (for "fsai":
+    of rows of G, which are then zero)}.
 
     Differentiable in values and b (x0 gets no gradient): b's gradient is solve_cg of the incoming gradient
     with the same settings and the same preconditioner, that of values is -outer(gb, x); both are as exact as
@@ -1059,9 +1062,9 @@ def solve_cg(pattern, values, b, precond="block_jacobi", tol=1e-10, max_steps=10
         if not isinstance(x0, torch.Tensor) or x0.shape != b.shape or x0.dtype != b.dtype or x0.device != b.device:
             raise ValueError("%s: x0 must be a %s tensor of b's shape %s on %s" % (what, b.dtype, tuple(b.shape), b.device))
     if isinstance(precond, str):
-        if precond not in ("jacobi", "block_jacobi", "factor32"):
-            raise ValueError("%s: precond must be None, 'jacobi', 'block_jacobi', 'factor32' or a callable, got %r"
-                             % (what, precond))
+        if precond not in ("jacobi", "block_jacobi", "fsai", "factor32"):
+            raise ValueError("%s: precond must be None, 'jacobi', 'block_jacobi', 'fsai', 'factor32' or a callable, "
+                             "got %r" % (what, precond))
         if precond == "factor32" and values.dtype != torch.float64:
             raise TypeError("%s: precond 'factor32' needs float64 values and b, got %s" % (what, values.dtype))
         if precond == "block_jacobi" and int(pattern.param_sizes.max(initial=0)) > _cg.MAX_BLOCK:
@@ -1069,7 +1072,7 @@ def solve_cg(pattern, values, b, precond="block_jacobi", tol=1e-10, max_steps=10
             raise ValueError("%s: param %d has %d scalars; 'block_jacobi' takes params of at most %d"
                              % (what, p, int(pattern.param_sizes[p]), _cg.MAX_BLOCK))
     elif precond is not None and not callable(precond):
-        raise ValueError("%s: precond must be None, 'jacobi', 'block_jacobi', 'factor32' or a callable, got %r"
+        raise ValueError("%s: precond must be None, 'jacobi', 'block_jacobi', 'fsai', 'factor32' or a callable, got %r"
                          % (what, precond))
     _ag._check_device(pattern.solver, what, values, b)
     x, iters, stop, relres, state, status = _SolveCG.apply(pattern, values, b, precond, float(tol), max_steps,
@@ -1077,7 +1080,7 @@ def solve_cg(pattern, values, b, precond="block_jacobi", tol=1e-10, max_steps=10
     if not return_info:
         return x
     info = {"iterations": iters, "stop": stop, "relres": relres, "state": state}
-    if precond in ("jacobi", "block_jacobi"):
+    if precond in ("jacobi", "block_jacobi", "fsai"):
         info["precond_status"] = status
     return x, info
 

@@ -766,12 +766,41 @@ int bsp_inv_norm1_batched_f32(bsp_solver* s, const float* const* dev_L, const fl
    solver or order, and a written operand that overlaps any other operand, workspace and records included.
    bsp_cg_precond_info: out = {blocks, items, elements of the inverse, widest block};
    bsp_cg_precond_table: the plan's tables (host only): block_start [blocks + 1], item_start [blocks + 1],
-   and per item its entry and its position (i - s) w + (j - s) inside its block. */
+   and per item its entry and its position (i - s) w + (j - s) inside its block.
+   KIND 3, THE FACTORISED SPARSE APPROXIMATE INVERSE: M^-1 = G^T G, G lower triangular
+   on the pattern of the lower triangle of A, at most 32 scalars per row (the row's own and the 31 largest
+   before it); every row comes from its own dense system A[S_i, S_i], so nothing depends on anything else.
+     bsp_cg_precond_info(p, 3, out): out = {rows, items, elements of G, widest row};
+     bsp_cg_precond_build_*(.., 3, ..): dev_minv receives the values of G (out[2] elements per member); a row
+                 whose local Cholesky meets a pivot that is not positive and finite is written as zeros, and
+                 dev_status = {the lowest caller's scalar of such a pivot or -1, the number of such rows};
+     bsp_fsai_apply_*: takes precond's place in the iteration: dev_t = G dev_r (dev_t is the caller's
+                 scratch, [n, q]), dev_z = G^T dev_t, rz and beta.  Sums in double, every product rounded, row
+                 and column terms in ascending scalar order; bsp_cg_precond_* refuses kind 3 and names this entry;
+     bsp_fsai_table: the plan's tables (host only): row_start [n + 1] and cols [elements of G]; item_start
+                 [n + 1] and per item its entry and its position la w + lb in the row's local matrix;
+                 col_start [n + 1] and per column term its position in G and its row; long_cols, the columns of
+                 more than 64 terms, ascending (room for n of them; their number is what col_start says);
+     bsp_fsai_check_sizes: the plan's size check alone: refuses an element or item count outside [0, 2^31)
+                 and states it. */
 int bsp_cg_state_words(int64_t* out);
 int bsp_cg_work_bytes(const bsp_solver* s, int64_t n, int64_t q, int64_t* out);
 int bsp_cg_precond_info(const bsp_sym_product* p, int32_t kind, int64_t out[4]);
 int bsp_cg_precond_table(const bsp_sym_product* p, int32_t kind, int32_t* block_start, int32_t* item_start,
                          int32_t* entry, int32_t* pos);
+int bsp_fsai_table(const bsp_sym_product* p, int32_t* row_start, int32_t* cols, int32_t* item_start, int32_t* entry,
+                      int32_t* pos, int32_t* col_start, int32_t* col_pos, int32_t* col_row, int32_t* long_cols);
+int bsp_fsai_check_sizes(int64_t elems, int64_t items);
+int bsp_fsai_apply_f64(bsp_solver* s, const bsp_sym_product* p, int64_t n, int64_t q, const double* dev_g,
+                          const double* dev_r, double* dev_t, double* dev_z, void* dev_work, int64_t* dev_state);
+int bsp_fsai_apply_batched_f64(bsp_solver* s, const bsp_sym_product* p, int64_t n, int64_t q,
+                                  const double* const* dev_g, const double* const* dev_r, double* const* dev_t,
+                                  double* const* dev_z, void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_fsai_apply_f32(bsp_solver* s, const bsp_sym_product* p, int64_t n, int64_t q, const float* dev_g,
+                          const float* dev_r, float* dev_t, float* dev_z, void* dev_work, int64_t* dev_state);
+int bsp_fsai_apply_batched_f32(bsp_solver* s, const bsp_sym_product* p, int64_t n, int64_t q,
+                                  const float* const* dev_g, const float* const* dev_r, float* const* dev_t,
+                                  float* const* dev_z, void* dev_work, int64_t* dev_state, int32_t batch);
 int bsp_cg_init_f64(bsp_solver* s, int64_t n, int64_t q, const double* dev_b, double* dev_x, double* dev_r, double tol,
                     int64_t max_steps, int32_t plain, void* dev_work, int64_t* dev_state);
 int bsp_cg_init_batched_f64(bsp_solver* s, int64_t n, int64_t q, const double* const* dev_b, double* const* dev_x,
