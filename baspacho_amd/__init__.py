@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["Settings", "Solver", "FactorizationError", "Assembly", "NormalEquations", "SymProduct", "create_solver", "SparseStructure", "BackendHip", "BackendCuda",
+__all__ = ["Settings", "Solver", "FactorizationError", "Assembly", "NormalEquations", "JacobianProduct", "SymProduct", "create_solver", "SparseStructure", "BackendHip", "BackendCuda",
            "BackendRef", "BackendFast", "AddFillComplete", "AddFillForAutoElims",
            "AddFillForGivenElims", "AddFillNone"]
 
@@ -1300,6 +1300,13 @@ class Solver:
         host; triangle as for assembly().  See SymProduct."""
         return SymProduct(self, rows, cols, triangle)
 
+    # ---- products with a Jacobian given as entries (DESIGN.md section 28) ---------------------
+    def jacobianProduct(self, rows, cols, m):
+        """extension: the map of the products with the m x order() Jacobian of the entries (rows[k], cols[k])
+        in the caller's scalar order (bsp_jac_product_create), built once on the host; this solver's layout
+        is never touched.  No (row, col) may repeat.  See JacobianProduct."""
+        return JacobianProduct(self, rows, cols, m)
+
     def diagOffsets(self):
         """extension: int64 array [order()], the layout offsets of the diagonal elements in internal
         order (what damp() touches)"""
@@ -1576,7 +1583,7 @@ class NormalEquations(_EntryMap):
             if x.dtype != values.dtype or x.device != values.device:
                 raise TypeError("%s: the input is %s on %s, values are %s on %s"
                                 % (name, x.dtype, x.device, values.dtype, values.device))
-            vec = fn.startswith("bsp_normal_eq_j")
+            vec = fn.startswith(("bsp_normal_eq_j", "bsp_jac_product_j"))
             ok = x.dim() in ((len(lead) + 1, len(lead) + 2) if vec else (len(lead) + 1,))
             if not ok or tuple(x.shape[:len(lead)]) != lead or x.shape[len(lead)] != x_rows:
                 raise ValueError("%s: the input must be %s%s with leading size %d, got shape %s" % (
@@ -1610,6 +1617,69 @@ class NormalEquations(_EntryMap):
     def jVec(self, values, v, out=None):
         """v [n] or [n, q] (leading B when values are batched) -> J v, [m] / [m, q] (bsp_normal_eq_j_vec_*)"""
         return self._run("jVec", "bsp_normal_eq_j_vec_", values, v, self.n, self.m, out)
+
+
+class JacobianProduct(_EntryMap):
+    """extension: products with the m x n Jacobian J of the entries (rows[k], cols[k],
+    values[k]) (n = the solver's order(), caller's scalar order, no position repeated) taken from the entries
+    alone: the lists of the rows and of the columns, each with its long runs, and the plan of the diagonal
+    blocks of J^T J over the solver's params.  No layout, no pair list.  Built by Solver.jacobianProduct();
+    keeps its solver alive.  jVec / jtVec are bitwise NormalEquations' (a run of more than 64 terms is summed
+    by a whole wave in the same sequential order); the pieces of the matrix-free least squares built on them
+    are driven by baspacho_amd.cgls."""
+
+    _C = "jac_product"
+    _KEYS = ("nnz", "m", "n", "max_row", "long_rows", "max_col", "long_cols", "row_bytes", "col_bytes")
+
+    def __init__(self, solver, rows, cols, m):
+        self._create("jacobianProduct", solver, rows, cols, before=(ctypes.c_int64(int(m)),))
+        self.m = int(m)
+        self.n = solver.order()
+
+    _run = NormalEquations._run  # (values, a vector of one side, the output of the other: the same checks)
+
+    def runTable(self, which):
+        """(start, entry, index, long_runs) of the "rows" or the "cols" list: int32 arrays; the terms of run u
+        are (entry[t], index[t]), t in [start[u], start[u + 1]), in ascending entry index; long_runs lists the
+        runs of more than 64 terms"""
+        if which not in ("rows", "cols"):
+            raise ValueError("runTable: which must be 'rows' or 'cols', got %r" % (which,))
+        runs = self.m if which == "rows" else self.n
+        start = np.zeros(runs + 1, dtype=np.int32)
+        entry, index = np.zeros(max(self.nnz, 1), dtype=np.int32), np.zeros(max(self.nnz, 1), dtype=np.int32)
+        longs = np.zeros(max(runs, 1), dtype=np.int32)
+        _check(self._lib.bsp_jac_product_table(self._h, ctypes.c_int32(0 if which == "rows" else 1),
+                                               *(a.ctypes.data_as(_I32P) for a in (start, entry, index, longs)), None))
+        return start, entry[:self.nnz], index[:self.nnz], longs[:int((np.diff(start) > 64).sum())]
+
+    def precondInfo(self, kind):
+        """{blocks, items, inverse_elems, max_width, device_bytes} of the plan of "jacobi" or "block_jacobi" for
+        J^T J + D (the solver's params; one wider than 32 scalars is refused).  Host work only."""
+        kinds = {"jacobi": 1, "block_jacobi": 2}
+        if kind not in kinds:
+            raise ValueError("precondInfo: kind must be 'jacobi' or 'block_jacobi', got %r" % (kind,))
+        out = (ctypes.c_int64 * 5)()
+        _check(self._lib.bsp_cgls_precond_info(self._h, ctypes.c_int32(kinds[kind]), out))
+        return dict(zip(("blocks", "items", "inverse_elems", "max_width", "device_bytes"), [int(x) for x in out]))
+
+    def blockTable(self):
+        """(block_start, item_start, ka, kb, pos) of the plan of the diagonal blocks of J^T J: int32 arrays; the
+        items of block b are t in [item_start[b], item_start[b + 1]), in ascending Jacobian row"""
+        info = self.precondInfo("block_jacobi")
+        nb, items = info["blocks"], info["items"]
+        bs, st = np.zeros(nb + 1, dtype=np.int32), np.zeros(nb + 1, dtype=np.int32)
+        ka, kb, pos = (np.zeros(max(items, 1), dtype=np.int32) for _ in range(3))
+        _check(self._lib.bsp_jac_product_table(self._h, ctypes.c_int32(2),
+                                               *(a.ctypes.data_as(_I32P) for a in (bs, st, ka, kb, pos))))
+        return bs, st, ka[:items], kb[:items], pos[:items]
+
+    def jtVec(self, values, r, out=None):
+        """r [m] or [m, q] (leading B when values are batched) -> J^T r, [n] / [n, q] (bsp_jac_product_jtv_*)"""
+        return self._run("jtVec", "bsp_jac_product_jtv_", values, r, self.m, self.n, out)
+
+    def jVec(self, values, v, out=None):
+        """v [n] or [n, q] (leading B when values are batched) -> J v, [m] / [m, q] (bsp_jac_product_jv_*)"""
+        return self._run("jVec", "bsp_jac_product_jv_", values, v, self.n, self.m, out)
 
 
 class SymProduct(_EntryMap):

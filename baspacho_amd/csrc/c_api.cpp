@@ -11,6 +11,7 @@
 
 #include "assembly.h"
 #include "factor_product_plan.h"
+#include "jac_product.h"
 #include "normal_eq.h"
 #include "sym_product.h"
 #include "reach.h"
@@ -1151,6 +1152,285 @@ static void cgRun(bsp_solver* s, const bsp_sym_product* p, int32_t op, int32_t k
 BSP_CG_API(f64, double)
 BSP_CG_API(f32, float)
 #undef BSP_CG_API
+// ---- matrix-free least squares --------------------------------------------------
+struct bsp_jac_product {
+  std::unique_ptr<JacobianProductMap> map;
+};
+
+int bsp_jac_product_create(bsp_solver* s, int64_t m, int64_t nnz, const int64_t* rows, const int64_t* cols,
+                           bsp_jac_product** out) {
+  BSP_TRY
+  if (s == nullptr || out == nullptr) throw std::runtime_error("bsp_jac_product_create: NULL solver or output");
+  std::unique_ptr<bsp_jac_product> p(new bsp_jac_product);
+  p->map = createJacobianProductMap(*s->solver, m, nnz, rows, cols);
+  *out = p.release();
+  BSP_CATCH
+}
+void bsp_jac_product_destroy(bsp_jac_product* p) { delete p; }
+int bsp_jac_product_info(const bsp_jac_product* p, int64_t out[9]) {
+  BSP_TRY
+  if (p == nullptr || out == nullptr) throw std::runtime_error("bsp_jac_product_info: NULL argument");
+  const JacobianProductMap& m = *p->map;
+  const int64_t v[9] = {m.nnz, m.m, m.n, m.rows.maxRun, (int64_t)m.rows.longRuns.size(), m.cols.maxRun,
+                        (int64_t)m.cols.longRuns.size(), m.rowDeviceBytes(), m.colDeviceBytes()};
+  std::copy(v, v + 9, out);
+  BSP_CATCH
+}
+int bsp_jac_product_check_items(int64_t items) {
+  BSP_TRY
+  checkJacBlockItems(items);
+  BSP_CATCH
+}
+int bsp_cgls_precond_info(const bsp_jac_product* p, int32_t kind, int64_t out[5]) {
+  BSP_TRY
+  if (p == nullptr || out == nullptr) throw std::runtime_error("bsp_cgls_precond_info: NULL argument");
+  if (kind == CgJacobi) {
+    const int64_t n = p->map->n, v[5] = {n, 0, n, n > 0 ? 1 : 0, (n + 1) * (int64_t)sizeof(int32_t)};
+    std::copy(v, v + 5, out);
+    return 0;
+  }
+  if (kind != CgBlockJacobi) {
+    throw std::runtime_error("bsp_cgls_precond_info: unknown kind " + std::to_string(kind) + " (1: jacobi, 2: block_jacobi)");
+  }
+  const JacBlockPlan& pl = jacBlockPlan(*p->map);
+  const int64_t v[5] = {pl.numBlocks, pl.numItems(), pl.inverseElems(), pl.maxWidth, pl.deviceBytes()};
+  std::copy(v, v + 5, out);
+  BSP_CATCH
+}
+int bsp_jac_product_table(const bsp_jac_product* p, int32_t part, int32_t* t0, int32_t* t1, int32_t* t2, int32_t* t3,
+                          int32_t* t4) {
+  BSP_TRY
+  if (p == nullptr) throw std::runtime_error("bsp_jac_product_table: the map is NULL");
+  const auto put = [](const std::vector<int32_t>& v, int32_t* out) {
+    if (!v.empty() && out == nullptr) throw std::runtime_error("bsp_jac_product_table: an output array is NULL");
+    std::copy(v.begin(), v.end(), out);
+  };
+  if (part == 0 || part == 1) {
+    const RunList& r = part == 0 ? p->map->rows : p->map->cols;
+    put(r.start, t0);
+    put(r.entry, t1);
+    put(r.idx, t2);
+    put(r.longRuns, t3);
+  } else if (part == 2) {
+    const JacBlockPlan& pl = jacBlockPlan(*p->map);
+    put(pl.blockStart, t0);
+    put(pl.itemStart, t1);
+    put(pl.itemA, t2);
+    put(pl.itemB, t3);
+    put(pl.itemPos, t4);
+  } else {
+    throw std::runtime_error("bsp_jac_product_table: unknown part " + std::to_string(part) +
+                             " (0: rows, 1: columns, 2: blocks)");
+  }
+  BSP_CATCH
+}
+int bsp_cgls_work_bytes(const bsp_solver* s, const bsp_jac_product* p, int64_t q, int64_t* out) {
+  BSP_TRY
+  if (s == nullptr || p == nullptr || out == nullptr) throw std::runtime_error("bsp_cgls_work_bytes: NULL argument");
+  *out = s->solver->cglsWorkBytes(p->map->m, p->map->n, q);
+  BSP_CATCH
+}
+namespace {
+// the operands of one piece; the single entries pass the addresses of their pointer arguments
+template <typename T>
+struct CglsCall {
+  CglsArgs<T> a;
+  CglsCall(int32_t op, const bsp_jac_product* p, int64_t q = 1) {
+    a.op = op;
+    a.map = p ? p->map.get() : nullptr;
+    a.q = q;
+  }
+  void run(bsp_solver* s, int32_t batch, bool single) {
+    if (s == nullptr) throw std::runtime_error("cgls: the solver is NULL");
+    if (a.map == nullptr) throw std::runtime_error("cgls: the map is NULL");
+    s->solver->cgls<T>(a, batch, single);
+  }
+};
+// p or NULL as the one-member array of a single call
+template <typename P>
+P* const* one(P* const& p) {
+  return p ? &p : nullptr;
+}
+}  // namespace
+template <typename T>
+static void cglsProductRun(bsp_solver* s, const bsp_jac_product* p, int32_t op, int32_t epi, const T* const* v,
+                           const T* const* vec, const T* const* addend, const T* const* damp, const T* const* x,
+                           int64_t q, T* const* out, int64_t* state, int32_t batch, bool single) {
+  CglsCall<T> c(op, p, q);
+  c.a.epi = epi;
+  c.a.values = v;
+  c.a.vec = vec;
+  c.a.addend = addend;
+  c.a.damp = damp;
+  c.a.x = const_cast<T* const*>(x);  // (only read by the epilogue)
+  c.a.out = out;
+  c.a.state = state;
+  c.run(s, batch, single);
+}
+template <typename T>
+static void cglsPieceRun(bsp_solver* s, const bsp_jac_product* p, int32_t op, int32_t kind, bool start, int64_t q,
+                         const T* const* values, const T* const* vec, const T* const* addend, const T* const* damp,
+                         T* const* x, T* const* out, double* const* colsq, double tol, int64_t maxSteps, double alpha,
+                         double beta, void* work, int64_t* state, int64_t* status, int32_t batch, bool single) {
+  CglsCall<T> c(op, p, q);
+  c.a.kind = kind;
+  c.a.start = start;
+  c.a.values = values;
+  c.a.vec = vec;
+  c.a.addend = addend;
+  c.a.damp = damp;
+  c.a.x = x;
+  c.a.out = out;
+  c.a.colsq = colsq;
+  c.a.tol = tol;
+  c.a.maxSteps = maxSteps;
+  c.a.alpha = alpha;
+  c.a.beta = beta;
+  c.a.work = work;
+  c.a.state = state;
+  c.a.status = status;
+  c.run(s, batch, single);
+}
+template <typename T>
+static void cglsIterateRun(bsp_solver* s, const bsp_jac_product* p, int32_t kind, int32_t phase, int64_t q,
+                           const T* const* values, const T* const* d, const T* const* c, const T* const* minv,
+                           T* const* pv, T* const* t, T* const* x, T* const* res, T* const* sv, T* const* z, void* work,
+                           int64_t* state, int32_t batch, bool single) {
+  CglsCall<T> call(CglsIterate, p, q);
+  call.a.kind = kind;
+  call.a.phase = phase;
+  call.a.values = values;
+  call.a.damp = d;
+  call.a.addend = c;
+  call.a.minv = minv;
+  call.a.p = pv;
+  call.a.t = t;
+  call.a.x = x;
+  call.a.res = res;
+  call.a.s = sv;
+  call.a.z = z;
+  call.a.work = work;
+  call.a.state = state;
+  call.run(s, batch, single);
+}
+#define BSP_CC(T, x) const_cast<T* const*>(x)
+#define BSP_CD(x) const_cast<double* const*>(x)
+#define BSP_CGLS_API(SFX, T)                                                                                     \
+  int bsp_jac_product_jv_##SFX(bsp_solver* s, const bsp_jac_product* p, const T* v, const T* x, int64_t q, T* out) \
+      BSP_BODY(cglsProductRun<T>(s, p, CglsJv, 0, &v, &x, nullptr, nullptr, nullptr, q, &out, nullptr, 1, true)) \
+  int bsp_jac_product_jv_batched_##SFX(bsp_solver* s, const bsp_jac_product* p, const T* const* v,               \
+                                       const T* const* x, int64_t q, T* const* out, int32_t batch)               \
+      BSP_BODY(cglsProductRun<T>(s, p, CglsJv, 0, v, x, nullptr, nullptr, nullptr, q, out, nullptr, batch, false)) \
+  int bsp_jac_product_jtv_##SFX(bsp_solver* s, const bsp_jac_product* p, const T* v, const T* u, int64_t q,      \
+                                T* out)                                                                          \
+      BSP_BODY(cglsProductRun<T>(s, p, CglsJtv, 0, &v, &u, nullptr, nullptr, nullptr, q, &out, nullptr, 1, true)) \
+  int bsp_jac_product_jtv_batched_##SFX(bsp_solver* s, const bsp_jac_product* p, const T* const* v,              \
+                                        const T* const* u, int64_t q, T* const* out, int32_t batch)              \
+      BSP_BODY(cglsProductRun<T>(s, p, CglsJtv, 0, v, u, nullptr, nullptr, nullptr, q, out, nullptr, batch, false)) \
+  int bsp_cgls_residual_##SFX(bsp_solver* s, const bsp_jac_product* p, const T* v, const T* x, const T* r,       \
+                              int64_t q, T* res, int64_t* state)                                                 \
+      BSP_BODY(cglsProductRun<T>(s, p, CglsJv, 1, &v, &x, one(r), nullptr, nullptr, q, &res, state, 1, true))    \
+  int bsp_cgls_residual_batched_##SFX(bsp_solver* s, const bsp_jac_product* p, const T* const* v,                \
+                                      const T* const* x, const T* const* r, int64_t q, T* const* res,            \
+                                      int64_t* state, int32_t batch)                                             \
+      BSP_BODY(cglsProductRun<T>(s, p, CglsJv, 1, v, x, r, nullptr, nullptr, q, res, state, batch, false))       \
+  int bsp_cgls_normal_##SFX(bsp_solver* s, const bsp_jac_product* p, const T* v, const T* res, const T* d,       \
+                            const T* x, const T* c, int64_t q, T* out, int64_t* state)                           \
+      BSP_BODY(cglsProductRun<T>(s, p, CglsJtv, 2, &v, &res, one(c), one(d), one(x), q, &out, state, 1, true))   \
+  int bsp_cgls_normal_batched_##SFX(bsp_solver* s, const bsp_jac_product* p, const T* const* v,                  \
+                                    const T* const* res, const T* const* d, const T* const* x,                   \
+                                    const T* const* c, int64_t q, T* const* out, int64_t* state, int32_t batch)  \
+      BSP_BODY(cglsProductRun<T>(s, p, CglsJtv, 2, v, res, c, d, x, q, out, state, batch, false))                \
+  int bsp_cgls_colsq_##SFX(bsp_solver* s, const bsp_jac_product* p, const T* v, double* colsq)                   \
+      BSP_BODY(cglsPieceRun<T>(s, p, CglsColSq, 0, false, 1, &v, nullptr, nullptr, nullptr, nullptr, nullptr,    \
+                               &colsq, 0, 0, 0, 0, nullptr, nullptr, nullptr, 1, true))                          \
+  int bsp_cgls_colsq_batched_##SFX(bsp_solver* s, const bsp_jac_product* p, const T* const* v,                   \
+                                   double* const* colsq, int32_t batch)                                          \
+      BSP_BODY(cglsPieceRun<T>(s, p, CglsColSq, 0, false, 1, v, nullptr, nullptr, nullptr, nullptr, nullptr,     \
+                               colsq, 0, 0, 0, 0, nullptr, nullptr, nullptr, batch, false))                      \
+  int bsp_cgls_damp_##SFX(bsp_solver* s, const bsp_jac_product* p, const double* colsq, double alpha,            \
+                          double beta, T* d)                                                                     \
+      BSP_BODY({                                                                                                 \
+        double* cs = const_cast<double*>(colsq);                                                                 \
+        cglsPieceRun<T>(s, p, CglsDamp, 0, false, 1, nullptr, nullptr, nullptr, nullptr, nullptr, &d, &cs, 0, 0, \
+                        alpha, beta, nullptr, nullptr, nullptr, 1, true);                                        \
+      })                                                                                                         \
+  int bsp_cgls_damp_batched_##SFX(bsp_solver* s, const bsp_jac_product* p, const double* const* colsq,           \
+                                  double alpha, double beta, T* const* d, int32_t batch)                         \
+      BSP_BODY(cglsPieceRun<T>(s, p, CglsDamp, 0, false, 1, nullptr, nullptr, nullptr, nullptr, nullptr, d,      \
+                               BSP_CD(colsq), 0, 0, alpha, beta, nullptr, nullptr, nullptr, batch, false))       \
+  int bsp_cgls_init_##SFX(bsp_solver* s, const bsp_jac_product* p, int64_t q, const T* b, T* x, double tol,      \
+                          int64_t max_steps, void* work, int64_t* state)                                         \
+      BSP_BODY(cglsPieceRun<T>(s, p, CglsInit, 0, false, q, nullptr, &b, nullptr, nullptr, &x, nullptr, nullptr, \
+                               tol, max_steps, 0, 0, work, state, nullptr, 1, true))                             \
+  int bsp_cgls_init_batched_##SFX(bsp_solver* s, const bsp_jac_product* p, int64_t q, const T* const* b,         \
+                                  T* const* x, double tol, int64_t max_steps, void* work, int64_t* state,        \
+                                  int32_t batch)                                                                 \
+      BSP_BODY(cglsPieceRun<T>(s, p, CglsInit, 0, false, q, nullptr, b, nullptr, nullptr, x, nullptr, nullptr,   \
+                               tol, max_steps, 0, 0, work, state, nullptr, batch, false))                        \
+  int bsp_cgls_delta_##SFX(bsp_solver* s, const bsp_jac_product* p, int64_t q, const T* t, const T* pv,          \
+                           const T* d, void* work, int64_t* state)                                               \
+      BSP_BODY({                                                                                                 \
+        T* pw = const_cast<T*>(pv);                                                                              \
+        cglsPieceRun<T>(s, p, CglsDelta, 0, false, q, nullptr, &t, nullptr, one(d), &pw, nullptr, nullptr, 0, 0, \
+                        0, 0, work, state, nullptr, 1, true);                                                    \
+      })                                                                                                         \
+  int bsp_cgls_delta_batched_##SFX(bsp_solver* s, const bsp_jac_product* p, int64_t q, const T* const* t,        \
+                                   const T* const* pv, const T* const* d, void* work, int64_t* state,            \
+                                   int32_t batch)                                                                \
+      BSP_BODY(cglsPieceRun<T>(s, p, CglsDelta, 0, false, q, nullptr, t, nullptr, d, BSP_CC(T, pv), nullptr,     \
+                               nullptr, 0, 0, 0, 0, work, state, nullptr, batch, false))                         \
+  int bsp_cgls_update_##SFX(bsp_solver* s, const bsp_jac_product* p, int64_t q, const T* pv, const T* t, T* x,   \
+                            T* res, int64_t* state)                                                              \
+      BSP_BODY(cglsPieceRun<T>(s, p, CglsUpdate, 0, false, q, nullptr, &pv, &t, nullptr, &x, &res, nullptr, 0,   \
+                               0, 0, 0, nullptr, state, nullptr, 1, true))                                       \
+  int bsp_cgls_update_batched_##SFX(bsp_solver* s, const bsp_jac_product* p, int64_t q, const T* const* pv,      \
+                                    const T* const* t, T* const* x, T* const* res, int64_t* state,               \
+                                    int32_t batch)                                                               \
+      BSP_BODY(cglsPieceRun<T>(s, p, CglsUpdate, 0, false, q, nullptr, pv, t, nullptr, x, res, nullptr, 0, 0, 0, \
+                               0, nullptr, state, nullptr, batch, false))                                        \
+  int bsp_cgls_apply_##SFX(bsp_solver* s, const bsp_jac_product* p, int32_t kind, int64_t q, const T* minv,      \
+                           const T* sv, T* z, int32_t start, void* work, int64_t* state)                         \
+      BSP_BODY(cglsPieceRun<T>(s, p, CglsApply, kind, start != 0, q, nullptr, &sv, nullptr, one(minv), nullptr,  \
+                               &z, nullptr, 0, 0, 0, 0, work, state, nullptr, 1, true))                          \
+  int bsp_cgls_apply_batched_##SFX(bsp_solver* s, const bsp_jac_product* p, int32_t kind, int64_t q,             \
+                                   const T* const* minv, const T* const* sv, T* const* z, int32_t start,         \
+                                   void* work, int64_t* state, int32_t batch)                                    \
+      BSP_BODY(cglsPieceRun<T>(s, p, CglsApply, kind, start != 0, q, nullptr, sv, nullptr, minv, nullptr, z,     \
+                               nullptr, 0, 0, 0, 0, work, state, nullptr, batch, false))                         \
+  int bsp_cgls_precond_build_##SFX(bsp_solver* s, const bsp_jac_product* p, int32_t kind, const T* v,            \
+                                   const double* colsq, const T* d, T* minv, void* work, int64_t* status)        \
+      BSP_BODY({                                                                                                 \
+        double* cs = const_cast<double*>(colsq);                                                                 \
+        cglsPieceRun<T>(s, p, CglsBuild, kind, false, 1, one(v), nullptr, nullptr, one(d), nullptr, &minv,       \
+                        one(cs), 0, 0, 0, 0, work, nullptr, status, 1, true);                                    \
+      })                                                                                                         \
+  int bsp_cgls_precond_build_batched_##SFX(bsp_solver* s, const bsp_jac_product* p, int32_t kind,                \
+                                           const T* const* v, const double* const* colsq, const T* const* d,     \
+                                           T* const* minv, void* work, int64_t* status, int32_t batch)           \
+      BSP_BODY(cglsPieceRun<T>(s, p, CglsBuild, kind, false, 1, v, nullptr, nullptr, d, nullptr, minv,           \
+                               BSP_CD(colsq), 0, 0, 0, 0, work, nullptr, status, batch, false))
+#define BSP_CGLS_ITERATE_API(SFX, T)                                                                             \
+  int bsp_cgls_iterate_##SFX(bsp_solver* s, const bsp_jac_product* p, int32_t kind, int32_t phase, int64_t q,    \
+                             const T* v, const T* d, const T* c, const T* minv, T* pv, T* t, T* x, T* res, T* sv, \
+                             T* z, void* work, int64_t* state)                                                   \
+      BSP_BODY(cglsIterateRun<T>(s, p, kind, phase, q, one(v), one(d), one(c), one(minv), one(pv), one(t),       \
+                                 one(x), one(res), one(sv), one(z), work, state, 1, true))                       \
+  int bsp_cgls_iterate_batched_##SFX(bsp_solver* s, const bsp_jac_product* p, int32_t kind, int32_t phase,       \
+                                     int64_t q, const T* const* v, const T* const* d, const T* const* c,         \
+                                     const T* const* minv, T* const* pv, T* const* t, T* const* x,               \
+                                     T* const* res, T* const* sv, T* const* z, void* work, int64_t* state,       \
+                                     int32_t batch)                                                              \
+      BSP_BODY(cglsIterateRun<T>(s, p, kind, phase, q, v, d, c, minv, pv, t, x, res, sv, z, work, state, batch,  \
+                                 false))
+BSP_CGLS_ITERATE_API(f64, double)
+BSP_CGLS_ITERATE_API(f32, float)
+#undef BSP_CGLS_ITERATE_API
+BSP_CGLS_API(f64, double)
+BSP_CGLS_API(f32, float)
+#undef BSP_CGLS_API
+#undef BSP_CC
+#undef BSP_CD
 // ---- the Lanczos recurrence -----------------------------------------------------
 int bsp_lanczos_state_words(int64_t* out) {
   BSP_TRY

@@ -186,5 +186,44 @@ static inline void checkEntryArrays(const char* op, int64_t nnz, const int64_t* 
     throw std::runtime_error(std::string(op) + ": the row or column array is NULL");
   }
 }
+// the entries of an m x n Jacobian: every index in range
+static inline void checkJacobianRange(const char* op, int64_t m, int64_t n, int64_t nnz, const int64_t* rows,
+                                      const int64_t* cols) {
+  for (int64_t k = 0; k < nnz; k++) {
+    const int64_t i = rows[k], j = cols[k];
+    if (i < 0 || i >= m || j < 0 || j >= n) {
+      throw std::runtime_error(std::string(op) + ": " + entryName(k, i, j) + " is out of range [0, " +
+                               std::to_string(m) + ") x [0, " + std::to_string(n) + ")");
+    }
+  }
+}
+// ... and no (row, col) repeated.  byCol: the entries by (col, k), the `entry` of the column lists; stably by
+// row they hold the repeats of one position side by side; the first repeated entry is the smallest
+// second-of-a-pair
+static inline void checkJacobianRepeats(const char* op, int64_t m, int64_t nnz, const int64_t* rows,
+                                        const int64_t* cols, const std::vector<int32_t>& byCol) {
+  std::vector<int32_t> byRowCol;
+  countingSort(byCol, byRowCol, m, [rows](int32_t k) { return rows[k]; });
+  int64_t first = -1, earlier = -1;
+  for (int64_t x = 1; x < nnz; x++) {
+    const int32_t a = byRowCol[x - 1], b = byRowCol[x];
+    if (rows[a] == rows[b] && cols[a] == cols[b] && (first < 0 || b < first)) {
+      first = b;
+      earlier = a;
+    }
+  }
+  if (first < 0) return;
+  // `earlier` is the repeat's predecessor in its group; name the group's first entry
+  int64_t k0 = earlier;
+  for (int64_t k = 0; k < earlier; k++) {
+    if (rows[k] == rows[first] && cols[k] == cols[first]) {
+      k0 = k;
+      break;
+    }
+  }
+  throw std::runtime_error(std::string(op) + ": " + entryName(first, rows[first], cols[first]) +
+                           " repeats the position of entry " + std::to_string(k0) +
+                           "; duplicate Jacobian entries are not summed");
+}
 
 }  // namespace BaSpaCho

@@ -276,6 +276,80 @@ inline int64_t cgWorkBytes(int64_t n, int64_t q) { return cgBadOffset(n, q) + ((
 template <typename T>
 void hipBackendCg(SymbolicCtx& sym, const CgArgs<T>& a, int64_t batch, bool single);
 
+// Matrix-free least squares (hip_cgls_kernels.h): one piece of CGLS for (J^T J + D) x =
+// J^T r + c on `batch` Jacobians of one map with q columns each.  n-space vectors are [n, q], m-space ones
+// [m, q], row-major; d (the damping vector) and colsq hold n values; state holds CgState's 12 words per
+// (matrix, column); the work areas sit cglsWorkBytes(m, n, q) apart from `work` on: the partials, then,
+// cglsBadOffset bytes in, the bad-pivot words of a build.  An operand that may be absent is NULL.
+//   CglsJv:       out = epilogue(J vec), epi CglsPlain or CglsResidual (addend = r, may be absent); state
+//                 NULL: every column, else the stopped columns are skipped
+//   CglsJtv:      out = epilogue(J^T vec), epi CglsPlain or CglsNormal (damp = d and x, both or neither;
+//                 addend = c, may be absent); state as for CglsJv
+//   CglsColSq:    colsq (doubles) from the values
+//   CglsDamp:     colsq (read); out = d = T(alpha colsq + beta)
+//   CglsInit:     vec = b (in n-space); x: the records reset, bb, x = 0 in the columns of a zero b
+//   CglsDelta:    vec = t (m-space), x = p, damp = d (may be absent): delta, alpha
+//   CglsUpdate:   vec = p, addend = t; x, out = res: x += alpha p, res -= alpha t
+//   CglsApply:    kind 0 / 1 / 2 (CgPrecondKind): damp = the preconditioner's values (kinds 1, 2), vec = s; out =
+//                 z (kind 0: only read): z = M^-1 s, ss, the iteration counted unless `start`, the stop test,
+//                 gamma = s.z, beta
+//   CglsBuild:    kind 1 / 2: values, colsq (kind 1), damp = d (may be absent); out = the preconditioner's
+//                 values; status: 2 words per matrix
+//   CglsIterate:  one whole iteration in one call: CglsJv (t = J p), the partials of CglsDelta, its fold and
+//                 CglsUpdate in one launch (cglsAlphaUpdate), CglsJtv (normal epilogue), CglsApply and
+//                 cgDirection queued one behind the other on p, t, x, res, s, z with values, damp = d, addend = c
+//                 and minv (the preconditioner's values): the same sums in the same order, so the same bits.  phase 0: all of it; 1: up to and including s
+//                 (the caller then writes its own z = M^-1 s); 2: apply and direction alone.  kind 0 with z ==
+//                 s is the iteration without a preconditioner
+struct JacobianProductMap;
+enum CglsOp : int32_t {
+  CglsJv = 0,
+  CglsJtv = 1,
+  CglsColSq = 2,
+  CglsDamp = 3,
+  CglsInit = 4,
+  CglsDelta = 5,
+  CglsUpdate = 6,
+  CglsApply = 7,
+  CglsBuild = 8,
+  CglsIterate = 9
+};
+template <typename T>
+struct CglsArgs {
+  int32_t op = CglsJv, kind = 0, epi = 0, phase = 0;
+  bool start = false;
+  int64_t q = 1, maxSteps = 0;
+  double tol = 0.0, alpha = 0.0, beta = 0.0;
+  const JacobianProductMap* map = nullptr;
+  const T* const* values = nullptr;
+  const T* const* vec = nullptr;
+  const T* const* addend = nullptr;
+  const T* const* damp = nullptr;
+  T* const* x = nullptr;
+  T* const* out = nullptr;
+  double* const* colsq = nullptr;
+  // CglsIterate alone
+  T* const* p = nullptr;
+  T* const* t = nullptr;
+  T* const* res = nullptr;
+  T* const* s = nullptr;
+  T* const* z = nullptr;
+  const T* const* minv = nullptr;
+  void* work = nullptr;
+  int64_t* state = nullptr;
+  int64_t* status = nullptr;
+};
+inline int64_t cglsBadOffset(int64_t m, int64_t n, int64_t q) {
+  const int64_t mp = (m + 1023) / 1024, np = (n + 1023) / 1024;
+  const int64_t parts = mp + np > 2 * np ? mp + np : 2 * np;
+  return q * (parts > 0 ? parts : 1) * 16;
+}
+inline int64_t cglsWorkBytes(int64_t m, int64_t n, int64_t q) {
+  return cglsBadOffset(m, n, q) + ((4 * (n > 0 ? n : 1) + 15) & ~int64_t(15));
+}
+template <typename T>
+void hipBackendCgls(SymbolicCtx& sym, const CglsArgs<T>& a, int64_t batch, bool single);
+
 // The Lanczos recurrence (hip_lanczos_kernels.h): one piece of a step on `batch`
 // matrices with q start vectors each.  Vectors are [n, q] row-major; slot s of a member's basis is the
 // vector at basis + s slotStride; state holds 12 words and coef 2 kmax doubles per (matrix, start vector);

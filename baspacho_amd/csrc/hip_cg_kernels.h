@@ -301,6 +301,54 @@ __global__ void __launch_bounds__(kRedThreads)
   work.bad()[i] = ok ? -1 : 0;
 }
 
+// The rest of a block-Jacobi build, shared with hip_cgls_kernels.h, by one wave on the block A (w x w, lower
+// triangle, row-major, in LDS) with Li zeroed: Cholesky, L^-1, the inverse stored as T; the zero matrix and
+// the pivot's step in *badWord for a bad pivot, -1 there else
+template <typename T>
+__device__ __forceinline__ void cgBlockInvert(double* A, double* Li, int w, int lane, GP<T> out, int32_t* badWord) {
+  int bad = -1;
+  for (int k = 0; k < w; k++) {
+    const double d = A[k * w + k];  // (the same value in every lane: the loop stays uniform)
+    if (!(d > 0.0) || !redFinite(d)) {
+      bad = k;
+      break;
+    }
+    const double s = __builtin_sqrt(d);
+    __syncthreads();
+    if (lane == 0) A[k * w + k] = s;
+    for (int i = k + 1 + lane; i < w; i += kCgBuildThreads) A[i * w + k] = A[i * w + k] / s;
+    __syncthreads();
+    // the trailing lower triangle: element (i, c), k < c <= i
+    for (int e = lane; e < w * w; e += kCgBuildThreads) {
+      const int i = e / w, c = e - i * w;
+      if (c > k && c <= i) A[e] = radd(A[e], -rmul(A[i * w + k], A[c * w + k]));
+    }
+    __syncthreads();
+  }
+  if (bad >= 0) {
+    for (int e = lane; e < w * w; e += kCgBuildThreads) out[e] = T(0);
+    if (lane == 0) *badWord = bad;
+    return;
+  }
+  // column c of L^-1 by lane c
+  for (int c = lane; c < w; c += kCgBuildThreads) {
+    Li[c * w + c] = 1.0 / A[c * w + c];
+    for (int i = c + 1; i < w; i++) {
+      double s = 0.0;
+      for (int k = c; k < i; k++) s = radd(s, rmul(A[i * w + k], Li[k * w + c]));
+      Li[i * w + c] = -s / A[i * w + i];
+    }
+  }
+  __syncthreads();
+  for (int e = lane; e < w * w; e += kCgBuildThreads) {
+    const int i = e / w, c = e - i * w;
+    double s = 0.0;
+    for (int k = i > c ? i : c; k < w; k++) s = radd(s, rmul(Li[k * w + i], Li[k * w + c]));
+    out[e] = (T)s;
+  }
+  if (lane == 0) *badWord = -1;
+}
+
 // Block-Jacobi, one wave per block of width w <= kCgMaxBlock, all in double in LDS: the block's entries
 // added in ascending entry index (duplicates and both triangles of the storage: an entry (i, j), i >= j,
 // lands at (i, j)); Cholesky, column by column; L^-1 by forward substitution, column by column; the
@@ -327,47 +375,7 @@ __global__ void __launch_bounds__(kCgBuildThreads)
     if ((pos & (kCgBuildThreads - 1)) == lane) A[pos] = radd(A[pos], (double)v[pl.itemEntry[t]]);
   }
   __syncthreads();
-  int bad = -1;
-  for (int k = 0; k < w; k++) {
-    const double d = A[k * w + k];  // (the same value in every lane: the loop stays uniform)
-    if (!(d > 0.0) || !redFinite(d)) {
-      bad = k;
-      break;
-    }
-    const double s = __builtin_sqrt(d);
-    __syncthreads();
-    if (lane == 0) A[k * w + k] = s;
-    for (int i = k + 1 + lane; i < w; i += kCgBuildThreads) A[i * w + k] = A[i * w + k] / s;
-    __syncthreads();
-    // the trailing lower triangle: element (i, c), k < c <= i
-    for (int e = lane; e < w * w; e += kCgBuildThreads) {
-      const int i = e / w, c = e - i * w;
-      if (c > k && c <= i) A[e] = radd(A[e], -rmul(A[i * w + k], A[c * w + k]));
-    }
-    __syncthreads();
-  }
-  if (bad >= 0) {
-    for (int e = lane; e < w * w; e += kCgBuildThreads) out[e] = T(0);
-    if (lane == 0) work.bad()[b] = bad;
-    return;
-  }
-  // column c of L^-1 by lane c
-  for (int c = lane; c < w; c += kCgBuildThreads) {
-    Li[c * w + c] = 1.0 / A[c * w + c];
-    for (int i = c + 1; i < w; i++) {
-      double s = 0.0;
-      for (int k = c; k < i; k++) s = radd(s, rmul(A[i * w + k], Li[k * w + c]));
-      Li[i * w + c] = -s / A[i * w + i];
-    }
-  }
-  __syncthreads();
-  for (int e = lane; e < w * w; e += kCgBuildThreads) {
-    const int i = e / w, c = e - i * w;
-    double s = 0.0;
-    for (int k = i > c ? i : c; k < w; k++) s = radd(s, rmul(Li[k * w + i], Li[k * w + c]));
-    out[e] = (T)s;
-  }
-  if (lane == 0) work.bad()[b] = -1;
+  cgBlockInvert<T>(A, Li, w, lane, out, work.bad() + b);
 }
 
 // the status record of a build, one workgroup per matrix: v counts the bad blocks, k is the lowest bad scalar

@@ -1,11 +1,12 @@
 // MI355X backend, the extension operations of hip_backend.h: selected inversion and its adjoint,
 // log-det and gradients on the pattern of L, factor status and damping, the reverse-mode sweep of the
 // factor, the dense Schur complement, assembly of coordinate entries, normal equations, products
-// with a matrix given as entries and products with the factor.  Every
+// with a matrix given as entries, matrix-free least squares and products with the factor.  Every
 // entry point stages its pointer arguments, splits the batch into chunks and enqueues the launches
 // of a chunk on the execution stream (the call path: HipSymbolicCtx::stage / forChunks).
 #include "hip_context.h"
 #include "hip_cg_kernels.h"
+#include "hip_cgls_kernels.h"
 #include "hip_chol_adjoint_kernels.h"
 #include "hip_factor_product.h"
 #include "hip_grad_kernels.h"
@@ -16,6 +17,7 @@
 #include "hip_selinv_adjoint_kernels.h"
 #include "hip_selinv_kernels.h"
 #include "hip_status_kernels.h"
+#include "jac_product.h"
 #include "normal_eq.h"
 #include "sym_product.h"
 
@@ -1103,6 +1105,190 @@ void hipBackendCg(SymbolicCtx& sym, const CgArgs<T>& a, int64_t batch, bool sing
   });
 }
 
+// ---- matrix-free least squares (hip_cgls_kernels.h) ------------------------------
+// one piece of CGLS (CglsOp) on `batch` Jacobians: one to three launches per chunk, nothing allocated but
+// the tables of the map, each uploaded by the first call that needs it
+template <typename T>
+void hipBackendCgls(SymbolicCtx& sym, const CglsArgs<T>& a, int64_t batch, bool single) {
+  using In = hipk::DataRef<const T>;
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  const JacobianProductMap& map = *a.map;
+  const int64_t m = map.m, n = map.n, q = a.q;
+  const int64_t nParts = (n + hipk::kRedChunk - 1) / hipk::kRedChunk, mParts = (m + hipk::kRedChunk - 1) / hipk::kRedChunk;
+  BASPACHO_CHECK_LT(q, (int64_t)INT32_MAX);
+  BASPACHO_CHECK_LT((nParts + mParts) * q, (int64_t)INT32_MAX);
+  const int64_t stride = cglsWorkBytes(m, n, q), badOff = cglsBadOffset(m, n, q);
+  HipEntryMapDev& d = HipEntryMapDev::of(map.dev);
+  const auto runsOf = [&](const RunList& r, int64_t vectors) {
+    const RunLaunch<int32_t> l = runLaunch(d, r, vectors, true);
+    return hipk::CglsRuns{l.numRuns, l.longWaves, (int32_t)l.shortWgs, l.start, l.longRuns, l.entry, l.idx};
+  };
+  const auto gridOf = [](const hipk::CglsRuns& r, unsigned nm) {
+    const int64_t longWgs = (r.numLongWaves + hipk::kAsmWavesPerWg - 1) / hipk::kAsmWavesPerWg;
+    return dim3((unsigned)(r.shortWgs + longWgs), nm);
+  };
+  hipk::CglsRuns runs{};
+  if (a.op == CglsJv || a.op == CglsJtv) runs = runsOf(a.op == CglsJv ? map.rows : map.cols, q);
+  if (a.op == CglsColSq) runs = runsOf(map.cols, 1);
+  hipk::CglsRuns rowRuns{}, colRuns{};
+  if (a.op == CglsIterate) {
+    rowRuns = runsOf(map.rows, q);
+    colRuns = runsOf(map.cols, q);
+  }
+  hipk::CgPrecondDev pl{};
+  hipk::CglsBlockItems items{};
+  int64_t numBlocks = a.op == CglsBuild ? n : 0;
+  if ((a.op == CglsApply || a.op == CglsBuild || a.op == CglsIterate) && a.kind == CgBlockJacobi) {
+    const JacBlockPlan& plan = jacBlockPlan(map);
+    pl = {d.get(plan.blockStart), d.get(plan.blockOff), d.get(plan.scalarBlock), nullptr, nullptr, nullptr};
+    if (a.op == CglsBuild) items = {d.get(plan.itemStart), d.get(plan.itemA), d.get(plan.itemB), d.get(plan.itemPos)};
+    numBlocks = plan.numBlocks;
+  } else if (a.op == CglsBuild) {
+    pl.blockStart = d.get(map.scalarStart);
+  }
+  const BatchPtrs<const T> vs = h.stage(a.values, batch, single), ws = h.stage(a.vec, batch, single);
+  const BatchPtrs<const T> as = h.stage(a.addend, batch, single), ds = h.stage(a.damp, batch, single);
+  const BatchPtrs<T> xs = h.stage(a.x, batch, single), os = h.stage(a.out, batch, single);
+  const BatchPtrs<double> cs = h.stage(a.colsq, batch, single);
+  const BatchPtrs<T> ps = h.stage(a.p, batch, single), ts = h.stage(a.t, batch, single);
+  const BatchPtrs<T> rs = h.stage(a.res, batch, single), ss = h.stage(a.s, batch, single);
+  const BatchPtrs<T> zs = h.stage(a.z, batch, single);
+  const BatchPtrs<const T> ms = h.stage(a.minv, batch, single);
+  const int threads = hipk::kRedThreads;
+  const double tol2 = a.tol * a.tol;
+  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+    const hipk::CgWork w{static_cast<char*>(a.work) + q0 * stride, stride, badOff};
+    hipk::CgState* st = a.state ? reinterpret_cast<hipk::CgState*>(a.state) + q0 * q : nullptr;
+    const In xIn{xs.at(q0).single, (const T* const*)xs.at(q0).many};
+    const hipk::DataRef<const double> cIn{cs.at(q0).single, (const double* const*)cs.at(q0).many};
+    const dim3 perColumn((unsigned)q, nm), nChunks((unsigned)(nParts * q), nm), mChunks((unsigned)(mParts * q), nm);
+    const dim3 perScalar((unsigned)((n + threads - 1) / threads), nm);
+    const auto asIn = [](const hipk::DataRef<T>& r) { return In{r.single, (const T* const*)r.many}; };
+    // delta = |t|^2 + p^T D p: the partials of t.t, then (d given) those of (p p) d, one fold
+    const auto delta = [&](In t, In p, In d, bool damped, bool fold) {
+      const int64_t total = mParts + (damped ? nParts : 0);
+      const int64_t chunks = mParts + (damped ? nParts : 0);
+      if (chunks > 0) {
+        hipk::cglsDeltaPartial<T><<<dim3((unsigned)(chunks * q), nm), threads, 0, stream>>>(
+            m, n, (int32_t)q, (int32_t)mParts, (int32_t)total, t, p, d, w, st);
+      }
+      if (fold) {
+        hipk::cgFold<<<perColumn, threads, 0, stream>>>((int32_t)q, (int32_t)total, hipk::CgFoldAlpha, false, 0.0, 0, w,
+                                                       st);
+      }
+      return total;
+    };
+    const auto update = [&](In p, In t, hipk::DataRef<T> x, hipk::DataRef<T> res) {
+      if (nParts + mParts > 0) {
+        hipk::cglsUpdate<T><<<dim3((unsigned)((nParts + mParts) * q), nm), threads, 0, stream>>>(
+            n, m, (int32_t)q, (int32_t)nParts, p, t, x, res, st);
+      }
+    };
+    const auto apply = [&](In minv, In sv, hipk::DataRef<T> z, bool start) {
+      if (nParts > 0) {
+        if (a.kind == CgJacobi) {
+          hipk::cglsApply<T, 1><<<nChunks, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, pl, minv, sv, z, w, st);
+        } else if (a.kind == CgBlockJacobi) {
+          hipk::cglsApply<T, 2><<<nChunks, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, pl, minv, sv, z, w, st);
+        } else {
+          hipk::cglsApply<T, 0><<<nChunks, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, pl, minv, sv, z, w, st);
+        }
+      }
+      hipk::cglsFold<<<perColumn, threads, 0, stream>>>((int32_t)q, (int32_t)nParts, start, w, st);
+    };
+    switch (a.op) {
+      case CglsJv:
+      case CglsJtv: {
+        if (runs.numRuns * q == 0) break;
+        const dim3 grid = gridOf(runs, nm);
+        const auto launch = [&](auto epi) {
+          hipk::cglsProduct<T, decltype(epi)::value><<<grid, hipk::kAsmThreads, 0, stream>>>(
+              runs, (int32_t)q, vs.at(q0), ws.at(q0), as.at(q0), ds.at(q0), xIn, os.at(q0), st);
+        };
+        if (a.epi == hipk::CglsResidual) {
+          launch(std::integral_constant<int, hipk::CglsResidual>());
+        } else if (a.epi == hipk::CglsNormal) {
+          launch(std::integral_constant<int, hipk::CglsNormal>());
+        } else {
+          launch(std::integral_constant<int, hipk::CglsPlain>());
+        }
+        break;
+      }
+      case CglsColSq:
+        if (n > 0) hipk::cglsColSq<T><<<gridOf(runs, nm), hipk::kAsmThreads, 0, stream>>>(runs, vs.at(q0), cs.at(q0));
+        break;
+      case CglsDamp:
+        if (n > 0) hipk::cglsDamp<T><<<perScalar, threads, 0, stream>>>(n, a.alpha, a.beta, cIn, os.at(q0));
+        break;
+      case CglsInit:
+        if (nParts > 0) {
+          hipk::cgDotPartial<T><<<nChunks, threads, 0, stream>>>(n, (int32_t)q, (int32_t)nParts, ws.at(q0), ws.at(q0), w,
+                                                                 st, true);
+        }
+        hipk::cgFold<<<perColumn, threads, 0, stream>>>((int32_t)q, (int32_t)nParts, hipk::CgFoldBB, false, tol2,
+                                                       a.maxSteps, w, st);
+        if (n > 0) {
+          hipk::cgStart<T><<<dim3((unsigned)((n * q + threads - 1) / threads), nm), threads, 0, stream>>>(
+              n, (int32_t)q, xs.at(q0), xs.at(q0), st);
+        }
+        break;
+      case CglsDelta:
+        delta(ws.at(q0), xIn, ds.at(q0), a.damp != nullptr, true);
+        break;
+      case CglsUpdate:
+        update(ws.at(q0), as.at(q0), xs.at(q0), os.at(q0));
+        break;
+      case CglsApply:
+        apply(ds.at(q0), ws.at(q0), os.at(q0), a.start);
+        break;
+      case CglsIterate: {
+        const In pIn = asIn(ps.at(q0)), tIn = asIn(ts.at(q0)), sIn = asIn(ss.at(q0));
+        if (a.phase != 2) {
+          if (rowRuns.numRuns * q > 0) {
+            hipk::cglsProduct<T, hipk::CglsPlain><<<gridOf(rowRuns, nm), hipk::kAsmThreads, 0, stream>>>(
+                rowRuns, (int32_t)q, vs.at(q0), pIn, In{}, In{}, In{}, ts.at(q0), nullptr);
+          }
+          // the fold of delta rides in the update's launch: the same sum, the same decision
+          const int64_t total = delta(tIn, pIn, ds.at(q0), a.damp != nullptr, false);
+          if (nParts + mParts > 0) {
+            hipk::cglsAlphaUpdate<T><<<dim3((unsigned)((nParts + mParts) * q), nm), threads, 0, stream>>>(
+                n, m, (int32_t)q, (int32_t)nParts, (int32_t)total, pIn, tIn, xs.at(q0), rs.at(q0), w, st);
+          }
+          if (colRuns.numRuns * q > 0) {
+            hipk::cglsProduct<T, hipk::CglsNormal><<<gridOf(colRuns, nm), hipk::kAsmThreads, 0, stream>>>(
+                colRuns, (int32_t)q, vs.at(q0), asIn(rs.at(q0)), as.at(q0), ds.at(q0),
+                a.damp != nullptr ? xIn : In{}, ss.at(q0), st);
+          }
+        }
+        if (a.phase != 1) {
+          apply(ms.at(q0), sIn, zs.at(q0), false);
+          const int64_t wgs = (n * q + threads - 1) / threads;
+          if (wgs > 0) {
+            hipk::cgDirection<T><<<dim3((unsigned)wgs, nm), threads, 0, stream>>>(n, (int32_t)q, asIn(zs.at(q0)),
+                                                                                  ps.at(q0), st);
+          }
+        }
+        break;
+      }
+      case CglsBuild:
+        if (numBlocks > 0) {
+          if (a.kind == CgJacobi) {
+            hipk::cglsJacobiBuild<T><<<perScalar, threads, 0, stream>>>(n, cIn, ds.at(q0), os.at(q0), w);
+          } else {
+            hipk::cglsBlockBuild<T><<<dim3((unsigned)numBlocks, nm), hipk::kCgBuildThreads, 0, stream>>>(
+                pl, items, vs.at(q0), ds.at(q0), os.at(q0), w);
+          }
+        }
+        hipk::cgPrecondStatus<<<dim3(1, nm), threads, 0, stream>>>(numBlocks, pl, w, a.status + 2 * q0);
+        break;
+      default:
+        throw std::runtime_error("cgls: unknown operation " + std::to_string(a.op));
+    }
+  });
+}
+
 // ---- the Lanczos recurrence (hip_lanczos_kernels.h) ------------------------------
 // one piece of a step (LanczosOp) on `batch` matrices: one to three launches per chunk, nothing allocated
 template <typename T>
@@ -1379,6 +1565,7 @@ void hipBackendFactorProduct(SymbolicCtx& sym, const T* const* L, bool transpose
   template void hipBackendNormEstStep<T>(SymbolicCtx&, int32_t, void*, const T* const*, int64_t*, double*,      \
                                          int64_t, bool);                                                        \
   template void hipBackendCg<T>(SymbolicCtx&, const CgArgs<T>&, int64_t, bool);                                 \
+  template void hipBackendCgls<T>(SymbolicCtx&, const CglsArgs<T>&, int64_t, bool);                             \
   template void hipBackendLanczos<T>(SymbolicCtx&, const LanczosArgs<T>&, int64_t, bool);                       \
   template void hipBackendKrylovCombine<T>(SymbolicCtx&, const KrylovCombineArgs<T>&, int64_t, bool);           \
   template void hipBackendReachSolveL<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                         \

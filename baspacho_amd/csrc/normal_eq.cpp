@@ -24,13 +24,7 @@ std::unique_ptr<NormalEqMap> createNormalEqMap(const Solver& solver, int64_t m, 
   q->dataSize = solver.dataSize();
   q->numTiles = (q->dataSize + kAssemblyTile - 1) / kAssemblyTile;
 
-  for (int64_t k = 0; k < nnz; k++) {
-    const int64_t i = rows[k], j = cols[k];
-    if (i < 0 || i >= m || j < 0 || j >= n) {
-      throw std::runtime_error("normal equations: " + entryName(k, i, j) + " is out of range [0, " +
-                               std::to_string(m) + ") x [0, " + std::to_string(n) + ")");
-    }
-  }
+  checkJacobianRange("normal equations", m, n, nnz, rows, cols);
 
   // vector lists: entries by column and by row, ascending k inside each
   const auto rowOf = [rows](int32_t k) { return rows[k]; };
@@ -39,33 +33,7 @@ std::unique_ptr<NormalEqMap> createNormalEqMap(const Solver& solver, int64_t m, 
   q->cols.build(nnz, n, colOf, self, rowOf, false);
   q->rows.build(nnz, m, rowOf, self, colOf, false);
 
-  // repeated (row, col): the entries by (row, col, k) -- the column lists, stably by row -- hold the
-  // repeats of one position side by side; the first repeated entry is the smallest second-of-a-pair
-  {
-    std::vector<int32_t> byRowCol;
-    countingSort(q->cols.entry, byRowCol, m, rowOf);
-    int64_t first = -1, earlier = -1;
-    for (int64_t x = 1; x < nnz; x++) {
-      const int32_t a = byRowCol[x - 1], b = byRowCol[x];
-      if (rows[a] == rows[b] && cols[a] == cols[b] && (first < 0 || b < first)) {
-        first = b;
-        earlier = a;
-      }
-    }
-    if (first >= 0) {
-      // `earlier` is the repeat's predecessor in its group; name the group's first entry
-      int64_t k0 = earlier;
-      for (int64_t k = 0; k < earlier; k++) {
-        if (rows[k] == rows[first] && cols[k] == cols[first]) {
-          k0 = k;
-          break;
-        }
-      }
-      throw std::runtime_error("normal equations: " + entryName(first, rows[first], cols[first]) +
-                               " repeats the position of entry " + std::to_string(k0) +
-                               "; duplicate Jacobian entries are not summed");
-    }
-  }
+  checkJacobianRepeats("normal equations", m, nnz, rows, cols, q->cols.entry);
 
   // P before anything of its size exists (sum d = nnz < 2^31, so the sum of d (d + 1) / 2 fits int64)
   int64_t P = 0;

@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "assembly.h"
+#include "jac_product.h"
 #include "normal_eq.h"
 #include "reach.h"
 #include "sym_product.h"
@@ -1316,6 +1317,122 @@ void Solver::cg(const CgArgs<T>& a, int64_t batch, bool single) const {
   hipBackendCg<T>(*symCtx, a, batch, single);
 }
 
+// ---- matrix-free least squares ------------------------------------------------
+int64_t Solver::cglsWorkBytes(int64_t m, int64_t n, int64_t q) const {
+  const int64_t lim = int64_t(1) << 31;
+  if (m < 0 || m >= lim || n < 0 || n >= lim || q < 1 || q >= INT32_MAX) {
+    throw std::runtime_error("cglsWorkBytes: m = " + std::to_string(m) + ", n = " + std::to_string(n) + ", q = " +
+                             std::to_string(q) + " is outside [0, 2^31) x [0, 2^31) x [1, 2^31 - 1)");
+  }
+  return BaSpaCho::cglsWorkBytes(m, n, q);
+}
+
+template <typename T>
+void Solver::cgls(const CglsArgs<T>& a, int64_t batch, bool single) const {
+  static const char* names[10] = {"cglsJv",    "cglsJtv",    "cglsColSq", "cglsDamp",  "cglsInit",
+                                  "cglsDelta", "cglsUpdate", "cglsApply", "cglsBuild", "cglsIterate"};
+  if (a.op < 0 || a.op > CglsIterate) throw std::runtime_error("cgls: unknown operation " + std::to_string(a.op));
+  const std::string what = names[a.op];
+  const auto fail = [&](const std::string& m) { throw std::runtime_error(what + ": " + m); };
+  if (a.map == nullptr) fail("the map is NULL");
+  if (a.map->solver != this) fail("the map was built on another solver");
+  if (batch < 1) fail("the batch is empty");
+  const std::string fault = badVectorCount(a.q);
+  if (!fault.empty()) fail(fault);
+  const int64_t m = a.map->m, n = a.map->n, q = a.q;
+  if ((m + n) * q >= (int64_t(1) << 40) || ((m + 1023) / 1024 + (n + 1023) / 1024) * q >= INT32_MAX) {
+    fail("(m + n) q = " + std::to_string((m + n) * q) + " is too large");
+  }
+  const bool product = a.op == CglsJv || a.op == CglsJtv;
+  const bool builtIn = a.kind == CgJacobi || a.kind == CgBlockJacobi;
+  if (product && a.epi != 0 && a.epi != (a.op == CglsJv ? 1 : 2)) {
+    fail("epilogue " + std::to_string(a.epi) + " (0: none, 1: residual, of J v; 2: normal, of J^T u)");
+  }
+  if (a.op == CglsIterate && (a.phase < 0 || a.phase > 2)) {
+    fail("phase " + std::to_string(a.phase) + " (0: the whole iteration, 1: up to s, 2: apply and direction)");
+  }
+  if (((a.op == CglsApply || a.op == CglsIterate) && !builtIn && a.kind != CgGiven) || (a.op == CglsBuild && !builtIn)) {
+    fail("unknown preconditioner kind " + std::to_string(a.kind) + " (0: the caller's z, 1: jacobi, 2: block_jacobi)");
+  }
+  if (a.op == CglsInit) {
+    if (!(a.tol >= 0.0)) fail("tol = " + std::to_string(a.tol) + "; it must be >= 0");
+    if (a.maxSteps < 0) fail("max_steps = " + std::to_string(a.maxSteps) + "; it must be >= 0");
+  }
+  const bool usesWork = a.op >= CglsInit && a.op != CglsUpdate;
+  if (usesWork) {
+    if (a.work == nullptr) fail("the workspace pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(a.work) % 16 != 0) fail("the workspace is not 16-byte aligned");
+  }
+  if (a.op == CglsBuild && a.status == nullptr) fail("the status pointer is NULL");
+  if (((a.op >= CglsInit && a.op <= CglsApply) || a.op == CglsIterate) && a.state == nullptr) {
+    fail("the state pointer is NULL");
+  }
+  // the operands the piece needs: (name, pointers, elements)
+  struct Slot {
+    const char* name;
+    const void* const* ptrs;
+    int64_t elems;
+    bool optional;
+  };
+  const auto p = [](auto ptrs) { return reinterpret_cast<const void* const*>(ptrs); };
+  const int64_t nq = n * q, mq = m * q, nnz = a.map->nnz;
+  const int64_t invElems = a.kind == CgBlockJacobi && (a.op == CglsApply || a.op == CglsBuild || a.op == CglsIterate)
+                               ? jacBlockPlan(*a.map).inverseElems()
+                               : n;
+  std::vector<Slot> slots;
+  switch (a.op) {
+    case CglsJv:
+      slots = {{"values", p(a.values), nnz, false}, {"vector", p(a.vec), nq, false}, {"r", p(a.addend), mq, true},
+               {"output", p(a.out), mq, false}};
+      break;
+    case CglsJtv:
+      slots = {{"values", p(a.values), nnz, false}, {"vector", p(a.vec), mq, false}, {"c", p(a.addend), nq, true},
+               {"d", p(a.damp), n, true}, {"x", p(a.x), nq, a.damp == nullptr}, {"output", p(a.out), nq, false}};
+      break;
+    case CglsColSq: slots = {{"values", p(a.values), nnz, false}, {"colsq", p(a.colsq), n, false}}; break;
+    case CglsDamp: slots = {{"colsq", p(a.colsq), n, false}, {"d", p(a.out), n, false}}; break;
+    case CglsInit: slots = {{"b", p(a.vec), nq, false}, {"x", p(a.x), nq, false}}; break;
+    case CglsDelta: slots = {{"t", p(a.vec), mq, false}, {"p", p(a.x), nq, false}, {"d", p(a.damp), n, true}}; break;
+    case CglsUpdate:
+      slots = {{"p", p(a.vec), nq, false}, {"t", p(a.addend), mq, false}, {"x", p(a.x), nq, false},
+               {"res", p(a.out), mq, false}};
+      break;
+    case CglsApply:
+      slots = {{"preconditioner", p(a.damp), invElems, !builtIn}, {"s", p(a.vec), nq, false}, {"z", p(a.out), nq, false}};
+      break;
+    case CglsIterate: {
+      const bool head = a.phase != 2, tail = a.phase != 1;
+      slots = {{"p", p(a.p), nq, false}};
+      if (head) {
+        slots.insert(slots.end(), {{"values", p(a.values), nnz, false}, {"t", p(a.t), mq, false}, {"d", p(a.damp), n, true},
+                                   {"x", p(a.x), nq, false}, {"res", p(a.res), mq, false}, {"c", p(a.addend), nq, true},
+                                   {"s", p(a.s), nq, false}});
+      }
+      if (tail) {
+        slots.insert(slots.end(), {{"preconditioner", p(a.minv), invElems, !builtIn}, {"s", p(a.s), nq, false},
+                                   {"z", p(a.z), nq, false}});
+      }
+      break;
+    }
+    default:
+      slots = {{"values", p(a.values), nnz, a.kind == CgJacobi}, {"colsq", p(a.colsq), n, a.kind != CgJacobi},
+               {"d", p(a.damp), n, true}, {"preconditioner", p(a.out), invElems, false}};
+      break;
+  }
+  for (const Slot& s : slots) {
+    if (s.ptrs == nullptr) {  // (an operand without elements may be NULL altogether)
+      if (!s.optional && s.elems > 0) fail(std::string("the ") + s.name + " pointers are NULL");
+      continue;
+    }
+    for (int64_t b = 0; b < batch; b++) {
+      if (s.ptrs[b] == nullptr && s.elems > 0) {
+        fail(std::string("the ") + s.name + " pointer of batch member " + std::to_string(b) + " is NULL");
+      }
+    }
+  }
+  hipBackendCgls<T>(*symCtx, a, batch, single);
+}
+
 // ---- the Lanczos recurrence ---------------------------------------------------
 static void checkLanczosSizes(const std::string& what, int64_t n, int64_t q, int64_t kmax) {
   const auto fail = [&](const std::string& m) { throw std::runtime_error(what + ": " + m); };
@@ -1586,6 +1703,7 @@ void Solver::mulLt(const std::vector<T*>& L, const std::vector<T*>& x, int64_t i
   template int64_t Solver::invNorm1WorkBytes<T>() const;                                                       \
   template void Solver::invNorm1Estimate<T>(BspCVec_##T, BspCVec_##T, void*, int64_t*, double*, bool) const;   \
   template void Solver::cg<T>(const CgArgs<T>&, int64_t, bool) const;                                          \
+  template void Solver::cgls<T>(const CglsArgs<T>&, int64_t, bool) const;                                      \
   template void Solver::lanczos<T>(const LanczosArgs<T>&, int64_t, bool) const;                                \
   template void Solver::krylovCombine<T>(const KrylovCombineArgs<T>&, int64_t, bool) const;                    \
   template void Solver::reachSolveL<T>(const T*, const std::vector<int64_t>&, T*) const;                       \

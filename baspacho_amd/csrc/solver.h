@@ -18,9 +18,12 @@ namespace BaSpaCho {
 
 struct AssemblyMap;
 struct NormalEqMap;
+struct JacobianProductMap;
 struct SymProductMap;
 template <typename T>
 struct CgArgs;
+template <typename T>
+struct CglsArgs;
 template <typename T>
 struct LanczosArgs;
 template <typename T>
@@ -307,6 +310,16 @@ class Solver {
   int64_t cgWorkBytes(int64_t n, int64_t q) const;
   template <typename T>
   void cg(const CgArgs<T>& a, int64_t batch, bool single) const;
+  // extension: the pieces of the matrix-free least squares (CGLS) on the device (DESIGN.md section 28;
+  // hip_cgls_kernels.h) over a JacobianProductMap of this Solver (jac_product.h).  `a` (CglsArgs,
+  // hip_backend.h) names the piece (CglsOp) and its operands, one pointer per batch member; `state`, `work`
+  // (cglsWorkBytes() per member, 16-byte aligned) and `status` as for cg().  Runs on the stream of
+  // setStream(), nothing is allocated (the first use of a part of the map uploads it) and nothing read back.
+  // Refused before any device work: an empty batch, q out of range, a NULL or misaligned workspace, a NULL
+  // pointer of an operand the piece needs, a map of another Solver, a negative or NaN tolerance or step limit.
+  int64_t cglsWorkBytes(int64_t m, int64_t n, int64_t q) const;
+  template <typename T>
+  void cgls(const CglsArgs<T>& a, int64_t batch, bool single) const;
   // extension: the pieces of the Lanczos recurrence on the device (DESIGN.md section 25;
   // hip_lanczos_kernels.h).  `a` (LanczosArgs, hip_backend.h) names the piece (LanczosOp) and its operands:
   // the vector [n, q] row-major and the basis (slot s at basis + s slotStride elements, `slots` of them), one

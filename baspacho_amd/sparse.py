@@ -36,6 +36,8 @@
     x = S.lstsq(jpat, jvalues, r, damping=(a, b))  # x = (J^T J + D)^-1 J^T r, D = a diag(J^T J) + b I
     st = S.check_positive_definite(pat, values)    # factor status: ok, or the caller's scalar of the first bad pivot
     data, g = S.normal_equations(jpat, jvalues, r) # H = J^T J in the layout and g = J^T r
+    jop = S.JacobianOperator(jrows, jcols, m, n)   # the Jacobian as an operator: row and column lists, no layout
+    x = S.lstsq_cg(jop, jvalues, r, damping=(a, b)) # the same step by CGLS from the entries: no pair list, no factor
 
 The matrix is given by entries (rows[k], cols[k], values[k]) in the caller's scalar order: A_ij = A_ji =
 the sum of the values of the entries at (i, j), i >= j.  `values` is [nnz] or a
@@ -53,6 +55,11 @@ A JacobianPattern takes the entries (rows[k], cols[k], values[k]) of an m x n Ja
 repeated; H = J^T J is formed on the device straight in the solver's layout, in a
 fixed summation order.  hessian / jt_vec / j_vec / normal_equations / lstsq are differentiable in the
 Jacobian values and the vectors, and in the two damping factors when they are tensors.
+
+lstsq_cg solves the same damped least-squares step matrix-free: CGLS on the row and
+column lists of a JacobianOperator (or of JacobianPattern.operator), the residual r - J x kept in m-space, the
+scalars of the iteration in solve_cg's state records; differentiable in the Jacobian values, r and the damping
+factors.  j_vec and jt_vec take a JacobianOperator as well.
 
 covariance and marginal_variances read A^-1 on the pattern from a selected inversion of the factor
 (assemble -> cholesky -> selected_inverse -> a gather) and are differentiable in
@@ -97,6 +104,8 @@ __all__ = ["SymmetricPattern", "JacobianPattern", "assemble", "solve", "logdet",
            "residual", "backward_error", "norm1", "cond_estimate",
            # conjugate gradient from the entries
            "solve_cg",
+           # matrix-free least squares from the entries of a Jacobian
+           "JacobianOperator", "lstsq_cg",
            # Lanczos from the entries: only logdet_slq is differentiable
            "lanczos", "eig_extremes", "cond2_estimate", "logdet_slq",
            # f(A) v from the Lanczos basis: differentiable in the vectors, not in values
@@ -298,6 +307,55 @@ class JacobianPattern(_Pattern):
         self._init_order()
         self._diag = self.solver.diagOffsets()
         self._jrows, self._jcols = rows, cols
+        self._operator = None
+
+    @property
+    def operator(self):
+        """the JacobianOperator of the entries on this pattern's solver, built on first use"""
+        if self._operator is None:
+            self._operator = JacobianOperator._on(self.solver, self._jrows, self._jcols, self.m, self.n,
+                                                  self.param_sizes)
+        return self._operator
+
+
+class JacobianOperator:
+    """The m x n Jacobian with entries (rows[k], cols[k]) as an operator: the lists of its
+    rows and columns for J v and J^T u, and the diagonal blocks of J^T J over the params, for lstsq_cg.  No
+    layout, no pair list of the normal equations: the solver it holds is one over the block-diagonal structure
+    of the params (default: all of size 1), whose analysis is trivial and whose layout is never allocated; it
+    serves as the device context.  Invalid entries are refused by the map, which names the first one."""
+
+    def __init__(self, rows, cols, m, n, param_sizes=None, settings=None):
+        rows, cols = _host_i64(rows), _host_i64(cols)
+        if len(rows) != len(cols):
+            raise ValueError("JacobianOperator: %d rows for %d cols" % (len(rows), len(cols)))
+        n = int(n)
+        ps = np.ones(n, dtype=np.int64) if param_sizes is None else _host_i64(param_sizes)
+        if np.any(ps < 1) or int(ps.sum()) != n:
+            raise ValueError("JacobianOperator: param sizes must be >= 1 and sum to n = %d" % n)
+        num = len(ps)
+        ss = SparseStructure(np.arange(num + 1, dtype=np.int64), np.arange(num, dtype=np.int64))
+        self._setup(create_solver(settings or Settings(), ps, ss), rows, cols, m, n, ps)
+
+    @classmethod
+    def _on(cls, solver, rows, cols, m, n, param_sizes):
+        self = cls.__new__(cls)
+        self._setup(solver, rows, cols, m, n, param_sizes)
+        return self
+
+    def _setup(self, solver, rows, cols, m, n, param_sizes):
+        self.solver, self.m, self.n, self.nnz = solver, int(m), int(n), len(rows)
+        self.param_sizes = param_sizes
+        self.product = solver.jacobianProduct(rows, cols, self.m)
+        self._jrows, self._jcols = rows, cols
+        self._dev = {}
+
+    def _index(self, which, device):
+        key = (which, device)
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy({"jrows": self._jrows, "jcols": self._jcols}[which]).to(device)
+        return self._dev[key]
+
 
 class _Assemble(torch.autograd.Function):
     @staticmethod
@@ -321,7 +379,8 @@ class _Assemble(torch.autograd.Function):
 
 def _check_values(pattern, values, what, kind=SymmetricPattern):
     if not isinstance(pattern, kind):
-        raise TypeError("%s: pattern must be a %s, got %s" % (what, kind.__name__, type(pattern).__name__))
+        names = " or a ".join(k.__name__ for k in (kind if isinstance(kind, tuple) else (kind,)))
+        raise TypeError("%s: pattern must be a %s, got %s" % (what, names, type(pattern).__name__))
     if not isinstance(values, torch.Tensor):
         raise TypeError("%s: values must be a torch.Tensor, got %s" % (what, type(values).__name__))
     if values.dtype not in (torch.float64, torch.float32):
@@ -616,6 +675,15 @@ class _Hessian(torch.autograd.Function):
         return None, gv
 
 
+def _products(jpat):
+    """what runs J^T r and J v: the normal-equations maps of a JacobianPattern (one lane per run), the lists of
+    a JacobianOperator (a wave for a long run); the same bits"""
+    return jpat.product if isinstance(jpat, JacobianOperator) else jpat.normal_eq
+
+
+_JACOBIANS = (JacobianPattern, JacobianOperator)
+
+
 class _JVec(torch.autograd.Function):
     """transposed: J^T x (x [.., m(, q)]), else J x (x [.., n(, q)]).  The gradient of x is the other
     kernel on the incoming gradient; that of values[k] is the dot product over the q vectors of the two
@@ -623,7 +691,7 @@ class _JVec(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, jpat, values, x, transposed):
-        ne = jpat.normal_eq
+        ne = _products(jpat)
         v, xc = values.detach().contiguous(), x.detach().contiguous()
         with _OnCurrentStream(ne.solver, v.device):
             out = ne.jtVec(v, xc) if transposed else ne.jVec(v, xc)
@@ -638,7 +706,7 @@ class _JVec(torch.autograd.Function):
         if g is None:
             return None, None, None, None
         jpat, (v, x) = ctx.jpat, ctx.saved_tensors
-        ne, g = jpat.normal_eq, g.contiguous()
+        ne, g = _products(jpat), g.contiguous()
         gv = gx = None
         if ctx.needs_input_grad[2]:
             with _OnCurrentStream(ne.solver, g.device):
@@ -698,15 +766,17 @@ def hessian(jpat, jvalues, damping=None):
 
 
 def jt_vec(jpat, jvalues, r):
-    """g = J^T r in the caller's order: r [m] or [m, q] -> [n] or [n, q] (leading B when batched)"""
-    _check_values(jpat, jvalues, "jt_vec", JacobianPattern)
+    """g = J^T r in the caller's order: r [m] or [m, q] -> [n] or [n, q] (leading B when batched).  jpat: a
+    JacobianPattern, or a JacobianOperator, whose lists give a run of more than 64 entries to a whole wave"""
+    _check_values(jpat, jvalues, "jt_vec", _JACOBIANS)
     _check_vec(jpat, jvalues, r, jpat.m, "jt_vec", "r")
     return _JVec.apply(jpat, jvalues, r, True)
 
 
 def j_vec(jpat, jvalues, v):
-    """y = J v: v [n] or [n, q] in the caller's order -> [m] or [m, q] (leading B when batched)"""
-    _check_values(jpat, jvalues, "j_vec", JacobianPattern)
+    """y = J v: v [n] or [n, q] in the caller's order -> [m] or [m, q] (leading B when batched).  jpat as for
+    jt_vec"""
+    _check_values(jpat, jvalues, "j_vec", _JACOBIANS)
     _check_vec(jpat, jvalues, v, jpat.n, "j_vec", "v")
     return _JVec.apply(jpat, jvalues, v, False)
 
@@ -1081,6 +1151,178 @@ def solve_cg(pattern, values, b, precond="block_jacobi", tol=1e-10, max_steps=10
         return x
     info = {"iterations": iters, "stop": stop, "relres": relres, "state": state}
     if precond in ("jacobi", "block_jacobi", "fsai"):
+        info["precond_status"] = status
+    return x, info
+
+
+# ---- matrix-free least squares from the entries -----------------------------------
+def _cgls_damping(what, damping):
+    """(alpha, beta) as given, checked like lstsq's damping"""
+    try:
+        alpha, beta = damping
+    except (TypeError, ValueError):
+        raise TypeError("%s: damping must be a pair (alpha, beta), got %r" % (what, damping)) from None
+    for name, t in (("alpha", alpha), ("beta", beta)):
+        if isinstance(t, torch.Tensor):
+            if t.dim() != 0:
+                raise ValueError("%s: damping %s must be a float or a 0-dim tensor, got shape %s"
+                                 % (what, name, tuple(t.shape)))
+        elif isinstance(t, bool) or not isinstance(t, (int, float)):
+            raise TypeError("%s: damping %s must be a float or a 0-dim tensor, got %s" % (what, name, type(t).__name__))
+    return alpha, beta
+
+
+def _cgls_run(jop, v, r, c, ab, precond, tol, max_steps, check_every, x0, cache):
+    """the iteration of lstsq_cg on detached, contiguous operands: (x shaped like c or J^T r, the CglsRun).
+    `cache` keeps what was built from v (the column norms, the damping vector, the preconditioner) for the
+    backward pass"""
+    from . import cgls as _cgls
+    if r is None and c is None:
+        raise ValueError("lstsq_cg: r and c cannot both be absent")
+    prod = jop.product
+    batched = v.dim() == 2
+    dim = 1 if batched else 0
+    like = r if r is not None else c
+    has_k = like.dim() == dim + 2
+    lead = tuple(v.shape[:-1])
+    q = like.shape[-1] if has_k else 1
+    r3 = None if r is None else r.contiguous().reshape(lead + (jop.m, q))
+    c3 = None if c is None else c.contiguous().reshape(lead + (jop.n, q))
+    shape = lead + (jop.n,) + ((q,) if has_k else ())
+    if "colsq" not in cache and (ab is not None or precond == "jacobi"):
+        cache["colsq"] = _cgls.column_norms(prod, v)
+    if "d" not in cache:
+        cache["d"] = None if ab is None else _cgls.damping_vector(prod, cache["colsq"], ab[0], ab[1], v)
+    d = cache["d"]
+    x3 = torch.zeros(lead + (jop.n, q), dtype=v.dtype, device=v.device) if x0 is None else \
+        x0.detach().contiguous().reshape(lead + (jop.n, q)).clone()
+    pc = None
+    if precond in ("jacobi", "block_jacobi"):
+        if precond not in cache:
+            cache[precond] = _cgls.Preconditioner(prod, precond, v, cache.get("colsq"), d)
+        pc = cache[precond]
+    elif precond is not None:
+        def pc(s):
+            z = precond(s if has_k else s.reshape(shape))
+            if not isinstance(z, torch.Tensor) or z.shape != shape:
+                raise ValueError("lstsq_cg: the preconditioner must return a tensor of shape %s" % (shape,))
+            return z.reshape(s.shape)
+    run = _cgls.CglsRun(prod, v, r3, c3, d, x3, x0 is not None, pc, tol, max_steps).run(check_every)
+    return x3.reshape(shape), run
+
+
+class _LstsqCG(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, jop, values, r, alpha, beta, precond, tol, max_steps, check_every, x0):
+        v = values.detach().contiguous()
+        ab = None if alpha is None else (float(alpha), float(beta))
+        cache = {}
+        with _OnCurrentStream(jop.solver, v.device):
+            x, run = _cgls_run(jop, v, r.detach(), None, ab, precond, tol, max_steps, check_every, x0, cache)
+            has_k = r.dim() == v.dim() + 1
+            info = [t if has_k else t.squeeze(-1) for t in (run.iterations(), run.stop(), run.relres())]
+            info.append(run.state if has_k else run.state.squeeze(-2))
+            built = cache.get(precond) if isinstance(precond, str) else None
+            status = built.status if built is not None else torch.empty(0, device=v.device)
+        ctx.jop, ctx.cache, ctx.ab = jop, cache, ab
+        ctx.ab_dtypes = tuple(t.dtype if isinstance(t, torch.Tensor) else None for t in (alpha, beta))
+        ctx.settings = (precond, tol, max_steps, check_every)
+        ctx.save_for_backward(v, r.detach().contiguous(), x)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*info, status)
+        return (x, *info, status)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, *_):
+        need = ctx.needs_input_grad
+        if g is None or not (need[1] or need[2] or need[3] or need[4]):
+            return (None,) * 10
+        jop, (v, r, x), ab = ctx.jop, ctx.saved_tensors, ctx.ab
+        precond, tol, max_steps, check_every = ctx.settings
+        prod = jop.product
+        gv = gr = ga = gb = None
+        with _OnCurrentStream(jop.solver, g.device):
+            # N is symmetric: the same iteration with the right-hand side c = g alone
+            w, _ = _cgls_run(jop, v, None, g.contiguous(), ab, precond, tol, max_steps, check_every, None, ctx.cache)
+            jw = prod.jVec(v, w)
+            if need[2]:
+                gr = jw
+            if need[1]:
+                dim = v.dim() - 1
+                rows, cols = jop._index("jrows", g.device), jop._index("jcols", g.device)
+                res = r - prod.jVec(v, x)  # the residual of the result, by a product
+                wc, xc = w.index_select(dim, cols), x.index_select(dim, cols)
+                gv = wc * res.index_select(dim, rows) - jw.index_select(dim, rows) * xc
+                wx = wc * xc
+                if gv.dim() > v.dim():
+                    gv, wx = gv.sum(-1), wx.sum(-1)
+                if ab is not None:
+                    gv = gv - 2.0 * ab[0] * v * wx
+        if ab is not None and (need[3] or need[4]):
+            wx = w * x
+            if wx.dim() > v.dim():
+                wx = wx.sum(-1)
+            if need[3]:
+                ga = -(ctx.cache["colsq"] * wx.double()).sum().to(ctx.ab_dtypes[0])
+            if need[4]:
+                gb = -wx.double().sum().to(ctx.ab_dtypes[1])
+        return (None, gv, gr, ga, gb) + (None,) * 5
+
+
+def lstsq_cg(jop, jvalues, r, damping=None, precond="block_jacobi", tol=1e-10, max_steps=100, check_every=8, x0=None,
+             return_info=False):
+    """x = (J^T J + D)^-1 J^T r in the caller's order by CGLS, the conjugate gradient on the normal equations
+    that keeps the residual r - J x in m-space, straight from the entries of J: the Gauss-Newton / Levenberg-
+    Marquardt step of lstsq without a layout, a pair list or a factor.  jop: a JacobianOperator, or a
+    JacobianPattern (its .operator is used).  jvalues [nnz] / [B, nnz], r [m] / [m, k] with a leading B for a
+    batch, float64 or float32: every (matrix, right-hand side) is a problem of its own, with its state record on
+    the device, and stops on its own as solve_cg's problems do, on s = J^T (r - J x) - D x: |s|^2 <= tol^2 |J^T
+    r|^2 (converged), max_steps, a breakdown (the curvature |J p|^2 + p^T D p or s.z not > 0), a non-finite
+    sum, or at once for J^T r = 0 (x = 0).
+
+    damping=(alpha, beta), floats or 0-dim tensors: D = diag(alpha colsq_i + beta), colsq_i the squared norm of
+    column i of J, lstsq's damping.  precond: None; "jacobi" (1 / (colsq_i + d_i)); "block_jacobi" (the inverses
+    of the diagonal blocks of J^T J + D over the params, at most 32 scalars each: a ValueError names a wider
+    one), both built and applied on the device; or a callable s -> z on tensors shaped like x.  The block build is one
+    wave per param: where a param gathers very many Jacobian rows (a camera with thousands of observations) it
+    dominates a short solve, and "jacobi" is then the cheaper choice (DESIGN.md section 28 has the figures).  check_every, x0
+    and return_info as for solve_cg; info has "iterations", "stop", "relres", "state" and, for a built-in
+    preconditioner, "precond_status".
+
+    Differentiable in jvalues, r, alpha and beta (x0 gets no gradient): one more run with the incoming gradient
+    as the right-hand side, the same preconditioner and settings, then products and elementwise gathers.  Runs
+    on the current torch stream; no stream capture, no double backward."""
+    from . import cg as _cg
+    what = "lstsq_cg"
+    if isinstance(jop, JacobianPattern):
+        jop = jop.operator
+    _check_values(jop, jvalues, what, _JACOBIANS)
+    _check_vec(jop, jvalues, r, jop.m, what, "r")
+    _cg.check_settings(what, tol, max_steps, check_every)
+    alpha = beta = None
+    if damping is not None:
+        alpha, beta = _cgls_damping(what, damping)
+    if x0 is not None:
+        shape = tuple(jvalues.shape[:-1]) + (jop.n,) + tuple(r.shape[jvalues.dim():])
+        if not isinstance(x0, torch.Tensor) or tuple(x0.shape) != shape or x0.dtype != r.dtype or x0.device != r.device:
+            raise ValueError("%s: x0 must be a %s tensor of shape %s on %s" % (what, r.dtype, shape, r.device))
+    if isinstance(precond, str):
+        if precond not in ("jacobi", "block_jacobi"):
+            raise ValueError("%s: precond must be None, 'jacobi', 'block_jacobi' or a callable, got %r" % (what, precond))
+        if precond == "block_jacobi" and int(np.max(jop.param_sizes, initial=0)) > _cg.MAX_BLOCK:
+            p = int(np.argmax(jop.param_sizes > _cg.MAX_BLOCK))
+            raise ValueError("%s: param %d has %d scalars; 'block_jacobi' takes params of at most %d"
+                             % (what, p, int(jop.param_sizes[p]), _cg.MAX_BLOCK))
+    elif precond is not None and not callable(precond):
+        raise ValueError("%s: precond must be None, 'jacobi', 'block_jacobi' or a callable, got %r" % (what, precond))
+    _ag._check_device(jop.solver, what, jvalues, r)
+    x, iters, stop, relres, state, status = _LstsqCG.apply(jop, jvalues, r, alpha, beta, precond, float(tol),
+                                                            max_steps, check_every, x0)
+    if not return_info:
+        return x
+    info = {"iterations": iters, "stop": stop, "relres": relres, "state": state}
+    if precond in ("jacobi", "block_jacobi"):
         info["precond_status"] = status
     return x, info
 

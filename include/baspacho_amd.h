@@ -857,6 +857,197 @@ int bsp_cg_precond_build_f32(bsp_solver* s, const bsp_sym_product* p, int32_t ki
 int bsp_cg_precond_build_batched_f32(bsp_solver* s, const bsp_sym_product* p, int32_t kind,
                                      const float* const* dev_values, float* const* dev_minv, void* dev_work,
                                      int64_t* dev_status, int32_t batch);
+/* EXTENSION without a counterpart in the reference: matrix-free least squares from the entries of a sparse
+   Jacobian J, m x order(), given as (rows[k], cols[k], values[k]) in the caller's scalar order (DESIGN.md
+   section 28): products with J and J^T, and the pieces of CGLS for (J^T J + D) x = J^T r + c, D = diag(d),
+   d_i = alpha colsq_i + beta, colsq_i the squared norm of column i.  No layout, no pair list, no factor.
+   bsp_jac_product_create builds the map once on the host (no device work): the entries of every row and of
+   every column in ascending k, each with the list of its runs of more than 64 terms, which a whole wave sums
+   in the same sequential order.  The solver gives the order, the stream and the params; its layout is never
+   touched.  It fails, with bsp_last_error() naming the first offending entry and its (row, col), on an index
+   out of range or a repeated position; nnz and m must be in [0, 2^31).  Nothing of the size of the pair count
+   of bsp_normal_eq_create is built.  Each part (rows, columns, blocks) is uploaded by the first call that
+   needs it and kept until bsp_jac_product_destroy; the map must be destroyed before its solver.
+   bsp_jac_product_info: out[0] nnz, [1] m, [2] n, [3] / [4] the longest row and the rows of more than 64
+   entries, [5] / [6] the same for columns, [7] / [8] device bytes of the row and of the column lists.
+   bsp_cgls_precond_info: kind 1 (Jacobi) or 2 (block-Jacobi over the solver's params; one wider than 32
+   scalars is refused by name, and so is an item count outside [0, 2^31), stated, before anything of that
+   size is allocated -- bsp_jac_product_check_items is that check alone): out = {blocks, items, elements of the
+   inverse, widest block, device bytes of the plan}.  The items of a block are the pairs (ka, kb) of entries of
+   one Jacobian row with both columns in the block, cols[ka] >= cols[kb], self-pairs included, at position
+   (cols[ka] - s) w + (cols[kb] - s); they come in ascending Jacobian row.
+   bsp_jac_product_table: host copies for tests.  part 0 (rows) and 1 (columns): t0 = start [runs + 1], t1 =
+   entry, t2 = the gathered index [nnz each], t3 = the long runs, t4 unused; part 2 (blocks): t0 = block_start,
+   t1 = item_start [blocks + 1 each], t2 = ka, t3 = kb, t4 = position [items each].
+   PRODUCTS.  jv: dev_out[i, j] = sum over the entries of row i, ascending k, of values[k] * dev_v[cols[k], j];
+   jtv: dev_out[c, j] = sum over the entries of column c of values[k] * dev_u[rows[k], j]; every product
+   rounded in the value type and added one by one from +0: bitwise bsp_normal_eq_j_vec_* / _jt_vec_*.
+     residual: dev_res = dev_r - J dev_x, the subtraction by the thread that holds the sum (dev_r NULL: -J x);
+     normal:   dev_out = (J^T dev_res - dev_d * dev_x) + dev_c in this order; dev_d (with dev_x) and dev_c may
+               each be NULL, and an absent operand's step is omitted, not added as a zero.
+     Both take dev_state (NULL: every column; else the columns of stopped problems are skipped).
+   THE ITERATION.  The state record, its stop codes and the frozen-column rule are those of the bsp_cg_* pieces,
+   with rz = s.z, pAp = delta = |J p|^2 + p^T D p, rr = s.s and bb = |J^T r + c|^2; the direction is
+   bsp_cg_direction_*.  x, p, s, z are [n, q], res and t [m, q], d [n], colsq [n] doubles.
+     colsq:   the fold over the column's entries, ascending k from +0, of double(v) * double(v)
+     damp:    d_i = T(alpha * colsq_i + beta), in double
+     init:    dev_b = J^T r + c (the caller's, by normal): the records reset, bb, x = 0 and stop 5 for a zero b
+     delta:   the partials of t.t over the chunks of m, then (dev_d given) those of (p_i * p_i) * d_i over the
+              chunks of n, folded as ONE list; not finite stops with 4, not > 0 with 3; alpha = rz / delta
+     update:  x += alpha p and res -= alpha t in one launch
+     apply:   kind 0: dev_z is the caller's M^-1 s and only read (s itself without a preconditioner); kinds 1,
+              2: dev_z = M^-1 dev_s from dev_minv.  The same pass takes s.s and s.z; one fold counts the
+              iteration (not with start = 1), tests s.s (non-finite: 4; <= tol^2 bb: 1; step limit: 2), then
+              gamma = s.z (non-finite: 4; not > 0: 3) and sets beta = gamma / gamma(old)
+     precond_build: kind 1: inv_i = T(1 / (colsq_i + double(d_i))) (dev_values may be NULL); kind 2: the block's
+              items summed in ascending Jacobian row in double, double(d) added to the diagonal last, then
+              bsp_cg_precond_build_*'s factorisation and inverse (dev_colsq may be NULL).  dev_d NULL: no
+              damping.  dev_status as for bsp_cg_precond_build_*.
+   One iteration is: t = J p (jv); delta; update; s (normal); apply; direction.
+     iterate: that whole iteration in ONE call, queued on dev_p, dev_t, dev_x, dev_res, dev_s, dev_z (with
+              dev_values, dev_d, dev_c, dev_minv as above).  The fold of delta rides in the update's launch (every
+              workgroup folds the column's partials in the fold's order and takes the same decision), so it is 7
+              launches for the pieces' 8, with the same sums in the same order: the same bits as the six calls.
+              phase 0: all of it (kind 0 with dev_z == dev_s: no preconditioner); phase 1: up to and including s,
+              for a caller that then writes its own z = M^-1 s; phase 2: apply and direction alone.
+   Sums in double in the two-pass
+   order of the bsp_cg_* pieces; no atomics, no memset; member b of a batched call is bitwise the single call.
+   WORKSPACE: the caller's, 16-byte aligned, bsp_cgls_work_bytes bytes per member.  Refused before any device
+   work: NULL arguments that the piece needs, an empty batch, q out of range, a misaligned workspace, a map of
+   another solver.  A written operand of a piece must not overlap another operand of it (with kind 0, dev_z may be
+   dev_s: it is only read); overlaps are the caller's to avoid and are not checked.
+   bsp_jac_product_check_items exists for the tests alone: it is the item-count check of the block plan, which no
+   test can reach through a map of 2^31 items. */
+typedef struct bsp_jac_product bsp_jac_product;
+int bsp_jac_product_create(bsp_solver* s, int64_t m, int64_t nnz, const int64_t* rows, const int64_t* cols,
+                           bsp_jac_product** out);
+void bsp_jac_product_destroy(bsp_jac_product* p);
+int bsp_jac_product_info(const bsp_jac_product* p, int64_t out[9]);
+int bsp_jac_product_check_items(int64_t items);
+int bsp_jac_product_table(const bsp_jac_product* p, int32_t part, int32_t* t0, int32_t* t1, int32_t* t2, int32_t* t3,
+                          int32_t* t4);
+int bsp_cgls_precond_info(const bsp_jac_product* p, int32_t kind, int64_t out[5]);
+int bsp_cgls_work_bytes(const bsp_solver* s, const bsp_jac_product* p, int64_t q, int64_t* out);
+int bsp_jac_product_jv_f64(bsp_solver* s, const bsp_jac_product* p, const double* dev_values, const double* dev_v, int64_t q,
+                           double* dev_out);
+int bsp_jac_product_jv_batched_f64(bsp_solver* s, const bsp_jac_product* p, const double* const* dev_values,
+                                   const double* const* dev_v, int64_t q, double* const* dev_out, int32_t batch);
+int bsp_jac_product_jtv_f64(bsp_solver* s, const bsp_jac_product* p, const double* dev_values, const double* dev_u, int64_t q,
+                            double* dev_out);
+int bsp_jac_product_jtv_batched_f64(bsp_solver* s, const bsp_jac_product* p, const double* const* dev_values,
+                                    const double* const* dev_u, int64_t q, double* const* dev_out, int32_t batch);
+int bsp_cgls_residual_f64(bsp_solver* s, const bsp_jac_product* p, const double* dev_values, const double* dev_x, const double* dev_r,
+                          int64_t q, double* dev_res, int64_t* dev_state);
+int bsp_cgls_residual_batched_f64(bsp_solver* s, const bsp_jac_product* p, const double* const* dev_values,
+                                  const double* const* dev_x, const double* const* dev_r, int64_t q, double* const* dev_res,
+                                  int64_t* dev_state, int32_t batch);
+int bsp_cgls_normal_f64(bsp_solver* s, const bsp_jac_product* p, const double* dev_values, const double* dev_res, const double* dev_d,
+                        const double* dev_x, const double* dev_c, int64_t q, double* dev_out, int64_t* dev_state);
+int bsp_cgls_normal_batched_f64(bsp_solver* s, const bsp_jac_product* p, const double* const* dev_values,
+                                const double* const* dev_res, const double* const* dev_d, const double* const* dev_x,
+                                const double* const* dev_c, int64_t q, double* const* dev_out, int64_t* dev_state, int32_t batch);
+int bsp_cgls_colsq_f64(bsp_solver* s, const bsp_jac_product* p, const double* dev_values, double* dev_colsq);
+int bsp_cgls_colsq_batched_f64(bsp_solver* s, const bsp_jac_product* p, const double* const* dev_values,
+                               double* const* dev_colsq, int32_t batch);
+int bsp_cgls_damp_f64(bsp_solver* s, const bsp_jac_product* p, const double* dev_colsq, double alpha, double beta,
+                      double* dev_d);
+int bsp_cgls_damp_batched_f64(bsp_solver* s, const bsp_jac_product* p, const double* const* dev_colsq, double alpha,
+                              double beta, double* const* dev_d, int32_t batch);
+int bsp_cgls_init_f64(bsp_solver* s, const bsp_jac_product* p, int64_t q, const double* dev_b, double* dev_x, double tol,
+                      int64_t max_steps, void* dev_work, int64_t* dev_state);
+int bsp_cgls_init_batched_f64(bsp_solver* s, const bsp_jac_product* p, int64_t q, const double* const* dev_b,
+                              double* const* dev_x, double tol, int64_t max_steps, void* dev_work, int64_t* dev_state,
+                              int32_t batch);
+int bsp_cgls_delta_f64(bsp_solver* s, const bsp_jac_product* p, int64_t q, const double* dev_t, const double* dev_p,
+                       const double* dev_d, void* dev_work, int64_t* dev_state);
+int bsp_cgls_delta_batched_f64(bsp_solver* s, const bsp_jac_product* p, int64_t q, const double* const* dev_t,
+                               const double* const* dev_p, const double* const* dev_d, void* dev_work, int64_t* dev_state,
+                               int32_t batch);
+int bsp_cgls_update_f64(bsp_solver* s, const bsp_jac_product* p, int64_t q, const double* dev_p, const double* dev_t, double* dev_x,
+                        double* dev_res, int64_t* dev_state);
+int bsp_cgls_update_batched_f64(bsp_solver* s, const bsp_jac_product* p, int64_t q, const double* const* dev_p,
+                                const double* const* dev_t, double* const* dev_x, double* const* dev_res, int64_t* dev_state,
+                                int32_t batch);
+int bsp_cgls_apply_f64(bsp_solver* s, const bsp_jac_product* p, int32_t kind, int64_t q, const double* dev_minv,
+                       const double* dev_s, double* dev_z, int32_t start, void* dev_work, int64_t* dev_state);
+int bsp_cgls_apply_batched_f64(bsp_solver* s, const bsp_jac_product* p, int32_t kind, int64_t q,
+                               const double* const* dev_minv, const double* const* dev_s, double* const* dev_z, int32_t start,
+                               void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_cgls_iterate_f64(bsp_solver* s, const bsp_jac_product* p, int32_t kind, int32_t phase, int64_t q,
+                         const double* dev_values, const double* dev_d, const double* dev_c, const double* dev_minv, double* dev_p, double* dev_t,
+                         double* dev_x, double* dev_res, double* dev_s, double* dev_z, void* dev_work, int64_t* dev_state);
+int bsp_cgls_iterate_batched_f64(bsp_solver* s, const bsp_jac_product* p, int32_t kind, int32_t phase, int64_t q,
+                                 const double* const* dev_values, const double* const* dev_d, const double* const* dev_c,
+                                 const double* const* dev_minv, double* const* dev_p, double* const* dev_t, double* const* dev_x,
+                                 double* const* dev_res, double* const* dev_s, double* const* dev_z, void* dev_work,
+                                 int64_t* dev_state, int32_t batch);
+int bsp_cgls_precond_build_f64(bsp_solver* s, const bsp_jac_product* p, int32_t kind, const double* dev_values,
+                               const double* dev_colsq, const double* dev_d, double* dev_minv, void* dev_work,
+                               int64_t* dev_status);
+int bsp_cgls_precond_build_batched_f64(bsp_solver* s, const bsp_jac_product* p, int32_t kind,
+                                       const double* const* dev_values, const double* const* dev_colsq,
+                                       const double* const* dev_d, double* const* dev_minv, void* dev_work, int64_t* dev_status,
+                                       int32_t batch);
+int bsp_jac_product_jv_f32(bsp_solver* s, const bsp_jac_product* p, const float* dev_values, const float* dev_v, int64_t q,
+                           float* dev_out);
+int bsp_jac_product_jv_batched_f32(bsp_solver* s, const bsp_jac_product* p, const float* const* dev_values,
+                                   const float* const* dev_v, int64_t q, float* const* dev_out, int32_t batch);
+int bsp_jac_product_jtv_f32(bsp_solver* s, const bsp_jac_product* p, const float* dev_values, const float* dev_u, int64_t q,
+                            float* dev_out);
+int bsp_jac_product_jtv_batched_f32(bsp_solver* s, const bsp_jac_product* p, const float* const* dev_values,
+                                    const float* const* dev_u, int64_t q, float* const* dev_out, int32_t batch);
+int bsp_cgls_residual_f32(bsp_solver* s, const bsp_jac_product* p, const float* dev_values, const float* dev_x, const float* dev_r,
+                          int64_t q, float* dev_res, int64_t* dev_state);
+int bsp_cgls_residual_batched_f32(bsp_solver* s, const bsp_jac_product* p, const float* const* dev_values,
+                                  const float* const* dev_x, const float* const* dev_r, int64_t q, float* const* dev_res,
+                                  int64_t* dev_state, int32_t batch);
+int bsp_cgls_normal_f32(bsp_solver* s, const bsp_jac_product* p, const float* dev_values, const float* dev_res, const float* dev_d,
+                        const float* dev_x, const float* dev_c, int64_t q, float* dev_out, int64_t* dev_state);
+int bsp_cgls_normal_batched_f32(bsp_solver* s, const bsp_jac_product* p, const float* const* dev_values,
+                                const float* const* dev_res, const float* const* dev_d, const float* const* dev_x,
+                                const float* const* dev_c, int64_t q, float* const* dev_out, int64_t* dev_state, int32_t batch);
+int bsp_cgls_colsq_f32(bsp_solver* s, const bsp_jac_product* p, const float* dev_values, double* dev_colsq);
+int bsp_cgls_colsq_batched_f32(bsp_solver* s, const bsp_jac_product* p, const float* const* dev_values,
+                               double* const* dev_colsq, int32_t batch);
+int bsp_cgls_damp_f32(bsp_solver* s, const bsp_jac_product* p, const double* dev_colsq, double alpha, double beta,
+                      float* dev_d);
+int bsp_cgls_damp_batched_f32(bsp_solver* s, const bsp_jac_product* p, const double* const* dev_colsq, double alpha,
+                              double beta, float* const* dev_d, int32_t batch);
+int bsp_cgls_init_f32(bsp_solver* s, const bsp_jac_product* p, int64_t q, const float* dev_b, float* dev_x, double tol,
+                      int64_t max_steps, void* dev_work, int64_t* dev_state);
+int bsp_cgls_init_batched_f32(bsp_solver* s, const bsp_jac_product* p, int64_t q, const float* const* dev_b,
+                              float* const* dev_x, double tol, int64_t max_steps, void* dev_work, int64_t* dev_state,
+                              int32_t batch);
+int bsp_cgls_delta_f32(bsp_solver* s, const bsp_jac_product* p, int64_t q, const float* dev_t, const float* dev_p,
+                       const float* dev_d, void* dev_work, int64_t* dev_state);
+int bsp_cgls_delta_batched_f32(bsp_solver* s, const bsp_jac_product* p, int64_t q, const float* const* dev_t,
+                               const float* const* dev_p, const float* const* dev_d, void* dev_work, int64_t* dev_state,
+                               int32_t batch);
+int bsp_cgls_update_f32(bsp_solver* s, const bsp_jac_product* p, int64_t q, const float* dev_p, const float* dev_t, float* dev_x,
+                        float* dev_res, int64_t* dev_state);
+int bsp_cgls_update_batched_f32(bsp_solver* s, const bsp_jac_product* p, int64_t q, const float* const* dev_p,
+                                const float* const* dev_t, float* const* dev_x, float* const* dev_res, int64_t* dev_state,
+                                int32_t batch);
+int bsp_cgls_apply_f32(bsp_solver* s, const bsp_jac_product* p, int32_t kind, int64_t q, const float* dev_minv,
+                       const float* dev_s, float* dev_z, int32_t start, void* dev_work, int64_t* dev_state);
+int bsp_cgls_apply_batched_f32(bsp_solver* s, const bsp_jac_product* p, int32_t kind, int64_t q,
+                               const float* const* dev_minv, const float* const* dev_s, float* const* dev_z, int32_t start,
+                               void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_cgls_iterate_f32(bsp_solver* s, const bsp_jac_product* p, int32_t kind, int32_t phase, int64_t q,
+                         const float* dev_values, const float* dev_d, const float* dev_c, const float* dev_minv, float* dev_p, float* dev_t,
+                         float* dev_x, float* dev_res, float* dev_s, float* dev_z, void* dev_work, int64_t* dev_state);
+int bsp_cgls_iterate_batched_f32(bsp_solver* s, const bsp_jac_product* p, int32_t kind, int32_t phase, int64_t q,
+                                 const float* const* dev_values, const float* const* dev_d, const float* const* dev_c,
+                                 const float* const* dev_minv, float* const* dev_p, float* const* dev_t, float* const* dev_x,
+                                 float* const* dev_res, float* const* dev_s, float* const* dev_z, void* dev_work,
+                                 int64_t* dev_state, int32_t batch);
+int bsp_cgls_precond_build_f32(bsp_solver* s, const bsp_jac_product* p, int32_t kind, const float* dev_values,
+                               const double* dev_colsq, const float* dev_d, float* dev_minv, void* dev_work,
+                               int64_t* dev_status);
+int bsp_cgls_precond_build_batched_f32(bsp_solver* s, const bsp_jac_product* p, int32_t kind,
+                                       const float* const* dev_values, const double* const* dev_colsq,
+                                       const float* const* dev_d, float* const* dev_minv, void* dev_work, int64_t* dev_status,
+                                       int32_t batch);
 /* EXTENSION without a counterpart in the reference's library: the pieces of the Lanczos recurrence with its
    scalars on the device, for extreme eigenvalues, a 2-norm condition estimate and
    stochastic Lanczos quadrature (log-determinants) without a factor.  One problem per (matrix, start vector):
