@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["Settings", "Solver", "FactorizationError", "Assembly", "NormalEquations", "JacobianProduct", "SymProduct", "create_solver", "SparseStructure", "BackendHip", "BackendCuda",
+__all__ = ["Settings", "Solver", "FactorizationError", "Assembly", "NormalEquations", "JacobianProduct", "JacobianSchur", "SymProduct", "create_solver", "SparseStructure", "BackendHip", "BackendCuda",
            "BackendRef", "BackendFast", "AddFillComplete", "AddFillForAutoElims",
            "AddFillForGivenElims", "AddFillNone"]
 
@@ -1307,6 +1307,14 @@ class Solver:
         is never touched.  No (row, col) may repeat.  See JacobianProduct."""
         return JacobianProduct(self, rows, cols, m)
 
+    def jacobianSchur(self, product, eliminate):
+        """extension: the map of the implicit Schur elimination of the params `eliminate` (indices into this
+        solver's params) on the JacobianProduct `product` (bsp_jac_schur_create), built once on the host.  See
+        JacobianSchur."""
+        if not isinstance(product, JacobianProduct) or product.solver is not self:
+            raise ValueError("jacobianSchur: product must be a JacobianProduct of this solver")
+        return JacobianSchur(product, eliminate)
+
     def diagOffsets(self):
         """extension: int64 array [order()], the layout offsets of the diagonal elements in internal
         order (what damp() touches)"""
@@ -1680,6 +1688,233 @@ class JacobianProduct(_EntryMap):
     def jVec(self, values, v, out=None):
         """v [n] or [n, q] (leading B when values are batched) -> J v, [m] / [m, q] (bsp_jac_product_jv_*)"""
         return self._run("jVec", "bsp_jac_product_jv_", values, v, self.n, self.m, out)
+
+
+class JacobianSchur:
+    """extension: implicit Schur elimination on the entries of a Jacobian.  The params
+    `eliminate` of the JacobianProduct's solver are eliminated exactly (no Jacobian row may touch two of them, each
+    has at most 8 scalars) and the reduced system S x_k = b_k, S = C - F^T B^-1 F, is reached through products
+    alone: S and F are never formed.  Built by Solver.jacobianSchur(); keeps its product alive.  The kept scalars
+    are numbered 0 .. nK - 1 and the eliminated ones 0 .. nE - 1 in ascending caller's scalar.  build: the inverses
+    of the diagonal blocks of B = J_e^T J_e + D_e; mv: S p; reduce: b_k = g_k - F^T B^-1 g_e; backSubstitute: the
+    full x from x_k.  Sums run in a fixed order with every product rounded first (bitwise the numpy restatement);
+    each part of the map is uploaded by the first call that needs it; everything runs on the solver's stream
+    without synchronising."""
+
+    _KEYS = ("nnz", "m", "n", "n_kept", "n_elim", "elim_params", "free_rows", "max_elim_width", "max_group",
+             "kept_entries", "elim_entries", "long_rows_kept", "long_rows_elim", "long_cols_elim", "long_cols_kept",
+             "block_items", "inverse_elems", "map_bytes", "plan_bytes", "group_rows")
+
+    def __init__(self, product, eliminate):
+        self._lib = product._lib
+        self._h = None
+        e = _host_indices(eliminate, "eliminate")
+        h = ctypes.c_void_p()
+        _check(self._lib.bsp_jac_schur_create(product._h, ctypes.c_int64(len(e)), e.ctypes.data_as(_I64P),
+                                              ctypes.byref(h)))
+        self._h = h
+        self.product, self.solver = product, product.solver
+        self.m, self.n, self.nnz = product.m, product.n, product.nnz
+        i = self.info()
+        self.nK, self.nE, self.inverse_elems = i["n_kept"], i["n_elim"], i["inverse_elems"]
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.bsp_jac_schur_destroy(h)
+
+    def info(self):
+        """figures of the map (bsp_jac_schur_info)"""
+        out = (ctypes.c_int64 * len(self._KEYS))()
+        _check(self._lib.bsp_jac_schur_info(self._h, out))
+        return dict(zip(self._KEYS, [int(x) for x in out]))
+
+    def table(self):
+        """every list of the map as int32 arrays (bsp_jac_schur_table): a dict with rows_kept, rows_elim, cols_elim
+        and cols_kept, each (start, entry, index, long_runs); kept_scalar, elim_scalar, elim_off, elim_param;
+        group_start, group_row, free_rows; block_start, block_width, item_start, item_a, item_b, item_pos"""
+        i = self.info()
+
+        def get(part, *sizes):
+            arrs = [np.zeros(max(n, 1), dtype=np.int32) for n in sizes]
+            ptrs = [a.ctypes.data_as(_I32P) for a in arrs] + [None] * (4 - len(arrs))
+            _check(self._lib.bsp_jac_schur_table(self._h, ctypes.c_int32(part), *ptrs))
+            return [a[:n] for a, n in zip(arrs, sizes)]
+
+        out = {}
+        lists = (("rows_kept", self.m, i["kept_entries"], i["long_rows_kept"]),
+                 ("rows_elim", self.m, i["elim_entries"], i["long_rows_elim"]),
+                 ("cols_elim", self.nE, i["elim_entries"], i["long_cols_elim"]),
+                 ("cols_kept", self.nK, i["kept_entries"], i["long_cols_kept"]))
+        for part, (name, runs, items, longs) in enumerate(lists):
+            out[name] = tuple(get(part, runs + 1, items, items, longs))
+        ne = i["elim_params"]
+        out["kept_scalar"], out["elim_scalar"], out["elim_off"], out["elim_param"] = get(4, self.nK, self.nE, ne + 1, ne)
+        out["group_start"], out["group_row"], out["free_rows"] = get(5, ne + 1, i["group_rows"], i["free_rows"])
+        out["block_start"], out["block_width"], out["item_start"] = get(6, ne + 1, ne, ne + 1)
+        out["item_a"], out["item_b"], out["item_pos"] = get(7, *([i["block_items"]] * 3))
+        return out
+
+    _KINDS = {"jacobi": 1, "block_jacobi": 2}
+
+    def precondInfo(self, kind):
+        """{blocks, items, inverse_elems, max_width, device_bytes} of the plan of "jacobi" or "block_jacobi" for the
+        reduced system, on the kept scalars (a kept param wider than 32 scalars is refused by name).  Host work only."""
+        if kind not in self._KINDS:
+            raise ValueError("precondInfo: kind must be 'jacobi' or 'block_jacobi', got %r" % (kind,))
+        out = (ctypes.c_int64 * 5)()
+        _check(self._lib.bsp_jac_schur_precond_info(self._h, ctypes.c_int32(self._KINDS[kind]), out))
+        return dict(zip(("blocks", "items", "inverse_elems", "max_width", "device_bytes"), [int(x) for x in out]))
+
+    def keptBlockTable(self):
+        """(block_start, block_width, item_start, param, ka, kb, pos) of the plan of the diagonal blocks of C over the
+        kept params: int32 arrays, block_start in the caller's scalars"""
+        info = self.precondInfo("block_jacobi")
+        nb, items = info["blocks"], info["items"]
+        a = [np.zeros(max(n, 1), dtype=np.int32) for n in (nb + 1, nb, nb + 1, nb)]
+        _check(self._lib.bsp_jac_schur_table(self._h, ctypes.c_int32(8), *(x.ctypes.data_as(_I32P) for x in a)))
+        b = [np.zeros(max(items, 1), dtype=np.int32) for _ in range(3)]
+        _check(self._lib.bsp_jac_schur_table(self._h, ctypes.c_int32(9), *(x.ctypes.data_as(_I32P) for x in b), None))
+        return a[0], a[1][:nb], a[2], a[3][:nb], b[0][:items], b[1][:items], b[2][:items]
+
+    def precondBuild(self, kind, values, colsq=None, d=None):
+        """(minv, status) of the built-in preconditioner `kind` of the reduced system for the entry values [nnz] /
+        [B, nnz] (bsp_jac_schur_precond_build_*): "jacobi" from the column norms colsq [n] / [B, n] (float64),
+        "block_jacobi" from the values; d: the damping vector or None.  status as build()'s."""
+        import torch
+        if kind not in self._KINDS:
+            raise ValueError("precondBuild: kind must be 'jacobi' or 'block_jacobi', got %r" % (kind,))
+        lead = self._lead("precondBuild", values)
+        batched = len(lead) == 1
+        if kind == "jacobi" and (not isinstance(colsq, torch.Tensor) or colsq.dtype != torch.float64
+                                 or tuple(colsq.shape) != lead + (self.n,) or colsq.device != values.device):
+            raise ValueError("precondBuild: colsq must be the float64 column norms %s" % (lead + (self.n,),))
+        if d is not None and self._operand("precondBuild", "d", d, values, lead, self.n) is not None:
+            raise ValueError("precondBuild: d must be [n] or [B, n]")
+        elems = self.precondInfo(kind)["inverse_elems"]
+        minv = torch.empty(lead + (max(elems, 1),), dtype=values.dtype, device=values.device)
+        status = torch.empty(lead + (2,), dtype=torch.int64, device=values.device)
+        need = ctypes.c_int64(0)
+        _check(self._lib.bsp_cgls_work_bytes(self.solver._h, self.product._h, ctypes.c_int64(1), ctypes.byref(need)))
+        nb = values.shape[0] if batched else 1
+        work = torch.empty(need.value * nb + 16, dtype=torch.uint8, device=values.device)
+        mem = self._members
+        if colsq is not None:
+            _ptr_of(colsq)
+        _call(self._lib, "bsp_jac_schur_precond_build_", batched, _suffix(values), self.solver._h, self._h,
+              ctypes.c_int32(self._KINDS[kind]), mem(values, batched), mem(colsq if kind == "jacobi" else None, batched),
+              mem(d, batched), mem(minv, batched), ctypes.c_void_p((work.data_ptr() + 15) // 16 * 16),
+              ctypes.c_void_p(_ptr_of(status)), *((ctypes.c_int32(nb),) if batched else ()))
+        return minv, status
+
+    # ---- the device entries: values [nnz] / [B, nnz]; vectors [rows] / [rows, q] with a leading B for a batch
+    def _lead(self, name, values):
+        import torch
+        if not isinstance(values, torch.Tensor):
+            raise TypeError("%s: values must be a torch.Tensor, got %s" % (name, type(values).__name__))
+        if values.dim() not in (1, 2) or values.shape[-1] != self.nnz:
+            raise ValueError("%s: values must be [%d] or [B, %d], got shape %s"
+                             % (name, self.nnz, self.nnz, tuple(values.shape)))
+        if values.dim() == 2 and values.shape[0] == 0:
+            raise ValueError("%s: empty batch" % name)
+        _ptr_of(values)
+        return tuple(values.shape[:-1])
+
+    def _operand(self, name, what, t, values, lead, rows, optional=False):
+        """checks one operand against `values`; returns q (None: the operand is absent or has no vector axis)"""
+        import torch
+        if t is None:
+            if optional:
+                return None
+            raise ValueError("%s: %s is missing" % (name, what))
+        if not isinstance(t, torch.Tensor) or t.dtype != values.dtype or t.device != values.device:
+            raise TypeError("%s: %s must be a %s tensor on %s" % (name, what, values.dtype, values.device))
+        nl = len(lead)
+        if t.dim() not in (nl + 1, nl + 2) or tuple(t.shape[:nl]) != lead or t.shape[nl] != rows:
+            raise ValueError("%s: %s must be %s[%d] or [%d, q], got shape %s"
+                             % (name, what, "[B, ...] " if nl else "", rows, rows, tuple(t.shape)))
+        _ptr_of(t)
+        if t.dim() == nl + 2 and t.shape[-1] < 1:
+            raise ValueError("%s: %s has no vectors" % (name, what))
+        return int(t.shape[-1]) if t.dim() == nl + 2 else None
+
+    @staticmethod
+    def _members(t, batched):
+        return None if t is None else _ptr_arg(t.unbind(0) if batched else [t], batched)
+
+    def build(self, values, d=None):
+        """(binv, status): the inverses of the diagonal blocks of B = J_e^T J_e + D_e, [inverse_elems] /
+        [B, inverse_elems], block e row-major, and status int64 [2] / [B, 2] = {the caller's scalar of the lowest
+        bad pivot or -1, bad blocks} (bsp_jac_schur_build_*).  d: the damping vector [n] / [B, n] or None.  The
+        blocks are bitwise those of cgls.Preconditioner(product, "block_jacobi", ...); a bad block gets a zero
+        inverse."""
+        import torch
+        lead = self._lead("build", values)
+        batched = len(lead) == 1
+        if d is not None and (self._operand("build", "d", d, values, lead, self.n) is not None):
+            raise ValueError("build: d must be [n] or [B, n]")
+        binv = torch.empty(lead + (max(self.inverse_elems, 1),), dtype=values.dtype, device=values.device)
+        status = torch.empty(lead + (2,), dtype=torch.int64, device=values.device)
+        need = ctypes.c_int64(0)
+        _check(self._lib.bsp_cgls_work_bytes(self.solver._h, self.product._h, ctypes.c_int64(1), ctypes.byref(need)))
+        nb = values.shape[0] if batched else 1
+        work = torch.empty(need.value * nb + 16, dtype=torch.uint8, device=values.device)
+        mem = self._members
+        _call(self._lib, "bsp_jac_schur_build_", batched, _suffix(values), self.solver._h, self._h, mem(values, batched),
+              mem(d, batched), mem(binv, batched), ctypes.c_void_p((work.data_ptr() + 15) // 16 * 16),
+              ctypes.c_void_p(_ptr_of(status)), *((ctypes.c_int32(nb),) if batched else ()))
+        return binv, status
+
+    def _run(self, name, values, binv, rows_out, ins, d=None, state=None, out=None, t=None):
+        """ins: ((what, tensor, rows), ...) in the entry's order, all of one q"""
+        import torch
+        lead = self._lead(name, values)
+        batched = len(lead) == 1
+        if (not isinstance(binv, torch.Tensor) or binv.dtype != values.dtype or binv.device != values.device
+                or tuple(binv.shape) != lead + (max(self.inverse_elems, 1),)):
+            raise ValueError("%s: binv must be what build() returned for these values" % name)
+        _ptr_of(binv)
+        if d is not None and self._operand(name, "d", d, values, lead, self.n) is not None:
+            raise ValueError("%s: d must be [n] or [B, n]" % name)
+        qs = [self._operand(name, what, x, values, lead, rows) for what, x, rows in ins]
+        if any(qi != qs[0] for qi in qs):
+            raise ValueError("%s: the vectors must have one shape [rows] or [rows, q]" % name)
+        q = 1 if qs[0] is None else qs[0]
+        tail = () if qs[0] is None else (q,)
+        out = _EntryMap._alloc_out(name, values, lead + (rows_out,) + tail, out)
+        t = _EntryMap._alloc_out(name + " scratch", values, lead + (self.m, q), t)
+        _ptr_of(out), _ptr_of(t)
+        mem = self._members
+        args = [mem(values, batched), mem(binv, batched)]
+        if name == "mv":
+            args.append(mem(d, batched))
+        args += [mem(x, batched) for _, x, _ in ins] + [mem(t, batched), mem(out, batched)]
+        if name == "mv":
+            if state is not None:
+                if state.dtype != torch.int64 or tuple(state.shape) != lead + (q, 12):
+                    raise ValueError("mv: state must be the int64 records %s of a CgRun" % (lead + (q, 12),))
+                args.append(ctypes.c_void_p(_ptr_of(state)))
+            else:
+                args.append(None)
+        _call(self._lib, "bsp_jac_schur_%s_" % {"backSubstitute": "back"}.get(name, name), batched, _suffix(values),
+              self.solver._h, self._h, ctypes.c_int64(q), *args, *((ctypes.c_int32(values.shape[0]),) if batched else ()))
+        return out
+
+    def mv(self, values, binv, p, d=None, state=None, out=None, t=None):
+        """p [nK] or [nK, q] (leading B when values are batched) -> S p (bsp_jac_schur_mv_*).  d: the damping vector
+        or None; state: the records of a cg.CgRun, whose stopped columns are then left untouched; t: scratch
+        [.., m, q]"""
+        return self._run("mv", values, binv, self.nK, (("p", p, self.nK),), d=d, state=state, out=out, t=t)
+
+    def reduce(self, values, binv, g, out=None, t=None):
+        """g [n] or [n, q], the full right-hand side J^T r + c -> b_k = g_k - F^T B^-1 g_e, [nK] / [nK, q]
+        (bsp_jac_schur_reduce_*)"""
+        return self._run("reduce", values, binv, self.nK, (("g", g, self.n),), out=out, t=t)
+
+    def backSubstitute(self, values, binv, g, xk, out=None, t=None):
+        """x [n] / [n, q] in the caller's order from the reduced solution xk [nK] / [nK, q]: the kept scalars are
+        xk's, the eliminated ones B^-1 (g_e - F x_k) (bsp_jac_schur_back_*)"""
+        return self._run("backSubstitute", values, binv, self.n, (("g", g, self.n), ("xk", xk, self.nK)), out=out, t=t)
 
 
 class SymProduct(_EntryMap):

@@ -71,7 +71,8 @@ class CgRun:
         self.b, self.x, self.r = b, x, r
         self.apply_a, self.precond = apply_a, precond
         self.plain = precond is None
-        self.built_in = isinstance(precond, Preconditioner)
+        # (a preconditioner with a cg_apply(run) of its own, as the reduced system's of sparse.lstsq_cg, is built-in too)
+        self.built_in = isinstance(precond, Preconditioner) or hasattr(precond, "cg_apply")
         self.p = torch.zeros_like(b)
         self.ap = torch.zeros_like(b)
         self.z = torch.zeros_like(b) if self.built_in else None
@@ -106,6 +107,9 @@ class CgRun:
         """z = M^-1 r, rz and beta; returns the tensor that holds z"""
         if self.built_in:
             pc = self.precond
+            if hasattr(pc, "cg_apply"):
+                pc.cg_apply(self)
+                return self.z
             if pc.kind == FSAI:
                 _call(self._lib, "bsp_fsai_apply_", self.batched, self.sfx, self.solver._h, pc.product._h, *self._nq,
                       *self._args("fsai", pc.values, self.r, self.t, self.z), *self._tail, *self._count)

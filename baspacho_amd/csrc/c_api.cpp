@@ -12,6 +12,7 @@
 #include "assembly.h"
 #include "factor_product_plan.h"
 #include "jac_product.h"
+#include "jac_schur.h"
 #include "normal_eq.h"
 #include "sym_product.h"
 #include "reach.h"
@@ -1429,6 +1430,201 @@ BSP_CGLS_ITERATE_API(f32, float)
 BSP_CGLS_API(f64, double)
 BSP_CGLS_API(f32, float)
 #undef BSP_CGLS_API
+// ---- implicit Schur elimination of the matrix-free least squares ----------------
+struct bsp_jac_schur {
+  std::unique_ptr<JacSchurMap> map;
+};
+
+int bsp_jac_schur_create(const bsp_jac_product* p, int64_t num_eliminate, const int64_t* eliminate, bsp_jac_schur** out) {
+  BSP_TRY
+  if (p == nullptr || out == nullptr) throw std::runtime_error("bsp_jac_schur_create: NULL product or output");
+  std::unique_ptr<bsp_jac_schur> h(new bsp_jac_schur);
+  h->map = createJacSchurMap(*p->map, num_eliminate, eliminate);
+  *out = h.release();
+  BSP_CATCH
+}
+void bsp_jac_schur_destroy(bsp_jac_schur* h) { delete h; }
+int bsp_jac_schur_info(const bsp_jac_schur* h, int64_t out[20]) {
+  BSP_TRY
+  if (h == nullptr || out == nullptr) throw std::runtime_error("bsp_jac_schur_info: NULL argument");
+  const JacSchurMap& m = *h->map;
+  const JacBlockPlan& pl = *m.elimBlocks;
+  const int64_t v[20] = {m.nnz,
+                         m.m,
+                         m.n,
+                         m.nK,
+                         m.nE,
+                         m.numElim,
+                         (int64_t)m.freeRows.size(),
+                         m.maxElimWidth,
+                         m.maxGroup,
+                         (int64_t)m.rowsKept.entry.size(),
+                         (int64_t)m.rowsElim.entry.size(),
+                         (int64_t)m.rowsKept.longRuns.size(),
+                         (int64_t)m.rowsElim.longRuns.size(),
+                         (int64_t)m.colsElim.longRuns.size(),
+                         (int64_t)m.colsKept.longRuns.size(),
+                         pl.numItems(),
+                         pl.inverseElems(),
+                         m.deviceBytes(),
+                         pl.deviceBytes(),
+                         (int64_t)m.groupRow.size()};
+  std::copy(v, v + 20, out);
+  BSP_CATCH
+}
+int bsp_jac_schur_table(const bsp_jac_schur* h, int32_t part, int32_t* t0, int32_t* t1, int32_t* t2, int32_t* t3) {
+  BSP_TRY
+  if (h == nullptr) throw std::runtime_error("bsp_jac_schur_table: the map is NULL");
+  const auto put = [](const std::vector<int32_t>& v, int32_t* out) {
+    if (!v.empty() && out == nullptr) throw std::runtime_error("bsp_jac_schur_table: an output array is NULL");
+    std::copy(v.begin(), v.end(), out);
+  };
+  const JacSchurMap& m = *h->map;
+  const JacBlockPlan& pl = *m.elimBlocks;
+  if (part >= 0 && part <= 3) {
+    const RunList& r = part == 0 ? m.rowsKept : part == 1 ? m.rowsElim : part == 2 ? m.colsElim : m.colsKept;
+    put(r.start, t0);
+    put(r.entry, t1);
+    put(r.idx, t2);
+    put(r.longRuns, t3);
+  } else if (part == 4) {
+    put(m.keptScalar, t0);
+    put(m.elimScalar, t1);
+    put(m.elimOff, t2);
+    put(m.elimParam, t3);
+  } else if (part == 5) {
+    put(m.groupStart, t0);
+    put(m.groupRow, t1);
+    put(m.freeRows, t2);
+  } else if (part == 6) {
+    put(pl.blockStart, t0);
+    put(pl.blockWidth, t1);
+    put(pl.itemStart, t2);
+  } else if (part == 7) {
+    put(pl.itemA, t0);
+    put(pl.itemB, t1);
+    put(pl.itemPos, t2);
+  } else if (part == 8) {
+    const JacBlockPlan& kp = jacSchurKeptPlan(m);
+    put(kp.blockStart, t0);
+    put(kp.blockWidth, t1);
+    put(kp.itemStart, t2);
+    put(m.keptParam, t3);
+  } else if (part == 9) {
+    const JacBlockPlan& kp = jacSchurKeptPlan(m);
+    put(kp.itemA, t0);
+    put(kp.itemB, t1);
+    put(kp.itemPos, t2);
+  } else {
+    throw std::runtime_error("bsp_jac_schur_table: unknown part " + std::to_string(part) +
+                             " (0 .. 3: the lists, 4: numberings, 5: groups, 6: blocks, 7: items, 8: kept blocks, 9: "
+                             "kept items)");
+  }
+  BSP_CATCH
+}
+int bsp_jac_schur_precond_info(const bsp_jac_schur* h, int32_t kind, int64_t out[5]) {
+  BSP_TRY
+  if (h == nullptr || out == nullptr) throw std::runtime_error("bsp_jac_schur_precond_info: NULL argument");
+  const JacSchurMap& m = *h->map;
+  if (kind == CgJacobi) {
+    const int64_t v[5] = {m.nK, 0, m.nK, 1, (int64_t)(m.keptScalar.size() * sizeof(int32_t))};
+    std::copy(v, v + 5, out);
+    return 0;
+  }
+  if (kind != CgBlockJacobi) {
+    throw std::runtime_error("bsp_jac_schur_precond_info: unknown kind " + std::to_string(kind) +
+                             " (1: jacobi, 2: block_jacobi)");
+  }
+  const JacBlockPlan& pl = jacSchurKeptPlan(m);
+  const int64_t v[5] = {pl.numBlocks, pl.numItems(), pl.inverseElems(), pl.maxWidth,
+                        pl.deviceBytes() + (int64_t)((m.keptBlockStart.size() + m.keptScalarBlock.size()) * sizeof(int32_t))};
+  std::copy(v, v + 5, out);
+  BSP_CATCH
+}
+template <typename T>
+static void jacSchurRun(bsp_solver* s, const bsp_jac_schur* h, int32_t op, int64_t q, const T* const* v,
+                        const T* const* d, const T* const* binv, const T* const* vec, const T* const* full, T* const* t,
+                        T* const* out, void* work, const int64_t* state, int64_t* status, int32_t batch, bool single,
+                        int32_t kind = 0, const double* const* colsq = nullptr) {
+  if (s == nullptr) throw std::runtime_error("jacobian schur: the solver is NULL");
+  if (h == nullptr) throw std::runtime_error("jacobian schur: the map is NULL");
+  JacSchurArgs<T> a;
+  a.op = op;
+  a.q = q;
+  a.map = h->map.get();
+  a.values = v;
+  a.damp = d;
+  a.binv = binv;
+  a.vec = vec;
+  a.full = full;
+  a.t = t;
+  a.out = out;
+  a.work = work;
+  a.state = const_cast<int64_t*>(state);  // (written by SchurPrecondApply alone, whose entries take it non-const)
+  a.status = status;
+  a.kind = kind;
+  a.colsq = colsq;
+  s->solver->jacSchur<T>(a, batch, single);
+}
+#define BSP_JAC_SCHUR_API(SFX, T)                                                                                \
+  int bsp_jac_schur_build_##SFX(bsp_solver* s, const bsp_jac_schur* h, const T* v, const T* d, T* binv,          \
+                                void* work, int64_t* status)                                                     \
+      BSP_BODY(jacSchurRun<T>(s, h, SchurBuild, 1, &v, one(d), nullptr, nullptr, nullptr, nullptr, &binv, work,  \
+                              nullptr, status, 1, true))                                                         \
+  int bsp_jac_schur_build_batched_##SFX(bsp_solver* s, const bsp_jac_schur* h, const T* const* v,                \
+                                        const T* const* d, T* const* binv, void* work, int64_t* status,          \
+                                        int32_t batch)                                                           \
+      BSP_BODY(jacSchurRun<T>(s, h, SchurBuild, 1, v, d, nullptr, nullptr, nullptr, nullptr, binv, work,         \
+                              nullptr, status, batch, false))                                                    \
+  int bsp_jac_schur_mv_##SFX(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const T* v, const T* binv,        \
+                             const T* d, const T* p, T* t, T* out, const int64_t* state)                         \
+      BSP_BODY(jacSchurRun<T>(s, h, SchurMv, q, &v, one(d), &binv, &p, nullptr, &t, &out, nullptr, state,        \
+                              nullptr, 1, true))                                                                 \
+  int bsp_jac_schur_mv_batched_##SFX(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const T* const* v,        \
+                                     const T* const* binv, const T* const* d, const T* const* p, T* const* t,    \
+                                     T* const* out, const int64_t* state, int32_t batch)                         \
+      BSP_BODY(jacSchurRun<T>(s, h, SchurMv, q, v, d, binv, p, nullptr, t, out, nullptr, state, nullptr, batch,  \
+                              false))                                                                            \
+  int bsp_jac_schur_reduce_##SFX(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const T* v, const T* binv,    \
+                                 const T* g, T* t, T* out)                                                       \
+      BSP_BODY(jacSchurRun<T>(s, h, SchurReduce, q, &v, nullptr, &binv, nullptr, &g, &t, &out, nullptr, nullptr, \
+                              nullptr, 1, true))                                                                 \
+  int bsp_jac_schur_reduce_batched_##SFX(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const T* const* v,    \
+                                         const T* const* binv, const T* const* g, T* const* t, T* const* out,    \
+                                         int32_t batch)                                                          \
+      BSP_BODY(jacSchurRun<T>(s, h, SchurReduce, q, v, nullptr, binv, nullptr, g, t, out, nullptr, nullptr,      \
+                              nullptr, batch, false))                                                            \
+  int bsp_jac_schur_back_##SFX(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const T* v, const T* binv,      \
+                               const T* g, const T* xk, T* t, T* out)                                            \
+      BSP_BODY(jacSchurRun<T>(s, h, SchurBack, q, &v, nullptr, &binv, &xk, &g, &t, &out, nullptr, nullptr,       \
+                              nullptr, 1, true))                                                                 \
+  int bsp_jac_schur_back_batched_##SFX(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const T* const* v,      \
+                                       const T* const* binv, const T* const* g, const T* const* xk, T* const* t, \
+                                       T* const* out, int32_t batch)                                             \
+      BSP_BODY(jacSchurRun<T>(s, h, SchurBack, q, v, nullptr, binv, xk, g, t, out, nullptr, nullptr, nullptr,    \
+                              batch, false))                                                                     \
+  int bsp_jac_schur_precond_build_##SFX(bsp_solver* s, const bsp_jac_schur* h, int32_t kind, const T* v,         \
+                                        const double* colsq, const T* d, T* minv, void* work, int64_t* status)   \
+      BSP_BODY(jacSchurRun<T>(s, h, SchurPrecondBuild, 1, one(v), one(d), nullptr, nullptr, nullptr, nullptr,    \
+                              &minv, work, nullptr, status, 1, true, kind, one(colsq)))                          \
+  int bsp_jac_schur_precond_build_batched_##SFX(bsp_solver* s, const bsp_jac_schur* h, int32_t kind,             \
+                                                const T* const* v, const double* const* colsq,                   \
+                                                const T* const* d, T* const* minv, void* work, int64_t* status,  \
+                                                int32_t batch)                                                   \
+      BSP_BODY(jacSchurRun<T>(s, h, SchurPrecondBuild, 1, v, d, nullptr, nullptr, nullptr, nullptr, minv, work,  \
+                              nullptr, status, batch, false, kind, colsq))                                       \
+  int bsp_jac_schur_precond_apply_##SFX(bsp_solver* s, const bsp_jac_schur* h, int32_t kind, int64_t q,          \
+                                        const T* minv, const T* r, T* z, void* work, int64_t* state)             \
+      BSP_BODY(jacSchurRun<T>(s, h, SchurPrecondApply, q, nullptr, nullptr, &minv, &r, nullptr, nullptr, &z,     \
+                              work, state, nullptr, 1, true, kind))                                              \
+  int bsp_jac_schur_precond_apply_batched_##SFX(bsp_solver* s, const bsp_jac_schur* h, int32_t kind, int64_t q,  \
+                                                const T* const* minv, const T* const* r, T* const* z,            \
+                                                void* work, int64_t* state, int32_t batch)                       \
+      BSP_BODY(jacSchurRun<T>(s, h, SchurPrecondApply, q, nullptr, nullptr, minv, r, nullptr, nullptr, z, work,  \
+                              state, nullptr, batch, false, kind))
+BSP_JAC_SCHUR_API(f64, double)
+BSP_JAC_SCHUR_API(f32, float)
+#undef BSP_JAC_SCHUR_API
 #undef BSP_CC
 #undef BSP_CD
 // ---- the Lanczos recurrence -----------------------------------------------------

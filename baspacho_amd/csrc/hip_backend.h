@@ -350,6 +350,48 @@ inline int64_t cglsWorkBytes(int64_t m, int64_t n, int64_t q) {
 template <typename T>
 void hipBackendCgls(SymbolicCtx& sym, const CglsArgs<T>& a, int64_t batch, bool single);
 
+// Implicit Schur elimination of the matrix-free least squares (hip_schur_kernels.h): one
+// piece on `batch` Jacobians of one structure over a JacSchurMap.  Kept vectors are [nK, q], full ones [n, q], t
+// [m, q] is scratch of the caller's; the work area and the status of SchurBuild are those of CglsBuild
+// (cglsWorkBytes(m, n, 1) per member).  An operand that may be absent is NULL.
+//   SchurBuild:   values, damp = d [n] (may be absent); binv = the inverses of the blocks of B; work, status
+//   SchurMv:      values, binv, damp = d (may be absent), vec = p; t; out = S p; state (may be NULL): the
+//                 records of a conjugate gradient, whose stopped columns are skipped
+//   SchurReduce:  values, binv, full = g; t; out = b_k
+//   SchurBack:    values, binv, full = g, vec = x_k; t; out = x [n, q] in the caller's order
+//   SchurPrecondBuild:  kind 1 / 2 (CgPrecondKind) of the preconditioner of S on the kept scalars: colsq [n] (kind
+//                 1), values (kind 2), damp = d (may be absent); out = its values; work, status as SchurBuild
+//   SchurPrecondApply:  CgPrecond of the conjugate gradient on the kept scalars with that preconditioner: binv =
+//                 its values, vec = r, out = z; work (cgWorkBytes(nK, q) per member) and state are the iteration's
+struct JacSchurMap;
+enum SchurOp : int32_t {
+  SchurBuild = 0,
+  SchurMv = 1,
+  SchurReduce = 2,
+  SchurBack = 3,
+  SchurPrecondBuild = 4,
+  SchurPrecondApply = 5
+};
+template <typename T>
+struct JacSchurArgs {
+  int32_t op = SchurBuild, kind = 0;
+  int64_t q = 1;
+  const JacSchurMap* map = nullptr;
+  const T* const* values = nullptr;
+  const T* const* damp = nullptr;
+  const T* const* binv = nullptr;
+  const T* const* vec = nullptr;
+  const T* const* full = nullptr;
+  T* const* t = nullptr;
+  T* const* out = nullptr;
+  const double* const* colsq = nullptr;
+  void* work = nullptr;
+  int64_t* state = nullptr;  // (only SchurPrecondApply writes it)
+  int64_t* status = nullptr;
+};
+template <typename T>
+void hipBackendJacSchur(SymbolicCtx& sym, const JacSchurArgs<T>& a, int64_t batch, bool single);
+
 // The Lanczos recurrence (hip_lanczos_kernels.h): one piece of a step on `batch`
 // matrices with q start vectors each.  Vectors are [n, q] row-major; slot s of a member's basis is the
 // vector at basis + s slotStride; state holds 12 words and coef 2 kmax doubles per (matrix, start vector);

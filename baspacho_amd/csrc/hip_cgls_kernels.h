@@ -345,9 +345,11 @@ __global__ void __launch_bounds__(kRedThreads)
   work.bad()[i] = ok ? -1 : 0;
 }
 
-// the item tables of a JacBlockPlan on the device; the block tables are a CgPrecondDev's
+// the item tables of a JacBlockPlan on the device; the block tables are a CgPrecondDev's.  blockWidth: the
+// widths of a plan over a subset of the params (block b starts at blockStart[b]), NULL for one over all of them
 struct CglsBlockItems {
   const int32_t *itemStart, *itemA, *itemB, *itemPos;
+  const int32_t* blockWidth = nullptr;
 };
 
 // Block-Jacobi, one wave per block, all in double in LDS: G_ab = the block's items (a >= b) added in list
@@ -364,7 +366,7 @@ __global__ void __launch_bounds__(kCgBuildThreads)
   const int lane = threadIdx.x;
   const int64_t b = blockIdx.x;
   const int32_t s0 = pl.blockStart[b];
-  const int w = pl.blockStart[b + 1] - s0;
+  const int w = it.blockWidth != nullptr ? it.blockWidth[b] : pl.blockStart[b + 1] - s0;
   const GP<const T> v = pickData(vref);
   const GP<T> out = pickData(mref) + pl.blockOff[b];
   for (int e = lane; e < w * w; e += kCgBuildThreads) {

@@ -14,10 +14,12 @@
 #include "hip_norm_est_kernels.h"
 #include "hip_ordered_sum.h"
 #include "hip_reach_kernels.h"
+#include "hip_schur_kernels.h"
 #include "hip_selinv_adjoint_kernels.h"
 #include "hip_selinv_kernels.h"
 #include "hip_status_kernels.h"
 #include "jac_product.h"
+#include "jac_schur.h"
 #include "normal_eq.h"
 #include "sym_product.h"
 
@@ -1289,6 +1291,144 @@ void hipBackendCgls(SymbolicCtx& sym, const CglsArgs<T>& a, int64_t batch, bool 
   });
 }
 
+// ---- implicit Schur elimination (hip_schur_kernels.h) ----------------------------
+// one piece (SchurOp) on `batch` Jacobians: one or two launches per chunk, nothing allocated but the tables
+// of the map, each uploaded by the first call that needs it
+static_assert(hipk::kSchurMaxW == kSchurMaxElimWidth, "the group kernel's registers hold the widest eliminated param");
+template <typename T>
+void hipBackendJacSchur(SymbolicCtx& sym, const JacSchurArgs<T>& a, int64_t batch, bool single) {
+  using In = hipk::DataRef<const T>;
+  HipSymbolicCtx& h = hipCtx(sym);
+  const hipStream_t stream = h.stream;
+  h.checkDevice();
+  const JacSchurMap& map = *a.map;
+  const int64_t m = map.m, n = map.n, q = a.q;
+  BASPACHO_CHECK_LT(q, (int64_t)INT32_MAX);
+  HipEntryMapDev& d = HipEntryMapDev::of(map.dev);
+  const JacBlockPlan& plan = *map.elimBlocks;
+  const BatchPtrs<const T> vs = h.stage(a.values, batch, single), ds = h.stage(a.damp, batch, single);
+  const BatchPtrs<const T> bs = h.stage(a.binv, batch, single), ws = h.stage(a.vec, batch, single);
+  const BatchPtrs<const T> gs = h.stage(a.full, batch, single);
+  const BatchPtrs<T> ts = h.stage(a.t, batch, single), os = h.stage(a.out, batch, single);
+  if (a.op == SchurBuild) {
+    const int64_t stride = cglsWorkBytes(m, n, 1), badOff = cglsBadOffset(m, n, 1);
+    const hipk::CgPrecondDev pl{d.get(plan.blockStart), d.get(plan.blockOff), d.get(plan.scalarBlock), nullptr, nullptr,
+                                nullptr};
+    const hipk::CglsBlockItems items{d.get(plan.itemStart), d.get(plan.itemA), d.get(plan.itemB), d.get(plan.itemPos),
+                                     d.get(plan.blockWidth)};
+    // (the output of the build is a.out: the inverses)
+    h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+      const hipk::CgWork w{static_cast<char*>(a.work) + q0 * stride, stride, badOff};
+      hipk::cglsBlockBuild<T><<<dim3((unsigned)plan.numBlocks, nm), hipk::kCgBuildThreads, 0, stream>>>(
+          pl, items, vs.at(q0), ds.at(q0), os.at(q0), w);
+      hipk::cgPrecondStatus<<<dim3(1, nm), hipk::kRedThreads, 0, stream>>>(plan.numBlocks, pl, w, a.status + 2 * q0);
+    });
+    return;
+  }
+  if (a.op == SchurPrecondBuild) {
+    const int64_t stride = cglsWorkBytes(m, n, 1), badOff = cglsBadOffset(m, n, 1);
+    const BatchPtrs<const double> cs = h.stage(a.colsq, batch, single);
+    const int32_t* keptScalar = d.get(map.keptScalar);
+    hipk::CgPrecondDev pl{keptScalar, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipk::CglsBlockItems items{};
+    int64_t numBlocks = map.nK;
+    if (a.kind == CgBlockJacobi) {
+      const JacBlockPlan& kp = jacSchurKeptPlan(map);
+      pl = {d.get(kp.blockStart), d.get(kp.blockOff), d.get(kp.scalarBlock), nullptr, nullptr, nullptr};
+      items = {d.get(kp.itemStart), d.get(kp.itemA), d.get(kp.itemB), d.get(kp.itemPos), d.get(kp.blockWidth)};
+      numBlocks = kp.numBlocks;
+    }
+    h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+      const hipk::CgWork w{static_cast<char*>(a.work) + q0 * stride, stride, badOff};
+      if (a.kind == CgBlockJacobi) {
+        hipk::cglsBlockBuild<T><<<dim3((unsigned)numBlocks, nm), hipk::kCgBuildThreads, 0, stream>>>(
+            pl, items, vs.at(q0), ds.at(q0), os.at(q0), w);
+      } else {
+        const unsigned wgs = (unsigned)((map.nK + hipk::kRedThreads - 1) / hipk::kRedThreads);
+        hipk::schurJacobiBuild<T><<<dim3(wgs, nm), hipk::kRedThreads, 0, stream>>>(map.nK, keptScalar, cs.at(q0),
+                                                                                  ds.at(q0), os.at(q0), w);
+      }
+      hipk::cgPrecondStatus<<<dim3(1, nm), hipk::kRedThreads, 0, stream>>>(numBlocks, pl, w, a.status + 2 * q0);
+    });
+    return;
+  }
+  if (a.op == SchurPrecondApply) {
+    const int64_t nK = map.nK, nParts = (nK + hipk::kRedChunk - 1) / hipk::kRedChunk;
+    BASPACHO_CHECK_LT(nParts * q, (int64_t)INT32_MAX);
+    const int64_t stride = cgWorkBytes(nK, q), badOff = cgBadOffset(nK, q);
+    hipk::CgPrecondDev pl{};
+    if (a.kind == CgBlockJacobi) {
+      const JacBlockPlan& kp = jacSchurKeptPlan(map);
+      pl = {d.get(map.keptBlockStart), d.get(kp.blockOff), d.get(map.keptScalarBlock), nullptr, nullptr, nullptr};
+    }
+    h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+      const hipk::CgWork w{static_cast<char*>(a.work) + q0 * stride, stride, badOff};
+      hipk::CgState* st = reinterpret_cast<hipk::CgState*>(a.state) + q0 * q;
+      const dim3 perChunk((unsigned)(nParts * q), nm);
+      if (a.kind == CgBlockJacobi) {
+        hipk::cgPrecond<T, 2><<<perChunk, hipk::kRedThreads, 0, stream>>>(nK, (int32_t)q, (int32_t)nParts, pl, bs.at(q0),
+                                                                         ws.at(q0), os.at(q0), w, st);
+      } else {
+        hipk::cgPrecond<T, 1><<<perChunk, hipk::kRedThreads, 0, stream>>>(nK, (int32_t)q, (int32_t)nParts, pl, bs.at(q0),
+                                                                         ws.at(q0), os.at(q0), w, st);
+      }
+      hipk::cgFold<<<dim3((unsigned)q, nm), hipk::kRedThreads, 0, stream>>>((int32_t)q, (int32_t)nParts, hipk::CgFoldBeta,
+                                                                          false, 0.0, 0, w, st);
+    });
+    return;
+  }
+  const hipk::SchurDev sd{map.numElim,
+                          (int64_t)map.freeRows.size(),
+                          map.nK,
+                          d.get(map.groupStart),
+                          d.get(map.groupRow),
+                          d.get(map.freeRows),
+                          d.get(map.elimOff),
+                          d.get(map.elimScalar),
+                          d.get(map.keptScalar),
+                          d.get(plan.blockOff),
+                          d.get(map.rowsKept.start),
+                          d.get(map.rowsKept.entry),
+                          d.get(map.rowsKept.idx),
+                          d.get(map.rowsElim.start),
+                          d.get(map.rowsElim.entry),
+                          d.get(map.rowsElim.idx),
+                          d.get(map.colsElim.start),
+                          d.get(map.colsElim.entry),
+                          d.get(map.colsElim.idx)};
+  const int64_t units = map.numElim + (int64_t)map.freeRows.size() + (a.op == SchurBack ? map.nK : 0);
+  const int64_t groupWgs = (units * q + hipk::kAsmThreads - 1) / hipk::kAsmThreads;
+  BASPACHO_CHECK_LT(groupWgs, (int64_t)INT32_MAX);
+  const RunLaunch<int32_t> l = runLaunch(d, map.colsKept, q, true);
+  const hipk::CglsRuns cols{l.numRuns, l.longWaves, (int32_t)l.shortWgs, l.start, l.longRuns, l.entry, l.idx};
+  const int32_t* keptScalar = d.get(map.keptScalar);
+  h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+    const hipk::CgState* st = a.state ? reinterpret_cast<const hipk::CgState*>(a.state) + q0 * q : nullptr;
+    const dim3 groupGrid((unsigned)groupWgs, nm), colGrid((unsigned)(l.shortWgs + l.longWgs), nm);
+    const In tIn{ts.at(q0).single, (const T* const*)ts.at(q0).many};
+    switch (a.op) {
+      case SchurMv:
+        hipk::schurGroups<T, hipk::SchurProduct><<<groupGrid, hipk::kAsmThreads, 0, stream>>>(
+            sd, (int32_t)q, vs.at(q0), bs.at(q0), ws.at(q0), In{}, ts.at(q0), os.at(q0), st);
+        hipk::schurKeptColumns<T, hipk::SchurProduct><<<colGrid, hipk::kAsmThreads, 0, stream>>>(
+            cols, keptScalar, (int32_t)q, vs.at(q0), tIn, ds.at(q0), ws.at(q0), os.at(q0), st);
+        break;
+      case SchurReduce:
+        hipk::schurGroups<T, hipk::SchurReduce><<<groupGrid, hipk::kAsmThreads, 0, stream>>>(
+            sd, (int32_t)q, vs.at(q0), bs.at(q0), In{}, gs.at(q0), ts.at(q0), os.at(q0), nullptr);
+        hipk::schurKeptColumns<T, hipk::SchurReduce><<<colGrid, hipk::kAsmThreads, 0, stream>>>(
+            cols, keptScalar, (int32_t)q, vs.at(q0), tIn, In{}, gs.at(q0), os.at(q0), nullptr);
+        break;
+      case SchurBack:
+        hipk::schurGroups<T, hipk::SchurBack><<<groupGrid, hipk::kAsmThreads, 0, stream>>>(
+            sd, (int32_t)q, vs.at(q0), bs.at(q0), ws.at(q0), gs.at(q0), ts.at(q0), os.at(q0), nullptr);
+        break;
+      default:
+        throw std::runtime_error("jacobian schur: unknown operation " + std::to_string(a.op));
+    }
+  });
+}
+
 // ---- the Lanczos recurrence (hip_lanczos_kernels.h) ------------------------------
 // one piece of a step (LanczosOp) on `batch` matrices: one to three launches per chunk, nothing allocated
 template <typename T>
@@ -1566,6 +1706,7 @@ void hipBackendFactorProduct(SymbolicCtx& sym, const T* const* L, bool transpose
                                          int64_t, bool);                                                        \
   template void hipBackendCg<T>(SymbolicCtx&, const CgArgs<T>&, int64_t, bool);                                 \
   template void hipBackendCgls<T>(SymbolicCtx&, const CglsArgs<T>&, int64_t, bool);                             \
+  template void hipBackendJacSchur<T>(SymbolicCtx&, const JacSchurArgs<T>&, int64_t, bool);                     \
   template void hipBackendLanczos<T>(SymbolicCtx&, const LanczosArgs<T>&, int64_t, bool);                       \
   template void hipBackendKrylovCombine<T>(SymbolicCtx&, const KrylovCombineArgs<T>&, int64_t, bool);           \
   template void hipBackendReachSolveL<T>(SymbolicCtx&, const ReachPlan&, const T*, T*);                         \

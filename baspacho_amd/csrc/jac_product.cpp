@@ -41,6 +41,8 @@ void checkJacBlockItems(int64_t items) {
   }
 }
 
+static void fillJacBlockItems(const JacobianProductMap& map, JacBlockPlan* p);
+
 std::unique_ptr<JacBlockPlan> createJacBlockPlan(const JacobianProductMap& map, const std::vector<int64_t>& blockSizes) {
   std::unique_ptr<JacBlockPlan> p(new JacBlockPlan);
   p->n = map.n;
@@ -71,22 +73,32 @@ std::unique_ptr<JacBlockPlan> createJacBlockPlan(const JacobianProductMap& map, 
     p->blockOff[b + 1] = p->blockOff[b] + w * w;
     std::fill(p->scalarBlock.begin() + p->blockStart[b], p->scalarBlock.begin() + p->blockStart[b + 1], (int32_t)b);
   }
+  fillJacBlockItems(map, p.get());
+  return p;
+}
+
+// the items of a plan whose block tables (blockStart, blockOff, scalarBlock; -1: a scalar of no block) stand
+static void fillJacBlockItems(const JacobianProductMap& map, JacBlockPlan* p) {
   // the positions of the row lists (row by row, ascending entry index inside a row), stably by the block of
   // their column: block by block, ascending row inside a block
   const RunList& rl = map.rows;
   std::vector<int32_t> rowOfPos(map.nnz);
   for (int64_t i = 0; i < map.m; i++) std::fill(rowOfPos.begin() + rl.start[i], rowOfPos.begin() + rl.start[i + 1], (int32_t)i);
-  std::vector<int32_t> ids(map.nnz), byBlock;
-  std::iota(ids.begin(), ids.end(), 0);
   const int32_t* blk = p->scalarBlock.data();
   const int32_t* col = rl.idx.data();
+  std::vector<int32_t> ids, byBlock;
+  ids.reserve(map.nnz);
+  for (int64_t x = 0; x < map.nnz; x++) {
+    if (blk[col[x]] >= 0) ids.push_back((int32_t)x);
+  }
+  const int64_t taken = (int64_t)ids.size();
   countingSort(ids, byBlock, p->numBlocks, [blk, col](int32_t x) { return blk[col[x]]; });
   // a group: the positions of one (block, row); c of them give c (c + 1) / 2 items
   const auto sameGroup = [&](int64_t x, int64_t y) {
     return blk[col[byBlock[x]]] == blk[col[byBlock[y]]] && rowOfPos[byBlock[x]] == rowOfPos[byBlock[y]];
   };
   int64_t items = 0;
-  for (int64_t x = 0, g0 = 0; x < map.nnz; x++) {
+  for (int64_t x = 0, g0 = 0; x < taken; x++) {
     if (!sameGroup(g0, x)) g0 = x;
     items += x - g0 + 1;
   }
@@ -95,9 +107,10 @@ std::unique_ptr<JacBlockPlan> createJacBlockPlan(const JacobianProductMap& map, 
   p->itemA.reserve(items);
   p->itemB.reserve(items);
   p->itemPos.reserve(items);
-  for (int64_t x = 0, g0 = 0; x < map.nnz; x++) {
+  for (int64_t x = 0, g0 = 0; x < taken; x++) {
     if (!sameGroup(g0, x)) g0 = x;
-    const int32_t b = blk[col[byBlock[x]]], s = p->blockStart[b], w = p->blockStart[b + 1] - s;
+    const int32_t b = blk[col[byBlock[x]]], s = p->blockStart[b];
+    const int32_t w = p->blockWidth.empty() ? p->blockStart[b + 1] - s : p->blockWidth[b];
     p->itemStart[b + 1] += (int32_t)(x - g0 + 1);
     for (int64_t y = g0; y <= x; y++) {
       int32_t px = byBlock[x], py = byBlock[y];
@@ -108,6 +121,30 @@ std::unique_ptr<JacBlockPlan> createJacBlockPlan(const JacobianProductMap& map, 
     }
   }
   for (int64_t b = 0; b < p->numBlocks; b++) p->itemStart[b + 1] += p->itemStart[b];
+}
+
+std::unique_ptr<JacBlockPlan> createJacBlockPlanOn(const JacobianProductMap& map, const std::vector<int32_t>& first,
+                                                   const std::vector<int32_t>& width) {
+  std::unique_ptr<JacBlockPlan> p(new JacBlockPlan);
+  p->n = map.n;
+  p->numBlocks = (int64_t)first.size();
+  p->blockStart = first;
+  p->blockStart.push_back((int32_t)map.n);
+  p->blockWidth = width;
+  p->scalarBlock.assign(map.n, -1);
+  p->blockOff.assign(p->numBlocks + 1, 0);
+  for (int64_t b = 0; b < p->numBlocks; b++) {
+    const int64_t w = width[b];
+    if (w > kCgMaxBlockWidth) {
+      throw std::runtime_error("jacobian product: the block at scalar " + std::to_string(first[b]) + " has " +
+                               std::to_string(w) + " scalars; block_jacobi takes blocks of at most " +
+                               std::to_string(kCgMaxBlockWidth));
+    }
+    p->maxWidth = std::max(p->maxWidth, w);
+    p->blockOff[b + 1] = p->blockOff[b] + w * w;
+    std::fill(p->scalarBlock.begin() + first[b], p->scalarBlock.begin() + first[b] + w, (int32_t)b);
+  }
+  fillJacBlockItems(map, p.get());
   return p;
 }
 

@@ -27,14 +27,18 @@ namespace BaSpaCho {
 // cols[itemB], at itemPos = (cols[itemA] - s) w + (cols[itemB] - s), s the block's first scalar and w its
 // width.  They come in ascending Jacobian row; inside a row the entries x of the block in ascending entry
 // index, each paired with the entries up to and including itself.
+// A plan over a subset of the params (createJacBlockPlanOn; jac_schur.h) has blockWidth: block b then holds the
+// scalars [blockStart[b], blockStart[b] + blockWidth[b]), blockStart[numBlocks] = n, and scalarBlock is -1 outside
+// the subset.  blockWidth is empty for a plan over all params.
 struct JacBlockPlan {
   int64_t n = 0, numBlocks = 0, maxWidth = 0;
-  std::vector<int32_t> blockStart, scalarBlock, itemStart, itemA, itemB, itemPos;
+  std::vector<int32_t> blockStart, blockWidth, scalarBlock, itemStart, itemA, itemB, itemPos;
   std::vector<int64_t> blockOff;
   int64_t inverseElems() const { return blockOff.empty() ? 0 : blockOff.back(); }
   int64_t numItems() const { return (int64_t)itemA.size(); }
   int64_t deviceBytes() const {
-    return (int64_t)((blockStart.size() + scalarBlock.size() + itemStart.size() + 3 * itemA.size()) * sizeof(int32_t) +
+    return (int64_t)((blockStart.size() + blockWidth.size() + scalarBlock.size() + itemStart.size() + 3 * itemA.size()) *
+                         sizeof(int32_t) +
                      blockOff.size() * sizeof(int64_t));
   }
 };
@@ -64,6 +68,10 @@ void checkJacBlockItems(int64_t items);
 // The plan over blocks of `blockSizes` scalars in the caller's order.  Throws for a block wider than
 // kCgMaxBlockWidth, naming it.  Host only: stable counting sorts.
 std::unique_ptr<JacBlockPlan> createJacBlockPlan(const JacobianProductMap& map, const std::vector<int64_t>& blockSizes);
+// The plan over the blocks [first[b], first[b] + width[b]) alone, ascending and disjoint (the caller's check):
+// the items of the other scalars are left out.  `maxWidth`: the widest block taken, named in the refusal.
+std::unique_ptr<JacBlockPlan> createJacBlockPlanOn(const JacobianProductMap& map, const std::vector<int32_t>& first,
+                                                   const std::vector<int32_t>& width);
 // ... of the map's solver (its params), cached in the map
 const JacBlockPlan& jacBlockPlan(const JacobianProductMap& map);
 

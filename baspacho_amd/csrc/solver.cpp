@@ -15,6 +15,7 @@
 
 #include "assembly.h"
 #include "jac_product.h"
+#include "jac_schur.h"
 #include "normal_eq.h"
 #include "reach.h"
 #include "sym_product.h"
@@ -1433,6 +1434,79 @@ void Solver::cgls(const CglsArgs<T>& a, int64_t batch, bool single) const {
   hipBackendCgls<T>(*symCtx, a, batch, single);
 }
 
+// ---- implicit Schur elimination of the matrix-free least squares --------------
+template <typename T>
+void Solver::jacSchur(const JacSchurArgs<T>& a, int64_t batch, bool single) const {
+  static const char* names[6] = {"schurBuild", "schurMv", "schurReduce", "schurBack", "schurPrecondBuild",
+                                 "schurPrecondApply"};
+  if (a.op < 0 || a.op > SchurPrecondApply) throw std::runtime_error("jacobian schur: unknown operation " + std::to_string(a.op));
+  const std::string what = names[a.op];
+  const auto fail = [&](const std::string& m) { throw std::runtime_error(what + ": " + m); };
+  if (a.map == nullptr) fail("the map is NULL");
+  if (a.map->product->solver != this) fail("the map was built on another solver");
+  if (batch < 1) fail("the batch is empty");
+  const std::string fault = badVectorCount(a.q);
+  if (!fault.empty()) fail(fault);
+  const int64_t m = a.map->m, n = a.map->n, nK = a.map->nK, q = a.q;
+  if ((m + n) * q >= (int64_t(1) << 40)) fail("(m + n) q = " + std::to_string((m + n) * q) + " is too large");
+  const bool precond = a.op == SchurPrecondBuild || a.op == SchurPrecondApply;
+  if (precond && a.kind != CgJacobi && a.kind != CgBlockJacobi) {
+    fail("unknown preconditioner kind " + std::to_string(a.kind) + " (1: jacobi, 2: block_jacobi)");
+  }
+  if (a.op == SchurBuild || precond) {
+    if (a.work == nullptr) fail("the workspace pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(a.work) % 16 != 0) fail("the workspace is not 16-byte aligned");
+    if (a.op != SchurPrecondApply && a.status == nullptr) fail("the status pointer is NULL");
+    if (a.op == SchurPrecondApply && a.state == nullptr) fail("the state pointer is NULL");
+  }
+  const int64_t pinv = !precond ? 0 : a.kind == CgBlockJacobi ? jacSchurKeptPlan(*a.map).inverseElems() : nK;
+  struct Slot {
+    const char* name;
+    const void* const* ptrs;
+    int64_t elems;
+    bool optional;
+  };
+  const auto p = [](auto ptrs) { return reinterpret_cast<const void* const*>(ptrs); };
+  const int64_t inv = a.map->elimBlocks->inverseElems(), nnz = a.map->nnz;
+  std::vector<Slot> slots;
+  switch (a.op) {
+    case SchurBuild:
+      slots = {{"values", p(a.values), nnz, false}, {"d", p(a.damp), n, true}, {"inverses", p(a.out), inv, false}};
+      break;
+    case SchurMv:
+      slots = {{"values", p(a.values), nnz, false}, {"inverses", p(a.binv), inv, false}, {"d", p(a.damp), n, true},
+               {"p", p(a.vec), nK * q, false},      {"t", p(a.t), m * q, false},         {"output", p(a.out), nK * q, false}};
+      break;
+    case SchurReduce:
+      slots = {{"values", p(a.values), nnz, false}, {"inverses", p(a.binv), inv, false}, {"g", p(a.full), n * q, false},
+               {"t", p(a.t), m * q, false},         {"output", p(a.out), nK * q, false}};
+      break;
+    case SchurBack:
+      slots = {{"values", p(a.values), nnz, false}, {"inverses", p(a.binv), inv, false}, {"g", p(a.full), n * q, false},
+               {"x_k", p(a.vec), nK * q, false},    {"t", p(a.t), m * q, false},         {"output", p(a.out), n * q, false}};
+      break;
+    case SchurPrecondBuild:
+      slots = {{"values", p(a.values), nnz, a.kind == CgJacobi}, {"colsq", p(a.colsq), n, a.kind != CgJacobi},
+               {"d", p(a.damp), n, true}, {"preconditioner", p(a.out), pinv, false}};
+      break;
+    default:
+      slots = {{"preconditioner", p(a.binv), pinv, false}, {"r", p(a.vec), nK * q, false}, {"z", p(a.out), nK * q, false}};
+      break;
+  }
+  for (const Slot& s : slots) {
+    if (s.ptrs == nullptr) {  // (an operand without elements may be NULL altogether)
+      if (!s.optional && s.elems > 0) fail(std::string("the ") + s.name + " pointers are NULL");
+      continue;
+    }
+    for (int64_t b = 0; b < batch; b++) {
+      if (s.ptrs[b] == nullptr && s.elems > 0) {
+        fail(std::string("the ") + s.name + " pointer of batch member " + std::to_string(b) + " is NULL");
+      }
+    }
+  }
+  hipBackendJacSchur<T>(*symCtx, a, batch, single);
+}
+
 // ---- the Lanczos recurrence ---------------------------------------------------
 static void checkLanczosSizes(const std::string& what, int64_t n, int64_t q, int64_t kmax) {
   const auto fail = [&](const std::string& m) { throw std::runtime_error(what + ": " + m); };
@@ -1704,6 +1778,7 @@ void Solver::mulLt(const std::vector<T*>& L, const std::vector<T*>& x, int64_t i
   template void Solver::invNorm1Estimate<T>(BspCVec_##T, BspCVec_##T, void*, int64_t*, double*, bool) const;   \
   template void Solver::cg<T>(const CgArgs<T>&, int64_t, bool) const;                                          \
   template void Solver::cgls<T>(const CglsArgs<T>&, int64_t, bool) const;                                      \
+  template void Solver::jacSchur<T>(const JacSchurArgs<T>&, int64_t, bool) const;                              \
   template void Solver::lanczos<T>(const LanczosArgs<T>&, int64_t, bool) const;                                \
   template void Solver::krylovCombine<T>(const KrylovCombineArgs<T>&, int64_t, bool) const;                    \
   template void Solver::reachSolveL<T>(const T*, const std::vector<int64_t>&, T*) const;                       \

@@ -19,11 +19,14 @@ namespace BaSpaCho {
 struct AssemblyMap;
 struct NormalEqMap;
 struct JacobianProductMap;
+struct JacSchurMap;
 struct SymProductMap;
 template <typename T>
 struct CgArgs;
 template <typename T>
 struct CglsArgs;
+template <typename T>
+struct JacSchurArgs;
 template <typename T>
 struct LanczosArgs;
 template <typename T>
@@ -320,6 +323,15 @@ class Solver {
   int64_t cglsWorkBytes(int64_t m, int64_t n, int64_t q) const;
   template <typename T>
   void cgls(const CglsArgs<T>& a, int64_t batch, bool single) const;
+  // extension: the pieces of the implicit Schur elimination of the matrix-free least squares (DESIGN.md section
+  // 29; hip_schur_kernels.h) over a JacSchurMap (jac_schur.h) of a JacobianProductMap of this Solver.  `a`
+  // (JacSchurArgs, hip_backend.h) names the piece (SchurOp) and its operands, one pointer per batch member;
+  // `work` (cglsWorkBytes(m, n, 1) per member, 16-byte aligned) and `status` as for cgls()'s build.  Runs on the
+  // stream of setStream(), nothing is allocated (the first use of a part of the map uploads it) and nothing read
+  // back.  Refused before any device work: an empty batch, q out of range, a NULL or misaligned workspace, a
+  // NULL pointer of an operand the piece needs, a map of another Solver.
+  template <typename T>
+  void jacSchur(const JacSchurArgs<T>& a, int64_t batch, bool single) const;
   // extension: the pieces of the Lanczos recurrence on the device (DESIGN.md section 25;
   // hip_lanczos_kernels.h).  `a` (LanczosArgs, hip_backend.h) names the piece (LanczosOp) and its operands:
   // the vector [n, q] row-major and the basis (slot s at basis + s slotStride elements, `slots` of them), one

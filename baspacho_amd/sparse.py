@@ -92,11 +92,11 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import Settings, SparseStructure, create_solver, _call, _count, _ptr_arg, _suffix
+from . import Settings, SparseStructure, create_solver, _call, _count, _ptr_arg, _ptr_of, _suffix
 from . import autograd as _ag
 from .autograd import _OnCurrentStream
 
-__all__ = ["SymmetricPattern", "JacobianPattern", "assemble", "solve", "logdet", "solve_logdet", "sample", "marginalize",
+__all__ = ["SymmetricPattern", "JacobianPattern", "JacobianSchur", "assemble", "solve", "logdet", "solve_logdet", "sample", "marginalize",
            "covariance", "marginal_variances", "cross_covariance", "joint_covariance",
            "hessian", "jt_vec", "j_vec", "normal_equations", "lstsq", "check_positive_definite",
            "matvec", "quad_form", "log_prob", "solve_refined", "whiten", "sample_cov",
@@ -349,12 +349,41 @@ class JacobianOperator:
         self.product = solver.jacobianProduct(rows, cols, self.m)
         self._jrows, self._jcols = rows, cols
         self._dev = {}
+        self._schur = {}  # the maps of lstsq_cg(eliminate=indices), by the indices
 
     def _index(self, which, device):
         key = (which, device)
         if key not in self._dev:
             self._dev[key] = torch.from_numpy({"jrows": self._jrows, "jcols": self._jcols}[which]).to(device)
         return self._dev[key]
+
+
+class JacobianSchur:
+    """Implicit Schur elimination on a JacobianOperator: the params `eliminate` (indices into
+    jop.param_sizes, any order; each at most 8 scalars, no Jacobian row touching two of them) are eliminated
+    exactly and lstsq_cg(..., eliminate=this) runs the conjugate gradient on the reduced system of the kept ones.
+    Holds the host map (Solver.jacobianSchur); build once, reuse across solves."""
+
+    def __init__(self, jop, eliminate):
+        if not isinstance(jop, JacobianOperator):
+            raise TypeError("JacobianSchur: jop must be a JacobianOperator, got %s" % type(jop).__name__)
+        self.jop = jop
+        self.eliminate = _host_i64(eliminate)
+        self.map = jop.solver.jacobianSchur(jop.product, eliminate)
+        self.nK, self.nE = self.map.nK, self.map.nE
+        self._kept = {}
+
+    def info(self):
+        return self.map.info()
+
+    def table(self):
+        return self.map.table()
+
+    def kept_scalars(self, device):
+        """int64 device tensor [nK]: the caller's scalar of every kept index"""
+        if device not in self._kept:
+            self._kept[device] = torch.from_numpy(self.map.table()["kept_scalar"].astype(np.int64)).to(device)
+        return self._kept[device]
 
 
 class _Assemble(torch.autograd.Function):
@@ -1211,40 +1240,131 @@ def _cgls_run(jop, v, r, c, ab, precond, tol, max_steps, check_every, x0, cache)
     return x3.reshape(shape), run
 
 
+class _SchurPrecond:
+    """a built-in preconditioner of the reduced system on the kept scalars, applied by bsp_jac_schur_precond_apply_*
+    inside a cg.CgRun (section 24's apply on the kept block table)"""
+
+    def __init__(self, smap, kind, v, colsq, d):
+        self.smap, self.kind = smap, smap._KINDS[kind]
+        self.values, self.status = smap.precondBuild(kind, v, colsq, d)
+
+    def cg_apply(self, run):
+        sm = self.smap
+        _call(sm._lib, "bsp_jac_schur_precond_apply_", run.batched, run.sfx, sm.solver._h, sm._h, ctypes.c_int32(self.kind),
+              ctypes.c_int64(run.q), *run._args("schur_precond", self.values, run.r, run.z), *run._tail, *run._count)
+
+
+def _schur_run(sch, v, r, c, ab, precond, tol, max_steps, check_every, x0, cache):
+    """the reduced iteration of lstsq_cg(eliminate=...) on detached, contiguous operands: (x shaped like c or J^T r,
+    the CgRun on the kept scalars).  `cache` keeps what was built from v (the column norms, the damping vector, the
+    inverses of the eliminated blocks with their status) for the backward pass"""
+    from . import cg as _cg
+    from . import cgls as _cgls
+    if r is None and c is None:
+        raise ValueError("lstsq_cg: r and c cannot both be absent")
+    jop, smap = sch.jop, sch.map
+    prod = jop.product
+    batched = v.dim() == 2
+    like = r if r is not None else c
+    has_k = like.dim() == v.dim() + 1
+    lead = tuple(v.shape[:-1])
+    q = like.shape[-1] if has_k else 1
+    r3 = None if r is None else r.contiguous().reshape(lead + (jop.m, q))
+    c3 = None if c is None else c.contiguous().reshape(lead + (jop.n, q))
+    shape = lead + (jop.n,) + ((q,) if has_k else ())
+    kshape = lead + (sch.nK,) + ((q,) if has_k else ())
+    if "colsq" not in cache and (ab is not None or precond == "jacobi"):
+        cache["colsq"] = _cgls.column_norms(prod, v)
+    if "d" not in cache:
+        cache["d"] = None if ab is None else _cgls.damping_vector(prod, cache["colsq"], ab[0], ab[1], v)
+    d = cache["d"]
+    if "binv" not in cache:
+        cache["binv"], cache["eliminate_status"] = smap.build(v, d)
+    binv = cache["binv"]
+    mem = lambda t: None if t is None else _ptr_arg(t.unbind(0) if batched else [t], batched)
+    count = _count(v, batched)
+    # g = J^T r + c in full space: the normal product of section 28 without x and d
+    if r3 is None:
+        g = c3
+    else:
+        g = torch.empty(lead + (jop.n, q), dtype=v.dtype, device=v.device)
+        _call(prod._lib, "bsp_cgls_normal_", batched, _suffix(v), jop.solver._h, prod._h, mem(v), mem(r3), None, None,
+              mem(c3), ctypes.c_int64(q), mem(g), None, *count)
+    t = torch.empty(lead + (jop.m, q), dtype=v.dtype, device=v.device)
+    bk = smap.reduce(v, binv, g, t=t)
+    fixed = {"v": mem(v), "binv": mem(binv), "d": mem(d), "t": mem(t)}
+    state = {}
+
+    def apply_a(p, ap):
+        if "ap" not in fixed:
+            fixed["p"], fixed["ap"] = mem(p), mem(ap)
+        _call(prod._lib, "bsp_jac_schur_mv_", batched, _suffix(v), jop.solver._h, smap._h, ctypes.c_int64(q), fixed["v"],
+              fixed["binv"], fixed["d"], fixed["p"], fixed["t"], fixed["ap"], state.get("ptr"), *count)
+        return ap
+
+    if x0 is None:
+        xk = torch.zeros_like(bk)
+        rk = bk.clone()
+    else:  # only the kept part of the start is read; r_k = b_k - S x_k0 by one product
+        x03 = x0.detach().reshape(lead + (jop.n, q))
+        xk = x03.index_select(len(lead), sch.kept_scalars(v.device)).contiguous()
+        rk = bk - smap.mv(v, binv, xk, d=d, t=t)
+    pc = None
+    if precond in ("jacobi", "block_jacobi"):
+        if precond not in cache:
+            cache[precond] = _SchurPrecond(smap, precond, v, cache.get("colsq"), d)
+        pc = cache[precond]
+    elif precond is not None:
+        def pc(s):
+            z = precond(s if has_k else s.reshape(kshape))
+            if not isinstance(z, torch.Tensor) or z.shape != kshape:
+                raise ValueError("lstsq_cg: the preconditioner must return a tensor of shape %s" % (kshape,))
+            return z.reshape(s.shape)
+    run = _cg.CgRun(jop.solver, bk, xk, rk, apply_a, pc, tol, max_steps)
+    state["ptr"] = ctypes.c_void_p(_ptr_of(run.state))
+    run.run(check_every)
+    x3 = smap.backSubstitute(v, binv, g, xk, t=t)
+    return x3.reshape(shape), run
+
+
 class _LstsqCG(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, jop, values, r, alpha, beta, precond, tol, max_steps, check_every, x0):
+    def forward(ctx, jop, values, r, alpha, beta, precond, tol, max_steps, check_every, x0, schur):
         v = values.detach().contiguous()
         ab = None if alpha is None else (float(alpha), float(beta))
         cache = {}
+        solve = _cgls_run if schur is None else _schur_run
+        on = jop if schur is None else schur
         with _OnCurrentStream(jop.solver, v.device):
-            x, run = _cgls_run(jop, v, r.detach(), None, ab, precond, tol, max_steps, check_every, x0, cache)
+            x, run = solve(on, v, r.detach(), None, ab, precond, tol, max_steps, check_every, x0, cache)
             has_k = r.dim() == v.dim() + 1
             info = [t if has_k else t.squeeze(-1) for t in (run.iterations(), run.stop(), run.relres())]
             info.append(run.state if has_k else run.state.squeeze(-2))
             built = cache.get(precond) if isinstance(precond, str) else None
             status = built.status if built is not None else torch.empty(0, device=v.device)
-        ctx.jop, ctx.cache, ctx.ab = jop, cache, ab
+            estatus = cache["eliminate_status"] if schur is not None else torch.empty(0, device=v.device)
+        ctx.jop, ctx.cache, ctx.ab, ctx.solve, ctx.on = jop, cache, ab, solve, on
         ctx.ab_dtypes = tuple(t.dtype if isinstance(t, torch.Tensor) else None for t in (alpha, beta))
         ctx.settings = (precond, tol, max_steps, check_every)
         ctx.save_for_backward(v, r.detach().contiguous(), x)
         ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(*info, status)
-        return (x, *info, status)
+        ctx.mark_non_differentiable(*info, status, estatus)
+        return (x, *info, status, estatus)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g, *_):
         need = ctx.needs_input_grad
         if g is None or not (need[1] or need[2] or need[3] or need[4]):
-            return (None,) * 10
+            return (None,) * 11
         jop, (v, r, x), ab = ctx.jop, ctx.saved_tensors, ctx.ab
         precond, tol, max_steps, check_every = ctx.settings
         prod = jop.product
         gv = gr = ga = gb = None
         with _OnCurrentStream(jop.solver, g.device):
             # N is symmetric: the same iteration with the right-hand side c = g alone
-            w, _ = _cgls_run(jop, v, None, g.contiguous(), ab, precond, tol, max_steps, check_every, None, ctx.cache)
+            # (with eliminate: one more reduced solve; the returned x solves the same N x = g, so the formulas hold)
+            w, _ = ctx.solve(ctx.on, v, None, g.contiguous(), ab, precond, tol, max_steps, check_every, None, ctx.cache)
             jw = prod.jVec(v, w)
             if need[2]:
                 gr = jw
@@ -1267,11 +1387,11 @@ class _LstsqCG(torch.autograd.Function):
                 ga = -(ctx.cache["colsq"] * wx.double()).sum().to(ctx.ab_dtypes[0])
             if need[4]:
                 gb = -wx.double().sum().to(ctx.ab_dtypes[1])
-        return (None, gv, gr, ga, gb) + (None,) * 5
+        return (None, gv, gr, ga, gb) + (None,) * 6
 
 
 def lstsq_cg(jop, jvalues, r, damping=None, precond="block_jacobi", tol=1e-10, max_steps=100, check_every=8, x0=None,
-             return_info=False):
+             return_info=False, eliminate=None):
     """x = (J^T J + D)^-1 J^T r in the caller's order by CGLS, the conjugate gradient on the normal equations
     that keeps the residual r - J x in m-space, straight from the entries of J: the Gauss-Newton / Levenberg-
     Marquardt step of lstsq without a layout, a pair list or a factor.  jop: a JacobianOperator, or a
@@ -1292,7 +1412,20 @@ def lstsq_cg(jop, jvalues, r, damping=None, precond="block_jacobi", tol=1e-10, m
 
     Differentiable in jvalues, r, alpha and beta (x0 gets no gradient): one more run with the incoming gradient
     as the right-hand side, the same preconditioner and settings, then products and elementwise gathers.  Runs
-    on the current torch stream; no stream capture, no double backward."""
+    on the current torch stream; no stream capture, no double backward.
+
+    eliminate: None, a JacobianSchur of this operator, or an array of param indices (the map
+    is then built once and kept on the operator).  Those params are eliminated exactly (each at most 8 scalars, no
+    Jacobian row touching two of them) and the conjugate gradient runs on the reduced system S x_k = b_k of the
+    kept scalars, S = C - F^T B^-1 F reached through products alone; the eliminated part of x comes from the
+    back-substitution x_e = B^-1 (g_e - F x_k).  The stop test is then on the reduced system: |r_k|^2 <= tol^2
+    |b_k|^2 for the recurrence residual of S x_k = b_k, and a zero b_k stops at once with x_k = 0 (x_e = B^-1 g_e is
+    still returned).  Only the kept part of x0 is read.  precond then acts on the kept scalars: None; "jacobi" (1 /
+    (colsq_c + d_c), the diagonal of C); "block_jacobi" (the inverses of the diagonal blocks of C = J_k^T J_k + D_k
+    over the kept params, at most 32 scalars each), built and applied on the device; or a callable on tensors shaped
+    [nK(, k)] (with the batch's leading B).  info gains "eliminate_status", int64 [2] / [B, 2] = {the caller's scalar of the lowest bad pivot of
+    the eliminated blocks or -1, the number of bad blocks (their inverses are zero)}.  Gradients as above, by one
+    more reduced solve."""
     from . import cg as _cg
     what = "lstsq_cg"
     if isinstance(jop, JacobianPattern):
@@ -1310,20 +1443,38 @@ def lstsq_cg(jop, jvalues, r, damping=None, precond="block_jacobi", tol=1e-10, m
     if isinstance(precond, str):
         if precond not in ("jacobi", "block_jacobi"):
             raise ValueError("%s: precond must be None, 'jacobi', 'block_jacobi' or a callable, got %r" % (what, precond))
-        if precond == "block_jacobi" and int(np.max(jop.param_sizes, initial=0)) > _cg.MAX_BLOCK:
-            p = int(np.argmax(jop.param_sizes > _cg.MAX_BLOCK))
-            raise ValueError("%s: param %d has %d scalars; 'block_jacobi' takes params of at most %d"
-                             % (what, p, int(jop.param_sizes[p]), _cg.MAX_BLOCK))
+        if precond == "block_jacobi":
+            sizes = np.asarray(jop.param_sizes).copy()
+            if eliminate is not None:  # (only the kept params carry a block of the reduced system's preconditioner)
+                el = eliminate.eliminate if isinstance(eliminate, JacobianSchur) else _host_i64(eliminate)
+                sizes[el[(el >= 0) & (el < len(sizes))]] = 0
+            if int(np.max(sizes, initial=0)) > _cg.MAX_BLOCK:
+                p = int(np.argmax(sizes > _cg.MAX_BLOCK))
+                raise ValueError("%s: param %d has %d scalars; 'block_jacobi' takes params of at most %d"
+                                 % (what, p, int(sizes[p]), _cg.MAX_BLOCK))
     elif precond is not None and not callable(precond):
         raise ValueError("%s: precond must be None, 'jacobi', 'block_jacobi' or a callable, got %r" % (what, precond))
+    schur = None
+    if eliminate is not None:
+        if isinstance(eliminate, JacobianSchur):
+            if eliminate.jop is not jop:
+                raise ValueError("%s: eliminate was built on another operator" % what)
+            schur = eliminate
+        else:
+            key = tuple(int(e) for e in _host_i64(eliminate))
+            if key not in jop._schur:
+                jop._schur[key] = JacobianSchur(jop, eliminate)
+            schur = jop._schur[key]
     _ag._check_device(jop.solver, what, jvalues, r)
-    x, iters, stop, relres, state, status = _LstsqCG.apply(jop, jvalues, r, alpha, beta, precond, float(tol),
-                                                            max_steps, check_every, x0)
+    x, iters, stop, relres, state, status, estatus = _LstsqCG.apply(jop, jvalues, r, alpha, beta, precond, float(tol),
+                                                                     max_steps, check_every, x0, schur)
     if not return_info:
         return x
     info = {"iterations": iters, "stop": stop, "relres": relres, "state": state}
     if precond in ("jacobi", "block_jacobi"):
         info["precond_status"] = status
+    if schur is not None:
+        info["eliminate_status"] = estatus
     return x, info
 
 

@@ -1048,6 +1048,111 @@ int bsp_cgls_precond_build_batched_f32(bsp_solver* s, const bsp_jac_product* p, 
                                        const float* const* dev_values, const double* const* dev_colsq,
                                        const float* const* dev_d, float* const* dev_minv, void* dev_work, int64_t* dev_status,
                                        int32_t batch);
+/* EXTENSION without a counterpart in the reference's library as a device entry (the method is the implicit
+   Schur complement of Ceres' ITERATIVE_SCHUR; Agarwal, Snavely, Seitz, Szeliski, "Bundle adjustment in the
+   large", ECCV 2010): implicit Schur elimination for the matrix-free least squares.  The
+   params of the solver are split into eliminated and kept ones; no Jacobian row may touch two eliminated params,
+   and an eliminated param has at most 8 scalars.  With N = J^T J + D = [B F; F^T C] in that split, the reduced
+   matrix is S = C - F^T B^-1 F; only the inverses of the diagonal blocks of B (binv) and products with vectors
+   are formed.  bsp_jac_schur_create builds the host map over a bsp_jac_product, which must outlive it
+   (eliminate: param indices in any order, taken in ascending order); it refuses an empty list, an index out of
+   range or given twice, an eliminated param wider than 8 scalars, nothing kept, and a row with entries in two
+   eliminated params.  The kept scalars are numbered 0 .. nK - 1 and the eliminated ones 0 .. nE - 1 in ascending
+   caller's scalar.
+     info:   {nnz, m, n, nK, nE, eliminated params, rows of no group, widest eliminated param, most rows in a
+             group, kept entries, eliminated entries, long runs of the four lists (rows kept, rows eliminated,
+             columns eliminated, columns kept), items of the blocks of B, elements of binv, device bytes of the
+             map, device bytes of the block plan, rows in groups}
+     table:  part 0 .. 3: (start, entry, index, long runs) of the kept entries by row, the eliminated entries by
+             row, the eliminated scalars' entries and the kept columns' entries; 4: (kept scalar, eliminated
+             scalar, first eliminated scalar of each eliminated param, its param index); 5: (group start, group
+             rows, rows of no group); 6: (block start, block width, item start); 7: (item a, item b, item pos);
+             8, 9: as 6 and 7 for the diagonal blocks of C over the kept params (8 also gives their param indices)
+     build:  binv from the values and the damping vector dev_d [n] (may be NULL): the blocks of
+             bsp_cgls_precond_build_* (kind 2) of the eliminated params, bit for bit; dev_work and dev_status as
+             there (bsp_cgls_work_bytes(q = 1) per member); a bad block gets a zero inverse and is counted
+     mv:     dev_out [nK, q] = S dev_p; dev_t [m, q] is scratch; dev_state (may be NULL) holds the records of a
+             bsp_cg_* iteration, whose stopped columns are skipped
+     reduce: dev_out [nK, q] = g_k - F^T B^-1 g_e for the full right-hand side dev_g [n, q]
+     back:   dev_out [n, q], caller's order: the kept scalars from dev_xk and x_e = B^-1 (g_e - F x_k)
+     precond_info / precond_build / precond_apply: the built-in preconditioners of S on the kept scalars, kind 1
+             (Jacobi, 1 / (colsq_c + d_c), from dev_colsq [n]) or 2 (block-Jacobi: the inverses of the diagonal
+             blocks of C over the kept params, bsp_cgls_precond_build_*'s sums; a kept param wider than 32 is
+             refused by name).  info = {blocks, items, inverse elements, widest block, device bytes}; build takes
+             dev_work and dev_status as `build`; apply is the preconditioner piece of bsp_cg_* on [nK, q] vectors
+             (z = M^-1 r, r.z, beta) with that iteration's dev_work and dev_state
+   Every sum runs in a fixed order with every product rounded before it is added (DESIGN.md section 29 states the
+   orders); no atomics; member b of a batched call is bitwise the single call. */
+typedef struct bsp_jac_schur bsp_jac_schur;
+int bsp_jac_schur_create(const bsp_jac_product* p, int64_t num_eliminate, const int64_t* eliminate, bsp_jac_schur** out);
+void bsp_jac_schur_destroy(bsp_jac_schur* h);
+int bsp_jac_schur_info(const bsp_jac_schur* h, int64_t out[20]);
+int bsp_jac_schur_table(const bsp_jac_schur* h, int32_t part, int32_t* t0, int32_t* t1, int32_t* t2, int32_t* t3);
+int bsp_jac_schur_precond_info(const bsp_jac_schur* h, int32_t kind, int64_t out[5]);
+int bsp_jac_schur_build_f64(bsp_solver* s, const bsp_jac_schur* h, const double* dev_values, const double* dev_d, double* dev_binv,
+                            void* dev_work, int64_t* dev_status);
+int bsp_jac_schur_build_batched_f64(bsp_solver* s, const bsp_jac_schur* h, const double* const* dev_values,
+                                    const double* const* dev_d, double* const* dev_binv, void* dev_work, int64_t* dev_status,
+                                    int32_t batch);
+int bsp_jac_schur_mv_f64(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const double* dev_values, const double* dev_binv,
+                         const double* dev_d, const double* dev_p, double* dev_t, double* dev_out, const int64_t* dev_state);
+int bsp_jac_schur_mv_batched_f64(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const double* const* dev_values,
+                                 const double* const* dev_binv, const double* const* dev_d, const double* const* dev_p,
+                                 double* const* dev_t, double* const* dev_out, const int64_t* dev_state, int32_t batch);
+int bsp_jac_schur_reduce_f64(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const double* dev_values, const double* dev_binv,
+                             const double* dev_g, double* dev_t, double* dev_out);
+int bsp_jac_schur_reduce_batched_f64(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const double* const* dev_values,
+                                     const double* const* dev_binv, const double* const* dev_g, double* const* dev_t,
+                                     double* const* dev_out, int32_t batch);
+int bsp_jac_schur_back_f64(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const double* dev_values, const double* dev_binv,
+                           const double* dev_g, const double* dev_xk, double* dev_t, double* dev_out);
+int bsp_jac_schur_back_batched_f64(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const double* const* dev_values,
+                                   const double* const* dev_binv, const double* const* dev_g, const double* const* dev_xk,
+                                   double* const* dev_t, double* const* dev_out, int32_t batch);
+int bsp_jac_schur_precond_build_f64(bsp_solver* s, const bsp_jac_schur* h, int32_t kind, const double* dev_values,
+                                    const double* dev_colsq, const double* dev_d, double* dev_minv, void* dev_work,
+                                    int64_t* dev_status);
+int bsp_jac_schur_precond_build_batched_f64(bsp_solver* s, const bsp_jac_schur* h, int32_t kind,
+                                            const double* const* dev_values, const double* const* dev_colsq,
+                                            const double* const* dev_d, double* const* dev_minv, void* dev_work,
+                                            int64_t* dev_status, int32_t batch);
+int bsp_jac_schur_precond_apply_f64(bsp_solver* s, const bsp_jac_schur* h, int32_t kind, int64_t q, const double* dev_minv,
+                                    const double* dev_r, double* dev_z, void* dev_work, int64_t* dev_state);
+int bsp_jac_schur_precond_apply_batched_f64(bsp_solver* s, const bsp_jac_schur* h, int32_t kind, int64_t q,
+                                            const double* const* dev_minv, const double* const* dev_r, double* const* dev_z,
+                                            void* dev_work, int64_t* dev_state, int32_t batch);
+int bsp_jac_schur_build_f32(bsp_solver* s, const bsp_jac_schur* h, const float* dev_values, const float* dev_d, float* dev_binv,
+                            void* dev_work, int64_t* dev_status);
+int bsp_jac_schur_build_batched_f32(bsp_solver* s, const bsp_jac_schur* h, const float* const* dev_values,
+                                    const float* const* dev_d, float* const* dev_binv, void* dev_work, int64_t* dev_status,
+                                    int32_t batch);
+int bsp_jac_schur_mv_f32(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const float* dev_values, const float* dev_binv,
+                         const float* dev_d, const float* dev_p, float* dev_t, float* dev_out, const int64_t* dev_state);
+int bsp_jac_schur_mv_batched_f32(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const float* const* dev_values,
+                                 const float* const* dev_binv, const float* const* dev_d, const float* const* dev_p,
+                                 float* const* dev_t, float* const* dev_out, const int64_t* dev_state, int32_t batch);
+int bsp_jac_schur_reduce_f32(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const float* dev_values, const float* dev_binv,
+                             const float* dev_g, float* dev_t, float* dev_out);
+int bsp_jac_schur_reduce_batched_f32(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const float* const* dev_values,
+                                     const float* const* dev_binv, const float* const* dev_g, float* const* dev_t,
+                                     float* const* dev_out, int32_t batch);
+int bsp_jac_schur_back_f32(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const float* dev_values, const float* dev_binv,
+                           const float* dev_g, const float* dev_xk, float* dev_t, float* dev_out);
+int bsp_jac_schur_back_batched_f32(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const float* const* dev_values,
+                                   const float* const* dev_binv, const float* const* dev_g, const float* const* dev_xk,
+                                   float* const* dev_t, float* const* dev_out, int32_t batch);
+int bsp_jac_schur_precond_build_f32(bsp_solver* s, const bsp_jac_schur* h, int32_t kind, const float* dev_values,
+                                    const double* dev_colsq, const float* dev_d, float* dev_minv, void* dev_work,
+                                    int64_t* dev_status);
+int bsp_jac_schur_precond_build_batched_f32(bsp_solver* s, const bsp_jac_schur* h, int32_t kind,
+                                            const float* const* dev_values, const double* const* dev_colsq,
+                                            const float* const* dev_d, float* const* dev_minv, void* dev_work,
+                                            int64_t* dev_status, int32_t batch);
+int bsp_jac_schur_precond_apply_f32(bsp_solver* s, const bsp_jac_schur* h, int32_t kind, int64_t q, const float* dev_minv,
+                                    const float* dev_r, float* dev_z, void* dev_work, int64_t* dev_state);
+int bsp_jac_schur_precond_apply_batched_f32(bsp_solver* s, const bsp_jac_schur* h, int32_t kind, int64_t q,
+                                            const float* const* dev_minv, const float* const* dev_r, float* const* dev_z,
+                                            void* dev_work, int64_t* dev_state, int32_t batch);
 /* EXTENSION without a counterpart in the reference's library: the pieces of the Lanczos recurrence with its
    scalars on the device, for extreme eigenvalues, a 2-norm condition estimate and
    stochastic Lanczos quadrature (log-determinants) without a factor.  One problem per (matrix, start vector):
