@@ -1807,6 +1807,111 @@ class JacobianSchur:
               ctypes.c_void_p(_ptr_of(status)), *((ctypes.c_int32(nb),) if batched else ()))
         return minv, status
 
+    # ---- the block diagonal of S as preconditioner
+    _SJ_KEYS = ("blocks", "real_pairs", "pseudo_pairs", "pair_rows", "chunks", "inverse_elems", "partial_elems",
+                "device_bytes")
+
+    def schurJacobiInfo(self):
+        """figures of the plan of "schur_jacobi", the block diagonal of S over the kept params (bsp_jac_schur_sjacobi_info;
+        a kept param wider than 32 scalars is refused by name), and kept_item_plan_built: whether the item plan of
+        "block_jacobi" exists, which this plan never needs.  Host work only; the plan is built by the first call."""
+        out = (ctypes.c_int64 * 8)()
+        _check(self._lib.bsp_jac_schur_sjacobi_info(self._h, out))
+        info = dict(zip(self._SJ_KEYS, [int(x) for x in out]))
+        built = ctypes.c_int32(0)
+        _check(self._lib.bsp_jac_schur_kept_plan_built(self._h, ctypes.byref(built)))
+        info["kept_item_plan_built"] = bool(built.value)
+        return info
+
+    def schurJacobiTable(self):
+        """every table of that plan (bsp_jac_schur_sjacobi_table): block_pair, block_chunk, block_width, block_off
+        (int64); chunk_pair, chunk_block, chunk_part (int64); pair_elim, pair_row, pair_rec; row_of, rec"""
+        i = self.schurJacobiInfo()
+        nb, nc, npairs = i["blocks"], i["chunks"], i["real_pairs"] + i["pseudo_pairs"]
+
+        def get(part, sizes, size64=None):
+            arrs = [np.zeros(max(n, 1), dtype=np.int32) for n in sizes]
+            ptrs = [a.ctypes.data_as(_I32P) for a in arrs] + [None] * (3 - len(arrs))
+            wide = None if size64 is None else np.zeros(max(size64, 1), dtype=np.int64)
+            _check(self._lib.bsp_jac_schur_sjacobi_table(self._h, ctypes.c_int32(part), *ptrs,
+                                                         None if wide is None else wide.ctypes.data_as(_I64P)))
+            return [a[:n] for a, n in zip(arrs, sizes)] + ([] if wide is None else [wide[:size64]])
+
+        out = {}
+        out["block_pair"], out["block_chunk"], out["block_width"], out["block_off"] = get(0, (nb + 1, nb + 1, nb), nb + 1)
+        out["chunk_pair"], out["chunk_block"], out["chunk_part"] = get(1, (nc + 1, nc), nc + 1)
+        out["pair_elim"], out["pair_row"], out["pair_rec"] = get(2, (npairs, npairs + 1, npairs + 1))
+        out["row_of"], out["rec"] = get(3, (i["pair_rows"], int(out["pair_rec"][-1])))
+        return out
+
+    def schurJacobiBuild(self, values, binv, d=None, partials=None, out=None):
+        """(minv, status): the inverses of the diagonal blocks of S = C - F^T B^-1 F over the kept params, [inverse_elems]
+        / [B, inverse_elems], block b row-major at the offsets of "block_jacobi"'s kept blocks, and status as build()'s
+        (bsp_jac_schur_sjacobi_build_*).  binv: what build() returned for these values and d; d: the damping vector or
+        None; partials: float64 scratch [partial_elems] / [B, partial_elems] for the chunk sums (allocated when
+        None); out: where minv goes.  All block arithmetic is in float64; a bad block gets a zero inverse."""
+        import torch
+        name = "schurJacobiBuild"
+        lead = self._lead(name, values)
+        batched = len(lead) == 1
+        if (not isinstance(binv, torch.Tensor) or binv.dtype != values.dtype or binv.device != values.device
+                or tuple(binv.shape) != lead + (max(self.inverse_elems, 1),)):
+            raise ValueError("%s: binv must be what build() returned for these values" % name)
+        _ptr_of(binv)
+        if d is not None and self._operand(name, "d", d, values, lead, self.n) is not None:
+            raise ValueError("%s: d must be [n] or [B, n]" % name)
+        info = self.schurJacobiInfo()
+        pshape = lead + (max(info["partial_elems"], 1),)
+        if partials is None:
+            partials = torch.empty(pshape, dtype=torch.float64, device=values.device)
+        elif (not isinstance(partials, torch.Tensor) or partials.dtype != torch.float64 or partials.device != values.device
+              or tuple(partials.shape) != pshape):
+            raise ValueError("%s: partials must be a float64 tensor of shape %s on %s" % (name, pshape, values.device))
+        minv = _EntryMap._alloc_out(name, values, lead + (max(info["inverse_elems"], 1),), out)
+        _ptr_of(partials), _ptr_of(minv)
+        status = torch.empty(lead + (2,), dtype=torch.int64, device=values.device)
+        need = ctypes.c_int64(0)
+        _check(self._lib.bsp_cgls_work_bytes(self.solver._h, self.product._h, ctypes.c_int64(1), ctypes.byref(need)))
+        nb = values.shape[0] if batched else 1
+        work = torch.empty(need.value * nb + 16, dtype=torch.uint8, device=values.device)
+        mem = self._members
+        _call(self._lib, "bsp_jac_schur_sjacobi_build_", batched, _suffix(values), self.solver._h, self._h,
+              mem(values, batched), mem(binv, batched), mem(d, batched), mem(partials, batched), mem(minv, batched),
+              ctypes.c_void_p((work.data_ptr() + 15) // 16 * 16), ctypes.c_void_p(_ptr_of(status)),
+              *((ctypes.c_int32(nb),) if batched else ()))
+        return minv, status
+
+    def schurJacobiApply(self, minv, r, z, work, state):
+        """the preconditioner piece of a conjugate gradient on the kept scalars with the minv of schurJacobiBuild
+        (bsp_jac_schur_sjacobi_apply_*): z = M^-1 r, r.z and beta for the running columns of `state`.  r, z: [nK, q]
+        ([B, nK, q] with minv [B, inverse_elems]); work: the iteration's 16-byte aligned device work area as a
+        ctypes pointer or an int address; state: its int64 records [.., q, 12].  Never builds the item plan of
+        "block_jacobi"."""
+        import torch
+        name = "schurJacobiApply"
+        if not isinstance(minv, torch.Tensor) or minv.dim() not in (1, 2):
+            raise ValueError("%s: minv must be what schurJacobiBuild() returned" % name)
+        batched = minv.dim() == 2
+        lead = tuple(minv.shape[:-1])
+        for what, t in (("r", r), ("z", z)):
+            if (not isinstance(t, torch.Tensor) or t.dtype != minv.dtype or t.device != minv.device
+                    or t.dim() != len(lead) + 2 or tuple(t.shape[:-1]) != lead + (self.nK,) or t.shape[-1] < 1
+                    or t.shape != r.shape):
+                raise ValueError("%s: %s must be a %s tensor %s on %s" % (name, what, minv.dtype, lead + (self.nK, "q"),
+                                                                         minv.device))
+            _ptr_of(t)
+        q = int(r.shape[-1])
+        if (not isinstance(state, torch.Tensor) or state.dtype != torch.int64 or tuple(state.shape) != lead + (q, 12)
+                or state.device != minv.device):
+            raise ValueError("%s: state must be the int64 records %s of a CgRun" % (name, lead + (q, 12)))
+        _ptr_of(minv)
+        mem = self._members
+        work = work if isinstance(work, ctypes.c_void_p) else ctypes.c_void_p(int(work))
+        _call(self._lib, "bsp_jac_schur_sjacobi_apply_", batched, _suffix(minv), self.solver._h, self._h, ctypes.c_int64(q),
+              mem(minv, batched), mem(r, batched), mem(z, batched), work, ctypes.c_void_p(_ptr_of(state)),
+              *((ctypes.c_int32(minv.shape[0]),) if batched else ()))
+        return z
+
     # ---- the device entries: values [nnz] / [B, nnz]; vectors [rows] / [rows, q] with a leading B for a batch
     def _lead(self, name, values):
         import torch

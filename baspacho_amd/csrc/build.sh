@@ -6,7 +6,7 @@ OUT=${BSP_OUT:-../libbaspacho_amd.so}
 BUILD=${BSP_BUILD_DIR:-../_build}
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="-O3 -std=c++17 -fPIC -Wall -Wno-unused-function --offload-arch=gfx950 -munsafe-fp-atomics ${BSP_KTRACE:+-DBSP_KTRACE=1} ${BSP_EXTRA_DEFS:-}"
-SRCS="bsp_utils.cpp sparse_structure.cpp min_degree.cpp computation_model.cpp elimination_tree.cpp skeleton.cpp solver.cpp assembly.cpp normal_eq.cpp jac_product.cpp jac_schur.cpp sym_product.cpp reach.cpp factor_product_plan.cpp bal_fill_plan.cpp hip_plan.cpp c_api.cpp"
+SRCS="bsp_utils.cpp sparse_structure.cpp min_degree.cpp computation_model.cpp elimination_tree.cpp skeleton.cpp solver.cpp assembly.cpp normal_eq.cpp jac_product.cpp jac_schur.cpp jac_schur_jacobi.cpp sym_product.cpp reach.cpp factor_product_plan.cpp bal_fill_plan.cpp hip_plan.cpp c_api.cpp"
 mkdir -p $BUILD
 OBJS=""
 pids=()

@@ -1625,6 +1625,108 @@ static void jacSchurRun(bsp_solver* s, const bsp_jac_schur* h, int32_t op, int64
 BSP_JAC_SCHUR_API(f64, double)
 BSP_JAC_SCHUR_API(f32, float)
 #undef BSP_JAC_SCHUR_API
+// ---- the block diagonal of S as preconditioner of the reduced system -------------
+int bsp_jac_schur_sjacobi_info(const bsp_jac_schur* h, int64_t out[8]) {
+  BSP_TRY
+  if (h == nullptr || out == nullptr) throw std::runtime_error("bsp_jac_schur_sjacobi_info: NULL argument");
+  const JacSchurMap& m = *h->map;
+  const JacSchurJacobiPlan& pl = jacSchurJacobiPlan(m);
+  const int64_t v[8] = {pl.numBlocks,
+                        pl.numReal,
+                        pl.numPseudo,
+                        pl.numPairRows(),
+                        pl.numChunks(),
+                        pl.inverseElems(),
+                        pl.partialElems(),
+                        pl.deviceBytes() + (int64_t)((m.keptBlockStart.size() + m.keptScalarBlock.size() +
+                                                      m.keptWidth.size() + m.keptFirst.size()) *
+                                                     sizeof(int32_t))};
+  std::copy(v, v + 8, out);
+  BSP_CATCH
+}
+int bsp_jac_schur_sjacobi_table(const bsp_jac_schur* h, int32_t part, int32_t* t0, int32_t* t1, int32_t* t2,
+                                int64_t* t3) {
+  BSP_TRY
+  if (h == nullptr) throw std::runtime_error("bsp_jac_schur_sjacobi_table: the map is NULL");
+  const auto put = [](const auto& v, auto* out) {
+    if (!v.empty() && out == nullptr) throw std::runtime_error("bsp_jac_schur_sjacobi_table: an output array is NULL");
+    std::copy(v.begin(), v.end(), out);
+  };
+  const JacSchurMap& m = *h->map;
+  if (part < 0 || part > 3) {
+    throw std::runtime_error("bsp_jac_schur_sjacobi_table: unknown part " + std::to_string(part) +
+                             " (0: blocks, 1: chunks, 2: pairs, 3: pair-rows and records)");
+  }
+  const JacSchurJacobiPlan& pl = jacSchurJacobiPlan(m);
+  if (part == 0) {
+    put(pl.blockPair, t0);
+    put(pl.blockChunk, t1);
+    put(m.keptWidth, t2);
+    put(pl.blockOff, t3);
+  } else if (part == 1) {
+    put(pl.chunkPair, t0);
+    put(pl.chunkBlock, t1);
+    put(pl.chunkPart, t3);
+  } else if (part == 2) {
+    put(pl.pairElim, t0);
+    put(pl.pairRow, t1);
+    put(pl.pairRec, t2);
+  } else {
+    put(pl.rowOf, t0);
+    put(pl.rec, t1);
+  }
+  BSP_CATCH
+}
+int bsp_jac_schur_kept_plan_built(const bsp_jac_schur* h, int32_t* out) {
+  BSP_TRY
+  if (h == nullptr || out == nullptr) throw std::runtime_error("bsp_jac_schur_kept_plan_built: NULL argument");
+  *out = h->map->keptBlocks ? 1 : 0;
+  BSP_CATCH
+}
+template <typename T>
+static void jacSchurJacobiRun(bsp_solver* s, const bsp_jac_schur* h, int32_t op, int64_t q, const T* const* v,
+                              const T* const* binv, const T* const* d, double* const* partials, const T* const* vec,
+                              T* const* out, void* work, int64_t* state, int64_t* status, int32_t batch, bool single) {
+  if (s == nullptr) throw std::runtime_error("jacobian schur: the solver is NULL");
+  if (h == nullptr) throw std::runtime_error("jacobian schur: the map is NULL");
+  JacSchurArgs<T> a;
+  a.op = op;
+  a.q = q;
+  a.map = h->map.get();
+  a.values = v;
+  a.binv = binv;
+  a.damp = d;
+  a.partials = partials;
+  a.vec = vec;
+  a.out = out;
+  a.work = work;
+  a.state = state;
+  a.status = status;
+  s->solver->jacSchur<T>(a, batch, single);
+}
+#define BSP_JAC_SCHUR_SJACOBI_API(SFX, T)                                                                         \
+  int bsp_jac_schur_sjacobi_build_##SFX(bsp_solver* s, const bsp_jac_schur* h, const T* v, const T* binv,         \
+                                        const T* d, double* partials, T* minv, void* work, int64_t* status)      \
+      BSP_BODY(jacSchurJacobiRun<T>(s, h, SchurSJacobiBuild, 1, &v, &binv, one(d), &partials, nullptr, &minv,     \
+                                    work, nullptr, status, 1, true))                                              \
+  int bsp_jac_schur_sjacobi_build_batched_##SFX(bsp_solver* s, const bsp_jac_schur* h, const T* const* v,         \
+                                                const T* const* binv, const T* const* d,                          \
+                                                double* const* partials, T* const* minv, void* work,              \
+                                                int64_t* status, int32_t batch)                                   \
+      BSP_BODY(jacSchurJacobiRun<T>(s, h, SchurSJacobiBuild, 1, v, binv, d, partials, nullptr, minv, work,        \
+                                    nullptr, status, batch, false))                                               \
+  int bsp_jac_schur_sjacobi_apply_##SFX(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const T* minv,          \
+                                        const T* r, T* z, void* work, int64_t* state)                             \
+      BSP_BODY(jacSchurJacobiRun<T>(s, h, SchurSJacobiApply, q, nullptr, &minv, nullptr, nullptr, &r, &z, work,   \
+                                    state, nullptr, 1, true))                                                     \
+  int bsp_jac_schur_sjacobi_apply_batched_##SFX(bsp_solver* s, const bsp_jac_schur* h, int64_t q,                 \
+                                                const T* const* minv, const T* const* r, T* const* z,             \
+                                                void* work, int64_t* state, int32_t batch)                        \
+      BSP_BODY(jacSchurJacobiRun<T>(s, h, SchurSJacobiApply, q, nullptr, minv, nullptr, nullptr, r, z, work,      \
+                                    state, nullptr, batch, false))
+BSP_JAC_SCHUR_SJACOBI_API(f64, double)
+BSP_JAC_SCHUR_SJACOBI_API(f32, float)
+#undef BSP_JAC_SCHUR_SJACOBI_API
 #undef BSP_CC
 #undef BSP_CD
 // ---- the Lanczos recurrence -----------------------------------------------------

@@ -363,6 +363,10 @@ void hipBackendCgls(SymbolicCtx& sym, const CglsArgs<T>& a, int64_t batch, bool 
 //                 1), values (kind 2), damp = d (may be absent); out = its values; work, status as SchurBuild
 //   SchurPrecondApply:  CgPrecond of the conjugate gradient on the kept scalars with that preconditioner: binv =
 //                 its values, vec = r, out = z; work (cgWorkBytes(nK, q) per member) and state are the iteration's
+//   SchurSJacobiBuild:  the block diagonal of S: values, binv, damp = d (may be absent),
+//                 partials = the chunk partials (JacSchurJacobiPlan::partialElems() doubles per member); out = the
+//                 inverses of the blocks; work, status as SchurBuild
+//   SchurSJacobiApply:  SchurPrecondApply of kind 2 on that plan's block offsets (the kept item plan is not built)
 struct JacSchurMap;
 enum SchurOp : int32_t {
   SchurBuild = 0,
@@ -370,7 +374,9 @@ enum SchurOp : int32_t {
   SchurReduce = 2,
   SchurBack = 3,
   SchurPrecondBuild = 4,
-  SchurPrecondApply = 5
+  SchurPrecondApply = 5,
+  SchurSJacobiBuild = 6,
+  SchurSJacobiApply = 7
 };
 template <typename T>
 struct JacSchurArgs {
@@ -385,8 +391,9 @@ struct JacSchurArgs {
   T* const* t = nullptr;
   T* const* out = nullptr;
   const double* const* colsq = nullptr;
+  double* const* partials = nullptr;
   void* work = nullptr;
-  int64_t* state = nullptr;  // (only SchurPrecondApply writes it)
+  int64_t* state = nullptr;  // (only SchurPrecondApply and SchurSJacobiApply write it)
   int64_t* status = nullptr;
 };
 template <typename T>

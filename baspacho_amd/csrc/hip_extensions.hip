@@ -1377,6 +1377,49 @@ void hipBackendJacSchur(SymbolicCtx& sym, const JacSchurArgs<T>& a, int64_t batc
     });
     return;
   }
+  if (a.op == SchurSJacobiBuild) {  // the block diagonal of S: the chunks, then the blocks
+    const JacSchurJacobiPlan& sp = jacSchurJacobiPlan(map);
+    const int64_t stride = cglsWorkBytes(m, n, 1), badOff = cglsBadOffset(m, n, 1);
+    const BatchPtrs<double> ps = h.stage(a.partials, batch, single);
+    const hipk::SchurJacobiDev sj{d.get(sp.chunkPair),   d.get(sp.chunkBlock), d.get(sp.chunkPart), d.get(sp.pairElim),
+                                  d.get(sp.pairRow),     d.get(sp.pairRec),    d.get(sp.rec),       d.get(map.keptWidth),
+                                  d.get(map.keptFirst),  d.get(map.elimOff),   d.get(sp.blockChunk), d.get(plan.blockOff),
+                                  d.get(sp.blockOff)};
+    const hipk::CgPrecondDev pl{sj.keptFirst, sj.blockOff, nullptr, nullptr, nullptr, nullptr};
+    const int64_t numChunks = sp.numChunks(), numBlocks = sp.numBlocks;
+    BASPACHO_CHECK_LT(numChunks, (int64_t)INT32_MAX);
+    h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+      const hipk::CgWork w{static_cast<char*>(a.work) + q0 * stride, stride, badOff};
+      const hipk::DataRef<double> pOut = ps.at(q0);
+      if (numChunks > 0) {
+        hipk::schurJacobiChunks<T><<<dim3((unsigned)numChunks, nm), hipk::kSjThreads, 0, stream>>>(sj, vs.at(q0),
+                                                                                                 bs.at(q0), pOut);
+      }
+      if (numBlocks > 0) {
+        hipk::schurJacobiBlocks<T><<<dim3((unsigned)numBlocks, nm), hipk::kCgBuildThreads, 0, stream>>>(
+            sj, hipk::DataRef<const double>{pOut.single, (const double* const*)pOut.many}, ds.at(q0), os.at(q0), w);
+      }
+      hipk::cgPrecondStatus<<<dim3(1, nm), hipk::kRedThreads, 0, stream>>>(numBlocks, pl, w, a.status + 2 * q0);
+    });
+    return;
+  }
+  if (a.op == SchurSJacobiApply) {  // SchurPrecondApply of kind 2 on the new plan's block offsets
+    const JacSchurJacobiPlan& sp = jacSchurJacobiPlan(map);
+    const int64_t nK = map.nK, nParts = (nK + hipk::kRedChunk - 1) / hipk::kRedChunk;
+    BASPACHO_CHECK_LT(nParts * q, (int64_t)INT32_MAX);
+    const int64_t stride = cgWorkBytes(nK, q), badOff = cgBadOffset(nK, q);
+    const hipk::CgPrecondDev pl{d.get(map.keptBlockStart), d.get(sp.blockOff), d.get(map.keptScalarBlock), nullptr,
+                                nullptr, nullptr};
+    h.forChunks(batch, HipSymbolicCtx::kMaxGridY, [&](int64_t q0, unsigned nm) {
+      const hipk::CgWork w{static_cast<char*>(a.work) + q0 * stride, stride, badOff};
+      hipk::CgState* st = reinterpret_cast<hipk::CgState*>(a.state) + q0 * q;
+      hipk::cgPrecond<T, 2><<<dim3((unsigned)(nParts * q), nm), hipk::kRedThreads, 0, stream>>>(
+          nK, (int32_t)q, (int32_t)nParts, pl, bs.at(q0), ws.at(q0), os.at(q0), w, st);
+      hipk::cgFold<<<dim3((unsigned)q, nm), hipk::kRedThreads, 0, stream>>>((int32_t)q, (int32_t)nParts, hipk::CgFoldBeta,
+                                                                          false, 0.0, 0, w, st);
+    });
+    return;
+  }
   const hipk::SchurDev sd{map.numElim,
                           (int64_t)map.freeRows.size(),
                           map.nK,

@@ -3,6 +3,8 @@
 // over the lists of a JacSchurMap (jac_schur.h).  S and F are never formed.  The inverses of the diagonal blocks
 // of B are built by cglsBlockBuild on the map's plan.  Launched by hip_extensions.hip.
 // Streaming kernels: no matrix cores, no persistent launch, no flags, no atomics, no scratch, no barrier.
+// At the end of the file: the block diagonal of S as preconditioner (section 30), two kernels of one wave per
+// workgroup that do stage through LDS behind barriers.
 //
 // CONVENTIONS.  Those of hip_cgls_kernels.h: vectors [rows, q] row-major, matrix blockIdx.y of a batch through
 // pickData, every product rounded before it is added, all in T.  Kept vectors are [nK, q], full ones [n, q], t is
@@ -221,6 +223,180 @@ __global__ void __launch_bounds__(kRedThreads)
   const bool ok = d > 0.0 && redFinite(d);
   pickData(mref)[c] = ok ? (T)(1.0 / d) : T(0);
   work.bad()[c] = ok ? -1 : 0;
+}
+
+// ---- the block diagonal of S: "schur_jacobi"  ---------------------------------------
+// S_bb = D_bb + sum over the pairs (e, b) of W_eb + sum over the pseudo-pairs of G, W_eb = G_eb - F_eb^T Binv_e
+// F_eb, over the tables of a JacSchurJacobiPlan (jac_schur.h).  Two launches, no atomics, all in double for both T.
+// ORDERS (part of the interface; tests/schur_jacobi_ref.py restates them).  v(i, s): the value of the pair-row's
+// record at scalar s, a term existing only where both of its entries do.  Every sum is a left fold from +0:
+//   G[a, c] = over the pair's rows, ascending, of rmul(v(i, a), v(i, c))         (a >= c in b)
+//   F[l, c] = over the pair's rows, ascending, of rmul(v(i, l), v(i, c))         (l in e, c in b)
+//   Y[l, c] = over l' ascending of rmul(Binv[l, l'], F[l', c])
+//   E[a, c] = over l ascending of rmul(F[l, a], Y[l, c]);  W[a, c] = radd(G[a, c], -E[a, c]) (a pseudo-pair: G)
+//   P[a, c] = over the chunk's pairs in list order of W[a, c];  A[a, c] = over b's chunks, ascending, of P[a, c]
+//   A[a, a] = radd(A[a, a], double(d[s0 + a])) where d is given; then cgBlockInvert
+constexpr int kSjThreads = 64;                                         // one wave per chunk
+constexpr int kSjMaxTri = kCgMaxBlock * (kCgMaxBlock + 1) / 2;         // lower-triangle elements of the widest block
+constexpr int kSjPerLane = (kSjMaxTri + kSjThreads - 1) / kSjThreads;  // ... of one lane: 9
+constexpr int kSjMaxF = kSchurMaxW * kCgMaxBlock;                      // elements of the widest F
+constexpr int kSjFPerLane = kSjMaxF / kSjThreads;                      // ... of one lane: 4
+constexpr int kSjMaxRec = kCgMaxBlock + kSchurMaxW;                    // widest record
+constexpr int kSjRowBatch = 8;                                         // pair-rows staged in LDS at a time
+
+struct SchurJacobiDev {
+  const int32_t *chunkPair, *chunkBlock;
+  const int64_t* chunkPart;
+  const int32_t *pairElim, *pairRow, *pairRec, *rec;
+  const int32_t *keptWidth, *keptFirst, *elimOff, *blockChunk;
+  const int64_t *elimBlockOff, *blockOff;
+};
+
+// (a, c), a >= c, of lower-triangle element el = a (a + 1) / 2 + c, packed as a | c << 8
+__device__ __forceinline__ int sjElement(int el) {
+  int a = 0;
+  while ((a + 1) * (a + 2) / 2 <= el) a++;
+  return a | ((el - a * (a + 1) / 2) << 8);
+}
+
+// The chunk kernel, one wave per (chunk, matrix): the pairs of the chunk in list order; a lane keeps the running
+// sums P of its elements lane + 64 r in registers.  The rows of a pair are walked serially, kSjRowBatch of them
+// staged in LDS at a time (entry index and value of every record slot); F and Y go through LDS.
+template <typename T>
+__global__ void __launch_bounds__(kSjThreads)
+    schurJacobiChunks(SchurJacobiDev sj, DataRef<const T> vref, DataRef<const T> bref, DataRef<double> pref) {
+  __shared__ double rowv[kSjRowBatch * kSjMaxRec];
+  __shared__ int32_t rowk[kSjRowBatch * kSjMaxRec];
+  __shared__ double Fs[kSjMaxF], Ys[kSjMaxF], Bs[kSchurMaxW * kSchurMaxW];
+  const int lane = threadIdx.x;
+  const int64_t h = blockIdx.x;
+  const int32_t b = sj.chunkBlock[h];
+  const int w = sj.keptWidth[b], tri = w * (w + 1) / 2;
+  const GP<const T> v = pickData(vref);
+  int ac[kSjPerLane], lc[kSjFPerLane];
+  double P[kSjPerLane];
+#pragma unroll
+  for (int r = 0; r < kSjPerLane; r++) {
+    const int el = lane + kSjThreads * r;
+    ac[r] = el < tri ? sjElement(el) : 0;
+    P[r] = 0.0;
+  }
+#pragma unroll
+  for (int r = 0; r < kSjFPerLane; r++) {
+    const int el = lane + kSjThreads * r, l = el / w;
+    lc[r] = l | ((el - l * w) << 8);
+  }
+  const int32_t p0 = sj.chunkPair[h], p1 = sj.chunkPair[h + 1];
+  for (int32_t p = p0; p < p1; p++) {
+    const int32_t e = sj.pairElim[p];
+    int we = 0;
+    if (e >= 0) {
+      const int32_t l0 = sj.elimOff[e];
+      we = sj.elimOff[e + 1] - l0;
+      // (the Bs of the pair before were last read ahead of a barrier of that pair)
+      if (lane < we * we) Bs[lane] = (double)pickData(bref)[sj.elimBlockOff[e] + lane];
+    }
+    const int wt = w + we, nf = we * w;
+    const int32_t r0 = sj.pairRow[p], r1 = sj.pairRow[p + 1];
+    const int32_t* __restrict__ rec = sj.rec + sj.pairRec[p];
+    double G[kSjPerLane], F[kSjFPerLane];
+#pragma unroll
+    for (int r = 0; r < kSjPerLane; r++) G[r] = 0.0;
+#pragma unroll
+    for (int r = 0; r < kSjFPerLane; r++) F[r] = 0.0;
+    for (int32_t rb = r0; rb < r1; rb += kSjRowBatch) {
+      const int nr = r1 - rb < kSjRowBatch ? (int)(r1 - rb) : kSjRowBatch;
+      __syncthreads();  // the batch before is consumed
+      for (int x = lane; x < nr * wt; x += kSjThreads) {
+        const int32_t k = rec[(int64_t)(rb - r0) * wt + x];
+        rowk[x] = k;
+        rowv[x] = k >= 0 ? (double)v[k] : 0.0;
+      }
+      __syncthreads();
+      for (int i = 0; i < nr; i++) {
+        const double* rv = rowv + i * wt;
+        const int32_t* rk = rowk + i * wt;
+#pragma unroll
+        for (int r = 0; r < kSjPerLane; r++) {
+          const int a = ac[r] & 255, c = ac[r] >> 8;
+          if (lane + kSjThreads * r < tri && rk[a] >= 0 && rk[c] >= 0) G[r] = radd(G[r], rmul(rv[a], rv[c]));
+        }
+#pragma unroll
+        for (int r = 0; r < kSjFPerLane; r++) {
+          const int l = lc[r] & 255, c = lc[r] >> 8;
+          if (lane + kSjThreads * r < nf && rk[w + l] >= 0 && rk[c] >= 0) F[r] = radd(F[r], rmul(rv[w + l], rv[c]));
+        }
+      }
+    }
+    if (e < 0) {  // a pseudo-pair: W = G  (uniform)
+#pragma unroll
+      for (int r = 0; r < kSjPerLane; r++) P[r] = radd(P[r], G[r]);
+      continue;
+    }
+    __syncthreads();  // the F and Y of the pair before are consumed
+#pragma unroll
+    for (int r = 0; r < kSjFPerLane; r++) {
+      if (lane + kSjThreads * r < nf) Fs[lane + kSjThreads * r] = F[r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < kSjFPerLane; r++) {
+      if (lane + kSjThreads * r < nf) {
+        const int l = lc[r] & 255, c = lc[r] >> 8;
+        double s = 0.0;
+        for (int k = 0; k < we; k++) s = radd(s, rmul(Bs[l * we + k], Fs[k * w + c]));
+        Ys[lane + kSjThreads * r] = s;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < kSjPerLane; r++) {
+      if (lane + kSjThreads * r < tri) {
+        const int a = ac[r] & 255, c = ac[r] >> 8;
+        double s = 0.0;
+        for (int l = 0; l < we; l++) s = radd(s, rmul(Fs[l * w + a], Ys[l * w + c]));
+        P[r] = radd(P[r], radd(G[r], -s));
+      }
+    }
+  }
+  const GP<double> out = pickData(pref) + sj.chunkPart[h];
+#pragma unroll
+  for (int r = 0; r < kSjPerLane; r++) {
+    if (lane + kSjThreads * r < tri) out[lane + kSjThreads * r] = P[r];
+  }
+}
+
+// The block kernel, one wave per (kept block, matrix): the chunk partials folded in ascending chunk, d added to the
+// diagonal, cgBlockInvert (it reads the lower triangle only)
+template <typename T>
+__global__ void __launch_bounds__(kCgBuildThreads)
+    schurJacobiBlocks(SchurJacobiDev sj, DataRef<const double> pref, DataRef<const T> dref, DataRef<T> mref,
+                      CgWork work) {
+  __shared__ double A[kCgMaxBlock * kCgMaxBlock];
+  __shared__ double Li[kCgMaxBlock * kCgMaxBlock];
+  const int lane = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int w = sj.keptWidth[b], tri = w * (w + 1) / 2;
+  for (int x = lane; x < w * w; x += kCgBuildThreads) {
+    A[x] = 0.0;
+    Li[x] = 0.0;
+  }
+  __syncthreads();
+  const GP<const double> part = pickData(pref);
+  const int32_t h0 = sj.blockChunk[b], h1 = sj.blockChunk[b + 1];
+  for (int el = lane; el < tri; el += kCgBuildThreads) {
+    const int at = sjElement(el);
+    double s = 0.0;
+    for (int32_t h = h0; h < h1; h++) s = radd(s, part[sj.chunkPart[h] + el]);
+    A[(at & 255) * w + (at >> 8)] = s;
+  }
+  __syncthreads();
+  if (cglsGiven(dref)) {
+    const GP<const T> d = pickData(dref);
+    if (lane < w) A[lane * w + lane] = radd(A[lane * w + lane], (double)d[sj.keptFirst[b] + lane]);
+  }
+  __syncthreads();
+  cgBlockInvert<T>(A, Li, w, lane, pickData(mref) + sj.blockOff[b], work.bad() + b);
 }
 
 }  // namespace hipk

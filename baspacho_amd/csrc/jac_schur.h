@@ -19,6 +19,19 @@
 // The kept params, ascending: param keptParam[b] holds the caller's scalars [keptFirst[b], keptFirst[b] +
 // keptWidth[b]) and the kept indices [keptBlockStart[b], keptBlockStart[b + 1]); keptScalarBlock[c] = b.  The plan of
 // the diagonal blocks of C = J_k^T J_k + D_k over them (jacSchurKeptPlan) is built by the first call that asks.
+//
+// THE BLOCK DIAGONAL OF S (schur_jacobi; built by jac_schur_jacobi.cpp from the lists above,
+// never from the kept item plan).  A pair (e, b) exists when a row of group e has an entry in a column of kept
+// param b; its rows are those rows, ascending.  The free rows that touch b are cut, ascending, into pieces of at
+// most kSchurJacobiChunk rows: pseudo-pairs (pairElim = -1).  The pairs of b -- real ones in ascending e, then the
+// pseudo-pairs -- are [blockPair[b], blockPair[b + 1]) and are cut into chunks of at most kSchurJacobiChunk pairs:
+// chunk h of block chunkBlock[h] holds the pairs [chunkPair[h], chunkPair[h + 1]) and writes the w_b (w_b + 1) / 2
+// lower-triangle elements of its partial sum (element (a, c), a >= c, at a (a + 1) / 2 + c) from chunkPart[h] on;
+// the chunks of b are [blockChunk[b], blockChunk[b + 1]).  Pair p has the pair-rows [pairRow[p], pairRow[p + 1]);
+// pair-row x of it (Jacobian row rowOf[pairRow[p] + x]) has a record of w_b + w_e entry indices from
+// rec[pairRec[p] + x (w_b + w_e)] on: the entry at (row, scalar a of b) for a < w_b, then the entry at (row,
+// scalar l of e), or -1 where the row has none (a pseudo-pair: w_e = 0).  blockOff[b]: the first element of the
+// inverse of block b, w_b^2 each, from keptWidth alone.
 #pragma once
 
 #include <cstdint>
@@ -30,6 +43,25 @@
 namespace BaSpaCho {
 
 constexpr int32_t kSchurMaxElimWidth = 8;  // widest eliminated param
+constexpr int32_t kSchurJacobiChunk = 64;  // pairs of a chunk, rows of a pseudo-pair (part of the interface)
+
+struct JacSchurJacobiPlan {
+  int64_t numBlocks = 0, numReal = 0, numPseudo = 0;
+  std::vector<int64_t> blockOff, chunkPart;
+  std::vector<int32_t> blockPair, blockChunk, chunkPair, chunkBlock, pairElim, pairRow, pairRec, rec;
+  std::vector<int32_t> rowOf;  // (host only: the kernels read the records)
+  int64_t numPairs() const { return (int64_t)pairElim.size(); }
+  int64_t numPairRows() const { return (int64_t)rowOf.size(); }
+  int64_t numChunks() const { return (int64_t)chunkBlock.size(); }
+  int64_t inverseElems() const { return blockOff.empty() ? 0 : blockOff.back(); }
+  int64_t partialElems() const { return chunkPart.empty() ? 0 : chunkPart.back(); }
+  int64_t deviceBytes() const {
+    return (int64_t)((blockOff.size() + chunkPart.size()) * sizeof(int64_t) +
+                     (blockPair.size() + blockChunk.size() + chunkPair.size() + chunkBlock.size() + pairElim.size() +
+                      pairRow.size() + pairRec.size() + rec.size()) *
+                         sizeof(int32_t));
+  }
+};
 
 struct JacSchurMap {
   const JacobianProductMap* product = nullptr;  // not owned; must outlive the map
@@ -42,6 +74,7 @@ struct JacSchurMap {
   std::unique_ptr<JacBlockPlan> elimBlocks;
   std::vector<int32_t> keptParam, keptFirst, keptWidth, keptBlockStart, keptScalarBlock;
   mutable std::unique_ptr<JacBlockPlan> keptBlocks;
+  mutable std::unique_ptr<JacSchurJacobiPlan> schurJacobi;  // built by the first call that asks (jacSchurJacobiPlan)
 
   mutable HipEntryMapDevPtr dev;
 
@@ -63,5 +96,12 @@ std::unique_ptr<JacSchurMap> createJacSchurMap(const JacobianProductMap& product
 // The plan of the diagonal blocks of C over the kept params, cached in the map.  Throws, naming it, for a kept
 // param wider than kCgMaxBlockWidth.
 const JacBlockPlan& jacSchurKeptPlan(const JacSchurMap& map);
+
+// The plan of the block diagonal of S (above) from the map's lists: counting sorts only, nothing of the size of the
+// kept item plan.  Throws, naming it and before anything of the entries' size is allocated, for a kept param wider
+// than kCgMaxBlockWidth and for a table count (pair-rows, record entries) outside [0, 2^31).
+std::unique_ptr<JacSchurJacobiPlan> createJacSchurJacobiPlan(const JacSchurMap& map);
+// ... cached in the map
+const JacSchurJacobiPlan& jacSchurJacobiPlan(const JacSchurMap& map);
 
 }  // namespace BaSpaCho

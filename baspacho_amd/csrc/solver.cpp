@@ -1437,9 +1437,9 @@ void Solver::cgls(const CglsArgs<T>& a, int64_t batch, bool single) const {
 // ---- implicit Schur elimination of the matrix-free least squares --------------
 template <typename T>
 void Solver::jacSchur(const JacSchurArgs<T>& a, int64_t batch, bool single) const {
-  static const char* names[6] = {"schurBuild", "schurMv", "schurReduce", "schurBack", "schurPrecondBuild",
-                                 "schurPrecondApply"};
-  if (a.op < 0 || a.op > SchurPrecondApply) throw std::runtime_error("jacobian schur: unknown operation " + std::to_string(a.op));
+  static const char* names[8] = {"schurBuild",        "schurMv",           "schurReduce",      "schurBack",
+                                 "schurPrecondBuild", "schurPrecondApply", "schurJacobiBuild", "schurJacobiApply"};
+  if (a.op < 0 || a.op > SchurSJacobiApply) throw std::runtime_error("jacobian schur: unknown operation " + std::to_string(a.op));
   const std::string what = names[a.op];
   const auto fail = [&](const std::string& m) { throw std::runtime_error(what + ": " + m); };
   if (a.map == nullptr) fail("the map is NULL");
@@ -1450,16 +1450,21 @@ void Solver::jacSchur(const JacSchurArgs<T>& a, int64_t batch, bool single) cons
   const int64_t m = a.map->m, n = a.map->n, nK = a.map->nK, q = a.q;
   if ((m + n) * q >= (int64_t(1) << 40)) fail("(m + n) q = " + std::to_string((m + n) * q) + " is too large");
   const bool precond = a.op == SchurPrecondBuild || a.op == SchurPrecondApply;
+  const bool sjacobi = a.op == SchurSJacobiBuild || a.op == SchurSJacobiApply;
+  const bool applies = a.op == SchurPrecondApply || a.op == SchurSJacobiApply;
   if (precond && a.kind != CgJacobi && a.kind != CgBlockJacobi) {
     fail("unknown preconditioner kind " + std::to_string(a.kind) + " (1: jacobi, 2: block_jacobi)");
   }
-  if (a.op == SchurBuild || precond) {
+  if (a.op == SchurBuild || precond || sjacobi) {
     if (a.work == nullptr) fail("the workspace pointer is NULL");
     if (reinterpret_cast<uintptr_t>(a.work) % 16 != 0) fail("the workspace is not 16-byte aligned");
-    if (a.op != SchurPrecondApply && a.status == nullptr) fail("the status pointer is NULL");
-    if (a.op == SchurPrecondApply && a.state == nullptr) fail("the state pointer is NULL");
+    if (!applies && a.status == nullptr) fail("the status pointer is NULL");
+    if (applies && a.state == nullptr) fail("the state pointer is NULL");
   }
-  const int64_t pinv = !precond ? 0 : a.kind == CgBlockJacobi ? jacSchurKeptPlan(*a.map).inverseElems() : nK;
+  const int64_t pinv = sjacobi   ? jacSchurJacobiPlan(*a.map).inverseElems()
+                       : !precond ? 0
+                       : a.kind == CgBlockJacobi ? jacSchurKeptPlan(*a.map).inverseElems()
+                                                 : nK;
   struct Slot {
     const char* name;
     const void* const* ptrs;
@@ -1488,6 +1493,13 @@ void Solver::jacSchur(const JacSchurArgs<T>& a, int64_t batch, bool single) cons
     case SchurPrecondBuild:
       slots = {{"values", p(a.values), nnz, a.kind == CgJacobi}, {"colsq", p(a.colsq), n, a.kind != CgJacobi},
                {"d", p(a.damp), n, true}, {"preconditioner", p(a.out), pinv, false}};
+      break;
+    case SchurSJacobiBuild:
+      slots = {{"values", p(a.values), nnz, false},
+               {"inverses", p(a.binv), inv, false},
+               {"d", p(a.damp), n, true},
+               {"partials", p(a.partials), jacSchurJacobiPlan(*a.map).partialElems(), false},
+               {"preconditioner", p(a.out), pinv, false}};
       break;
     default:
       slots = {{"preconditioner", p(a.binv), pinv, false}, {"r", p(a.vec), nK * q, false}, {"z", p(a.out), nK * q, false}};

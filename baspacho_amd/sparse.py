@@ -1254,6 +1254,20 @@ class _SchurPrecond:
               ctypes.c_int64(run.q), *run._args("schur_precond", self.values, run.r, run.z), *run._tail, *run._count)
 
 
+class _SchurJacobiPrecond:
+    """the block diagonal of S itself on the kept params ("schur_jacobi"), built once from the
+    cached inverses of the eliminated blocks and applied by bsp_jac_schur_sjacobi_apply_* inside a cg.CgRun"""
+
+    def __init__(self, smap, v, binv, d):
+        self.smap, self.kind = smap, 2  # (the apply is the block apply, kind 2; cg.CgRun asks for the kind)
+        self.values, self.status = smap.schurJacobiBuild(v, binv, d)
+
+    def cg_apply(self, run):
+        sm = self.smap
+        _call(sm._lib, "bsp_jac_schur_sjacobi_apply_", run.batched, run.sfx, sm.solver._h, sm._h, ctypes.c_int64(run.q),
+              *run._args("schur_jacobi", self.values, run.r, run.z), *run._tail, *run._count)
+
+
 def _schur_run(sch, v, r, c, ab, precond, tol, max_steps, check_every, x0, cache):
     """the reduced iteration of lstsq_cg(eliminate=...) on detached, contiguous operands: (x shaped like c or J^T r,
     the CgRun on the kept scalars).  `cache` keeps what was built from v (the column norms, the damping vector, the
@@ -1313,6 +1327,10 @@ def _schur_run(sch, v, r, c, ab, precond, tol, max_steps, check_every, x0, cache
     if precond in ("jacobi", "block_jacobi"):
         if precond not in cache:
             cache[precond] = _SchurPrecond(smap, precond, v, cache.get("colsq"), d)
+        pc = cache[precond]
+    elif precond == "schur_jacobi":
+        if precond not in cache:
+            cache[precond] = _SchurJacobiPrecond(smap, v, binv, d)
         pc = cache[precond]
     elif precond is not None:
         def pc(s):
@@ -1422,7 +1440,9 @@ def lstsq_cg(jop, jvalues, r, damping=None, precond="block_jacobi", tol=1e-10, m
     |b_k|^2 for the recurrence residual of S x_k = b_k, and a zero b_k stops at once with x_k = 0 (x_e = B^-1 g_e is
     still returned).  Only the kept part of x0 is read.  precond then acts on the kept scalars: None; "jacobi" (1 /
     (colsq_c + d_c), the diagonal of C); "block_jacobi" (the inverses of the diagonal blocks of C = J_k^T J_k + D_k
-    over the kept params, at most 32 scalars each), built and applied on the device; or a callable on tensors shaped
+    over the kept params, at most 32 scalars each); "schur_jacobi" (the inverses of the diagonal
+    blocks of S itself over the kept params, at most 32 scalars each, built once per solve from the inverses of the
+    eliminated blocks; only with eliminate), built and applied on the device; or a callable on tensors shaped
     [nK(, k)] (with the batch's leading B).  info gains "eliminate_status", int64 [2] / [B, 2] = {the caller's scalar of the lowest bad pivot of
     the eliminated blocks or -1, the number of bad blocks (their inverses are zero)}.  Gradients as above, by one
     more reduced solve."""
@@ -1441,17 +1461,21 @@ def lstsq_cg(jop, jvalues, r, damping=None, precond="block_jacobi", tol=1e-10, m
         if not isinstance(x0, torch.Tensor) or tuple(x0.shape) != shape or x0.dtype != r.dtype or x0.device != r.device:
             raise ValueError("%s: x0 must be a %s tensor of shape %s on %s" % (what, r.dtype, shape, r.device))
     if isinstance(precond, str):
-        if precond not in ("jacobi", "block_jacobi"):
-            raise ValueError("%s: precond must be None, 'jacobi', 'block_jacobi' or a callable, got %r" % (what, precond))
-        if precond == "block_jacobi":
+        if precond == "schur_jacobi" and eliminate is None:
+            raise ValueError("%s: precond 'schur_jacobi' is the block diagonal of the reduced system and needs eliminate"
+                             % what)
+        if precond not in ("jacobi", "block_jacobi", "schur_jacobi"):
+            raise ValueError("%s: precond must be None, 'jacobi', 'block_jacobi' or a callable (with eliminate also "
+                             "'schur_jacobi'), got %r" % (what, precond))
+        if precond in ("block_jacobi", "schur_jacobi"):
             sizes = np.asarray(jop.param_sizes).copy()
             if eliminate is not None:  # (only the kept params carry a block of the reduced system's preconditioner)
                 el = eliminate.eliminate if isinstance(eliminate, JacobianSchur) else _host_i64(eliminate)
                 sizes[el[(el >= 0) & (el < len(sizes))]] = 0
             if int(np.max(sizes, initial=0)) > _cg.MAX_BLOCK:
                 p = int(np.argmax(sizes > _cg.MAX_BLOCK))
-                raise ValueError("%s: param %d has %d scalars; 'block_jacobi' takes params of at most %d"
-                                 % (what, p, int(sizes[p]), _cg.MAX_BLOCK))
+                raise ValueError("%s: param %d has %d scalars; '%s' takes params of at most %d"
+                                 % (what, p, int(sizes[p]), precond, _cg.MAX_BLOCK))
     elif precond is not None and not callable(precond):
         raise ValueError("%s: precond must be None, 'jacobi', 'block_jacobi' or a callable, got %r" % (what, precond))
     schur = None
@@ -1471,7 +1495,7 @@ def lstsq_cg(jop, jvalues, r, damping=None, precond="block_jacobi", tol=1e-10, m
     if not return_info:
         return x
     info = {"iterations": iters, "stop": stop, "relres": relres, "state": state}
-    if precond in ("jacobi", "block_jacobi"):
+    if precond in ("jacobi", "block_jacobi", "schur_jacobi"):
         info["precond_status"] = status
     if schur is not None:
         info["eliminate_status"] = estatus

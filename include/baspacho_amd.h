@@ -1153,6 +1153,57 @@ int bsp_jac_schur_precond_apply_f32(bsp_solver* s, const bsp_jac_schur* h, int32
 int bsp_jac_schur_precond_apply_batched_f32(bsp_solver* s, const bsp_jac_schur* h, int32_t kind, int64_t q,
                                             const float* const* dev_minv, const float* const* dev_r, float* const* dev_z,
                                             void* dev_work, int64_t* dev_state, int32_t batch);
+/* EXTENSION without a counterpart in the reference's library: the block diagonal of the reduced matrix S itself as
+   the preconditioner of the implicit Schur iteration ("schur_jacobi").  With e an eliminated
+   param, b a kept one (at most 32 scalars: a wider one is refused by name), S_bb = D_bb + sum over the free rows of
+   J_ib^T J_ib + sum over e of (G_eb - F_eb^T Binv_e F_eb); M^-1 = blockdiag(S_bb^-1), block b row-major at the
+   offsets of the kept blocks of kind 2 above.  The host plan is built by the first call from the map's lists
+   (counting sorts; never the item plan of kind 2): a pair (e, b) exists when a row of group e has an entry in a
+   column of b; the free rows that touch b are cut into pseudo-pairs of at most 64 rows; the pairs of b (real ones
+   in ascending e, then the pseudo-pairs) are cut into chunks of at most 64.
+     sjacobi_info:  {blocks, real pairs, pseudo-pairs, pair rows, chunks, inverse elements, partial elements per
+                    matrix, device bytes}
+     sjacobi_table: part 0: (first pair [blocks + 1], first chunk [blocks + 1], width [blocks]; t3: first inverse
+                    element [blocks + 1]); 1: (first pair [chunks + 1], block [chunks]; t3: first partial element
+                    [chunks + 1]); 2: (eliminated param or -1 [pairs], first pair row [pairs + 1], first record
+                    entry [pairs + 1]); 3: (Jacobian row [pair rows], records: per pair row the entry index at every
+                    scalar of b, then of e, or -1).  An unknown part is refused by number
+     kept_plan_built: 1 when the item plan of kind 2 over the kept params exists on the host, else 0
+     sjacobi_build: dev_minv from the values, dev_binv of bsp_jac_schur_build_* and dev_d [n] (may be NULL), in two
+                    launches: one wave per (chunk, matrix) writes the lower triangle of its partial sum to
+                    dev_partials (partial elements doubles per member), one wave per (block, matrix) folds them,
+                    adds d and inverts; dev_work and dev_status as bsp_jac_schur_precond_build_*; a bad block gets
+                    a zero inverse and is counted
+     sjacobi_apply: bsp_jac_schur_precond_apply_* of kind 2 on dev_minv, without the item plan
+   All block arithmetic is in double for both types, every product rounded before it is added, in the orders of
+   DESIGN.md section 30; no atomics; member b of a batched call is bitwise the single call. */
+int bsp_jac_schur_sjacobi_info(const bsp_jac_schur* h, int64_t out[8]);
+int bsp_jac_schur_sjacobi_table(const bsp_jac_schur* h, int32_t part, int32_t* t0, int32_t* t1, int32_t* t2, int64_t* t3);
+int bsp_jac_schur_kept_plan_built(const bsp_jac_schur* h, int32_t* out);
+int bsp_jac_schur_sjacobi_build_f64(bsp_solver* s, const bsp_jac_schur* h, const double* dev_values, const double* dev_binv,
+                                    const double* dev_d, double* dev_partials, double* dev_minv, void* dev_work,
+                                    int64_t* dev_status);
+int bsp_jac_schur_sjacobi_build_batched_f64(bsp_solver* s, const bsp_jac_schur* h, const double* const* dev_values,
+                                            const double* const* dev_binv, const double* const* dev_d,
+                                            double* const* dev_partials, double* const* dev_minv, void* dev_work,
+                                            int64_t* dev_status, int32_t batch);
+int bsp_jac_schur_sjacobi_apply_f64(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const double* dev_minv,
+                                    const double* dev_r, double* dev_z, void* dev_work, int64_t* dev_state);
+int bsp_jac_schur_sjacobi_apply_batched_f64(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const double* const* dev_minv,
+                                            const double* const* dev_r, double* const* dev_z, void* dev_work,
+                                            int64_t* dev_state, int32_t batch);
+int bsp_jac_schur_sjacobi_build_f32(bsp_solver* s, const bsp_jac_schur* h, const float* dev_values, const float* dev_binv,
+                                    const float* dev_d, double* dev_partials, float* dev_minv, void* dev_work,
+                                    int64_t* dev_status);
+int bsp_jac_schur_sjacobi_build_batched_f32(bsp_solver* s, const bsp_jac_schur* h, const float* const* dev_values,
+                                            const float* const* dev_binv, const float* const* dev_d,
+                                            double* const* dev_partials, float* const* dev_minv, void* dev_work,
+                                            int64_t* dev_status, int32_t batch);
+int bsp_jac_schur_sjacobi_apply_f32(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const float* dev_minv,
+                                    const float* dev_r, float* dev_z, void* dev_work, int64_t* dev_state);
+int bsp_jac_schur_sjacobi_apply_batched_f32(bsp_solver* s, const bsp_jac_schur* h, int64_t q, const float* const* dev_minv,
+                                            const float* const* dev_r, float* const* dev_z, void* dev_work,
+                                            int64_t* dev_state, int32_t batch);
 /* EXTENSION without a counterpart in the reference's library: the pieces of the Lanczos recurrence with its
    scalars on the device, for extreme eigenvalues, a 2-norm condition estimate and
    stochastic Lanczos quadrature (log-determinants) without a factor.  One problem per (matrix, start vector):
